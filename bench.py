@@ -6,6 +6,12 @@ batch 64 per GPU, fp16 storage / fp32 accumulate (BASELINE.json configs[2]; conf
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run (the command above) sets up, warms up, times the K steps and prints the line; everything
+else it can measure runs only with --full.  --dump-outputs DIR writes what the last timed step
+returned (see dump_outputs) so that two builds can be compared output for output: images and weights
+are seeded and the class-bias calibration is an untimed pass over seeded images, so the same
+arguments give the same inputs on every run.
+
 One "step" = one pass of the whole hot path over one batch of B synthetic uint8 BGR images that
 are already resident in HBM (lp_run_batch_device), plus -- at N>1 -- the single RCCL gather of the
 detection records to rank 0.  Weak scaling: every rank processes its own B images per step.
@@ -20,6 +26,7 @@ classifier stage has real work.  No dataset/checkpoint 
 
 The JSON line (rank 0):
   value / ms_per_step -- the K timed steps between barrier + synchronize pairs (the contract)
+With --full (null otherwise):
   windows             -- --windows further windows of K steps each: median and p95 of ms/step
   h2d_inclusive       -- the same loop with the batch starting in PINNED HOST memory: async H2D copy
                          on the handle's stream, then the pipeline (the reference's t_total starts
@@ -69,6 +76,12 @@ def parse_args():
     ap.add_argument("--preset", default="v1", choices=["v1", "v2"])
     ap.add_argument("--precision", default="fp16", choices=["fp16", "fp32"])
     ap.add_argument("--max-det", type=int, default=300)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the extra windows, h2d_inclusive, dropin, "
+                         "roofline (profiled passes) and cpu_baseline.  --windows, --profile-steps, --dump-profile, --no-h2d, "
+                         "--no-dropin, --no-cpu-baseline and --cpu-images shape these and apply only with --full")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one returned to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-images", type=int, default=256, help="images in the CPU baseline sample (all-core run)")
     ap.add_argument("--profile-steps", type=int, default=3)
@@ -88,7 +101,10 @@ def parse_args():
     ap.add_argument("--native-gather", action="store_true",
                     help="move the records with the library's own collective (lp_comm_init + lp_gather = ncclGather bound with dlopen, on "
                          "the handle's stream) instead of torch.distributed.gather; with --rccl-self also at N=1")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_profile and not args.full:
+        ap.error("--dump-profile writes the roofline pass's profile, which runs only with --full")
+    return args
 
 
 def build_models(args, workdir, engine_factory, cal_imgs):
@@ -186,6 +202,27 @@ def cpu_baseline(param, binf, cls_state, imgs_np, n_images):
             "value_4_threads": v4, "sample_4_threads": f"{n4} images, {dt4:.1f} s, torch.set_num_threads(4)"}
 
 
+def dump_outputs(outdir, dets, counts, batch):
+    """What one timed step hands its caller -- the detection records and the per-image counts of the step's handle
+    ([world, ...] after a gather, [1, ...] otherwise) -- as float32 arrays under outdir.  Record slots past an image's
+    kept count hold whatever an earlier step left there, so they are written as zeros."""
+    from litepi.distributed import records_to_numpy
+
+    rec = records_to_numpy(dets).reshape(-1, batch, dets.shape[-2])          # [world, B, max_det]
+    cnt = counts.cpu().numpy().reshape(-1, 3, batch)                          # kept, pre-filter, mean-score bits
+    valid = np.arange(rec.shape[-1]) < cnt[:, 0, :, None]
+    arrays = {"boxes": np.stack([rec[f] for f in ("x1", "y1", "x2", "y2")], axis=-1)}
+    for f in ("det_conf", "det_class", "cls_class", "cls_conf"):
+        arrays[f] = rec[f]
+    arrays = {k: np.where(valid[..., None] if v.ndim == 4 else valid, v, 0) for k, v in arrays.items()}
+    arrays["kept"] = cnt[:, 0]
+    arrays["boxes_pre_area_filter"] = cnt[:, 1]
+    arrays["mean_det_score"] = np.ascontiguousarray(cnt[:, 2]).view(np.float32)
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), v.astype(np.float32))
+
+
 def main():
     args = parse_args()
     run_conf = CONF if args.conf is None else args.conf   # (the calibration always targets CONF)
@@ -272,8 +309,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        last = None
         for _ in range(n):
-            fn()
+            last = fn()
         enq = time.perf_counter() - t0   # host time to enqueue (no GPU wait unless a queue fills)
         torch.cuda.synchronize()
         if world > 1:
@@ -284,7 +322,7 @@ def main():
             t = torch.tensor([el], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
-        return el, enq
+        return el, enq, last
 
     # set-up, untimed: every (handle, input batch) pair twice -- the library runs a launch sequence eagerly the first time
     # it sees it and captures it into a hipGraph the second time; from then on a step is one graph launch
@@ -294,10 +332,12 @@ def main():
     torch.cuda.synchronize()
     for _ in range(args.warmup):
         step()
-    elapsed, host_enqueue_s = timed(step, K)
+    elapsed, host_enqueue_s, last = timed(step, K)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last, B)
     window_ms = [elapsed / K * 1e3]
-    for _ in range(max(0, args.windows)):
-        el, _ = timed(step, K)
+    for _ in range(max(0, args.windows) if args.full else 0):
+        el, _, _ = timed(step, K)
         window_ms.append(el / K * 1e3)
 
     # ---- workload facts (untimed) --------------------------------------------------------------
@@ -318,7 +358,7 @@ def main():
     # stream into 2 staging buffers per handle (the copy of step k+NH overlaps the kernels of steps k..k+NH-1); the
     # payload (records + counts, 0.61 MB) leaves through an async D2H into pinned memory on the handle's stream.
     h2d = None
-    if not args.no_h2d:
+    if args.full and not args.no_h2d:
         host = [torch.from_numpy(imgs_np[j]).pin_memory() for j in range(NB)]
         NS = 2 * NH
         stage = [torch.empty((B, SRC, SRC, 3), dtype=torch.uint8, device=dev) for _ in range(NS)]
@@ -349,7 +389,7 @@ def main():
         lcm_h = NS * NB // int(np.gcd(NS, NB))
         for _ in range(2 * lcm_h + args.warmup):
             hstep()
-        hel, _ = timed(hstep, K)
+        hel, _, _ = timed(hstep, K)
         nbytes = B * SRC * SRC * 3
         h2d = {"value": world * B * K / hel, "unit": "images/sec", "ms_per_step": hel / K * 1e3,
                "upload_gbs": nbytes * K / hel / 1e9,
@@ -359,7 +399,7 @@ def main():
 
     # ---- the drop-in call itself: HybridPipeline.run_batch on B host NumPy images -> per-image result dicts ----------
     dropin = None
-    if rank == 0 and world == 1 and not args.no_dropin:   # a single-GPU measurement (as cpu_baseline): the other ranks do not wait for it
+    if args.full and rank == 0 and world == 1 and not args.no_dropin:   # a single-GPU measurement (as cpu_baseline): the other ranks do not wait for it
         from litepi import HybridPipeline
         cls_path = os.path.join(workdir, "cls.pth")
         torch.save({k: torch.from_numpy(np.asarray(v)) for k, v in cls_state.items()}, cls_path)
@@ -392,7 +432,7 @@ def main():
 
     # ---- roofline of the dominant conv kernel (one template instantiation): profiled passes of the same step ----
     roofline, families = None, {}
-    if rank == 0 and args.profile_steps > 0:
+    if args.full and rank == 0 and args.profile_steps > 0:
         torch.cuda.synchronize()
         torch.cuda.set_stream(streams[0])
         launches = []
@@ -490,7 +530,7 @@ def main():
                 json.dump({"families": families, "launches": launches[-1]}, fh, indent=1)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(param, binf, cls_state, imgs_np[0], args.cpu_images)
 
     if rank == 0:
@@ -535,7 +575,7 @@ def main():
             },
             "windows": {"n": int(len(wm)), "steps_each": K, "ms_per_step_median": float(np.median(wm)),
                         "ms_per_step_p95": float(np.percentile(wm, 95)), "ms_per_step_min": float(wm.min()),
-                        "images_per_sec_median": world * B / (float(np.median(wm)) * 1e-3)},
+                        "images_per_sec_median": world * B / (float(np.median(wm)) * 1e-3)} if args.full else None,
             "h2d_inclusive": h2d,
             "dropin": dropin,
             "roofline": roofline,

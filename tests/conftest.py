@@ -1,6 +1,7 @@
 import os
 import sys
 
+import numpy as np
 import pytest
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -9,21 +10,26 @@ for p in (_ROOT, os.path.join(_ROOT, "yolo-litepi_amd")):
         sys.path.insert(0, p)
 
 GOLDEN = os.path.join(_ROOT, "tests", "golden")
-REF_ROOT = "/root/reference"
 
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    config.addinivalue_line("markers", "reference: needs /root/reference (build container only)")
-
-
-def has_reference():
-    return os.path.isdir(os.path.join(REF_ROOT, "src"))
 
 
 @pytest.fixture(scope="session")
 def golden_dir():
     return GOLDEN
+
+
+@pytest.fixture(scope="session")
+def postprocess_goldens(golden_dir):
+    """The eight ref_postprocess cases as one dict; tools/make_goldens.py splits them over two files so that each stays
+    under the 1 MiB limit for a committed file."""
+    g = {}
+    for name in ("ref_postprocess.npz", "ref_postprocess_2.npz"):
+        with np.load(os.path.join(golden_dir, name)) as z:
+            g.update({k: z[k] for k in z.files})
+    return g
 
 
 @pytest.fixture(scope="session")

@@ -109,11 +109,11 @@ def _check_post(eng, out0, orig, ratio, pad, conf, iou, exp_boxes, exp_scores, e
     assert np.array_equal(d["det_class"], exp_cls.astype(np.int32))
 
 
-def test_postprocess_reference_goldens(eng32, golden_dir):
+def test_postprocess_reference_goldens(eng32, postprocess_goldens):
     """decode-filter + NMS kernels vs outputs of the REFERENCE's own NCNNDetector.postprocess."""
-    g = np.load(os.path.join(golden_dir, "ref_postprocess.npz"))
+    g = postprocess_goldens
     i = 0
-    while f"c{i}_out0" in g.files:
+    while f"c{i}_out0" in g:
         oh, ow, r, p0, p1, conf, iou = g[f"c{i}_geom"]
         _check_post(eng32, g[f"c{i}_out0"], (int(oh), int(ow)), r, (p0, p1), conf, iou, g[f"c{i}_boxes"], g[f"c{i}_scores"],
                     g[f"c{i}_cls"])

@@ -2,8 +2,8 @@
 
 Everything else in the suite runs LSUV-scaled random weights on uniform noise.  Here the detector is the reference's
 exported YOLO-LitePi v1 (``oracle/_ref/yolo_plus_v1.{param,bin}``) and the inputs are scenes built from the 15 traffic-
-sign crops the reference keeps next to its pipeline (``src/vntsr/pipeline/debug_rois``, staged as image DATA under
-``oracle/_ref/debug_rois`` by ``__graft_entry__.build()`` when the reference checkout exists; never committed): every
+sign crops the reference keeps next to its pipeline (``src/vntsr/pipeline/debug_rois``, committed as image DATA in
+``tests/golden/debug_rois.npz``, one array of the file's bytes per crop): every
 crop pasted at native scale onto a smooth background.  The real model finds real signs in them (scores up to 0.8).
 
   * fp32: the post-NMS result lists equal the CPU oracle's box for box (count, order, int boxes, scores <= 1e-3,
@@ -21,7 +21,7 @@ capacity-64 handle (the benchmarked plan: other tile shapes and the whole-C2f la
 The float forward itself stays "parity unpinned" (the reference holds no expected outputs; NCNN / ONNX Runtime are not
 installable here): the checker is oracle/ncnn_ref.py.  The classifier runs seeded synthetic weights (the reference ships
 none)."""
-import glob
+import io
 import os
 
 import numpy as np
@@ -33,7 +33,8 @@ pytestmark = pytest.mark.gpu
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _REF = os.path.join(_ROOT, "oracle", "_ref")
 _REAL = (os.path.join(_REF, "yolo_plus_v1.param"), os.path.join(_REF, "yolo_plus_v1.bin"))
-_CROPS = sorted(glob.glob(os.path.join(_REF, "debug_rois", "*")))
+with np.load(os.path.join(_ROOT, "tests", "golden", "debug_rois.npz")) as _z:
+    _CROPS = [_z[k].tobytes() for k in sorted(_z.files)]
 _HAVE = all(os.path.exists(p) for p in _REAL) and len(_CROPS) >= 10
 
 CONF, IOU, MIN_AREA = 0.10, 0.45, 50   # the first operating point; the reference's own are 0.25 (--benchmark_conf) and 0.001 (--yolo_conf)
@@ -45,7 +46,7 @@ def _scenes(n=16):
     """n BGR scenes 640x640: every crop once per scene at native scale on a 4 x 4 grid with jitter; backgrounds cycle
     through flat grey, a bicubic colour wash and a vertical gradient."""
     from PIL import Image
-    crops = [np.asarray(Image.open(f).convert("RGB"))[..., ::-1].copy() for f in _CROPS]
+    crops = [np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))[..., ::-1].copy() for f in _CROPS]
     out = []
     for s in range(n):
         rng = np.random.default_rng(1000 + s)
@@ -75,7 +76,7 @@ def _cluttered(n=8):
     """n BGR scenes for the conf 0.001 pass: scene 0 is uniform noise (the real model leaves ~350 anchors above 0.001 on
     it, ~240 survive NMS), the others a clean scene with 60 * (1 + s % 3) crops, rescaled by 0.4-1.6, pasted at random."""
     from PIL import Image
-    crops = [np.asarray(Image.open(f).convert("RGB"))[..., ::-1].copy() for f in _CROPS]
+    crops = [np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))[..., ::-1].copy() for f in _CROPS]
     base = _scenes(n)
     rng = np.random.default_rng(7)
     out = []
@@ -136,7 +137,7 @@ def _models(tmp_path):
     return ncnn_ref.load_model(*_REAL), S.build(91, sd), cls_path
 
 
-@pytest.mark.skipif(not _HAVE, reason="reference v1 model / debug_rois crops not staged under oracle/_ref")
+@pytest.mark.skipif(not _HAVE, reason="reference v1 model not staged under oracle/_ref")
 @pytest.mark.parametrize("CONF", [0.10, 0.25], ids=["conf0.10", "conf0.25"])
 def test_real_weights_fp32_post_nms_sets_equal_oracle(tmp_path, CONF):
     from litepi import HybridPipeline
@@ -168,7 +169,7 @@ def test_real_weights_fp32_post_nms_sets_equal_oracle(tmp_path, CONF):
     assert total >= 24 and smax >= 0.5, "the real model must find real signs in these scenes"
 
 
-@pytest.mark.skipif(not _HAVE, reason="reference v1 model / debug_rois crops not staged under oracle/_ref")
+@pytest.mark.skipif(not _HAVE, reason="reference v1 model not staged under oracle/_ref")
 def test_real_weights_fp32_evaluation_pass_conf_0_001(tmp_path):
     """The reference's evaluation pass (--yolo_conf 0.001, e2e.py:975-992) on cluttered scenes: hundreds of candidates per
     image through the sort + greedy sweep on the real score distribution.
@@ -216,7 +217,7 @@ def test_real_weights_fp32_evaluation_pass_conf_0_001(tmp_path):
     assert n_flip <= max(2, n_boxes // 100)
 
 
-@pytest.mark.skipif(not _HAVE, reason="reference v1 model / debug_rois crops not staged under oracle/_ref")
+@pytest.mark.skipif(not _HAVE, reason="reference v1 model not staged under oracle/_ref")
 @pytest.mark.parametrize("CONF,cap", [(0.10, 16), (0.25, 16), (0.25, 64)], ids=["conf0.10-cap16", "conf0.25-cap16", "conf0.25-cap64"])
 def test_real_weights_fp16_no_stability_filter(tmp_path, CONF, cap):
     """cap 64 = the benchmarked plan (handle built for 64 images: the whole-C2f launches and the capacity-64 tile shapes) on
@@ -279,7 +280,7 @@ def test_real_weights_fp16_no_stability_filter(tmp_path, CONF, cap):
     assert err_s <= 2 * BAND and n_oracle - n_band >= 24 and n_swap <= max(1, (n_oracle - n_band) // 50)
 
 
-@pytest.mark.skipif(not _HAVE, reason="reference v1 model / debug_rois crops not staged under oracle/_ref")
+@pytest.mark.skipif(not _HAVE, reason="reference v1 model not staged under oracle/_ref")
 def test_real_weights_fp16_evaluation_pass_conf_0_001(tmp_path):
     """fp16 at the reference's evaluation threshold (--yolo_conf 0.001) on the cluttered scenes.  Below ~0.02 the fp16 score
     error (0.004 measured) is as large as the scores, so box-for-box equality of the junk is not a meaningful ask; what

@@ -3,18 +3,24 @@
 * post-processing restatement == outputs of the REFERENCE's own functions (goldens made by
   tools/make_goldens.py in the build container), bit for bit;
 * PIL-resize restatement == Pillow itself;
-* NCNN reader extracts exactly the tensors the ONNX export of the same checkpoint holds
-  (needs /root/reference: skipped on the GPU box);
+* NCNN reader extracts exactly the tensors the ONNX export of the same checkpoint holds;
 * the oracle's forward on the real v1 weights is stable against committed checksums.
+
+The reference's v1 checkpoint (NCNN + ONNX, 4 MB each) is too large to commit: __graft_entry__.build() stages it under
+oracle/_ref/ where the reference checkout exists, and the tests that read it skip where it was not staged.
 """
+import json
 import os
 
 import numpy as np
 import pytest
 
-from conftest import REF_ROOT, has_reference
-
-needs_ref = pytest.mark.skipif(not has_reference(), reason="/root/reference not present")
+_REF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref")
+V1_PARAM, V1_BIN, V1_ONNX = (os.path.join(_REF, "yolo_plus_v1." + ext) for ext in ("param", "bin", "onnx"))
+needs_v1 = pytest.mark.skipif(not (os.path.exists(V1_PARAM) and os.path.exists(V1_BIN)),
+                              reason="the reference's v1 model is not staged under oracle/_ref (build() without the reference)")
+needs_v1_onnx = pytest.mark.skipif(not (os.path.exists(V1_PARAM) and os.path.exists(V1_BIN) and os.path.exists(V1_ONNX)),
+                                   reason="the reference's v1 model + ONNX export are not staged under oracle/_ref")
 
 
 def test_nms_matches_reference_goldens(golden_dir):
@@ -27,11 +33,11 @@ def test_nms_matches_reference_goldens(golden_dir):
         assert np.array_equal(keep, g[k + "_keep"]), k
 
 
-def test_postprocess_matches_reference_goldens(golden_dir):
+def test_postprocess_matches_reference_goldens(postprocess_goldens):
     from oracle import postprocess_ref as P
-    g = np.load(os.path.join(golden_dir, "ref_postprocess.npz"))
+    g = postprocess_goldens
     i = 0
-    while f"c{i}_out0" in g.files:
+    while f"c{i}_out0" in g:
         oh, ow, r, p0, p1, conf, iou = g[f"c{i}_geom"]
         b, s, c = P.postprocess(g[f"c{i}_out0"], (int(oh), int(ow)), r, (p0, p1), conf, iou)
         eb = g[f"c{i}_boxes"]
@@ -78,28 +84,26 @@ def test_pil_resize_restatement_equals_pillow():
         assert np.array_equal(R.resize_bilinear_u8(im, 64, 64), ref), (h, w)
 
 
-@needs_ref
-def test_pil_resize_on_reference_debug_rois():
-    import glob
+def test_pil_resize_on_reference_debug_rois(golden_dir):
+    """The 15 sign crops the reference keeps next to its pipeline (src/vntsr/pipeline/debug_rois), committed as the
+    files' bytes."""
+    import io
     from PIL import Image
     from oracle import pil_resize_ref as R
-    files = sorted(glob.glob(os.path.join(REF_ROOT, "src/vntsr/pipeline/debug_rois/*")))
+    with np.load(os.path.join(golden_dir, "debug_rois.npz")) as z:
+        files = {k: z[k].tobytes() for k in z.files}
     assert len(files) == 15
-    for f in files:
-        im = np.array(Image.open(f).convert("RGB"))
+    for name, data in sorted(files.items()):
+        im = np.array(Image.open(io.BytesIO(data)).convert("RGB"))
         ref = np.array(Image.fromarray(im).resize((64, 64), Image.BILINEAR))
-        assert np.array_equal(R.resize_bilinear_u8(im, 64, 64), ref), f
+        assert np.array_equal(R.resize_bilinear_u8(im, 64, 64), ref), name
 
 
-V1_DIR = os.path.join(REF_ROOT, "src/vntsr/convert/model/yolo_plus")
-
-
-@needs_ref
+@needs_v1_onnx
 def test_ncnn_reader_matches_onnx_initializers():
     from oracle import ncnn_ref, onnx_init
-    layers = ncnn_ref.load_model(os.path.join(V1_DIR, "yolo_plus_ncnn_model/model.ncnn.param"),
-                                 os.path.join(V1_DIR, "yolo_plus_ncnn_model/model.ncnn.bin"))
-    init = onnx_init.read_initializers(os.path.join(V1_DIR, "yolo_plus.onnx"))
+    layers = ncnn_ref.load_model(V1_PARAM, V1_BIN)
+    init = onnx_init.read_initializers(V1_ONNX)
     pool = [v for v in init.values() if v.dtype == np.float32]
     convs = ncnn_ref.conv_layers(layers)
     assert len(convs) == 64
@@ -110,14 +114,13 @@ def test_ncnn_reader_matches_onnx_initializers():
     assert ncnn_ref.conv_macs(layers) == 1418713600  # 1.4187 GMAC
 
 
-@needs_ref
+@needs_v1
 def test_oracle_forward_on_real_weights_is_stable(golden_dir):
     """Seeded rand(1,3,640,640) as in the reference's model_ncnn.py:6-7.  The reference holds no
     expected output (parity unpinned); this pins the oracle against silent drift only."""
     import torch
     from oracle import ncnn_ref
-    layers = ncnn_ref.load_model(os.path.join(V1_DIR, "yolo_plus_ncnn_model/model.ncnn.param"),
-                                 os.path.join(V1_DIR, "yolo_plus_ncnn_model/model.ncnn.bin"))
+    layers = ncnn_ref.load_model(V1_PARAM, V1_BIN)
     g = np.load(os.path.join(golden_dir, "oracle_v1_out0_checksums.npz"))
     for seed in (0, 1):
         torch.manual_seed(seed)
@@ -127,7 +130,7 @@ def test_oracle_forward_on_real_weights_is_stable(golden_dir):
         assert np.allclose(out.mean(axis=1), g[f"s{seed}_mean"], rtol=1e-4)
 
 
-@needs_ref
+@needs_v1_onnx
 def test_two_reference_graph_descriptions_agree_on_real_weights():
     """The reference's ONNX export of the v1 checkpoint (yolo_plus.onnx, opset 12), walked node by node with the ONNX
     specification's operator semantics (oracle/onnx_ref.py), against oracle/ncnn_ref.py's reading of the NCNN graph of the
@@ -136,9 +139,8 @@ def test_two_reference_graph_descriptions_agree_on_real_weights():
     the reference's engines -- forward parity stays UNPINNED."""
     import torch
     from oracle import ncnn_ref, onnx_ref
-    layers = ncnn_ref.load_model(os.path.join(V1_DIR, "yolo_plus_ncnn_model/model.ncnn.param"),
-                                 os.path.join(V1_DIR, "yolo_plus_ncnn_model/model.ncnn.bin"))
-    nodes, init, g_in, g_out = onnx_ref.read_graph(os.path.join(V1_DIR, "yolo_plus.onnx"))
+    layers = ncnn_ref.load_model(V1_PARAM, V1_BIN)
+    nodes, init, g_in, g_out = onnx_ref.read_graph(V1_ONNX)
     assert len(nodes) == 238 and sum(n.op == "Conv" for n in nodes) == 64 and g_in == ["images"] and g_out == ["output0"]
     yy, xx = np.mgrid[0:640, 0:640].astype(np.float32)
     structured = np.stack([0.5 + 0.5 * np.sin(xx / 37.0 + c) * np.cos(yy / 53.0 - c) for c in range(3)])[None]
@@ -166,12 +168,13 @@ def test_synthetic_models_have_the_reference_architecture(synth_models):
     assert out.shape == (1, 5, 8400) and torch.isfinite(out).all()
 
 
-@needs_ref
-def test_exporter_layer_sequence_equals_reference_graph(synth_models):
-    ref = [l.split()[:4] for l in open(os.path.join(V1_DIR, "yolo_plus_ncnn_model/model.ncnn.param")).read().splitlines()[2:]]
+def test_exporter_layer_sequence_equals_reference_graph(synth_models, golden_dir):
+    """Layer type, #inputs, #outputs of every line of the reference's v1 NCNN graph (recorded from its model.ncnn.param)."""
+    with open(os.path.join(golden_dir, "ref_v1_layer_sequence.json")) as fh:
+        ref = json.load(fh)
     mine = [l.split()[:4] for l in open(synth_models["v1"][0]).read().splitlines()[2:]]
     assert len(ref) == len(mine) == 206
-    assert all(a[0] == b[0] and a[2:] == b[2:] for a, b in zip(ref, mine))  # layer type, #in, #out
+    assert all(a == [b[0], int(b[2]), int(b[3])] for a, b in zip(ref, mine))  # layer type, #in, #out
 
 
 def test_shufflenet_oracle_shapes_and_param_count():

@@ -3,7 +3,8 @@
 # printing the pipelined rate, one-step-in-flight rate and the eager times of the kernels matching $KERNELS (default: all > 15 us)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$R"
-cat > /tmp/_line.py <<'PY'
+LINE=$(mktemp)
+cat > "$LINE" <<'PY'
 import json, os, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d["roofline"]
 pat = os.environ.get("KERNELS", "")
@@ -12,5 +13,5 @@ print("%-28s %7.0f img/s  median %.4f ms  dropin %s  eager step %.3f ms  %s" % (
       ("%.0f" % d["dropin"]["value"]) if d.get("dropin") else "-", r["profiled_step_ms"], ks), flush=True)
 PY
 for v in "$@"; do
-  ( [ -n "$v" ] && export $v; python bench.py --steps 40 --warmup 8 --no-cpu-baseline ${DROPIN:---no-dropin} --no-h2d --windows 5 2>/dev/null | python /tmp/_line.py "$v" )
+  ( [ -n "$v" ] && export $v; python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline ${DROPIN:---no-dropin} --no-h2d --windows 5 2>/dev/null | python "$LINE" "$v" )
 done

@@ -6,15 +6,15 @@ TAG=${1:-v2ab}
 shift || true
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$R"
-mkdir -p gpurun_out
-LITEPI_C2F_STORE_ALL=1 timeout -k 10 240 python tools/c2f_check.py v2 3 > gpurun_out/${TAG}_check.txt 2>&1 || { echo "c2f_check failed"; tail -20 gpurun_out/${TAG}_check.txt; exit 1; }
-tail -4 gpurun_out/${TAG}_check.txt
+OUT=${OUT:-$(mktemp -d)}; mkdir -p "$OUT"
+LITEPI_C2F_STORE_ALL=1 timeout -k 10 240 python tools/c2f_check.py v2 3 > $OUT/${TAG}_check.txt 2>&1 || { echo "c2f_check failed"; tail -20 $OUT/${TAG}_check.txt; exit 1; }
+tail -4 $OUT/${TAG}_check.txt
 bench() {  # name, env...
   local name=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --preset v2 --steps 30 --warmup 5 --no-cpu-baseline --no-dropin --no-h2d --windows 4 --dump-profile gpurun_out/${TAG}_${name}_launches.json > gpurun_out/${TAG}_${name}.json 2> gpurun_out/${TAG}_${name}.err || { echo "bench $name failed"; tail -5 gpurun_out/${TAG}_${name}.err; return 1; }
+  env "$@" timeout -k 10 300 python bench.py --full --preset v2 --steps 30 --warmup 5 --no-cpu-baseline --no-dropin --no-h2d --windows 4 --dump-profile $OUT/${TAG}_${name}_launches.json > $OUT/${TAG}_${name}.json 2> $OUT/${TAG}_${name}.err || { echo "bench $name failed"; tail -5 $OUT/${TAG}_${name}.err; return 1; }
   python - <<PY
 import json
-d = json.loads(open("gpurun_out/${TAG}_${name}.json").read().strip().splitlines()[-1])
+d = json.loads(open("$OUT/${TAG}_${name}.json").read().strip().splitlines()[-1])
 r = d["roofline"]
 print("${name}: %.0f img/s, %.4f ms/step, median %.4f; %d launches, eager %.3f ms" % (d["value"], d["ms_per_step"], d["windows"]["ms_per_step_median"], r["profiled_launches"], r["profiled_step_ms"]))
 PY
@@ -26,6 +26,6 @@ for s in "$@"; do
 done
 python - <<PY
 import json
-for l in json.load(open("gpurun_out/${TAG}_default_launches.json"))["launches"]:
+for l in json.load(open("$OUT/${TAG}_default_launches.json"))["launches"]:
     print("   %-40s %-36s %7.1f us" % (l["name"], l["layer"], l["ms"] * 1e3))
 PY
