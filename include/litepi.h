@@ -164,6 +164,44 @@ int lp_comm_init(lp_handle* h, const void* id, int rank, int world);
 int lp_gather(lp_handle* h, const void* dev_send, size_t bytes, void* dev_recv, int root);
 int lp_comm_destroy(lp_handle* h);
 
+/* ---- tiled inference of large frames (additive to ABI 310) ------------------------- */
+/* A frame larger than det_input S is also seen at native resolution: it is cut into overlapping S x S crops, every crop is
+ * a view of the detector batch, and the candidates of all views of a frame go through ONE per-class greedy NMS in frame
+ * coordinates (e2e.py:89-119; ties: higher (view, anchor) first).  Per axis of length L: step = S - overlap, n = 1 if
+ * L <= S else 1 + ceil((L - S) / step), x_k = min(k * step, max(L - S, 0)).  A frame that needs more than one crop gets,
+ * with full_frame = 1, the letterboxed whole frame as view 0 (the view lp_run_batch makes), then the crops row-major; a
+ * frame that fits one tile has that single letterboxed view and gives lp_run_batch's result.  Crop pixels beyond the frame
+ * edge are 114.  The frame NMS keeps two LDS flag bits per candidate slot, so one frame may span at most ~614 k slots
+ * (views x anchors: 73 views of 8400 anchors); a larger frame is LP_ERR_ARG before anything is enqueued.  DESIGN.md §6b. */
+typedef struct lp_tiling {
+  int overlap;       /* pixels shared by neighbouring crops: 0 <= overlap < det_input */
+  int full_frame;    /* 0 or 1: the letterboxed whole frame is view 0 of a frame that needs more than one crop */
+  int reserved[6];   /* zero */
+} lp_tiling;
+/* The views of an H x W frame (pure host; no handle, no device): *n_views their number; views (may be NULL: count only)
+ * receives cap x 4 ints {x, y, w, h} of each view's source window in the frame, {x0, y0, S, S} for a crop and
+ * {-1, -1, W, H} for the letterboxed whole frame.  cap < *n_views with views != NULL is LP_ERR_ARG. */
+int lp_tile_grid(int det_input, const lp_tiling* tiling, int H, int W, int* n_views, int* views, int cap);
+/* lp_run_batch over B host frames, each seen through its views: the sum of the frames' views must not exceed max_batch
+ * (LP_ERR_ARG otherwise: nothing is truncated).  dets [B*max_det], counts / num_det / det_conf_avg [B] per frame. */
+int lp_run_tiled(lp_handle* h, const uint8_t* const* imgs, const int* heights, const int* widths, int B, const lp_tiling* tiling,
+                 float conf, float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing);
+/* lp_run_batch_device over B equally sized frames resident in HBM (uint8 BGR [B,H,W,3]): dev_dets [B*max_det],
+ * dev_counts [3*B] int32 per frame (kept, pre-filter, float bits of the mean pre-filter score).  Asynchronous. */
+int lp_run_tiled_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, const lp_tiling* tiling,
+                        float conf, float iou, int min_area, void* dev_dets, void* dev_counts);
+/* The frame NMS alone (tests): n host candidates of one orig_h x orig_w frame, xyxy in frame pixels, each tagged with its
+ * view (0 .. n_views-1) and anchor (0 .. 16383, unique within a view); dets / rects / count / num_det as lp_test_nms_boxes.
+ * max_det <= 0: keep every survivor. */
+int lp_test_nms_views(lp_handle* h, const float* boxes, const float* scores, const int* classes, const int* views,
+                      const int* anchors, int n, int n_views, int orig_h, int orig_w, float iou, int min_area, int max_det,
+                      lp_det* dets, int* rects, int* count, int* num_det);
+
+/* The view gather alone (tests): the views of one host H x W frame, uploaded byte_offset (0..63) bytes past an aligned
+ * address, in the frame's view order -> out [n_views, S, S, 3] uint8 BGR (may be NULL: *n_views only). */
+int lp_test_tile_views(lp_handle* h, const uint8_t* img, int H, int W, const lp_tiling* tiling, int byte_offset, uint8_t* out,
+                       int cap, int* n_views);
+
 /* ---- classifier alone ------------------------------------------------------------ */
 /* replaces PyTorchClassifier.predict_batch (e2e.py:378-396) for R host BGR crops of
  * individual sizes: ids [R], probs [R*num_classes] (softmax). */

@@ -2,6 +2,7 @@
 // point replaces).  Owns the device, the stream, all activation/result buffers and the two
 // model plans; every pipeline stage runs on the GPU -- there is no CPU fallback anywhere.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <atomic>
@@ -165,6 +166,9 @@ struct lp_handle {
   DevBuf d_src, d_lb, d_geom, d_cand, d_cand_count, d_sorted, d_dets, d_counts, d_rects, d_out0;
   DevBuf d_roi_base, d_roi_total, d_roi_img, d_roi_slot, d_roi_rgb, d_probs, d_ids, d_conf;
   std::vector<ImgGeom> geom_cache;
+  // tiled inference (lp_run_tiled*): frame geometry, frame table + view slots, per-view counts; allocated on first use
+  DevBuf d_fgeom, d_ftab, d_vcnt;
+  std::vector<char> tile_cache;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // lp_run_batch: start, after the ROI resize, after detect + NMS, end
   int last_roi_count = 0;
   // chunked lp_run_batch (uniform frames, >= 32 of them): uploads on copy_stream, five events per chunk, ROI totals per chunk
@@ -470,11 +474,13 @@ void enqueue_nms(lp_handle* h, int B, float iou, int min_area, lp_det* dets, int
 // PIL resize + ShuffleNetV2 + softmax over the ROI list; scatters (cls, conf) into dets when given
 // stage: 0 = both halves, 1 = only the ROI crop + resize (the device's share of the reference's ROI loop, e2e.py:460-475),
 // 2 = only the classifier (lp_run_batch times the two separately: PipelineMetrics.t_roi_extract / t_classification)
-void enqueue_classify(lp_handle* h, const uint8_t* src, int B, lp_det* dets, float* probs, int* ids, float* conf, Profiler* prof, int stage = 0) {
+// geom: the images' geometry (default d_geom; the tiled path passes its frame geometry)
+void enqueue_classify(lp_handle* h, const uint8_t* src, int B, lp_det* dets, float* probs, int* ids, float* conf, Profiler* prof, int stage = 0,
+                      const ImgGeom* geom = nullptr) {
   RoiTable tab = h->roi_table();
   if (stage != 2 && !skip_stage(h, "roi", prof)) {
     RoiResizeArgs r;
-    r.src = src; r.geom = h->d_geom.as<ImgGeom>(); r.rects = h->d_rects.as<int>(); r.tab = tab;
+    r.src = src; r.geom = geom ? geom : h->d_geom.as<ImgGeom>(); r.rects = h->d_rects.as<int>(); r.tab = tab;
     r.out = h->d_roi_rgb.as<uint8_t>(); r.max_det = h->cfg.max_det; r.S = h->cfg.cls_input; r.linear = h->cfg.numerics;
     if (prof) prof->begin(h->stream);
     launch_roi_resize(r, std::min(h->max_rois, B * h->cfg.max_det), h->stream);
@@ -708,9 +714,332 @@ void run_batch_chunked(lp_handle* h, const uint8_t* const* imgs, int H, int W, i
            want_rois, h->max_rois, want_rois - h->max_rois);
 }
 
+// ---- tiled inference (lp_run_tiled*) ---------------------------------------------------------------------------------------
+// one axis of the view grid (include/litepi.h lp_tile_grid)
+int tile_axis(int L, int S, int overlap, std::vector<int>& xs) {
+  xs.clear();
+  if (L <= S) { xs.push_back(0); return 1; }
+  const int step = S - overlap, n = 1 + (L - S + step - 1) / step;
+  for (int k = 0; k < n; ++k) xs.push_back(std::min(k * step, L - S));
+  return n;
+}
+
+void check_tiling(const lp_tiling* t, int S) {
+  LP_CHECK(t, LP_ERR_ARG, "null tiling");
+  LP_CHECK(t->overlap >= 0 && t->overlap < S, LP_ERR_ARG, "tiling overlap %d outside 0..%d", t->overlap, S - 1);
+  LP_CHECK(t->full_frame == 0 || t->full_frame == 1, LP_ERR_ARG, "tiling full_frame must be 0 or 1 (got %d)", t->full_frame);
+}
+
+// views of one H x W frame as {x, y, w, h} windows; x = -1 marks the letterboxed whole frame
+std::vector<std::array<int, 4>> tile_views(int S, const lp_tiling& t, int H, int W) {
+  std::vector<int> xs, ys;
+  const int nx = tile_axis(W, S, t.overlap, xs), ny = tile_axis(H, S, t.overlap, ys);
+  std::vector<std::array<int, 4>> v;
+  if (nx * ny == 1 || t.full_frame) v.push_back({-1, -1, W, H});
+  if (nx * ny > 1)
+    for (int y : ys)
+      for (int x : xs) v.push_back({x, y, S, S});
+  return v;
+}
+
+// The call's view layout.  Batch slots: first the letterboxed views (one launch of the letterbox kernel, so they are exactly
+// lp_run_batch's input), then the crops.  frames[f] / vslot list each frame's slots in the frame's view order.
+struct TileLayout {
+  std::vector<ImgGeom> vgeom;     // [V] by slot
+  std::vector<TileFrame> frames;  // [F]
+  std::vector<int> vslot;         // [V] frame-major
+  int L = 0, V = 0, max_views = 0;
+};
+
+TileLayout tile_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const lp_tiling& t) {
+  const int S = h->cfg.det_input, F = (int)fg.size();
+  std::vector<std::vector<std::array<int, 4>>> per(F);
+  TileLayout lay;
+  int ncrop = 0;
+  for (int f = 0; f < F; ++f) {
+    per[f] = tile_views(S, t, fg[f].h, fg[f].w);
+    for (auto& w : per[f]) (w[0] < 0 ? lay.L : ncrop) += 1;
+    lay.max_views = std::max(lay.max_views, (int)per[f].size());
+  }
+  lay.V = lay.L + ncrop;
+  LP_CHECK(lay.V <= h->cfg.max_batch, LP_ERR_ARG, "%d frames need %d views, more than max_batch = %d: split the call", F, lay.V,
+           h->cfg.max_batch);
+  if (h->det && h->det->loaded()) {   // the frame NMS's LDS flag masks: checked here, before anything is enqueued
+    const int A = h->det->num_anchors();
+    LP_CHECK(lay.max_views <= 1024 && frame_nms_lds_bytes(lay.max_views * A) <= FRAME_NMS_LDS_CAP, LP_ERR_ARG,
+             "a frame of %d views x %d anchors exceeds the frame NMS capacity (%d candidate slots per frame): raise the overlap "
+             "or lower the frame size", lay.max_views, A, (int)((FRAME_NMS_LDS_CAP - 16) / 8 * 32));
+  }
+  lay.vgeom.resize(lay.V);
+  int next_lb = 0, next_crop = lay.L;
+  for (int f = 0; f < F; ++f) {
+    lay.frames.push_back(TileFrame{(int)lay.vslot.size(), (int)per[f].size()});
+    for (auto& w : per[f]) {
+      const int slot = w[0] < 0 ? next_lb++ : next_crop++;
+      ImgGeom g = fg[f];   // letterbox geometry of the whole frame (make_geom)
+      if (w[0] >= 0) {
+        g.new_w = S; g.new_h = S; g.top = -w[1]; g.left = -w[0];
+        g.ratio = 1.0f; g.pad_w = -(float)w[0]; g.pad_h = -(float)w[1];
+      }
+      lay.vgeom[slot] = g;
+      lay.vslot.push_back(slot);
+    }
+  }
+  return lay;
+}
+
+// upload the frame geometry + frame table + view slots when they changed; a change invalidates captured graphs (geom_ver)
+void upload_tiles(lp_handle* h, const std::vector<ImgGeom>& fg, const TileLayout& lay) {
+  const int B = h->cfg.max_batch;
+  if (!h->d_fgeom.p) {
+    h->d_fgeom.alloc((size_t)B * sizeof(ImgGeom));
+    h->d_ftab.alloc((size_t)B * (sizeof(TileFrame) + sizeof(int)));
+    h->d_vcnt.alloc((size_t)B * 4);
+  }
+  h->upload_geom(lay.vgeom);
+  const size_t nf = fg.size();
+  std::vector<char> blob(nf * sizeof(ImgGeom) + nf * sizeof(TileFrame) + lay.vslot.size() * sizeof(int));
+  memcpy(blob.data(), fg.data(), nf * sizeof(ImgGeom));
+  memcpy(blob.data() + nf * sizeof(ImgGeom), lay.frames.data(), nf * sizeof(TileFrame));
+  memcpy(blob.data() + nf * (sizeof(ImgGeom) + sizeof(TileFrame)), lay.vslot.data(), lay.vslot.size() * sizeof(int));
+  if (blob == h->tile_cache) return;
+  LP_HIP(hipMemcpyAsync(h->d_fgeom.p, fg.data(), nf * sizeof(ImgGeom), hipMemcpyHostToDevice, h->stream));
+  LP_HIP(hipMemcpyAsync(h->d_ftab.p, lay.frames.data(), nf * sizeof(TileFrame), hipMemcpyHostToDevice, h->stream));
+  LP_HIP(hipMemcpyAsync(h->d_ftab.as<char>() + (size_t)B * sizeof(TileFrame), lay.vslot.data(), lay.vslot.size() * sizeof(int),
+                        hipMemcpyHostToDevice, h->stream));
+  LP_HIP(hipStreamSynchronize(h->stream));
+  h->tile_cache.swap(blob);
+  ++h->geom_ver;
+}
+
+// view gather + detector on the views + frame NMS (+ the ROI list when with_rois)
+void enqueue_tiled_detect(lp_handle* h, const uint8_t* src, const TileLayout& lay, int F, float conf, float iou, int min_area, lp_det* dets,
+                          int* counts, bool with_rois, Profiler* prof) {
+  const int S = h->cfg.det_input;
+  if (lay.L > 0) {
+    if (prof) prof->begin(h->stream);
+    launch_letterbox(src, h->d_geom.as<ImgGeom>(), h->d_lb.as<uint8_t>(), lay.L, S, h->stream, lay.vgeom.data());
+    if (prof) {
+      double bytes = (double)lay.L * S * S * 3;
+      for (int i = 0; i < lay.L; ++i) bytes += (double)lay.vgeom[i].h * lay.vgeom[i].w * 3;
+      prof->end(h->stream, "letterbox_u8", "letterbox", 0.0, bytes);
+    }
+  }
+  if (lay.V > lay.L) {
+    if (prof) prof->begin(h->stream);
+    launch_crop_views(src, h->d_geom.as<ImgGeom>(), h->d_lb.as<uint8_t>(), lay.L, lay.V - lay.L, S, h->stream);
+    if (prof) prof->end(h->stream, "tile_crop_u8", "tile_crop", 0.0, 2.0 * (lay.V - lay.L) * S * S * 3);
+  }
+  h->det->forward(h->d_lb.as<uint8_t>(), lay.V, h->d_geom.as<ImgGeom>(), conf, nullptr, h->d_cand.as<Cand>(), h->d_cand_count.as<int>(),
+                  h->stream, prof);
+  FrameNmsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.cand = h->d_cand.as<Cand>(); a.cand_count = h->d_cand_count.as<int>(); a.vcnt = h->d_vcnt.as<int>(); a.sorted = h->d_sorted.as<Cand>();
+  a.frames = h->d_ftab.as<TileFrame>();
+  a.vslot = reinterpret_cast<const int*>(h->d_ftab.as<char>() + (size_t)h->cfg.max_batch * sizeof(TileFrame));
+  a.dets = dets; a.counts = counts; a.rects = h->d_rects.as<int>(); a.fgeom = h->d_fgeom.as<ImgGeom>();
+  a.A = h->det->num_anchors(); a.max_det = h->cfg.max_det; a.nc = h->det->num_classes(); a.iou = iou; a.min_area = min_area;
+  if (with_rois) a.tab = h->roi_table();
+  a.max_rois = h->max_rois;
+  a.roi_rule = h->cfg.numerics;
+  if (prof) prof->begin(h->stream);
+  launch_view_sort(a, lay.V, h->stream);
+  if (prof) prof->end(h->stream, "view_sort", "nms", 0.0, 0.0);
+  if (prof) prof->begin(h->stream);
+  launch_frame_nms(a, F, lay.max_views, h->stream);
+  if (prof) prof->end(h->stream, "frame_nms", "nms", 0.0, 0.0);
+}
+
 }  // namespace
 
 extern "C" {
+
+int lp_tile_grid(int det_input, const lp_tiling* tiling, int H, int W, int* n_views, int* views, int cap) {
+  LP_API_BEGIN
+  LP_CHECK(n_views && det_input >= 1 && H > 0 && W > 0, LP_ERR_ARG, "bad argument (det_input %d, frame %dx%d)", det_input, H, W);
+  check_tiling(tiling, det_input);
+  const auto v = tile_views(det_input, *tiling, H, W);
+  *n_views = (int)v.size();
+  if (views) {
+    LP_CHECK(cap >= (int)v.size(), LP_ERR_ARG, "%zu views, room for %d", v.size(), cap);
+    for (size_t i = 0; i < v.size(); ++i)
+      for (int k = 0; k < 4; ++k) views[4 * i + k] = v[i][k];
+  }
+  LP_API_END
+}
+
+int lp_run_tiled(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, const lp_tiling* tiling, float conf,
+                 float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing) {
+  LP_API_BEGIN
+  LP_CHECK(h && imgs && hs && ws && dets && counts, LP_ERR_ARG, "null argument");
+  LP_CHECK(h->det && h->det->loaded(), LP_ERR_STATE, "detector not loaded");
+  LP_CHECK(h->cls && h->cls->loaded(), LP_ERR_STATE, "classifier not loaded");
+  LP_CHECK(B >= 1 && B <= h->cfg.max_batch, LP_ERR_ARG, "batch %d outside 1..%d", B, h->cfg.max_batch);
+  LP_CHECK(min_area >= 0, LP_ERR_ARG, "min_area must be >= 0");
+  check_tiling(tiling, h->cfg.det_input);
+  for (int i = 0; i < B; ++i) LP_CHECK(hs[i] > 0 && ws[i] > 0, LP_ERR_ARG, "frame %d is empty", i);
+  LP_HIP(hipSetDevice(h->cfg.device));
+  std::vector<ImgGeom> fg(B);
+  for (int i = 0; i < B; ++i) fg[i] = make_geom(hs[i], ws[i], h->cfg.det_input, 0);
+  (void)tile_layout(h, fg, *tiling);   // view count checked before anything is uploaded
+  fg = upload_images(h, imgs, hs, ws, B);
+  const TileLayout lay = tile_layout(h, fg, *tiling);
+  upload_tiles(h, fg, lay);
+  Profiler* prof = begin_profile(h);
+  const ImgGeom* fgeom = h->d_fgeom.as<ImgGeom>();
+  LP_HIP(hipEventRecord(h->ev[0], h->stream));
+  lp_handle::GraphKey k1{9, B, h->geom_ver, min_area, h->d_src.p, h->d_dets.p, h->d_counts.p, conf, iou};
+  run_or_capture(h, k1, prof == nullptr, [&]() {
+    enqueue_tiled_detect(h, h->d_src.as<uint8_t>(), lay, B, conf, iou, min_area, h->d_dets.as<lp_det>(), h->d_counts.as<int>(), true, prof);
+  });
+  LP_HIP(hipEventRecord(h->ev[2], h->stream));
+  lp_handle::GraphKey k2{10, B, h->geom_ver, min_area, h->d_src.p, h->d_dets.p, h->d_counts.p, conf, iou};
+  run_or_capture(h, k2, prof == nullptr, [&]() {
+    enqueue_classify(h, h->d_src.as<uint8_t>(), B, h->d_dets.as<lp_det>(), nullptr, nullptr, nullptr, prof, 1, fgeom);
+  });
+  LP_HIP(hipEventRecord(h->ev[1], h->stream));
+  lp_handle::GraphKey k3{11, B, h->geom_ver, min_area, h->d_src.p, h->d_dets.p, h->d_counts.p, conf, iou};
+  run_or_capture(h, k3, prof == nullptr, [&]() {
+    enqueue_classify(h, h->d_src.as<uint8_t>(), B, h->d_dets.as<lp_det>(), nullptr, nullptr, nullptr, prof, 2, fgeom);
+  });
+  LP_HIP(hipEventRecord(h->ev[3], h->stream));
+  LP_HIP(hipMemcpyAsync(dets, h->d_dets.p, (size_t)B * h->cfg.max_det * sizeof(lp_det), hipMemcpyDeviceToHost, h->stream));
+  std::vector<int> cnt(3 * B);
+  LP_HIP(hipMemcpyAsync(cnt.data(), h->d_counts.p, (size_t)3 * B * 4, hipMemcpyDeviceToHost, h->stream));
+  int R[2] = {0, 0};
+  LP_HIP(hipMemcpyAsync(R, h->d_roi_total.p, 8, hipMemcpyDeviceToHost, h->stream));
+  LP_HIP(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < B; ++i) {
+    counts[i] = cnt[i];
+    if (num_det) num_det[i] = cnt[B + i];
+    if (det_conf_avg) memcpy(&det_conf_avg[i], &cnt[2 * B + i], 4);
+  }
+  h->last_roi_count = R[0];
+  if (timing) {   // booked as lp_run_batch books them: view gather, detector and frame NMS under detection
+    (void)hipEventElapsedTime(&timing->t_detection, h->ev[0], h->ev[2]);
+    (void)hipEventElapsedTime(&timing->t_roi_extract, h->ev[2], h->ev[1]);
+    (void)hipEventElapsedTime(&timing->t_classification, h->ev[1], h->ev[3]);
+    (void)hipEventElapsedTime(&timing->t_total, h->ev[0], h->ev[3]);
+  }
+  if (prof) { prof->collect(R[0]); prof->enabled = false; }
+  LP_CHECK(R[1] <= h->max_rois, LP_ERR_STATE, "%d ROIs in this batch exceed max_rois = %d: %d detections were left unclassified", R[1],
+           h->max_rois, R[1] - h->max_rois);
+  LP_API_END
+}
+
+int lp_run_tiled_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, const lp_tiling* tiling, float conf, float iou,
+                        int min_area, void* dev_dets, void* dev_counts) {
+  LP_API_BEGIN
+  LP_CHECK(h && dev_imgs && dev_dets && dev_counts, LP_ERR_ARG, "null argument");
+  LP_CHECK(h->det && h->det->loaded(), LP_ERR_STATE, "detector not loaded");
+  LP_CHECK(B >= 1 && B <= h->cfg.max_batch && H > 0 && W > 0, LP_ERR_ARG, "bad batch/shape");
+  check_tiling(tiling, h->cfg.det_input);
+  LP_HIP(hipSetDevice(h->cfg.device));
+  std::vector<ImgGeom> fg(B);
+  for (int i = 0; i < B; ++i) fg[i] = make_geom(H, W, h->cfg.det_input, (long)i * H * W * 3);
+  const TileLayout lay = tile_layout(h, fg, *tiling);
+  upload_tiles(h, fg, lay);
+  Profiler* prof = begin_profile(h);
+  const uint8_t* src = static_cast<const uint8_t*>(dev_imgs);
+  const bool classify = h->cls && h->cls->loaded();
+  lp_handle::GraphKey key{12, B, h->geom_ver, min_area, dev_imgs, dev_dets, dev_counts, conf, iou};
+  run_or_capture(h, key, prof == nullptr, [&]() {
+    enqueue_tiled_detect(h, src, lay, B, conf, iou, classify ? min_area : -1, static_cast<lp_det*>(dev_dets), static_cast<int*>(dev_counts),
+                         classify, prof);
+    if (classify) enqueue_classify(h, src, B, static_cast<lp_det*>(dev_dets), nullptr, nullptr, nullptr, prof, 0, h->d_fgeom.as<ImgGeom>());
+  });
+  if (prof) prof->enabled = false;  // records are collected by lp_profile_read after the caller synchronises
+  LP_API_END
+}
+
+int lp_test_nms_views(lp_handle* h, const float* boxes, const float* scores, const int* classes, const int* views, const int* anchors,
+                      int n, int n_views, int orig_h, int orig_w, float iou, int min_area, int max_det, lp_det* dets, int* rects,
+                      int* count, int* num_det) {
+  LP_API_BEGIN
+  LP_CHECK(h && dets && count && n >= 0 && n_views >= 1 && n_views <= 1024 && orig_h > 0 && orig_w > 0, LP_ERR_ARG, "bad argument");
+  LP_CHECK(n == 0 || (boxes && scores && views && anchors), LP_ERR_ARG, "null argument");
+  LP_HIP(hipSetDevice(h->cfg.device));
+  int A = 1, nc = 1;
+  for (int i = 0; i < n; ++i) {
+    LP_CHECK(views[i] >= 0 && views[i] < n_views && anchors[i] >= 0 && anchors[i] < 16384, LP_ERR_ARG,
+             "candidate %d: view %d / anchor %d out of range", i, views[i], anchors[i]);
+    A = std::max(A, anchors[i] + 1);
+    nc = std::max(nc, (classes ? classes[i] : 0) + 1);
+  }
+  std::vector<Cand> cand((size_t)n_views * A);
+  std::vector<int> cnt(n_views, 0);
+  std::vector<char> seen((size_t)n_views * A, 0);
+  for (int i = 0; i < n; ++i) {
+    const int v = views[i];
+    LP_CHECK(!seen[(size_t)v * A + anchors[i]], LP_ERR_ARG, "candidate %d: anchor %d appears twice in view %d", i, anchors[i], v);
+    seen[(size_t)v * A + anchors[i]] = 1;
+    Cand c;
+    c.x1 = boxes[4 * i]; c.y1 = boxes[4 * i + 1]; c.x2 = boxes[4 * i + 2]; c.y2 = boxes[4 * i + 3];
+    c.score = scores[i]; c.cls = classes ? classes[i] : 0; c.anchor = anchors[i]; c.pad = 0;
+    cand[(size_t)v * A + cnt[v]++] = c;
+  }
+  ImgGeom g;
+  memset(&g, 0, sizeof(g));
+  g.h = orig_h; g.w = orig_w; g.ratio = 1.f;
+  TileFrame fr{0, n_views};
+  std::vector<int> vslot(n_views);
+  for (int v = 0; v < n_views; ++v) vslot[v] = v;
+  if (max_det <= 0 || max_det > n_views * A) max_det = n_views * A;  // the reference keeps every survivor
+  DevBuf d_geom, d_cand, d_sorted, d_cnt, d_vcnt, d_fr, d_vslot, d_dets, d_counts, d_rects;
+  d_geom.alloc(sizeof(g));
+  LP_HIP(hipMemcpy(d_geom.p, &g, sizeof(g), hipMemcpyHostToDevice));
+  d_cand.alloc(cand.size() * sizeof(Cand)); d_sorted.alloc(cand.size() * sizeof(Cand));
+  LP_HIP(hipMemcpy(d_cand.p, cand.data(), cand.size() * sizeof(Cand), hipMemcpyHostToDevice));
+  d_cnt.alloc((size_t)n_views * 4); d_vcnt.alloc((size_t)n_views * 4);
+  LP_HIP(hipMemcpy(d_cnt.p, cnt.data(), (size_t)n_views * 4, hipMemcpyHostToDevice));
+  d_fr.alloc(sizeof(fr)); LP_HIP(hipMemcpy(d_fr.p, &fr, sizeof(fr), hipMemcpyHostToDevice));
+  d_vslot.alloc((size_t)n_views * 4); LP_HIP(hipMemcpy(d_vslot.p, vslot.data(), (size_t)n_views * 4, hipMemcpyHostToDevice));
+  d_dets.alloc((size_t)max_det * sizeof(lp_det)); d_counts.alloc(16); d_rects.alloc((size_t)max_det * 16);
+  FrameNmsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.cand = d_cand.as<Cand>(); a.cand_count = d_cnt.as<int>(); a.vcnt = d_vcnt.as<int>(); a.sorted = d_sorted.as<Cand>();
+  a.frames = d_fr.as<TileFrame>(); a.vslot = d_vslot.as<int>();
+  a.dets = d_dets.as<lp_det>(); a.counts = d_counts.as<int>(); a.rects = d_rects.as<int>(); a.fgeom = d_geom.as<ImgGeom>();
+  a.A = A; a.max_det = max_det; a.nc = nc; a.iou = iou; a.min_area = min_area; a.roi_rule = h->cfg.numerics;
+  launch_view_sort(a, n_views, h->stream);
+  launch_frame_nms(a, 1, n_views, h->stream);
+  LP_HIP(hipStreamSynchronize(h->stream));
+  int c3[3];
+  LP_HIP(hipMemcpy(c3, d_counts.p, 12, hipMemcpyDeviceToHost));
+  *count = c3[0];
+  if (num_det) *num_det = c3[1];
+  LP_HIP(hipMemcpy(dets, d_dets.p, (size_t)(*count) * sizeof(lp_det), hipMemcpyDeviceToHost));
+  if (rects) LP_HIP(hipMemcpy(rects, d_rects.p, (size_t)(*count) * 16, hipMemcpyDeviceToHost));
+  LP_API_END
+}
+
+int lp_test_tile_views(lp_handle* h, const uint8_t* img, int H, int W, const lp_tiling* tiling, int byte_offset, uint8_t* out, int cap,
+                       int* n_views) {
+  LP_API_BEGIN
+  LP_CHECK(h && img && n_views && H > 0 && W > 0 && byte_offset >= 0 && byte_offset < 64, LP_ERR_ARG, "bad argument");
+  check_tiling(tiling, h->cfg.det_input);
+  LP_HIP(hipSetDevice(h->cfg.device));
+  const int S = h->cfg.det_input;
+  const size_t bytes = (size_t)H * W * 3;
+  std::vector<ImgGeom> fg(1, make_geom(H, W, S, byte_offset));
+  const TileLayout lay = tile_layout(h, fg, *tiling);
+  *n_views = lay.V;
+  LP_CHECK(!out || cap >= lay.V, LP_ERR_ARG, "%d views, room for %d", lay.V, cap);
+  if (!out) return LP_OK;
+  DevBuf d_src, d_geom, d_out;
+  d_src.alloc(bytes + 64);
+  LP_HIP(hipMemcpy(d_src.as<uint8_t>() + byte_offset, img, bytes, hipMemcpyHostToDevice));
+  d_geom.alloc((size_t)lay.V * sizeof(ImgGeom));
+  LP_HIP(hipMemcpy(d_geom.p, lay.vgeom.data(), (size_t)lay.V * sizeof(ImgGeom), hipMemcpyHostToDevice));
+  d_out.alloc((size_t)lay.V * S * S * 3);
+  if (lay.L > 0) launch_letterbox(d_src.as<uint8_t>(), d_geom.as<ImgGeom>(), d_out.as<uint8_t>(), lay.L, S, h->stream, lay.vgeom.data());
+  launch_crop_views(d_src.as<uint8_t>(), d_geom.as<ImgGeom>(), d_out.as<uint8_t>(), lay.L, lay.V - lay.L, S, h->stream);
+  LP_HIP(hipStreamSynchronize(h->stream));
+  const size_t vb = (size_t)S * S * 3;
+  for (int k = 0; k < lay.V; ++k)   // in the frame's view order
+    LP_HIP(hipMemcpy(out + (size_t)k * vb, d_out.as<uint8_t>() + (size_t)lay.vslot[k] * vb, vb, hipMemcpyDeviceToHost));
+  LP_API_END
+}
 
 int lp_detect_raw(lp_handle* h, const uint8_t* bgr, int B, float* out0) {
   LP_API_BEGIN

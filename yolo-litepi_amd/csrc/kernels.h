@@ -92,6 +92,39 @@ void launch_nms(const NmsArgs& a, int N, hipStream_t st);
 size_t nms_lds_bytes(int A);
 
 
+// ---- tile_kernels.hip (tiled inference of large frames) -------------------------------------
+// crop views slot0 .. slot0+nslots-1 of the view batch [V,S,S,3]: frame[-top : -top+S, -left : -left+S], 114 off the frame
+void launch_crop_views(const uint8_t* src, const ImgGeom* geom, uint8_t* dst, int slot0, int nslots, int S, hipStream_t st);
+
+struct TileFrame { int view0, nviews; };   // frame f's views: vslot[view0 .. view0 + nviews), in the frame's view order
+struct FrameNmsArgs {
+  Cand* cand;             // [V][A] per-view candidates; after the view sort, frame f's merged list at cand + view0 * A
+  int* cand_count;        // [V]   (reset to 0 by the view sort for the next call)
+  int* vcnt;              // [V]   candidates per view slot (written by the view sort)
+  Cand* sorted;           // [V][A] per-view sorted candidates
+  const TileFrame* frames;  // [F]
+  const int* vslot;       // [V]   view batch slot of the frames' views, frame-major
+  lp_det* dets;           // [F][max_det]
+  int* counts;            // [3F] as NmsArgs::counts, per frame
+  int* rects;             // [F][max_det][4]
+  const ImgGeom* fgeom;   // [F] frame geometry (size, src_off)
+  int A, max_det, nc;
+  float iou;
+  int min_area;
+  RoiTable tab;
+  int max_rois;
+  int roi_rule;
+  int no_small;
+};
+// per-view sort (one workgroup per view slot, V slots), then the merged per-class greedy NMS of every frame (one workgroup
+// per frame; max_views bounds the views of one frame: it sizes the LDS flag masks)
+void launch_view_sort(const FrameNmsArgs& a, int V, hipStream_t st);
+void launch_frame_nms(const FrameNmsArgs& a, int F, int max_views, hipStream_t st);
+// LDS of the frame NMS's two flag masks (removed, kept) for a union of at most max_union candidates; FRAME_NMS_LDS_CAP bounds it,
+// i.e. one frame may hold at most about 614 k candidate slots (views x anchors): 73 views of 8400 anchors
+size_t frame_nms_lds_bytes(int max_union);
+#define FRAME_NMS_LDS_CAP (150 * 1024)
+
 // PIL Image.resize((S,S), BILINEAR) of every ROI + BGR->RGB (e2e.py:385-389): uint8 RGB [R,S,S,3]
 struct RoiResizeArgs {
   const uint8_t* src;       // source images

@@ -37,6 +37,10 @@ class LpKernelTime(C.Structure):
                 ("bytes", C.c_double)]
 
 
+class LpTiling(C.Structure):
+    _fields_ = [("overlap", C.c_int), ("full_frame", C.c_int), ("reserved", C.c_int * 6)]
+
+
 # numpy view of lp_det records
 DET_DTYPE = [("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("det_conf", "<f4"), ("det_class", "<i4"),
              ("cls_class", "<i4"), ("cls_conf", "<f4")]
@@ -47,6 +51,7 @@ SYMBOLS = [
     "lp_set_stream", "lp_synchronize", "lp_profile_next", "lp_profile_read", "lp_detector_info", "lp_debug_blob",
     "lp_test_conv", "lp_test_postprocess", "lp_test_nms_boxes", "lp_test_roi_resize", "lp_test_letterbox", "lp_roi_overflow",
     "lp_comm_unique_id", "lp_comm_init", "lp_gather", "lp_comm_destroy",
+    "lp_tile_grid", "lp_run_tiled", "lp_run_tiled_device", "lp_test_nms_views", "lp_test_tile_views",
 ]
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
 
@@ -97,6 +102,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_comm_init.argtypes = [vp, vp, C.c_int, C.c_int]
     lib.lp_gather.argtypes = [vp, vp, C.c_size_t, vp, C.c_int]
     lib.lp_comm_destroy.argtypes = [vp]
+    tp = C.POINTER(LpTiling)
+    lib.lp_tile_grid.argtypes = [C.c_int, tp, C.c_int, C.c_int, ip, ip, C.c_int]
+    lib.lp_run_tiled.argtypes = [vp, u8pp, ip, ip, C.c_int, tp, C.c_float, C.c_float, C.c_int, vp, ip, ip, fp, C.POINTER(LpTiming)]
+    lib.lp_run_tiled_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, tp, C.c_float, C.c_float, C.c_int, vp, vp]
+    lib.lp_test_nms_views.argtypes = [vp, fp, fp, ip, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp,
+                                      ip, ip, ip]
+    lib.lp_test_tile_views.argtypes = [vp, vp, C.c_int, C.c_int, tp, C.c_int, vp, C.c_int, ip]
     for s in SYMBOLS:
         if s not in ("lp_last_error", "lp_default_config", "lp_destroy"):
             getattr(lib, s).restype = C.c_int

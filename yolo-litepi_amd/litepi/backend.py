@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _ffi
-from ._ffi import DET_DTYPE, LpConfig, LpKernelTime, LpTiming, check
+from ._ffi import DET_DTYPE, LpConfig, LpKernelTime, LpTiming, LpTiling, check
 
 _PREC = {"fp32": _ffi.LP_FP32, "fp16": _ffi.LP_FP16, "float32": _ffi.LP_FP32, "float16": _ffi.LP_FP16, "half": _ffi.LP_FP16}
 
@@ -30,6 +30,24 @@ def _as_bgr(img: np.ndarray) -> np.ndarray:
 
 
 CLS_ARCHS = ("resnet18", "efficientnet", "mobilenetv2", "shufflenetv2")   # the --clf_arch choices of e2e.py:1021
+
+
+def _tiling(overlap: int, full_frame: bool) -> LpTiling:
+    t = LpTiling()
+    t.overlap, t.full_frame = int(overlap), int(bool(full_frame))
+    return t
+
+
+def tile_grid(det_input: int, H: int, W: int, overlap: int = 128, full_frame: bool = True) -> List[Tuple[int, int, int, int]]:
+    """The views of an H x W frame in tiled mode (lp_tile_grid: host only, no GPU needed): (x, y, w, h) source windows,
+    (x0, y0, S, S) for a crop and (-1, -1, W, H) for the letterboxed whole frame, in the library's view order."""
+    lib = _ffi.load_library()
+    t = _tiling(overlap, full_frame)
+    n = C.c_int()
+    check(lib, lib.lp_tile_grid(int(det_input), C.byref(t), int(H), int(W), C.byref(n), None, 0))
+    buf = (C.c_int * (4 * n.value))()
+    check(lib, lib.lp_tile_grid(int(det_input), C.byref(t), int(H), int(W), C.byref(n), buf, n.value))
+    return [tuple(buf[4 * i:4 * i + 4]) for i in range(n.value)]
 
 
 class Engine:
@@ -139,6 +157,31 @@ class Engine:
         check(self.lib, self.lib.lp_run_batch_device(self._h, C.c_void_p(dev_imgs), B, H, W, conf, iou, int(min_area),
                                                      C.c_void_p(dev_dets), C.c_void_p(dev_counts)))
 
+    # ---- tiled inference of large frames ------------------------------------------------------
+    def tile_grid(self, H: int, W: int, overlap: int = 128, full_frame: bool = True) -> List[Tuple[int, int, int, int]]:
+        return tile_grid(self.cfg.det_input, H, W, overlap, full_frame)
+
+    def run_tiled(self, images: Sequence[np.ndarray], conf: float, iou: float, min_area: int, overlap: int = 128,
+                  full_frame: bool = True):
+        """run_batch with every frame seen through its views (lp_run_tiled): same return values, per frame."""
+        imgs, ptrs, hs, ws = self._img_args(images)
+        B = len(imgs)
+        dets = np.zeros((B, self.cfg.max_det), dtype=DET_DTYPE)
+        counts, num_det = (C.c_int * B)(), (C.c_int * B)()
+        conf_avg = (C.c_float * B)()
+        timing = LpTiming()
+        t = _tiling(overlap, full_frame)
+        check(self.lib, self.lib.lp_run_tiled(self._h, ptrs, hs, ws, B, C.byref(t), conf, iou, int(min_area), dets.ctypes.data, counts,
+                                              num_det, conf_avg, C.byref(timing)))
+        self.last_det_conf_avg = np.array(conf_avg[:], dtype=np.float32)
+        return dets, np.array(counts[:], dtype=np.int64), np.array(num_det[:], dtype=np.int64), timing
+
+    def run_tiled_device(self, dev_imgs: int, B: int, H: int, W: int, conf: float, iou: float, min_area: int,
+                         dev_dets: int, dev_counts: int, overlap: int = 128, full_frame: bool = True) -> None:
+        t = _tiling(overlap, full_frame)
+        check(self.lib, self.lib.lp_run_tiled_device(self._h, C.c_void_p(dev_imgs), B, H, W, C.byref(t), conf, iou, int(min_area),
+                                                     C.c_void_p(dev_dets), C.c_void_p(dev_counts)))
+
     def roi_overflow(self) -> Tuple[int, int]:
         """(classified, kept) of the last run_batch_device call (synchronises): kept > classified means max_rois was too small."""
         a, b = C.c_int(), C.c_int()
@@ -227,6 +270,37 @@ class Engine:
                                                    int(orig_shape[1]), float(iou), int(min_area), int(max_det), dets.ctypes.data,
                                                    rects.ctypes.data_as(ip), C.byref(cnt), C.byref(num)))
         return dets[:cnt.value], rects[:cnt.value], num.value
+
+    def test_nms_views(self, boxes, scores, classes, views, anchors, n_views, orig_shape, iou, min_area: int = -1, max_det: int = 0):
+        """The frame NMS of tiled inference on host candidates tagged (view, anchor) -> (records, int rects [n,4], pre-filter count)."""
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
+        b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 4)
+        sc = np.ascontiguousarray(scores, np.float32)
+        n = len(b)
+        cl = None if classes is None else np.ascontiguousarray(classes, np.int32)
+        vw, an = np.ascontiguousarray(views, np.int32), np.ascontiguousarray(anchors, np.int32)
+        dets = np.zeros(max(n, 1), dtype=DET_DTYPE)
+        rects = np.zeros((max(n, 1), 4), dtype=np.int32)
+        cnt, num = C.c_int(), C.c_int()
+        check(self.lib, self.lib.lp_test_nms_views(self._h, b.ctypes.data_as(fp), sc.ctypes.data_as(fp),
+                                                   None if cl is None else cl.ctypes.data_as(ip), vw.ctypes.data_as(ip),
+                                                   an.ctypes.data_as(ip), n, int(n_views), int(orig_shape[0]), int(orig_shape[1]),
+                                                   float(iou), int(min_area), int(max_det), dets.ctypes.data, rects.ctypes.data_as(ip),
+                                                   C.byref(cnt), C.byref(num)))
+        return dets[:cnt.value], rects[:cnt.value], num.value
+
+    def test_tile_views(self, img: np.ndarray, overlap: int = 128, full_frame: bool = True, byte_offset: int = 0) -> np.ndarray:
+        """The gathered views of one frame (uploaded byte_offset bytes past an aligned address) -> uint8 [n_views, S, S, 3]."""
+        a = _as_bgr(img)
+        S = self.cfg.det_input
+        t = _tiling(overlap, full_frame)
+        n = C.c_int()
+        check(self.lib, self.lib.lp_test_tile_views(self._h, a.ctypes.data, a.shape[0], a.shape[1], C.byref(t), int(byte_offset), None,
+                                                    0, C.byref(n)))
+        out = np.empty((n.value, S, S, 3), np.uint8)
+        check(self.lib, self.lib.lp_test_tile_views(self._h, a.ctypes.data, a.shape[0], a.shape[1], C.byref(t), int(byte_offset),
+                                                    out.ctypes.data, n.value, C.byref(n)))
+        return out
 
     def test_roi_resize(self, rois: Sequence[np.ndarray]) -> np.ndarray:
         imgs, ptrs, hs, ws = self._img_args(rois)
@@ -533,7 +607,12 @@ class HybridPipeline:
     def __init__(self, detector_param: str, detector_bin: str, classifier_path: str, classifier_arch: str,
                  num_classes: int = 58, det_input_size: int = 640, cls_input_size: int = 64, use_gpu_detector: bool = False,
                  detector_threads: int = 4, classifier_device: str = "cpu", batch_size: int = 8, *, precision: str = "fp16",
-                 max_batch: int = 1, max_det: int = 300, device: int = 0, max_rois: int = 0, numerics: str = "e2e"):
+                 max_batch: int = 1, max_det: int = 300, device: int = 0, max_rois: int = 0, numerics: str = "e2e",
+                 tile_overlap: Optional[int] = None, tile_full_frame: bool = True):
+        """tile_overlap: None = every frame is letterboxed to det_input (the reference's behaviour); an int = tiled inference
+        (lp_run_tiled): frames larger than det_input are also seen as native-resolution crops overlapping by that many pixels,
+        with the letterboxed whole frame as an extra view when tile_full_frame."""
+        self.tile_overlap, self.tile_full_frame = tile_overlap, bool(tile_full_frame)
         print("\n" + "=" * 70)
         print("HYBRID PIPELINE: HIP Detector + HIP Classifier (MI355X)")
         print("=" * 70)
@@ -601,11 +680,43 @@ class HybridPipeline:
         self.engine.last_det_conf_avg = np.concatenate([p[4] for p in parts])
         return dets, counts, num_det, timing
 
+    def _run_tiled(self, images, conf, iou, min_area):
+        """run_batch's engine call in tiled mode: consecutive frames go to one lp_run_tiled call while their views fit
+        max_batch and their ROIs fit max_rois (at most max_det per frame); results concatenated in frame order, stage times
+        summed over the calls."""
+        cfg = self.engine.cfg
+        S, cap = cfg.det_input, cfg.max_batch
+        max_frames = max(1, (cfg.max_rois if cfg.max_rois > 0 else cfg.max_batch * cfg.max_det) // cfg.max_det)
+        groups, cur, used = [], [], 0
+        for img in images:
+            nv = len(tile_grid(S, img.shape[0], img.shape[1], self.tile_overlap, self.tile_full_frame))
+            if nv > cap:
+                raise ValueError(f"a {img.shape[1]}x{img.shape[0]} frame needs {nv} views, more than max_batch = {cap}")
+            if cur and (used + nv > cap or len(cur) >= max_frames):
+                groups.append(cur)
+                cur, used = [], 0
+            cur.append(img)
+            used += nv
+        if cur:
+            groups.append(cur)
+        parts = []
+        for g in groups:
+            d, c, nd, t = self.engine.run_tiled(g, conf, iou, min_area, self.tile_overlap, self.tile_full_frame)
+            parts.append((d, c, nd, t, self.engine.last_det_conf_avg))
+        timing = LpTiming()
+        for f in ("t_detection", "t_roi_extract", "t_classification", "t_total"):
+            setattr(timing, f, sum(getattr(p[3], f) for p in parts))
+        self.engine.last_det_conf_avg = np.concatenate([p[4] for p in parts])
+        return (np.concatenate([p[0] for p in parts], 0), np.concatenate([p[1] for p in parts]),
+                np.concatenate([p[2] for p in parts]), timing)
+
     def run_batch(self, images: Sequence[np.ndarray], conf_threshold: float = 0.5, iou_threshold: float = 0.45,
                   min_area: int = 100) -> List[Tuple[List[Dict], PipelineMetrics]]:
         t0 = time.perf_counter()
         try:
-            if self._lanes and len(images) >= 32 and len(images) <= self._lane_cap * len(self._lanes):
+            if self.tile_overlap is not None:
+                dets, counts, num_det, timing = self._run_tiled(list(images), conf_threshold, iou_threshold, min_area)
+            elif self._lanes and len(images) >= 32 and len(images) <= self._lane_cap * len(self._lanes):
                 dets, counts, num_det, timing = self._run_lanes(list(images), conf_threshold, iou_threshold, min_area)
             else:
                 dets, counts, num_det, timing = self.engine.run_batch(images, conf_threshold, iou_threshold, min_area)

@@ -72,6 +72,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="warm-up passes on a random 640x640 frame before the timed loop (e2e_optimize.py:552-570 warmup_pipeline); "
                         "default 10 under --numerics e2e_optimize as there, 0 otherwise (e2e.py has none).  Here they also take "
                         "the hipGraph capture of the benchmark pass out of the first timed image")
+    p.add_argument("--tile_overlap", type=int, default=None,
+                   help="tiled inference (off when absent): frames larger than det_input are also seen as native-resolution "
+                        "det_input crops overlapping by this many pixels, merged by one NMS per frame; the handle holds "
+                        "batch_images x the views of a 2048x2048 frame")
+    p.add_argument("--tile_full_frame", type=int, choices=[0, 1], default=1,
+                   help="tiled inference: the letterboxed whole frame is an extra view of every frame that needs crops")
     p.add_argument("--no_jit", action="store_true", help="accepted and ignored: there is no TorchScript on this path (e2e_optimize.py:884)")
     return p
 
@@ -301,13 +307,19 @@ def run_evaluation(args) -> Dict:
     say(f"\n{'=' * 60}\nMODEL COMBINATION: {combo}\n{'=' * 60}")
     nb = max(1, args.batch_images)
     max_det = args.max_det if args.max_det > 0 else num_anchors(args.det_input_size)
+    max_batch, max_rois = nb, args.max_rois
+    if args.tile_overlap is not None:   # room for the views of batch_images TT100K-size frames; ROIs are still per frame
+        from .backend import tile_grid
+        max_batch = nb * len(tile_grid(args.det_input_size, 2048, 2048, args.tile_overlap, bool(args.tile_full_frame)))
+        max_rois = max_rois if max_rois > 0 else nb * max_det
     import contextlib
     import io
     with contextlib.redirect_stdout(io.StringIO()) if rank != 0 else contextlib.nullcontext():   # one banner, rank 0's
         pipeline = HybridPipeline(args.detector_param, args.detector_bin, args.classifier, args.clf_arch, num_classes,
                                   args.det_input_size, args.cls_input_size, False, args.detector_threads, args.device,
-                                  args.batch_size, precision=args.precision, max_batch=nb, max_det=max_det,
-                                  device=args.hip_device, max_rois=args.max_rois, numerics=args.numerics)
+                                  args.batch_size, precision=args.precision, max_batch=max_batch, max_det=max_det,
+                                  device=args.hip_device, max_rois=max_rois, numerics=args.numerics,
+                                  tile_overlap=args.tile_overlap, tile_full_frame=bool(args.tile_full_frame))
     out_dir = Path(args.output) / combo
     out_dir.mkdir(parents=True, exist_ok=True)
 
