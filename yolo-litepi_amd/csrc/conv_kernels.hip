@@ -216,6 +216,11 @@ __device__ __forceinline__ void store_lane_at(T* o, const T* r, int chbase, int 
 #pragma unroll
     for (int t = 0; t + 1 < NT; t += 2) {
       if (chbase + t * 4 < Cout) {
+        // Cout may end between the pair's two quads (NT = 3: chbase = 12g + 48ns, e.g. EfficientNet-B0's 40-channel
+        // projections): then only the first quad is this pixel's -- 8 channels would reach into the next pixel's first
+        // 4 when the output pitch is Cout, racing with that pixel's own store.  With NT even every pair starts at a
+        // multiple of 8 channels and Cout is one too: the pair is always whole.
+        const bool pair = NT % 2 == 0 || chbase + t * 4 + 4 < Cout;
         half8 q;
         const floatx4 y0 = act4<T, ACT>(v[t], bias[t]), y1 = act4<T, ACT>(v[t + 1], bias[t + 1]);
 #pragma unroll
@@ -228,13 +233,24 @@ __device__ __forceinline__ void store_lane_at(T* o, const T* r, int chbase, int 
           if (rq) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) { rr[i] = rq[t][i]; rr[4 + i] = rq[t + 1][i]; }
-          } else {
+          } else if (pair) {
             rr = *reinterpret_cast<const half8*>(r + t * 4);
+          } else {
+            const half4 r4 = *reinterpret_cast<const half4*>(r + t * 4);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { rr[i] = r4[i]; rr[4 + i] = (half_t)0.f; }
           }
 #pragma unroll
           for (int i = 0; i < 8; ++i) q[i] = (half_t)((float)q[i] + (float)rr[i]);
         }
-        *reinterpret_cast<half8*>(o + t * 4) = q;
+        if (pair) {
+          *reinterpret_cast<half8*>(o + t * 4) = q;
+        } else {
+          half4 q4;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) q4[i] = q[i];
+          *reinterpret_cast<half4*>(o + t * 4) = q4;
+        }
       }
     }
     if (NT & 1) {
