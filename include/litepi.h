@@ -202,6 +202,46 @@ int lp_test_nms_views(lp_handle* h, const float* boxes, const float* scores, con
 int lp_test_tile_views(lp_handle* h, const uint8_t* img, int H, int W, const lp_tiling* tiling, int byte_offset, uint8_t* out,
                        int cap, int* n_views);
 
+/* ---- pixel format of the frames (additive to ABI 310) ------------------------------- */
+/* Hardware video decoders and capture pipelines deliver NV12: a full-resolution Y plane followed by a half-resolution
+ * interleaved UV plane (U first), 1.5 bytes per pixel.  With LP_PIX_NV12 set on the handle, every entry point that takes
+ * FRAMES converts them on the device into a handle-owned packed BGR buffer and runs unchanged on that buffer, so the result
+ * equals the result on the converted frames.  The conversion is limited-range YCbCr -> 8-bit BGR in 20-bit fixed point (the
+ * arithmetic OpenCV publishes for COLOR_YUV2BGR_NV12), all in int32, >> arithmetic:
+ *   u = U - 128;  v = V - 128;  y = max(Y - 16, 0) * CY;  h = 1 << 19
+ *   R = clamp((y + h + CVR * v) >> 20, 0, 255)
+ *   G = clamp((y + h - CVG * v - CUG * u) >> 20, 0, 255)
+ *   B = clamp((y + h + CUB * u) >> 20, 0, 255)
+ *   BT601 (cv2's constants): CY 1220542, CVR 1673527, CUG 409993, CVG 852492, CUB 2116026
+ *   BT709 (HD video)       : CY 1220542, CVR 1880097, CUG 223347, CVG 558891, CUB 2214593
+ * NV12 needs even H and W, pitch >= W, uv_offset >= pitch * H and frame_stride >= one frame; for LP_PIX_BGR8 the layout
+ * fields must be 0.  Anything else, an unknown enum value or a non-zero reserved word is LP_ERR_ARG at the call that sees it
+ * (lp_set_input_format for what needs no frame size, the frame-taking call for what does), before anything is enqueued.
+ * lp_detect_raw, lp_classify and the lp_test_* hooks other than lp_test_convert_frames keep taking BGR.  DESIGN.md 6c. */
+enum lp_pixfmt { LP_PIX_BGR8 = 0, LP_PIX_NV12 = 1 };
+enum lp_csc    { LP_CSC_BT601_LIMITED = 0, LP_CSC_BT709_LIMITED = 1 };
+typedef struct lp_frame_format {
+  int pixfmt;            /* lp_pixfmt */
+  int matrix;            /* lp_csc; ignored for BGR8 */
+  int pitch;             /* bytes per row of the Y plane and of the UV plane; 0 = W (tight) */
+  int reserved0;
+  int64_t uv_offset;     /* bytes from a frame's first Y byte to its first UV byte; 0 = pitch * H */
+  int64_t frame_stride;  /* lp_*_device only: bytes between consecutive frames; 0 = uv_offset + pitch * H / 2 */
+  int reserved[6];       /* zero */
+} lp_frame_format;
+
+/* pure host, no handle, no device: validates fmt (NULL = packed BGR) for an H x W frame and resolves the zeros: *uv_offset
+ * (0 for BGR8) and *frame_bytes, the bytes of one frame (H * W * 3 for BGR8); either may be NULL */
+int lp_frame_layout(const lp_frame_format* fmt, int H, int W, int64_t* uv_offset, int64_t* frame_bytes);
+/* the format of the frames given to the NEXT calls of lp_detect, lp_run_batch, lp_run_batch_device, lp_run_tiled and
+ * lp_run_tiled_device; NULL = packed BGR (the default).  Copied; like lp_set_stream it is handle state.  Host frames in NV12
+ * are frame_bytes each (frame_stride is ignored for them). */
+int lp_set_input_format(lp_handle* h, const lp_frame_format* fmt);
+/* the converter alone (tests): B host frames of one size (contiguous, frame_stride apart), uploaded byte_offset (0..63)
+ * bytes past an aligned address -> out_bgr [B,H,W,3] */
+int lp_test_convert_frames(lp_handle* h, const uint8_t* frames, int B, int H, int W, const lp_frame_format* fmt,
+                           int byte_offset, uint8_t* out_bgr);
+
 /* ---- classifier alone ------------------------------------------------------------ */
 /* replaces PyTorchClassifier.predict_batch (e2e.py:378-396) for R host BGR crops of
  * individual sizes: ids [R], probs [R*num_classes] (softmax). */

@@ -182,11 +182,32 @@ struct lp_handle {
     int kind, B, geom_ver, min_area;
     const void* p0; void* p1; void* p2;
     float conf, iou;
+    // the frame format the step was captured with (key_format; all zero for packed BGR) and the identity of its conversion table
+    int pixfmt = 0, matrix = 0, pitch = 0, csc_gen = 0;
+    int64_t uv_offset = 0, frame_stride = 0;
     bool operator==(const GraphKey& o) const {
       return kind == o.kind && B == o.B && geom_ver == o.geom_ver && min_area == o.min_area && p0 == o.p0 && p1 == o.p1 && p2 == o.p2 &&
-             conf == o.conf && iou == o.iou;
+             conf == o.conf && iou == o.iou && pixfmt == o.pixfmt && matrix == o.matrix && pitch == o.pitch && csc_gen == o.csc_gen &&
+             uv_offset == o.uv_offset && frame_stride == o.frame_stride;
     }
   };
+  // ---- input pixel format (lp_set_input_format).  NV12 frames are converted into d_src, which then holds exactly the packed
+  //      BGR frames a BGR call would have put there; host NV12 frames are uploaded into d_raw first.  The converter reads its
+  //      per-frame geometry from one of four table slots in d_csc: a slot's content never changes while a captured step may
+  //      still point at it (a re-used slot gets a new generation number, which is part of the graph key), so alternating
+  //      layouts keep their captured steps.
+  lp_frame_format fmt = {};
+  DevBuf d_raw, d_csc;
+  struct CscSlot { std::vector<char> tab; int gen = 0; };
+  CscSlot csc_slots[4];
+  int csc_gen = 0, csc_next = 0;
+  bool nv12() const { return fmt.pixfmt == LP_PIX_NV12; }
+  void ensure_raw(size_t bytes) {
+    if (d_raw.bytes < bytes) {
+      d_raw.alloc(bytes + bytes / 4, false);
+      ++geom_ver;
+    }
+  }
   struct GraphEntry { GraphKey key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; bool failed = false; unsigned long stamp = 0; };
   std::vector<GraphEntry> graphs;
   int geom_ver = 0;
@@ -547,22 +568,156 @@ void run_or_capture(lp_handle* h, const lp_handle::GraphKey& key, bool allow, F&
   LP_HIP(hipGraphLaunch(e->exec, h->stream));
 }
 
-// upload B host images of individual sizes into d_src; returns their geometry
-std::vector<ImgGeom> upload_images(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B) {
+// ---- input pixel format (include/litepi.h lp_frame_format) ------------------------------------------------------------------
+// what can be said without a frame size: enum values, reserved words, signs, BGR8 without layout fields
+void check_format(const lp_frame_format* f) {
+  if (!f) return;   // packed BGR
+  LP_CHECK(f->pixfmt == LP_PIX_BGR8 || f->pixfmt == LP_PIX_NV12, LP_ERR_ARG, "unknown pixel format %d", f->pixfmt);
+  bool zero = f->reserved0 == 0;
+  for (int r : f->reserved) zero = zero && r == 0;
+  LP_CHECK(zero, LP_ERR_ARG, "lp_frame_format: reserved words must be zero");
+  if (f->pixfmt == LP_PIX_BGR8) {
+    LP_CHECK(f->pitch == 0 && f->uv_offset == 0 && f->frame_stride == 0, LP_ERR_ARG,
+             "packed BGR frames are tight: pitch / uv_offset / frame_stride must be 0");
+    return;
+  }
+  LP_CHECK(f->matrix == LP_CSC_BT601_LIMITED || f->matrix == LP_CSC_BT709_LIMITED, LP_ERR_ARG, "unknown colour matrix %d", f->matrix);
+  LP_CHECK(f->pitch >= 0 && f->uv_offset >= 0 && f->frame_stride >= 0, LP_ERR_ARG, "lp_frame_format: negative pitch / uv_offset / frame_stride");
+}
+
+// the layout of one H x W frame with the zeros resolved; throws LP_ERR_ARG for what the size rules out
+struct FrameLayout { int pitch; int64_t uv_off, frame_bytes, stride; };
+FrameLayout frame_layout(const lp_frame_format& f, int H, int W) {
+  LP_CHECK(H > 0 && W > 0, LP_ERR_ARG, "frame of %dx%d is empty", W, H);
+  FrameLayout L;
+  if (f.pixfmt != LP_PIX_NV12) {
+    L.pitch = W * 3; L.uv_off = 0; L.frame_bytes = (int64_t)H * W * 3; L.stride = L.frame_bytes;
+    return L;
+  }
+  LP_CHECK(H % 2 == 0 && W % 2 == 0, LP_ERR_ARG, "NV12 frames need an even width and height (got %dx%d)", W, H);
+  L.pitch = f.pitch ? f.pitch : W;
+  LP_CHECK(L.pitch >= W, LP_ERR_ARG, "NV12 pitch %d is smaller than the frame width %d", L.pitch, W);
+  L.uv_off = f.uv_offset ? f.uv_offset : (int64_t)L.pitch * H;
+  LP_CHECK(L.uv_off >= (int64_t)L.pitch * H, LP_ERR_ARG, "NV12 uv_offset %lld lies inside the Y plane (pitch %d x height %d = %lld bytes)",
+           (long long)L.uv_off, L.pitch, H, (long long)L.pitch * H);
+  L.frame_bytes = L.uv_off + (int64_t)L.pitch * (H / 2);
+  L.stride = f.frame_stride ? f.frame_stride : L.frame_bytes;
+  LP_CHECK(L.stride >= L.frame_bytes, LP_ERR_ARG, "NV12 frame_stride %lld is smaller than one frame (%lld bytes)", (long long)L.stride,
+           (long long)L.frame_bytes);
+  return L;
+}
+
+inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// one conversion launch: table in a slot of d_csc, grid extent, matrix, identity for the graph key, pixels for the profile
+struct CscPlan {
+  const CscFrame* dev = nullptr;
+  int B = 0, max_blocks = 0, matrix = 0, gen = 0;
+  double pixels = 0.0;
+};
+
+void finish_csc_table(std::vector<CscFrame>& tab, const void* src, const void* dst) {
+  for (auto& f : tab)
+    f.aligned = (reinterpret_cast<uintptr_t>(src) + f.src_off) % 16 == 0 && f.pitch % 16 == 0 && f.uv_off % 16 == 0 && f.w % 16 == 0 &&
+                (reinterpret_cast<uintptr_t>(dst) + f.dst_off) % 16 == 0;
+}
+
+// put the call's table into a slot of d_csc (found by content, else the next slot round-robin under a new generation)
+CscPlan plan_csc(lp_handle* h, std::vector<CscFrame>& tab, const void* src) {
+  const int cap = h->cfg.max_batch;
+  LP_CHECK((int)tab.size() <= cap, LP_ERR_ARG, "%zu frames exceed max_batch = %d", tab.size(), cap);
+  if (!h->d_csc.p) h->d_csc.alloc((size_t)4 * cap * sizeof(CscFrame));
+  finish_csc_table(tab, src, h->d_src.p);
+  CscPlan p;
+  p.B = (int)tab.size(); p.matrix = h->fmt.matrix;
+  for (const auto& f : tab) {
+    p.max_blocks = std::max(p.max_blocks, (f.h / 2) * ((f.w + 15) / 16));
+    p.pixels += (double)f.h * f.w;
+  }
+  const size_t nbytes = tab.size() * sizeof(CscFrame);
+  std::vector<char> blob(nbytes);
+  memcpy(blob.data(), tab.data(), nbytes);
+  int slot = -1;
+  for (int s = 0; s < 4; ++s)
+    if (h->csc_slots[s].gen && h->csc_slots[s].tab == blob) slot = s;
+  if (slot < 0) {
+    slot = h->csc_next;
+    h->csc_next = (h->csc_next + 1) % 4;
+    LP_HIP(hipStreamSynchronize(h->stream));   // an earlier asynchronous call may still read the slot
+    LP_HIP(hipMemcpyAsync(h->d_csc.as<CscFrame>() + (size_t)slot * cap, tab.data(), nbytes, hipMemcpyHostToDevice, h->stream));
+    LP_HIP(hipStreamSynchronize(h->stream));   // tab is the caller's temporary; uploads are rare (layout changes only)
+    h->csc_slots[slot].tab.swap(blob);
+    h->csc_slots[slot].gen = ++h->csc_gen;
+  }
+  p.dev = h->d_csc.as<CscFrame>() + (size_t)slot * cap;
+  p.gen = h->csc_slots[slot].gen;
+  return p;
+}
+
+void enqueue_csc(lp_handle* h, const uint8_t* src, const CscPlan& p, Profiler* prof) {
+  if (prof) prof->begin(h->stream);
+  launch_nv12_to_bgr(src, p.dev, h->d_src.as<uint8_t>(), p.B, p.max_blocks, p.matrix, h->stream);
+  if (prof) prof->end(h->stream, "nv12_to_bgr", "csc", 0.0, 4.5 * p.pixels);
+}
+
+// the handle's format as part of a graph key (nothing for packed BGR: those keys are what they were)
+void key_format(const lp_handle* h, const CscPlan& p, lp_handle::GraphKey& k) {
+  if (!h->nv12()) return;
+  k.pixfmt = h->fmt.pixfmt; k.matrix = h->fmt.matrix; k.pitch = h->fmt.pitch; k.csc_gen = p.gen;
+  k.uv_offset = h->fmt.uv_offset; k.frame_stride = h->fmt.frame_stride;
+}
+
+// B equally sized NV12 frames resident at dev_imgs (lp_*_device): validates the layout, sizes d_src for the converted frames,
+// gives their geometry (make_geom offsets, 16-byte aligned like the host path's) and the conversion plan
+CscPlan device_csc(lp_handle* h, const void* dev_imgs, int B, int H, int W, std::vector<ImgGeom>& g) {
+  const FrameLayout L = frame_layout(h->fmt, H, W);
+  const size_t fb = align16((size_t)H * W * 3);
+  std::vector<CscFrame> tab(B);
+  for (int i = 0; i < B; ++i) {
+    g[i] = make_geom(H, W, h->cfg.det_input, (long)(i * fb));
+    tab[i] = CscFrame{(long)(i * L.stride), (long)L.uv_off, (long)(i * fb), H, W, L.pitch, 0};
+  }
+  h->ensure_src(fb * B);
+  return plan_csc(h, tab, dev_imgs);
+}
+
+// upload B host images of individual sizes into d_src (NV12 frames: into d_raw, with the plan of their conversion into d_src
+// in *csc); returns their geometry
+std::vector<ImgGeom> upload_images(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, CscPlan* csc = nullptr) {
+  const bool nv = h->nv12();
+  lp_frame_format hf = h->fmt;
+  hf.frame_stride = 0;   // host frames come one pointer each: frame_bytes apiece, the stride of device batches does not apply
   std::vector<ImgGeom> g(B);
-  size_t total = 0;
+  std::vector<size_t> nb(B), off(B);   // bytes of every frame as it is uploaded, and its offset in the upload buffer
+  std::vector<CscFrame> tab;
+  size_t bgr_total = 0, total = 0;
   for (int i = 0; i < B; ++i) {
     LP_CHECK(imgs[i] && hs[i] > 0 && ws[i] > 0, LP_ERR_ARG, "image %d is empty", i);
-    g[i] = make_geom(hs[i], ws[i], h->cfg.det_input, (long)total);
-    total += (size_t)hs[i] * ws[i] * 3;
-    total = (total + 15) & ~(size_t)15;
+    g[i] = make_geom(hs[i], ws[i], h->cfg.det_input, (long)bgr_total);
+    bgr_total = align16(bgr_total + (size_t)hs[i] * ws[i] * 3);
+    if (nv) {
+      const FrameLayout L = frame_layout(hf, hs[i], ws[i]);
+      nb[i] = (size_t)L.frame_bytes; off[i] = total;
+      tab.push_back(CscFrame{(long)total, (long)L.uv_off, g[i].src_off, hs[i], ws[i], L.pitch, 0});
+      total = align16(total + nb[i]);
+    } else {
+      nb[i] = (size_t)hs[i] * ws[i] * 3; off[i] = (size_t)g[i].src_off;
+      total = bgr_total;
+    }
   }
-  h->ensure_src(total);
+  h->ensure_src(bgr_total);
+  uint8_t* dst = h->d_src.as<uint8_t>();
+  if (nv) {
+    LP_CHECK(csc, LP_ERR_STATE, "this entry point takes packed BGR frames only");
+    h->ensure_raw(total);
+    dst = h->d_raw.as<uint8_t>();
+    *csc = plan_csc(h, tab, dst);
+  }
   // small uploads (a single frame: the batch-1 latency path) go straight from the caller's memory
   static const int n_threads = getenv("LITEPI_UPLOAD_THREADS") ? atoi(getenv("LITEPI_UPLOAD_THREADS")) : 8;
   if (n_threads <= 0 || B < 4 || total < ((size_t)4 << 20)) {
     for (int i = 0; i < B; ++i)
-      LP_HIP(hipMemcpyAsync(h->d_src.as<uint8_t>() + g[i].src_off, imgs[i], (size_t)hs[i] * ws[i] * 3, hipMemcpyHostToDevice, h->stream));
+      LP_HIP(hipMemcpyAsync(dst + off[i], imgs[i], nb[i], hipMemcpyHostToDevice, h->stream));
     return g;
   }
   if (h->h_stage_bytes < total) {
@@ -585,15 +740,14 @@ std::vector<ImgGeom> upload_images(lp_handle* h, const uint8_t* const* imgs, con
     const size_t group_bytes = ngroup == 0 ? (size_t)2 << 20 : (ngroup == 1 ? (size_t)5 << 20 : group_mb << 20);
     ++ngroup;
     jobs.clear();
-    while (i1 < B && (i1 == i0 || gb + (size_t)hs[i1] * ws[i1] * 3 <= group_bytes)) {
-      const size_t nb = (size_t)hs[i1] * ws[i1] * 3;
-      for (size_t o = 0; o < nb; o += slice) jobs.push_back({imgs[i1] + o, h->h_stage + g[i1].src_off + o, std::min(slice, nb - o)});
-      gb += nb;
+    while (i1 < B && (i1 == i0 || gb + nb[i1] <= group_bytes)) {
+      for (size_t o = 0; o < nb[i1]; o += slice) jobs.push_back({imgs[i1] + o, h->h_stage + off[i1] + o, std::min(slice, nb[i1] - o)});
+      gb += nb[i1];
       ++i1;
     }
     h->pool->run(jobs.data(), (int)jobs.size());
-    const size_t lo = (size_t)g[i0].src_off, hi = (size_t)g[i1 - 1].src_off + (size_t)hs[i1 - 1] * ws[i1 - 1] * 3;
-    LP_HIP(hipMemcpyAsync(h->d_src.as<uint8_t>() + lo, h->h_stage + lo, hi - lo, hipMemcpyHostToDevice, h->stream));
+    const size_t lo = off[i0], hi = off[i1 - 1] + nb[i1 - 1];
+    LP_HIP(hipMemcpyAsync(dst + lo, h->h_stage + lo, hi - lo, hipMemcpyHostToDevice, h->stream));
     i0 = i1;
   }
   return g;
@@ -614,7 +768,7 @@ int run_chunk_frames() {   // (read per call: tests switch it inside one process
 }
 bool chunked_ok(const lp_handle* h, const int* hs, const int* ws, int B) {
   const int c = run_chunk_frames();
-  if (c <= 0 || B < 32 || B < 2 * c || h->prof_next) return false;
+  if (c <= 0 || B < 32 || B < 2 * c || h->prof_next || h->nv12()) return false;   // (the experiment moves packed BGR only)
   for (int i = 1; i < B; ++i)
     if (hs[i] != hs[0] || ws[i] != ws[0]) return false;
   return ((size_t)hs[0] * ws[0] * 3) % 16 == 0;
@@ -882,14 +1036,23 @@ int lp_run_tiled(lp_handle* h, const uint8_t* const* imgs, const int* hs, const 
   std::vector<ImgGeom> fg(B);
   for (int i = 0; i < B; ++i) fg[i] = make_geom(hs[i], ws[i], h->cfg.det_input, 0);
   (void)tile_layout(h, fg, *tiling);   // view count checked before anything is uploaded
-  fg = upload_images(h, imgs, hs, ws, B);
+  const bool nv = h->nv12();
+  if (nv) {   // and the format, likewise (host frames: frame_stride does not apply)
+    lp_frame_format hf = h->fmt;
+    hf.frame_stride = 0;
+    for (int i = 0; i < B; ++i) (void)frame_layout(hf, hs[i], ws[i]);
+  }
+  CscPlan csc;
+  fg = upload_images(h, imgs, hs, ws, B, &csc);
   const TileLayout lay = tile_layout(h, fg, *tiling);
   upload_tiles(h, fg, lay);
   Profiler* prof = begin_profile(h);
   const ImgGeom* fgeom = h->d_fgeom.as<ImgGeom>();
   LP_HIP(hipEventRecord(h->ev[0], h->stream));
   lp_handle::GraphKey k1{9, B, h->geom_ver, min_area, h->d_src.p, h->d_dets.p, h->d_counts.p, conf, iou};
+  key_format(h, csc, k1);
   run_or_capture(h, k1, prof == nullptr, [&]() {
+    if (nv) enqueue_csc(h, h->d_raw.as<uint8_t>(), csc, prof);
     enqueue_tiled_detect(h, h->d_src.as<uint8_t>(), lay, B, conf, iou, min_area, h->d_dets.as<lp_det>(), h->d_counts.as<int>(), true, prof);
   });
   LP_HIP(hipEventRecord(h->ev[2], h->stream));
@@ -936,14 +1099,23 @@ int lp_run_tiled_device(lp_handle* h, const void* dev_imgs, int B, int H, int W,
   check_tiling(tiling, h->cfg.det_input);
   LP_HIP(hipSetDevice(h->cfg.device));
   std::vector<ImgGeom> fg(B);
+  const bool nv = h->nv12();
+  CscPlan csc;
   for (int i = 0; i < B; ++i) fg[i] = make_geom(H, W, h->cfg.det_input, (long)i * H * W * 3);
+  if (nv) {
+    (void)frame_layout(h->fmt, H, W);
+    (void)tile_layout(h, fg, *tiling);   // format and view count checked before any buffer is sized
+    csc = device_csc(h, dev_imgs, B, H, W, fg);
+  }
   const TileLayout lay = tile_layout(h, fg, *tiling);
   upload_tiles(h, fg, lay);
   Profiler* prof = begin_profile(h);
-  const uint8_t* src = static_cast<const uint8_t*>(dev_imgs);
+  const uint8_t* src = nv ? h->d_src.as<uint8_t>() : static_cast<const uint8_t*>(dev_imgs);
   const bool classify = h->cls && h->cls->loaded();
   lp_handle::GraphKey key{12, B, h->geom_ver, min_area, dev_imgs, dev_dets, dev_counts, conf, iou};
+  key_format(h, csc, key);
   run_or_capture(h, key, prof == nullptr, [&]() {
+    if (nv) enqueue_csc(h, static_cast<const uint8_t*>(dev_imgs), csc, prof);
     enqueue_tiled_detect(h, src, lay, B, conf, iou, classify ? min_area : -1, static_cast<lp_det*>(dev_dets), static_cast<int*>(dev_counts),
                          classify, prof);
     if (classify) enqueue_classify(h, src, B, static_cast<lp_det*>(dev_dets), nullptr, nullptr, nullptr, prof, 0, h->d_fgeom.as<ImgGeom>());
@@ -1041,6 +1213,65 @@ int lp_test_tile_views(lp_handle* h, const uint8_t* img, int H, int W, const lp_
   LP_API_END
 }
 
+int lp_frame_layout(const lp_frame_format* fmt, int H, int W, int64_t* uv_offset, int64_t* frame_bytes) {
+  LP_API_BEGIN
+  check_format(fmt);
+  const lp_frame_format bgr = {};
+  const FrameLayout L = frame_layout(fmt ? *fmt : bgr, H, W);
+  if (uv_offset) *uv_offset = L.uv_off;
+  if (frame_bytes) *frame_bytes = L.frame_bytes;
+  LP_API_END
+}
+
+int lp_set_input_format(lp_handle* h, const lp_frame_format* fmt) {
+  LP_API_BEGIN
+  LP_CHECK(h, LP_ERR_ARG, "null handle");
+  check_format(fmt);
+  const lp_frame_format bgr = {};
+  h->fmt = fmt ? *fmt : bgr;
+  LP_API_END
+}
+
+int lp_test_convert_frames(lp_handle* h, const uint8_t* frames, int B, int H, int W, const lp_frame_format* fmt, int byte_offset,
+                           uint8_t* out_bgr) {
+  LP_API_BEGIN
+  LP_CHECK(h && frames && out_bgr && fmt && B >= 1 && byte_offset >= 0 && byte_offset < 64, LP_ERR_ARG, "bad argument");
+  check_format(fmt);
+  LP_CHECK(fmt->pixfmt == LP_PIX_NV12, LP_ERR_ARG, "lp_test_convert_frames converts NV12 frames");
+  const FrameLayout L = frame_layout(*fmt, H, W);
+  LP_HIP(hipSetDevice(h->cfg.device));
+  // the output sits between two guard zones, and its frames at 16-byte aligned offsets as in d_src; every byte the
+  // converter does not own (guards, the gaps between frames) must still hold the fill pattern afterwards
+  const size_t guard = 256, fb = (size_t)H * W * 3, fs = align16(fb), in_bytes = (size_t)(B - 1) * L.stride + L.frame_bytes;
+  DevBuf d_in, d_tab, d_out;
+  d_in.alloc(in_bytes + 64);
+  LP_HIP(hipMemcpy(d_in.as<uint8_t>() + byte_offset, frames, in_bytes, hipMemcpyHostToDevice));
+  d_out.alloc(2 * guard + fs * B, false);
+  LP_HIP(hipMemset(d_out.p, 0xA5, d_out.bytes));
+  LP_HIP(hipDeviceSynchronize());
+  std::vector<CscFrame> tab(B);
+  int max_blocks = 0;
+  for (int i = 0; i < B; ++i) {
+    tab[i] = CscFrame{(long)(byte_offset + i * L.stride), (long)L.uv_off, (long)(guard + i * fs), H, W, L.pitch, 0};
+    max_blocks = std::max(max_blocks, (H / 2) * ((W + 15) / 16));
+  }
+  finish_csc_table(tab, d_in.p, d_out.p);
+  d_tab.alloc(tab.size() * sizeof(CscFrame));
+  LP_HIP(hipMemcpy(d_tab.p, tab.data(), tab.size() * sizeof(CscFrame), hipMemcpyHostToDevice));
+  launch_nv12_to_bgr(d_in.as<uint8_t>(), d_tab.as<CscFrame>(), d_out.as<uint8_t>(), B, max_blocks, fmt->matrix, h->stream);
+  LP_HIP(hipStreamSynchronize(h->stream));
+  std::vector<uint8_t> all(d_out.bytes);
+  LP_HIP(hipMemcpy(all.data(), d_out.p, all.size(), hipMemcpyDeviceToHost));
+  for (int i = 0; i < B; ++i) memcpy(out_bgr + i * fb, all.data() + guard + i * fs, fb);
+  size_t touched = 0;
+  for (size_t k = 0; k < all.size(); ++k) {
+    const bool owned = k >= guard && k < guard + fs * B && (k - guard) % fs < fb;
+    touched += !owned && all[k] != 0xA5;
+  }
+  LP_CHECK(touched == 0, LP_ERR_STATE, "the converter wrote %zu bytes outside its output frames", touched);
+  LP_API_END
+}
+
 int lp_detect_raw(lp_handle* h, const uint8_t* bgr, int B, float* out0) {
   LP_API_BEGIN
   LP_CHECK(h && bgr && out0, LP_ERR_ARG, "null argument");
@@ -1071,11 +1302,15 @@ int lp_detect(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int
   LP_CHECK(h->det && h->det->loaded(), LP_ERR_STATE, "detector not loaded");
   LP_CHECK(B >= 1 && B <= h->cfg.max_batch, LP_ERR_ARG, "batch %d outside 1..%d", B, h->cfg.max_batch);
   LP_HIP(hipSetDevice(h->cfg.device));
-  std::vector<ImgGeom> g = upload_images(h, imgs, hs, ws, B);
+  const bool nv = h->nv12();
+  CscPlan csc;
+  std::vector<ImgGeom> g = upload_images(h, imgs, hs, ws, B, &csc);
   h->upload_geom(g);
   Profiler* prof = begin_profile(h);
   lp_handle::GraphKey key{2, B, h->geom_ver, -1, h->d_src.p, h->d_dets.p, h->d_counts.p, conf, iou};
+  key_format(h, csc, key);
   run_or_capture(h, key, prof == nullptr, [&]() {
+    if (nv) enqueue_csc(h, h->d_raw.as<uint8_t>(), csc, prof);
     enqueue_detect(h, h->d_src.as<uint8_t>(), g, B, conf, nullptr, prof);
     enqueue_nms(h, B, iou, -1, h->d_dets.as<lp_det>(), h->d_counts.as<int>(), false, prof);
   });
@@ -1099,14 +1334,18 @@ int lp_run_batch(lp_handle* h, const uint8_t* const* imgs, const int* hs, const 
     run_batch_chunked(h, imgs, hs[0], ws[0], B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing);
     return LP_OK;
   }
-  std::vector<ImgGeom> g = upload_images(h, imgs, hs, ws, B);
+  const bool nv = h->nv12();
+  CscPlan csc;
+  std::vector<ImgGeom> g = upload_images(h, imgs, hs, ws, B, &csc);
   h->upload_geom(g);
   Profiler* prof = begin_profile(h);
   // three captured pieces with the stage-boundary events between them (PipelineMetrics wants detection, ROI extraction and
-  // classification times separately, e2e.py:452-499)
+  // classification times separately, e2e.py:452-499); the colour conversion of NV12 frames is booked under detection
   LP_HIP(hipEventRecord(h->ev[0], h->stream));
   lp_handle::GraphKey k1{3, B, h->geom_ver, min_area, h->d_src.p, h->d_dets.p, h->d_counts.p, conf, iou};
+  key_format(h, csc, k1);
   run_or_capture(h, k1, prof == nullptr, [&]() {
+    if (nv) enqueue_csc(h, h->d_raw.as<uint8_t>(), csc, prof);
     enqueue_detect(h, h->d_src.as<uint8_t>(), g, B, conf, nullptr, prof);
     enqueue_nms(h, B, iou, min_area, h->d_dets.as<lp_det>(), h->d_counts.as<int>(), true, prof);
   });
@@ -1157,13 +1396,19 @@ int lp_run_batch_device(lp_handle* h, const void* dev_imgs, int B, int H, int W,
   LP_CHECK(B >= 1 && B <= h->cfg.max_batch && H > 0 && W > 0, LP_ERR_ARG, "bad batch/shape");
   LP_HIP(hipSetDevice(h->cfg.device));
   std::vector<ImgGeom> g(B);
-  for (int i = 0; i < B; ++i) g[i] = make_geom(H, W, h->cfg.det_input, (long)i * H * W * 3);
+  const bool nv = h->nv12();
+  CscPlan csc;
+  if (nv) csc = device_csc(h, dev_imgs, B, H, W, g);
+  else
+    for (int i = 0; i < B; ++i) g[i] = make_geom(H, W, h->cfg.det_input, (long)i * H * W * 3);
   h->upload_geom(g);
   Profiler* prof = begin_profile(h);
-  const uint8_t* src = static_cast<const uint8_t*>(dev_imgs);
+  const uint8_t* src = nv ? h->d_src.as<uint8_t>() : static_cast<const uint8_t*>(dev_imgs);
   const bool classify = h->cls && h->cls->loaded();
   lp_handle::GraphKey key{1, B, h->geom_ver, min_area, dev_imgs, dev_dets, dev_counts, conf, iou};
+  key_format(h, csc, key);
   run_or_capture(h, key, prof == nullptr, [&]() {
+    if (nv) enqueue_csc(h, static_cast<const uint8_t*>(dev_imgs), csc, prof);
     enqueue_detect(h, src, g, B, conf, nullptr, prof);
     enqueue_nms(h, B, iou, classify ? min_area : -1, static_cast<lp_det*>(dev_dets), static_cast<int*>(dev_counts), classify, prof);
     if (classify) enqueue_classify(h, src, B, static_cast<lp_det*>(dev_dets), nullptr, nullptr, nullptr, prof);

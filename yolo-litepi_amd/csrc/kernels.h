@@ -138,6 +138,18 @@ struct RoiResizeArgs {
 void launch_roi_resize(const RoiResizeArgs& a, int max_items, hipStream_t st);
 size_t roi_resize_lds_bytes();
 
+// ---- csc_kernels.hip (NV12 frames -> the packed BGR frames the pipeline reads) ---------------
+struct CscFrame {      // one frame of a conversion call, device resident
+  long src_off;        // byte offset of the frame's first Y byte in the source buffer
+  long uv_off;         // bytes from the first Y byte to the first UV byte
+  long dst_off;        // byte offset of the BGR frame in the destination buffer (ImgGeom::src_off of the same frame)
+  int h, w, pitch;     // even size; bytes per row of both planes
+  int aligned;         // 1: every 16-byte access of the frame's full blocks is 16-byte aligned
+};
+struct CscCoef { int cy, cvr, cug, cvg, cub; };   // 20-bit fixed point (include/litepi.h lp_csc)
+// B frames in one launch; max_blocks = the largest (h / 2) * ceil(w / 16) of the table (2-row x 16-pixel blocks of a frame)
+void launch_nv12_to_bgr(const uint8_t* src, const CscFrame* frames, uint8_t* dst, int B, int max_blocks, int matrix, hipStream_t st);
+
 // ---- cls_kernels.hip ------------------------------------------------------------------
 // conv1 3x3/s2 (3->CO) + folded BN + ReLU on (x/255 - mean)/std of the uint8 RGB crops
 void launch_cls_stem(int prec, const uint8_t* rgb, const float* w /*[27][CO]*/, const float* bias, int CO,

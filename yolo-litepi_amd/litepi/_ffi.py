@@ -41,6 +41,15 @@ class LpTiling(C.Structure):
     _fields_ = [("overlap", C.c_int), ("full_frame", C.c_int), ("reserved", C.c_int * 6)]
 
 
+LP_PIX_BGR8, LP_PIX_NV12 = 0, 1
+LP_CSC_BT601_LIMITED, LP_CSC_BT709_LIMITED = 0, 1
+
+
+class LpFrameFormat(C.Structure):
+    _fields_ = [("pixfmt", C.c_int), ("matrix", C.c_int), ("pitch", C.c_int), ("reserved0", C.c_int), ("uv_offset", C.c_int64),
+                ("frame_stride", C.c_int64), ("reserved", C.c_int * 6)]
+
+
 # numpy view of lp_det records
 DET_DTYPE = [("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("det_conf", "<f4"), ("det_class", "<i4"),
              ("cls_class", "<i4"), ("cls_conf", "<f4")]
@@ -52,6 +61,7 @@ SYMBOLS = [
     "lp_test_conv", "lp_test_postprocess", "lp_test_nms_boxes", "lp_test_roi_resize", "lp_test_letterbox", "lp_roi_overflow",
     "lp_comm_unique_id", "lp_comm_init", "lp_gather", "lp_comm_destroy",
     "lp_tile_grid", "lp_run_tiled", "lp_run_tiled_device", "lp_test_nms_views", "lp_test_tile_views",
+    "lp_frame_layout", "lp_set_input_format", "lp_test_convert_frames",
 ]
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
 
@@ -109,6 +119,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_test_nms_views.argtypes = [vp, fp, fp, ip, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp,
                                       ip, ip, ip]
     lib.lp_test_tile_views.argtypes = [vp, vp, C.c_int, C.c_int, tp, C.c_int, vp, C.c_int, ip]
+    ffp, i64p = C.POINTER(LpFrameFormat), C.POINTER(C.c_int64)
+    lib.lp_frame_layout.argtypes = [ffp, C.c_int, C.c_int, i64p, i64p]
+    lib.lp_set_input_format.argtypes = [vp, ffp]
+    lib.lp_test_convert_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ffp, C.c_int, vp]
     for s in SYMBOLS:
         if s not in ("lp_last_error", "lp_default_config", "lp_destroy"):
             getattr(lib, s).restype = C.c_int

@@ -17,7 +17,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _ffi
-from ._ffi import DET_DTYPE, LpConfig, LpKernelTime, LpTiming, LpTiling, check
+from ._ffi import DET_DTYPE, LpConfig, LpFrameFormat, LpKernelTime, LpTiming, LpTiling, check
+from .pixfmt import CSC_MATRICES, PIXEL_FORMATS, nv12_frame_hw
 
 _PREC = {"fp32": _ffi.LP_FP32, "fp16": _ffi.LP_FP16, "float32": _ffi.LP_FP32, "float16": _ffi.LP_FP16, "half": _ffi.LP_FP16}
 
@@ -27,6 +28,33 @@ def _as_bgr(img: np.ndarray) -> np.ndarray:
     if a.ndim != 3 or a.shape[2] != 3:
         raise ValueError(f"expected a BGR uint8 HxWx3 image, got shape {img.shape}")
     return a
+
+
+def _as_nv12(img: np.ndarray) -> np.ndarray:
+    a = np.ascontiguousarray(img, dtype=np.uint8)
+    nv12_frame_hw(a.shape)   # ValueError for anything but (H * 3 // 2, W)
+    return a
+
+
+def _frame_format(pixfmt: str = "bgr", matrix: str = "bt601", pitch: int = 0, uv_offset: int = 0, frame_stride: int = 0) -> LpFrameFormat:
+    if pixfmt not in PIXEL_FORMATS:
+        raise ValueError(f"unknown pixel format {pixfmt!r} (one of {sorted(PIXEL_FORMATS)})")
+    if matrix not in CSC_MATRICES:
+        raise ValueError(f"unknown colour matrix {matrix!r} (one of {sorted(CSC_MATRICES)})")
+    f = LpFrameFormat()
+    f.pixfmt, f.matrix, f.pitch, f.uv_offset, f.frame_stride = PIXEL_FORMATS[pixfmt], CSC_MATRICES[matrix], int(pitch), int(uv_offset), int(frame_stride)
+    return f
+
+
+def frame_layout(H: int, W: int, pixfmt: str = "nv12", matrix: str = "bt601", pitch: int = 0, uv_offset: int = 0,
+                 frame_stride: int = 0) -> Tuple[int, int]:
+    """(uv_offset, frame_bytes) of an H x W frame in the given format with the zeros resolved (lp_frame_layout: host only, no
+    GPU needed); LitepiError(LP_ERR_ARG) for a layout the size rules out."""
+    lib = _ffi.load_library()
+    f = _frame_format(pixfmt, matrix, pitch, uv_offset, frame_stride)
+    uv, nb = C.c_int64(), C.c_int64()
+    check(lib, lib.lp_frame_layout(C.byref(f), int(H), int(W), C.byref(uv), C.byref(nb)))
+    return uv.value, nb.value
 
 
 CLS_ARCHS = ("resnet18", "efficientnet", "mobilenetv2", "shufflenetv2")   # the --clf_arch choices of e2e.py:1021
@@ -73,6 +101,7 @@ class Engine:
         check(self.lib, self.lib.lp_create(C.byref(cfg), C.byref(self._h)))
         self.has_detector = False
         self.has_classifier = False
+        self.pixel_format, self.csc_matrix, self._tight_frames = "bgr", "bt601", True
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h:
@@ -124,16 +153,42 @@ class Engine:
         check(self.lib, self.lib.lp_detect_raw(self._h, a.ctypes.data, a.shape[0], out.ctypes.data))
         return out
 
-    def _img_args(self, images: Sequence[np.ndarray]):
-        imgs = [_as_bgr(i) for i in images]
+    # ---- pixel format of the frames ------------------------------------------------------------
+    def set_input_format(self, pixfmt: str = "bgr", matrix: str = "bt601", pitch: int = 0, uv_offset: int = 0,
+                         frame_stride: int = 0) -> None:
+        """The format of the frames given to the next detect / run_batch / run_tiled calls and their device twins
+        (lp_set_input_format).  "nv12" host frames are uint8 arrays of shape (H * 3 // 2, W)."""
+        f = _frame_format(pixfmt, matrix, pitch, uv_offset, frame_stride)
+        check(self.lib, self.lib.lp_set_input_format(self._h, C.byref(f)))
+        self.pixel_format, self.csc_matrix = pixfmt, matrix
+        self._tight_frames = not (pitch or uv_offset)
+
+    def frame_layout(self, H: int, W: int, **fmt) -> Tuple[int, int]:
+        return frame_layout(H, W, **fmt)
+
+    def frame_hw(self, frame: np.ndarray) -> Tuple[int, int]:
+        """(H, W) of a host frame in the engine's pixel format."""
+        return nv12_frame_hw(frame.shape) if self.pixel_format == "nv12" else (frame.shape[0], frame.shape[1])
+
+    def _img_args(self, images: Sequence[np.ndarray], frames: bool = False):
+        """ctypes arguments of host images; frames=True: they are frames in the engine's pixel format (everything else --
+        classifier crops, the test hooks -- is packed BGR)."""
+        if frames and self.pixel_format == "nv12":
+            if not self._tight_frames:
+                raise ValueError("host NV12 arrays are tight (H * 3 // 2, W): a pitch / uv_offset describes device-resident frames")
+            imgs = [_as_nv12(i) for i in images]
+            sizes = [nv12_frame_hw(i.shape) for i in imgs]
+        else:
+            imgs = [_as_bgr(i) for i in images]
+            sizes = [(i.shape[0], i.shape[1]) for i in imgs]
         n = len(imgs)
         ptrs = (C.c_void_p * n)(*[i.ctypes.data for i in imgs])
-        hs = (C.c_int * n)(*[i.shape[0] for i in imgs])
-        ws = (C.c_int * n)(*[i.shape[1] for i in imgs])
+        hs = (C.c_int * n)(*[s[0] for s in sizes])
+        ws = (C.c_int * n)(*[s[1] for s in sizes])
         return imgs, ptrs, hs, ws
 
     def detect(self, images: Sequence[np.ndarray], conf: float, iou: float):
-        imgs, ptrs, hs, ws = self._img_args(images)
+        imgs, ptrs, hs, ws = self._img_args(images, frames=True)
         B = len(imgs)
         dets = np.zeros((B, self.cfg.max_det), dtype=DET_DTYPE)
         counts = (C.c_int * B)()
@@ -141,7 +196,7 @@ class Engine:
         return dets, np.array(counts[:], dtype=np.int64)
 
     def run_batch(self, images: Sequence[np.ndarray], conf: float, iou: float, min_area: int):
-        imgs, ptrs, hs, ws = self._img_args(images)
+        imgs, ptrs, hs, ws = self._img_args(images, frames=True)
         B = len(imgs)
         dets = np.zeros((B, self.cfg.max_det), dtype=DET_DTYPE)
         counts, num_det = (C.c_int * B)(), (C.c_int * B)()
@@ -164,7 +219,7 @@ class Engine:
     def run_tiled(self, images: Sequence[np.ndarray], conf: float, iou: float, min_area: int, overlap: int = 128,
                   full_frame: bool = True):
         """run_batch with every frame seen through its views (lp_run_tiled): same return values, per frame."""
-        imgs, ptrs, hs, ws = self._img_args(images)
+        imgs, ptrs, hs, ws = self._img_args(images, frames=True)
         B = len(imgs)
         dets = np.zeros((B, self.cfg.max_det), dtype=DET_DTYPE)
         counts, num_det = (C.c_int * B)(), (C.c_int * B)()
@@ -302,6 +357,20 @@ class Engine:
                                                     out.ctypes.data, n.value, C.byref(n)))
         return out
 
+    def test_convert_frames(self, frames: np.ndarray, B: int, H: int, W: int, matrix: str = "bt601", pitch: int = 0, uv_offset: int = 0,
+                            frame_stride: int = 0, byte_offset: int = 0) -> np.ndarray:
+        """The NV12 converter alone: the bytes of B frames of one layout -> uint8 BGR [B, H, W, 3]."""
+        f = _frame_format("nv12", matrix, pitch, uv_offset, frame_stride)
+        _, nb = frame_layout(H, W, "nv12", matrix, pitch, uv_offset, frame_stride)
+        a = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+        need = (B - 1) * (frame_stride or nb) + nb
+        if a.size < need:
+            raise ValueError(f"{B} frames of this layout are {need} bytes, got {a.size}")
+        out = np.empty((B, H, W, 3), np.uint8)
+        check(self.lib, self.lib.lp_test_convert_frames(self._h, a.ctypes.data, int(B), int(H), int(W), C.byref(f), int(byte_offset),
+                                                        out.ctypes.data))
+        return out
+
     def test_roi_resize(self, rois: Sequence[np.ndarray]) -> np.ndarray:
         imgs, ptrs, hs, ws = self._img_args(rois)
         S = self.cfg.cls_input
@@ -379,7 +448,8 @@ class NCNNDetector:
 
     def __init__(self, param_path: str, bin_path: str, input_size: int = 640, use_gpu: bool = False, num_threads: int = 4,
                  input_name: str = "in0", output_name: str = "out0", *, precision: str = "fp16", max_batch: int = 1,
-                 max_det: int = 300, device: int = 0, _engine: Optional[Engine] = None):
+                 max_det: int = 300, device: int = 0, pixel_format: str = "bgr", csc_matrix: str = "bt601",
+                 _engine: Optional[Engine] = None):
         self.input_size = input_size
         self.input_name = input_name
         self.output_name = output_name
@@ -388,6 +458,8 @@ class NCNNDetector:
         print(f"  Bin: {bin_path}")
         self.engine = _engine or Engine(precision=precision, max_batch=max_batch, max_det=max_det, det_input=input_size,
                                         device=device)
+        if _engine is None:
+            self.engine.set_input_format(pixel_format, csc_matrix)
         try:
             self.engine.load_detector(param_path, bin_path)
         except _ffi.LitepiError as e:  # e2e.py:213-216 raises RuntimeError on load failure
@@ -608,8 +680,11 @@ class HybridPipeline:
                  num_classes: int = 58, det_input_size: int = 640, cls_input_size: int = 64, use_gpu_detector: bool = False,
                  detector_threads: int = 4, classifier_device: str = "cpu", batch_size: int = 8, *, precision: str = "fp16",
                  max_batch: int = 1, max_det: int = 300, device: int = 0, max_rois: int = 0, numerics: str = "e2e",
-                 tile_overlap: Optional[int] = None, tile_full_frame: bool = True):
-        """tile_overlap: None = every frame is letterboxed to det_input (the reference's behaviour); an int = tiled inference
+                 tile_overlap: Optional[int] = None, tile_full_frame: bool = True, pixel_format: str = "bgr",
+                 csc_matrix: str = "bt601"):
+        """pixel_format: "bgr" = HxWx3 arrays (the reference's cv2 images); "nv12" = video frames as (H * 3 // 2, W) arrays,
+        converted on the device with csc_matrix ("bt601" = cv2's COLOR_YUV2BGR_NV12 constants, "bt709" = HD video).
+        tile_overlap: None = every frame is letterboxed to det_input (the reference's behaviour); an int = tiled inference
         (lp_run_tiled): frames larger than det_input are also seen as native-resolution crops overlapping by that many pixels,
         with the letterboxed whole frame as an extra view when tile_full_frame."""
         self.tile_overlap, self.tile_full_frame = tile_overlap, bool(tile_full_frame)
@@ -619,6 +694,8 @@ class HybridPipeline:
         self.engine = Engine(precision=precision, max_batch=max_batch, max_det=max_det, num_classes=num_classes,
                              det_input=det_input_size, cls_input=cls_input_size, device=device, max_rois=max_rois,
                              numerics=numerics, cls_arch=classifier_arch if classifier_arch in CLS_ARCHS else "shufflenetv2")
+        self.engine.set_input_format(pixel_format, csc_matrix)
+        self.pixel_format, self.csc_matrix = pixel_format, csc_matrix
         self.detector = NCNNDetector(detector_param, detector_bin, det_input_size, use_gpu_detector, detector_threads,
                                      _engine=self.engine)
         self.classifier = PyTorchClassifier(classifier_path, classifier_arch, num_classes, cls_input_size, classifier_device,
@@ -634,6 +711,8 @@ class HybridPipeline:
         self._lanes: List[Engine] = []
         self._lane_pool = None
         n_lanes = int(os.environ.get("LITEPI_DROPIN_LANES", "1"))
+        if n_lanes > 1 and pixel_format != "bgr":
+            raise ValueError("LITEPI_DROPIN_LANES: the upload lanes take packed BGR frames only; unset it for pixel_format " + repr(pixel_format))
         if n_lanes > 1 and max_batch >= 2 * n_lanes:
             from concurrent.futures import ThreadPoolExecutor
             lane_cap = -(-max_batch // n_lanes)
@@ -689,9 +768,10 @@ class HybridPipeline:
         max_frames = max(1, (cfg.max_rois if cfg.max_rois > 0 else cfg.max_batch * cfg.max_det) // cfg.max_det)
         groups, cur, used = [], [], 0
         for img in images:
-            nv = len(tile_grid(S, img.shape[0], img.shape[1], self.tile_overlap, self.tile_full_frame))
+            fh, fw = self.engine.frame_hw(img)
+            nv = len(tile_grid(S, fh, fw, self.tile_overlap, self.tile_full_frame))
             if nv > cap:
-                raise ValueError(f"a {img.shape[1]}x{img.shape[0]} frame needs {nv} views, more than max_batch = {cap}")
+                raise ValueError(f"a {fw}x{fh} frame needs {nv} views, more than max_batch = {cap}")
             if cur and (used + nv > cap or len(cur) >= max_frames):
                 groups.append(cur)
                 cur, used = [], 0

@@ -6,6 +6,11 @@ FPS figure, evaluation pass at ``--yolo_conf`` that feeds mAP; e2e.py:955-1011),
 Ultralytics-style metric (e2e.py:656-824) and the same appended ``comparison_summary.csv`` schema
 (e2e.py:1166-1184).  New flags: ``--batch_images``, ``--precision``, ``--hip_device``, ``--gpus``.
 
+``--raw_frames FILE --frame_size WxH --pixel_format nv12|bgr [--csc_matrix bt601|bt709]``: the frames come from a headerless
+file of concatenated frames (what ``ffmpeg -pix_fmt nv12 -f rawvideo`` writes) instead of the images under ``--input``; they
+are named ``frame_000001`` ..., go through the same batching, sharding, result rows and CSV, and a frame's ground truth is
+``<name>.txt`` under ``--labels``.  NV12 frames are converted on the device.
+
 ``--gpus N`` (launched as ``python -m torch.distributed.run --nproc-per-node N -m litepi.e2e ... --gpus N``): one process
 per GPU, the sorted image list is sharded contiguously (``distributed.shard_range``), every rank runs both passes on its
 shard with a full weight replica, the per-image predictions and ground truths are gathered to rank 0 once
@@ -78,6 +83,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "batch_images x the views of a 2048x2048 frame")
     p.add_argument("--tile_full_frame", type=int, choices=[0, 1], default=1,
                    help="tiled inference: the letterboxed whole frame is an extra view of every frame that needs crops")
+    p.add_argument("--raw_frames", type=str, default=None,
+                   help="headerless file of concatenated video frames (ffmpeg -f rawvideo) evaluated instead of the images of --input; "
+                        "needs --frame_size; frames are named frame_000001, frame_000002, ...")
+    p.add_argument("--frame_size", type=str, default=None, help="WxH of the frames of --raw_frames, e.g. 1280x720")
+    p.add_argument("--pixel_format", type=str, choices=["bgr", "nv12"], default="bgr",
+                   help="pixel format of the frames of --raw_frames: packed bgr24, or nv12 (converted on the device)")
+    p.add_argument("--csc_matrix", type=str, choices=["bt601", "bt709"], default="bt601",
+                   help="YCbCr matrix of nv12 frames (limited range): bt601 = cv2's COLOR_YUV2BGR_NV12, bt709 = HD video")
     p.add_argument("--no_jit", action="store_true", help="accepted and ignored: there is no TorchScript on this path (e2e_optimize.py:884)")
     return p
 
@@ -160,6 +173,47 @@ def visualize_prediction(img_bgr: np.ndarray, predictions: Sequence[Dict], groun
     d.rectangle([5, 5, 400, 35], fill=BLACK)
     d.text((10, 14), f"GT: {len(ground_truths)} | Predictions: {len(predictions)}", fill=WHITE, font=font)
     im.save(str(output_path))
+
+
+class RawFrame:
+    """One frame of a --raw_frames file, standing where an image path stands in the evaluation loop."""
+
+    def __init__(self, index: int, parent: Path):
+        self.index, self.parent = index, parent
+        self.name = self.stem = f"frame_{index + 1:06d}"
+
+    def __lt__(self, other):
+        return self.index < other.index
+
+
+def parse_frame_size(text: Optional[str]) -> Tuple[int, int]:
+    """"WxH" -> (W, H)."""
+    try:
+        w, h = (int(v) for v in str(text).lower().split("x"))
+    except ValueError:
+        raise ValueError(f"--frame_size must be WxH, e.g. 1280x720 (got {text!r})") from None
+    if w <= 0 or h <= 0:
+        raise ValueError(f"--frame_size must be positive (got {text!r})")
+    return w, h
+
+
+def read_raw_frames(path, width: int, height: int, pixel_format: str = "nv12") -> np.ndarray:
+    """The frames of a headerless file of concatenated frames as one read-only array: [n, H * 3 // 2, W] for nv12 (the
+    host frame shape of the backend), [n, H, W, 3] for bgr.  A trailing partial frame is an error."""
+    if pixel_format == "nv12":
+        if width % 2 or height % 2:
+            raise ValueError(f"NV12 frames need an even width and height (got {width}x{height})")
+        shape = (height * 3 // 2, width)
+    elif pixel_format == "bgr":
+        shape = (height, width, 3)
+    else:
+        raise ValueError(f"unknown pixel format {pixel_format!r}")
+    nbytes = int(np.prod(shape))
+    size = os.path.getsize(path)
+    if size == 0 or size % nbytes:
+        raise ValueError(f"{path}: {size} bytes is not a whole number of {width}x{height} {pixel_format} frames of {nbytes} bytes "
+                         f"({size // nbytes} frames and {size % nbytes} bytes left over)")
+    return np.memmap(path, dtype=np.uint8, mode="r", shape=(size // nbytes,) + shape)
 
 
 def read_image_bgr(path) -> Optional[np.ndarray]:
@@ -270,6 +324,16 @@ def evaluate_predictions(all_preds, all_gts, num_classes, iou_threshold=0.5, iou
 
 
 # ------------------------------------------------------------------------------------------------
+def check_frame_args(args) -> None:
+    if args.raw_frames and not args.frame_size:
+        raise SystemExit("--raw_frames needs --frame_size WxH")
+    if args.raw_frames:   # a malformed size or a trailing partial frame is reported before any model is loaded
+        fw, fh = parse_frame_size(args.frame_size)
+        read_raw_frames(args.raw_frames, fw, fh, args.pixel_format)
+    if args.pixel_format != "bgr" and not args.raw_frames:
+        raise SystemExit(f"--pixel_format {args.pixel_format} describes the frames of --raw_frames; images of --input are decoded to BGR")
+
+
 def run_evaluation(args) -> Dict:
     """The reference's main loop (e2e.py:1090-1130) over image CHUNKS of --batch_images: per chunk one benchmark pass at
     --benchmark_conf (its wall time feeds the FPS figure) and, unless the two thresholds are equal, one evaluation pass at
@@ -278,6 +342,7 @@ def run_evaluation(args) -> Dict:
 
     from . import distributed as D
 
+    check_frame_args(args)
     rank, local_rank, world = D.env_rank_world()
     if args.gpus > 1 or world > 1:
         import torch
@@ -319,12 +384,21 @@ def run_evaluation(args) -> Dict:
                                   args.det_input_size, args.cls_input_size, False, args.detector_threads, args.device,
                                   args.batch_size, precision=args.precision, max_batch=max_batch, max_det=max_det,
                                   device=args.hip_device, max_rois=max_rois, numerics=args.numerics,
-                                  tile_overlap=args.tile_overlap, tile_full_frame=bool(args.tile_full_frame))
+                                  tile_overlap=args.tile_overlap, tile_full_frame=bool(args.tile_full_frame),
+                                  pixel_format=args.pixel_format, csc_matrix=args.csc_matrix)
     out_dir = Path(args.output) / combo
     out_dir.mkdir(parents=True, exist_ok=True)
 
     inp = Path(args.input)
-    if inp.is_file():
+    raw = None
+    if args.raw_frames:
+        fw, fh = parse_frame_size(args.frame_size)
+        raw = read_raw_frames(args.raw_frames, fw, fh, args.pixel_format)
+        label_dir = Path(args.labels) if args.labels else None
+        files = [RawFrame(i, Path(args.raw_frames).parent) for i in range(len(raw))]
+        if args.num_samples:
+            files = sample_images(files, args.num_samples, args.seed)
+    elif inp.is_file():
         files = [inp]
         label_dir = Path(args.labels) if args.labels else None
     else:
@@ -341,14 +415,14 @@ def run_evaluation(args) -> Dict:
     try:
         n_warm = args.warmup if args.warmup is not None else (10 if args.numerics == "e2e_optimize" else 0)
         if n_warm > 0:   # warmup_pipeline (e2e_optimize.py:552-570): random frame, conf 0.5
-            dummy = np.random.randint(0, 255, (640, 640, 3), dtype=np.uint8)
+            dummy = np.random.randint(0, 255, (960, 640) if args.pixel_format == "nv12" else (640, 640, 3), dtype=np.uint8)
             for _ in range(n_warm):
                 pipeline.run(dummy, conf_threshold=0.5)
             say(f"Warmup complete ({n_warm} passes)")
         for i in range(0, len(files), nb):
             chunk, imgs = [], []
             for f in files[i:i + nb]:
-                im = read_image_bgr(f)
+                im = np.ascontiguousarray(raw[f.index]) if raw is not None else read_image_bgr(f)
                 if im is None:
                     print(f"\nSkipping {f.name}")
                     continue
@@ -361,10 +435,14 @@ def run_evaluation(args) -> Dict:
             ev = bench if args.yolo_conf == args.benchmark_conf else pipeline.run_batch(imgs, args.yolo_conf, args.iou_threshold, args.min_area)
             for f, im, (res, _) in zip(chunk, imgs, ev):
                 lp = (label_dir / f"{f.stem}.txt") if label_dir else f.parent / "labels" / f"{f.stem}.txt"
-                all_gts.append(parse_yolo_label(lp, im.shape[1], im.shape[0]))
+                im_h, im_w = (fh, fw) if raw is not None else im.shape[:2]
+                all_gts.append(parse_yolo_label(lp, im_w, im_h))
                 if args.save_viz:   # overlays of the evaluation pass, e2e.py:1003-1009
                     viz_dir = out_dir / "visualizations"
                     viz_dir.mkdir(parents=True, exist_ok=True)
+                    if args.pixel_format == "nv12":   # the overlay is drawn on a host conversion with the device's arithmetic
+                        from .pixfmt import nv12_to_bgr
+                        im = nv12_to_bgr(im, args.csc_matrix)
                     visualize_prediction(im, res, all_gts[-1], class_names, viz_dir / f"vis_{f.stem}.png")
                 all_preds.append([{"bbox": r["bbox"], "conf": r.get("det_conf", 0.0), "cls_class": r.get("cls_class", -1)} for r in res])
                 names.append(f.name)
