@@ -242,6 +242,96 @@ int lp_set_input_format(lp_handle* h, const lp_frame_format* fmt);
 int lp_test_convert_frames(lp_handle* h, const uint8_t* frames, int B, int H, int W, const lp_frame_format* fmt,
                            int byte_offset, uint8_t* out_bgr);
 
+/* ---- sign tracking across frames (additive to ABI 310) ------------------------------ */
+/* A tracker turns the per-frame lp_det records of a frame SEQUENCE into identities with a voted class.  It consumes the
+ * records where lp_run_batch_device / lp_run_tiled_device left them, on the handle's stream, and keeps its track table in
+ * HBM between calls.  n_streams independent sequences (cameras) are tracked side by side; the frames of one stream are
+ * consumed in batch order.  Nothing in the reference tracks: the contract is the rule below (tests/tracking_ref.py restates
+ * it in NumPy).  All arithmetic is fp32, every operation rounded on its own (nothing contracted), in the order written.
+ * Per frame of a stream:
+ *   1 predict  for every live track dt = missed + 1; pred = box + vel * (float)dt per coordinate (motion = 0: pred = box)
+ *   2 match    the frame's detections are taken in descending det_conf (order of the fp32 bit patterns as signed
+ *              magnitudes; ties: lower record index first).  Each takes the track of highest IoU with IoU > iou_match among
+ *              the live tracks not yet claimed in this frame (class_gate: and of equal det_class); ties: lower slot.  With the
+ *              detection as i and the predicted box as j, a = (x2 - x1) * (y2 - y1) of each:
+ *                w = max(0, min(ix2, jx2) - max(ix1, jx1)); h likewise; inter = w * h
+ *                iou = inter / (((ai + aj) - inter) + 1e-6f)
+ *              A NaN never matches.
+ *   3 update   a matched track: motion = 1: vel = (det_box - box) / (float)dt; then box = det_box; hits += 1; missed = 0;
+ *              and if 0 <= cls_class < num_classes (the vote): acc[c] *= vote_decay for every class c;
+ *              wsum = wsum * vote_decay + cls_conf; acc[cls_class] += cls_conf
+ *   4 age      every live track not matched in this frame: missed += 1, freed when missed > max_age; every surviving track
+ *              that was live before this frame: age += 1
+ *   5 birth    the unmatched detections with det_conf >= new_conf, in record order, take the lowest free slot (slots freed
+ *              in step 4 included): id = next_id[stream]++ (from 1), vel = 0, hits = 1, missed = 0, age = 0, acc = 0, wsum = 0,
+ *              then the detection's own vote as in step 3.  With no free slot the detection stays untracked and the stream's
+ *              overflow counter goes up.
+ *   6 emit     one lp_track per record with its track's state after the frame: voted_class = argmax of acc (ties: lower
+ *              class), voted_conf = acc[voted_class] / wsum (0 unless wsum > 0).
+ * A kept count outside 0..max_det is clamped to that range.  Like every kernel of the library the tracker flushes fp32
+ * denormals to zero, inputs and results: a vote that vote_decay has shrunk below 2^-126 (0.9: after ~800 matched frames
+ * without a vote for that class) counts as 0.  DESIGN.md 6d. */
+typedef struct lp_track_config {
+  int n_streams;      /* 1..1024 independent frame sequences (cameras) */
+  int max_tracks;     /* 1..256 live tracks per stream */
+  float iou_match;    /* 0 <= v < 1; a detection matches a track when IoU > iou_match (default 0.3) */
+  int max_age;        /* >= 0; a track unmatched for MORE than max_age consecutive frames is freed (default 5) */
+  int min_hits;       /* >= 1; flag bit 0 (confirmed) once hits >= min_hits (default 3) */
+  float new_conf;     /* an unmatched detection starts a track when det_conf >= new_conf (default 0) */
+  float vote_decay;   /* 0 < d <= 1 (default 1) */
+  int class_gate;     /* 0/1: a match needs equal det_class (default 1) */
+  int motion;         /* 0 = predicted box is the last box; 1 = constant velocity (default 1) */
+  int reserved[7];    /* zero */
+} lp_track_config;
+
+/* 32 bytes, parallel to lp_det: record i of frame b describes dets[b*max_det+i].  A struct tag only (write `struct lp_track`):
+ * the plain name is the entry point lp_track() below, and C keeps typedef names and functions in one name space. */
+struct lp_track {
+  int32_t track_id;    /* >= 1; 0 = untracked (below new_conf, or the table was full) */
+  int32_t slot;        /* table slot 0..max_tracks-1, -1 when untracked */
+  int32_t hits;        /* frames in which the track was matched, birth included */
+  int32_t age;         /* frames since birth, 0 in the birth frame */
+  int32_t voted_class; /* -1 while the track has no vote */
+  float   voted_conf;  /* acc[voted_class] / wsum, 0 with no vote */
+  float   vote_weight; /* wsum */
+  int32_t flags;       /* bit 0 confirmed, bit 1 born in this frame */
+};
+typedef struct lp_track lp_track_rec;   /* the record type under a plain name */
+#define LP_TRACK_CONFIRMED 1
+#define LP_TRACK_BORN 2
+
+typedef struct lp_track_state {   /* 64 bytes: one live track of lp_tracker_snapshot */
+  int32_t slot, track_id;
+  float x1, y1, x2, y2;           /* last matched box */
+  float vx1, vy1, vx2, vy2;       /* velocity per frame of each coordinate */
+  int32_t hits, missed, age, det_class;
+  float wsum;
+  int32_t has_vote;               /* 0 until a detection with a classifier result was matched */
+} lp_track_state;
+
+void lp_track_default_config(lp_track_config* cfg);
+/* pure host, no handle, no device: LP_ERR_ARG for a value outside the ranges above, a non-zero reserved word or NULL */
+int lp_track_config_check(const lp_track_config* cfg);
+/* one tracker per handle; calling it again replaces the tracker and restarts the ids at 1 */
+int lp_tracker_create(lp_handle* h, const lp_track_config* cfg);
+int lp_tracker_destroy(lp_handle* h);   /* also done by lp_destroy */
+/* frees the tracks of one stream (-1: of all); next_id keeps counting, so an id is never reused during a tracker's life.
+ * Asynchronous on the handle's stream. */
+int lp_tracker_reset(lp_handle* h, int stream);
+/* dev_dets [B*max_det] lp_det and dev_counts (kept counts = its first B words) as lp_run_batch_device / lp_run_tiled_device
+ * wrote them; stream_ids: HOST array of B ints (NULL: every frame belongs to stream 0), read before the call returns;
+ * dev_tracks [B*max_det] lp_track, of which only the first count[b] records of frame b are written.  Asynchronous on the
+ * handle's stream, i.e. ordered behind the pipeline call with no event; any number of calls may be enqueued without a
+ * synchronise in between.  LP_ERR_STATE without a tracker; LP_ERR_ARG for B outside 1..max_batch, a stream id outside
+ * 0..n_streams-1 or record buffers that are not 16-byte aligned, before anything is enqueued. */
+int lp_track_device(lp_handle* h, const void* dev_dets, const void* dev_counts, int B, const int* stream_ids, void* dev_tracks);
+/* the same on host records as lp_run_batch / lp_run_tiled return them (uploads, runs the same kernel, downloads; synchronous) */
+int lp_track(lp_handle* h, const lp_det* dets, const int* counts, int B, const int* stream_ids, struct lp_track* tracks);
+/* synchronises; the live tracks of a stream in slot order, coasting ones included: *n their number, out (may be NULL: count
+ * only; cap < *n is LP_ERR_ARG) their state, acc (may be NULL) the [*n, num_classes] vote accumulators, next_id / overflow
+ * (may be NULL) the stream's next id and the number of detections that found the table full */
+int lp_tracker_snapshot(lp_handle* h, int stream, lp_track_state* out, int cap, int* n, float* acc, int* next_id, int* overflow);
+
 /* ---- classifier alone ------------------------------------------------------------ */
 /* replaces PyTorchClassifier.predict_batch (e2e.py:378-396) for R host BGR crops of
  * individual sizes: ids [R], probs [R*num_classes] (softmax). */

@@ -150,6 +150,37 @@ struct CscCoef { int cy, cvr, cug, cvg, cub; };   // 20-bit fixed point (include
 // B frames in one launch; max_blocks = the largest (h / 2) * ceil(w / 16) of the table (2-row x 16-pixel blocks of a frame)
 void launch_nv12_to_bgr(const uint8_t* src, const CscFrame* frames, uint8_t* dst, int B, int max_blocks, int matrix, hipStream_t st);
 
+// ---- track_kernels.hip (sign tracking across frames, include/litepi.h lp_track_*) --------------
+typedef struct lp_track TrackRec;   // (the plain name is the entry point)
+struct TrackSlot {     // one slot of a stream's track table, 64 bytes, device resident between calls
+  float box[4], vel[4];
+  int id, hits, missed, age, det_class;
+  float wsum;
+  int has_vote, live;
+};
+struct TrackHead { int next_id, overflow, pad[2]; };   // per stream
+struct TrackJob { int stream, first, nframes, pad; };  // one workgroup: frames[first .. first + nframes) of the call's frame list
+#define LP_TRACK_KEY_LDS 1024   // detections of a frame whose sort key / assignment live in LDS; a larger frame uses `scratch`
+struct TrackArgs {
+  const lp_det* dets;       // [B * max_det]
+  const int* counts;        // [B] kept counts
+  TrackRec* out;            // [B * max_det]
+  const TrackJob* jobs;     // [n_jobs]
+  const int* frames;        // batch indices of the call's frames, grouped by job
+  TrackSlot* table;         // [n_streams][T]
+  TrackHead* heads;         // [n_streams]
+  float* acc;               // [n_streams][T][nc] vote accumulators
+  unsigned* scratch;        // [n_jobs capacity][2][max_det] when max_det > LP_TRACK_KEY_LDS, else null
+  int max_det, T, nc;
+  float iou_match;
+  int max_age, min_hits;
+  float new_conf, decay;
+  int class_gate, motion;
+};
+void launch_track(const TrackArgs& a, int n_jobs, hipStream_t st);
+// frees every slot of `n` streams from `first` on (next_id and the overflow counter stay)
+void launch_track_reset(TrackSlot* table, int T, int first, int n, hipStream_t st);
+
 // ---- cls_kernels.hip ------------------------------------------------------------------
 // conv1 3x3/s2 (3->CO) + folded BN + ReLU on (x/255 - mean)/std of the uint8 RGB crops
 void launch_cls_stem(int prec, const uint8_t* rgb, const float* w /*[27][CO]*/, const float* bias, int CO,

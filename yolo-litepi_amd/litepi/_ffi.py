@@ -50,6 +50,31 @@ class LpFrameFormat(C.Structure):
                 ("frame_stride", C.c_int64), ("reserved", C.c_int * 6)]
 
 
+class LpTrackConfig(C.Structure):
+    _fields_ = [("n_streams", C.c_int), ("max_tracks", C.c_int), ("iou_match", C.c_float), ("max_age", C.c_int),
+                ("min_hits", C.c_int), ("new_conf", C.c_float), ("vote_decay", C.c_float), ("class_gate", C.c_int),
+                ("motion", C.c_int), ("reserved", C.c_int * 7)]
+
+
+class LpTrack(C.Structure):
+    _fields_ = [("track_id", C.c_int32), ("slot", C.c_int32), ("hits", C.c_int32), ("age", C.c_int32), ("voted_class", C.c_int32),
+                ("voted_conf", C.c_float), ("vote_weight", C.c_float), ("flags", C.c_int32)]
+
+
+class LpTrackState(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("track_id", C.c_int32), ("x1", C.c_float), ("y1", C.c_float), ("x2", C.c_float), ("y2", C.c_float),
+                ("vx1", C.c_float), ("vy1", C.c_float), ("vx2", C.c_float), ("vy2", C.c_float), ("hits", C.c_int32),
+                ("missed", C.c_int32), ("age", C.c_int32), ("det_class", C.c_int32), ("wsum", C.c_float), ("has_vote", C.c_int32)]
+
+
+LP_TRACK_CONFIRMED, LP_TRACK_BORN = 1, 2
+# numpy views of lp_track records and of lp_track_state
+TRACK_DTYPE = [("track_id", "<i4"), ("slot", "<i4"), ("hits", "<i4"), ("age", "<i4"), ("voted_class", "<i4"), ("voted_conf", "<f4"),
+               ("vote_weight", "<f4"), ("flags", "<i4")]
+TRACK_STATE_DTYPE = [("slot", "<i4"), ("track_id", "<i4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("vx1", "<f4"),
+                     ("vy1", "<f4"), ("vx2", "<f4"), ("vy2", "<f4"), ("hits", "<i4"), ("missed", "<i4"), ("age", "<i4"),
+                     ("det_class", "<i4"), ("wsum", "<f4"), ("has_vote", "<i4")]
+
 # numpy view of lp_det records
 DET_DTYPE = [("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("det_conf", "<f4"), ("det_class", "<i4"),
              ("cls_class", "<i4"), ("cls_conf", "<f4")]
@@ -62,6 +87,8 @@ SYMBOLS = [
     "lp_comm_unique_id", "lp_comm_init", "lp_gather", "lp_comm_destroy",
     "lp_tile_grid", "lp_run_tiled", "lp_run_tiled_device", "lp_test_nms_views", "lp_test_tile_views",
     "lp_frame_layout", "lp_set_input_format", "lp_test_convert_frames",
+    "lp_track_default_config", "lp_track_config_check", "lp_tracker_create", "lp_tracker_destroy", "lp_tracker_reset",
+    "lp_track_device", "lp_track", "lp_tracker_snapshot",
 ]
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
 
@@ -123,8 +150,18 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_frame_layout.argtypes = [ffp, C.c_int, C.c_int, i64p, i64p]
     lib.lp_set_input_format.argtypes = [vp, ffp]
     lib.lp_test_convert_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ffp, C.c_int, vp]
+    tcp = C.POINTER(LpTrackConfig)
+    lib.lp_track_default_config.argtypes = [tcp]
+    lib.lp_track_default_config.restype = None
+    lib.lp_track_config_check.argtypes = [tcp]
+    lib.lp_tracker_create.argtypes = [vp, tcp]
+    lib.lp_tracker_destroy.argtypes = [vp]
+    lib.lp_tracker_reset.argtypes = [vp, C.c_int]
+    lib.lp_track_device.argtypes = [vp, vp, vp, C.c_int, ip, vp]
+    lib.lp_track.argtypes = [vp, vp, ip, C.c_int, ip, vp]
+    lib.lp_tracker_snapshot.argtypes = [vp, C.c_int, vp, C.c_int, ip, vp, ip, ip]
     for s in SYMBOLS:
-        if s not in ("lp_last_error", "lp_default_config", "lp_destroy"):
+        if s not in ("lp_last_error", "lp_default_config", "lp_destroy", "lp_track_default_config"):
             getattr(lib, s).restype = C.c_int
     got = lib.lp_version()
     if got != ABI_VERSION:

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _ffi
-from ._ffi import DET_DTYPE, LpConfig, LpFrameFormat, LpKernelTime, LpTiming, LpTiling, check
+from ._ffi import DET_DTYPE, TRACK_DTYPE, TRACK_STATE_DTYPE, LpConfig, LpFrameFormat, LpKernelTime, LpTiming, LpTiling, LpTrackConfig, check
 from .pixfmt import CSC_MATRICES, PIXEL_FORMATS, nv12_frame_hw
 
 _PREC = {"fp32": _ffi.LP_FP32, "fp16": _ffi.LP_FP16, "float32": _ffi.LP_FP32, "float16": _ffi.LP_FP16, "half": _ffi.LP_FP16}
@@ -76,6 +76,27 @@ def tile_grid(det_input: int, H: int, W: int, overlap: int = 128, full_frame: bo
     buf = (C.c_int * (4 * n.value))()
     check(lib, lib.lp_tile_grid(int(det_input), C.byref(t), int(H), int(W), C.byref(n), buf, n.value))
     return [tuple(buf[4 * i:4 * i + 4]) for i in range(n.value)]
+
+
+TRACK_CONFIG_FIELDS = ("n_streams", "max_tracks", "iou_match", "max_age", "min_hits", "new_conf", "vote_decay", "class_gate", "motion")
+
+
+def track_config(**cfg) -> LpTrackConfig:
+    """lp_track_config with the library's defaults (lp_track_default_config) and the given fields (host only, no GPU needed)."""
+    lib = _ffi.load_library()
+    c = LpTrackConfig()
+    lib.lp_track_default_config(C.byref(c))
+    for k, v in cfg.items():
+        if k not in TRACK_CONFIG_FIELDS:
+            raise TypeError(f"unknown tracker setting {k!r} (one of {TRACK_CONFIG_FIELDS})")
+        setattr(c, k, v)
+    return c
+
+
+def track_config_check(cfg: Optional[LpTrackConfig]) -> int:
+    """lp_track_config_check's status for a configuration (host only, no GPU needed)."""
+    lib = _ffi.load_library()
+    return lib.lp_track_config_check(C.byref(cfg) if cfg is not None else None)
 
 
 class Engine:
@@ -236,6 +257,64 @@ class Engine:
         t = _tiling(overlap, full_frame)
         check(self.lib, self.lib.lp_run_tiled_device(self._h, C.c_void_p(dev_imgs), B, H, W, C.byref(t), conf, iou, int(min_area),
                                                      C.c_void_p(dev_dets), C.c_void_p(dev_counts)))
+
+    # ---- sign tracking across frames ----------------------------------------------------------
+    def tracker_create(self, **cfg) -> None:
+        """One tracker per engine (lp_tracker_create); calling it again replaces the tracker and restarts the ids.  Settings are
+        lp_track_config's fields: n_streams, max_tracks, iou_match, max_age, min_hits, new_conf, vote_decay, class_gate, motion."""
+        c = track_config(**cfg)
+        check(self.lib, self.lib.lp_tracker_create(self._h, C.byref(c)))
+        self.track_cfg = c
+
+    def tracker_destroy(self) -> None:
+        check(self.lib, self.lib.lp_tracker_destroy(self._h))
+        if hasattr(self, "track_cfg"):
+            del self.track_cfg
+
+    def tracker_reset(self, stream: int = -1) -> None:
+        """Frees the tracks of one stream (-1: all); ids keep counting.  Asynchronous on the engine's stream."""
+        check(self.lib, self.lib.lp_tracker_reset(self._h, int(stream)))
+
+    def _stream_ids(self, stream_ids, B: int):
+        if stream_ids is None:
+            return None
+        ids = np.ascontiguousarray(stream_ids, dtype=np.int32)
+        if ids.shape != (B,):
+            raise ValueError(f"stream_ids must hold one id per frame ({B}), got shape {ids.shape}")
+        return ids
+
+    def track(self, dets: np.ndarray, counts, stream_ids=None) -> np.ndarray:
+        """lp_track on host records as run_batch / run_tiled return them: dets [B, max_det] lp_det records, counts [B] ->
+        [B, max_det] lp_track records (TRACK_DTYPE), zero beyond a frame's count.  Synchronous."""
+        d = np.ascontiguousarray(dets, dtype=DET_DTYPE).reshape(-1, self.cfg.max_det)
+        B = d.shape[0]
+        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+        if cnt.shape != (B,):
+            raise ValueError(f"counts must hold one count per frame ({B}), got shape {cnt.shape}")
+        ids = self._stream_ids(stream_ids, B)
+        out = np.zeros((B, self.cfg.max_det), dtype=TRACK_DTYPE)
+        ip = C.POINTER(C.c_int)
+        check(self.lib, self.lib.lp_track(self._h, d.ctypes.data, cnt.ctypes.data_as(ip), B, None if ids is None else ids.ctypes.data_as(ip),
+                                          out.ctypes.data))
+        return out
+
+    def track_device(self, dev_dets: int, dev_counts: int, B: int, dev_tracks: int, stream_ids=None) -> None:
+        """lp_track_device: consumes the records run_batch_device / run_tiled_device left at dev_dets / dev_counts and writes
+        [B * max_det] lp_track records at dev_tracks.  Asynchronous on the engine's stream."""
+        ids = self._stream_ids(stream_ids, B)
+        check(self.lib, self.lib.lp_track_device(self._h, C.c_void_p(dev_dets), C.c_void_p(dev_counts), int(B),
+                                                 None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int)), C.c_void_p(dev_tracks)))
+
+    def tracker_snapshot(self, stream: int = 0) -> Dict[str, object]:
+        """The live tracks of a stream in slot order, coasting ones included (synchronises): {"tracks": TRACK_STATE_DTYPE records,
+        "acc": [n, num_classes] vote accumulators, "next_id", "overflow"}."""
+        n, nid, ovf = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib, self.lib.lp_tracker_snapshot(self._h, int(stream), None, 0, C.byref(n), None, C.byref(nid), C.byref(ovf)))
+        st = np.zeros(n.value, dtype=TRACK_STATE_DTYPE)
+        acc = np.zeros((n.value, max(self.cfg.num_classes, 1)), np.float32)
+        check(self.lib, self.lib.lp_tracker_snapshot(self._h, int(stream), st.ctypes.data, n.value, C.byref(n), acc.ctypes.data,
+                                                     C.byref(nid), C.byref(ovf)))
+        return {"tracks": st, "acc": acc, "next_id": nid.value, "overflow": ovf.value}
 
     def roi_overflow(self) -> Tuple[int, int]:
         """(classified, kept) of the last run_batch_device call (synchronises): kept > classified means max_rois was too small."""
@@ -681,8 +760,11 @@ class HybridPipeline:
                  detector_threads: int = 4, classifier_device: str = "cpu", batch_size: int = 8, *, precision: str = "fp16",
                  max_batch: int = 1, max_det: int = 300, device: int = 0, max_rois: int = 0, numerics: str = "e2e",
                  tile_overlap: Optional[int] = None, tile_full_frame: bool = True, pixel_format: str = "bgr",
-                 csc_matrix: str = "bt601"):
-        """pixel_format: "bgr" = HxWx3 arrays (the reference's cv2 images); "nv12" = video frames as (H * 3 // 2, W) arrays,
+                 csc_matrix: str = "bt601", track: bool = False, track_config: Optional[Dict] = None):
+        """track: run_batch also tracks the detections across calls (lp_track on the engine's tracker, created here with
+        track_config: lp_track_config's fields); every result dict then gains track_id, track_hits, track_age, track_cls,
+        track_cls_conf and track_confirmed.  The frames of consecutive calls are a sequence (per stream id).
+        pixel_format: "bgr" = HxWx3 arrays (the reference's cv2 images); "nv12" = video frames as (H * 3 // 2, W) arrays,
         converted on the device with csc_matrix ("bt601" = cv2's COLOR_YUV2BGR_NV12 constants, "bt709" = HD video).
         tile_overlap: None = every frame is letterboxed to det_input (the reference's behaviour); an int = tiled inference
         (lp_run_tiled): frames larger than det_input are also seen as native-resolution crops overlapping by that many pixels,
@@ -701,6 +783,9 @@ class HybridPipeline:
         self.classifier = PyTorchClassifier(classifier_path, classifier_arch, num_classes, cls_input_size, classifier_device,
                                             _engine=self.engine)
         self.batch_size = batch_size  # kept for signature parity: all ROIs of a call are classified in one pass
+        self.track = bool(track)
+        if self.track or track_config is not None:
+            self.engine.tracker_create(**(track_config or {}))
         # ---- upload lanes (an experiment kept behind LITEPI_DROPIN_LANES=<n>, off by default: measured SLOWER, 3.2-3.6 ms per
         # 64-frame call against 2.7-2.9 for one handle -- four 16-frame passes cost 1.4 ms of kernels instead of 0.9 and four
         # sets of copy workers fight over the cores; the overlap of upload and kernels lives inside lp_run_batch instead, which
@@ -790,8 +875,19 @@ class HybridPipeline:
         return (np.concatenate([p[0] for p in parts], 0), np.concatenate([p[1] for p in parts]),
                 np.concatenate([p[2] for p in parts]), timing)
 
+    def _track(self, dets, counts, stream_ids):
+        """the call's records through the engine's tracker, at most max_batch frames per lp_track call, in frame order"""
+        B, cap = len(counts), self.engine.cfg.max_batch
+        ids = None if stream_ids is None else np.asarray(stream_ids, dtype=np.int32)
+        parts = [self.engine.track(dets[i:i + cap], counts[i:i + cap], None if ids is None else ids[i:i + cap]) for i in range(0, B, cap)]
+        return np.concatenate(parts, 0)
+
     def run_batch(self, images: Sequence[np.ndarray], conf_threshold: float = 0.5, iou_threshold: float = 0.45,
-                  min_area: int = 100) -> List[Tuple[List[Dict], PipelineMetrics]]:
+                  min_area: int = 100, stream_ids=None, track: Optional[bool] = None) -> List[Tuple[List[Dict], PipelineMetrics]]:
+        """stream_ids: the tracker stream of every image (None: all stream 0); track: None = the constructor's setting."""
+        do_track = self.track if track is None else bool(track)
+        if do_track and not hasattr(self.engine, "track_cfg"):
+            raise ValueError("run_batch(track=True) needs a pipeline constructed with track=True or a track_config")
         t0 = time.perf_counter()
         try:
             if self.tile_overlap is not None:
@@ -805,6 +901,7 @@ class HybridPipeline:
                 raise
             print(f"[HIP Pipeline] engine failure, returning no detections: {e}")
             return [([], PipelineMetrics()) for _ in images]
+        tracks = self._track(dets[:len(images)], np.asarray(counts[:len(images)], dtype=np.int32), stream_ids) if do_track else None
         wall_ms = (time.perf_counter() - t0) * 1000.0   # t_total ends here; system metrics are sampled after it (e2e.py:505-516)
         conf_avg = self.engine.last_det_conf_avg
         sysm = _system_metrics()
@@ -831,6 +928,10 @@ class HybridPipeline:
         t_det, t_roi, t_cls, t_tot = timing.t_detection / B, timing.t_roi_extract / B, timing.t_classification / B, wall_ms / B
         fps = 1000.0 / t_tot if t_tot > 0 else 0
         cpu_p, mem_mb, temp = sysm
+        if tracks is not None:
+            tu = tracks[:B][np.arange(tracks.shape[1])[None, :] < cnt_a[:, None]]
+            trk_cols = list(zip(tu["track_id"].tolist(), tu["hits"].tolist(), tu["age"].tolist(), tu["voted_class"].tolist(),
+                                tu["voted_conf"].astype(np.float64).tolist(), ((tu["flags"] & _ffi.LP_TRACK_CONFIRMED) != 0).tolist()))
         out = []
         pos = 0
         for i in range(B):
@@ -847,6 +948,9 @@ class HybridPipeline:
                 e = pos + n
                 results = [{"bbox": bb, "det_class": dc, "det_conf": df, "cls_class": cc, "cls_conf": cf, "time_det": td, "time_cls": tc}
                            for bb, dc, df, cc, cf in zip(boxes[pos:e], det_cls[pos:e], det_cf[pos:e], cls_cls[pos:e], cls_cf[pos:e])]
+                if tracks is not None:
+                    for r, (tid, th, ta, tc_, tcc, tok) in zip(results, trk_cols[pos:e]):
+                        r.update(track_id=tid, track_hits=th, track_age=ta, track_cls=tc_, track_cls_conf=tcc, track_confirmed=tok)
                 pos = e
             out.append((results, m))
         return out

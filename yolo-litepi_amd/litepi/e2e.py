@@ -91,6 +91,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="pixel format of the frames of --raw_frames: packed bgr24, or nv12 (converted on the device)")
     p.add_argument("--csc_matrix", type=str, choices=["bt601", "bt709"], default="bt601",
                    help="YCbCr matrix of nv12 frames (limited range): bt601 = cv2's COLOR_YUV2BGR_NV12, bt709 = HD video")
+    p.add_argument("--track", action="store_true",
+                   help="track the signs across the frames of --raw_frames (a sequence) on the device and write tracks.csv: identity, "
+                        "voted class, hits and confirmation per detection of the benchmark pass")
+    p.add_argument("--track_iou", type=float, default=0.3, help="a detection matches a track when their IoU exceeds this")
+    p.add_argument("--track_max_age", type=int, default=5, help="frames a track may stay unmatched before it is dropped")
+    p.add_argument("--track_min_hits", type=int, default=3, help="matched frames after which a track counts as confirmed")
     p.add_argument("--no_jit", action="store_true", help="accepted and ignored: there is no TorchScript on this path (e2e_optimize.py:884)")
     return p
 
@@ -324,7 +330,18 @@ def evaluate_predictions(all_preds, all_gts, num_classes, iou_threshold=0.5, iou
 
 
 # ------------------------------------------------------------------------------------------------
+TRACKS_CSV_COLUMNS = ("frame", "track_id", "x1", "y1", "x2", "y2", "det_conf", "cls_class", "cls_conf", "voted_class", "voted_conf", "hits",
+                      "confirmed")
+
+
 def check_frame_args(args) -> None:
+    if getattr(args, "track", False):   # tracking needs the frames of ONE sequence, all of them, in order, in one process
+        if not args.raw_frames:
+            raise SystemExit("--track needs --raw_frames: the frames of a raw file are a sequence, the images of --input are not")
+        if args.num_samples:
+            raise SystemExit("--track and --num_samples exclude each other: a sample of the frames is not a sequence")
+        if args.gpus > 1:
+            raise SystemExit(f"--track and --gpus {args.gpus} exclude each other: the shards of a sequence cannot be tracked apart")
     if args.raw_frames and not args.frame_size:
         raise SystemExit("--raw_frames needs --frame_size WxH")
     if args.raw_frames:   # a malformed size or a trailing partial frame is reported before any model is loaded
@@ -343,7 +360,10 @@ def run_evaluation(args) -> Dict:
     from . import distributed as D
 
     check_frame_args(args)
+    args.track = bool(getattr(args, "track", False))
     rank, local_rank, world = D.env_rank_world()
+    if args.track and world > 1:   # a launcher's WORLD_SIZE shards the files as --gpus does
+        raise SystemExit(f"--track runs in one process: the shards of a sequence cannot be tracked apart (WORLD_SIZE is {world})")
     if args.gpus > 1 or world > 1:
         import torch
         import torch.distributed as dist
@@ -379,13 +399,16 @@ def run_evaluation(args) -> Dict:
         max_rois = max_rois if max_rois > 0 else nb * max_det
     import contextlib
     import io
+    # with --track off the pipeline is constructed and called exactly as before
+    track_kw = dict(track=True, track_config=dict(iou_match=args.track_iou, max_age=args.track_max_age, min_hits=args.track_min_hits)) if args.track else {}
+    bench_kw, eval_kw = (dict(track=True), dict(track=False)) if args.track else ({}, {})
     with contextlib.redirect_stdout(io.StringIO()) if rank != 0 else contextlib.nullcontext():   # one banner, rank 0's
         pipeline = HybridPipeline(args.detector_param, args.detector_bin, args.classifier, args.clf_arch, num_classes,
                                   args.det_input_size, args.cls_input_size, False, args.detector_threads, args.device,
                                   args.batch_size, precision=args.precision, max_batch=max_batch, max_det=max_det,
                                   device=args.hip_device, max_rois=max_rois, numerics=args.numerics,
                                   tile_overlap=args.tile_overlap, tile_full_frame=bool(args.tile_full_frame),
-                                  pixel_format=args.pixel_format, csc_matrix=args.csc_matrix)
+                                  pixel_format=args.pixel_format, csc_matrix=args.csc_matrix, **track_kw)
     out_dir = Path(args.output) / combo
     out_dir.mkdir(parents=True, exist_ok=True)
 
@@ -412,12 +435,16 @@ def run_evaluation(args) -> Dict:
     files = files[lo:hi]
 
     all_preds, all_gts, bench_time, names = [], [], 0.0, []
+    track_rows = []
     try:
         n_warm = args.warmup if args.warmup is not None else (10 if args.numerics == "e2e_optimize" else 0)
         if n_warm > 0:   # warmup_pipeline (e2e_optimize.py:552-570): random frame, conf 0.5
             dummy = np.random.randint(0, 255, (960, 640) if args.pixel_format == "nv12" else (640, 640, 3), dtype=np.uint8)
             for _ in range(n_warm):
-                pipeline.run(dummy, conf_threshold=0.5)
+                if args.track:   # the warm-up frames are not part of the sequence: they never reach the tracker
+                    pipeline.run_batch([dummy], 0.5, track=False)
+                else:
+                    pipeline.run(dummy, conf_threshold=0.5)
             say(f"Warmup complete ({n_warm} passes)")
         for i in range(0, len(files), nb):
             chunk, imgs = [], []
@@ -430,9 +457,14 @@ def run_evaluation(args) -> Dict:
                 imgs.append(im)
             if not imgs:
                 continue
-            bench = pipeline.run_batch(imgs, args.benchmark_conf, args.iou_threshold, args.min_area)
+            # the tracker is fed exactly once per frame: by the benchmark pass; the evaluation pass is not tracked
+            bench = pipeline.run_batch(imgs, args.benchmark_conf, args.iou_threshold, args.min_area, **bench_kw)
             bench_time += sum(m.t_total for _, m in bench) / 1000.0
-            ev = bench if args.yolo_conf == args.benchmark_conf else pipeline.run_batch(imgs, args.yolo_conf, args.iou_threshold, args.min_area)
+            ev = bench if args.yolo_conf == args.benchmark_conf else pipeline.run_batch(imgs, args.yolo_conf, args.iou_threshold, args.min_area, **eval_kw)
+            if args.track:
+                for f, (res, _) in zip(chunk, bench):
+                    track_rows += [(f.index, r["track_id"], *r["bbox"], r["det_conf"], r["cls_class"], r["cls_conf"], r["track_cls"],
+                                    r["track_cls_conf"], r["track_hits"], int(r["track_confirmed"])) for r in res]
             for f, im, (res, _) in zip(chunk, imgs, ev):
                 lp = (label_dir / f"{f.stem}.txt") if label_dir else f.parent / "labels" / f"{f.stem}.txt"
                 im_h, im_w = (fh, fw) if raw is not None else im.shape[:2]
@@ -448,6 +480,14 @@ def run_evaluation(args) -> Dict:
                 names.append(f.name)
     finally:
         pipeline.engine.close()
+    if args.track:
+        import csv
+        with open(out_dir / "tracks.csv", "w", newline="") as fcsv:
+            w = csv.writer(fcsv)
+            w.writerow(TRACKS_CSV_COLUMNS)
+            w.writerows(track_rows)
+        confirmed = {r[1] for r in track_rows if r[-1] and r[1] > 0}
+        say(f"Tracking: {len(confirmed)} confirmed tracks over {len(files)} frames ({len(track_rows)} detections) -> {out_dir / 'tracks.csv'}")
     rank_times = [bench_time]
     if world > 1:   # the one exchange of the sharded evaluation: every rank's predictions + ground truths -> rank 0
         import torch.distributed as dist
