@@ -16,6 +16,10 @@
 //            registers, pixel on the lane) IS the B operand of the next MFMA once its rows are rounded to fp16, with the
 //            projection's K order permuted to match (MI355X guide, "an accumulator tile as the next MFMA's operand")
 //   decode   in registers: the projection rows are permuted so that a lane holds the 16 bins of one box side
+// Order: stage A -> class tower's stage B -> class projection and scores -> the workgroup's VOTE (can any anchor of the tile pass
+// conf?) -> only then the box tower's stage B, the box projection and the decode.  A workgroup nobody voted in returns at the vote:
+// the box tower's second conv is 24 - 47 % of a level's MACs and a typical frame has a handful of candidates among 8400 anchors.
+// What is emitted is unchanged to the bit: the vote is emit_candidate's own test, and neither tower's arithmetic or order changes.
 // MFMA: v_mfma_f32_32x32x16_f16, D[out-channel][pixel] = W . X.  A wave computes RT (or 2) row tiles x P pixel tiles per
 // K step: (RT + P) KiB of LDS operands per RT*P MFMAs of 32 cycles = 0.8 - 2 ds_read_b128 per MFMA (two per MFMA and SIMD
 // saturate the LDS); measured, the K loops run at 37-44 cycles per MFMA and are half of a workgroup's cycles -- the rest is
@@ -113,7 +117,7 @@ __device__ __forceinline__ void lds_barrier() {
 //  * SLOTF: fragments (KiB) per ring slot, 24 or 12; a wave owns SLOTF / 4 pieces of every chunk.
 //  * SLOTF == 8 (three workgroups per CU): a ring slot is 64 bytes short of 8 KiB -- the LDS granule is 1280 B and 42 granules
 //    per workgroup are the limit -- and lanes 60..63 of fragment 7 live in four padding slots of MID instead: f7[parity] is
-//    this lane's address of fragment 7, f7_0 / f7_1 by slot parity (only the box tower's chunks have eight fragments).
+//    this lane's address of fragment 7, f7_0 / f7_1 by slot parity (only the box tower's chunks and the box projection's have eight fragments).
 template <int NA, int NB, int KS, bool FIRST, bool LAST, int SLOTF, typename F, typename G>
 __device__ __forceinline__ void kchunk(const char* ring, int c, int lane16, const char* img, const int (&pix)[NB], F&& next_boff, G&& side,
                                        floatx16 (&acc)[NA][NB], half8 (&af)[2][NA], half8 (&bf)[2][NB], const char* f7_0, const char* f7_1) {
@@ -218,7 +222,7 @@ __device__ __forceinline__ void kchunkA16(const char* ring, int c, int lane16, c
 template <int C3T, int PA, int PB, int NPC, int KSA, int SLOTF, int NRW, bool OV = (SLOTF == 8), bool A16 = false, int NCA = 9>
 __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void head_fused_kernel(const HeadArgs a) {
   // SLOTF == 8: THREE workgroups per CU -- MID overlays the input tile (dead after stage A's K loops: one more barrier), 8 KiB
-  // ring slots (the projections are then two chunks), <= 168 registers: 54,272 B of LDS.
+  // ring slots (the projections are then two chunks), <= 168 registers: 53,696 B of LDS (42 granules of 1280 B).
   constexpr int RT = 2 + C3T;       // row tiles (32 channels) of the merged first convs: box 2 | class C3T
   constexpr int SLOT = SLOTF * 1024, NPW = SLOTF / 4;   // chunk stride in the weight stream; 1 KiB pieces per wave and chunk
   constexpr int SLOTB = SLOTF == 8 ? 8192 - 64 : SLOT;   // ring slot stride in LDS (see kchunk)
@@ -358,7 +362,7 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
     wload1(j);
   };
 
-  floatx16 biasB_box[2], biasB_cls[C3T];
+  floatx16 biasB_cls[C3T];
   // ======================= stage A: [64 + 32*C3T] x (9 * Cin) x region-1 pixels =======================
   if constexpr (A16) {
     floatx4 accA[2 * RT][PA];
@@ -397,14 +401,16 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
     HD_STAMP(4)
     if (a.flags & 1) __builtin_amdgcn_s_setprio(0);
     if (a.flags & 2) __builtin_amdgcn_s_setprio(1);
-    // (stage B's biases are requested here: their round trip runs under the SiLU epilogue instead of in front of stage B's first MFMA)
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt) biasB_box[rt] = bias16(a.biasB + rt * 32 + h * 16);
+    // (the class tower's stage-B biases are requested here: their round trip runs under the SiLU epilogue instead of in front of stage
+    //  B's first MFMA; the box tower's are requested behind the vote, by the workgroups that stay)
 #pragma unroll
     for (int rt = 0; rt < C3T; ++rt) biasB_cls[rt] = bias16(a.biasB + 64 + rt * 32 + h * 16);
     // ---- SiLU, fp16, -> MID: this lane holds channels 32t + 8 kg .. + 7 of its pixel in row tiles 2t | 2t+1: one 16-byte store each
     {
       if (OVL) lds_barrier();   // MID overlays the input tile: every wave has read its last stage-A operands
+      // the workgroup's vote word = the padding slot of MID pixel 0 (no MID store or stage-B read touches a padding slot; the
+      // three-per-CU shape keeps ring fragments in those of the LAST eight pixels): cleared here, the class tower's first barrier follows
+      if (tid == 0) *reinterpret_cast<volatile int*>(MID + 4 * RT * 16) = 0;
       const bool interior = oy0 >= 1 && ox0 >= 1 && oy0 + TH + 1 <= a.H && ox0 + TW + 1 <= a.W;  // block-uniform
 #pragma unroll
       for (int p = 0; p < PA; ++p) {
@@ -454,8 +460,8 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
         }
         return boff;
       };
-      // stream = A chunks | box-B chunks | class-B chunks | 1 C
-      const int ncA = nch - (36 / (SLOTF / 2)) - (C3T == 2 ? 36 / (SLOTF / 2) : 18 / (SLOTF >= 18 ? 18 : 6)) - (SLOTF == 8 ? 2 : 1);
+      // stream = A chunks | class-B chunks | class projection | box-B chunks | box projection
+      const int ncA = nch - (36 / (SLOTF / 2)) - (C3T == 2 ? 36 / (SLOTF / 2) : 18 / (SLOTF >= 18 ? 18 : 6)) - 2;
       half8 af[2][RT], bf[2][PA];
       if constexpr (KSA % 2 == 0) {   // one operand pipeline over all of stage A (ncA >= 2, host-checked)
         wsource(c + 2);
@@ -483,6 +489,9 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
     //      so that this lane holds channels 32*rt + 16*h .. +15 of its pixel: two 16-byte stores per row tile.
     {
       if (OVL) lds_barrier();   // MID overlays the input tile: every wave has read its last stage-A operands
+      // the workgroup's vote word = the padding slot of MID pixel 0 (no MID store or stage-B read touches a padding slot; the
+      // three-per-CU shape keeps ring fragments in those of the LAST eight pixels): cleared here, the class tower's first barrier follows
+      if (tid == 0) *reinterpret_cast<volatile int*>(MID + 4 * RT * 16) = 0;
       const bool interior = oy0 >= 1 && ox0 >= 1 && oy0 + TH + 1 <= a.H && ox0 + TW + 1 <= a.W;  // block-uniform
   #pragma unroll
       for (int p = 0; p < PA; ++p) {
@@ -514,11 +523,8 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
   if (a.flags & 1) __builtin_amdgcn_s_setprio(1);
   if (a.flags & 2) __builtin_amdgcn_s_setprio(0);
 
-  // ---- this lane's stage-B pixels; what only the decode needs (anchors, geometry, DFL weights) is requested here, behind
-  //      stage A -- live across it these 30 registers were the difference to the three-workgroup shape's 168 -- and arrives
-  //      during stage B
+  // ---- this lane's stage-B pixels
   int pixB[PB];
-  float anc_x[PB], anc_y[PB], anc_s[PB];
   int anchor_i[PB];
   bool pvalid[PB];
 #pragma unroll
@@ -529,47 +535,16 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
     const int ty = idx / TW, tx = idx - ty * TW;
     pixB[p] = (ty * RW1 + tx) * SPM * 16 + h * 16;
     const int gy = oy0 + ty, gx = ox0 + tx;
-    pvalid[p] = pt < nB && idx0 < R2 && gy < a.H && gx < a.W;
+    pvalid[p] = pt < nB && idx0 < R2 && gy < a.H && gx < a.W;   // (false for the clamped duplicate lanes, idx0 >= R2)
     anchor_i[p] = a.anchor_off + (pvalid[p] ? gy * a.W + gx : 0);
-    anc_x[p] = a.anchors[anchor_i[p]];
-    anc_y[p] = a.anchors[a.A + anchor_i[p]];
-    anc_s[p] = a.strides[anchor_i[p]];
-  }
-  const ImgGeom gm = a.geom[n];
-  float dflw[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) dflw[i] = a.dfl_w[i];
-
-  // ======================= stage B, box tower: 64 x (9 * 64) x tile pixels =======================
-  floatx16 accB[2][PB];
-#pragma unroll
-  for (int rt = 0; rt < 2; ++rt) {
-    const floatx16 b = A16 ? biasB_box[rt] : bias16(a.biasB + rt * 32 + h * 16);
-#pragma unroll
-    for (int p = 0; p < PB; ++p) accB[rt][p] = b;
   }
   int tapB[9];   // byte offset of tap (dy, dx) in MID
 #pragma unroll
   for (int t = 0; t < 9; ++t) tapB[t] = ((t / 3) * RW1 + (t % 3)) * SPM * 16;
-  {
-    // three chunks of 12 steps, one pipeline; tap and channel group of every step are immediates after unrolling.  (The
-    // first barrier also orders the MID stores before the reads.)
-    int kq = 0;
-    auto next_boff = [&]() {
-      const int boff = tapB[kq >> 2] + (kq & 3) * 32;
-      ++kq;
-      return boff;
-    };
-    half8 af[2][2], bf[2][PB];
-    constexpr int KSB = SLOTF / 2, NCB = 36 / KSB;   // 36 K steps (9 taps x 4 channel groups), two row tiles: SLOTF / 2 steps per chunk
-    static_for<0, NCB>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      wsource(c + 2);
-      kchunk<2, PB, KSB, i == 0, i == NCB - 1, SLOTF>(RING, c, lane16, MID, pixB, next_boff, ring_side, accB, af, bf, f7_0, f7_1);
-      ++c;
-    });
-  }
-  HD_STAMP(6)
+
+  // The class tower runs FIRST: its projection's best score decides whether any anchor of the tile can become a candidate, and a
+  // workgroup whose tile holds none leaves in front of the box tower (36 K steps x 2 row tiles: 24 - 47 % of a level's MACs).  A
+  // typical frame has a handful of candidates among 8400 anchors, so most workgroups leave.
   // ======================= stage B, class tower: (32*C3T) x (9 * 32*C3T) x tile pixels =======================
   floatx16 accC[C3T][PB];
 #pragma unroll
@@ -596,32 +571,17 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
       ++c;
     });
   }
-  // ======================= stage C: the 1x1 projections from the accumulators, then decode =======================
-  HD_STAMP(7)
+  // ======================= class projection from the accumulators, scores, the workgroup's vote =======================
+  HD_STAMP(6)
   if (a.flags & 1) __builtin_amdgcn_s_setprio(0);
   if (a.flags & 2) __builtin_amdgcn_s_setprio(1);
-  half8 wcb[2][4], wcc[2 * C3T];
-  if constexpr (SLOTF == 8) {
-    // two projection chunks: the class projection (chunk c, stored behind the class tower's steps), then the box projection
-    // (chunk c + 1: its pieces are in wreg; the slot it goes to held the class tower's last chunk, which every wave has left)
-    lds_barrier();
+  half8 wcc[2 * C3T];
+  {
+    lds_barrier();   // the class projection's chunk (c) was stored behind the class tower's steps
     const char* wc = RING + (c & 1) * SLOTB + lane16;
 #pragma unroll
     for (int q = 0; q < 2 * C3T; ++q) wcc[q] = lds_h8(wc + q * 1024);
-#pragma unroll
-    for (int j = 0; j < NPW; ++j) wstore1(c + 1, j);
-    lds_barrier();   // (publishes the box projection's slot: its fragments are read only where an anchor can pass, below)
-  } else {
-    lds_barrier();   // the projection chunk was stored behind the class tower's steps
-    const char* wb = RING + (c & 1) * SLOT + lane16;
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) wcb[rt][q] = lds_h8(wb + (rt * 4 + q) * 1024);
-#pragma unroll
-    for (int q = 0; q < 2 * C3T; ++q) wcc[q] = lds_h8(wb + (8 + q) * 1024);
   }
-  HD_STAMP(8)
   // class bias: two wave-uniform 16-float rows (scalar loads, no vector-memory round trip in front of the projection) + a select
   floatx16 bCc;
   if (a.nc == 1) {   // wave-uniform: only logit 0 is ever looked at; its bias was requested at the top of the kernel
@@ -631,11 +591,12 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
   } else {
     bCc = bias16(a.biasC + 64 + h * 16);
   }
-  bool box_w_loaded = SLOTF != 8;
+  float best[PB];     // all that the decode keeps of the class tower: the best class of the lane's anchor and its score
+  int best_c[PB];
+  bool vote = false;
 #pragma unroll
   for (int p = 0; p < PB; ++p) {
     // B operands: element j of K step (mt, s) of this lane = channel 32*mt + 16*h + 8*s + j = accumulator register 8*s + j
-    // ---- class projection first: its best score decides whether the anchor can become a candidate at all
     floatx16 oc = bCc;
 #pragma unroll
     for (int mt = 0; mt < C3T; ++mt)
@@ -644,7 +605,7 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
     // class scores: this lane holds the logits of classes 16*h .. 16*h + 15.  The sigmoid is monotonic: the best class is the
     // arg-max of the LOGITS (selects, no branches, no transcendentals), and one sigmoid gives its score.
     float bl = -INFINITY;
-    int best_c = 0;
+    int bc = 0;
     if (a.nc == 1) {   // wave-uniform: the one class (the reference's detectors) needs no arg-max
       bl = h == 0 ? oc[0] : -INFINITY;
     } else {
@@ -653,27 +614,105 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
         const float v = (16 * h + i < a.nc) ? oc[i] : -INFINITY;
         const bool up = v > bl;   // strict: the first maximum in class order stays
         bl = up ? v : bl;
-        best_c = up ? 16 * h + i : best_c;
+        bc = up ? 16 * h + i : bc;
       }
       const float obl = __shfl_xor(bl, 32);
-      const int oc_ = __shfl_xor(best_c, 32);
-      if (h == 0 && obl > bl) { bl = obl; best_c = oc_; }   // the upper half wins only if larger
+      const int oc_ = __shfl_xor(bc, 32);
+      if (h == 0 && obl > bl) { bl = obl; bc = oc_; }   // the upper half wins only if larger
     }
-    const float best = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(bl * -1.4426950408889634f));
-    // ---- box projection + DFL decode only where it can matter: emit_candidate keeps an anchor iff best > conf (the same
-    //      expression, so the kept set is identical), and a typical image has a handful of such anchors among 8400 -- the box
-    //      tower's projection (8 of this loop's 10 MFMAs), its 32 SiLUs and the two 16-bin softmaxes per lane are most of
-    //      stage C's cycles.  Wave-uniform branch; the parity hook (out0) needs every anchor and takes it always.
-    const bool pass = pvalid[p] && h == 0 && best > a.conf;
+    best[p] = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(bl * -1.4426950408889634f));
+    best_c[p] = bc;
+    if (a.out0 && pvalid[p]) {   // parity hook only (lp_detect_raw): the whole score rows
+      float* o = a.out0 + (long)n * (4 + a.nc) * a.A + anchor_i[p];
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (16 * h + i < a.nc) o[(long)(4 + 16 * h + i) * a.A] = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(oc[i] * -1.4426950408889634f));
+    }
+    // the vote: emit_candidate keeps an anchor iff best > conf -- the same expression, so a tile that holds a kept anchor never
+    // leaves; the clamped duplicate lanes (pvalid false) and the upper lane half (its score is in the lower one) do not vote
+    vote = vote || (pvalid[p] && h == 0 && best[p] > a.conf);
+  }
+  // One LDS word per workgroup, cleared in front of the MID stores: a wave with a passing anchor sets it, everybody reads it behind the barrier.
+  // (lds_barrier, not __syncthreads: the ring's global loads stay in flight.)  The decision is workgroup-uniform, and no barrier
+  // follows on the path of those who leave: all four waves return together.  The parity hook needs every anchor and never leaves.
+  volatile int* vote_word = reinterpret_cast<volatile int*>(MID + 4 * RT * 16);
+  if (__any(vote) && lane == 0) *vote_word = 1;
+  lds_barrier();
+  const bool stay = a.out0 != nullptr || __builtin_amdgcn_readfirstlane(*vote_word) != 0;
+  HD_STAMP(7)
+  if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 16 + 14] = stay ? 0 : 1;
+  if (!stay) {   // the ring pieces still in flight into wreg are abandoned
+    HD_STAMP(15)
+    return;
+  }
+  // ---- hand-off across the projection chunk: box-tower chunk 0 (c + 1) is in wreg -- requested behind the class tower's last steps --
+  //      and goes to the slot that held the class tower's last chunk, which every wave left at the barrier above; the chunk after it
+  //      is requested, and the box tower's pipeline starts with a barrier of its own (FIRST) that publishes the slot
+#pragma unroll
+  for (int j = 0; j < NPW; ++j) wstore1(c + 1, j);
+  wsource(c + 2);
+#pragma unroll
+  for (int j = 0; j < NPW; ++j) wload1(j);
+  ++c;
+  // what only the decode needs (anchors, geometry, DFL weights) is requested here and arrives during the box tower
+  float anc_x[PB], anc_y[PB], anc_s[PB];
+#pragma unroll
+  for (int p = 0; p < PB; ++p) {
+    anc_x[p] = a.anchors[anchor_i[p]];
+    anc_y[p] = a.anchors[a.A + anchor_i[p]];
+    anc_s[p] = a.strides[anchor_i[p]];
+  }
+  const ImgGeom gm = a.geom[n];
+  float dflw[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) dflw[i] = a.dfl_w[i];
+  if (a.flags & 1) __builtin_amdgcn_s_setprio(1);
+  if (a.flags & 2) __builtin_amdgcn_s_setprio(0);
+
+  // ======================= stage B, box tower: 64 x (9 * 64) x tile pixels =======================
+  floatx16 accB[2][PB];
+#pragma unroll
+  for (int rt = 0; rt < 2; ++rt) {
+    const floatx16 b = bias16(a.biasB + rt * 32 + h * 16);
+#pragma unroll
+    for (int p = 0; p < PB; ++p) accB[rt][p] = b;
+  }
+  {
+    // three chunks of 12 steps, one pipeline; tap and channel group of every step are immediates after unrolling
+    int kq = 0;
+    auto next_boff = [&]() {
+      const int boff = tapB[kq >> 2] + (kq & 3) * 32;
+      ++kq;
+      return boff;
+    };
+    half8 af[2][2], bf[2][PB];
+    constexpr int KSB = SLOTF / 2, NCB = 36 / KSB;   // 36 K steps (9 taps x 4 channel groups), two row tiles: SLOTF / 2 steps per chunk
+    static_for<0, NCB>([&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+      wsource(c + 2);
+      kchunk<2, PB, KSB, i == 0, i == NCB - 1, SLOTF>(RING, c, lane16, MID, pixB, next_boff, ring_side, accB, af, bf, f7_0, f7_1);
+      ++c;
+    });
+  }
+  // ======================= box projection from the accumulators, then decode =======================
+  HD_STAMP(8)
+  if (a.flags & 1) __builtin_amdgcn_s_setprio(0);
+  if (a.flags & 2) __builtin_amdgcn_s_setprio(1);
+  half8 wcb[2][4];
+  {
+    lds_barrier();   // the box projection's chunk (c) was stored behind the box tower's steps
+    const char* wb = RING + (c & 1) * SLOTB + lane16;
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) wcb[rt][q] = lds_h8(rt * 4 + q == 7 ? ((c & 1) ? f7_1 : f7_0) : wb + (rt * 4 + q) * 1024);
+  }
+#pragma unroll
+  for (int p = 0; p < PB; ++p) {
+    // ---- box projection + DFL decode only where it can matter: in a workgroup that stays, a wave skips the pixel tiles none of
+    //      whose anchors can pass (wave-uniform branch; the parity hook takes every tile)
+    const bool pass = pvalid[p] && h == 0 && best[p] > a.conf;
     if (a.out0 == nullptr && !__any(pass)) continue;
-    if (SLOTF == 8 && !box_w_loaded) {   // wave-uniform; a typical wave never gets here (no anchor of its tile can pass)
-      box_w_loaded = true;
-      const char* wb = RING + ((c + 1) & 1) * SLOTB + lane16;
-#pragma unroll
-      for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) wcb[rt][q] = lds_h8(rt * 4 + q == 7 ? (((c + 1) & 1) ? f7_1 : f7_0) : wb + (rt * 4 + q) * 1024);
-    }
     floatx16 ob[2];
     ob[0] = bias16(a.biasC + h * 16); ob[1] = bias16(a.biasC + 32 + h * 16);
 #pragma unroll
@@ -705,22 +744,15 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
     }
     const float x0 = __shfl_xor(dist[0], 32), x1 = __shfl_xor(dist[1], 32);
     const float d0 = h ? x0 : dist[0], d1 = h ? dist[0] : x0, d2 = h ? x1 : dist[1], d3 = h ? dist[1] : x1;
-    if (pvalid[p]) {
+    if (pvalid[p] && h == 0) {
       const int anchor = anchor_i[p];
       float* o = a.out0 ? a.out0 + (long)n * (4 + a.nc) * a.A + anchor : nullptr;
-      if (o) {   // parity hook only (lp_detect_raw): the whole score rows
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-          if (16 * h + i < a.nc) o[(long)(4 + 16 * h + i) * a.A] = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(oc[i] * -1.4426950408889634f));
-      }
-      if (h == 0) {
-        const float ax = anc_x[p], ay = anc_y[p], s = anc_s[p];
-        const float bx1 = ax - d0, by1 = ay - d1, bx2 = ax + d2, by2 = ay + d3;
-        const float cx = (bx1 + bx2) * 0.5f * s, cy = (by1 + by2) * 0.5f * s;
-        const float w = (bx2 - bx1) * s, hh = (by2 - by1) * s;
-        if (o) { o[0] = cx; o[(long)a.A] = cy; o[2L * a.A] = w; o[3L * a.A] = hh; }
-        emit_candidate(cx, cy, w, hh, best, best_c, anchor, gm, a.conf, a.cand + (long)n * a.A, a.cand_count + n);
-      }
+      const float ax = anc_x[p], ay = anc_y[p], s = anc_s[p];
+      const float bx1 = ax - d0, by1 = ay - d1, bx2 = ax + d2, by2 = ay + d3;
+      const float cx = (bx1 + bx2) * 0.5f * s, cy = (by1 + by2) * 0.5f * s;
+      const float w = (bx2 - bx1) * s, hh = (by2 - by1) * s;
+      if (o) { o[0] = cx; o[(long)a.A] = cy; o[2L * a.A] = w; o[3L * a.A] = hh; }
+      emit_candidate(cx, cy, w, hh, best[p], best_c[p], anchor, gm, a.conf, a.cand + (long)n * a.A, a.cand_count + n);
     }
   }
   HD_STAMP(9)
@@ -734,6 +766,7 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
 // half h then holds channels 16*h .. 16*h+15 in its 16 registers
 static inline int row_channel(int rho) { return 16 * ((rho >> 2) & 1) + 4 * (rho >> 3) + (rho & 3); }
 
+// (the workgroup's vote word needs no bytes of its own: it is the padding slot of MID pixel 0)
 static size_t head_lds(int th, int tw, int kpt, int c3t, int slotf, int ovl) {
   const size_t in = ((size_t)(th + 4) * (tw + 4) * (2 * kpt + 1) * 16 + 1023) & ~(size_t)1023;
   const size_t mid = ((size_t)(th + 2) * (tw + 2) * (4 * (2 + c3t) + 1) * 16 + 1023) & ~(size_t)1023;
@@ -755,7 +788,7 @@ static size_t head_lds(int th, int tw, int kpt, int c3t, int slotf, int ovl) {
 // registers; round 2).  slotf 8: THREE per CU (round 3: 98 us per launch against 112): MID overlays the input tile, 8-fragment
 // slots 64 bytes short of 8 KiB (the LDS granule is 1280 B: 42 granules = 53,760 B per workgroup is the limit, measured with
 // tools/ubench/lds_occupancy.hip; MID + two whole slots would be 53,824), the projections as two chunks, and 168 registers --
-// reached by requesting what only the decode needs (anchors, geometry, DFL weights) after stage A instead of before it.
+// reached by requesting what only the decode needs (anchors, geometry, DFL weights) late: behind stage A at first, now behind the vote.
 struct HeadCfg { int c3t, kpt, th, tw, pa, pb, npc, ksa, slotf, ovl, a16; };
 // a16 (round 4): stage A on 16x16x32 MFMAs -- pa counts 16-pixel tiles per wave, ksa half-steps per chunk (one tap per chunk)
 static const HeadCfg kHeadCfg[] = {
@@ -801,7 +834,7 @@ void HeadLayer::build(int cin_phys, int c3_, int nc_, int h, int w, int batch_hi
   lds_bytes = head_lds(TH, TW, KPT, C3T, SLOTF, OVL);
   const int RT = 2 + C3T, CM = 32 * C3T;
   // chunks hold at most 24 fragments (one ring slot): stage A KSA K steps x RT row tiles, stage B box 12 x 2, class 18 x 1
-  // (12 x 2 for two class row tiles), projections 10 (12)
+  // (12 x 2 for two class row tiles), projections 2 (4) and 8
   LP_CHECK(KSA % 2 != 0 || 9 * KPT / KSA >= 2, LP_ERR_STATE, "Detect head %s: stage A needs two chunks", name.c_str());
   const int SPT = (KPT + 1) / 2;   // A16: K steps of 32 channels per tap (Cin = 16 mod 32: the last one half zero weights)
   if (A16)   // a chunk is KSA half-steps = KSA / 2 K steps x two row halves; fragment 7 of an 8-fragment slot is not addressable
@@ -811,7 +844,7 @@ void HeadLayer::build(int cin_phys, int c3_, int nc_, int h, int w, int batch_hi
   LP_CHECK(lds_bytes <= (SLOTF == 8 ? 53760u : (SLOTF == 12 ? 80u * 1024 : 160u * 1024)) && ((TW + 4) * (2 * KPT + 1) + 63) / 64 == NPC &&
                (A16 || ((9 * KPT) % KSA == 0 && RT * KSA <= SLOTF)) && TH + 4 <= (SLOTF <= 12 && !(OVL && SLOTF == 12) ? 12 : (OVL ? 16 : 20)) &&
                (SLOTF == 8 || SLOTF == 12 || SLOTF == 24) &&
-               (SLOTF == 8 ? C3T == 1 : 8 + 2 * C3T <= SLOTF) &&
+               (SLOTF != 8 || C3T == 1) &&   // (fragment 7 of an 8-fragment slot: only the box tower's chunks and the box projection)
                (A16 || (TH + 2) * (TW + 2) <= 128 * PA) && TH * TW <= 128 * PB, LP_ERR_STATE, "Detect head %s: inconsistent configuration", name.c_str());
   (void)batch_hint;
   std::vector<uint16_t> stream;
@@ -872,16 +905,7 @@ void HeadLayer::build(int cin_phys, int c3_, int nc_, int h, int w, int batch_hi
       });
     if (ks % KSA == KSA - 1) end_chunk(KSA);
   }
-  // ---- stage B box: K step kq = (tap, cg), 4 per tap
-  const int KSB = SLOTF / 2;   // two row tiles per step
-  for (int kq = 0; kq < 36; ++kq) {
-    if (kq % KSB == 0) begin_chunk();
-    const int tap = kq >> 2, cg = kq & 3;
-    for (int rt = 0; rt < 2; ++rt)
-      frag([&](int rho, int e) { return (*s.wbb)[((size_t)(rt * 32 + row_channel(rho)) * 9 + tap) * 64 + 16 * cg + e]; });
-    if (kq % KSB == KSB - 1) end_chunk(KSB);
-  }
-  // ---- stage B class: 2*C3T K steps per tap
+  // ---- stage B class (in front of the box tower: the kernel runs it first): 2*C3T K steps per tap
   {
     const int per_tap = 2 * C3T, total = 9 * per_tap, per_chunk = C3T == 2 ? SLOTF / 2 : (SLOTF >= 18 ? 18 : 6);
     for (int kq = 0; kq < total; ++kq) {
@@ -913,13 +937,24 @@ void HeadLayer::build(int cin_phys, int c3_, int nc_, int h, int w, int batch_hi
         return (co < nc && ci < c3) ? (*s.wpc)[(size_t)co * c3 + ci] : 0.f;
       });
   };
-  if (SLOTF == 8) {   // 8-fragment slots: the class projection (needed first) and the box projection are two chunks
-    begin_chunk(); cls_proj(); end_chunk(0);
-    begin_chunk(); box_proj(); end_chunk(0);
-  } else {
-    begin_chunk(); box_proj(); cls_proj(); end_chunk(0);
+  // stream order = consumption order: A chunks | class-B chunks | class projection | box-B chunks | box projection (a workgroup
+  // whose tile holds no candidate leaves behind the class projection)
+  begin_chunk(); cls_proj(); end_chunk(0);
+  // ---- stage B box: K step kq = (tap, cg), 4 per tap
+  const int KSB = SLOTF / 2;   // two row tiles per step
+  for (int kq = 0; kq < 36; ++kq) {
+    if (kq % KSB == 0) begin_chunk();
+    const int tap = kq >> 2, cg = kq & 3;
+    for (int rt = 0; rt < 2; ++rt)
+      frag([&](int rho, int e) { return (*s.wbb)[((size_t)(rt * 32 + row_channel(rho)) * 9 + tap) * 64 + 16 * cg + e]; });
+    if (kq % KSB == KSB - 1) end_chunk(KSB);
   }
+  begin_chunk(); box_proj(); end_chunk(0);
   nchunks = (int)coff.size();
+  {  // what the kernel's chunk counter walks through: stage A, the class tower, its projection, the box tower, its projection
+    const int ncA = A16 ? 9 * SPT / (KSA / 2) : 9 * KPT / KSA, ncC = C3T == 2 ? 36 / (SLOTF / 2) : 18 / (SLOTF >= 18 ? 18 : 6);
+    LP_CHECK(nchunks == ncA + ncC + 1 + 36 / (SLOTF / 2) + 1, LP_ERR_STATE, "Detect head %s: %d chunks in the weight stream", name.c_str(), nchunks);
+  }
   LP_CHECK(nchunks <= 64 && stream.size() / 512 < 65536, LP_ERR_STATE, "Detect head: weight stream too long (%d chunks)", nchunks);
   stream.resize(stream.size() + (size_t)2 * SLOTF * 512, 0);   // the ring requests two chunks past the end
   d_stream.alloc(stream.size() * 2 + 64);   // (one copy: replicating the stream per XCD changed nothing -- it is L2-resident)
@@ -958,6 +993,7 @@ void HeadLayer::launch(const View& in, int N, int anchor_off, int A, const float
   DevBuf d_stamps;
   if (stamp_path && *stamp_path) {
     d_stamps.alloc((size_t)grid.x * 16 * 8);
+    LP_HIP(hipMemsetAsync(d_stamps.p, 0, (size_t)grid.x * 16 * 8, st));   // a workgroup that leaves at the vote writes stamps 0-7, 14 and 15 only
     a.stamps = d_stamps.as<unsigned long long>();
   }
 #define LP_HEAD(C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_)                                                                          \
