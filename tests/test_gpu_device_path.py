@@ -213,35 +213,3 @@ def test_dropin_upload_lanes_equal_single_handles(tmp_path, monkeypatch):
     assert n >= 2 * 32, f"only {n // 2} results in 32 images"
     print(f"upload lanes: {n // 2} results in 32 images identical to the single-handle path (first call and replay)")
 
-
-def test_run_batch_chunked_equals_whole_batch(tmp_path, monkeypatch):
-    """LITEPI_RUN_CHUNK=16 (an A/B switch, off by default: no gain measured): lp_run_batch on >= 32 frames of one size walks the
-    batch in chunks of 16 (api.cpp run_batch_chunked: chunk k's upload on a copy stream under chunk k-1's kernels, every chunk a
-    complete detect -> NMS -> ROI -> classifier pass over its slice of the handle's buffers, captured per chunk).  The same
-    handle without the switch runs the batch whole: records, counts,
-    pre-filter counts and the mean-score bits must be identical, on the first (eager), second (capturing) and third (replaying)
-    call; a 40-frame batch has a ragged last chunk."""
-    from litepi import Engine
-    p, b, sd, imgs = _models(tmp_path)
-    frames = [imgs[j // 16][j % 16] for j in range(32)] + [imgs[0][j] for j in range(8)]
-    eng = Engine(precision="fp16", max_batch=40, max_det=300, num_classes=91)
-    try:
-        eng.load_detector(p, b)
-        eng.load_classifier(sd)
-        monkeypatch.delenv("LITEPI_RUN_CHUNK", raising=False)
-        want = {n: _host_reference(eng, frames[:n]) for n in (32, 40)}
-        monkeypatch.setenv("LITEPI_RUN_CHUNK", "16")
-        total = 0
-        for call in range(3):
-            for n in (32, 40):
-                dets, counts, num_det, avg = _host_reference(eng, frames[:n])
-                wd, wc, wn, wa = want[n]
-                assert np.array_equal(counts, wc) and np.array_equal(num_det, wn), (call, n)
-                assert np.array_equal(avg.view(np.uint32), wa.view(np.uint32)), (call, n)
-                for i in range(n):
-                    assert dets[i, :counts[i]].tobytes() == wd[i, :wc[i]].tobytes(), (call, n, i)
-                total += int(counts.sum())
-        assert total >= 3 * 72
-        print(f"chunked lp_run_batch: {total // 3} records in 32 + 40 frames identical to the whole-batch pass (eager, capture, replay)")
-    finally:
-        eng.close()

@@ -45,10 +45,10 @@ def models(tmp_path_factory):
     return dict(param=p, bin=b, cls=cls_path, sd=sd, big=big, mid=mid)
 
 
-def _engine(models, prec, max_batch, classifier=True, max_det=300):
+def _engine(models, prec, max_batch, classifier=True, max_det=300, max_rois=0):
     from litepi import Engine
     from litepi.backend import random_shufflenet_state
-    e = Engine(precision=prec, max_batch=max_batch, max_det=max_det, num_classes=91)
+    e = Engine(precision=prec, max_batch=max_batch, max_det=max_det, num_classes=91, max_rois=max_rois)
     e.load_detector(models["param"], models["bin"])
     if classifier:
         e.load_classifier(random_shufflenet_state(91, seed=3))
@@ -230,5 +230,46 @@ def test_tiled_errors(models):
                 fn()
             codes.append(ex.value.code)
         assert codes == [LP_ERR_STATE, LP_ERR_STATE]
+    finally:
+        e.close()
+
+
+# ---------------------------------------------------------------------------- 7. the staged host pass behind lp_run_tiled
+def test_tiled_host_pass_timing_and_roi_overflow(models):
+    """lp_run_tiled goes through the same staged host pass as lp_run_batch (run_host_pass): the stage times come from the four
+    events around the three captured pieces, and a max_rois that is too small is an error raised after the records were
+    delivered, which leaves the handle usable.
+
+    The confidence is 0.20, not the 0.25 of the other tests: the fixture calibrates 4..8 candidates per view over the 24 views
+    of big and mid together, and every one of them falls on big (the fp32 oracle's best score on mid is 0.235, so at 0.25 mid
+    has no record at all).  At 0.20 the oracle (CpuTiledPipeline) has 300 candidates on mid's 7 views (24..57 per view) and 179
+    records after the frame NMS, 5 candidates lie above 0.2276 (more than the fp16 score bound of 0.02 over the threshold), and
+    mid[:640, :640] has none at 0.25."""
+    from litepi._ffi import LP_ERR_STATE, LitepiError
+    mid = models["mid"]
+    assert mid.shape[:2] == (1024, 1280)
+    tile = np.ascontiguousarray(mid[:640, :640])
+    e = _engine(models, "fp16", 8)
+    try:
+        assert len(e.tile_grid(1024, 1280, overlap=128, full_frame=True)) == 7
+        _, counts, _, t = e.run_tiled([mid], 0.20, 0.45, 0, overlap=128, full_frame=True)
+        print(f"records {int(counts.sum())}, t_detection {t.t_detection:.4f} t_roi_extract {t.t_roi_extract:.4f} "
+              f"t_classification {t.t_classification:.4f} t_total {t.t_total:.4f} ms")
+        assert int(counts.sum()) >= 2, "the calibrated model found fewer than 2 records: the comparison is empty"
+        stages = (t.t_detection, t.t_roi_extract, t.t_classification)
+        assert all(x > 0 for x in stages), stages
+        assert all(t.t_total >= x for x in stages), (t.t_total, stages)   # event 0 .. event 3 encloses all three
+        # a confidence at which the one-tile frame keeps at most one record, found on this (default max_rois) engine
+        few = [c for c in (0.25, 0.5, 0.75, 0.9, 0.99, 1.0) if int(e.run_tiled([tile], c, 0.45, 0)[1].sum()) <= 1]
+        assert few, "no confidence leaves at most one record on the one-tile frame"
+    finally:
+        e.close()
+    e = _engine(models, "fp16", 8, max_rois=1)
+    try:
+        with pytest.raises(LitepiError) as ex:
+            e.run_tiled([mid], 0.20, 0.45, 0, overlap=128, full_frame=True)
+        assert ex.value.code == LP_ERR_STATE and "max_rois" in str(ex.value)
+        _, counts, _, _ = e.run_tiled([tile], few[0], 0.45, 0, overlap=128, full_frame=True)   # the handle is still usable
+        assert int(counts.sum()) <= 1
     finally:
         e.close()

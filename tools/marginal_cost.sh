@@ -1,6 +1,6 @@
 #!/bin/bash
 # Marginal cost of every launch of the step in a PIPELINED step (three in flight): the bench with launch i left out of every
-# pass after a handle's first (LITEPI_SKIP_OP / LITEPI_SKIP_STAGE, diagnostics in detector.cpp / api.cpp).  GPU box, ~8 min.
+# pass after a handle's first (LITEPI_SKIP_OP / LITEPI_SKIP_STAGE, diagnostics in detector.cpp / pipeline.cpp).  GPU box, ~8 min.
 # usage: [PRESET=v2] tools/marginal_cost.sh [n_ops=16] > gpurun_out/marginal.txt
 set -u
 N=${1:-16}

@@ -1,4 +1,4 @@
-// Copy workers of the host entry points (lp_run_batch / lp_detect), see api.cpp upload_images().  Header-only so that
+// Copy workers of the host entry points (lp_run_batch / lp_detect), see pipeline.cpp upload_images().  Header-only so that
 // tests/native/copy_pool_stress.cpp can exercise it on the CPU (also under -fsanitize=thread).
 #pragma once
 #include <atomic>

@@ -1,0 +1,230 @@
+// Internal to the C-ABI translation units (api.cpp, pipeline.cpp, pixfmt.cpp, tiling.cpp, tracking.cpp, test_hooks.cpp): the handle
+// behind include/litepi.h's lp_handle, the captured-step cache, and the pipeline pieces the entry points share.
+#pragma once
+#include <algorithm>
+#include <array>
+#include <functional>
+
+#include "classifier.h"
+#include "common.h"
+#include "copy_pool.h"
+#include "detector.h"
+#include "kernels.h"
+
+namespace lp {
+
+// Sign tracker of a handle (lp_tracker_*, lp_track*; include/litepi.h): the track table, the stream heads and the vote accumulators
+// stay in HBM between calls.  A call's per-stream frame lists are written into a slot of a pinned ring and copied from there
+// into the same slot of a device ring on the handle's stream (a pageable source would synchronise it); a slot is re-used only
+// after the event recorded behind the launch that read it.
+struct Tracker {
+  static constexpr int RING = 8;
+  lp_track_config cfg;
+  int nc = 1, max_det = 0, max_batch = 0;
+  DevBuf table, heads, acc, scratch, plan_dev;
+  DevBuf d_dets, d_counts, d_tracks;   // lp_track (host records): allocated on first use
+  int* plan_host = nullptr;            // pinned, RING slots of slot_ints
+  size_t slot_ints = 0;
+  hipEvent_t ev[RING] = {};
+  bool busy[RING] = {};
+  int next = 0;
+  ~Tracker() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (plan_host) (void)hipHostFree(plan_host);
+  }
+};
+
+// ---- captured steps: the launch sequence of a call is a pure function of (entry point, buffers, batch, geometry,
+//      thresholds), so the second call with the same key is captured into a hipGraph and later calls replay it
+//      (one hipGraphLaunch instead of ~40 kernel launches on the host).  LITEPI_NO_GRAPH=1 keeps every call eager.
+// One enumerator per captured piece: a key of another piece never compares equal, so no entry point replays another's step.
+enum GraphKind {
+  GK_BATCH_DEVICE,                                // lp_run_batch_device
+  GK_DETECT,                                      // lp_detect
+  GK_BATCH_FRONT, GK_BATCH_ROI, GK_BATCH_CLS,     // lp_run_batch: detect + NMS, ROI resize, classifier
+  GK_TILED_FRONT, GK_TILED_ROI, GK_TILED_CLS,     // lp_run_tiled: tiled detect + frame NMS, ROI resize, classifier
+  GK_TILED_DEVICE,                                // lp_run_tiled_device
+};
+struct GraphKey {
+  GraphKind kind;
+  int B, geom_ver, min_area;
+  const void* p0; void* p1; void* p2;
+  float conf, iou;
+  // the frame format the step was captured with (key_format; all zero for packed BGR) and the identity of its conversion table
+  int pixfmt = 0, matrix = 0, pitch = 0, csc_gen = 0;
+  int64_t uv_offset = 0, frame_stride = 0;
+  bool operator==(const GraphKey& o) const {
+    return kind == o.kind && B == o.B && geom_ver == o.geom_ver && min_area == o.min_area && p0 == o.p0 && p1 == o.p1 && p2 == o.p2 &&
+           conf == o.conf && iou == o.iou && pixfmt == o.pixfmt && matrix == o.matrix && pitch == o.pitch && csc_gen == o.csc_gen &&
+           uv_offset == o.uv_offset && frame_stride == o.frame_stride;
+  }
+};
+struct GraphEntry { GraphKey key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; bool failed = false; unsigned long stamp = 0; };
+
+}  // namespace lp
+
+struct lp_handle {
+  lp_config cfg;
+  std::unique_ptr<lp::Tracker> trk;   // null until lp_tracker_create: no other path looks at it
+  void* comm = nullptr;        // ncclComm_t of lp_comm_init
+  int comm_rank = 0, comm_world = 1;
+  // pinned staging of the host entry points + the copy workers (created on first use)
+  uint8_t* h_stage = nullptr;
+  size_t h_stage_bytes = 0;
+  std::unique_ptr<lp::CopyPool> pool;
+  hipStream_t own_stream = nullptr, stream = nullptr;
+  std::unique_ptr<lp::Detector> det;
+  std::unique_ptr<lp::ClassifierBase> cls;
+  lp::Profiler prof;
+  bool prof_next = false;
+  int max_rois = 0;
+  // device buffers
+  lp::DevBuf d_src, d_lb, d_geom, d_cand, d_cand_count, d_sorted, d_dets, d_counts, d_rects, d_out0;
+  lp::DevBuf d_roi_base, d_roi_total, d_roi_img, d_roi_slot, d_roi_rgb, d_probs, d_ids, d_conf;
+  std::vector<lp::ImgGeom> geom_cache;
+  // tiled inference (lp_run_tiled*): frame geometry, frame table + view slots, per-view counts; allocated on first use
+  lp::DevBuf d_fgeom, d_ftab, d_vcnt;
+  std::vector<char> tile_cache;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // staged host pass: start, after the ROI resize, after the front, end
+  int last_roi_count = 0;
+  // ---- input pixel format (lp_set_input_format).  NV12 frames are converted into d_src, which then holds exactly the packed
+  //      BGR frames a BGR call would have put there; host NV12 frames are uploaded into d_raw first.  The converter reads its
+  //      per-frame geometry from one of four table slots in d_csc: a slot's content never changes while a captured step may
+  //      still point at it (a re-used slot gets a new generation number, which is part of the graph key), so alternating
+  //      layouts keep their captured steps.
+  lp_frame_format fmt = {};
+  lp::DevBuf d_raw, d_csc;
+  struct CscSlot { std::vector<char> tab; int gen = 0; };
+  CscSlot csc_slots[4];
+  int csc_gen = 0, csc_next = 0;
+  bool nv12() const { return fmt.pixfmt == LP_PIX_NV12; }
+  void ensure_raw(size_t bytes) {
+    if (d_raw.bytes < bytes) {
+      d_raw.alloc(bytes + bytes / 4, false);
+      ++geom_ver;
+    }
+  }
+  std::vector<lp::GraphEntry> graphs;   // captured steps (run_or_capture)
+  int geom_ver = 0;
+  unsigned long graph_clock = 0;
+  void drop_graphs() {
+    for (auto& g : graphs) {
+      if (g.exec) (void)hipGraphExecDestroy(g.exec);
+      if (g.graph) (void)hipGraphDestroy(g.graph);
+    }
+    graphs.clear();
+  }
+
+  lp::RoiTable roi_table() {
+    lp::RoiTable t;
+    t.base = d_roi_base.as<int>(); t.total = d_roi_total.as<int>(); t.work = d_roi_total.as<int>() + 4;
+    t.img = d_roi_img.as<int>(); t.slot = d_roi_slot.as<int>();
+    return t;
+  }
+  void ensure_src(size_t bytes) {
+    if (d_src.bytes < bytes) {
+      d_src.alloc(bytes + bytes / 4, false);
+      ++geom_ver;  // captured steps hold the old address
+    }
+  }
+  void alloc_post_buffers() {
+    const int B = cfg.max_batch, A = det->num_anchors(), nc = det->num_classes();
+    d_cand.alloc((size_t)B * A * sizeof(lp::Cand), false);
+    d_sorted.alloc((size_t)B * A * sizeof(lp::Cand), false);
+    d_cand_count.alloc((size_t)B * 4);
+    d_dets.alloc((size_t)B * cfg.max_det * sizeof(lp_det));
+    d_counts.alloc((size_t)3 * B * 4);
+    d_rects.alloc((size_t)B * cfg.max_det * 16);
+    d_out0.alloc((size_t)B * (4 + nc) * A * 4, false);
+  }
+  void upload_geom(const std::vector<lp::ImgGeom>& g) {
+    bool same = g.size() == geom_cache.size() && (g.empty() || memcmp(g.data(), geom_cache.data(), g.size() * sizeof(lp::ImgGeom)) == 0);
+    if (same) return;
+    LP_HIP(hipMemcpyAsync(d_geom.p, g.data(), g.size() * sizeof(lp::ImgGeom), hipMemcpyHostToDevice, stream));
+    LP_HIP(hipStreamSynchronize(stream));  // g may be a temporary; uploads are rare (shape changes only)
+    geom_cache = g;
+    ++geom_ver;
+  }
+};
+
+#define LP_API_BEGIN try {
+#define LP_API_END                                   \
+  }                                                  \
+  catch (const lp::Error& e) {                       \
+    lp::set_last_error(e.what());                    \
+    return e.code;                                   \
+  }                                                  \
+  catch (const std::exception& e) {                  \
+    lp::set_last_error(e.what());                    \
+    return LP_ERR_STATE;                             \
+  }                                                  \
+  return LP_OK;
+
+namespace lp {
+
+// ---- pipeline pieces shared by the entry points (pipeline.cpp) -----------------------------------------------------------------
+// letterbox geometry exactly as the reference computes it in Python doubles (e2e.py:72-83)
+ImgGeom make_geom(int h, int w, int S, long src_off);
+Profiler* begin_profile(lp_handle* h);
+// detector (+ optional letterbox) on images resident at src with geometry already uploaded
+void enqueue_detect(lp_handle* h, const uint8_t* src, const std::vector<ImgGeom>& geoms, int B, float conf, float* out0, Profiler* prof);
+// NMS + ROI rectangles; with_rois: also the batch-wide ROI list the classifier stage consumes
+void enqueue_nms(lp_handle* h, int B, float iou, int min_area, lp_det* dets, int* counts, bool with_rois, Profiler* prof);
+// PIL resize + classifier + softmax over the ROI list; stage 0 = both halves, 1 = only the ROI resize, 2 = only the classifier;
+// geom: the images' geometry (default d_geom; the tiled path passes its frame geometry)
+void enqueue_classify(lp_handle* h, const uint8_t* src, int B, lp_det* dets, float* probs, int* ids, float* conf, Profiler* prof, int stage = 0,
+                      const ImgGeom* geom = nullptr);
+// eager the first time a key is seen, captured into a hipGraph the second time, replayed from then on
+void run_or_capture(lp_handle* h, const GraphKey& key, bool allow, const std::function<void()>& enqueue);
+
+// ---- input pixel format (pixfmt.cpp) -------------------------------------------------------------------------------------------
+// the layout of one H x W frame with the zeros resolved
+struct FrameLayout { int pitch; int64_t uv_off, frame_bytes, stride; };
+// one conversion launch: table in a slot of d_csc, grid extent, matrix, identity for the graph key, pixels for the profile
+struct CscPlan {
+  const CscFrame* dev = nullptr;
+  int B = 0, max_blocks = 0, matrix = 0, gen = 0;
+  double pixels = 0.0;
+};
+inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+void check_format(const lp_frame_format* f);
+FrameLayout frame_layout(const lp_frame_format& f, int H, int W);
+void finish_csc_table(std::vector<CscFrame>& tab, const void* src, const void* dst);
+CscPlan plan_csc(lp_handle* h, std::vector<CscFrame>& tab, const void* src);
+void enqueue_csc(lp_handle* h, const uint8_t* src, const CscPlan& p, Profiler* prof);
+void key_format(const lp_handle* h, const CscPlan& p, GraphKey& k);
+CscPlan device_csc(lp_handle* h, const void* dev_imgs, int B, int H, int W, std::vector<ImgGeom>& g);
+
+// ---- host frames (pipeline.cpp) ------------------------------------------------------------------------------------------------
+// upload B host images of individual sizes into d_src (NV12 frames: into d_raw, with the plan of their conversion into d_src
+// in *csc); returns their geometry
+std::vector<ImgGeom> upload_images(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, CscPlan* csc = nullptr);
+// The staged host pass of lp_run_batch and lp_run_tiled: `front` (colour conversion + detect + NMS of either kind), the ROI
+// resize reading roi_geom (nullptr: d_geom) and the classifier as three captured pieces with the stage events between them,
+// then records, counts and timing back on the host.  An overflow of max_rois is reported last: the records are delivered.
+void run_host_pass(lp_handle* h, int B, float conf, float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg,
+                   lp_timing* timing, const CscPlan& csc, GraphKind front_kind, GraphKind roi_kind, GraphKind cls_kind,
+                   const std::function<void(Profiler*)>& front, const ImgGeom* roi_geom);
+// R crops as R "images" whose single ROI is the whole crop (lp_classify, lp_test_roi_resize): geometry at 16-byte aligned
+// offsets, one rectangle each, img[i] = i, slot 0; total = bytes of the packed crops
+struct CropRois {
+  std::vector<ImgGeom> g;
+  std::vector<int> rects, img, slot;
+  size_t total = 0;
+};
+CropRois whole_crop_rois(const uint8_t* const* rois, const int* hs, const int* ws, int R);
+
+// ---- tiled inference (tiling.cpp) ----------------------------------------------------------------------------------------------
+// The call's view layout.  Batch slots: first the letterboxed views (one launch of the letterbox kernel, so they are exactly
+// lp_run_batch's input), then the crops.  frames[f] / vslot list each frame's slots in the frame's view order.
+struct TileLayout {
+  std::vector<ImgGeom> vgeom;     // [V] by slot
+  std::vector<TileFrame> frames;  // [F]
+  std::vector<int> vslot;         // [V] frame-major
+  int L = 0, V = 0, max_views = 0;
+};
+void check_tiling(const lp_tiling* t, int S);
+TileLayout tile_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const lp_tiling& t);
+
+}  // namespace lp

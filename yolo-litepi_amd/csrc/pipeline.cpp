@@ -1,0 +1,429 @@
+// The pipeline pieces the entry points share, the host upload path, the staged host pass, and the untiled entry points.
+#include <cmath>
+#include <cstdlib>
+
+#include "handle.h"
+
+namespace lp {
+
+// letterbox geometry exactly as the reference computes it in Python doubles (e2e.py:72-83);
+// Python's round() is round-half-to-even == nearbyint in the default rounding mode.
+ImgGeom make_geom(int h, int w, int S, long src_off) {
+  ImgGeom g;
+  memset(&g, 0, sizeof(g));  // padding bytes too: geometry is compared with memcmp
+  const double r = std::min((double)S / h, (double)S / w);
+  const int nw = (int)std::nearbyint(w * r), nh = (int)std::nearbyint(h * r);
+  const double dw = (S - nw) / 2.0, dh = (S - nh) / 2.0;
+  g.src_off = src_off; g.h = h; g.w = w; g.new_w = nw; g.new_h = nh;
+  g.top = (int)std::nearbyint(dh - 0.1);
+  g.left = (int)std::nearbyint(dw - 0.1);
+  g.ratio = (float)r; g.pad_w = (float)dw; g.pad_h = (float)dh;
+  return g;
+}
+
+Profiler* begin_profile(lp_handle* h) {
+  if (!h->prof_next) return nullptr;
+  h->prof_next = false;
+  h->prof.enabled = true;
+  h->prof.results.clear();
+  return &h->prof;
+}
+
+// detector (+ optional letterbox) on images resident at src with geometry already uploaded
+void enqueue_detect(lp_handle* h, const uint8_t* src, const std::vector<ImgGeom>& geoms, int B, float conf, float* out0,
+                    Profiler* prof) {
+  const int S = h->cfg.det_input;
+  bool identity = true;
+  for (int i = 0; i < B; ++i)
+    identity = identity && geoms[i].h == S && geoms[i].w == S && geoms[i].src_off == (long)i * S * S * 3;
+  const uint8_t* img = src;
+  if (!identity) {
+    if (prof) prof->begin(h->stream);
+    launch_letterbox(src, h->d_geom.as<ImgGeom>(), h->d_lb.as<uint8_t>(), B, S, h->stream, geoms.data());
+    if (prof) {
+      double bytes = (double)B * S * S * 3;
+      for (int i = 0; i < B; ++i) bytes += (double)geoms[i].h * geoms[i].w * 3;
+      prof->end(h->stream, "letterbox_u8", "letterbox", 0.0, bytes);
+    }
+    img = h->d_lb.as<uint8_t>();
+  }
+  h->det->forward(img, B, h->d_geom.as<ImgGeom>(), conf, out0, h->d_cand.as<Cand>(), h->d_cand_count.as<int>(), h->stream, prof);
+}
+
+// Diagnostic only (tools/marginal_cost.sh): LITEPI_SKIP_STAGE=nms|roi|cls leaves that stage out of every pass after the handle's
+// first (its outputs stay in the handle's buffers): the marginal cost of the stage in a pipelined step.  Results are stale.
+static bool skip_stage(const lp_handle* h, const char* name, const Profiler* prof) {
+  static const char* s = getenv("LITEPI_SKIP_STAGE");
+  return s && !prof && h->graph_clock > 1 && strcmp(s, name) == 0;
+}
+
+// NMS + ROI rectangles; with_rois: also the batch-wide ROI list the classifier stage consumes
+void enqueue_nms(lp_handle* h, int B, float iou, int min_area, lp_det* dets, int* counts, bool with_rois, Profiler* prof) {
+  NmsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.cand = h->d_cand.as<Cand>(); a.cand_count = h->d_cand_count.as<int>(); a.sorted = h->d_sorted.as<Cand>();
+  a.dets = dets; a.counts = counts; a.rects = h->d_rects.as<int>(); a.geom = h->d_geom.as<ImgGeom>();
+  a.A = h->det->num_anchors(); a.max_det = h->cfg.max_det; a.nc = h->det->num_classes(); a.iou = iou; a.min_area = min_area;
+  if (with_rois) a.tab = h->roi_table();
+  a.max_rois = h->max_rois;
+  a.roi_rule = h->cfg.numerics;
+  if (skip_stage(h, "nms", prof)) return;
+  if (prof) prof->begin(h->stream);
+  launch_nms(a, B, h->stream);
+  if (prof) prof->end(h->stream, "nms", "nms", 0.0, 0.0);
+}
+
+// PIL resize + ShuffleNetV2 + softmax over the ROI list; scatters (cls, conf) into dets when given
+// stage: 0 = both halves, 1 = only the ROI crop + resize (the device's share of the reference's ROI loop, e2e.py:460-475),
+// 2 = only the classifier (lp_run_batch times the two separately: PipelineMetrics.t_roi_extract / t_classification)
+// geom: the images' geometry (default d_geom; the tiled path passes its frame geometry)
+void enqueue_classify(lp_handle* h, const uint8_t* src, int B, lp_det* dets, float* probs, int* ids, float* conf, Profiler* prof, int stage,
+                      const ImgGeom* geom) {
+  RoiTable tab = h->roi_table();
+  if (stage != 2 && !skip_stage(h, "roi", prof)) {
+    RoiResizeArgs r;
+    r.src = src; r.geom = geom ? geom : h->d_geom.as<ImgGeom>(); r.rects = h->d_rects.as<int>(); r.tab = tab;
+    r.out = h->d_roi_rgb.as<uint8_t>(); r.max_det = h->cfg.max_det; r.S = h->cfg.cls_input; r.linear = h->cfg.numerics;
+    if (prof) prof->begin(h->stream);
+    launch_roi_resize(r, std::min(h->max_rois, B * h->cfg.max_det), h->stream);
+    if (prof) prof->end(h->stream, "roi_resize_pil", "roi_resize", 0.0, (double)r.S * r.S * 3 * 2, true);
+  }
+  if (stage == 1 || skip_stage(h, "cls", prof)) return;
+  ClsPost post;
+  post.probs = probs; post.ids = ids; post.dets = dets; post.max_det = h->cfg.max_det; post.roi_img = tab.img; post.roi_slot = tab.slot;
+  h->cls->forward(h->d_roi_rgb.as<uint8_t>(), tab.total, h->stream, prof, &post);
+  if (!h->cls->fused_head()) {
+    if (prof) prof->begin(h->stream);
+    launch_softmax_argmax(h->cls->logits(), h->cls->logits_pitch(), h->cls->num_classes(), probs, ids, conf, dets, h->cfg.max_det,
+                          &tab, tab.total, h->max_rois, h->stream);
+    if (prof) prof->end(h->stream, "softmax_argmax", "softmax", 0.0, (double)h->cls->num_classes() * 8, true);
+  }
+}
+
+// Run `enqueue` (kernel launches on h->stream only: no allocation, no synchronisation) eagerly the first time a key is
+// seen -- that call also performs every one-time set-up (LDS attributes, lazy packing) --, capture it into a hipGraph the
+// second time, replay the graph from then on.
+void run_or_capture(lp_handle* h, const GraphKey& key, bool allow, const std::function<void()>& enqueue) {
+  static const bool disabled = getenv("LITEPI_NO_GRAPH") != nullptr;
+  if (disabled || !allow) { enqueue(); return; }
+  GraphEntry* e = nullptr;
+  for (auto& g : h->graphs)
+    if (g.key == key) { e = &g; break; }
+  if (!e) {  // first sight: eager, remember the key
+    if (h->graphs.size() >= 32) {  // evict the least recently used entry
+      size_t lru = 0;
+      for (size_t i = 1; i < h->graphs.size(); ++i)
+        if (h->graphs[i].stamp < h->graphs[lru].stamp) lru = i;
+      if (h->graphs[lru].exec) (void)hipGraphExecDestroy(h->graphs[lru].exec);
+      if (h->graphs[lru].graph) (void)hipGraphDestroy(h->graphs[lru].graph);
+      h->graphs.erase(h->graphs.begin() + lru);
+    }
+    GraphEntry ne;
+    ne.key = key;
+    ne.stamp = ++h->graph_clock;
+    h->graphs.push_back(ne);
+    enqueue();
+    return;
+  }
+  e->stamp = ++h->graph_clock;
+  if (e->failed) { enqueue(); return; }
+  if (!e->exec) {
+    if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { e->failed = true; enqueue(); return; }
+    bool ok = true;
+    std::string err;
+    try { enqueue(); } catch (const lp::Error& ex) { ok = false; err = ex.what(); }
+    hipGraph_t graph = nullptr;
+    if (hipStreamEndCapture(h->stream, &graph) != hipSuccess || !graph) ok = false;
+    if (ok && hipGraphInstantiate(&e->exec, graph, nullptr, nullptr, 0) != hipSuccess) { ok = false; e->exec = nullptr; }
+    if (!ok) {
+      if (graph) (void)hipGraphDestroy(graph);
+      (void)hipGetLastError();
+      e->failed = true;
+      LP_CHECK(err.empty(), LP_ERR_STATE, "%s", err.c_str());
+      enqueue();
+      return;
+    }
+    e->graph = graph;
+  }
+  LP_HIP(hipGraphLaunch(e->exec, h->stream));
+}
+
+// upload B host images of individual sizes into d_src (NV12 frames: into d_raw, with the plan of their conversion into d_src
+// in *csc); returns their geometry
+std::vector<ImgGeom> upload_images(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, CscPlan* csc) {
+  const bool nv = h->nv12();
+  lp_frame_format hf = h->fmt;
+  hf.frame_stride = 0;   // host frames come one pointer each: frame_bytes apiece, the stride of device batches does not apply
+  std::vector<ImgGeom> g(B);
+  std::vector<size_t> nb(B), off(B);   // bytes of every frame as it is uploaded, and its offset in the upload buffer
+  std::vector<CscFrame> tab;
+  size_t bgr_total = 0, total = 0;
+  for (int i = 0; i < B; ++i) {
+    LP_CHECK(imgs[i] && hs[i] > 0 && ws[i] > 0, LP_ERR_ARG, "image %d is empty", i);
+    g[i] = make_geom(hs[i], ws[i], h->cfg.det_input, (long)bgr_total);
+    bgr_total = align16(bgr_total + (size_t)hs[i] * ws[i] * 3);
+    if (nv) {
+      const FrameLayout L = frame_layout(hf, hs[i], ws[i]);
+      nb[i] = (size_t)L.frame_bytes; off[i] = total;
+      tab.push_back(CscFrame{(long)total, (long)L.uv_off, g[i].src_off, hs[i], ws[i], L.pitch, 0});
+      total = align16(total + nb[i]);
+    } else {
+      nb[i] = (size_t)hs[i] * ws[i] * 3; off[i] = (size_t)g[i].src_off;
+      total = bgr_total;
+    }
+  }
+  h->ensure_src(bgr_total);
+  uint8_t* dst = h->d_src.as<uint8_t>();
+  if (nv) {
+    LP_CHECK(csc, LP_ERR_STATE, "this entry point takes packed BGR frames only");
+    h->ensure_raw(total);
+    dst = h->d_raw.as<uint8_t>();
+    *csc = plan_csc(h, tab, dst);
+  }
+  // small uploads (a single frame: the batch-1 latency path) go straight from the caller's memory
+  static const int n_threads = getenv("LITEPI_UPLOAD_THREADS") ? atoi(getenv("LITEPI_UPLOAD_THREADS")) : 8;
+  if (n_threads <= 0 || B < 4 || total < ((size_t)4 << 20)) {
+    for (int i = 0; i < B; ++i)
+      LP_HIP(hipMemcpyAsync(dst + off[i], imgs[i], nb[i], hipMemcpyHostToDevice, h->stream));
+    return g;
+  }
+  if (h->h_stage_bytes < total) {
+    if (h->h_stage) { LP_HIP(hipStreamSynchronize(h->stream)); (void)hipHostFree(h->h_stage); h->h_stage = nullptr; h->h_stage_bytes = 0; }
+    LP_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->h_stage), total + total / 4, hipHostMallocDefault));
+    h->h_stage_bytes = total + total / 4;
+  }
+  if (!h->pool) h->pool.reset(new CopyPool(n_threads - 1));
+  // (the previous call synchronised the stream before it returned: the staging buffer is free)
+  // groups of about 10 MB: the workers fill group k+1 while the DMA engine moves group k; an image larger than that is split
+  // into slices so that every worker has a share
+  std::vector<CopyPool::Job> jobs;
+  // (the first groups are small: nothing overlaps the first group's copy, the link idles until it is staged)
+  static const size_t group_mb = getenv("LITEPI_UPLOAD_GROUP_MB") ? (size_t)atol(getenv("LITEPI_UPLOAD_GROUP_MB")) : 10;
+  const size_t slice = (size_t)1 << 20;
+  int i0 = 0, ngroup = 0;
+  while (i0 < B) {
+    int i1 = i0;
+    size_t gb = 0;
+    const size_t group_bytes = ngroup == 0 ? (size_t)2 << 20 : (ngroup == 1 ? (size_t)5 << 20 : group_mb << 20);
+    ++ngroup;
+    jobs.clear();
+    while (i1 < B && (i1 == i0 || gb + nb[i1] <= group_bytes)) {
+      for (size_t o = 0; o < nb[i1]; o += slice) jobs.push_back({imgs[i1] + o, h->h_stage + off[i1] + o, std::min(slice, nb[i1] - o)});
+      gb += nb[i1];
+      ++i1;
+    }
+    h->pool->run(jobs.data(), (int)jobs.size());
+    const size_t lo = off[i0], hi = off[i1 - 1] + nb[i1 - 1];
+    LP_HIP(hipMemcpyAsync(dst + lo, h->h_stage + lo, hi - lo, hipMemcpyHostToDevice, h->stream));
+    i0 = i1;
+  }
+  return g;
+}
+
+void run_host_pass(lp_handle* h, int B, float conf, float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg,
+                   lp_timing* timing, const CscPlan& csc, GraphKind front_kind, GraphKind roi_kind, GraphKind cls_kind,
+                   const std::function<void(Profiler*)>& front, const ImgGeom* roi_geom) {
+  Profiler* prof = begin_profile(h);
+  const uint8_t* src = h->d_src.as<uint8_t>();
+  lp_det* d_dets = h->d_dets.as<lp_det>();
+  // three captured pieces with the stage-boundary events between them (PipelineMetrics wants detection, ROI extraction and
+  // classification times separately, e2e.py:452-499); the colour conversion of NV12 frames is booked under detection
+  GraphKey k1{front_kind, B, h->geom_ver, min_area, h->d_src.p, h->d_dets.p, h->d_counts.p, conf, iou}, k2 = k1, k3 = k1;
+  k2.kind = roi_kind; k3.kind = cls_kind;
+  key_format(h, csc, k1);   // the conversion is part of the front only
+  LP_HIP(hipEventRecord(h->ev[0], h->stream));
+  run_or_capture(h, k1, prof == nullptr, [&]() { front(prof); });
+  LP_HIP(hipEventRecord(h->ev[2], h->stream));
+  run_or_capture(h, k2, prof == nullptr, [&]() { enqueue_classify(h, src, B, d_dets, nullptr, nullptr, nullptr, prof, 1, roi_geom); });
+  LP_HIP(hipEventRecord(h->ev[1], h->stream));
+  run_or_capture(h, k3, prof == nullptr, [&]() { enqueue_classify(h, src, B, d_dets, nullptr, nullptr, nullptr, prof, 2, roi_geom); });
+  LP_HIP(hipEventRecord(h->ev[3], h->stream));
+  LP_HIP(hipMemcpyAsync(dets, h->d_dets.p, (size_t)B * h->cfg.max_det * sizeof(lp_det), hipMemcpyDeviceToHost, h->stream));
+  std::vector<int> cnt(3 * B);
+  LP_HIP(hipMemcpyAsync(cnt.data(), h->d_counts.p, (size_t)3 * B * 4, hipMemcpyDeviceToHost, h->stream));
+  int R[2] = {0, 0};
+  LP_HIP(hipMemcpyAsync(R, h->d_roi_total.p, 8, hipMemcpyDeviceToHost, h->stream));
+  LP_HIP(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < B; ++i) {
+    counts[i] = cnt[i];
+    if (num_det) num_det[i] = cnt[B + i];
+    if (det_conf_avg) memcpy(&det_conf_avg[i], &cnt[2 * B + i], 4);
+  }
+  h->last_roi_count = R[0];
+  if (timing) {
+    // the front (view gather, detector, decode + NMS) is booked under detection like the reference's detect() (e2e.py:452-453);
+    // the ROI rectangles come out of the NMS kernel, the crop + PIL resize is the device's share of the ROI loop (e2e.py:460-475)
+    (void)hipEventElapsedTime(&timing->t_detection, h->ev[0], h->ev[2]);
+    (void)hipEventElapsedTime(&timing->t_roi_extract, h->ev[2], h->ev[1]);
+    (void)hipEventElapsedTime(&timing->t_classification, h->ev[1], h->ev[3]);
+    (void)hipEventElapsedTime(&timing->t_total, h->ev[0], h->ev[3]);
+  }
+  if (prof) { prof->collect(R[0]); prof->enabled = false; }
+  // every kept ROI must have been classified (the reference classifies all of them): a user-set max_rois that was too
+  // small is an error, not a silent cls_class = -1
+  LP_CHECK(R[1] <= h->max_rois, LP_ERR_STATE, "%d ROIs in this batch exceed max_rois = %d: %d detections were left unclassified", R[1],
+           h->max_rois, R[1] - h->max_rois);
+}
+
+CropRois whole_crop_rois(const uint8_t* const* rois, const int* hs, const int* ws, int R) {
+  CropRois c;
+  c.g.resize(R); c.rects.resize((size_t)R * 4); c.img.resize(R); c.slot.assign(R, 0);
+  for (int i = 0; i < R; ++i) {
+    LP_CHECK(rois[i] && hs[i] > 0 && ws[i] > 0 && hs[i] <= 4096 && ws[i] <= 4096, LP_ERR_ARG, "ROI %d has a bad size", i);
+    memset(&c.g[i], 0, sizeof(ImgGeom));
+    c.g[i].src_off = (long)c.total; c.g[i].h = hs[i]; c.g[i].w = ws[i];
+    c.total += align16((size_t)hs[i] * ws[i] * 3);
+    c.img[i] = i;
+    int* rc = &c.rects[(size_t)i * 4];
+    rc[0] = 0; rc[1] = 0; rc[2] = ws[i]; rc[3] = hs[i];
+  }
+  return c;
+}
+}  // namespace lp
+
+using namespace lp;
+
+extern "C" {
+
+int lp_detect_raw(lp_handle* h, const uint8_t* bgr, int B, float* out0) {
+  LP_API_BEGIN
+  LP_CHECK(h && bgr && out0, LP_ERR_ARG, "null argument");
+  LP_CHECK(h->det && h->det->loaded(), LP_ERR_STATE, "detector not loaded");
+  LP_CHECK(B >= 1 && B <= h->cfg.max_batch, LP_ERR_ARG, "batch %d outside 1..%d", B, h->cfg.max_batch);
+  LP_HIP(hipSetDevice(h->cfg.device));
+  const int S = h->cfg.det_input;
+  const size_t bytes = (size_t)B * S * S * 3;
+  h->ensure_src(bytes);
+  LP_HIP(hipMemcpyAsync(h->d_src.p, bgr, bytes, hipMemcpyHostToDevice, h->stream));
+  std::vector<ImgGeom> g(B);
+  for (int i = 0; i < B; ++i) g[i] = make_geom(S, S, S, (long)i * S * S * 3);
+  h->upload_geom(g);
+  Profiler* prof = begin_profile(h);
+  LP_HIP(hipMemsetAsync(h->d_cand_count.p, 0, (size_t)h->cfg.max_batch * 4, h->stream));
+  enqueue_detect(h, h->d_src.as<uint8_t>(), g, B, 2.0f /* nothing passes: raw output only */, h->d_out0.as<float>(), prof);
+  const size_t obytes = (size_t)B * (4 + h->det->num_classes()) * h->det->num_anchors() * 4;
+  LP_HIP(hipMemcpyAsync(out0, h->d_out0.p, obytes, hipMemcpyDeviceToHost, h->stream));
+  LP_HIP(hipStreamSynchronize(h->stream));
+  if (prof) { prof->collect(0); prof->enabled = false; }
+  LP_API_END
+}
+
+int lp_detect(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, float conf, float iou,
+              lp_det* dets, int* counts) {
+  LP_API_BEGIN
+  LP_CHECK(h && imgs && hs && ws && dets && counts, LP_ERR_ARG, "null argument");
+  LP_CHECK(h->det && h->det->loaded(), LP_ERR_STATE, "detector not loaded");
+  LP_CHECK(B >= 1 && B <= h->cfg.max_batch, LP_ERR_ARG, "batch %d outside 1..%d", B, h->cfg.max_batch);
+  LP_HIP(hipSetDevice(h->cfg.device));
+  const bool nv = h->nv12();
+  CscPlan csc;
+  std::vector<ImgGeom> g = upload_images(h, imgs, hs, ws, B, &csc);
+  h->upload_geom(g);
+  Profiler* prof = begin_profile(h);
+  GraphKey key{GK_DETECT, B, h->geom_ver, -1, h->d_src.p, h->d_dets.p, h->d_counts.p, conf, iou};
+  key_format(h, csc, key);
+  run_or_capture(h, key, prof == nullptr, [&]() {
+    if (nv) enqueue_csc(h, h->d_raw.as<uint8_t>(), csc, prof);
+    enqueue_detect(h, h->d_src.as<uint8_t>(), g, B, conf, nullptr, prof);
+    enqueue_nms(h, B, iou, -1, h->d_dets.as<lp_det>(), h->d_counts.as<int>(), false, prof);
+  });
+  LP_HIP(hipMemcpyAsync(dets, h->d_dets.p, (size_t)B * h->cfg.max_det * sizeof(lp_det), hipMemcpyDeviceToHost, h->stream));
+  LP_HIP(hipMemcpyAsync(counts, h->d_counts.p, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
+  LP_HIP(hipStreamSynchronize(h->stream));
+  if (prof) { prof->collect(0); prof->enabled = false; }
+  LP_API_END
+}
+
+int lp_run_batch(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, float conf, float iou,
+                 int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing) {
+  LP_API_BEGIN
+  LP_CHECK(h && imgs && hs && ws && dets && counts, LP_ERR_ARG, "null argument");
+  LP_CHECK(h->det && h->det->loaded(), LP_ERR_STATE, "detector not loaded");
+  LP_CHECK(h->cls && h->cls->loaded(), LP_ERR_STATE, "classifier not loaded");
+  LP_CHECK(B >= 1 && B <= h->cfg.max_batch, LP_ERR_ARG, "batch %d outside 1..%d", B, h->cfg.max_batch);
+  LP_CHECK(min_area >= 0, LP_ERR_ARG, "min_area must be >= 0");
+  LP_HIP(hipSetDevice(h->cfg.device));
+  const bool nv = h->nv12();
+  CscPlan csc;
+  std::vector<ImgGeom> g = upload_images(h, imgs, hs, ws, B, &csc);
+  h->upload_geom(g);
+  run_host_pass(h, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, csc, GK_BATCH_FRONT, GK_BATCH_ROI, GK_BATCH_CLS,
+                [&](Profiler* prof) {
+                  if (nv) enqueue_csc(h, h->d_raw.as<uint8_t>(), csc, prof);
+                  enqueue_detect(h, h->d_src.as<uint8_t>(), g, B, conf, nullptr, prof);
+                  enqueue_nms(h, B, iou, min_area, h->d_dets.as<lp_det>(), h->d_counts.as<int>(), true, prof);
+                }, nullptr);
+  LP_API_END
+}
+
+int lp_run_batch_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, float conf, float iou, int min_area,
+                        void* dev_dets, void* dev_counts) {
+  LP_API_BEGIN
+  LP_CHECK(h && dev_imgs && dev_dets && dev_counts, LP_ERR_ARG, "null argument");
+  LP_CHECK(h->det && h->det->loaded(), LP_ERR_STATE, "detector not loaded");
+  LP_CHECK(B >= 1 && B <= h->cfg.max_batch && H > 0 && W > 0, LP_ERR_ARG, "bad batch/shape");
+  LP_HIP(hipSetDevice(h->cfg.device));
+  std::vector<ImgGeom> g(B);
+  const bool nv = h->nv12();
+  CscPlan csc;
+  if (nv) csc = device_csc(h, dev_imgs, B, H, W, g);
+  else
+    for (int i = 0; i < B; ++i) g[i] = make_geom(H, W, h->cfg.det_input, (long)i * H * W * 3);
+  h->upload_geom(g);
+  Profiler* prof = begin_profile(h);
+  const uint8_t* src = nv ? h->d_src.as<uint8_t>() : static_cast<const uint8_t*>(dev_imgs);
+  const bool classify = h->cls && h->cls->loaded();
+  GraphKey key{GK_BATCH_DEVICE, B, h->geom_ver, min_area, dev_imgs, dev_dets, dev_counts, conf, iou};
+  key_format(h, csc, key);
+  run_or_capture(h, key, prof == nullptr, [&]() {
+    if (nv) enqueue_csc(h, static_cast<const uint8_t*>(dev_imgs), csc, prof);
+    enqueue_detect(h, src, g, B, conf, nullptr, prof);
+    enqueue_nms(h, B, iou, classify ? min_area : -1, static_cast<lp_det*>(dev_dets), static_cast<int*>(dev_counts), classify, prof);
+    if (classify) enqueue_classify(h, src, B, static_cast<lp_det*>(dev_dets), nullptr, nullptr, nullptr, prof);
+  });
+  if (prof) prof->enabled = false;  // records are collected by lp_profile_read after the caller synchronises
+  LP_API_END
+}
+
+int lp_classify(lp_handle* h, const uint8_t* const* rois, const int* hs, const int* ws, int R, int* ids, float* probs) {
+  LP_API_BEGIN
+  LP_CHECK(h && ids && probs, LP_ERR_ARG, "null argument");
+  LP_CHECK(h->cls && h->cls->loaded(), LP_ERR_STATE, "classifier not loaded");
+  LP_CHECK(R >= 0 && R <= h->max_rois && R <= h->cfg.max_batch * h->cfg.max_det, LP_ERR_ARG,
+           "%d ROIs exceed the capacity (%d)", R, std::min(h->max_rois, h->cfg.max_batch * h->cfg.max_det));
+  if (R == 0) return LP_OK;
+  LP_CHECK(rois && hs && ws, LP_ERR_ARG, "null argument");
+  LP_HIP(hipSetDevice(h->cfg.device));
+  const CropRois c = whole_crop_rois(rois, hs, ws, R);
+  LP_CHECK(R <= (int)(h->d_geom.bytes / sizeof(ImgGeom)), LP_ERR_ARG, "too many ROIs");
+  h->ensure_src(c.total);
+  for (int i = 0; i < R; ++i)
+    LP_HIP(hipMemcpyAsync(h->d_src.as<uint8_t>() + c.g[i].src_off, rois[i], (size_t)hs[i] * ws[i] * 3, hipMemcpyHostToDevice, h->stream));
+  h->geom_cache.clear();
+  LP_HIP(hipMemcpyAsync(h->d_geom.p, c.g.data(), (size_t)R * sizeof(ImgGeom), hipMemcpyHostToDevice, h->stream));
+  DevBuf d_rects_tmp;  // [R][1][4]: one whole-crop rectangle per "image"
+  d_rects_tmp.alloc((size_t)R * 16);
+  LP_HIP(hipMemcpyAsync(d_rects_tmp.p, c.rects.data(), c.rects.size() * 4, hipMemcpyHostToDevice, h->stream));
+  LP_HIP(hipMemcpyAsync(h->d_roi_img.p, c.img.data(), (size_t)R * 4, hipMemcpyHostToDevice, h->stream));
+  LP_HIP(hipMemcpyAsync(h->d_roi_slot.p, c.slot.data(), (size_t)R * 4, hipMemcpyHostToDevice, h->stream));
+  LP_HIP(hipMemcpyAsync(h->d_roi_total.p, &R, 4, hipMemcpyHostToDevice, h->stream));
+  Profiler* prof = begin_profile(h);
+  RoiTable tab = h->roi_table();
+  RoiResizeArgs r;
+  r.src = h->d_src.as<uint8_t>(); r.geom = h->d_geom.as<ImgGeom>(); r.rects = d_rects_tmp.as<int>(); r.tab = tab;
+  r.out = h->d_roi_rgb.as<uint8_t>(); r.max_det = 1; r.S = h->cfg.cls_input; r.linear = h->cfg.numerics;
+  launch_roi_resize(r, R, h->stream);
+  ClsPost post;
+  post.probs = h->d_probs.as<float>(); post.ids = h->d_ids.as<int>();
+  h->cls->forward(h->d_roi_rgb.as<uint8_t>(), tab.total, h->stream, prof, &post);
+  if (!h->cls->fused_head())
+    launch_softmax_argmax(h->cls->logits(), h->cls->logits_pitch(), h->cls->num_classes(), h->d_probs.as<float>(), h->d_ids.as<int>(),
+                          nullptr, nullptr, h->cfg.max_det, nullptr, tab.total, h->max_rois, h->stream);
+  LP_HIP(hipMemcpyAsync(ids, h->d_ids.p, (size_t)R * 4, hipMemcpyDeviceToHost, h->stream));
+  LP_HIP(hipMemcpyAsync(probs, h->d_probs.p, (size_t)R * h->cls->num_classes() * 4, hipMemcpyDeviceToHost, h->stream));
+  LP_HIP(hipStreamSynchronize(h->stream));
+  if (prof) { prof->collect(R); prof->enabled = false; }
+  LP_API_END
+}
+
+}  // extern "C"

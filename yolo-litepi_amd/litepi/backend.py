@@ -788,8 +788,8 @@ class HybridPipeline:
             self.engine.tracker_create(**(track_config or {}))
         # ---- upload lanes (an experiment kept behind LITEPI_DROPIN_LANES=<n>, off by default: measured SLOWER, 3.2-3.6 ms per
         # 64-frame call against 2.7-2.9 for one handle -- four 16-frame passes cost 1.4 ms of kernels instead of 0.9 and four
-        # sets of copy workers fight over the cores; the overlap of upload and kernels lives inside lp_run_batch instead, which
-        # walks a large batch in chunks, api.cpp run_batch_chunked).  Lanes are further handles of max_batch / lanes images each
+        # sets of copy workers fight over the cores; walking a large batch in chunks inside lp_run_batch gained nothing either
+        # and was removed).  Lanes are further handles of max_batch / lanes images each
         # (own stream, staging buffer, copy workers, the same models); a call's images are dealt to them in contiguous slices and
         # every slice runs lp_run_batch on its lane from a worker thread (ctypes drops the GIL).  Results do not depend on the
         # split (tests/test_gpu_device_path.py compares both).
