@@ -335,8 +335,9 @@ void Classifier::forward(const uint8_t* rgb, const int* d_R, hipStream_t st, Pro
     fa.s30 = s2w(fused_s2_[1]);
     P0();
     launch_cls_front(fa, maxR_, st);
-    // conv1 0.66 + stage2 2.10 + stage3.0 0.6 MMAC per ROI; bytes: the uint8 crop in, 8 KB out
-    P1("cls_front", "conv1..stage3.0", 2.0 * (0.66e6 + 2.10e6 + 0.60e6), 12288.0 + 8192.0);
+    // conv1 0.66 + stage2 2.10 + stage3.0 0.6 MMAC per ROI; bytes: the uint8 crop in, stage 3.0's two depthwise sets
+    // (staged per ROI, from L2), 8 KB out
+    P1("cls_front", "conv1..stage3.0", 2.0 * (0.66e6 + 2.10e6 + 0.60e6), 12288.0 + 10240.0 + 8192.0);
     ClsBackArgs ba;
     memset(&ba, 0, sizeof(ba));
     ba.in = a_x3_.p; ba.m_dyn = d_R;

@@ -1,7 +1,7 @@
 // Whole-network ShuffleNetV2 x1.0 kernels (cls_net.hip), fp16 storage / fp32 accumulate: host-side declarations.
 // Two launches replace the ~25 of the layer-at-a-time plan (reference: self.model(batch), e2e.py:393, on the
 // ToTensor/Normalize'd 64x64 crops of e2e.py:366-370):
-//   cls_front: one workgroup per ROI   -- conv1+BN+ReLU, maxpool, stage2 (4 blocks), stage3.0       -> [R,4,4,256]
+//   cls_front: one workgroup per ROI (two resident per CU) -- conv1+BN+ReLU, maxpool, stage2 (4 blocks), stage3.0 -> [R,4,4,256]
 //   cls_back : one workgroup per 4 ROIs -- stage3.1-7, stage4 (4 blocks), conv5, mean, fc, softmax, arg-max, scatter
 // Activations never leave LDS inside a launch; weights stream from L2 straight into MFMA A fragments.
 #pragma once

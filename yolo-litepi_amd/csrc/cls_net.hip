@@ -7,12 +7,15 @@
 // trips of tensors that fit in LDS.  Here a workgroup keeps its ROI(s) in LDS from the uint8 crop to the class
 // probabilities; the only traffic is the weight stream (2.6 MB per workgroup pass, served by L2) and 8 KB per ROI
 // between the two kernels.
-//   cls_front: 1 ROI per workgroup (256 .. 64 pixels per map: enough MFMA columns on its own)
-//   cls_back : 4 ROIs per workgroup (16 / 4 pixels per ROI: four ROIs fill one 16-column MFMA tile at stage 4)
+//   cls_front: 1 ROI per workgroup (256 .. 64 pixels per map: enough MFMA columns on its own), two workgroups per CU
+//   cls_back : 4 ROIs per workgroup (16 / 4 pixels per ROI: four ROIs fill one 16-column MFMA tile at stage 4), one
+//              workgroup per CU.  (A third launch behind stage 4.0 with 16 ROIs per pass was measured and lost: the
+//              tail's time follows its chain of phases, not its weight bytes -- DESIGN section 7.)
 // MFMA orientation as everywhere in this library: D[out-channel][pixel] = W . X, A = weight fragments
 // (pack_fused_pw: [tile][K step][lane][8 halfs], read from L2 straight into registers: every fragment is used by
 // exactly one wave, so LDS staging would only add a copy), B = 16 pixels x 8 channels per lane = one ds_read_b128
-// of the NHWC LDS image.  Rows of every LDS image are padded by 16 B (odd number of 16-byte slots per row).
+// of the NHWC LDS image.  Rows of every LDS image are padded by 16 B (odd number of 16-byte slots per row); the
+// 24-channel images of cls_front have 48-byte rows, three slots as they are.
 #include "cls_net.h"
 
 namespace lp {
@@ -265,44 +268,55 @@ __device__ __forceinline__ void s1_block(char* X, int xrow, char* T1, char* T2, 
 
 // =====================================================================================================================
 // cls_front: conv1+BN+ReLU (MFMA, straight from the uint8 crop) -> maxpool -> stage2.0..3 -> stage3.0, one ROI per
-// workgroup pass.
-// LDS (bytes):  IN [64 rows][192] uint8 (+16 guard each side)      12352   (later: T2 of the stage-2 blocks)
-//               RA: STEM [32x32][24 ch] fp16 = 49152                49152   (later: T1 / D1 / stage3.0 buffers)
-//               POOL [16x16][24 ch, 64 B rows]                      16384
-//               X2 [64 px][2 x 64 ch + 16 B]                        17408
+// workgroup pass, TWO workgroups per CU: the whole kernel is one latency chain (crop, ~20 barrier-separated phases of a
+// few hundred cycles of work each), and a second resident workgroup is the only thing a CU can run behind it.  That
+// needs <= 80 KB of LDS and <= 128 registers, so buffers that are live in different phases share three regions:
+//   region  bytes   tenants, in the order of a ROI's pass
+//   R0      14336   IN [64 rows][192] uint8 (+16 B guard each side) -> POOL [16x16][24 ch, 48 B rows]
+//                   -> T2 [64 px][144] of stage 2 | SA: stage3.0's branch1 depthwise set, fp32 [10][128]
+//   R1      39936   STEM [32x32][24 ch] (runs on into R2) -> T1 [256 px][144] | D1 [64 px][48 B rows]
+//                   -> T1' [64 px][144] of stage2.1-3 -> stage3.0's T1c, D1c, T2c, X3 | SB: its branch2 depthwise set
+//   R2      17408   tail of STEM -> X2 [64 px][2 x 64 ch + 16 B]
+// Every change of tenant has a barrier between the old tenant's last read and the new one's first write; each is named
+// where the new tenant is first written.  Behind the regions: the parameters that stay for the workgroup's life.
 // =====================================================================================================================
 #define CF_IN 16
-#define CF_RA 12352
-#define CF_POOL (CF_RA + 49152)
-#define CF_X2 (CF_POOL + 16384)
+#define CF_R0SZ 14336
+#define CF_R1 CF_R0SZ
+#define CF_R1SZ 39936
+#define CF_X2 (CF_R1 + CF_R1SZ)
 #define CF_LDS (CF_X2 + 17408)
 #define CF_DW (10 * 64 * 4)      /* depthwise parameters of the running stride-1 block, fp32 [10][64], behind everything else */
 #define CF_BI (3 * 2 * 64 * 4)   /* pointwise biases of the stage's stride-1 blocks, fp32 [3][2][64] */
-#define CF_S2 ((10 * 24 + 10 * 64 + 10 * 128 + 10 * 128) * 4)   /* depthwise parameters of stage2.0 (24 | 64 ch) and stage3.0 (128 | 128) */
-#define CF_POOLROW 64
+#define CF_S2 ((10 * 24 + 10 * 64) * 4)   /* depthwise parameters of stage2.0 (24 | 64 ch) */
+#define CF_S3SET (10 * 128 * 4)  /* one depthwise set of stage3.0, staged per ROI (SA, SB) */
+#define CF_POOLROW 48            /* 24 ch x 2 B exactly: 3 slots of 16 B, odd like every padded row */
 #define CF_T1ROW 144   /* 64 ch x 2 B + 16 */
 #define CF_X2ROW 272   /* 128 ch x 2 B + 16 */
 #define CF_X3ROW 528   /* 256 ch x 2 B + 16 */
+#define CF_SA (64 * CF_T1ROW)                          /* in R0, behind T2 */
+#define CF_SB (CF_R1 + 96 * CF_X2ROW + 16 * CF_X3ROW)  /* in R1, behind stage3.0's buffers */
+static_assert(CF_IN + 12288 + 16 <= CF_R0SZ && 256 * CF_POOLROW <= CF_R0SZ && CF_SA + CF_S3SET <= CF_R0SZ, "cls_front R0");
+static_assert(256 * CF_T1ROW + 64 * CF_POOLROW <= CF_R1SZ && CF_SB + CF_S3SET <= CF_R1 + CF_R1SZ, "cls_front R1");
+static_assert(32 * 32 * 48 <= CF_R1SZ + 17408, "STEM must fit R1 + R2");
+static_assert(CF_LDS + CF_DW + CF_BI + CF_S2 <= 81920, "cls_front: two workgroups per CU need <= 80 KB of LDS each");
 
-__global__ __launch_bounds__(CN_THREADS) void cls_front_kernel(const ClsFrontArgs a) {
+__global__ __launch_bounds__(CN_THREADS, 4) void cls_front_kernel(const ClsFrontArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid0 = threadIdx.x, lane0 = tid0 & 63;
   const int R = *a.m_dyn;
   if ((int)blockIdx.x >= R) return;
   char* IN = smem + CF_IN;
-  char* RA = smem + CF_RA;
-  char* POOL = smem + CF_POOL;
+  char* R1 = smem + CF_R1;
+  char* POOL = smem;
   char* X2 = smem + CF_X2;
-  char* T2 = smem;  // [64 px][144]: the IN region is dead once the stem has run
-  // X2's padding channels are never written by the shuffle stores and must read as zero
-  for (int i = tid0; i < 64 * CF_X2ROW / 16; i += CN_THREADS) *reinterpret_cast<u32x4*>(X2 + i * 16) = u32x4{0u, 0u, 0u, 0u};
-  if (tid0 < 2) *reinterpret_cast<u32x4*>(smem + (tid0 ? CF_IN + 12288 : 0)) = u32x4{0u, 0u, 0u, 0u};  // guards
+  char* T2 = smem;  // [64 px][144]
   stage_biases<BFP2, 3>(reinterpret_cast<float*>(smem + CF_LDS + CF_DW), a.s2, tid0);   // (published by the first barrier below)
   float* S2P = reinterpret_cast<float*>(smem + CF_LDS + CF_DW + CF_BI);   // stride-2 blocks' depthwise parameters, as above
   stage_dw<24>(S2P, a.s20.dw1, a.s20.dw1b, tid0);
   stage_dw<64>(S2P + 240, a.s20.dw2, a.s20.dw2b, tid0);
-  stage_dw<128>(S2P + 240 + 640, a.s30.dw1, a.s30.dw1b, tid0);
-  stage_dw<128>(S2P + 240 + 640 + 1280, a.s30.dw2, a.s30.dw2b, tid0);
+  const float* SA = reinterpret_cast<const float*>(smem + CF_SA);
+  const float* SB = reinterpret_cast<const float*>(smem + CF_SB);
   const half8 sa0 = __builtin_bit_cast(half8, a.stem_w[lane0]), sa1 = __builtin_bit_cast(half8, a.stem_w[64 + lane0]);
 
   for (int r = blockIdx.x; r < R; r += gridDim.x) {
@@ -310,8 +324,10 @@ __global__ __launch_bounds__(CN_THREADS) void cls_front_kernel(const ClsFrontArg
     asm volatile("" : "+v"(tid), "+v"(lane));
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, col = lane & 15;
-    // ---- crop -> LDS (12288 B, 16 B per lane)
+    // ---- crop -> LDS (12288 B, 16 B per lane).  IN takes R0 from the previous ROI's T2 and SA, last read (stage 2.3's
+    //      pw2, stage 3.0's first depthwise) before the barrier that ends the ROI loop; the guards go with it.
     {
+      if (tid < 2) *reinterpret_cast<u32x4*>(smem + (tid ? CF_IN + 12288 : 0)) = u32x4{0u, 0u, 0u, 0u};
       const u32x4* src = reinterpret_cast<const u32x4*>(a.rgb + (size_t)r * 12288);
       for (int i = tid; i < 768; i += CN_THREADS) *reinterpret_cast<u32x4*>(IN + i * 16) = src[i];
     }
@@ -360,7 +376,9 @@ __global__ __launch_bounds__(CN_THREADS) void cls_front_kernel(const ClsFrontArg
       c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(sa1, bf, c1, 0, 0, 0);
       const int ci = (oy == 0 ? 1 : 0) | (ox == 0 ? 2 : 0);
       const floatx4 bb0 = *reinterpret_cast<const floatx4*>(a.stem_b + ci * 32 + 4 * g);
-      char* o = RA + (oy * 32 + ox) * 48;
+      // STEM takes R1 and the head of R2 from the previous ROI's stage-3.0 buffers and X2: X2 was last read by stage 3.0's
+      // pw1 / depthwise, X3 by the copy to global, both before the barrier that ends the ROI loop
+      char* o = R1 + (oy * 32 + ox) * 48;
       half4 q;
 #pragma unroll
       for (int i = 0; i < 4; ++i) q[i] = (half_t)fmaxf(c0[i] + bb0[i], 0.f);
@@ -373,7 +391,8 @@ __global__ __launch_bounds__(CN_THREADS) void cls_front_kernel(const ClsFrontArg
       }
     }
     __syncthreads();
-    // ---- maxpool 3x3/s2/p1: [32x32x24] -> POOL [16x16][24]
+    // ---- maxpool 3x3/s2/p1: [32x32x24] -> POOL [16x16][24].  POOL takes R0 from IN, last read by the stem before the
+    //      barrier above.
     for (int i = tid; i < 768; i += CN_THREADS) {
       const int cg = i % 3, px = i / 3;
       const int oy = px >> 4, ox = px & 15;
@@ -386,7 +405,7 @@ __global__ __launch_bounds__(CN_THREADS) void cls_front_kernel(const ClsFrontArg
         for (int kx = 0; kx < 3; ++kx) {
           const int iy = 2 * oy - 1 + ky, ix = 2 * ox - 1 + kx;
           if (iy >= 0 && ix >= 0) {  // iy, ix <= 31 always
-            const half8 v = *reinterpret_cast<const half8*>(RA + (iy * 32 + ix) * 48 + cg * 16);
+            const half8 v = *reinterpret_cast<const half8*>(R1 + (iy * 32 + ix) * 48 + cg * 16);
 #pragma unroll
             for (int j = 0; j < 8; ++j) m[j] = v[j] > m[j] ? v[j] : m[j];
           }
@@ -397,8 +416,11 @@ __global__ __launch_bounds__(CN_THREADS) void cls_front_kernel(const ClsFrontArg
     __syncthreads();
 
     // ================= stage2.0 (stride 2): 16x16x24 -> 8x8x116 =================
-    char* T1 = RA;               // [256 px][144]
-    char* D1 = RA + 256 * CF_T1ROW;  // [64 px][64 B rows] branch1 depthwise output (24 ch)
+    // T1, D1 and X2 take R1 / R2 from STEM, last read by the maxpool before the barrier above.  X2's padding channels are
+    // never written by the shuffle stores and must read as zero: STEM ran over them, so they are cleared for every ROI.
+    char* T1 = R1;               // [256 px][144]
+    char* D1 = R1 + 256 * CF_T1ROW;  // [64 px][48 B rows] branch1 depthwise output (24 ch)
+    for (int i = tid; i < 64 * CF_X2ROW / 16; i += CN_THREADS) *reinterpret_cast<u32x4*>(X2 + i * 16) = u32x4{0u, 0u, 0u, 0u};
     u32x4 fy[2];                 // final pointwise of this wave's branch: branch1.2 (1 step) or branch2.5 (2 steps)
     {
       const int t = wave & 3, p0 = (wave >> 2) * 128;
@@ -407,17 +429,30 @@ __global__ __launch_bounds__(CN_THREADS) void cls_front_kernel(const ClsFrontArg
       gemm_acc<1, 8>(fpw1, 1, 0, POOL, CF_POOLROW, 24, p0, lane, acc);
       store_relu<8>(T1, CF_T1ROW, p0, t, a.s20.pw1b, acc, lane);
       if (wave < 4) wload<2>(fy, a.s20.pwb1, t, 1, lane); else wload<2>(fy, a.s20.pw2, t, 2, lane);
-      dwconv<24, 16, 8, 2>(POOL, CF_POOLROW, D1, 64, S2P, S2P + 9 * 24, 1, tid);
+      dwconv<24, 16, 8, 2>(POOL, CF_POOLROW, D1, CF_POOLROW, S2P, S2P + 9 * 24, 1, tid);
     }
     __syncthreads();
+    // T2 takes the head of R0 from POOL, last read by pw1 / branch1's depthwise before the barrier above
     dwconv<64, 16, 8, 2>(T1, CF_T1ROW, T2, CF_T1ROW, S2P + 240, S2P + 240 + 9 * 64, 1, tid);
     __syncthreads();
     u32x4 f1[1][2];
+    // stage3.0's two depthwise sets ([9][128] taps + [128] bias each, 640 float4 over 512 threads): requested here, they
+    // land while the GEMM below runs
+    floatx4 s3reg[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      int i = tid + k * CN_THREADS;
+      i = i < 640 ? i : 639;
+      const int set = i >= 320, j = i - set * 320;
+      const float* w = set ? a.s30.dw2 : a.s30.dw1;
+      const float* bb = set ? a.s30.dw2b : a.s30.dw1b;
+      s3reg[k] = j < 288 ? *reinterpret_cast<const floatx4*>(w + 4 * j) : *reinterpret_cast<const floatx4*>(bb + 4 * (j - 288));
+    }
     {
       const int t = wave & 3, which = wave >> 2;
       floatx4 acc[4];
       zero_acc<4>(acc);
-      if (which == 0) gemm_acc<2, 4>(fy, 1, 0, D1, 64, 24, 0, lane, acc);
+      if (which == 0) gemm_acc<2, 4>(fy, 1, 0, D1, CF_POOLROW, 24, 0, lane, acc);
       else gemm_acc<2, 4>(fy, 2, 0, T2, CF_T1ROW, 64, 0, lane, acc);
       wload<2>(f1[0], a.s2[0].w1, t, 2, lane);
       const float* bias = which == 0 ? a.s20.pwb1b : a.s20.pw2b;
@@ -435,15 +470,24 @@ __global__ __launch_bounds__(CN_THREADS) void cls_front_kernel(const ClsFrontArg
       }
     }
     __syncthreads();
+    // SA takes the tail of R0 from POOL (dead since stage 2.0's first barrier), SB the tail of R1 from D1, last read by
+    // branch1's pointwise before the barrier above.  The stride-1 blocks touch neither (T1' and T2 end at 9216 B); their
+    // barriers publish both sets to stage 3.0.
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int i = tid + k * CN_THREADS;
+      if (i < 640) *reinterpret_cast<floatx4*>(smem + (i < 320 ? CF_SA + 16 * i : CF_SB + 16 * (i - 320))) = s3reg[k];
+    }
     // ================= stage2.1-3 (stride 1) on the 64 pixels =================
 #pragma unroll 1
     for (int b = 0; b < 3; ++b)
-      s1_block<BF2, BFP2, 8, 2, 1>(X2, CF_X2ROW, RA, T2, CF_T1ROW, a.s2[b], b + 1 < 3 ? a.s2[b + 1].w1 : nullptr, 1, (wave >> 2) * 32, wave & 3,
+      s1_block<BF2, BFP2, 8, 2, 1>(X2, CF_X2ROW, R1, T2, CF_T1ROW, a.s2[b], b + 1 < 3 ? a.s2[b + 1].w1 : nullptr, 1, (wave >> 2) * 32, wave & 3,
                                    4, f1, tid, reinterpret_cast<float*>(smem + CF_LDS), reinterpret_cast<const float*>(smem + CF_LDS + CF_DW) + b * 2 * BFP2);
 
     // ================= stage3.0 (stride 2): 8x8x116 -> 4x4x232 =================
-    char* T1c = RA;                         // [64 px][272]
-    char* D1c = RA + 64 * CF_X2ROW;         // [16 px][272] branch1 depthwise (128 physical channels)
+    // its buffers take R1 from T1', last read by stage 2.3's depthwise, barriers ago
+    char* T1c = R1;                         // [64 px][272]
+    char* D1c = R1 + 64 * CF_X2ROW;         // [16 px][272] branch1 depthwise (128 physical channels)
     char* T2c = D1c + 16 * CF_X2ROW;        // [16 px][272]
     char* X3 = T2c + 16 * CF_X2ROW;         // [16 px][528]
     {
@@ -456,9 +500,9 @@ __global__ __launch_bounds__(CN_THREADS) void cls_front_kernel(const ClsFrontArg
       zero_acc<4>(acc);
       gemm_acc<4, 4>(fa, 4, 0, X2, CF_X2ROW, 128, 0, lane, acc);
       store_relu<4>(T1c, CF_X2ROW, 0, wave, a.s30.pw1b, acc, lane);
-      dwconv<128, 8, 4, 2>(X2, CF_X2ROW, D1c, CF_X2ROW, S2P + 880, S2P + 880 + 9 * 128, 1, tid);
+      dwconv<128, 8, 4, 2>(X2, CF_X2ROW, D1c, CF_X2ROW, SA, SA + 9 * 128, 1, tid);
       __syncthreads();
-      dwconv<128, 8, 4, 2>(T1c, CF_X2ROW, T2c, CF_X2ROW, S2P + 2160, S2P + 2160 + 9 * 128, 1, tid);
+      dwconv<128, 8, 4, 2>(T1c, CF_X2ROW, T2c, CF_X2ROW, SB, SB + 9 * 128, 1, tid);
       __syncthreads();
       floatx4 y1[1], y2[1];
       zero_acc<1>(y1);
