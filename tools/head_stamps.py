@@ -37,8 +37,13 @@ open(path, "wb").close()          # keep only the second (warm) call
 run()
 e.close()
 raw = np.fromfile(path, dtype=np.uint64)
-# stamps 2..9 (cycles, each minus the one before): a workgroup that leaves at the vote writes 2..7 only; stamp 14 = 1 marks it
-names = ["start", "", "issued", "chunk0 landed", "stage A loop", "A epilogue", "B cls", "cls proj + vote", "B box", "box proj + decode"]
+# stamps 2..9 (cycles, each minus the one before): a workgroup that leaves at the vote writes 2..7 only; stamp 14 = 1 marks it.
+# Split stage A (the v1 default shapes): stage A in front of the vote is the class tower's first conv alone, and a workgroup that
+# stays runs the box tower's behind the vote -- stamps 10..13, in time between 7 and 8: box pass entered, its K loops done (the hand-off
+# and, where MID overlays the input tile, the tile's second staging are inside), its SiLU epilogue entered (behind the overlay barrier)
+# and done.  They are zero in a leaver and on the shapes with the merged stage A (v2, LITEPI_HEAD_MERGED_A=1, the 32-pixel-slot shapes).
+names = {2: "issued", 3: "chunk0 landed", 4: "stage A loop", 5: "A epilogue", 6: "B cls", 7: "cls proj + vote", 10: "(box pass entered)",
+         11: "A box: tile + loop", 12: "A box: barrier", 13: "A box epilogue", 8: "B box", 9: "box proj + decode"}
 off = 0
 while off < len(raw):
     assert raw[off] == 0x48454144
@@ -49,14 +54,16 @@ while off < len(raw):
     left = s[:, 14] == 1
     print(f"level {H}x{H}: {grid} workgroups, {int(left.sum())} left at the vote ({100.0 * left.mean():.1f} %); "
           f"kernel span {(s[:, 15].max() - s[:, 0].min()) / 100:.1f} us")
-    for tag, sel, last in (("stayed", ~left, 10), ("left at the vote", left, 8)):
+    split_a = bool((s[~left][:, 10:14] != 0).all()) if (~left).any() else False
+    stay_order = [2, 3, 4, 5, 6, 7] + ([10, 11, 12, 13] if split_a else []) + [8, 9]
+    for tag, sel, order in (("stayed" + (" (split stage A)" if split_a else ""), ~left, stay_order), ("left at the vote", left, [2, 3, 4, 5, 6, 7])):
         if not sel.any():
             continue
         q = s[sel]
         print(f"  {tag}: {int(sel.sum())} workgroups, per-WG wall {np.median(wall[sel]) / 100:.2f} us median, "
-              f"{np.median(q[:, last - 1] - q[:, 1]):.0f} cycles from start to the last stamp")
+              f"{np.median(q[:, order[-1]] - q[:, 1]):.0f} cycles from start to the last stamp")
         prev = 1
-        for k in range(2, last):
+        for k in order:
             dt = q[:, k] - q[:, prev]
             print(f"   {names[k]:18s} median {np.median(dt):9.0f} cyc   p90 {np.percentile(dt, 90):9.0f}")
             prev = k

@@ -38,6 +38,8 @@ struct HeadLayer {
   int KPT = 0, KSA = 6, NPC = 2, SLOTF = 24, nchunks = 0;   // SLOTF: fragments per weight-ring slot
   int OVL = 0;                                              // MID overlays the input tile in LDS
   int A16 = 0;                                              // stage A on 16x16x32 MFMAs (16-pixel tiles)
+  int SPLIT_A = 0;                                          // A16: class rows of stage A in front of the vote, box rows behind it
+  int KSAC = 0, NCAC = 0, KSAB = 0, NCAB = 0;               // its chunks: half-steps per chunk and chunks of the class | box pass
   std::vector<unsigned short> coff;
   std::vector<unsigned char> csz, cks;
   DevBuf d_stream, d_biasA, d_biasB, d_biasC;

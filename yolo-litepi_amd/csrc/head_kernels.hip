@@ -20,6 +20,18 @@
 // conf?) -> only then the box tower's stage B, the box projection and the decode.  A workgroup nobody voted in returns at the vote:
 // the box tower's second conv is 24 - 47 % of a level's MACs and a typical frame has a handful of candidates among 8400 anchors.
 // What is emitted is unchanged to the bit: the vote is emit_candidate's own test, and neither tower's arithmetic or order changes.
+// SPLIT stage A (HeadCfg::split_a: the default shapes except v2's P5; LITEPI_HEAD_MERGED_A=1 restores the merged one everywhere): the
+// first conv is split by tower as well.  Order: stage A of the CLASS rows only (32*C3T of the 64 + 32*C3T output channels: a third of
+// the MFMAs, SiLUs and MID stores at v1, half at v2) -> class tower's stage B -> class projection -> vote -> and only in a workgroup
+// that stays: stage A of the BOX rows -> SiLU -> MID slots 0-7 -> box tower's stage B -> box projection -> decode.  A 16-row MFMA tile
+// does not depend on the other row tiles and each pass walks K in the same order (tap-major, then 32-channel block) from the same
+// bias, so every MID value is what the merged stage A stores.  MID keeps its layout (box channels in slots 0-7, class from slot 8).
+// Where MID overlays the input tile the class rows' stores destroy it: a workgroup that stays stages its tile a second time from
+// global memory (L2-hot; stage_tile, shared with the prologue) -- loads, then a barrier (the vote word lies in the tile's span and
+// every wave must have read it), then the stores; where MID lies beside the tile (v1 P5) nothing is reloaded.  The weight stream is
+// class-A chunks | class-B chunks | class projection | box-A chunks | box-B chunks | box projection; what sits in wreg at the vote
+// is box-A chunk 0, and the ring runs from box-A's last chunk into box-B's first without a hand-off.  Price: a tile that stays reads
+// its pixel fragments twice and, with two row tiles per half-step, its box pass is LDS-rate-bound (DESIGN.md sections 3 and 7).
 // MFMA: v_mfma_f32_32x32x16_f16, D[out-channel][pixel] = W . X.  A wave computes RT (or 2) row tiles x P pixel tiles per
 // K step: (RT + P) KiB of LDS operands per RT*P MFMAs of 32 cycles = 0.8 - 2 ds_read_b128 per MFMA (two per MFMA and SIMD
 // saturate the LDS); measured, the K loops run at 37-44 cycles per MFMA and are half of a workgroup's cycles -- the rest is
@@ -215,11 +227,64 @@ __device__ __forceinline__ void kchunkA16(const char* ring, int c, int lane16, c
   }
 }
 
+// Input tile (halo 2) of workgroup (n, oy0, ox0) -> IN through registers: rows of RSin 16-byte slots = (pixel, channel group); pad
+// slots, pixels outside the image and the row's tail are zeros (= the conv's zero padding).  A wave takes rows wave, wave + 4, ..;
+// what depends on the lane only (pixel, channel group, validity of a slot) is computed once per 64-slot piece.  All rows are
+// requested, then between() runs (the prologue requests its first weight chunks there; a workgroup that stages its tile a SECOND
+// time -- split stage A with MID over the tile -- puts the barrier there that separates the last reads of what the tile's span
+// held from the stores), then the rows are stored.  guard: the zeroed slot behind the tile's last pixel (A16 with an odd KPT).
+template <int NRW, int NPC, typename F>
+__device__ __forceinline__ void stage_tile(const HeadArgs& a, char* IN, int n, int oy0, int ox0, int wave, int lane, bool guard, F&& between) {
+  const int KPT = a.KPT;
+  const int RWin = a.TW + 4, IHin = a.TH + 4, SPin = 2 * KPT + 1, RSin = RWin * SPin;
+  const unsigned rcp_sp = (65536u + SPin - 1) / SPin;  // exact for slot indices < 2048 (host-checked)
+  int voff[NPC];
+  bool xok[NPC];
+#pragma unroll
+  for (int pc = 0; pc < NPC; ++pc) {
+    const int sl = pc * 64 + lane;
+    const int ix = (int)(((unsigned)sl * rcp_sp) >> 16), cgs = sl - ix * SPin;
+    const int gx = ox0 - 2 + ix;
+    xok[pc] = sl < RSin && gx >= 0 && gx < a.W && ix < RWin && cgs < 2 * KPT;
+    voff[pc] = xok[pc] ? (ix * a.in_pitch + cgs * 8) * 2 : (ox0 >= 2 ? 0 : (2 - ox0) * a.in_pitch * 2);
+  }
+  const char* in_n = reinterpret_cast<const char*>(a.in) + ((long)n * a.H * a.W) * a.in_pitch * 2;
+  u32x4 v[NRW][NPC];
+#pragma unroll
+  for (int j = 0; j < NRW; ++j) {
+    const int iy = wave + 4 * j;
+    const int gy = oy0 - 2 + iy;
+    const bool rok = iy < IHin && gy >= 0 && gy < a.H;
+    const char* rowp = in_n + ((long)(rok ? gy : 0) * a.W + (ox0 - 2)) * a.in_pitch * 2;
+#pragma unroll
+    for (int pc = 0; pc < NPC; ++pc) {
+      // unconditional load from a valid address (voff of an invalid slot points at the row's first in-image pixel), masked after
+      const u32x4 x = *reinterpret_cast<const u32x4*>(rowp + voff[pc]);
+      v[j][pc] = (rok && xok[pc]) ? x : u32x4{0u, 0u, 0u, 0u};
+    }
+  }
+  between();
+#pragma unroll
+  for (int j = 0; j < NRW; ++j) {
+    const int iy = wave + 4 * j;
+#pragma unroll
+    for (int pc = 0; pc < NPC; ++pc) {
+      const int sl = pc * 64 + lane;
+      if (iy < IHin && sl < RSin) *reinterpret_cast<u32x4*>(IN + (iy * RSin + sl) * 16) = v[j][pc];
+    }
+  }
+  // A16 with an odd KPT: the slot behind the tile's last pixel is read (against zero weights) by the last K step of a tap
+  if (guard && (KPT & 1) && wave == 0 && lane == 0) *reinterpret_cast<u32x4*>(IN + IHin * RSin * 16) = u32x4{0u, 0u, 0u, 0u};
+}
+
 // NPC: 64-slot pieces per input-tile row, KSA: K steps per stage-A chunk (both fixed by the level's tile shape, see host)
 // SLOTF: fragments per weight-ring slot (24; 12 for the two-workgroups-per-CU shape), NRW: input-tile rows per wave = ceil((TH+4)/4)
 // A16: stage A on 16x16x32 MFMAs (kchunkA16): PA = 16-pixel tiles per wave, KSA = half-steps per chunk (one tap per chunk)
 // NCA: stage-A chunks of the A16 path = 9 taps x ceil(Cin / 32) K steps / (KSA / 2) K steps per chunk
-template <int C3T, int PA, int PB, int NPC, int KSA, int SLOTF, int NRW, bool OV = (SLOTF == 8), bool A16 = false, int NCA = 9>
+// KSAC != 0: SPLIT stage A (A16 only) -- the class tower's first conv alone in front of the vote (NCAC chunks of KSAC half-steps of
+// C3T row tiles), the box tower's first conv behind it, in the workgroups that stay (NCAB chunks of KSAB half-steps of two row tiles)
+template <int C3T, int PA, int PB, int NPC, int KSA, int SLOTF, int NRW, bool OV = (SLOTF == 8), bool A16 = false, int NCA = 9,
+          int KSAC = 0, int NCAC = 0, int KSAB = 0, int NCAB = 0>
 __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void head_fused_kernel(const HeadArgs a) {
   // SLOTF == 8: THREE workgroups per CU -- MID overlays the input tile (dead after stage A's K loops: one more barrier), 8 KiB
   // ring slots (the projections are then two chunks), <= 168 registers: 53,696 B of LDS (42 granules of 1280 B).
@@ -227,6 +292,8 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
   constexpr int SLOT = SLOTF * 1024, NPW = SLOTF / 4;   // chunk stride in the weight stream; 1 KiB pieces per wave and chunk
   constexpr int SLOTB = SLOTF == 8 ? 8192 - 64 : SLOT;   // ring slot stride in LDS (see kchunk)
   constexpr int SPM = 4 * RT + 1;   // 16-byte slots per MID pixel, one of them padding (odd: conflict-free pixel stride)
+  constexpr bool SPLIT = KSAC != 0;
+  static_assert(!SPLIT || (A16 && NCAC > 0 && KSAB != 0 && NCAB > 0), "the split stage A exists on 16-pixel tiles only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -263,13 +330,15 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
   // A16: the first convs' biases are requested in front of the tile (they initialise the accumulators right behind the prologue;
   // requested there, their round trip stood between the prologue and the first MFMA)
   const float bias_c0 = a.biasC[64];   // class 0's projection bias (the only one a one-class detector needs; used in stage C)
-  floatx4 biasA16[A16 ? 2 * RT : 1];
+  // (split: the class rows' only -- row tiles 4 .. -- ; the box rows' are requested behind the vote, by the workgroups that stay)
+  constexpr int TA0 = SPLIT ? 2 : 0, NTA = SPLIT ? C3T : RT;   // first pair of 16-row tiles and pairs of the pass in front of the vote
+  floatx4 biasA16[A16 ? 2 * NTA : 1];
   if constexpr (A16) {
     const int kgb = (lane >> 4) * 8;
 #pragma unroll
-    for (int t = 0; t < RT; ++t) {
-      biasA16[2 * t] = *reinterpret_cast<const floatx4*>(a.biasA + 32 * t + kgb);
-      biasA16[2 * t + 1] = *reinterpret_cast<const floatx4*>(a.biasA + 32 * t + kgb + 4);
+    for (int t = 0; t < NTA; ++t) {
+      biasA16[2 * t] = *reinterpret_cast<const floatx4*>(a.biasA + 32 * (TA0 + t) + kgb);
+      biasA16[2 * t + 1] = *reinterpret_cast<const floatx4*>(a.biasA + 32 * (TA0 + t) + kgb + 4);
     }
   }
   u32x4 wreg[NPW];
@@ -283,59 +352,23 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
     if (SLOTF == 8 && j == 1 && wave == 3) dst = const_cast<char*>((c & 1) ? f7_1 : f7_0);   // piece 7
     *reinterpret_cast<u32x4*>(dst) = wreg[j];
   };
-  // ---- input tile (halo 2) -> IN through registers: rows of RSin 16-byte slots = (pixel, channel group); pad slots, pixels
-  //      outside the image and the row's tail are zeros (= the conv's zero padding).  A wave takes rows wave, wave + 4, ..;
-  //      what depends on the lane only (pixel, channel group, validity of a slot) is computed once per 64-slot piece.
+  // ---- input tile (halo 2) -> IN through registers (stage_tile); chunk 0 of the weight stream goes through a register set of its
+  //      own so that chunk 1 can be requested in the same breath, both behind the tile's loads and in front of its stores
   {
-    const unsigned rcp_sp = (65536u + SPin - 1) / SPin;  // exact for slot indices < 2048 (host-checked)
-    int voff[NPC];
-    bool xok[NPC];
+    u32x4 w0[NPW];
+    stage_tile<NRW, NPC>(a, IN, n, oy0, ox0, wave, lane, A16, [&]() {
 #pragma unroll
-    for (int pc = 0; pc < NPC; ++pc) {
-      const int sl = pc * 64 + lane;
-      const int ix = (int)(((unsigned)sl * rcp_sp) >> 16), cgs = sl - ix * SPin;
-      const int gx = ox0 - 2 + ix;
-      xok[pc] = sl < RSin && gx >= 0 && gx < a.W && ix < RWin && cgs < 2 * KPT;
-      voff[pc] = xok[pc] ? (ix * a.in_pitch + cgs * 8) * 2 : (ox0 >= 2 ? 0 : (2 - ox0) * a.in_pitch * 2);
-    }
-    const char* in_n = reinterpret_cast<const char*>(a.in) + ((long)n * a.H * a.W) * a.in_pitch * 2;
-    u32x4 v[NRW][NPC];
+      for (int j = 0; j < NPW; ++j) w0[j] = *reinterpret_cast<const u32x4*>(wstream + (wave + 4 * j) * 1024);
+      wsource(1);
 #pragma unroll
-    for (int j = 0; j < NRW; ++j) {
-      const int iy = wave + 4 * j;
-      const int gy = oy0 - 2 + iy;
-      const bool rok = iy < IHin && gy >= 0 && gy < a.H;
-      const char* rowp = in_n + ((long)(rok ? gy : 0) * a.W + (ox0 - 2)) * a.in_pitch * 2;
-#pragma unroll
-      for (int pc = 0; pc < NPC; ++pc) {
-        // unconditional load from a valid address (voff of an invalid slot points at the row's first in-image pixel), masked after
-        const u32x4 x = *reinterpret_cast<const u32x4*>(rowp + voff[pc]);
-        v[j][pc] = (rok && xok[pc]) ? x : u32x4{0u, 0u, 0u, 0u};
-      }
-    }
-    u32x4 w0[NPW];   // chunk 0 goes through a register set of its own so that chunk 1 can be requested in the same breath
-#pragma unroll
-    for (int j = 0; j < NPW; ++j) w0[j] = *reinterpret_cast<const u32x4*>(wstream + (wave + 4 * j) * 1024);
-    wsource(1);
-#pragma unroll
-    for (int j = 0; j < NPW; ++j) wload1(j);
-#pragma unroll
-    for (int j = 0; j < NRW; ++j) {
-      const int iy = wave + 4 * j;
-#pragma unroll
-      for (int pc = 0; pc < NPC; ++pc) {
-        const int sl = pc * 64 + lane;
-        if (iy < IHin && sl < RSin) *reinterpret_cast<u32x4*>(IN + (iy * RSin + sl) * 16) = v[j][pc];
-      }
-    }
+      for (int j = 0; j < NPW; ++j) wload1(j);
+    });
 #pragma unroll
     for (int j = 0; j < NPW; ++j) {
       char* dst = RING + lane * 16 + (wave + 4 * j) * 1024;
       if (SLOTF == 8 && j == 1 && wave == 3) dst = const_cast<char*>(f7_0);
       *reinterpret_cast<u32x4*>(dst) = w0[j];
     }
-    // A16 with an odd KPT: the slot behind the tile's last pixel is read (against zero weights) by the last K step of a tap
-    if (A16 && (KPT & 1) && tid == 0) *reinterpret_cast<u32x4*>(IN + IHin * RSin * 16) = u32x4{0u, 0u, 0u, 0u};
   }
   HD_STAMP(2)
   if (a.flags & 1) __builtin_amdgcn_s_setprio(1);
@@ -363,41 +396,78 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
   };
 
   floatx16 biasB_cls[C3T];
-  // ======================= stage A: [64 + 32*C3T] x (9 * Cin) x region-1 pixels =======================
-  if constexpr (A16) {
-    floatx4 accA[2 * RT][PA];
+  // A16: one pass of the first convs over RTP row tiles per half-step (merged: all of them; split: the class tower's, or the box
+  // tower's), NCP chunks of KSP half-steps.  K step = (tap, 32-channel block): ceil(KPT / 2) steps per tap, the byte offset kept
+  // incrementally.  Cin = 16 (mod 32), v2's 48-channel P3: the last step of a tap reads one pixel's padding slot and the NEXT pixel's
+  // first slot as its channels Cin .. Cin + 15 -- their weights are zero (HeadLayer::build) and what is read is finite: activations,
+  // or the zeroed guard slot behind the tile's last pixel
+  auto stageA16 = [&](auto rtp_, auto ksp_, auto ncp_, auto stamp3_, auto& acc) {
+    constexpr int RTP = decltype(rtp_)::value, KSP = decltype(ksp_)::value, NCP = decltype(ncp_)::value;
+    int cg = 0, dx = 0, boff_run = 0;
+    const int SPT = (KPT + 1) >> 1;
+    const int d_tap = SPin * 16 - 64 * (SPT - 1), d_row = (RWin - 2) * SPin * 16 - 64 * (SPT - 1);
+    auto next_boff = [&]() {
+      const int boff = boff_run;
+      if (++cg == SPT) {
+        cg = 0;
+        if (++dx == 3) { dx = 0; boff_run += d_row; } else boff_run += d_tap;
+      } else {
+        boff_run += 64;
+      }
+      return boff;
+    };
+    half8 af[2][RTP], bf[2][PA];
+    static_for<0, NCP>([&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+      wsource(c + 2);
+      kchunkA16<RTP, PA, KSP, i == 0, i == NCP - 1, (i * (KSP / 2)) & 1, SLOTF>(RING, c, lane16, IN, pixA, next_boff, ring_side, acc, af, bf);
+      if (decltype(stamp3_)::value && i == 0) { HD_STAMP(3) }
+      ++c;
+    });
+  };
+  // A16: SiLU, fp16, -> MID (zero outside the image: stage B's padding) for NT pairs of 16-row tiles: this lane holds channels
+  // 32 (t0 + t) + 8 kg .. + 7 of its pixel in acc[2t] | acc[2t+1]: one 16-byte store each
+  auto mid_store16 = [&](auto nt_, int t0, const auto& acc) {
+    constexpr int NT = decltype(nt_)::value;
+    const bool interior = oy0 >= 1 && ox0 >= 1 && oy0 + TH + 1 <= a.H && ox0 + TW + 1 <= a.W;  // block-uniform
 #pragma unroll
-    for (int t = 0; t < RT; ++t) {   // row tiles 2t, 2t+1 hold channels 32t + 8 kg + {0..3}, {4..7} of this lane's pixel
+    for (int p = 0; p < PA; ++p) {
+      const int pt = wave + 4 * p;
+      const int idx = 16 * pt + sig16;
+      if (pt < nA && idx < R1) {
+        bool inside = true;
+        if (!interior) {
+          const int ry = idx / RW1, rx = idx - ry * RW1;
+          const int gy = oy0 - 1 + ry, gx = ox0 - 1 + rx;
+          inside = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+        }
+        char* dst = MID + idx * SPM * 16 + kg16 * 16 + t0 * 64;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const floatx2 y0 = hd_silu2(floatx2{acc[2 * t][p][0], acc[2 * t][p][1]}), y1 = hd_silu2(floatx2{acc[2 * t][p][2], acc[2 * t][p][3]});
+          const floatx2 y2 = hd_silu2(floatx2{acc[2 * t + 1][p][0], acc[2 * t + 1][p][1]}), y3 = hd_silu2(floatx2{acc[2 * t + 1][p][2], acc[2 * t + 1][p][3]});
+          half8 q = {(half_t)y0[0], (half_t)y0[1], (half_t)y1[0], (half_t)y1[1], (half_t)y2[0], (half_t)y2[1], (half_t)y3[0], (half_t)y3[1]};
+          if (!inside) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) q[j] = (half_t)0.f;
+          }
+          *reinterpret_cast<half8*>(dst + t * 64) = q;
+        }
+      }
+    }
+  };
+  // ======================= stage A: [64 + 32*C3T] x (9 * Cin) x region-1 pixels (split: the class tower's 32*C3T rows) =======================
+  if constexpr (A16) {
+    // pass in front of the vote: all RT pairs of 16-row tiles (merged; pair t = channels 32t ..), or the class tower's C3T pairs from
+    // pair 2 on (split).  A half-step holds NTA row tiles: tiles 0 .. NTA-1 | NTA .. 2 NTA-1 of the pass
+    floatx4 accA[2 * NTA][PA];
+#pragma unroll
+    for (int t = 0; t < NTA; ++t) {   // row tiles 2t, 2t+1 hold channels 32 (TA0 + t) + 8 kg + {0..3}, {4..7} of this lane's pixel
 #pragma unroll
       for (int p = 0; p < PA; ++p) { accA[2 * t][p] = biasA16[2 * t]; accA[2 * t + 1][p] = biasA16[2 * t + 1]; }
     }
-    {
-      // K step = (tap, 32-channel block): ceil(KPT / 2) steps per tap, the byte offset kept incrementally.  Cin = 16 (mod 32), v2's
-      // 48-channel P3: the last step of a tap reads one pixel's padding slot and the NEXT pixel's first slot as its channels
-      // Cin .. Cin + 15 -- their weights are zero (HeadLayer::build) and what is read is finite: activations, or the zeroed guard
-      // slot behind the tile's last pixel
-      int cg = 0, dx = 0, boff_run = 0;
-      const int SPT = (KPT + 1) >> 1;
-      const int d_tap = SPin * 16 - 64 * (SPT - 1), d_row = (RWin - 2) * SPin * 16 - 64 * (SPT - 1);
-      auto next_boff = [&]() {
-        const int boff = boff_run;
-        if (++cg == SPT) {
-          cg = 0;
-          if (++dx == 3) { dx = 0; boff_run += d_row; } else boff_run += d_tap;
-        } else {
-          boff_run += 64;
-        }
-        return boff;
-      };
-      half8 af[2][RT], bf[2][PA];
-      static_for<0, NCA>([&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        wsource(c + 2);
-        kchunkA16<RT, PA, KSA, i == 0, i == NCA - 1, (i * (KSA / 2)) & 1, SLOTF>(RING, c, lane16, IN, pixA, next_boff, ring_side, accA, af, bf);
-        if (i == 0) { HD_STAMP(3) }
-        ++c;
-      });
-    }
+    stageA16(std::integral_constant<int, NTA>{}, std::integral_constant<int, SPLIT ? KSAC : KSA>{}, std::integral_constant<int, SPLIT ? NCAC : NCA>{},
+             std::true_type{}, accA);
     HD_STAMP(4)
     if (a.flags & 1) __builtin_amdgcn_s_setprio(0);
     if (a.flags & 2) __builtin_amdgcn_s_setprio(1);
@@ -405,39 +475,11 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
     //  B's first MFMA; the box tower's are requested behind the vote, by the workgroups that stay)
 #pragma unroll
     for (int rt = 0; rt < C3T; ++rt) biasB_cls[rt] = bias16(a.biasB + 64 + rt * 32 + h * 16);
-    // ---- SiLU, fp16, -> MID: this lane holds channels 32t + 8 kg .. + 7 of its pixel in row tiles 2t | 2t+1: one 16-byte store each
-    {
-      if (OVL) lds_barrier();   // MID overlays the input tile: every wave has read its last stage-A operands
-      // the workgroup's vote word = the padding slot of MID pixel 0 (no MID store or stage-B read touches a padding slot; the
-      // three-per-CU shape keeps ring fragments in those of the LAST eight pixels): cleared here, the class tower's first barrier follows
-      if (tid == 0) *reinterpret_cast<volatile int*>(MID + 4 * RT * 16) = 0;
-      const bool interior = oy0 >= 1 && ox0 >= 1 && oy0 + TH + 1 <= a.H && ox0 + TW + 1 <= a.W;  // block-uniform
-#pragma unroll
-      for (int p = 0; p < PA; ++p) {
-        const int pt = wave + 4 * p;
-        const int idx = 16 * pt + sig16;
-        if (pt < nA && idx < R1) {
-          bool inside = true;
-          if (!interior) {
-            const int ry = idx / RW1, rx = idx - ry * RW1;
-            const int gy = oy0 - 1 + ry, gx = ox0 - 1 + rx;
-            inside = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-          }
-          char* dst = MID + idx * SPM * 16 + kg16 * 16;
-#pragma unroll
-          for (int t = 0; t < RT; ++t) {
-            const floatx2 y0 = hd_silu2(floatx2{accA[2 * t][p][0], accA[2 * t][p][1]}), y1 = hd_silu2(floatx2{accA[2 * t][p][2], accA[2 * t][p][3]});
-            const floatx2 y2 = hd_silu2(floatx2{accA[2 * t + 1][p][0], accA[2 * t + 1][p][1]}), y3 = hd_silu2(floatx2{accA[2 * t + 1][p][2], accA[2 * t + 1][p][3]});
-            half8 q = {(half_t)y0[0], (half_t)y0[1], (half_t)y1[0], (half_t)y1[1], (half_t)y2[0], (half_t)y2[1], (half_t)y3[0], (half_t)y3[1]};
-            if (!inside) {
-#pragma unroll
-              for (int j = 0; j < 8; ++j) q[j] = (half_t)0.f;
-            }
-            *reinterpret_cast<half8*>(dst + t * 64) = q;
-          }
-        }
-      }
-    }
+    if (OVL) lds_barrier();   // MID overlays the input tile: every wave has read its last stage-A operands
+    // the workgroup's vote word = the padding slot of MID pixel 0 (no MID store or stage-B read touches a padding slot; the
+    // three-per-CU shape keeps ring fragments in those of the LAST eight pixels): cleared here, the class tower's first barrier follows
+    if (tid == 0) *reinterpret_cast<volatile int*>(MID + 4 * RT * 16) = 0;
+    mid_store16(std::integral_constant<int, NTA>{}, TA0, accA);
   } else {
     floatx16 accA[RT][PA];
   #pragma unroll
@@ -645,15 +687,50 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
     HD_STAMP(15)
     return;
   }
-  // ---- hand-off across the projection chunk: box-tower chunk 0 (c + 1) is in wreg -- requested behind the class tower's last steps --
-  //      and goes to the slot that held the class tower's last chunk, which every wave left at the barrier above; the chunk after it
-  //      is requested, and the box tower's pipeline starts with a barrier of its own (FIRST) that publishes the slot
+  // ---- hand-off across the projection chunk: box-tower chunk 0 (c + 1; split: its first conv's) is in wreg -- requested behind the
+  //      class tower's last steps -- and goes to the slot that held the class tower's last chunk, which every wave left at the barrier
+  //      above; the chunk after it is requested, and the box tower's pipeline starts with a barrier of its own (FIRST) that publishes the slot
+  auto hand_off = [&]() {
 #pragma unroll
-  for (int j = 0; j < NPW; ++j) wstore1(c + 1, j);
-  wsource(c + 2);
+    for (int j = 0; j < NPW; ++j) wstore1(c + 1, j);
+    wsource(c + 2);
 #pragma unroll
-  for (int j = 0; j < NPW; ++j) wload1(j);
-  ++c;
+    for (int j = 0; j < NPW; ++j) wload1(j);
+    ++c;
+  };
+  if constexpr (SPLIT) {
+    // ======================= stage A, box tower: 64 x (9 * Cin) x region-1 pixels, only in a workgroup that stays =======================
+    HD_STAMP(10)
+    floatx4 biasAb[4];
+    {
+      const int kgb = (lane >> 4) * 8;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) biasAb[t] = *reinterpret_cast<const floatx4*>(a.biasA + 32 * (t >> 1) + kgb + 4 * (t & 1));
+    }
+    if constexpr (OVL) {
+      // the class rows' MID stores went over the input tile: it is staged again (L2-hot).  Its span holds the vote word, which every
+      // wave has read by the barrier between the tile's loads and its stores; the barrier that publishes the tile is the box pass's own
+      stage_tile<NRW, NPC>(a, IN, n, oy0, ox0, wave, lane, true, [&]() {
+        hand_off();
+        lds_barrier();
+      });
+    } else {
+      hand_off();   // IN is intact beside MID
+    }
+    floatx4 accA[4][PA];   // row tiles 0,1 | 2,3: channels 0 .. 63
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int p = 0; p < PA; ++p) accA[t][p] = biasAb[t];
+    stageA16(std::integral_constant<int, 2>{}, std::integral_constant<int, KSAB>{}, std::integral_constant<int, NCAB>{}, std::false_type{}, accA);
+    HD_STAMP(11)
+    if (OVL) lds_barrier();   // MID overlays the input tile: every wave has read its last operands
+    HD_STAMP(12)
+    mid_store16(std::integral_constant<int, 2>{}, 0, accA);
+    HD_STAMP(13)
+  } else {
+    hand_off();
+  }
   // what only the decode needs (anchors, geometry, DFL weights) is requested here and arrives during the box tower
   float anc_x[PB], anc_y[PB], anc_s[PB];
 #pragma unroll
@@ -789,15 +866,17 @@ static size_t head_lds(int th, int tw, int kpt, int c3t, int slotf, int ovl) {
 // slots 64 bytes short of 8 KiB (the LDS granule is 1280 B: 42 granules = 53,760 B per workgroup is the limit, measured with
 // tools/ubench/lds_occupancy.hip; MID + two whole slots would be 53,824), the projections as two chunks, and 168 registers --
 // reached by requesting what only the decode needs (anchors, geometry, DFL weights) late: behind stage A at first, now behind the vote.
-struct HeadCfg { int c3t, kpt, th, tw, pa, pb, npc, ksa, slotf, ovl, a16; };
+struct HeadCfg { int c3t, kpt, th, tw, pa, pb, npc, ksa, slotf, ovl, a16, split_a; };
 // a16 (round 4): stage A on 16x16x32 MFMAs -- pa counts 16-pixel tiles per wave, ksa half-steps per chunk (one tap per chunk)
+// split_a (a16 only): the class tower's first conv alone in front of the vote, the box tower's behind it in the workgroups that stay
+// (LITEPI_HEAD_MERGED_A=1: the merged stage A on every shape); the chunk sizes of the two passes follow from the slot size (build)
 static const HeadCfg kHeadCfg[] = {
-    {1, 2, 8, 16, 3, 1, 2, 2, 8, 1, 1},      // v1 P3: Cin 32, THREE workgroups per CU, stage A on 16-pixel tiles (12 for 180 pixels)
-    {1, 4, 10, 20, 5, 2, 4, 4, 12, 1, 1},    // v1 P4: Cin 64, TWO workgroups per CU, 17 tiles of 16 for 264 pixels
-    {1, 8, 10, 10, 3, 1, 4, 8, 24, 0, 1},    // v1 P5: Cin 128, 9 tiles of 16 for 144 pixels
-    {2, 3, 8, 16, 3, 1, 3, 2, 12, 1, 1},     // v2 P3: Cin 48 (K padded to 64 per tap), 48-channel class tower, TWO workgroups per CU (73.5 KB)
-    {2, 6, 10, 10, 3, 1, 3, 2, 12, 1, 1},    // v2 P4: Cin 96, 9 tiles of 16 for 144 pixels; MID over the input tile + 12-fragment slots: 64.8 KB, TWO per CU
-    {2, 12, 10, 10, 3, 1, 6, 6, 24, 1, 1},   // v2 P5: Cin 192, 10 x 10 tiles (256 workgroups = one round; MID over the input tile: 126 KB)
+    {1, 2, 8, 16, 3, 1, 2, 2, 8, 1, 1, 1},      // v1 P3: Cin 32, THREE workgroups per CU, stage A on 16-pixel tiles (12 for 180 pixels)
+    {1, 4, 10, 20, 5, 2, 4, 4, 12, 1, 1, 1},    // v1 P4: Cin 64, TWO workgroups per CU, 17 tiles of 16 for 264 pixels
+    {1, 8, 10, 10, 3, 1, 4, 8, 24, 0, 1, 1},    // v1 P5: Cin 128, 9 tiles of 16 for 144 pixels
+    {2, 3, 8, 16, 3, 1, 3, 2, 12, 1, 1, 1},  // v2 P3: Cin 48 (K padded to 64 per tap), 48-channel class tower, TWO workgroups per CU (73.5 KB)
+    {2, 6, 10, 10, 3, 1, 3, 2, 12, 1, 1, 1}, // v2 P4: Cin 96, 9 tiles of 16 for 144 pixels; MID over the input tile + 12-fragment slots: 64.8 KB, TWO per CU
+    {2, 12, 10, 10, 3, 1, 6, 6, 24, 1, 1, 0}, // v2 P5: Cin 192, 10 x 10 tiles (256 workgroups = one round; MID over the input tile: 126 KB); merged stage A: split measured slower
     {1, 2, 8, 16, 2, 1, 2, 2, 8, 1, 0},      // v1 P3, round 3's shape: stage A on 32-pixel slots (LITEPI_HEAD_A32=1)
     {1, 2, 8, 16, 2, 1, 2, 2, 12, 0, 0},     // v1 P3: Cin 32, two workgroups per CU (LITEPI_HEAD_2WG=1)
     {1, 2, 16, 16, 3, 2, 2, 6, 24, 0, 0},    // v1 P3: Cin 32
@@ -808,12 +887,16 @@ static const HeadCfg kHeadCfg[] = {
     {2, 6, 10, 10, 2, 1, 3, 6, 24, 0, 0},    // v2 P4: Cin 96
     {2, 12, 8, 8, 1, 1, 5, 6, 24, 0, 0},     // v2 P5: Cin 192
 };
-static const HeadCfg* find_cfg(int c3t, int kpt) {
+static const HeadCfg* find_cfg(int c3t, int kpt, bool* split_a = nullptr) {
+  static const bool merged_a = getenv("LITEPI_HEAD_MERGED_A") != nullptr;   // A/B switch: the merged stage A on every shape
   static const bool one_wg = getenv("LITEPI_HEAD_1WG") != nullptr;   // A/B switches: the 16 x 16 one-workgroup shape,
   static const bool two_wg = getenv("LITEPI_HEAD_2WG") != nullptr;   // the two-workgroup shape of round 2,
   static const bool a32 = getenv("LITEPI_HEAD_A32") != nullptr;      // round 3's stage A (32-pixel slots)
   for (auto& c : kHeadCfg)
-    if (c.c3t == c3t && c.kpt == kpt && !(one_wg && c.slotf <= 12) && !(c.ovl && two_wg) && !(c.a16 && (a32 || one_wg || two_wg))) return &c;
+    if (c.c3t == c3t && c.kpt == kpt && !(one_wg && c.slotf <= 12) && !(c.ovl && two_wg) && !(c.a16 && (a32 || one_wg || two_wg))) {
+      if (split_a) *split_a = c.split_a && !merged_a;
+      return &c;
+    }
   return nullptr;
 }
 
@@ -828,7 +911,8 @@ void HeadLayer::build(int cin_phys, int c3_, int nc_, int h, int w, int batch_hi
   Cin = cin_phys; c3 = c3_; nc = nc_; H = h; W = w;
   C3T = c3 > 32 ? 2 : 1;
   KPT = Cin / 16;
-  const HeadCfg* cfg = find_cfg(C3T, KPT);
+  bool split = false;
+  const HeadCfg* cfg = find_cfg(C3T, KPT, &split);
   LP_CHECK(cfg, LP_ERR_STATE, "Detect head %s: no kernel configuration for Cin %d", name.c_str(), Cin);
   TH = cfg->th; TW = cfg->tw; PA = cfg->pa; PB = cfg->pb; NPC = cfg->npc; KSA = cfg->ksa; SLOTF = cfg->slotf; OVL = cfg->ovl; A16 = cfg->a16;
   lds_bytes = head_lds(TH, TW, KPT, C3T, SLOTF, OVL);
@@ -837,6 +921,20 @@ void HeadLayer::build(int cin_phys, int c3_, int nc_, int h, int w, int batch_hi
   // (12 x 2 for two class row tiles), projections 2 (4) and 8
   LP_CHECK(KSA % 2 != 0 || 9 * KPT / KSA >= 2, LP_ERR_STATE, "Detect head %s: stage A needs two chunks", name.c_str());
   const int SPT = (KPT + 1) / 2;   // A16: K steps of 32 channels per tap (Cin = 16 mod 32: the last one half zero weights)
+  // split stage A: a pass of RTP row tiles per half-step puts as many K steps (2 RTP fragments each) into a chunk as a slot addresses
+  // -- fragment 7 of an 8-fragment slot is not addressable -- and as divide the 9 SPT steps of the conv
+  SPLIT_A = cfg && A16 && split;
+  KSAC = NCAC = KSAB = NCAB = 0;
+  if (SPLIT_A) {
+    auto steps_per_chunk = [&](int rtp) {
+      int d = (SLOTF == 8 ? 7 : SLOTF) / (2 * rtp);
+      while (d > 1 && (9 * SPT) % d != 0) --d;
+      return d;
+    };
+    const int kc = steps_per_chunk(C3T), kb = steps_per_chunk(2);
+    LP_CHECK(kc >= 1 && kb >= 1, LP_ERR_STATE, "Detect head %s: a K step of the split stage A does not fit a ring slot", name.c_str());
+    KSAC = 2 * kc; NCAC = 9 * SPT / kc; KSAB = 2 * kb; NCAB = 9 * SPT / kb;
+  }
   if (A16)   // a chunk is KSA half-steps = KSA / 2 K steps x two row halves; fragment 7 of an 8-fragment slot is not addressable
     LP_CHECK(KSA % 2 == 0 && (9 * SPT) % (KSA / 2) == 0 && RT * KSA <= (SLOTF == 8 ? 7 : SLOTF) && (TH + 2) * (TW + 2) <= 64 * PA &&
                  (KPT % 2 == 0 || (OVL && (size_t)(TH + 4) * (TW + 4) * (2 * KPT + 1) + 1 <= (size_t)(TH + 2) * (TW + 2) * (4 * RT + 1))), LP_ERR_STATE,   // (odd KPT: the zeroed guard slot behind the tile lies inside MID's span)
@@ -878,21 +976,24 @@ void HeadLayer::build(int cin_phys, int c3_, int nc_, int h, int w, int batch_hi
         stream[base + lane * 8 + j] = f32_to_f16(weight_of(lane & 15, 8 * slot + j));
       }
   };
-  if (A16) {
+  // one pass of the A16 first convs: RTP row tiles per half-step from row tile R0 on, KPC K steps per chunk
+  auto packA16 = [&](int R0, int RTP, int KPC) {
     for (int ks = 0; ks < 9 * SPT; ++ks) {
       const int tap = ks / SPT, q = ks % SPT;
-      if (ks % (KSA / 2) == 0) begin_chunk();
+      if (ks % KPC == 0) begin_chunk();
       for (int rh = 0; rh < 2; ++rh)
-        for (int rt = 0; rt < RT; ++rt)
+        for (int rt = 0; rt < RTP; ++rt)
           frag16([&](int r, int e) {
-            const int R = rh * RT + rt;
+            const int R = R0 + rh * RTP + rt;
             const int c = 32 * (R >> 1) + 8 * (r >> 2) + 4 * (R & 1) + (r & 3);   // physical MID channel
             const int src = c < 64 ? c : (c - 64 < c3 ? 64 + (c - 64) : -1);
             return (src < 0 || 32 * q + e >= Cin) ? 0.f : wa[((size_t)src * 9 + tap) * Cin + 32 * q + e];
           });
-      if (ks % (KSA / 2) == KSA / 2 - 1) end_chunk(KSA);
+      if (ks % KPC == KPC - 1) end_chunk(2 * KPC);
     }
-  }
+  };
+  if (A16 && !SPLIT_A) packA16(0, RT, KSA / 2);
+  if (SPLIT_A) packA16(4, C3T, KSAC / 2);   // the class rows: row tiles 4 ..; the box rows follow the class projection
   // ---- stage A: K step (tap, cg): element e = input channel 16*cg + e
   for (int ks = 0; ks < (A16 ? 0 : 9 * KPT); ++ks) {
     if (ks % KSA == 0) begin_chunk();
@@ -938,8 +1039,10 @@ void HeadLayer::build(int cin_phys, int c3_, int nc_, int h, int w, int batch_hi
       });
   };
   // stream order = consumption order: A chunks | class-B chunks | class projection | box-B chunks | box projection (a workgroup
-  // whose tile holds no candidate leaves behind the class projection)
+  // whose tile holds no candidate leaves behind the class projection); split stage A: class-A chunks | class-B chunks | class
+  // projection | box-A chunks | box-B chunks | box projection
   begin_chunk(); cls_proj(); end_chunk(0);
+  if (SPLIT_A) packA16(0, 2, KSAB / 2);
   // ---- stage B box: K step kq = (tap, cg), 4 per tap
   const int KSB = SLOTF / 2;   // two row tiles per step
   for (int kq = 0; kq < 36; ++kq) {
@@ -952,7 +1055,7 @@ void HeadLayer::build(int cin_phys, int c3_, int nc_, int h, int w, int batch_hi
   begin_chunk(); box_proj(); end_chunk(0);
   nchunks = (int)coff.size();
   {  // what the kernel's chunk counter walks through: stage A, the class tower, its projection, the box tower, its projection
-    const int ncA = A16 ? 9 * SPT / (KSA / 2) : 9 * KPT / KSA, ncC = C3T == 2 ? 36 / (SLOTF / 2) : 18 / (SLOTF >= 18 ? 18 : 6);
+    const int ncA = SPLIT_A ? NCAC + NCAB : (A16 ? 9 * SPT / (KSA / 2) : 9 * KPT / KSA), ncC = C3T == 2 ? 36 / (SLOTF / 2) : 18 / (SLOTF >= 18 ? 18 : 6);
     LP_CHECK(nchunks == ncA + ncC + 1 + 36 / (SLOTF / 2) + 1, LP_ERR_STATE, "Detect head %s: %d chunks in the weight stream", name.c_str(), nchunks);
   }
   LP_CHECK(nchunks <= 64 && stream.size() / 512 < 65536, LP_ERR_STATE, "Detect head: weight stream too long (%d chunks)", nchunks);
@@ -993,7 +1096,7 @@ void HeadLayer::launch(const View& in, int N, int anchor_off, int A, const float
   DevBuf d_stamps;
   if (stamp_path && *stamp_path) {
     d_stamps.alloc((size_t)grid.x * 16 * 8);
-    LP_HIP(hipMemsetAsync(d_stamps.p, 0, (size_t)grid.x * 16 * 8, st));   // a workgroup that leaves at the vote writes stamps 0-7, 14 and 15 only
+    LP_HIP(hipMemsetAsync(d_stamps.p, 0, (size_t)grid.x * 16 * 8, st));   // a workgroup that leaves at the vote writes stamps 0-7, 14 and 15 only (10-13: the split stage A's box pass)
     a.stamps = d_stamps.as<unsigned long long>();
   }
 #define LP_HEAD(C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_)                                                                          \
@@ -1016,7 +1119,21 @@ void HeadLayer::launch(const View& in, int N, int anchor_off, int A, const float
     set_max_dynamic_lds(reinterpret_cast<const void*>(head_fused_kernel<C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_, true, NCA_>), 160 * 1024); \
     LP_LAUNCH((head_fused_kernel<C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_, true, NCA_>), grid, dim3(256), lds_bytes, st, a);                 \
   }
-  if (A16 && C3T == 2 && KPT == 3) LP_HEAD16N(2, 3, 1, 3, 2, 12, 3, true, 18)
+  // split stage A: the kernel's chunk shapes of the two passes are template arguments; they must be what build() packed
+#define LP_HEAD16S(C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_, KSAC_, NCAC_, KSAB_, NCAB_)                                                      \
+  {                                                                                                                                                \
+    LP_CHECK(KSAC == KSAC_ && NCAC == NCAC_ && KSAB == KSAB_ && NCAB == NCAB_, LP_ERR_STATE, "Detect head %s: split stage A packed as %d x %d | %d x %d", \
+             name.c_str(), NCAC, KSAC, NCAB, KSAB);                                                                                                \
+    set_max_dynamic_lds(reinterpret_cast<const void*>(head_fused_kernel<C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_, true, 9, KSAC_, NCAC_, KSAB_, NCAB_>), 160 * 1024); \
+    LP_LAUNCH((head_fused_kernel<C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_, true, 9, KSAC_, NCAC_, KSAB_, NCAB_>), grid, dim3(256), lds_bytes, st, a); \
+  }
+  if (SPLIT_A && C3T == 1 && KPT == 2) LP_HEAD16S(1, 3, 1, 2, 2, 8, 3, true, 6, 3, 2, 9)
+  else if (SPLIT_A && C3T == 1 && KPT == 4) LP_HEAD16S(1, 5, 2, 4, 4, 12, 4, true, 12, 3, 6, 6)
+  else if (SPLIT_A && C3T == 1 && KPT == 8) LP_HEAD16S(1, 3, 1, 4, 8, 24, 5, false, 24, 3, 12, 6)
+  else if (SPLIT_A && C3T == 2 && KPT == 3) LP_HEAD16S(2, 3, 1, 3, 2, 12, 3, true, 6, 6, 6, 6)
+  else if (SPLIT_A && C3T == 2 && KPT == 6) LP_HEAD16S(2, 3, 1, 3, 2, 12, 4, true, 6, 9, 6, 9)
+  else if (SPLIT_A) throw Error(LP_ERR_STATE, "Detect head: no split-stage-A kernel for this shape");
+  else if (A16 && C3T == 2 && KPT == 3) LP_HEAD16N(2, 3, 1, 3, 2, 12, 3, true, 18)
   else if (A16 && C3T == 2 && KPT == 6) LP_HEAD16N(2, 3, 1, 3, 2, 12, 4, true, 27)
   else if (A16 && C3T == 2 && KPT == 12) LP_HEAD16N(2, 3, 1, 6, 6, 24, 4, true, 18)
   else if (A16 && KPT == 2) LP_HEAD16(1, 3, 1, 2, 2, 8, 3, true)
@@ -1036,6 +1153,7 @@ void HeadLayer::launch(const View& in, int N, int anchor_off, int A, const float
 #undef LP_HEAD2
 #undef LP_HEAD16
 #undef LP_HEAD16N
+#undef LP_HEAD16S
   LP_HIP(hipGetLastError());
   if (a.stamps) {  // diagnostic: dump [grid][16] stamps, one record per launch
     LP_HIP(hipStreamSynchronize(st));
