@@ -357,7 +357,8 @@ int lp_profile_read(lp_handle* h, lp_kernel_time* out, int cap, int* n);
 int lp_detector_info(lp_handle* h, int* num_anchors, int* num_det_classes, int* reg_max,
                      double* conv_macs_per_image);
 /* Copy an intermediate detector blob of the last lp_detect_raw call to host as fp32
- * logical [B,C,H,W] (NCNN blob names, e.g. "44" = P3).  Test/bisect aid. */
+ * logical [B,C,H,W] (NCNN blob names, e.g. "44" = P3), B = the whole images that cap floats
+ * hold: at least one; more than the handle's capacity is an error.  out NULL: only C, H, W.  Test/bisect aid. */
 int lp_debug_blob(lp_handle* h, const char* blob, float* out, int64_t cap, int* C, int* H, int* W);
 /* Run one convolution through the chosen kernel family on host data (tests):
  * x fp32 [N,Cin,H,W], w fp32 [Cout,Cin,k,k], bias [Cout] or NULL, res [N,Cout,Ho,Wo] or NULL. */

@@ -168,6 +168,12 @@ int lp_debug_blob(lp_handle* h, const char* blob, float* out, int64_t cap, int* 
   LP_HIP(hipStreamSynchronize(h->stream));
   std::vector<float> v;
   h->det->fetch_blob(blob, 1, v, *C, *H, *W);
+  // as many leading images of the last batch as the caller's buffer holds (at least one, at most the handle's capacity)
+  const int64_t per_image = (int64_t)v.size();
+  if (out && per_image > 0 && cap >= 2 * per_image) {
+    LP_CHECK(cap / per_image <= h->cfg.max_batch, LP_ERR_ARG, "buffer for %lld images, the handle holds %d", (long long)(cap / per_image), h->cfg.max_batch);
+    h->det->fetch_blob(blob, (int)(cap / per_image), v, *C, *H, *W);
+  }
   if (out) {
     LP_CHECK((int64_t)v.size() <= cap, LP_ERR_ARG, "blob needs %zu floats, buffer has %lld", v.size(), (long long)cap);
     memcpy(out, v.data(), v.size() * 4);

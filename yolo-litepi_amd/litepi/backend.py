@@ -349,10 +349,11 @@ class Engine:
                      bytes=buf[i].bytes) for i in range(min(cap, n.value))]
 
     # ---- test hooks ----------------------------------------------------------------------------
-    def debug_blob(self, name: str) -> np.ndarray:
+    def debug_blob(self, name: str, batch: int = 1) -> np.ndarray:
+        """Blob ``name`` of the first ``batch`` images of the last ``detect_raw`` call (at most the handle's capacity)."""
         c, h, w = C.c_int(), C.c_int(), C.c_int()
         check(self.lib, self.lib.lp_debug_blob(self._h, name.encode(), None, 0, C.byref(c), C.byref(h), C.byref(w)))
-        out = np.empty((1, c.value, h.value, w.value), np.float32)
+        out = np.empty((batch, c.value, h.value, w.value), np.float32)
         check(self.lib, self.lib.lp_debug_blob(self._h, name.encode(), out.ctypes.data_as(C.POINTER(C.c_float)), out.size,
                                                C.byref(c), C.byref(h), C.byref(w)))
         return out
