@@ -332,6 +332,92 @@ int lp_track(lp_handle* h, const lp_det* dets, const int* counts, int B, const i
  * (may be NULL) the stream's next id and the number of detections that found the table full */
 int lp_tracker_snapshot(lp_handle* h, int stream, lp_track_state* out, int cap, int* n, float* acc, int* next_id, int* overflow);
 
+/* ---- sign inventory: one record and best crop per finished track (additive to ABI 310) ---- */
+/* The tracker gives every detection an identity; the inventory turns the two record streams (lp_det, lp_track) into the
+ * de-duplicated list of signs: one lp_sign per finished track, with the crop of its best sighting, logged on the device
+ * when the track ends.  It sees only the records of each frame (a separate launch behind the tracker's; the tracker and its
+ * outputs are unchanged) and mirrors the tracker's ageing.  It belongs to the tracker: lp_tracker_create called again and
+ * lp_tracker_destroy destroy it; lp_tracker_reset leaves it alone (the orphaned entries close by the rule).
+ * Per stream it holds max_tracks entries, indexed by tracker slot, and a frame counter, 0 at creation and never reset
+ * (neither by lp_tracker_reset nor by lp_inventory_flush).  Per frame of a stream, with t = the counter's value:
+ *   1 sight   among the frame's first count records (count clamped to 0..max_det), a record with track_id > 0 and
+ *             0 <= slot < max_tracks sights its slot.  A slot out of range is ignored; if several records name one slot, the
+ *             lowest record index counts (the tracker produces neither; host callers can)
+ *   2 close   an open entry closes if its slot is sighted with another id, or if it is not sighted and
+ *             missed + 1 > max_age (the tracker's max_age).  An open entry that is not sighted and does not close: missed += 1
+ *   3 log     the closing entries with hits >= min_hits are appended to the log in ascending slot order, as one block per
+ *             (stream, frame).  When the block does not fit, the lowest slots that fit are written and `dropped` grows by
+ *             the rest.  Across the streams of one call the order of blocks is unspecified; within a stream it is frame order
+ *   4 open /  a sighted slot with no open entry opens one: first_frame = t, and its first sighting is its best whatever its
+ *     update  quality.  Every sighted entry takes last_frame = t, hits, voted_class, voted_conf and vote_weight from the
+ *             lp_track record, and missed = 0.  Quality q in fp32, each operation rounded on its own:
+ *               LP_BEST_AREA (x2 - x1) * (y2 - y1); LP_BEST_DET_CONF det_conf; LP_BEST_CLS_CONF cls_class >= 0 ? cls_conf : -1.0f
+ *             A later sighting replaces the best iff q > best_quality (ties keep the earlier sighting; a NaN never replaces).
+ *             Replacing copies the box, det_class, best_frame = t, best_quality = q and, with crops = 1 and a crop for that
+ *             record, the crop; LP_SIGN_HAS_CROP is set or cleared for that sighting
+ *   5 the counter advances.
+ * lp_inventory_flush closes every open entry of the stream as step 3 does, with LP_SIGN_FLUSHED (the end of a video).
+ * tests/inventory_ref.py restates the rule in NumPy.  DESIGN.md 6e. */
+enum lp_best { LP_BEST_AREA = 0, LP_BEST_DET_CONF = 1, LP_BEST_CLS_CONF = 2 };
+typedef struct lp_inventory_config {
+  int max_signs;    /* capacity of the log of finished signs, 1 .. 1<<20 (default 4096) */
+  int keep_crops;   /* 0/1 (default 1): keep the classifier's input crop of every track's best sighting */
+  int best;         /* one of enum lp_best; default LP_BEST_AREA */
+  int min_hits;     /* >= 0; a finished track is logged only with hits >= min_hits; 0 (default) = the tracker's min_hits */
+  int reserved[12]; /* zero */
+} lp_inventory_config;
+
+typedef struct lp_sign {          /* 64 bytes */
+  int32_t stream, track_id;
+  int32_t first_frame, last_frame;   /* frame numbers of the first and the last sighting */
+  int32_t hits;                      /* lp_track::hits of the last sighting */
+  int32_t voted_class; float voted_conf, vote_weight;   /* of the last sighting's lp_track record */
+  int32_t best_frame; float best_quality;
+  float x1, y1, x2, y2;              /* box of the best sighting */
+  int32_t det_class;                 /* of the best sighting */
+  int32_t flags;                     /* LP_SIGN_HAS_CROP 1, LP_SIGN_FLUSHED 2 */
+} lp_sign;
+#define LP_SIGN_HAS_CROP 1
+#define LP_SIGN_FLUSHED 2
+
+void lp_inventory_default_config(lp_inventory_config* cfg);
+/* pure host, no handle, no device: LP_ERR_ARG for a value outside the ranges above, a non-zero reserved word or NULL */
+int lp_inventory_config_check(const lp_inventory_config* cfg);
+/* LP_ERR_STATE without a tracker; calling it again replaces the inventory (the log is lost, the frame counters restart).
+ * Memory: the gallery of best crops is n_streams x max_tracks x 3 * cls_input^2 bytes (keep_crops only), the log
+ * max_signs x (64 + 3 * cls_input^2).  keep_crops needs a cls_input that is a multiple of 4 (crops move 16 bytes per lane). */
+int lp_inventory_create(lp_handle* h, const lp_inventory_config* cfg);
+int lp_inventory_destroy(lp_handle* h);
+/* dev_dets, dev_counts, dev_tracks, B and stream_ids exactly as the preceding lp_track_device took and wrote them.
+ * Asynchronous on the handle's stream, ordered behind that call with no event; any number of calls may be enqueued without a
+ * synchronise.  crops = 1 asserts that frames 0..B-1 of this call are frames 0..B-1 of the last pipeline call on this handle
+ * (lp_run_batch, lp_run_batch_device, lp_run_tiled, lp_run_tiled_device; the tiled ones index frames, not views), whose ROI
+ * list and classifier input crops the handle still holds: record (b, slot) has a crop iff the ROI list names it among its
+ * first `total` entries.  crops = 0 attaches no crops.  LP_ERR_STATE without a tracker or an inventory; LP_ERR_ARG for B
+ * outside 1..max_batch, a stream id out of range, crops outside 0/1, crops = 1 with keep_crops = 0, or record buffers that
+ * are not 16-byte aligned, before anything is enqueued.  The ROI list names each record at most once (the pipeline's does;
+ * a list installed with lp_test_set_rois that names one twice gets either crop). */
+int lp_inventory_device(lp_handle* h, const void* dev_dets, const void* dev_counts, const void* dev_tracks, int B,
+                        const int* stream_ids, int crops);
+/* the same on host records (uploads [B * max_det] records of both kinds, runs the same kernel; synchronous) */
+int lp_inventory(lp_handle* h, const lp_det* dets, const int* counts, const struct lp_track* tracks, int B, const int* stream_ids,
+                 int crops);
+/* closes every open entry of a stream (-1: of all streams) into the log, with LP_SIGN_FLUSHED; asynchronous */
+int lp_inventory_flush(lp_handle* h, int stream);
+/* synchronises.  *n = the logged signs, *dropped (may be NULL) = the signs lost to a full log since the last drain.
+ * out == NULL: the numbers only, nothing is consumed.  cap < *n: LP_ERR_ARG, nothing is consumed.  Otherwise out receives
+ * the *n signs, crops (may be NULL) their [*n, S, S, 3] uint8 RGB crops (S = cls_input: the bytes the classifier read; zeros
+ * for a sign without LP_SIGN_HAS_CROP), and the log is emptied.  Only a drain resets the count of offered signs: it is an
+ * int32, so drain at least once per 2^31 finished signs (a log that is never drained wraps and then reports 0 / 0). */
+int lp_inventory_drain(lp_handle* h, lp_sign* out, uint8_t* crops, int cap, int* n, int* dropped);
+/* synchronises; the open entries of a stream in slot order as they would be logged now (out may be NULL: *n only;
+ * cap < *n is LP_ERR_ARG) */
+int lp_inventory_open(lp_handle* h, int stream, lp_sign* out, int cap, int* n);
+/* test hooks: put a ROI list (img[r], slot[r]) and its R crops [R, S, S, 3] into the handle as a pipeline call would leave
+ * them / download the last call's (crops, img, slot may be NULL; cap < *n is LP_ERR_ARG when any is given) */
+int lp_test_set_rois(lp_handle* h, const uint8_t* crops, const int* img, const int* slot, int R);
+int lp_debug_rois(lp_handle* h, uint8_t* crops, int* img, int* slot, int cap, int* n);
+
 /* ---- classifier alone ------------------------------------------------------------ */
 /* replaces PyTorchClassifier.predict_batch (e2e.py:378-396) for R host BGR crops of
  * individual sizes: ids [R], probs [R*num_classes] (softmax). */

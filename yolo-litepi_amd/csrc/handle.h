@@ -1,9 +1,11 @@
-// Internal to the C-ABI translation units (api.cpp, pipeline.cpp, pixfmt.cpp, tiling.cpp, tracking.cpp, test_hooks.cpp): the handle
-// behind include/litepi.h's lp_handle, the captured-step cache, and the pipeline pieces the entry points share.
+// Internal to the C-ABI translation units (api.cpp, pipeline.cpp, pixfmt.cpp, tiling.cpp, tracking.cpp, inventory.cpp,
+// test_hooks.cpp): the handle behind include/litepi.h's lp_handle, the captured-step cache, and the pipeline pieces the entry points share.
 #pragma once
 #include <algorithm>
 #include <array>
 #include <functional>
+#include <map>
+#include <vector>
 
 #include "classifier.h"
 #include "common.h"
@@ -13,12 +15,58 @@
 
 namespace lp {
 
+// The call plan both rings carry (one slot: up to max_batch TrackJobs, then the max_batch frame indices): one job per stream
+// present in the call, in order of first appearance; its frames in batch order.  Returns the number of jobs.
+inline int plan_stream_jobs(int* slot, int max_batch, int B, const int* stream_ids) {
+  TrackJob* jobs = reinterpret_cast<TrackJob*>(slot);
+  int* frames = slot + (size_t)max_batch * (sizeof(TrackJob) / sizeof(int));
+  std::map<int, int> job_of;
+  std::vector<int> sid(B, 0), per_job;
+  for (int b = 0; b < B; ++b) {
+    const int s = stream_ids ? stream_ids[b] : 0;
+    auto it = job_of.find(s);
+    if (it == job_of.end()) {
+      it = job_of.emplace(s, (int)per_job.size()).first;
+      jobs[per_job.size()] = TrackJob{s, 0, 0, 0};
+      per_job.push_back(0);
+    }
+    sid[b] = it->second;
+    ++per_job[it->second];
+  }
+  const int n_jobs = (int)per_job.size();
+  for (int j = 0, off = 0; j < n_jobs; ++j) { jobs[j].first = off; off += per_job[j]; }
+  for (int b = 0; b < B; ++b) frames[jobs[sid[b]].first + jobs[sid[b]].nframes++] = b;
+  return n_jobs;
+}
+
+// Sign inventory of a tracker (lp_inventory_*; include/litepi.h): entries, frame counters, the gallery of best crops and the
+// log of finished signs stay in HBM between calls.  Its call plans go through a pinned -> device ring of its own, built like
+// the tracker's: the tracker's ring keeps its re-use timing.
+struct Inventory {
+  static constexpr int RING = 8;
+  lp_inventory_config cfg;
+  int min_hits = 0, crop_bytes = 0;
+  DevBuf entries, frame_no, head, log, log_crops, gallery, roi_of, plan_dev;
+  DevBuf d_dets, d_counts, d_tracks;   // lp_inventory (host records): allocated on first use
+  int* plan_host = nullptr;            // pinned, RING slots of slot_ints
+  size_t slot_ints = 0;
+  hipEvent_t ev[RING] = {};
+  bool busy[RING] = {};
+  int next = 0;
+  ~Inventory() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (plan_host) (void)hipHostFree(plan_host);
+  }
+};
+
 // Sign tracker of a handle (lp_tracker_*, lp_track*; include/litepi.h): the track table, the stream heads and the vote accumulators
 // stay in HBM between calls.  A call's per-stream frame lists are written into a slot of a pinned ring and copied from there
 // into the same slot of a device ring on the handle's stream (a pageable source would synchronise it); a slot is re-used only
 // after the event recorded behind the launch that read it.
 struct Tracker {
   static constexpr int RING = 8;
+  std::unique_ptr<Inventory> inv;   // null until lp_inventory_create: no other path looks at it
   lp_track_config cfg;
   int nc = 1, max_det = 0, max_batch = 0;
   DevBuf table, heads, acc, scratch, plan_dev;

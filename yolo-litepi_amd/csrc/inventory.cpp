@@ -1,0 +1,227 @@
+// Sign inventory (lp_inventory_*; include/litepi.h); the Inventory itself is in handle.h, owned by the handle's Tracker.
+#include "handle.h"
+
+using namespace lp;
+
+static void check_inventory_config(const lp_inventory_config* c) {
+  LP_CHECK(c, LP_ERR_ARG, "null inventory configuration");
+  LP_CHECK(c->max_signs >= 1 && c->max_signs <= (1 << 20), LP_ERR_ARG, "max_signs %d outside 1..%d", c->max_signs, 1 << 20);
+  LP_CHECK(c->keep_crops == 0 || c->keep_crops == 1, LP_ERR_ARG, "keep_crops %d is not 0 or 1", c->keep_crops);
+  LP_CHECK(c->best >= LP_BEST_AREA && c->best <= LP_BEST_CLS_CONF, LP_ERR_ARG, "best %d is no lp_best", c->best);
+  LP_CHECK(c->min_hits >= 0, LP_ERR_ARG, "min_hits %d is negative", c->min_hits);
+  for (int r : c->reserved) LP_CHECK(r == 0, LP_ERR_ARG, "a reserved word of lp_inventory_config is not zero");
+}
+
+static Inventory& inventory_of(lp_handle* h) {
+  LP_CHECK(h, LP_ERR_ARG, "null handle");
+  LP_CHECK(h->trk, LP_ERR_STATE, "no tracker: call lp_tracker_create first");
+  LP_CHECK(h->trk->inv, LP_ERR_STATE, "no inventory: call lp_inventory_create first");
+  return *h->trk->inv;
+}
+
+// everything but the records, the plan and the crops of a call
+static InvArgs base_args(const lp_handle* h) {
+  const Tracker& t = *h->trk;
+  const Inventory& v = *t.inv;
+  InvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.entries = v.entries.as<InvEntry>(); a.frame_no = v.frame_no.as<int>(); a.head = v.head.as<InvHead>(); a.log = v.log.as<lp_sign>();
+  a.log_crops = v.log_crops.as<uint8_t>(); a.gallery = v.gallery.as<uint8_t>(); a.roi_of = v.roi_of.as<int>();
+  a.max_rois = h->max_rois; a.max_det = t.max_det; a.T = t.cfg.max_tracks; a.max_age = t.cfg.max_age; a.min_hits = v.min_hits;
+  a.best = v.cfg.best; a.max_signs = v.cfg.max_signs; a.crop_bytes = v.crop_bytes;
+  return a;
+}
+
+static void check_inventory_call(lp_handle* h, int B, const int* stream_ids, int crops) {
+  const Inventory& v = inventory_of(h);
+  const Tracker& t = *h->trk;
+  LP_CHECK(B >= 1 && B <= t.max_batch, LP_ERR_ARG, "batch %d outside 1..%d", B, t.max_batch);
+  if (stream_ids)
+    for (int b = 0; b < B; ++b)
+      LP_CHECK(stream_ids[b] >= 0 && stream_ids[b] < t.cfg.n_streams, LP_ERR_ARG, "stream_ids[%d] = %d outside 0..%d", b, stream_ids[b],
+               t.cfg.n_streams - 1);
+  LP_CHECK(crops == 0 || crops == 1, LP_ERR_ARG, "crops %d is not 0 or 1", crops);
+  LP_CHECK(!crops || v.cfg.keep_crops, LP_ERR_ARG, "crops = 1 on an inventory created with keep_crops = 0");
+}
+
+// validates everything, then enqueues the plan upload and the launches on the handle's stream
+static void enqueue_inventory(lp_handle* h, const void* dev_dets, const void* dev_counts, const void* dev_tracks, int B, const int* stream_ids,
+                              int crops) {
+  check_inventory_call(h, B, stream_ids, crops);
+  Tracker& t = *h->trk;
+  Inventory& v = *t.inv;
+  LP_CHECK(((uintptr_t)dev_dets | (uintptr_t)dev_tracks) % 16 == 0 && (uintptr_t)dev_counts % 4 == 0, LP_ERR_ARG,
+           "the record buffers must be 16-byte aligned");
+  LP_HIP(hipSetDevice(h->cfg.device));
+  const int k = v.next;
+  if (v.busy[k]) LP_HIP(hipEventSynchronize(v.ev[k]));
+  int* slot = v.plan_host + (size_t)k * v.slot_ints;
+  const int n_jobs = plan_stream_jobs(slot, t.max_batch, B, stream_ids);   // the tracker's plan
+  int* dslot = v.plan_dev.as<int>() + (size_t)k * v.slot_ints;
+  LP_HIP(hipMemcpyAsync(dslot, slot, v.slot_ints * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  InvArgs a = base_args(h);
+  a.dets = static_cast<const lp_det*>(dev_dets); a.counts = static_cast<const int*>(dev_counts); a.tracks = static_cast<const TrackRec*>(dev_tracks);
+  a.jobs = reinterpret_cast<const TrackJob*>(dslot); a.frames = dslot + (size_t)t.max_batch * (sizeof(TrackJob) / sizeof(int));
+  a.B = B;
+  if (crops) {
+    const RoiTable tab = h->roi_table();
+    a.roi_rgb = h->d_roi_rgb.as<uint8_t>(); a.roi_total = tab.total; a.roi_img = tab.img; a.roi_slot = tab.slot;
+  }
+  launch_inventory(a, n_jobs, h->stream);
+  LP_HIP(hipEventRecord(v.ev[k], h->stream));
+  v.busy[k] = true;
+  v.next = (k + 1) % Inventory::RING;
+}
+
+// the first n entries of the log (signs, and their crops when wanted) after a synchronise
+static void read_head(lp_handle* h, Inventory& v, int* n, int* dropped) {
+  LP_HIP(hipSetDevice(h->cfg.device));
+  LP_HIP(hipStreamSynchronize(h->stream));
+  InvHead head;
+  LP_HIP(hipMemcpy(&head, v.head.p, sizeof(head), hipMemcpyDeviceToHost));
+  *n = std::min(std::max(head.logged, 0), v.cfg.max_signs);
+  if (dropped) *dropped = std::max(head.logged - v.cfg.max_signs, 0);
+}
+
+extern "C" {
+
+void lp_inventory_default_config(lp_inventory_config* c) {
+  if (!c) return;
+  memset(c, 0, sizeof(*c));
+  c->max_signs = 4096; c->keep_crops = 1; c->best = LP_BEST_AREA; c->min_hits = 0;
+}
+
+int lp_inventory_config_check(const lp_inventory_config* cfg) {
+  LP_API_BEGIN
+  check_inventory_config(cfg);
+  LP_API_END
+}
+
+int lp_inventory_destroy(lp_handle* h) {
+  LP_API_BEGIN
+  LP_CHECK(h, LP_ERR_ARG, "null handle");
+  if (h->trk && h->trk->inv) {
+    LP_HIP(hipSetDevice(h->cfg.device));
+    LP_HIP(hipStreamSynchronize(h->stream));
+    h->trk->inv.reset();
+  }
+  LP_API_END
+}
+
+int lp_inventory_create(lp_handle* h, const lp_inventory_config* cfg) {
+  LP_API_BEGIN
+  LP_CHECK(h, LP_ERR_ARG, "null handle");
+  check_inventory_config(cfg);
+  LP_CHECK(h->trk, LP_ERR_STATE, "no tracker: call lp_tracker_create first");
+  Tracker& t = *h->trk;
+  const int S = h->cfg.cls_input;
+  LP_CHECK(!cfg->keep_crops || (S > 0 && S % 4 == 0), LP_ERR_ARG, "keep_crops needs a cls_input that is a multiple of 4 (it is %d)", S);
+  LP_HIP(hipSetDevice(h->cfg.device));
+  LP_HIP(hipStreamSynchronize(h->stream));   // a replaced inventory may still be in use
+  std::unique_ptr<Inventory> v(new Inventory());
+  v->cfg = *cfg;
+  v->min_hits = cfg->min_hits > 0 ? cfg->min_hits : t.cfg.min_hits;
+  v->crop_bytes = 3 * S * S;
+  const size_t NS = t.cfg.n_streams, T = t.cfg.max_tracks;
+  v->entries.alloc(NS * T * sizeof(InvEntry));
+  v->frame_no.alloc(NS * sizeof(int));
+  v->head.alloc(sizeof(InvHead));
+  v->log.alloc((size_t)cfg->max_signs * sizeof(lp_sign));
+  if (cfg->keep_crops) {
+    v->log_crops.alloc((size_t)cfg->max_signs * v->crop_bytes, false);
+    v->gallery.alloc(NS * T * v->crop_bytes, false);
+    v->roi_of.alloc((size_t)t.max_batch * t.max_det * sizeof(int));
+  }
+  v->slot_ints = (size_t)t.max_batch * (sizeof(TrackJob) / sizeof(int) + 1);
+  v->plan_dev.alloc(Inventory::RING * v->slot_ints * sizeof(int));
+  LP_HIP(hipHostMalloc(reinterpret_cast<void**>(&v->plan_host), Inventory::RING * v->slot_ints * sizeof(int), hipHostMallocDefault));
+  for (auto& e : v->ev) LP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  t.inv = std::move(v);
+  LP_API_END
+}
+
+int lp_inventory_device(lp_handle* h, const void* dev_dets, const void* dev_counts, const void* dev_tracks, int B, const int* stream_ids,
+                        int crops) {
+  LP_API_BEGIN
+  inventory_of(h);
+  LP_CHECK(dev_dets && dev_counts && dev_tracks, LP_ERR_ARG, "null argument");
+  enqueue_inventory(h, dev_dets, dev_counts, dev_tracks, B, stream_ids, crops);
+  LP_API_END
+}
+
+int lp_inventory(lp_handle* h, const lp_det* dets, const int* counts, const struct lp_track* tracks, int B, const int* stream_ids, int crops) {
+  LP_API_BEGIN
+  Inventory& v = inventory_of(h);
+  LP_CHECK(dets && counts && tracks, LP_ERR_ARG, "null argument");
+  check_inventory_call(h, B, stream_ids, crops);   // every argument error before the first copy is enqueued
+  const Tracker& t = *h->trk;
+  LP_HIP(hipSetDevice(h->cfg.device));
+  const size_t cap = (size_t)t.max_batch * t.max_det, used = (size_t)B * t.max_det;
+  if (!v.d_dets.p) {
+    v.d_dets.alloc(cap * sizeof(lp_det));
+    v.d_counts.alloc((size_t)t.max_batch * sizeof(int));
+    v.d_tracks.alloc(cap * sizeof(TrackRec));
+  }
+  LP_HIP(hipMemcpyAsync(v.d_dets.p, dets, used * sizeof(lp_det), hipMemcpyHostToDevice, h->stream));
+  LP_HIP(hipMemcpyAsync(v.d_counts.p, counts, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  LP_HIP(hipMemcpyAsync(v.d_tracks.p, tracks, used * sizeof(TrackRec), hipMemcpyHostToDevice, h->stream));
+  LP_HIP(hipStreamSynchronize(h->stream));   // the sources are the caller's pageable memory
+  enqueue_inventory(h, v.d_dets.p, v.d_counts.p, v.d_tracks.p, B, stream_ids, crops);
+  LP_HIP(hipStreamSynchronize(h->stream));
+  LP_API_END
+}
+
+int lp_inventory_flush(lp_handle* h, int stream) {
+  LP_API_BEGIN
+  inventory_of(h);
+  const Tracker& t = *h->trk;
+  LP_CHECK(stream >= -1 && stream < t.cfg.n_streams, LP_ERR_ARG, "stream %d outside -1..%d", stream, t.cfg.n_streams - 1);
+  LP_HIP(hipSetDevice(h->cfg.device));
+  launch_inventory_flush(base_args(h), stream < 0 ? 0 : stream, stream < 0 ? t.cfg.n_streams : 1, h->stream);
+  LP_API_END
+}
+
+int lp_inventory_drain(lp_handle* h, lp_sign* out, uint8_t* crops, int cap, int* n, int* dropped) {
+  LP_API_BEGIN
+  Inventory& v = inventory_of(h);
+  LP_CHECK(n, LP_ERR_ARG, "null argument");
+  LP_CHECK(!crops || v.cfg.keep_crops, LP_ERR_ARG, "crops asked of an inventory created with keep_crops = 0");
+  read_head(h, v, n, dropped);
+  if (!out) return LP_OK;
+  LP_CHECK(cap >= *n, LP_ERR_ARG, "%d logged signs do not fit cap = %d", *n, cap);
+  if (*n > 0) {
+    LP_HIP(hipMemcpy(out, v.log.p, (size_t)*n * sizeof(lp_sign), hipMemcpyDeviceToHost));
+    if (crops) {
+      LP_HIP(hipMemcpy(crops, v.log_crops.p, (size_t)*n * v.crop_bytes, hipMemcpyDeviceToHost));
+      for (int i = 0; i < *n; ++i)   // a sign without a crop left its place in the log's crop buffer unwritten
+        if (!(out[i].flags & LP_SIGN_HAS_CROP)) memset(crops + (size_t)i * v.crop_bytes, 0, v.crop_bytes);
+    }
+  }
+  LP_HIP(hipMemsetAsync(v.head.p, 0, sizeof(InvHead), h->stream));
+  LP_HIP(hipStreamSynchronize(h->stream));
+  LP_API_END
+}
+
+int lp_inventory_open(lp_handle* h, int stream, lp_sign* out, int cap, int* n) {
+  LP_API_BEGIN
+  Inventory& v = inventory_of(h);
+  LP_CHECK(n, LP_ERR_ARG, "null argument");
+  const Tracker& t = *h->trk;
+  LP_CHECK(stream >= 0 && stream < t.cfg.n_streams, LP_ERR_ARG, "stream %d outside 0..%d", stream, t.cfg.n_streams - 1);
+  LP_HIP(hipSetDevice(h->cfg.device));
+  LP_HIP(hipStreamSynchronize(h->stream));
+  const int T = t.cfg.max_tracks;
+  std::vector<InvEntry> ent(T);
+  LP_HIP(hipMemcpy(ent.data(), v.entries.as<InvEntry>() + (size_t)stream * T, (size_t)T * sizeof(InvEntry), hipMemcpyDeviceToHost));
+  int open = 0;
+  for (const InvEntry& e : ent) open += e.open != 0;
+  *n = open;
+  if (!out) return LP_OK;
+  LP_CHECK(cap >= open, LP_ERR_ARG, "%d open entries do not fit cap = %d", open, cap);
+  int k = 0;
+  for (const InvEntry& e : ent)
+    if (e.open) out[k++] = e.sign;
+  LP_API_END
+}
+
+}  // extern "C"

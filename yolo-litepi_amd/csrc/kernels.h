@@ -181,6 +181,38 @@ void launch_track(const TrackArgs& a, int n_jobs, hipStream_t st);
 // frees every slot of `n` streams from `first` on (next_id and the overflow counter stay)
 void launch_track_reset(TrackSlot* table, int T, int first, int n, hipStream_t st);
 
+// ---- inventory_kernels.hip (one record + best crop per finished track, include/litepi.h lp_inventory_*) ----
+struct InvEntry {      // one slot of a stream's inventory, 80 bytes, device resident between calls
+  lp_sign sign;        // as it would be logged (flags: LP_SIGN_HAS_CROP only)
+  int open, missed, pad[2];
+};
+struct InvHead { int logged, pad[3]; };   // closings offered to the log since the last drain (beyond max_signs: dropped)
+struct InvArgs {
+  const lp_det* dets;       // [B * max_det]
+  const int* counts;        // [B]
+  const TrackRec* tracks;   // [B * max_det]
+  const TrackJob* jobs;     // [n_jobs]; nframes == 0: flush the stream
+  const int* frames;        // batch indices of the call's frames, grouped by job
+  InvEntry* entries;        // [n_streams][T]
+  int* frame_no;            // [n_streams]
+  InvHead* head;
+  lp_sign* log;             // [max_signs]
+  uint8_t* log_crops;       // [max_signs][crop_bytes] or null
+  uint8_t* gallery;         // [n_streams][T][crop_bytes] or null
+  // crops = 1: the last pipeline call's ROI list and crops, and the record -> ROI index scatter of launch_inventory
+  const uint8_t* roi_rgb;   // null: attach no crops
+  const int* roi_total;
+  const int* roi_img;
+  const int* roi_slot;
+  int* roi_of;              // [max_batch * max_det]
+  int max_rois, B;
+  int max_det, T, max_age, min_hits, best, max_signs, crop_bytes;
+};
+// the record -> ROI scatter (crops only), then one wave per job
+void launch_inventory(const InvArgs& a, int n_jobs, hipStream_t st);
+// closes every open entry of `n` streams from `first` on into the log (LP_SIGN_FLUSHED); jobs / frames / records are not read
+void launch_inventory_flush(const InvArgs& a, int first, int n, hipStream_t st);
+
 // ---- cls_kernels.hip ------------------------------------------------------------------
 // conv1 3x3/s2 (3->CO) + folded BN + ReLU on (x/255 - mean)/std of the uint8 RGB crops
 void launch_cls_stem(int prec, const uint8_t* rgb, const float* w /*[27][CO]*/, const float* bias, int CO,

@@ -351,4 +351,41 @@ int lp_test_letterbox(lp_handle* h, const uint8_t* img, int H, int W, uint8_t* o
   LP_API_END
 }
 
+// the ROI list and the classifier input crops of a pipeline call (tests of the sign inventory's crops)
+int lp_test_set_rois(lp_handle* h, const uint8_t* crops, const int* img, const int* slot, int R) {
+  LP_API_BEGIN
+  LP_CHECK(h && R >= 0 && (R == 0 || (crops && img && slot)), LP_ERR_ARG, "bad argument");
+  LP_CHECK(R <= h->max_rois, LP_ERR_ARG, "%d ROIs exceed max_rois = %d", R, h->max_rois);
+  LP_HIP(hipSetDevice(h->cfg.device));
+  LP_HIP(hipStreamSynchronize(h->stream));
+  const size_t crop = (size_t)h->cfg.cls_input * h->cfg.cls_input * 3;
+  if (R > 0) {
+    LP_HIP(hipMemcpy(h->d_roi_rgb.p, crops, (size_t)R * crop, hipMemcpyHostToDevice));
+    LP_HIP(hipMemcpy(h->d_roi_img.p, img, (size_t)R * 4, hipMemcpyHostToDevice));
+    LP_HIP(hipMemcpy(h->d_roi_slot.p, slot, (size_t)R * 4, hipMemcpyHostToDevice));
+  }
+  const int total[2] = {R, R};
+  LP_HIP(hipMemcpy(h->d_roi_total.p, total, sizeof(total), hipMemcpyHostToDevice));
+  LP_API_END
+}
+
+int lp_debug_rois(lp_handle* h, uint8_t* crops, int* img, int* slot, int cap, int* n) {
+  LP_API_BEGIN
+  LP_CHECK(h && n, LP_ERR_ARG, "null argument");
+  LP_HIP(hipSetDevice(h->cfg.device));
+  LP_HIP(hipStreamSynchronize(h->stream));
+  int total = 0;
+  LP_HIP(hipMemcpy(&total, h->d_roi_total.p, 4, hipMemcpyDeviceToHost));
+  total = std::min(std::max(total, 0), h->max_rois);
+  *n = total;
+  if (!crops && !img && !slot) return LP_OK;
+  LP_CHECK(cap >= total, LP_ERR_ARG, "%d ROIs do not fit cap = %d", total, cap);
+  if (total == 0) return LP_OK;
+  const size_t crop = (size_t)h->cfg.cls_input * h->cfg.cls_input * 3;
+  if (crops) LP_HIP(hipMemcpy(crops, h->d_roi_rgb.p, (size_t)total * crop, hipMemcpyDeviceToHost));
+  if (img) LP_HIP(hipMemcpy(img, h->d_roi_img.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+  if (slot) LP_HIP(hipMemcpy(slot, h->d_roi_slot.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+  LP_API_END
+}
+
 }  // extern "C"

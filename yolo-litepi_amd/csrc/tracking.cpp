@@ -1,6 +1,4 @@
 // Sign tracking (lp_tracker_*, lp_track*; include/litepi.h); the Tracker itself is in handle.h.
-#include <map>
-
 #include "handle.h"
 
 using namespace lp;
@@ -103,25 +101,7 @@ static void enqueue_track(lp_handle* h, const void* dev_dets, const void* dev_co
   const int k = t.next;
   if (t.busy[k]) LP_HIP(hipEventSynchronize(t.ev[k]));
   int* slot = t.plan_host + (size_t)k * t.slot_ints;
-  TrackJob* jobs = reinterpret_cast<TrackJob*>(slot);
-  int* frames = slot + (size_t)t.max_batch * (sizeof(TrackJob) / sizeof(int));
-  // one job per stream present, in order of first appearance; its frames in batch order
-  std::map<int, int> job_of;
-  std::vector<int> sid(B, 0), per_job;
-  for (int b = 0; b < B; ++b) {
-    const int s = stream_ids ? stream_ids[b] : 0;
-    auto it = job_of.find(s);
-    if (it == job_of.end()) {
-      it = job_of.emplace(s, (int)per_job.size()).first;
-      jobs[per_job.size()] = TrackJob{s, 0, 0, 0};
-      per_job.push_back(0);
-    }
-    sid[b] = it->second;
-    ++per_job[it->second];
-  }
-  const int n_jobs = (int)per_job.size();
-  for (int j = 0, off = 0; j < n_jobs; ++j) { jobs[j].first = off; off += per_job[j]; }
-  for (int b = 0; b < B; ++b) frames[jobs[sid[b]].first + jobs[sid[b]].nframes++] = b;
+  const int n_jobs = plan_stream_jobs(slot, t.max_batch, B, stream_ids);
   int* dslot = t.plan_dev.as<int>() + (size_t)k * t.slot_ints;
   LP_HIP(hipMemcpyAsync(dslot, slot, t.slot_ints * sizeof(int), hipMemcpyHostToDevice, h->stream));
   TrackArgs a;

@@ -68,6 +68,25 @@ class LpTrackState(C.Structure):
 
 
 LP_TRACK_CONFIRMED, LP_TRACK_BORN = 1, 2
+
+
+class LpInventoryConfig(C.Structure):
+    _fields_ = [("max_signs", C.c_int), ("keep_crops", C.c_int), ("best", C.c_int), ("min_hits", C.c_int), ("reserved", C.c_int * 12)]
+
+
+class LpSign(C.Structure):
+    _fields_ = [("stream", C.c_int32), ("track_id", C.c_int32), ("first_frame", C.c_int32), ("last_frame", C.c_int32), ("hits", C.c_int32),
+                ("voted_class", C.c_int32), ("voted_conf", C.c_float), ("vote_weight", C.c_float), ("best_frame", C.c_int32),
+                ("best_quality", C.c_float), ("x1", C.c_float), ("y1", C.c_float), ("x2", C.c_float), ("y2", C.c_float),
+                ("det_class", C.c_int32), ("flags", C.c_int32)]
+
+
+LP_BEST_AREA, LP_BEST_DET_CONF, LP_BEST_CLS_CONF = 0, 1, 2
+LP_SIGN_HAS_CROP, LP_SIGN_FLUSHED = 1, 2
+# numpy view of lp_sign records
+SIGN_DTYPE = [("stream", "<i4"), ("track_id", "<i4"), ("first_frame", "<i4"), ("last_frame", "<i4"), ("hits", "<i4"), ("voted_class", "<i4"),
+              ("voted_conf", "<f4"), ("vote_weight", "<f4"), ("best_frame", "<i4"), ("best_quality", "<f4"), ("x1", "<f4"), ("y1", "<f4"),
+              ("x2", "<f4"), ("y2", "<f4"), ("det_class", "<i4"), ("flags", "<i4")]
 # numpy views of lp_track records and of lp_track_state
 TRACK_DTYPE = [("track_id", "<i4"), ("slot", "<i4"), ("hits", "<i4"), ("age", "<i4"), ("voted_class", "<i4"), ("voted_conf", "<f4"),
                ("vote_weight", "<f4"), ("flags", "<i4")]
@@ -89,6 +108,8 @@ SYMBOLS = [
     "lp_frame_layout", "lp_set_input_format", "lp_test_convert_frames",
     "lp_track_default_config", "lp_track_config_check", "lp_tracker_create", "lp_tracker_destroy", "lp_tracker_reset",
     "lp_track_device", "lp_track", "lp_tracker_snapshot",
+    "lp_inventory_default_config", "lp_inventory_config_check", "lp_inventory_create", "lp_inventory_destroy", "lp_inventory_device",
+    "lp_inventory", "lp_inventory_flush", "lp_inventory_drain", "lp_inventory_open", "lp_test_set_rois", "lp_debug_rois",
 ]
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
 
@@ -160,8 +181,21 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_track_device.argtypes = [vp, vp, vp, C.c_int, ip, vp]
     lib.lp_track.argtypes = [vp, vp, ip, C.c_int, ip, vp]
     lib.lp_tracker_snapshot.argtypes = [vp, C.c_int, vp, C.c_int, ip, vp, ip, ip]
+    icp = C.POINTER(LpInventoryConfig)
+    lib.lp_inventory_default_config.argtypes = [icp]
+    lib.lp_inventory_default_config.restype = None
+    lib.lp_inventory_config_check.argtypes = [icp]
+    lib.lp_inventory_create.argtypes = [vp, icp]
+    lib.lp_inventory_destroy.argtypes = [vp]
+    lib.lp_inventory_device.argtypes = [vp, vp, vp, vp, C.c_int, ip, C.c_int]
+    lib.lp_inventory.argtypes = [vp, vp, ip, vp, C.c_int, ip, C.c_int]
+    lib.lp_inventory_flush.argtypes = [vp, C.c_int]
+    lib.lp_inventory_drain.argtypes = [vp, vp, vp, C.c_int, ip, ip]
+    lib.lp_inventory_open.argtypes = [vp, C.c_int, vp, C.c_int, ip]
+    lib.lp_test_set_rois.argtypes = [vp, vp, ip, ip, C.c_int]
+    lib.lp_debug_rois.argtypes = [vp, vp, ip, ip, C.c_int, ip]
     for s in SYMBOLS:
-        if s not in ("lp_last_error", "lp_default_config", "lp_destroy", "lp_track_default_config"):
+        if s not in ("lp_last_error", "lp_default_config", "lp_destroy", "lp_track_default_config", "lp_inventory_default_config"):
             getattr(lib, s).restype = C.c_int
     got = lib.lp_version()
     if got != ABI_VERSION:

@@ -17,7 +17,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _ffi
-from ._ffi import DET_DTYPE, TRACK_DTYPE, TRACK_STATE_DTYPE, LpConfig, LpFrameFormat, LpKernelTime, LpTiming, LpTiling, LpTrackConfig, check
+from ._ffi import (DET_DTYPE, SIGN_DTYPE, TRACK_DTYPE, TRACK_STATE_DTYPE, LpConfig, LpFrameFormat, LpInventoryConfig, LpKernelTime, LpTiming,
+                   LpTiling, LpTrackConfig, check)
 from .pixfmt import CSC_MATRICES, PIXEL_FORMATS, nv12_frame_hw
 
 _PREC = {"fp32": _ffi.LP_FP32, "fp16": _ffi.LP_FP16, "float32": _ffi.LP_FP32, "float16": _ffi.LP_FP16, "half": _ffi.LP_FP16}
@@ -97,6 +98,33 @@ def track_config_check(cfg: Optional[LpTrackConfig]) -> int:
     """lp_track_config_check's status for a configuration (host only, no GPU needed)."""
     lib = _ffi.load_library()
     return lib.lp_track_config_check(C.byref(cfg) if cfg is not None else None)
+
+
+INVENTORY_CONFIG_FIELDS = ("max_signs", "keep_crops", "best", "min_hits")
+INVENTORY_BEST = {"area": _ffi.LP_BEST_AREA, "det_conf": _ffi.LP_BEST_DET_CONF, "cls_conf": _ffi.LP_BEST_CLS_CONF}
+
+
+def inventory_config(**cfg) -> LpInventoryConfig:
+    """lp_inventory_config with the library's defaults and the given fields (host only, no GPU needed); best may be a name of
+    INVENTORY_BEST."""
+    lib = _ffi.load_library()
+    c = LpInventoryConfig()
+    lib.lp_inventory_default_config(C.byref(c))
+    for k, v in cfg.items():
+        if k not in INVENTORY_CONFIG_FIELDS:
+            raise TypeError(f"unknown inventory setting {k!r} (one of {INVENTORY_CONFIG_FIELDS})")
+        if k == "best" and isinstance(v, str):
+            if v not in INVENTORY_BEST:
+                raise ValueError(f"best must be one of {tuple(INVENTORY_BEST)}, got {v!r}")
+            v = INVENTORY_BEST[v]
+        setattr(c, k, int(v))
+    return c
+
+
+def inventory_config_check(cfg: Optional[LpInventoryConfig]) -> int:
+    """lp_inventory_config_check's status for a configuration (host only, no GPU needed)."""
+    lib = _ffi.load_library()
+    return lib.lp_inventory_config_check(C.byref(cfg) if cfg is not None else None)
 
 
 class Engine:
@@ -265,11 +293,13 @@ class Engine:
         c = track_config(**cfg)
         check(self.lib, self.lib.lp_tracker_create(self._h, C.byref(c)))
         self.track_cfg = c
+        self.__dict__.pop("inv_cfg", None)   # the inventory belongs to the tracker it was created on
 
     def tracker_destroy(self) -> None:
         check(self.lib, self.lib.lp_tracker_destroy(self._h))
         if hasattr(self, "track_cfg"):
             del self.track_cfg
+        self.__dict__.pop("inv_cfg", None)
 
     def tracker_reset(self, stream: int = -1) -> None:
         """Frees the tracks of one stream (-1: all); ids keep counting.  Asynchronous on the engine's stream."""
@@ -315,6 +345,82 @@ class Engine:
         check(self.lib, self.lib.lp_tracker_snapshot(self._h, int(stream), st.ctypes.data, n.value, C.byref(n), acc.ctypes.data,
                                                      C.byref(nid), C.byref(ovf)))
         return {"tracks": st, "acc": acc, "next_id": nid.value, "overflow": ovf.value}
+
+    # ---- sign inventory: one record and best crop per finished track ---------------------------
+    def inventory_create(self, **cfg) -> None:
+        """One inventory per tracker (lp_inventory_create); calling it again replaces it.  Settings are lp_inventory_config's fields:
+        max_signs, keep_crops, best ("area" | "det_conf" | "cls_conf" or the enum value), min_hits."""
+        c = inventory_config(**cfg)
+        check(self.lib, self.lib.lp_inventory_create(self._h, C.byref(c)))
+        self.inv_cfg = c
+
+    def inventory_destroy(self) -> None:
+        check(self.lib, self.lib.lp_inventory_destroy(self._h))
+        self.__dict__.pop("inv_cfg", None)
+
+    def inventory(self, dets: np.ndarray, counts, tracks: np.ndarray, stream_ids=None, crops: bool = False) -> None:
+        """lp_inventory on host records: dets [B, max_det] lp_det, counts [B], tracks [B, max_det] lp_track as track() returned
+        them.  crops: frames 0..B-1 are those of the engine's last pipeline call, whose crops are attached.  Synchronous."""
+        d = np.ascontiguousarray(dets, dtype=DET_DTYPE).reshape(-1, self.cfg.max_det)
+        B = d.shape[0]
+        t = np.ascontiguousarray(tracks, dtype=TRACK_DTYPE).reshape(-1, self.cfg.max_det)
+        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+        if cnt.shape != (B,) or t.shape[0] != B:
+            raise ValueError(f"counts and tracks must hold {B} frames, got shapes {cnt.shape} and {t.shape}")
+        ids = self._stream_ids(stream_ids, B)
+        ip = C.POINTER(C.c_int)
+        check(self.lib, self.lib.lp_inventory(self._h, d.ctypes.data, cnt.ctypes.data_as(ip), t.ctypes.data, B,
+                                              None if ids is None else ids.ctypes.data_as(ip), int(crops)))
+
+    def inventory_device(self, dev_dets: int, dev_counts: int, dev_tracks: int, B: int, stream_ids=None, crops: bool = False) -> None:
+        """lp_inventory_device: the buffers and stream ids of the preceding track_device call.  Asynchronous on the engine's stream."""
+        ids = self._stream_ids(stream_ids, B)
+        check(self.lib, self.lib.lp_inventory_device(self._h, C.c_void_p(dev_dets), C.c_void_p(dev_counts), C.c_void_p(dev_tracks), int(B),
+                                                     None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int)), int(crops)))
+
+    def inventory_flush(self, stream: int = -1) -> None:
+        """Closes every open entry of one stream (-1: all) into the log with LP_SIGN_FLUSHED.  Asynchronous."""
+        check(self.lib, self.lib.lp_inventory_flush(self._h, int(stream)))
+
+    def inventory_drain(self, crops: bool = True):
+        """The logged signs since the last drain (synchronises, empties the log): (SIGN_DTYPE records [n], crops [n, S, S, 3] uint8
+        RGB or None, dropped)."""
+        n, dropped = C.c_int(), C.c_int()
+        check(self.lib, self.lib.lp_inventory_drain(self._h, None, None, 0, C.byref(n), C.byref(dropped)))
+        S = self.cfg.cls_input
+        signs = np.zeros(n.value, dtype=SIGN_DTYPE)
+        pix = np.zeros((n.value, S, S, 3), np.uint8) if crops else None
+        check(self.lib, self.lib.lp_inventory_drain(self._h, signs.ctypes.data, None if pix is None else pix.ctypes.data, n.value, C.byref(n),
+                                                    C.byref(dropped)))
+        return signs, pix, dropped.value
+
+    def inventory_open(self, stream: int = 0) -> np.ndarray:
+        """The open entries of a stream in slot order as they would be logged now (synchronises): SIGN_DTYPE records."""
+        n = C.c_int()
+        check(self.lib, self.lib.lp_inventory_open(self._h, int(stream), None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=SIGN_DTYPE)
+        check(self.lib, self.lib.lp_inventory_open(self._h, int(stream), out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def test_set_rois(self, crops: np.ndarray, img, slot) -> None:
+        """lp_test_set_rois: a ROI list (img[r], slot[r]) and its crops [R, S, S, 3] as a pipeline call would leave them."""
+        S = self.cfg.cls_input
+        c = np.ascontiguousarray(crops, dtype=np.uint8).reshape(-1, S, S, 3)
+        i, s = np.ascontiguousarray(img, dtype=np.int32), np.ascontiguousarray(slot, dtype=np.int32)
+        if i.shape != (len(c),) or s.shape != (len(c),):
+            raise ValueError("img and slot must hold one entry per crop")
+        ip = C.POINTER(C.c_int)
+        check(self.lib, self.lib.lp_test_set_rois(self._h, c.ctypes.data, i.ctypes.data_as(ip), s.ctypes.data_as(ip), len(c)))
+
+    def debug_rois(self):
+        """lp_debug_rois: the last pipeline call's (crops [R, S, S, 3] uint8 RGB, img [R], slot [R]) (synchronises)."""
+        n = C.c_int()
+        check(self.lib, self.lib.lp_debug_rois(self._h, None, None, None, 0, C.byref(n)))
+        S, R = self.cfg.cls_input, n.value
+        crops, img, slot = np.zeros((R, S, S, 3), np.uint8), np.zeros(R, np.int32), np.zeros(R, np.int32)
+        ip = C.POINTER(C.c_int)
+        check(self.lib, self.lib.lp_debug_rois(self._h, crops.ctypes.data, img.ctypes.data_as(ip), slot.ctypes.data_as(ip), R, C.byref(n)))
+        return crops, img, slot
 
     def roi_overflow(self) -> Tuple[int, int]:
         """(classified, kept) of the last run_batch_device call (synchronises): kept > classified means max_rois was too small."""
@@ -761,8 +867,11 @@ class HybridPipeline:
                  detector_threads: int = 4, classifier_device: str = "cpu", batch_size: int = 8, *, precision: str = "fp16",
                  max_batch: int = 1, max_det: int = 300, device: int = 0, max_rois: int = 0, numerics: str = "e2e",
                  tile_overlap: Optional[int] = None, tile_full_frame: bool = True, pixel_format: str = "bgr",
-                 csc_matrix: str = "bt601", track: bool = False, track_config: Optional[Dict] = None):
-        """track: run_batch also tracks the detections across calls (lp_track on the engine's tracker, created here with
+                 csc_matrix: str = "bt601", track: bool = False, track_config: Optional[Dict] = None, inventory=False):
+        """inventory: True or a dict of lp_inventory_config's fields (max_signs, keep_crops, best, min_hits): every tracked call
+        also feeds the engine's sign inventory, while the handle still holds that call's classifier crops; drain_signs() returns
+        the finished signs.  Needs track.
+        track: run_batch also tracks the detections across calls (lp_track on the engine's tracker, created here with
         track_config: lp_track_config's fields); every result dict then gains track_id, track_hits, track_age, track_cls,
         track_cls_conf and track_confirmed.  The frames of consecutive calls are a sequence (per stream id).
         pixel_format: "bgr" = HxWx3 arrays (the reference's cv2 images); "nv12" = video frames as (H * 3 // 2, W) arrays,
@@ -771,6 +880,11 @@ class HybridPipeline:
         (lp_run_tiled): frames larger than det_input are also seen as native-resolution crops overlapping by that many pixels,
         with the letterboxed whole frame as an extra view when tile_full_frame."""
         self.tile_overlap, self.tile_full_frame = tile_overlap, bool(tile_full_frame)
+        self.inventory = bool(inventory) or isinstance(inventory, dict)
+        if self.inventory and not (track or track_config is not None):
+            raise ValueError("inventory needs a pipeline constructed with track=True or a track_config")
+        if self.inventory and int(os.environ.get("LITEPI_DROPIN_LANES", "1")) > 1:
+            raise ValueError("inventory: the upload lanes keep their crops on other handles; unset LITEPI_DROPIN_LANES")
         print("\n" + "=" * 70)
         print("HYBRID PIPELINE: HIP Detector + HIP Classifier (MI355X)")
         print("=" * 70)
@@ -787,6 +901,9 @@ class HybridPipeline:
         self.track = bool(track)
         if self.track or track_config is not None:
             self.engine.tracker_create(**(track_config or {}))
+        self.signs_dropped = 0
+        if self.inventory:
+            self.engine.inventory_create(**(inventory if isinstance(inventory, dict) else {}))
         # ---- upload lanes (an experiment kept behind LITEPI_DROPIN_LANES=<n>, off by default: measured SLOWER, 3.2-3.6 ms per
         # 64-frame call against 2.7-2.9 for one handle -- four 16-frame passes cost 1.4 ms of kernels instead of 0.9 and four
         # sets of copy workers fight over the cores; walking a large batch in chunks inside lp_run_batch gained nothing either
@@ -845,10 +962,10 @@ class HybridPipeline:
         self.engine.last_det_conf_avg = np.concatenate([p[4] for p in parts])
         return dets, counts, num_det, timing
 
-    def _run_tiled(self, images, conf, iou, min_area):
+    def _run_tiled(self, images, conf, iou, min_area, feed=None):
         """run_batch's engine call in tiled mode: consecutive frames go to one lp_run_tiled call while their views fit
         max_batch and their ROIs fit max_rois (at most max_det per frame); results concatenated in frame order, stage times
-        summed over the calls."""
+        summed over the calls.  feed(dets, counts, first_frame) is called behind every engine call."""
         cfg = self.engine.cfg
         S, cap = cfg.det_input, cfg.max_batch
         max_frames = max(1, (cfg.max_rois if cfg.max_rois > 0 else cfg.max_batch * cfg.max_det) // cfg.max_det)
@@ -865,10 +982,13 @@ class HybridPipeline:
             used += nv
         if cur:
             groups.append(cur)
-        parts = []
+        parts, done = [], 0
         for g in groups:
             d, c, nd, t = self.engine.run_tiled(g, conf, iou, min_area, self.tile_overlap, self.tile_full_frame)
             parts.append((d, c, nd, t, self.engine.last_det_conf_avg))
+            if feed is not None:
+                feed(d[:len(g)], c[:len(g)], done)
+            done += len(g)
         timing = LpTiming()
         for f in ("t_detection", "t_roi_extract", "t_classification", "t_total"):
             setattr(timing, f, sum(getattr(p[3], f) for p in parts))
@@ -883,26 +1003,78 @@ class HybridPipeline:
         parts = [self.engine.track(dets[i:i + cap], counts[i:i + cap], None if ids is None else ids[i:i + cap]) for i in range(0, B, cap)]
         return np.concatenate(parts, 0)
 
+    def _feed(self, dets, counts, stream_ids, first):
+        """one engine call's records through the tracker and, while the handle still holds that call's crops, the inventory"""
+        cnt = np.asarray(counts, dtype=np.int32)
+        ids = None if stream_ids is None else stream_ids[first:first + len(cnt)]
+        tracks = self.engine.track(dets, cnt, ids)
+        if self.inventory:
+            self.engine.inventory(dets, cnt, tracks, ids, crops=bool(self.engine.inv_cfg.keep_crops))
+        return tracks
+
+    def drain_signs(self, flush: bool = False) -> List[Dict]:
+        """The signs finished since the last call, one dict per track: stream, track_id, first_frame, last_frame, hits, cls,
+        cls_conf (the final vote), bbox, det_class, best_frame (of the best sighting), crop (the classifier's RGB input crop of
+        the best sighting, or None), flushed.  flush: first close every open track (the end of a video).  The signs lost to a
+        full log are counted in signs_dropped."""
+        if not self.inventory:
+            raise ValueError("drain_signs needs a pipeline constructed with inventory=True")
+        if flush:
+            self.engine.inventory_flush(-1)
+        signs, crops, dropped = self.engine.inventory_drain(crops=bool(self.engine.inv_cfg.keep_crops))
+        self.signs_dropped += dropped
+        boxes = np.stack([signs["x1"], signs["y1"], signs["x2"], signs["y2"]], 1).astype(int).tolist()
+        out = []
+        for k, s in enumerate(signs.tolist()):
+            rec = dict(zip(signs.dtype.names, s))
+            has = crops is not None and bool(rec["flags"] & _ffi.LP_SIGN_HAS_CROP)
+            out.append({"stream": rec["stream"], "track_id": rec["track_id"], "first_frame": rec["first_frame"], "last_frame": rec["last_frame"],
+                        "hits": rec["hits"], "cls": rec["voted_class"], "cls_conf": rec["voted_conf"], "bbox": tuple(boxes[k]),
+                        "det_class": rec["det_class"], "best_frame": rec["best_frame"], "crop": crops[k].copy() if has else None,
+                        "flushed": bool(rec["flags"] & _ffi.LP_SIGN_FLUSHED)})
+        return out
+
     def run_batch(self, images: Sequence[np.ndarray], conf_threshold: float = 0.5, iou_threshold: float = 0.45,
                   min_area: int = 100, stream_ids=None, track: Optional[bool] = None) -> List[Tuple[List[Dict], PipelineMetrics]]:
-        """stream_ids: the tracker stream of every image (None: all stream 0); track: None = the constructor's setting."""
+        """stream_ids: the tracker stream of every image (None: all stream 0); track: None = the constructor's setting.
+        In tiled mode tracker and inventory are fed behind every lp_run_tiled call of the batch: if a later call of the batch
+        fails, they have consumed the frames of the earlier ones although the caller gets no result for the batch."""
         do_track = self.track if track is None else bool(track)
         if do_track and not hasattr(self.engine, "track_cfg"):
             raise ValueError("run_batch(track=True) needs a pipeline constructed with track=True or a track_config")
+        # track (and inventory) are fed per engine call; the tracker's result does not depend on the split
+        fed, ids = [], None
+        if do_track and stream_ids is not None:
+            ids = self.engine._stream_ids(stream_ids, len(images))
+
+        def feed(d, c, first):   # a failure of the tracker or the inventory is never taken for an engine failure below
+            try:
+                fed.append(self._feed(d, c, ids, first))
+            except _ffi.LitepiError as e:
+                e.from_feed = True
+                raise
         t0 = time.perf_counter()
         try:
             if self.tile_overlap is not None:
-                dets, counts, num_det, timing = self._run_tiled(list(images), conf_threshold, iou_threshold, min_area)
+                dets, counts, num_det, timing = self._run_tiled(list(images), conf_threshold, iou_threshold, min_area, feed if do_track else None)
             elif self._lanes and len(images) >= 32 and len(images) <= self._lane_cap * len(self._lanes):
                 dets, counts, num_det, timing = self._run_lanes(list(images), conf_threshold, iou_threshold, min_area)
             else:
                 dets, counts, num_det, timing = self.engine.run_batch(images, conf_threshold, iou_threshold, min_area)
         except _ffi.LitepiError as e:
-            if e.code != _ffi.LP_ERR_HIP:  # misuse / capacity errors are raised, only an engine failure yields "nothing found"
+            if e.code != _ffi.LP_ERR_HIP or getattr(e, "from_feed", False):  # misuse / capacity errors are raised, only an engine failure yields "nothing found"
                 raise
             print(f"[HIP Pipeline] engine failure, returning no detections: {e}")
             return [([], PipelineMetrics()) for _ in images]
-        tracks = self._track(dets[:len(images)], np.asarray(counts[:len(images)], dtype=np.int32), stream_ids) if do_track else None
+        tracks = None
+        if do_track:
+            B = len(images)
+            if self.tile_overlap is not None:
+                tracks = np.concatenate(fed, 0)
+            elif self.inventory:   # one engine call on this handle
+                tracks = self._feed(dets[:B], counts[:B], ids, 0)
+            else:
+                tracks = self._track(dets[:B], np.asarray(counts[:B], dtype=np.int32), stream_ids)
         wall_ms = (time.perf_counter() - t0) * 1000.0   # t_total ends here; system metrics are sampled after it (e2e.py:505-516)
         conf_avg = self.engine.last_det_conf_avg
         sysm = _system_metrics()

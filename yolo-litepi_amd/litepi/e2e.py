@@ -94,6 +94,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--track", action="store_true",
                    help="track the signs across the frames of --raw_frames (a sequence) on the device and write tracks.csv: identity, "
                         "voted class, hits and confirmation per detection of the benchmark pass")
+    p.add_argument("--inventory", action="store_true",
+                   help="with --track: one row per finished track in signs.csv (final voted class, first / last frame, best sighting) "
+                        "and the classifier's input crop of the best sighting as signs/sign_<stream>_<track>.png; collected on the device")
+    p.add_argument("--inventory_best", choices=["area", "det_conf", "cls_conf"], default="area",
+                   help="what makes a sighting the best of its track")
     p.add_argument("--track_iou", type=float, default=0.3, help="a detection matches a track when their IoU exceeds this")
     p.add_argument("--track_max_age", type=int, default=5, help="frames a track may stay unmatched before it is dropped")
     p.add_argument("--track_min_hits", type=int, default=3, help="matched frames after which a track counts as confirmed")
@@ -334,7 +339,13 @@ TRACKS_CSV_COLUMNS = ("frame", "track_id", "x1", "y1", "x2", "y2", "det_conf", "
                       "confirmed")
 
 
+SIGNS_CSV_COLUMNS = ("stream", "track_id", "first_frame", "last_frame", "hits", "voted_class", "voted_conf", "best_frame", "x1", "y1", "x2",
+                     "y2", "det_class", "flushed", "crop")
+
+
 def check_frame_args(args) -> None:
+    if getattr(args, "inventory", False) and not getattr(args, "track", False):
+        raise SystemExit("--inventory needs --track: the inventory lists the tracker's finished tracks")
     if getattr(args, "track", False):   # tracking needs the frames of ONE sequence, all of them, in order, in one process
         if not args.raw_frames:
             raise SystemExit("--track needs --raw_frames: the frames of a raw file are a sequence, the images of --input are not")
@@ -361,6 +372,7 @@ def run_evaluation(args) -> Dict:
 
     check_frame_args(args)
     args.track = bool(getattr(args, "track", False))
+    args.inventory = bool(getattr(args, "inventory", False))
     rank, local_rank, world = D.env_rank_world()
     if args.track and world > 1:   # a launcher's WORLD_SIZE shards the files as --gpus does
         raise SystemExit(f"--track runs in one process: the shards of a sequence cannot be tracked apart (WORLD_SIZE is {world})")
@@ -401,6 +413,8 @@ def run_evaluation(args) -> Dict:
     import io
     # with --track off the pipeline is constructed and called exactly as before
     track_kw = dict(track=True, track_config=dict(iou_match=args.track_iou, max_age=args.track_max_age, min_hits=args.track_min_hits)) if args.track else {}
+    if args.inventory:
+        track_kw["inventory"] = dict(best=args.inventory_best)
     bench_kw, eval_kw = (dict(track=True), dict(track=False)) if args.track else ({}, {})
     with contextlib.redirect_stdout(io.StringIO()) if rank != 0 else contextlib.nullcontext():   # one banner, rank 0's
         pipeline = HybridPipeline(args.detector_param, args.detector_bin, args.classifier, args.clf_arch, num_classes,
@@ -435,7 +449,7 @@ def run_evaluation(args) -> Dict:
     files = files[lo:hi]
 
     all_preds, all_gts, bench_time, names = [], [], 0.0, []
-    track_rows = []
+    track_rows, signs = [], []
     try:
         n_warm = args.warmup if args.warmup is not None else (10 if args.numerics == "e2e_optimize" else 0)
         if n_warm > 0:   # warmup_pipeline (e2e_optimize.py:552-570): random frame, conf 0.5
@@ -465,6 +479,8 @@ def run_evaluation(args) -> Dict:
                 for f, (res, _) in zip(chunk, bench):
                     track_rows += [(f.index, r["track_id"], *r["bbox"], r["det_conf"], r["cls_class"], r["cls_conf"], r["track_cls"],
                                     r["track_cls_conf"], r["track_hits"], int(r["track_confirmed"])) for r in res]
+                if args.inventory:
+                    signs += pipeline.drain_signs()
             for f, im, (res, _) in zip(chunk, imgs, ev):
                 lp = (label_dir / f"{f.stem}.txt") if label_dir else f.parent / "labels" / f"{f.stem}.txt"
                 im_h, im_w = (fh, fw) if raw is not None else im.shape[:2]
@@ -478,6 +494,8 @@ def run_evaluation(args) -> Dict:
                     visualize_prediction(im, res, all_gts[-1], class_names, viz_dir / f"vis_{f.stem}.png")
                 all_preds.append([{"bbox": r["bbox"], "conf": r.get("det_conf", 0.0), "cls_class": r.get("cls_class", -1)} for r in res])
                 names.append(f.name)
+        if args.inventory:   # the end of the sequence: the tracks still open are signs too
+            signs += pipeline.drain_signs(flush=True)
     finally:
         pipeline.engine.close()
     if args.track:
@@ -488,6 +506,23 @@ def run_evaluation(args) -> Dict:
             w.writerows(track_rows)
         confirmed = {r[1] for r in track_rows if r[-1] and r[1] > 0}
         say(f"Tracking: {len(confirmed)} confirmed tracks over {len(files)} frames ({len(track_rows)} detections) -> {out_dir / 'tracks.csv'}")
+    if args.inventory:
+        import csv
+        from PIL import Image
+        crop_dir = out_dir / "signs"
+        crop_dir.mkdir(parents=True, exist_ok=True)
+        with open(out_dir / "signs.csv", "w", newline="") as fcsv:
+            w = csv.writer(fcsv)
+            w.writerow(SIGNS_CSV_COLUMNS)
+            for s in signs:
+                name = ""
+                if s["crop"] is not None:
+                    name = f"signs/sign_{s['stream']}_{s['track_id']}.png"
+                    Image.fromarray(s["crop"], "RGB").save(out_dir / name)
+                w.writerow((s["stream"], s["track_id"], s["first_frame"], s["last_frame"], s["hits"], s["cls"], s["cls_conf"], s["best_frame"],
+                            *s["bbox"], s["det_class"], int(s["flushed"]), name))
+        say(f"Inventory: {len(signs)} signs ({sum(s['crop'] is not None for s in signs)} with a crop, {pipeline.signs_dropped} dropped) "
+            f"-> {out_dir / 'signs.csv'}")
     rank_times = [bench_time]
     if world > 1:   # the one exchange of the sharded evaluation: every rank's predictions + ground truths -> rank 0
         import torch.distributed as dist
