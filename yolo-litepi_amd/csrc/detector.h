@@ -66,6 +66,7 @@ class Detector {
   void fetch_blob(const std::string& name, int B, std::vector<float>& out, int& C, int& H, int& W) const;
 
  private:
+  friend struct Planner;   // detector_plan.cpp: builds the plan inside load()
   View view(int t) const;
   int prec_, impl_, maxB_, S_;
   int fwd_calls_ = 0;   // LITEPI_SKIP_OP diagnostic
