@@ -202,6 +202,46 @@ int lp_test_nms_views(lp_handle* h, const float* boxes, const float* scores, con
 int lp_test_tile_views(lp_handle* h, const uint8_t* img, int H, int W, const lp_tiling* tiling, int byte_offset, uint8_t* out,
                        int cap, int* n_views);
 
+/* ---- scaled views: letterbox any frame window into the detector batch (additive to ABI 310) ---- */
+/* Between the one letterboxed view of lp_run_batch and the native-resolution crops of lp_run_tiled: the caller chooses the
+ * scale and the place of every look at a frame.  A view is four ints {x, y, w, h}, a source window in frame pixels; x = -1
+ * means the whole frame whatever its size (w, h are then ignored): the format lp_tile_grid emits.  Any other window needs
+ * x, y >= 0, w, h >= 16, x + w <= W and y + h <= H for EVERY frame of the call.  One list of n_views >= 1 views applies to
+ * all frames of a call.  Geometry of a window view for det_input S, in doubles, as the letterbox of an h x w image:
+ *   r = min(S / h, S / w);  new_w = rint(w * r);  new_h = rint(h * r);  dw = (S - new_w) / 2;  dh = (S - new_h) / 2
+ *   top = rint(dh - 0.1);  left = rint(dw - 0.1)
+ *   ratio = (float)r;  pad_w = (float)(dw - r * x);  pad_h = (float)(dh - r * y)
+ * (rint: round half to even); the whole-frame view is the window {0, 0, W, H}.  The view's pixels are the letterbox of
+ * frame[y : y + h, x : x + w]: byte for byte what lp_test_letterbox returns for that sub-image copied out contiguously, 114
+ * in the bars.  Boxes are mapped back with the three floats, in fp32 ((v - pad) / ratio), and clipped to the FRAME
+ * ([0, W] x [0, H]); the candidates of all views of a frame go through the frame NMS of tiled inference in list order (ties:
+ * higher (view, anchor) first); ROIs are cut from the native frame as in lp_run_tiled.  B * n_views > max_batch, or a list
+ * beyond the frame NMS capacity (see tiled inference), is LP_ERR_ARG like every window error: before anything is enqueued,
+ * and the handle stays usable.  DESIGN.md 6f. */
+/* The window grid of an H x W frame (pure host; no handle, no device), 16 <= tile, 0 <= overlap < tile.  Per axis of length L:
+ * L <= tile: one window at 0 of side L; else step = tile - overlap, n = 1 + ceil((L - tile) / step), x_k = min(k * step,
+ * L - tile), side tile.  Windows come row-major; with full_frame = 1 a frame that needs more than one window gets
+ * {-1, -1, W, H} first; a frame that fits one window yields only {-1, -1, W, H}.  tile = det_input on a frame with
+ * H, W >= det_input reproduces lp_tile_grid.  views may be NULL (count only); cap < *n_views with views != NULL is LP_ERR_ARG. */
+int lp_view_grid(int tile, int overlap, int full_frame, int H, int W, int* n_views, int* views, int cap);
+/* The geometry of one view {x, y, w, h} of an H x W frame (pure host); every output may be NULL */
+int lp_view_geometry(int det_input, int H, int W, const int* view, float* ratio, float* pad_w, float* pad_h,
+                     int* new_w, int* new_h, int* top, int* left);
+/* lp_run_batch over B host frames, each seen through the n_views views (views: n_views x 4 ints): dets [B*max_det],
+ * counts / num_det / det_conf_avg [B] per frame.  views = {-1, ..} alone gives lp_run_batch's result. */
+int lp_run_views(lp_handle* h, const uint8_t* const* imgs, const int* heights, const int* widths, int B,
+                 const int* views, int n_views, float conf, float iou, int min_area,
+                 lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing);
+/* lp_run_batch_device over B equally sized frames resident in HBM, seen through the views; the list is a HOST array, read
+ * before the call returns.  dev_dets [B*max_det], dev_counts [3*B] per frame as lp_run_tiled_device.  Asynchronous. */
+int lp_run_views_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, const int* views, int n_views,
+                        float conf, float iou, int min_area, void* dev_dets, void* dev_counts);
+/* The view gather alone (tests): the views of one host H x W frame, uploaded byte_offset (0..63) bytes past an aligned
+ * address into a buffer that ends with the frame's last byte, in list order -> out [n_views, S, S, 3] uint8 BGR
+ * (cap views of room; n_views <= max_batch). */
+int lp_test_view_windows(lp_handle* h, const uint8_t* img, int H, int W, const int* views, int n_views,
+                         int byte_offset, uint8_t* out, int cap);
+
 /* ---- pixel format of the frames (additive to ABI 310) ------------------------------- */
 /* Hardware video decoders and capture pipelines deliver NV12: a full-resolution Y plane followed by a half-resolution
  * interleaved UV plane (U first), 1.5 bytes per pixel.  With LP_PIX_NV12 set on the handle, every entry point that takes
@@ -233,8 +273,8 @@ typedef struct lp_frame_format {
 /* pure host, no handle, no device: validates fmt (NULL = packed BGR) for an H x W frame and resolves the zeros: *uv_offset
  * (0 for BGR8) and *frame_bytes, the bytes of one frame (H * W * 3 for BGR8); either may be NULL */
 int lp_frame_layout(const lp_frame_format* fmt, int H, int W, int64_t* uv_offset, int64_t* frame_bytes);
-/* the format of the frames given to the NEXT calls of lp_detect, lp_run_batch, lp_run_batch_device, lp_run_tiled and
- * lp_run_tiled_device; NULL = packed BGR (the default).  Copied; like lp_set_stream it is handle state.  Host frames in NV12
+/* the format of the frames given to the NEXT calls of lp_detect, lp_run_batch, lp_run_batch_device, lp_run_tiled,
+ * lp_run_tiled_device, lp_run_views and lp_run_views_device; NULL = packed BGR (the default).  Copied; like lp_set_stream it is handle state.  Host frames in NV12
  * are frame_bytes each (frame_stride is ignored for them). */
 int lp_set_input_format(lp_handle* h, const lp_frame_format* fmt);
 /* the converter alone (tests): B host frames of one size (contiguous, frame_stride apart), uploaded byte_offset (0..63)
@@ -391,7 +431,8 @@ int lp_inventory_destroy(lp_handle* h);
 /* dev_dets, dev_counts, dev_tracks, B and stream_ids exactly as the preceding lp_track_device took and wrote them.
  * Asynchronous on the handle's stream, ordered behind that call with no event; any number of calls may be enqueued without a
  * synchronise.  crops = 1 asserts that frames 0..B-1 of this call are frames 0..B-1 of the last pipeline call on this handle
- * (lp_run_batch, lp_run_batch_device, lp_run_tiled, lp_run_tiled_device; the tiled ones index frames, not views), whose ROI
+ * (lp_run_batch, lp_run_batch_device, lp_run_tiled, lp_run_tiled_device, lp_run_views, lp_run_views_device; the tiled
+ * and the views ones index frames, not views), whose ROI
  * list and classifier input crops the handle still holds: record (b, slot) has a crop iff the ROI list names it among its
  * first `total` entries.  crops = 0 attaches no crops.  LP_ERR_STATE without a tracker or an inventory; LP_ERR_ARG for B
  * outside 1..max_batch, a stream id out of range, crops outside 0/1, crops = 1 with keep_crops = 0, or record buffers that

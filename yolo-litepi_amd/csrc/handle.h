@@ -1,4 +1,4 @@
-// Internal to the C-ABI translation units (api.cpp, pipeline.cpp, pixfmt.cpp, tiling.cpp, tracking.cpp, inventory.cpp,
+// Internal to the C-ABI translation units (api.cpp, pipeline.cpp, pixfmt.cpp, tiling.cpp, views.cpp, tracking.cpp, inventory.cpp,
 // test_hooks.cpp): the handle behind include/litepi.h's lp_handle, the captured-step cache, and the pipeline pieces the entry points share.
 #pragma once
 #include <algorithm>
@@ -93,6 +93,8 @@ enum GraphKind {
   GK_BATCH_FRONT, GK_BATCH_ROI, GK_BATCH_CLS,     // lp_run_batch: detect + NMS, ROI resize, classifier
   GK_TILED_FRONT, GK_TILED_ROI, GK_TILED_CLS,     // lp_run_tiled: tiled detect + frame NMS, ROI resize, classifier
   GK_TILED_DEVICE,                                // lp_run_tiled_device
+  GK_VIEWS_FRONT, GK_VIEWS_ROI, GK_VIEWS_CLS,     // lp_run_views: view gather + detect + frame NMS, ROI resize, classifier
+  GK_VIEWS_DEVICE,                                // lp_run_views_device
 };
 struct GraphKey {
   GraphKind kind;
@@ -133,6 +135,7 @@ struct lp_handle {
   std::vector<lp::ImgGeom> geom_cache;
   // tiled inference (lp_run_tiled*): frame geometry, frame table + view slots, per-view counts; allocated on first use
   lp::DevBuf d_fgeom, d_ftab, d_vcnt;
+  lp::DevBuf d_vwin;   // scaled views (lp_run_views*): the window table, [max_batch] ViewWin; allocated on first use
   std::vector<char> tile_cache;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // staged host pass: start, after the ROI resize, after the front, end
   int last_roi_count = 0;
@@ -274,5 +277,24 @@ struct TileLayout {
 };
 void check_tiling(const lp_tiling* t, int S);
 TileLayout tile_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const lp_tiling& t);
+// upload the frame geometry, the frame table, the view slots, the view geometry and (scaled views) the window table when any
+// of them changed; a change invalidates captured graphs (geom_ver)
+void upload_tiles(lp_handle* h, const std::vector<ImgGeom>& fg, const TileLayout& lay, const std::vector<ViewWin>* wins = nullptr);
+// the detector on the V gathered views in d_lb + view sort + frame NMS (+ the ROI list when with_rois)
+void enqueue_view_detect(lp_handle* h, const TileLayout& lay, int F, float conf, float iou, int min_area, lp_det* dets, int* counts,
+                         bool with_rois, Profiler* prof);
+
+// ---- scaled views (views.cpp) --------------------------------------------------------------------------------------------------
+// The layout of a call whose frames are all seen through ONE list of {x, y, w, h} views (include/litepi.h "scaled views").
+// Batch slots: first the whole-frame views (x = -1; launch_letterbox, so they are exactly lp_run_batch's input), then the
+// windows, whose table entries wins[i] fill slot lay.L + i.
+struct ViewLayout {
+  TileLayout lay;
+  std::vector<ViewWin> wins;   // [V - L]
+};
+ViewLayout view_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const int* views, int n_views);
+// whole-frame views through launch_letterbox, windows through launch_window_views, into dst [V,S,S,3]
+void enqueue_view_gather(const uint8_t* src, const ImgGeom* d_geom, const ViewWin* d_wins, uint8_t* dst, const ViewLayout& vl, int S,
+                         hipStream_t st, Profiler* prof);
 
 }  // namespace lp

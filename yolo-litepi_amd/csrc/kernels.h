@@ -96,6 +96,22 @@ size_t nms_lds_bytes(int A);
 // crop views slot0 .. slot0+nslots-1 of the view batch [V,S,S,3]: frame[-top : -top+S, -left : -left+S], 114 off the frame
 void launch_crop_views(const uint8_t* src, const ImgGeom* geom, uint8_t* dst, int slot0, int nslots, int S, hipStream_t st);
 
+// Scaled views (lp_run_views*): one window view of the view batch, device resident.  The view is the letterbox of
+// frame[y : y + h, x : x + w], a frame whose rows are `pitch` bytes apart; no byte outside the frame's frame_bytes is read.
+struct ViewWin {
+  long src_off;        // byte offset of the FRAME in the source buffer
+  long frame_bytes;    // rows * pitch
+  int pitch;           // frame row bytes
+  int x, y, w, h;      // source window in frame pixels
+  int new_w, new_h;    // resized (unpadded) window inside the S x S view
+  int top, left;       // integer border offsets
+  int pad;
+};
+// window views slot0 .. slot0+n-1 of the view batch [V,S,S,3] from wins[0 .. n); host_wins (the same n entries) sizes the
+// LDS rows: when a source row span does not fit (down-scales beyond ~10x) the per-pixel kernel runs
+void launch_window_views(const uint8_t* src, const ViewWin* wins, uint8_t* dst, int slot0, int n, int S, hipStream_t st,
+                         const ViewWin* host_wins);
+
 struct TileFrame { int view0, nviews; };   // frame f's views: vslot[view0 .. view0 + nviews), in the frame's view order
 struct FrameNmsArgs {
   Cand* cand;             // [V][A] per-view candidates; after the view sort, frame f's merged list at cand + view0 * A

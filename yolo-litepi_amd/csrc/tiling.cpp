@@ -67,28 +67,56 @@ TileLayout tile_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const
   return lay;
 }
 
-// upload the frame geometry + frame table + view slots when they changed; a change invalidates captured graphs (geom_ver)
-static void upload_tiles(lp_handle* h, const std::vector<ImgGeom>& fg, const TileLayout& lay) {
+// upload the frame geometry + frame table + view slots (+ the window table of scaled views) when they changed; a change
+// invalidates captured graphs (geom_ver)
+void upload_tiles(lp_handle* h, const std::vector<ImgGeom>& fg, const TileLayout& lay, const std::vector<ViewWin>* wins) {
   const int B = h->cfg.max_batch;
   if (!h->d_fgeom.p) {
     h->d_fgeom.alloc((size_t)B * sizeof(ImgGeom));
     h->d_ftab.alloc((size_t)B * (sizeof(TileFrame) + sizeof(int)));
     h->d_vcnt.alloc((size_t)B * 4);
   }
+  const size_t nw = wins ? wins->size() : 0;
+  if (nw && !h->d_vwin.p) h->d_vwin.alloc((size_t)B * sizeof(ViewWin));
   h->upload_geom(lay.vgeom);
   const size_t nf = fg.size();
-  std::vector<char> blob(nf * sizeof(ImgGeom) + nf * sizeof(TileFrame) + lay.vslot.size() * sizeof(int));
+  std::vector<char> blob(nf * sizeof(ImgGeom) + nf * sizeof(TileFrame) + lay.vslot.size() * sizeof(int) + nw * sizeof(ViewWin));
   memcpy(blob.data(), fg.data(), nf * sizeof(ImgGeom));
   memcpy(blob.data() + nf * sizeof(ImgGeom), lay.frames.data(), nf * sizeof(TileFrame));
   memcpy(blob.data() + nf * (sizeof(ImgGeom) + sizeof(TileFrame)), lay.vslot.data(), lay.vslot.size() * sizeof(int));
+  if (nw) memcpy(blob.data() + blob.size() - nw * sizeof(ViewWin), wins->data(), nw * sizeof(ViewWin));
   if (blob == h->tile_cache) return;
   LP_HIP(hipMemcpyAsync(h->d_fgeom.p, fg.data(), nf * sizeof(ImgGeom), hipMemcpyHostToDevice, h->stream));
   LP_HIP(hipMemcpyAsync(h->d_ftab.p, lay.frames.data(), nf * sizeof(TileFrame), hipMemcpyHostToDevice, h->stream));
   LP_HIP(hipMemcpyAsync(h->d_ftab.as<char>() + (size_t)B * sizeof(TileFrame), lay.vslot.data(), lay.vslot.size() * sizeof(int),
                         hipMemcpyHostToDevice, h->stream));
+  if (nw) LP_HIP(hipMemcpyAsync(h->d_vwin.p, wins->data(), nw * sizeof(ViewWin), hipMemcpyHostToDevice, h->stream));
   LP_HIP(hipStreamSynchronize(h->stream));
   h->tile_cache.swap(blob);
   ++h->geom_ver;
+}
+
+// the detector on the gathered views + view sort + frame NMS (+ the ROI list when with_rois)
+void enqueue_view_detect(lp_handle* h, const TileLayout& lay, int F, float conf, float iou, int min_area, lp_det* dets, int* counts,
+                         bool with_rois, Profiler* prof) {
+  h->det->forward(h->d_lb.as<uint8_t>(), lay.V, h->d_geom.as<ImgGeom>(), conf, nullptr, h->d_cand.as<Cand>(), h->d_cand_count.as<int>(),
+                  h->stream, prof);
+  FrameNmsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.cand = h->d_cand.as<Cand>(); a.cand_count = h->d_cand_count.as<int>(); a.vcnt = h->d_vcnt.as<int>(); a.sorted = h->d_sorted.as<Cand>();
+  a.frames = h->d_ftab.as<TileFrame>();
+  a.vslot = reinterpret_cast<const int*>(h->d_ftab.as<char>() + (size_t)h->cfg.max_batch * sizeof(TileFrame));
+  a.dets = dets; a.counts = counts; a.rects = h->d_rects.as<int>(); a.fgeom = h->d_fgeom.as<ImgGeom>();
+  a.A = h->det->num_anchors(); a.max_det = h->cfg.max_det; a.nc = h->det->num_classes(); a.iou = iou; a.min_area = min_area;
+  if (with_rois) a.tab = h->roi_table();
+  a.max_rois = h->max_rois;
+  a.roi_rule = h->cfg.numerics;
+  if (prof) prof->begin(h->stream);
+  launch_view_sort(a, lay.V, h->stream);
+  if (prof) prof->end(h->stream, "view_sort", "nms", 0.0, 0.0);
+  if (prof) prof->begin(h->stream);
+  launch_frame_nms(a, F, lay.max_views, h->stream);
+  if (prof) prof->end(h->stream, "frame_nms", "nms", 0.0, 0.0);
 }
 
 // view gather + detector on the views + frame NMS (+ the ROI list when with_rois)
@@ -109,24 +137,7 @@ static void enqueue_tiled_detect(lp_handle* h, const uint8_t* src, const TileLay
     launch_crop_views(src, h->d_geom.as<ImgGeom>(), h->d_lb.as<uint8_t>(), lay.L, lay.V - lay.L, S, h->stream);
     if (prof) prof->end(h->stream, "tile_crop_u8", "tile_crop", 0.0, 2.0 * (lay.V - lay.L) * S * S * 3);
   }
-  h->det->forward(h->d_lb.as<uint8_t>(), lay.V, h->d_geom.as<ImgGeom>(), conf, nullptr, h->d_cand.as<Cand>(), h->d_cand_count.as<int>(),
-                  h->stream, prof);
-  FrameNmsArgs a;
-  memset(&a, 0, sizeof(a));
-  a.cand = h->d_cand.as<Cand>(); a.cand_count = h->d_cand_count.as<int>(); a.vcnt = h->d_vcnt.as<int>(); a.sorted = h->d_sorted.as<Cand>();
-  a.frames = h->d_ftab.as<TileFrame>();
-  a.vslot = reinterpret_cast<const int*>(h->d_ftab.as<char>() + (size_t)h->cfg.max_batch * sizeof(TileFrame));
-  a.dets = dets; a.counts = counts; a.rects = h->d_rects.as<int>(); a.fgeom = h->d_fgeom.as<ImgGeom>();
-  a.A = h->det->num_anchors(); a.max_det = h->cfg.max_det; a.nc = h->det->num_classes(); a.iou = iou; a.min_area = min_area;
-  if (with_rois) a.tab = h->roi_table();
-  a.max_rois = h->max_rois;
-  a.roi_rule = h->cfg.numerics;
-  if (prof) prof->begin(h->stream);
-  launch_view_sort(a, lay.V, h->stream);
-  if (prof) prof->end(h->stream, "view_sort", "nms", 0.0, 0.0);
-  if (prof) prof->begin(h->stream);
-  launch_frame_nms(a, F, lay.max_views, h->stream);
-  if (prof) prof->end(h->stream, "frame_nms", "nms", 0.0, 0.0);
+  enqueue_view_detect(h, lay, F, conf, iou, min_area, dets, counts, with_rois, prof);
 }
 
 }  // namespace lp

@@ -105,6 +105,7 @@ SYMBOLS = [
     "lp_test_conv", "lp_test_postprocess", "lp_test_nms_boxes", "lp_test_roi_resize", "lp_test_letterbox", "lp_roi_overflow",
     "lp_comm_unique_id", "lp_comm_init", "lp_gather", "lp_comm_destroy",
     "lp_tile_grid", "lp_run_tiled", "lp_run_tiled_device", "lp_test_nms_views", "lp_test_tile_views",
+    "lp_view_grid", "lp_view_geometry", "lp_run_views", "lp_run_views_device", "lp_test_view_windows",
     "lp_frame_layout", "lp_set_input_format", "lp_test_convert_frames",
     "lp_track_default_config", "lp_track_config_check", "lp_tracker_create", "lp_tracker_destroy", "lp_tracker_reset",
     "lp_track_device", "lp_track", "lp_tracker_snapshot",
@@ -167,6 +168,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_test_nms_views.argtypes = [vp, fp, fp, ip, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp,
                                       ip, ip, ip]
     lib.lp_test_tile_views.argtypes = [vp, vp, C.c_int, C.c_int, tp, C.c_int, vp, C.c_int, ip]
+    lib.lp_view_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int]
+    lib.lp_view_geometry.argtypes = [C.c_int, C.c_int, C.c_int, ip, fp, fp, fp, ip, ip, ip, ip]
+    lib.lp_run_views.argtypes = [vp, u8pp, ip, ip, C.c_int, ip, C.c_int, C.c_float, C.c_float, C.c_int, vp, ip, ip, fp, C.POINTER(LpTiming)]
+    lib.lp_run_views_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp]
+    lib.lp_test_view_windows.argtypes = [vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, vp, C.c_int]
     ffp, i64p = C.POINTER(LpFrameFormat), C.POINTER(C.c_int64)
     lib.lp_frame_layout.argtypes = [ffp, C.c_int, C.c_int, i64p, i64p]
     lib.lp_set_input_format.argtypes = [vp, ffp]

@@ -79,6 +79,42 @@ def tile_grid(det_input: int, H: int, W: int, overlap: int = 128, full_frame: bo
     return [tuple(buf[4 * i:4 * i + 4]) for i in range(n.value)]
 
 
+def _view_array(views) -> np.ndarray:
+    """a view list as the [n, 4] int32 array the library takes: (x, y, w, h) windows, "full" (or any x = -1) = the whole frame"""
+    rows = [(-1, -1, 0, 0) if isinstance(v, str) and v == "full" else tuple(int(c) for c in v) for v in views]
+    if any(len(r) != 4 for r in rows):
+        raise ValueError('a view is (x, y, w, h) or "full"')
+    return np.ascontiguousarray(np.array(rows, dtype=np.int32).reshape(-1, 4))
+
+
+def _ip(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def view_grid(tile: int, H: int, W: int, overlap: int = 0, full_frame: bool = True) -> List[Tuple[int, int, int, int]]:
+    """The window grid of an H x W frame (lp_view_grid: host only, no GPU needed): (x, y, w, h) windows of side `tile` (or the
+    frame's, where it is shorter) overlapping by `overlap`, row-major, behind (-1, -1, W, H) for the whole frame."""
+    lib = _ffi.load_library()
+    n = C.c_int()
+    check(lib, lib.lp_view_grid(int(tile), int(overlap), int(bool(full_frame)), int(H), int(W), C.byref(n), None, 0))
+    buf = (C.c_int * (4 * n.value))()
+    check(lib, lib.lp_view_grid(int(tile), int(overlap), int(bool(full_frame)), int(H), int(W), C.byref(n), buf, n.value))
+    return [tuple(buf[4 * i:4 * i + 4]) for i in range(n.value)]
+
+
+def view_geometry(det_input: int, H: int, W: int, view) -> Dict[str, object]:
+    """The geometry of one view of an H x W frame (lp_view_geometry: host only): ratio, pad_w, pad_h (float32 values), new_w,
+    new_h, top, left."""
+    lib = _ffi.load_library()
+    v = _view_array([view])
+    r, pw, ph = C.c_float(), C.c_float(), C.c_float()
+    nw, nh, top, left = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    check(lib, lib.lp_view_geometry(int(det_input), int(H), int(W), _ip(v), C.byref(r), C.byref(pw), C.byref(ph), C.byref(nw), C.byref(nh),
+                                    C.byref(top), C.byref(left)))
+    return dict(ratio=np.float32(r.value), pad_w=np.float32(pw.value), pad_h=np.float32(ph.value), new_w=nw.value, new_h=nh.value,
+                top=top.value, left=left.value)
+
+
 TRACK_CONFIG_FIELDS = ("n_streams", "max_tracks", "iou_match", "max_age", "min_hits", "new_conf", "vote_decay", "class_gate", "motion")
 
 
@@ -284,6 +320,34 @@ class Engine:
                          dev_dets: int, dev_counts: int, overlap: int = 128, full_frame: bool = True) -> None:
         t = _tiling(overlap, full_frame)
         check(self.lib, self.lib.lp_run_tiled_device(self._h, C.c_void_p(dev_imgs), B, H, W, C.byref(t), conf, iou, int(min_area),
+                                                     C.c_void_p(dev_dets), C.c_void_p(dev_counts)))
+
+    # ---- scaled views: any window of a frame, letterboxed at its own scale --------------------
+    def view_grid(self, H: int, W: int, tile: int, overlap: int = 0, full_frame: bool = True) -> List[Tuple[int, int, int, int]]:
+        return view_grid(tile, H, W, overlap, full_frame)
+
+    def view_geometry(self, H: int, W: int, view) -> Dict[str, object]:
+        return view_geometry(self.cfg.det_input, H, W, view)
+
+    def run_views(self, images: Sequence[np.ndarray], views, conf: float, iou: float, min_area: int):
+        """run_batch with every frame seen through the views (lp_run_views; (x, y, w, h) windows or "full"): same return
+        values, per frame."""
+        imgs, ptrs, hs, ws = self._img_args(images, frames=True)
+        B = len(imgs)
+        v = _view_array(views)
+        dets = np.zeros((B, self.cfg.max_det), dtype=DET_DTYPE)
+        counts, num_det = (C.c_int * B)(), (C.c_int * B)()
+        conf_avg = (C.c_float * B)()
+        timing = LpTiming()
+        check(self.lib, self.lib.lp_run_views(self._h, ptrs, hs, ws, B, _ip(v), len(v), conf, iou, int(min_area), dets.ctypes.data, counts,
+                                              num_det, conf_avg, C.byref(timing)))
+        self.last_det_conf_avg = np.array(conf_avg[:], dtype=np.float32)
+        return dets, np.array(counts[:], dtype=np.int64), np.array(num_det[:], dtype=np.int64), timing
+
+    def run_views_device(self, dev_imgs: int, B: int, H: int, W: int, views, conf: float, iou: float, min_area: int,
+                         dev_dets: int, dev_counts: int) -> None:
+        v = _view_array(views)
+        check(self.lib, self.lib.lp_run_views_device(self._h, C.c_void_p(dev_imgs), B, H, W, _ip(v), len(v), conf, iou, int(min_area),
                                                      C.c_void_p(dev_dets), C.c_void_p(dev_counts)))
 
     # ---- sign tracking across frames ----------------------------------------------------------
@@ -541,6 +605,16 @@ class Engine:
         out = np.empty((n.value, S, S, 3), np.uint8)
         check(self.lib, self.lib.lp_test_tile_views(self._h, a.ctypes.data, a.shape[0], a.shape[1], C.byref(t), int(byte_offset),
                                                     out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def test_view_windows(self, img: np.ndarray, views, byte_offset: int = 0) -> np.ndarray:
+        """The gathered views of one frame (uploaded byte_offset bytes past an aligned address) -> uint8 [n_views, S, S, 3]."""
+        a = _as_bgr(img)
+        S = self.cfg.det_input
+        v = _view_array(views)
+        out = np.empty((len(v), S, S, 3), np.uint8)
+        check(self.lib, self.lib.lp_test_view_windows(self._h, a.ctypes.data, a.shape[0], a.shape[1], _ip(v), len(v), int(byte_offset),
+                                                      out.ctypes.data, len(v)))
         return out
 
     def test_convert_frames(self, frames: np.ndarray, B: int, H: int, W: int, matrix: str = "bt601", pitch: int = 0, uv_offset: int = 0,
@@ -867,7 +941,8 @@ class HybridPipeline:
                  detector_threads: int = 4, classifier_device: str = "cpu", batch_size: int = 8, *, precision: str = "fp16",
                  max_batch: int = 1, max_det: int = 300, device: int = 0, max_rois: int = 0, numerics: str = "e2e",
                  tile_overlap: Optional[int] = None, tile_full_frame: bool = True, pixel_format: str = "bgr",
-                 csc_matrix: str = "bt601", track: bool = False, track_config: Optional[Dict] = None, inventory=False):
+                 csc_matrix: str = "bt601", track: bool = False, track_config: Optional[Dict] = None, inventory=False,
+                 views=None, view_tile: Optional[int] = None, view_overlap: int = 0, view_full_frame: bool = True):
         """inventory: True or a dict of lp_inventory_config's fields (max_signs, keep_crops, best, min_hits): every tracked call
         also feeds the engine's sign inventory, while the handle still holds that call's classifier crops; drain_signs() returns
         the finished signs.  Needs track.
@@ -878,8 +953,18 @@ class HybridPipeline:
         converted on the device with csc_matrix ("bt601" = cv2's COLOR_YUV2BGR_NV12 constants, "bt709" = HD video).
         tile_overlap: None = every frame is letterboxed to det_input (the reference's behaviour); an int = tiled inference
         (lp_run_tiled): frames larger than det_input are also seen as native-resolution crops overlapping by that many pixels,
-        with the letterboxed whole frame as an extra view when tile_full_frame."""
+        with the letterboxed whole frame as an extra view when tile_full_frame.
+        views: scaled views (lp_run_views): a list of (x, y, w, h) source windows and / or "full", each letterboxed into the
+        detector batch at its own scale and applied to every frame; or view_tile (with view_overlap, view_full_frame): the
+        window grid of lp_view_grid for every frame's size.  Mutually exclusive with each other and with tile_overlap."""
         self.tile_overlap, self.tile_full_frame = tile_overlap, bool(tile_full_frame)
+        if sum(x is not None for x in (tile_overlap, views, view_tile)) > 1:
+            raise ValueError("tile_overlap, views and view_tile are mutually exclusive")
+        self.views = None if views is None else [tuple(r) for r in _view_array(views).tolist()]
+        if self.views is not None and not self.views:
+            raise ValueError("views needs at least one view")
+        self.view_tile, self.view_overlap, self.view_full_frame = view_tile, int(view_overlap), bool(view_full_frame)
+        self.view_mode = self.views is not None or view_tile is not None
         self.inventory = bool(inventory) or isinstance(inventory, dict)
         if self.inventory and not (track or track_config is not None):
             raise ValueError("inventory needs a pipeline constructed with track=True or a track_config")
@@ -996,6 +1081,40 @@ class HybridPipeline:
         return (np.concatenate([p[0] for p in parts], 0), np.concatenate([p[1] for p in parts]),
                 np.concatenate([p[2] for p in parts]), timing)
 
+    def _run_views(self, images, conf, iou, min_area, feed=None):
+        """run_batch's engine call with scaled views: consecutive frames that share a view list (view_tile: the grid of their
+        size) go to one lp_run_views call while frames x views fit max_batch and the ROIs fit max_rois; results concatenated
+        in frame order, stage times summed over the calls.  feed(dets, counts, first_frame) is called behind every engine call."""
+        cfg = self.engine.cfg
+        cap = cfg.max_batch
+        max_frames = max(1, (cfg.max_rois if cfg.max_rois > 0 else cfg.max_batch * cfg.max_det) // cfg.max_det)
+        groups, cur, cur_views = [], [], None
+        for img in images:
+            fh, fw = self.engine.frame_hw(img)
+            vs = self.views if self.views is not None else view_grid(self.view_tile, fh, fw, self.view_overlap, self.view_full_frame)
+            if len(vs) > cap:
+                raise ValueError(f"a {fw}x{fh} frame has {len(vs)} views, more than max_batch = {cap}")
+            if cur and (vs != cur_views or (len(cur) + 1) * len(vs) > cap or len(cur) >= max_frames):
+                groups.append((cur, cur_views))
+                cur = []
+            cur.append(img)
+            cur_views = vs
+        if cur:
+            groups.append((cur, cur_views))
+        parts, done = [], 0
+        for g, vs in groups:
+            d, c, nd, t = self.engine.run_views(g, vs, conf, iou, min_area)
+            parts.append((d, c, nd, t, self.engine.last_det_conf_avg))
+            if feed is not None:
+                feed(d[:len(g)], c[:len(g)], done)
+            done += len(g)
+        timing = LpTiming()
+        for f in ("t_detection", "t_roi_extract", "t_classification", "t_total"):
+            setattr(timing, f, sum(getattr(p[3], f) for p in parts))
+        self.engine.last_det_conf_avg = np.concatenate([p[4] for p in parts])
+        return (np.concatenate([p[0] for p in parts], 0), np.concatenate([p[1] for p in parts]),
+                np.concatenate([p[2] for p in parts]), timing)
+
     def _track(self, dets, counts, stream_ids):
         """the call's records through the engine's tracker, at most max_batch frames per lp_track call, in frame order"""
         B, cap = len(counts), self.engine.cfg.max_batch
@@ -1037,7 +1156,7 @@ class HybridPipeline:
     def run_batch(self, images: Sequence[np.ndarray], conf_threshold: float = 0.5, iou_threshold: float = 0.45,
                   min_area: int = 100, stream_ids=None, track: Optional[bool] = None) -> List[Tuple[List[Dict], PipelineMetrics]]:
         """stream_ids: the tracker stream of every image (None: all stream 0); track: None = the constructor's setting.
-        In tiled mode tracker and inventory are fed behind every lp_run_tiled call of the batch: if a later call of the batch
+        In tiled mode (and with scaled views) tracker and inventory are fed behind every engine call of the batch: if a later call of the batch
         fails, they have consumed the frames of the earlier ones although the caller gets no result for the batch."""
         do_track = self.track if track is None else bool(track)
         if do_track and not hasattr(self.engine, "track_cfg"):
@@ -1057,6 +1176,8 @@ class HybridPipeline:
         try:
             if self.tile_overlap is not None:
                 dets, counts, num_det, timing = self._run_tiled(list(images), conf_threshold, iou_threshold, min_area, feed if do_track else None)
+            elif self.view_mode:
+                dets, counts, num_det, timing = self._run_views(list(images), conf_threshold, iou_threshold, min_area, feed if do_track else None)
             elif self._lanes and len(images) >= 32 and len(images) <= self._lane_cap * len(self._lanes):
                 dets, counts, num_det, timing = self._run_lanes(list(images), conf_threshold, iou_threshold, min_area)
             else:
@@ -1069,7 +1190,7 @@ class HybridPipeline:
         tracks = None
         if do_track:
             B = len(images)
-            if self.tile_overlap is not None:
+            if self.tile_overlap is not None or self.view_mode:
                 tracks = np.concatenate(fed, 0)
             elif self.inventory:   # one engine call on this handle
                 tracks = self._feed(dets[:B], counts[:B], ids, 0)

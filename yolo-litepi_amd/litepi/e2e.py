@@ -83,6 +83,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "batch_images x the views of a 2048x2048 frame")
     p.add_argument("--tile_full_frame", type=int, choices=[0, 1], default=1,
                    help="tiled inference: the letterboxed whole frame is an extra view of every frame that needs crops")
+    p.add_argument("--view_tile", type=int, default=None,
+                   help="scaled views (off when absent): every frame is also seen through windows of this many pixels, each "
+                        "letterboxed to det_input (a 1280 window at det_input 640 is a half-resolution look), overlapping by "
+                        "--view_overlap, merged by one NMS per frame; excludes --tile_overlap and --views")
+    p.add_argument("--view_overlap", type=int, default=0, help="scaled views: pixels shared by neighbouring --view_tile windows")
+    p.add_argument("--view_full_frame", type=int, choices=[0, 1], default=1,
+                   help="scaled views: the letterboxed whole frame is an extra view of every frame that needs more than one window")
+    p.add_argument("--views", type=str, default=None,
+                   help='scaled views given one by one, applied to every frame: "full;x,y,w,h;..." (full = the letterboxed whole '
+                        'frame; x,y,w,h = a source window in frame pixels, letterboxed to det_input at its own scale)')
     p.add_argument("--raw_frames", type=str, default=None,
                    help="headerless file of concatenated video frames (ffmpeg -f rawvideo) evaluated instead of the images of --input; "
                         "needs --frame_size; frames are named frame_000001, frame_000002, ...")
@@ -343,7 +353,30 @@ SIGNS_CSV_COLUMNS = ("stream", "track_id", "first_frame", "last_frame", "hits", 
                      "y2", "det_class", "flushed", "crop")
 
 
+def parse_views(text: str) -> List:
+    """--views "full;x,y,w,h;..." -> ["full", (x, y, w, h), ...]"""
+    out = []
+    for part in text.split(";"):
+        part = part.strip()
+        if part == "full":
+            out.append("full")
+            continue
+        try:
+            x, y, w, h = (int(v) for v in part.split(","))
+        except ValueError:
+            raise SystemExit(f'--views: {part!r} is neither "full" nor x,y,w,h') from None
+        out.append((x, y, w, h))
+    if not out:
+        raise SystemExit("--views needs at least one view")
+    return out
+
+
 def check_frame_args(args) -> None:
+    modes = [n for n in ("tile_overlap", "view_tile", "views") if getattr(args, n, None) is not None]
+    if len(modes) > 1:
+        raise SystemExit("--" + ", --".join(modes) + " exclude each other: one way of looking at a frame per run")
+    if getattr(args, "views", None) is not None:
+        parse_views(args.views)
     if getattr(args, "inventory", False) and not getattr(args, "track", False):
         raise SystemExit("--inventory needs --track: the inventory lists the tracker's finished tracks")
     if getattr(args, "track", False):   # tracking needs the frames of ONE sequence, all of them, in order, in one process
@@ -409,6 +442,16 @@ def run_evaluation(args) -> Dict:
         from .backend import tile_grid
         max_batch = nb * len(tile_grid(args.det_input_size, 2048, 2048, args.tile_overlap, bool(args.tile_full_frame)))
         max_rois = max_rois if max_rois > 0 else nb * max_det
+    view_kw = {}
+    if getattr(args, "view_tile", None) is not None:   # likewise: the windows of batch_images TT100K-size frames
+        from .backend import view_grid
+        view_kw = dict(view_tile=args.view_tile, view_overlap=args.view_overlap, view_full_frame=bool(args.view_full_frame))
+        max_batch = nb * len(view_grid(args.view_tile, 2048, 2048, args.view_overlap, bool(args.view_full_frame)))
+        max_rois = max_rois if max_rois > 0 else nb * max_det
+    elif getattr(args, "views", None) is not None:
+        view_kw = dict(views=parse_views(args.views))
+        max_batch = nb * len(view_kw["views"])
+        max_rois = max_rois if max_rois > 0 else nb * max_det
     import contextlib
     import io
     # with --track off the pipeline is constructed and called exactly as before
@@ -422,7 +465,7 @@ def run_evaluation(args) -> Dict:
                                   args.batch_size, precision=args.precision, max_batch=max_batch, max_det=max_det,
                                   device=args.hip_device, max_rois=max_rois, numerics=args.numerics,
                                   tile_overlap=args.tile_overlap, tile_full_frame=bool(args.tile_full_frame),
-                                  pixel_format=args.pixel_format, csc_matrix=args.csc_matrix, **track_kw)
+                                  pixel_format=args.pixel_format, csc_matrix=args.csc_matrix, **view_kw, **track_kw)
     out_dir = Path(args.output) / combo
     out_dir.mkdir(parents=True, exist_ok=True)
 
@@ -453,7 +496,11 @@ def run_evaluation(args) -> Dict:
     try:
         n_warm = args.warmup if args.warmup is not None else (10 if args.numerics == "e2e_optimize" else 0)
         if n_warm > 0:   # warmup_pipeline (e2e_optimize.py:552-570): random frame, conf 0.5
-            dummy = np.random.randint(0, 255, (960, 640) if args.pixel_format == "nv12" else (640, 640, 3), dtype=np.uint8)
+            wh, ww = 640, 640
+            for v in view_kw.get("views", []):   # --views windows are frame pixels: the warm-up frame must hold them
+                if v != "full":
+                    wh, ww = max(wh, v[1] + v[3] + (v[1] + v[3]) % 2), max(ww, v[0] + v[2] + (v[0] + v[2]) % 2)
+            dummy = np.random.randint(0, 255, (wh * 3 // 2, ww) if args.pixel_format == "nv12" else (wh, ww, 3), dtype=np.uint8)
             for _ in range(n_warm):
                 if args.track:   # the warm-up frames are not part of the sequence: they never reach the tracker
                     pipeline.run_batch([dummy], 0.5, track=False)
