@@ -60,6 +60,57 @@ def test_view_grid_matches_python_on_random_cases():
         assert view_grid(tile, H, W, ov, full) == V.view_grid(tile, H, W, ov, full), (H, W, tile, ov, full)
 
 
+def _lib_views(call):
+    """a grid of the library as an int32 [n, 4] array: call(n, buf, cap) is lp_tile_grid / lp_view_grid with its leading arguments bound"""
+    from litepi import _ffi
+    n = C.c_int()
+    assert call(C.byref(n), None, 0) == _ffi.LP_OK
+    buf = np.empty((n.value, 4), np.int32)
+    assert call(C.byref(n), buf.ctypes.data_as(C.POINTER(C.c_int)), n.value) == _ffi.LP_OK
+    return buf
+
+
+def _ref_views(grid, axis, side, H, W, full):
+    """The reference's grid as an array.  Up to 4096 windows it is the reference's own list (tiling_ref.tile_grid,
+    views_ref.view_grid); a longer one (up to four million windows at overlap = tile - 1) is put together here from the
+    reference's axis rule, row-major behind the whole frame, without a Python tuple per window."""
+    xs, ys = axis(W), axis(H)
+    if len(xs) * len(ys) <= 4096:
+        return np.array(grid(H, W, full), np.int32).reshape(-1, 4)
+    v = np.empty((len(ys), len(xs), 4), np.int32)
+    v[..., 0], v[..., 1] = np.array(xs, np.int32)[None, :], np.array(ys, np.int32)[:, None]
+    v[..., 2], v[..., 3] = side(W), side(H)
+    head = np.array([[-1, -1, W, H]], np.int32) if full else np.empty((0, 4), np.int32)
+    return np.concatenate([head, v.reshape(-1, 4)])
+
+
+@pytest.mark.parametrize("tile", [64, 320, 640])
+def test_both_grids_equal_their_references_over_the_size_sweep(tile):
+    """lp_tile_grid (det_input = tile) and lp_view_grid share one axis and one emitter in the library; the two differ in the
+    window's side where the frame is not larger than the tile (the tile's against the frame's)."""
+    from litepi import _ffi
+    from litepi.backend import _tiling
+    lib = _ffi.load_library()
+    sizes = (16, 63, 64, 65, 320, 321, 640, 641, 1279, 2048)
+    n_cases = n_differ = 0
+    for ov in (0, 1, tile // 2, tile - 1):
+        for full in (True, False):
+            t = _tiling(ov, full)
+            for H in sizes:
+                for W in sizes:
+                    tiles = _lib_views(lambda n, buf, cap: lib.lp_tile_grid(tile, C.byref(t), H, W, n, buf, cap))
+                    views = _lib_views(lambda n, buf, cap: lib.lp_view_grid(tile, ov, int(full), H, W, n, buf, cap))
+                    exp_t = _ref_views(lambda h, w, f: T.tile_grid(tile, h, w, ov, f), lambda L: T.tile_axis(L, tile, ov), lambda L: tile,
+                                       H, W, full)
+                    exp_v = _ref_views(lambda h, w, f: V.view_grid(tile, h, w, ov, f), lambda L: V.view_axis(L, tile, ov)[0],
+                                       lambda L: V.view_axis(L, tile, ov)[1], H, W, full)
+                    assert np.array_equal(tiles, exp_t), ("lp_tile_grid", tile, ov, full, H, W)
+                    assert np.array_equal(views, exp_v), ("lp_view_grid", tile, ov, full, H, W)
+                    n_cases += 1
+                    n_differ += not np.array_equal(tiles, views)
+    assert n_cases == 800 and n_differ > 0   # e.g. a 63 x 2048 frame at tile 64: crops of 64 x 64, windows of 63 x 64
+
+
 def _geometry_bits(g):
     return (np.array([g["ratio"], g["pad_w"], g["pad_h"]], np.float32).view(np.uint32).tolist(),
             (g["new_w"], g["new_h"], g["top"], g["left"]))

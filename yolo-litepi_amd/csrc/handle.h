@@ -1,4 +1,4 @@
-// Internal to the C-ABI translation units (api.cpp, pipeline.cpp, pixfmt.cpp, tiling.cpp, views.cpp, tracking.cpp, inventory.cpp,
+// Internal to the C-ABI translation units (api.cpp, pipeline.cpp, pixfmt.cpp, views.cpp, tracking.cpp, inventory.cpp,
 // test_hooks.cpp): the handle behind include/litepi.h's lp_handle, the captured-step cache, and the pipeline pieces the entry points share.
 #pragma once
 #include <algorithm>
@@ -133,7 +133,7 @@ struct lp_handle {
   lp::DevBuf d_src, d_lb, d_geom, d_cand, d_cand_count, d_sorted, d_dets, d_counts, d_rects, d_out0;
   lp::DevBuf d_roi_base, d_roi_total, d_roi_img, d_roi_slot, d_roi_rgb, d_probs, d_ids, d_conf;
   std::vector<lp::ImgGeom> geom_cache;
-  // tiled inference (lp_run_tiled*): frame geometry, frame table + view slots, per-view counts; allocated on first use
+  // frame views (lp_run_tiled*, lp_run_views*): frame geometry, frame table + view slots, per-view counts; allocated on first use
   lp::DevBuf d_fgeom, d_ftab, d_vcnt;
   lp::DevBuf d_vwin;   // scaled views (lp_run_views*): the window table, [max_batch] ViewWin; allocated on first use
   std::vector<char> tile_cache;
@@ -218,6 +218,13 @@ namespace lp {
 // letterbox geometry exactly as the reference computes it in Python doubles (e2e.py:72-83)
 ImgGeom make_geom(int h, int w, int S, long src_off);
 Profiler* begin_profile(lp_handle* h);
+// the argument checks of lp_run_batch*, lp_run_tiled* and lp_run_views*: pointers, loaded models (host calls need the classifier),
+// batch size, and for host calls min_area
+void check_run_args(const lp_handle* h, bool pointers, int B, bool host, int min_area);
+// the letterbox of n images (geometry geoms on the host, d_geom on the device) into dst [n,S,S,3], booked as every source byte
+// once + every output byte once
+void enqueue_letterbox(const uint8_t* src, const ImgGeom* d_geom, uint8_t* dst, const ImgGeom* geoms, int n, int S, hipStream_t st,
+                       Profiler* prof);
 // detector (+ optional letterbox) on images resident at src with geometry already uploaded
 void enqueue_detect(lp_handle* h, const uint8_t* src, const std::vector<ImgGeom>& geoms, int B, float conf, float* out0, Profiler* prof);
 // NMS + ROI rectangles; with_rois: also the batch-wide ROI list the classifier stage consumes
@@ -251,7 +258,7 @@ CscPlan device_csc(lp_handle* h, const void* dev_imgs, int B, int H, int W, std:
 // upload B host images of individual sizes into d_src (NV12 frames: into d_raw, with the plan of their conversion into d_src
 // in *csc); returns their geometry
 std::vector<ImgGeom> upload_images(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, CscPlan* csc = nullptr);
-// The staged host pass of lp_run_batch and lp_run_tiled: `front` (colour conversion + detect + NMS of either kind), the ROI
+// The staged host pass of lp_run_batch, lp_run_tiled and lp_run_views: `front` (colour conversion + detect + NMS of either kind), the ROI
 // resize reading roi_geom (nullptr: d_geom) and the classifier as three captured pieces with the stage events between them,
 // then records, counts and timing back on the host.  An overflow of max_rois is reported last: the records are delivered.
 void run_host_pass(lp_handle* h, int B, float conf, float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg,
@@ -266,35 +273,34 @@ struct CropRois {
 };
 CropRois whole_crop_rois(const uint8_t* const* rois, const int* hs, const int* ws, int R);
 
-// ---- tiled inference (tiling.cpp) ----------------------------------------------------------------------------------------------
-// The call's view layout.  Batch slots: first the letterboxed views (one launch of the letterbox kernel, so they are exactly
-// lp_run_batch's input), then the crops.  frames[f] / vslot list each frame's slots in the frame's view order.
-struct TileLayout {
+// ---- frame views: tiled inference and scaled views (views.cpp) ------------------------------------------------------------------
+// One view of a frame: the letterboxed whole frame, a native S x S crop at (x, y) -- it may pass the frame's edge where the
+// frame is shorter than S --, or the window {x, y, w, h} letterboxed at its own scale.
+enum ViewKind { VIEW_FULL, VIEW_CROP, VIEW_WINDOW };
+struct FrameView { ViewKind kind; int x, y, w, h; };
+using FrameViews = std::vector<std::vector<FrameView>>;   // every frame's views, in the frame's view order
+// The call's view layout.  Batch slots: first the L letterboxed views (one launch of the letterbox kernel, so they are exactly
+// lp_run_batch's input), then the C crops, then the windows, whose table entries wins[i] fill slot L + C + i (no windows: an
+// empty table).  frames[f] / vslot list each frame's slots in the frame's view order.
+struct ViewLayout {
   std::vector<ImgGeom> vgeom;     // [V] by slot
   std::vector<TileFrame> frames;  // [F]
   std::vector<int> vslot;         // [V] frame-major
-  int L = 0, V = 0, max_views = 0;
+  std::vector<ViewWin> wins;      // [V - L - C]
+  int L = 0, C = 0, V = 0, max_views = 0;
 };
 void check_tiling(const lp_tiling* t, int S);
-TileLayout tile_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const lp_tiling& t);
-// upload the frame geometry, the frame table, the view slots, the view geometry and (scaled views) the window table when any
-// of them changed; a change invalidates captured graphs (geom_ver)
-void upload_tiles(lp_handle* h, const std::vector<ImgGeom>& fg, const TileLayout& lay, const std::vector<ViewWin>* wins = nullptr);
-// the detector on the V gathered views in d_lb + view sort + frame NMS (+ the ROI list when with_rois)
-void enqueue_view_detect(lp_handle* h, const TileLayout& lay, int F, float conf, float iou, int min_area, lp_det* dets, int* counts,
-                         bool with_rois, Profiler* prof);
-
-// ---- scaled views (views.cpp) --------------------------------------------------------------------------------------------------
-// The layout of a call whose frames are all seen through ONE list of {x, y, w, h} views (include/litepi.h "scaled views").
-// Batch slots: first the whole-frame views (x = -1; launch_letterbox, so they are exactly lp_run_batch's input), then the
-// windows, whose table entries wins[i] fill slot lay.L + i.
-struct ViewLayout {
-  TileLayout lay;
-  std::vector<ViewWin> wins;   // [V - L]
-};
-ViewLayout view_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const int* views, int n_views);
-// whole-frame views through launch_letterbox, windows through launch_window_views, into dst [V,S,S,3]
-void enqueue_view_gather(const uint8_t* src, const ImgGeom* d_geom, const ViewWin* d_wins, uint8_t* dst, const ViewLayout& vl, int S,
+// the frames' views under tiling (lp_tile_grid of every frame) / through one list of {x, y, w, h} views, validated against every frame
+FrameViews tiled_views(int S, const lp_tiling& t, const std::vector<ImgGeom>& fg);
+FrameViews listed_views(const lp_handle* h, const int* views, int n_views, const std::vector<ImgGeom>& fg);
+// the one builder; LP_ERR_ARG for more views than max_batch or than the frame NMS holds per frame
+ViewLayout view_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const FrameViews& per);
+// upload the frame geometry, the frame table, the view slots, the view geometry and the window table when any of them changed;
+// a change invalidates captured graphs (geom_ver)
+void upload_tiles(lp_handle* h, const std::vector<ImgGeom>& fg, const ViewLayout& lay);
+// letterboxed views through launch_letterbox, crops through launch_crop_views, windows through launch_window_views, into dst
+// [V,S,S,3]; what the layout does not contain is not launched
+void enqueue_view_gather(const uint8_t* src, const ImgGeom* d_geom, const ViewWin* d_wins, uint8_t* dst, const ViewLayout& lay, int S,
                          hipStream_t st, Profiler* prof);
 
 }  // namespace lp

@@ -29,6 +29,25 @@ Profiler* begin_profile(lp_handle* h) {
   return &h->prof;
 }
 
+void check_run_args(const lp_handle* h, bool pointers, int B, bool host, int min_area) {
+  LP_CHECK(h && pointers, LP_ERR_ARG, "null argument");
+  LP_CHECK(h->det && h->det->loaded(), LP_ERR_STATE, "detector not loaded");
+  LP_CHECK(!host || (h->cls && h->cls->loaded()), LP_ERR_STATE, "classifier not loaded");
+  LP_CHECK(B >= 1 && B <= h->cfg.max_batch, LP_ERR_ARG, "batch %d outside 1..%d", B, h->cfg.max_batch);
+  LP_CHECK(!host || min_area >= 0, LP_ERR_ARG, "min_area must be >= 0");
+}
+
+void enqueue_letterbox(const uint8_t* src, const ImgGeom* d_geom, uint8_t* dst, const ImgGeom* geoms, int n, int S, hipStream_t st,
+                       Profiler* prof) {
+  if (prof) prof->begin(st);
+  launch_letterbox(src, d_geom, dst, n, S, st, geoms);
+  if (prof) {
+    double bytes = (double)n * S * S * 3;
+    for (int i = 0; i < n; ++i) bytes += (double)geoms[i].h * geoms[i].w * 3;
+    prof->end(st, "letterbox_u8", "letterbox", 0.0, bytes);
+  }
+}
+
 // detector (+ optional letterbox) on images resident at src with geometry already uploaded
 void enqueue_detect(lp_handle* h, const uint8_t* src, const std::vector<ImgGeom>& geoms, int B, float conf, float* out0,
                     Profiler* prof) {
@@ -38,13 +57,7 @@ void enqueue_detect(lp_handle* h, const uint8_t* src, const std::vector<ImgGeom>
     identity = identity && geoms[i].h == S && geoms[i].w == S && geoms[i].src_off == (long)i * S * S * 3;
   const uint8_t* img = src;
   if (!identity) {
-    if (prof) prof->begin(h->stream);
-    launch_letterbox(src, h->d_geom.as<ImgGeom>(), h->d_lb.as<uint8_t>(), B, S, h->stream, geoms.data());
-    if (prof) {
-      double bytes = (double)B * S * S * 3;
-      for (int i = 0; i < B; ++i) bytes += (double)geoms[i].h * geoms[i].w * 3;
-      prof->end(h->stream, "letterbox_u8", "letterbox", 0.0, bytes);
-    }
+    enqueue_letterbox(src, h->d_geom.as<ImgGeom>(), h->d_lb.as<uint8_t>(), geoms.data(), B, S, h->stream, prof);
     img = h->d_lb.as<uint8_t>();
   }
   h->det->forward(img, B, h->d_geom.as<ImgGeom>(), conf, out0, h->d_cand.as<Cand>(), h->d_cand_count.as<int>(), h->stream, prof);
@@ -337,11 +350,7 @@ int lp_detect(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int
 int lp_run_batch(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, float conf, float iou,
                  int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing) {
   LP_API_BEGIN
-  LP_CHECK(h && imgs && hs && ws && dets && counts, LP_ERR_ARG, "null argument");
-  LP_CHECK(h->det && h->det->loaded(), LP_ERR_STATE, "detector not loaded");
-  LP_CHECK(h->cls && h->cls->loaded(), LP_ERR_STATE, "classifier not loaded");
-  LP_CHECK(B >= 1 && B <= h->cfg.max_batch, LP_ERR_ARG, "batch %d outside 1..%d", B, h->cfg.max_batch);
-  LP_CHECK(min_area >= 0, LP_ERR_ARG, "min_area must be >= 0");
+  check_run_args(h, imgs && hs && ws && dets && counts, B, true, min_area);
   LP_HIP(hipSetDevice(h->cfg.device));
   const bool nv = h->nv12();
   CscPlan csc;
@@ -359,9 +368,8 @@ int lp_run_batch(lp_handle* h, const uint8_t* const* imgs, const int* hs, const 
 int lp_run_batch_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, float conf, float iou, int min_area,
                         void* dev_dets, void* dev_counts) {
   LP_API_BEGIN
-  LP_CHECK(h && dev_imgs && dev_dets && dev_counts, LP_ERR_ARG, "null argument");
-  LP_CHECK(h->det && h->det->loaded(), LP_ERR_STATE, "detector not loaded");
-  LP_CHECK(B >= 1 && B <= h->cfg.max_batch && H > 0 && W > 0, LP_ERR_ARG, "bad batch/shape");
+  check_run_args(h, dev_imgs && dev_dets && dev_counts, B, false, min_area);
+  LP_CHECK(H > 0 && W > 0, LP_ERR_ARG, "frames of %dx%d", W, H);
   LP_HIP(hipSetDevice(h->cfg.device));
   std::vector<ImgGeom> g(B);
   const bool nv = h->nv12();

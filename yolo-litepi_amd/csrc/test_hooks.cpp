@@ -33,6 +33,27 @@ void nms_one_image(lp_handle* h, const DevBuf& d_geom, const DevBuf& d_cand, con
   read_one_image(h, d_dets, d_counts, d_rects, dets, rects, count, num_det);
 }
 
+// The views of one frame through enqueue_view_gather on buffers of its own, back in the frame's view order.  The frame is
+// uploaded frame.src_off bytes into an allocation of its size + slack bytes.
+void gather_one_frame(lp_handle* h, const uint8_t* img, const ImgGeom& frame, size_t slack, const ViewLayout& lay, uint8_t* out) {
+  const int S = h->cfg.det_input;
+  const size_t bytes = (size_t)frame.h * frame.w * 3, vb = (size_t)S * S * 3;
+  DevBuf d_src, d_geom, d_wins, d_out;
+  d_src.alloc(bytes + slack);
+  LP_HIP(hipMemcpy(d_src.as<uint8_t>() + frame.src_off, img, bytes, hipMemcpyHostToDevice));
+  d_geom.alloc((size_t)lay.V * sizeof(ImgGeom));
+  LP_HIP(hipMemcpy(d_geom.p, lay.vgeom.data(), (size_t)lay.V * sizeof(ImgGeom), hipMemcpyHostToDevice));
+  if (!lay.wins.empty()) {
+    d_wins.alloc(lay.wins.size() * sizeof(ViewWin));
+    LP_HIP(hipMemcpy(d_wins.p, lay.wins.data(), lay.wins.size() * sizeof(ViewWin), hipMemcpyHostToDevice));
+  }
+  d_out.alloc((size_t)lay.V * vb);
+  enqueue_view_gather(d_src.as<uint8_t>(), d_geom.as<ImgGeom>(), d_wins.as<ViewWin>(), d_out.as<uint8_t>(), lay, S, h->stream, nullptr);
+  LP_HIP(hipStreamSynchronize(h->stream));
+  for (int k = 0; k < lay.V; ++k)
+    LP_HIP(hipMemcpy(out + (size_t)k * vb, d_out.as<uint8_t>() + (size_t)lay.vslot[k] * vb, vb, hipMemcpyDeviceToHost));
+}
+
 }  // namespace
 
 extern "C" {
@@ -98,25 +119,24 @@ int lp_test_tile_views(lp_handle* h, const uint8_t* img, int H, int W, const lp_
   LP_CHECK(h && img && n_views && H > 0 && W > 0 && byte_offset >= 0 && byte_offset < 64, LP_ERR_ARG, "bad argument");
   check_tiling(tiling, h->cfg.det_input);
   LP_HIP(hipSetDevice(h->cfg.device));
-  const int S = h->cfg.det_input;
-  const size_t bytes = (size_t)H * W * 3;
-  std::vector<ImgGeom> fg(1, make_geom(H, W, S, byte_offset));
-  const TileLayout lay = tile_layout(h, fg, *tiling);
+  const std::vector<ImgGeom> fg(1, make_geom(H, W, h->cfg.det_input, byte_offset));
+  const ViewLayout lay = view_layout(h, fg, tiled_views(h->cfg.det_input, *tiling, fg));
   *n_views = lay.V;
   LP_CHECK(!out || cap >= lay.V, LP_ERR_ARG, "%d views, room for %d", lay.V, cap);
-  if (!out) return LP_OK;
-  DevBuf d_src, d_geom, d_out;
-  d_src.alloc(bytes + 64);
-  LP_HIP(hipMemcpy(d_src.as<uint8_t>() + byte_offset, img, bytes, hipMemcpyHostToDevice));
-  d_geom.alloc((size_t)lay.V * sizeof(ImgGeom));
-  LP_HIP(hipMemcpy(d_geom.p, lay.vgeom.data(), (size_t)lay.V * sizeof(ImgGeom), hipMemcpyHostToDevice));
-  d_out.alloc((size_t)lay.V * S * S * 3);
-  if (lay.L > 0) launch_letterbox(d_src.as<uint8_t>(), d_geom.as<ImgGeom>(), d_out.as<uint8_t>(), lay.L, S, h->stream, lay.vgeom.data());
-  launch_crop_views(d_src.as<uint8_t>(), d_geom.as<ImgGeom>(), d_out.as<uint8_t>(), lay.L, lay.V - lay.L, S, h->stream);
-  LP_HIP(hipStreamSynchronize(h->stream));
-  const size_t vb = (size_t)S * S * 3;
-  for (int k = 0; k < lay.V; ++k)   // in the frame's view order
-    LP_HIP(hipMemcpy(out + (size_t)k * vb, d_out.as<uint8_t>() + (size_t)lay.vslot[k] * vb, vb, hipMemcpyDeviceToHost));
+  if (out) gather_one_frame(h, img, fg[0], 64, lay, out);
+  LP_API_END
+}
+
+int lp_test_view_windows(lp_handle* h, const uint8_t* img, int H, int W, const int* views, int n_views, int byte_offset, uint8_t* out,
+                         int cap) {
+  LP_API_BEGIN
+  LP_CHECK(h && img && out && H > 0 && W > 0 && byte_offset >= 0 && byte_offset < 64, LP_ERR_ARG, "bad argument");
+  LP_HIP(hipSetDevice(h->cfg.device));
+  const std::vector<ImgGeom> fg(1, make_geom(H, W, h->cfg.det_input, byte_offset));
+  const ViewLayout lay = view_layout(h, fg, listed_views(h, views, n_views, fg));
+  LP_CHECK(cap >= lay.V, LP_ERR_ARG, "%d views, room for %d", lay.V, cap);
+  // the frame is the whole allocation but for the offset in front: nothing the gather may read lies beyond it
+  gather_one_frame(h, img, fg[0], byte_offset, lay, out);
   LP_API_END
 }
 

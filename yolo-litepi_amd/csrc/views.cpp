@@ -1,19 +1,59 @@
-// Scaled views (lp_view_grid, lp_view_geometry, lp_run_views*, lp_test_view_windows; include/litepi.h "scaled views"): any
-// window of a frame, letterboxed into the detector batch at its own scale.  The view's ImgGeom carries the window as
-// ratio / pad, so decode, frame NMS, ROI stage, tracker and inventory run as in tiled inference (tiling.cpp).
+// Frame views: tiled inference (lp_tile_grid, lp_run_tiled*) and scaled views (lp_view_grid, lp_view_geometry, lp_run_views*;
+// include/litepi.h "tiled inference", "scaled views").  A frame is seen through a list of views -- the letterboxed whole frame,
+// native crops, windows letterboxed at their own scale --; every view's ImgGeom carries its place in the frame as ratio / pad,
+// so decode, frame NMS, ROI stage, tracker and inventory do not know which kind a view is.  One grid, one layout, one gather
+// and one host / one device front serve both families: they differ in how a call's frames become view lists.
 #include <cmath>
 
 #include "handle.h"
 
 namespace lp {
 
-// one axis of the window grid (include/litepi.h lp_view_grid): origins and the common side
-static int view_axis(int L, int tile, int overlap, std::vector<int>& xs) {
-  xs.clear();
-  if (L <= tile) { xs.push_back(0); return L; }
+// ---- the view grid -------------------------------------------------------------------------------------------------------------
+// one axis of a view grid: the origins of windows of side `tile` overlapping by `overlap` ({0} where one window covers the axis)
+static std::vector<int> grid_axis(int L, int tile, int overlap) {
+  if (L <= tile) return {0};
   const int step = tile - overlap, n = 1 + (L - tile + step - 1) / step;
-  for (int k = 0; k < n; ++k) xs.push_back(std::min(k * step, L - tile));
-  return tile;
+  std::vector<int> xs(n);
+  for (int k = 0; k < n; ++k) xs[k] = std::min(k * step, L - tile);
+  return xs;
+}
+
+// The views of an H x W frame as {x, y, w, h}: {-1, -1, W, H}, the letterboxed whole frame, when full_frame or when one window
+// covers the frame, then the ys x xs windows row-major.  clip: a window's side is the frame's where that is shorter than `tile`
+// (lp_view_grid); otherwise every window is tile x tile and may pass the frame's edge (lp_tile_grid's crops).
+static std::vector<std::array<int, 4>> grid_views(int H, int W, int tile, int overlap, int full_frame, bool clip) {
+  const std::vector<int> xs = grid_axis(W, tile, overlap), ys = grid_axis(H, tile, overlap);
+  const int sw = clip ? std::min(W, tile) : tile, sh = clip ? std::min(H, tile) : tile;
+  std::vector<std::array<int, 4>> v;
+  if (xs.size() * ys.size() == 1 || full_frame) v.push_back({-1, -1, W, H});
+  if (xs.size() * ys.size() > 1)
+    for (int y : ys)
+      for (int x : xs) v.push_back({x, y, sw, sh});
+  return v;
+}
+
+static void write_views(const std::vector<std::array<int, 4>>& v, int* n_views, int* views, int cap) {
+  *n_views = (int)v.size();
+  if (!views) return;
+  LP_CHECK(cap >= (int)v.size(), LP_ERR_ARG, "%zu views, room for %d", v.size(), cap);
+  for (size_t i = 0; i < v.size(); ++i)
+    for (int k = 0; k < 4; ++k) views[4 * i + k] = v[i][k];
+}
+
+void check_tiling(const lp_tiling* t, int S) {
+  LP_CHECK(t, LP_ERR_ARG, "null tiling");
+  LP_CHECK(t->overlap >= 0 && t->overlap < S, LP_ERR_ARG, "tiling overlap %d outside 0..%d", t->overlap, S - 1);
+  LP_CHECK(t->full_frame == 0 || t->full_frame == 1, LP_ERR_ARG, "tiling full_frame must be 0 or 1 (got %d)", t->full_frame);
+}
+
+// ---- a call's frames as view lists ---------------------------------------------------------------------------------------------
+FrameViews tiled_views(int S, const lp_tiling& t, const std::vector<ImgGeom>& fg) {
+  FrameViews per(fg.size());
+  for (size_t f = 0; f < fg.size(); ++f)
+    for (const auto& w : grid_views(fg[f].h, fg[f].w, S, t.overlap, t.full_frame, false))
+      per[f].push_back(FrameView{w[0] < 0 ? VIEW_FULL : VIEW_CROP, w[0], w[1], w[2], w[3]});
+  return per;
 }
 
 // a view of an H x W frame as the window it covers; LP_ERR_ARG for a window the frame does not hold
@@ -26,6 +66,23 @@ static std::array<int, 4> view_window(const int* v, int H, int W, int index) {
   return {v[0], v[1], v[2], v[3]};
 }
 
+static void check_view_count(const lp_handle* h, int F, long V) {
+  LP_CHECK(V <= h->cfg.max_batch, LP_ERR_ARG, "%d frames need %ld views, more than max_batch = %d: split the call", F, V, h->cfg.max_batch);
+}
+
+FrameViews listed_views(const lp_handle* h, const int* views, int n_views, const std::vector<ImgGeom>& fg) {
+  LP_CHECK(views && n_views >= 1, LP_ERR_ARG, "a call needs at least one view (n_views = %d)", n_views);
+  check_view_count(h, (int)fg.size(), (long)fg.size() * n_views);   // before a list of any length is copied once per frame
+  FrameViews per(fg.size());
+  for (size_t f = 0; f < fg.size(); ++f)
+    for (int k = 0; k < n_views; ++k) {
+      const std::array<int, 4> w = view_window(views + 4 * k, fg[f].h, fg[f].w, k);
+      per[f].push_back(FrameView{views[4 * k] == -1 ? VIEW_FULL : VIEW_WINDOW, w[0], w[1], w[2], w[3]});
+    }
+  return per;
+}
+
+// ---- the layout ----------------------------------------------------------------------------------------------------------------
 // geometry of the window {x, y, w, h} of a frame: make_geom of a h x w image, the pads moved by the window's origin
 static ImgGeom window_geom(const ImgGeom& frame, const std::array<int, 4>& win, int S) {
   ImgGeom g = make_geom(win[3], win[2], S, frame.src_off);
@@ -37,68 +94,194 @@ static ImgGeom window_geom(const ImgGeom& frame, const std::array<int, 4>& win, 
   return g;
 }
 
-ViewLayout view_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const int* views, int n_views) {
+ViewLayout view_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const FrameViews& per) {
   const int S = h->cfg.det_input, F = (int)fg.size();
-  LP_CHECK(views && n_views >= 1, LP_ERR_ARG, "a call needs at least one view (n_views = %d)", n_views);
-  LP_CHECK((long)F * n_views <= h->cfg.max_batch, LP_ERR_ARG, "%d frames x %d views are more than max_batch = %d: split the call", F, n_views,
-           h->cfg.max_batch);
+  ViewLayout lay;
+  int count[3] = {0, 0, 0};   // by ViewKind
+  for (const auto& views : per) {
+    for (const FrameView& v : views) ++count[v.kind];
+    lay.max_views = std::max(lay.max_views, (int)views.size());
+  }
+  lay.L = count[VIEW_FULL]; lay.C = count[VIEW_CROP];
+  lay.V = lay.L + lay.C + count[VIEW_WINDOW];
+  check_view_count(h, F, lay.V);
   if (h->det && h->det->loaded()) {   // the frame NMS's LDS flag masks: checked here, before anything is enqueued
     const int A = h->det->num_anchors();
-    LP_CHECK(n_views <= 1024 && frame_nms_lds_bytes(n_views * A) <= FRAME_NMS_LDS_CAP, LP_ERR_ARG,
-             "a frame of %d views x %d anchors exceeds the frame NMS capacity (%d candidate slots per frame)", n_views, A,
-             (int)((FRAME_NMS_LDS_CAP - 16) / 8 * 32));
+    LP_CHECK(lay.max_views <= 1024 && frame_nms_lds_bytes(lay.max_views * A) <= FRAME_NMS_LDS_CAP, LP_ERR_ARG,
+             "a frame of %d views x %d anchors exceeds the frame NMS capacity (%d candidate slots per frame): use fewer views per "
+             "frame (tiled: raise the overlap or lower the frame size)", lay.max_views, A, (int)((FRAME_NMS_LDS_CAP - 16) / 8 * 32));
   }
-  int n_full = 0;
-  for (int k = 0; k < n_views; ++k) n_full += views[4 * k] == -1;
-  ViewLayout vl;
-  TileLayout& lay = vl.lay;
-  lay.L = F * n_full; lay.V = F * n_views; lay.max_views = n_views;
   lay.vgeom.resize(lay.V);
-  vl.wins.resize(lay.V - lay.L);
-  int next_lb = 0, next_win = lay.L;
+  lay.wins.resize(count[VIEW_WINDOW]);
+  int next[3] = {0, lay.L, lay.L + lay.C};   // the first slot of every kind
   for (int f = 0; f < F; ++f) {
-    lay.frames.push_back(TileFrame{(int)lay.vslot.size(), n_views});
-    for (int k = 0; k < n_views; ++k) {
-      const std::array<int, 4> win = view_window(views + 4 * k, fg[f].h, fg[f].w, k);
-      const bool full = views[4 * k] == -1;
-      const int slot = full ? next_lb++ : next_win++;
-      lay.vgeom[slot] = full ? fg[f] : window_geom(fg[f], win, S);
-      lay.vslot.push_back(slot);
-      if (!full) {
-        const ImgGeom& g = lay.vgeom[slot];
+    lay.frames.push_back(TileFrame{(int)lay.vslot.size(), (int)per[f].size()});
+    for (const FrameView& v : per[f]) {
+      const int slot = next[v.kind]++;
+      ImgGeom g = fg[f];   // letterbox geometry of the whole frame (make_geom)
+      if (v.kind == VIEW_CROP) {
+        g.new_w = S; g.new_h = S; g.top = -v.y; g.left = -v.x;
+        g.ratio = 1.0f; g.pad_w = -(float)v.x; g.pad_h = -(float)v.y;
+      } else if (v.kind == VIEW_WINDOW) {
+        g = window_geom(fg[f], {v.x, v.y, v.w, v.h}, S);
         ViewWin w;
         memset(&w, 0, sizeof(w));   // padding bytes too: the table is compared with memcmp
         w.src_off = fg[f].src_off; w.pitch = 3 * fg[f].w; w.frame_bytes = (long)fg[f].h * w.pitch;
-        w.x = win[0]; w.y = win[1]; w.w = win[2]; w.h = win[3];
+        w.x = v.x; w.y = v.y; w.w = v.w; w.h = v.h;
         w.new_w = g.new_w; w.new_h = g.new_h; w.top = g.top; w.left = g.left;
-        vl.wins[slot - lay.L] = w;
+        lay.wins[slot - lay.L - lay.C] = w;
       }
+      lay.vgeom[slot] = g;
+      lay.vslot.push_back(slot);
     }
   }
-  return vl;
+  return lay;
 }
 
-void enqueue_view_gather(const uint8_t* src, const ImgGeom* d_geom, const ViewWin* d_wins, uint8_t* dst, const ViewLayout& vl, int S,
-                         hipStream_t st, Profiler* prof) {
-  const TileLayout& lay = vl.lay;
-  if (lay.L > 0) {
-    if (prof) prof->begin(st);
-    launch_letterbox(src, d_geom, dst, lay.L, S, st, lay.vgeom.data());
-    if (prof) {
-      double bytes = (double)lay.L * S * S * 3;
-      for (int i = 0; i < lay.L; ++i) bytes += (double)lay.vgeom[i].h * lay.vgeom[i].w * 3;
-      prof->end(st, "letterbox_u8", "letterbox", 0.0, bytes);
-    }
+// upload the frame geometry, the frame table, the view slots, the view geometry and the window table when any of them changed;
+// a change invalidates captured graphs (geom_ver)
+void upload_tiles(lp_handle* h, const std::vector<ImgGeom>& fg, const ViewLayout& lay) {
+  const int B = h->cfg.max_batch;
+  if (!h->d_fgeom.p) {
+    h->d_fgeom.alloc((size_t)B * sizeof(ImgGeom));
+    h->d_ftab.alloc((size_t)B * (sizeof(TileFrame) + sizeof(int)));
+    h->d_vcnt.alloc((size_t)B * 4);
   }
-  if (lay.V > lay.L) {
+  const size_t nw = lay.wins.size();
+  if (nw && !h->d_vwin.p) h->d_vwin.alloc((size_t)B * sizeof(ViewWin));
+  h->upload_geom(lay.vgeom);
+  const size_t nf = fg.size();
+  std::vector<char> blob(nf * sizeof(ImgGeom) + nf * sizeof(TileFrame) + lay.vslot.size() * sizeof(int) + nw * sizeof(ViewWin));
+  memcpy(blob.data(), fg.data(), nf * sizeof(ImgGeom));
+  memcpy(blob.data() + nf * sizeof(ImgGeom), lay.frames.data(), nf * sizeof(TileFrame));
+  memcpy(blob.data() + nf * (sizeof(ImgGeom) + sizeof(TileFrame)), lay.vslot.data(), lay.vslot.size() * sizeof(int));
+  if (nw) memcpy(blob.data() + blob.size() - nw * sizeof(ViewWin), lay.wins.data(), nw * sizeof(ViewWin));
+  if (blob == h->tile_cache) return;
+  LP_HIP(hipMemcpyAsync(h->d_fgeom.p, fg.data(), nf * sizeof(ImgGeom), hipMemcpyHostToDevice, h->stream));
+  LP_HIP(hipMemcpyAsync(h->d_ftab.p, lay.frames.data(), nf * sizeof(TileFrame), hipMemcpyHostToDevice, h->stream));
+  LP_HIP(hipMemcpyAsync(h->d_ftab.as<char>() + (size_t)B * sizeof(TileFrame), lay.vslot.data(), lay.vslot.size() * sizeof(int),
+                        hipMemcpyHostToDevice, h->stream));
+  if (nw) LP_HIP(hipMemcpyAsync(h->d_vwin.p, lay.wins.data(), nw * sizeof(ViewWin), hipMemcpyHostToDevice, h->stream));
+  LP_HIP(hipStreamSynchronize(h->stream));
+  h->tile_cache.swap(blob);
+  ++h->geom_ver;
+}
+
+// ---- gather and detect ---------------------------------------------------------------------------------------------------------
+void enqueue_view_gather(const uint8_t* src, const ImgGeom* d_geom, const ViewWin* d_wins, uint8_t* dst, const ViewLayout& lay, int S,
+                         hipStream_t st, Profiler* prof) {
+  const int nwin = (int)lay.wins.size();
+  if (lay.L > 0) enqueue_letterbox(src, d_geom, dst, lay.vgeom.data(), lay.L, S, st, prof);
+  if (lay.C > 0) {
     if (prof) prof->begin(st);
-    launch_window_views(src, d_wins, dst, lay.L, lay.V - lay.L, S, st, vl.wins.data());
+    launch_crop_views(src, d_geom, dst, lay.L, lay.C, S, st);
+    if (prof) prof->end(st, "tile_crop_u8", "tile_crop", 0.0, 2.0 * lay.C * S * S * 3);
+  }
+  if (nwin > 0) {
+    if (prof) prof->begin(st);
+    launch_window_views(src, d_wins, dst, lay.L + lay.C, nwin, S, st, lay.wins.data());
     if (prof) {   // booked like the letterbox: every window byte once, every view byte once
-      double bytes = (double)(lay.V - lay.L) * S * S * 3;
-      for (const ViewWin& w : vl.wins) bytes += (double)w.h * w.w * 3;
+      double bytes = (double)nwin * S * S * 3;
+      for (const ViewWin& w : lay.wins) bytes += (double)w.h * w.w * 3;
       prof->end(st, "window_views_u8", "view_gather", 0.0, bytes);
     }
   }
+}
+
+// the detector on the gathered views + view sort + frame NMS (+ the ROI list when with_rois)
+static void enqueue_view_detect(lp_handle* h, const ViewLayout& lay, int F, float conf, float iou, int min_area, lp_det* dets, int* counts,
+                                bool with_rois, Profiler* prof) {
+  h->det->forward(h->d_lb.as<uint8_t>(), lay.V, h->d_geom.as<ImgGeom>(), conf, nullptr, h->d_cand.as<Cand>(), h->d_cand_count.as<int>(),
+                  h->stream, prof);
+  FrameNmsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.cand = h->d_cand.as<Cand>(); a.cand_count = h->d_cand_count.as<int>(); a.vcnt = h->d_vcnt.as<int>(); a.sorted = h->d_sorted.as<Cand>();
+  a.frames = h->d_ftab.as<TileFrame>();
+  a.vslot = reinterpret_cast<const int*>(h->d_ftab.as<char>() + (size_t)h->cfg.max_batch * sizeof(TileFrame));
+  a.dets = dets; a.counts = counts; a.rects = h->d_rects.as<int>(); a.fgeom = h->d_fgeom.as<ImgGeom>();
+  a.A = h->det->num_anchors(); a.max_det = h->cfg.max_det; a.nc = h->det->num_classes(); a.iou = iou; a.min_area = min_area;
+  if (with_rois) a.tab = h->roi_table();
+  a.max_rois = h->max_rois;
+  a.roi_rule = h->cfg.numerics;
+  if (prof) prof->begin(h->stream);
+  launch_view_sort(a, lay.V, h->stream);
+  if (prof) prof->end(h->stream, "view_sort", "nms", 0.0, 0.0);
+  if (prof) prof->begin(h->stream);
+  launch_frame_nms(a, F, lay.max_views, h->stream);
+  if (prof) prof->end(h->stream, "frame_nms", "nms", 0.0, 0.0);
+}
+
+// view gather + detector on the views + frame NMS (+ the ROI list when with_rois)
+static void enqueue_view_front(lp_handle* h, const uint8_t* src, const ViewLayout& lay, int F, float conf, float iou, int min_area, lp_det* dets,
+                               int* counts, bool with_rois, Profiler* prof) {
+  enqueue_view_gather(src, h->d_geom.as<ImgGeom>(), h->d_vwin.as<ViewWin>(), h->d_lb.as<uint8_t>(), lay, h->cfg.det_input, h->stream, prof);
+  enqueue_view_detect(h, lay, F, conf, iou, min_area, dets, counts, with_rois, prof);
+}
+
+// ---- the two fronts ------------------------------------------------------------------------------------------------------------
+// What an entry point brings along: its frames' geometry -> the call's layout (its own argument checks included).  Everything
+// is validated in one order: the shared arguments, the layout against every frame, the NV12 format; only then is anything
+// uploaded or allocated.
+using LayoutFn = std::function<ViewLayout(const std::vector<ImgGeom>&)>;
+
+// the staged host call of lp_run_tiled and lp_run_views
+static void run_views_host(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, float conf, float iou, int min_area,
+                           lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing, GraphKind front_kind,
+                           GraphKind roi_kind, GraphKind cls_kind, const LayoutFn& layout_of) {
+  check_run_args(h, imgs && hs && ws && dets && counts, B, true, min_area);
+  for (int i = 0; i < B; ++i) LP_CHECK(hs[i] > 0 && ws[i] > 0, LP_ERR_ARG, "frame %d is empty", i);
+  LP_HIP(hipSetDevice(h->cfg.device));
+  std::vector<ImgGeom> fg(B);
+  for (int i = 0; i < B; ++i) fg[i] = make_geom(hs[i], ws[i], h->cfg.det_input, 0);
+  // The layout is built twice, here and behind the upload: this one validates the call before anything is uploaded, from
+  // geometry without the frames' offsets in d_src, which upload_images assigns.
+  (void)layout_of(fg);
+  const bool nv = h->nv12();
+  if (nv) {   // host frames: frame_stride does not apply
+    lp_frame_format hf = h->fmt;
+    hf.frame_stride = 0;
+    for (int i = 0; i < B; ++i) (void)frame_layout(hf, hs[i], ws[i]);
+  }
+  CscPlan csc;
+  fg = upload_images(h, imgs, hs, ws, B, &csc);
+  const ViewLayout lay = layout_of(fg);
+  upload_tiles(h, fg, lay);
+  run_host_pass(h, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, csc, front_kind, roi_kind, cls_kind,
+                [&](Profiler* prof) {
+                  if (nv) enqueue_csc(h, h->d_raw.as<uint8_t>(), csc, prof);
+                  enqueue_view_front(h, h->d_src.as<uint8_t>(), lay, B, conf, iou, min_area, h->d_dets.as<lp_det>(), h->d_counts.as<int>(), true,
+                                     prof);
+                }, h->d_fgeom.as<ImgGeom>());
+}
+
+// the device call of lp_run_tiled_device and lp_run_views_device
+static void run_views_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, float conf, float iou, int min_area, void* dev_dets,
+                             void* dev_counts, GraphKind kind, const LayoutFn& layout_of) {
+  check_run_args(h, dev_imgs && dev_dets && dev_counts, B, false, min_area);
+  LP_CHECK(H > 0 && W > 0, LP_ERR_ARG, "frames of %dx%d", W, H);
+  LP_HIP(hipSetDevice(h->cfg.device));
+  std::vector<ImgGeom> fg(B);
+  for (int i = 0; i < B; ++i) fg[i] = make_geom(H, W, h->cfg.det_input, (long)i * H * W * 3);
+  ViewLayout lay = layout_of(fg);
+  const bool nv = h->nv12();
+  CscPlan csc;
+  if (nv) {   // device_csc checks the format before it sizes d_src; the converted frames sit at 16-byte aligned offsets
+    csc = device_csc(h, dev_imgs, B, H, W, fg);
+    lay = layout_of(fg);
+  }
+  upload_tiles(h, fg, lay);
+  Profiler* prof = begin_profile(h);
+  const uint8_t* src = nv ? h->d_src.as<uint8_t>() : static_cast<const uint8_t*>(dev_imgs);
+  const bool classify = h->cls && h->cls->loaded();
+  GraphKey key{kind, B, h->geom_ver, min_area, dev_imgs, dev_dets, dev_counts, conf, iou};
+  key_format(h, csc, key);
+  run_or_capture(h, key, prof == nullptr, [&]() {
+    if (nv) enqueue_csc(h, static_cast<const uint8_t*>(dev_imgs), csc, prof);
+    enqueue_view_front(h, src, lay, B, conf, iou, classify ? min_area : -1, static_cast<lp_det*>(dev_dets), static_cast<int*>(dev_counts),
+                       classify, prof);
+    if (classify) enqueue_classify(h, src, B, static_cast<lp_det*>(dev_dets), nullptr, nullptr, nullptr, prof, 0, h->d_fgeom.as<ImgGeom>());
+  });
+  if (prof) prof->enabled = false;  // records are collected by lp_profile_read after the caller synchronises
 }
 
 }  // namespace lp
@@ -107,25 +290,21 @@ using namespace lp;
 
 extern "C" {
 
+int lp_tile_grid(int det_input, const lp_tiling* tiling, int H, int W, int* n_views, int* views, int cap) {
+  LP_API_BEGIN
+  LP_CHECK(n_views && det_input >= 1 && H > 0 && W > 0, LP_ERR_ARG, "bad argument (det_input %d, frame %dx%d)", det_input, H, W);
+  check_tiling(tiling, det_input);
+  write_views(grid_views(H, W, det_input, tiling->overlap, tiling->full_frame, false), n_views, views, cap);
+  LP_API_END
+}
+
 int lp_view_grid(int tile, int overlap, int full_frame, int H, int W, int* n_views, int* views, int cap) {
   LP_API_BEGIN
   LP_CHECK(n_views && H > 0 && W > 0, LP_ERR_ARG, "bad argument (frame %dx%d)", H, W);
   LP_CHECK(tile >= 16 && overlap >= 0 && overlap < tile, LP_ERR_ARG, "view grid needs tile >= 16 and 0 <= overlap < tile (tile %d, overlap %d)",
            tile, overlap);
   LP_CHECK(full_frame == 0 || full_frame == 1, LP_ERR_ARG, "full_frame must be 0 or 1 (got %d)", full_frame);
-  std::vector<int> xs, ys;
-  const int sw = view_axis(W, tile, overlap, xs), sh = view_axis(H, tile, overlap, ys);
-  std::vector<std::array<int, 4>> v;
-  if (xs.size() * ys.size() == 1 || full_frame) v.push_back({-1, -1, W, H});
-  if (xs.size() * ys.size() > 1)
-    for (int y : ys)
-      for (int x : xs) v.push_back({x, y, sw, sh});
-  *n_views = (int)v.size();
-  if (views) {
-    LP_CHECK(cap >= (int)v.size(), LP_ERR_ARG, "%zu views, room for %d", v.size(), cap);
-    for (size_t i = 0; i < v.size(); ++i)
-      for (int k = 0; k < 4; ++k) views[4 * i + k] = v[i][k];
-  }
+  write_views(grid_views(H, W, tile, overlap, full_frame, true), n_views, views, cap);
   LP_API_END
 }
 
@@ -145,100 +324,40 @@ int lp_view_geometry(int det_input, int H, int W, const int* view, float* ratio,
   LP_API_END
 }
 
+int lp_run_tiled(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, const lp_tiling* tiling, float conf,
+                 float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing) {
+  LP_API_BEGIN
+  run_views_host(h, imgs, hs, ws, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, GK_TILED_FRONT, GK_TILED_ROI,
+                 GK_TILED_CLS, [&](const std::vector<ImgGeom>& fg) {
+                   check_tiling(tiling, h->cfg.det_input);
+                   return view_layout(h, fg, tiled_views(h->cfg.det_input, *tiling, fg));
+                 });
+  LP_API_END
+}
+
+int lp_run_tiled_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, const lp_tiling* tiling, float conf, float iou,
+                        int min_area, void* dev_dets, void* dev_counts) {
+  LP_API_BEGIN
+  run_views_device(h, dev_imgs, B, H, W, conf, iou, min_area, dev_dets, dev_counts, GK_TILED_DEVICE, [&](const std::vector<ImgGeom>& fg) {
+    check_tiling(tiling, h->cfg.det_input);
+    return view_layout(h, fg, tiled_views(h->cfg.det_input, *tiling, fg));
+  });
+  LP_API_END
+}
+
 int lp_run_views(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, const int* views, int n_views, float conf,
                  float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing) {
   LP_API_BEGIN
-  LP_CHECK(h && imgs && hs && ws && dets && counts, LP_ERR_ARG, "null argument");
-  LP_CHECK(h->det && h->det->loaded(), LP_ERR_STATE, "detector not loaded");
-  LP_CHECK(h->cls && h->cls->loaded(), LP_ERR_STATE, "classifier not loaded");
-  LP_CHECK(B >= 1 && B <= h->cfg.max_batch, LP_ERR_ARG, "batch %d outside 1..%d", B, h->cfg.max_batch);
-  LP_CHECK(min_area >= 0, LP_ERR_ARG, "min_area must be >= 0");
-  for (int i = 0; i < B; ++i) LP_CHECK(hs[i] > 0 && ws[i] > 0, LP_ERR_ARG, "frame %d is empty", i);
-  LP_HIP(hipSetDevice(h->cfg.device));
-  std::vector<ImgGeom> fg(B);
-  for (int i = 0; i < B; ++i) fg[i] = make_geom(hs[i], ws[i], h->cfg.det_input, 0);
-  (void)view_layout(h, fg, views, n_views);   // the list checked against every frame before anything is uploaded
-  const bool nv = h->nv12();
-  if (nv) {   // and the format, likewise (host frames: frame_stride does not apply)
-    lp_frame_format hf = h->fmt;
-    hf.frame_stride = 0;
-    for (int i = 0; i < B; ++i) (void)frame_layout(hf, hs[i], ws[i]);
-  }
-  CscPlan csc;
-  fg = upload_images(h, imgs, hs, ws, B, &csc);
-  const ViewLayout vl = view_layout(h, fg, views, n_views);
-  upload_tiles(h, fg, vl.lay, &vl.wins);
-  run_host_pass(h, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, csc, GK_VIEWS_FRONT, GK_VIEWS_ROI, GK_VIEWS_CLS,
-                [&](Profiler* prof) {
-                  if (nv) enqueue_csc(h, h->d_raw.as<uint8_t>(), csc, prof);
-                  enqueue_view_gather(h->d_src.as<uint8_t>(), h->d_geom.as<ImgGeom>(), h->d_vwin.as<ViewWin>(), h->d_lb.as<uint8_t>(), vl,
-                                      h->cfg.det_input, h->stream, prof);
-                  enqueue_view_detect(h, vl.lay, B, conf, iou, min_area, h->d_dets.as<lp_det>(), h->d_counts.as<int>(), true, prof);
-                }, h->d_fgeom.as<ImgGeom>());
+  run_views_host(h, imgs, hs, ws, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, GK_VIEWS_FRONT, GK_VIEWS_ROI,
+                 GK_VIEWS_CLS, [&](const std::vector<ImgGeom>& fg) { return view_layout(h, fg, listed_views(h, views, n_views, fg)); });
   LP_API_END
 }
 
 int lp_run_views_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, const int* views, int n_views, float conf, float iou,
                         int min_area, void* dev_dets, void* dev_counts) {
   LP_API_BEGIN
-  LP_CHECK(h && dev_imgs && dev_dets && dev_counts, LP_ERR_ARG, "null argument");
-  LP_CHECK(h->det && h->det->loaded(), LP_ERR_STATE, "detector not loaded");
-  LP_CHECK(B >= 1 && B <= h->cfg.max_batch && H > 0 && W > 0, LP_ERR_ARG, "bad batch/shape");
-  LP_HIP(hipSetDevice(h->cfg.device));
-  std::vector<ImgGeom> fg(B);
-  const bool nv = h->nv12();
-  CscPlan csc;
-  for (int i = 0; i < B; ++i) fg[i] = make_geom(H, W, h->cfg.det_input, (long)i * H * W * 3);
-  (void)view_layout(h, fg, views, n_views);   // the list and the format checked before any buffer is sized
-  if (nv) {
-    (void)frame_layout(h->fmt, H, W);
-    csc = device_csc(h, dev_imgs, B, H, W, fg);
-  }
-  const ViewLayout vl = view_layout(h, fg, views, n_views);
-  upload_tiles(h, fg, vl.lay, &vl.wins);
-  Profiler* prof = begin_profile(h);
-  const uint8_t* src = nv ? h->d_src.as<uint8_t>() : static_cast<const uint8_t*>(dev_imgs);
-  const bool classify = h->cls && h->cls->loaded();
-  GraphKey key{GK_VIEWS_DEVICE, B, h->geom_ver, min_area, dev_imgs, dev_dets, dev_counts, conf, iou};
-  key_format(h, csc, key);
-  run_or_capture(h, key, prof == nullptr, [&]() {
-    if (nv) enqueue_csc(h, static_cast<const uint8_t*>(dev_imgs), csc, prof);
-    enqueue_view_gather(src, h->d_geom.as<ImgGeom>(), h->d_vwin.as<ViewWin>(), h->d_lb.as<uint8_t>(), vl, h->cfg.det_input, h->stream, prof);
-    enqueue_view_detect(h, vl.lay, B, conf, iou, classify ? min_area : -1, static_cast<lp_det*>(dev_dets), static_cast<int*>(dev_counts),
-                        classify, prof);
-    if (classify) enqueue_classify(h, src, B, static_cast<lp_det*>(dev_dets), nullptr, nullptr, nullptr, prof, 0, h->d_fgeom.as<ImgGeom>());
-  });
-  if (prof) prof->enabled = false;  // records are collected by lp_profile_read after the caller synchronises
-  LP_API_END
-}
-
-int lp_test_view_windows(lp_handle* h, const uint8_t* img, int H, int W, const int* views, int n_views, int byte_offset, uint8_t* out,
-                         int cap) {
-  LP_API_BEGIN
-  LP_CHECK(h && img && out && H > 0 && W > 0 && byte_offset >= 0 && byte_offset < 64, LP_ERR_ARG, "bad argument");
-  LP_HIP(hipSetDevice(h->cfg.device));
-  const int S = h->cfg.det_input;
-  const size_t bytes = (size_t)H * W * 3;
-  std::vector<ImgGeom> fg(1, make_geom(H, W, S, byte_offset));
-  const ViewLayout vl = view_layout(h, fg, views, n_views);
-  const TileLayout& lay = vl.lay;
-  LP_CHECK(cap >= lay.V, LP_ERR_ARG, "%d views, room for %d", lay.V, cap);
-  // the frame is the whole allocation but for the offset in front: nothing the gather may read lies beyond it
-  DevBuf d_src, d_geom, d_wins, d_out;
-  d_src.alloc(bytes + byte_offset);
-  LP_HIP(hipMemcpy(d_src.as<uint8_t>() + byte_offset, img, bytes, hipMemcpyHostToDevice));
-  d_geom.alloc((size_t)lay.V * sizeof(ImgGeom));
-  LP_HIP(hipMemcpy(d_geom.p, lay.vgeom.data(), (size_t)lay.V * sizeof(ImgGeom), hipMemcpyHostToDevice));
-  if (!vl.wins.empty()) {
-    d_wins.alloc(vl.wins.size() * sizeof(ViewWin));
-    LP_HIP(hipMemcpy(d_wins.p, vl.wins.data(), vl.wins.size() * sizeof(ViewWin), hipMemcpyHostToDevice));
-  }
-  d_out.alloc((size_t)lay.V * S * S * 3);
-  enqueue_view_gather(d_src.as<uint8_t>(), d_geom.as<ImgGeom>(), d_wins.as<ViewWin>(), d_out.as<uint8_t>(), vl, S, h->stream, nullptr);
-  LP_HIP(hipStreamSynchronize(h->stream));
-  const size_t vb = (size_t)S * S * 3;
-  for (int k = 0; k < lay.V; ++k)   // in the list's order
-    LP_HIP(hipMemcpy(out + (size_t)k * vb, d_out.as<uint8_t>() + (size_t)lay.vslot[k] * vb, vb, hipMemcpyDeviceToHost));
+  run_views_device(h, dev_imgs, B, H, W, conf, iou, min_area, dev_dets, dev_counts, GK_VIEWS_DEVICE,
+                   [&](const std::vector<ImgGeom>& fg) { return view_layout(h, fg, listed_views(h, views, n_views, fg)); });
   LP_API_END
 }
 

@@ -280,17 +280,22 @@ class Engine:
         check(self.lib, self.lib.lp_detect(self._h, ptrs, hs, ws, B, conf, iou, dets.ctypes.data, counts))
         return dets, np.array(counts[:], dtype=np.int64)
 
-    def run_batch(self, images: Sequence[np.ndarray], conf: float, iou: float, min_area: int):
+    def _run_staged(self, fn, images: Sequence[np.ndarray], extra: tuple, conf: float, iou: float, min_area: int):
+        """One staged host call (lp_run_batch, lp_run_tiled, lp_run_views; `extra`: the arguments between B and conf):
+        (records [B, max_det], counts, num_det, timing), and last_det_conf_avg."""
         imgs, ptrs, hs, ws = self._img_args(images, frames=True)
         B = len(imgs)
         dets = np.zeros((B, self.cfg.max_det), dtype=DET_DTYPE)
         counts, num_det = (C.c_int * B)(), (C.c_int * B)()
         conf_avg = (C.c_float * B)()
         timing = LpTiming()
-        check(self.lib, self.lib.lp_run_batch(self._h, ptrs, hs, ws, B, conf, iou, int(min_area), dets.ctypes.data, counts,
-                                              num_det, conf_avg, C.byref(timing)))
+        check(self.lib, fn(self._h, ptrs, hs, ws, B, *extra, conf, iou, int(min_area), dets.ctypes.data, counts, num_det, conf_avg,
+                           C.byref(timing)))
         self.last_det_conf_avg = np.array(conf_avg[:], dtype=np.float32)
         return dets, np.array(counts[:], dtype=np.int64), np.array(num_det[:], dtype=np.int64), timing
+
+    def run_batch(self, images: Sequence[np.ndarray], conf: float, iou: float, min_area: int):
+        return self._run_staged(self.lib.lp_run_batch, images, (), conf, iou, min_area)
 
     def run_batch_device(self, dev_imgs: int, B: int, H: int, W: int, conf: float, iou: float, min_area: int,
                          dev_dets: int, dev_counts: int) -> None:
@@ -304,17 +309,8 @@ class Engine:
     def run_tiled(self, images: Sequence[np.ndarray], conf: float, iou: float, min_area: int, overlap: int = 128,
                   full_frame: bool = True):
         """run_batch with every frame seen through its views (lp_run_tiled): same return values, per frame."""
-        imgs, ptrs, hs, ws = self._img_args(images, frames=True)
-        B = len(imgs)
-        dets = np.zeros((B, self.cfg.max_det), dtype=DET_DTYPE)
-        counts, num_det = (C.c_int * B)(), (C.c_int * B)()
-        conf_avg = (C.c_float * B)()
-        timing = LpTiming()
         t = _tiling(overlap, full_frame)
-        check(self.lib, self.lib.lp_run_tiled(self._h, ptrs, hs, ws, B, C.byref(t), conf, iou, int(min_area), dets.ctypes.data, counts,
-                                              num_det, conf_avg, C.byref(timing)))
-        self.last_det_conf_avg = np.array(conf_avg[:], dtype=np.float32)
-        return dets, np.array(counts[:], dtype=np.int64), np.array(num_det[:], dtype=np.int64), timing
+        return self._run_staged(self.lib.lp_run_tiled, images, (C.byref(t),), conf, iou, min_area)
 
     def run_tiled_device(self, dev_imgs: int, B: int, H: int, W: int, conf: float, iou: float, min_area: int,
                          dev_dets: int, dev_counts: int, overlap: int = 128, full_frame: bool = True) -> None:
@@ -332,17 +328,8 @@ class Engine:
     def run_views(self, images: Sequence[np.ndarray], views, conf: float, iou: float, min_area: int):
         """run_batch with every frame seen through the views (lp_run_views; (x, y, w, h) windows or "full"): same return
         values, per frame."""
-        imgs, ptrs, hs, ws = self._img_args(images, frames=True)
-        B = len(imgs)
         v = _view_array(views)
-        dets = np.zeros((B, self.cfg.max_det), dtype=DET_DTYPE)
-        counts, num_det = (C.c_int * B)(), (C.c_int * B)()
-        conf_avg = (C.c_float * B)()
-        timing = LpTiming()
-        check(self.lib, self.lib.lp_run_views(self._h, ptrs, hs, ws, B, _ip(v), len(v), conf, iou, int(min_area), dets.ctypes.data, counts,
-                                              num_det, conf_avg, C.byref(timing)))
-        self.last_det_conf_avg = np.array(conf_avg[:], dtype=np.float32)
-        return dets, np.array(counts[:], dtype=np.int64), np.array(num_det[:], dtype=np.int64), timing
+        return self._run_staged(self.lib.lp_run_views, images, (_ip(v), len(v)), conf, iou, min_area)
 
     def run_views_device(self, dev_imgs: int, B: int, H: int, W: int, views, conf: float, iou: float, min_area: int,
                          dev_dets: int, dev_counts: int) -> None:
@@ -1047,29 +1034,33 @@ class HybridPipeline:
         self.engine.last_det_conf_avg = np.concatenate([p[4] for p in parts])
         return dets, counts, num_det, timing
 
-    def _run_tiled(self, images, conf, iou, min_area, feed=None):
-        """run_batch's engine call in tiled mode: consecutive frames go to one lp_run_tiled call while their views fit
-        max_batch and their ROIs fit max_rois (at most max_det per frame); results concatenated in frame order, stage times
-        summed over the calls.  feed(dets, counts, first_frame) is called behind every engine call."""
+    def _run_grouped(self, images, feed, verb, frame_views, call):
+        """run_batch's engine call in tiled mode and with scaled views.  frame_views(fh, fw) -> (key, n): the frame's n views
+        and what the engine call needs to know of them.  Consecutive frames go to one call(frames, key) while they share the
+        key, the sum of their views fits max_batch and their ROIs fit max_rois (at most max_det per frame).  Tiled frames all
+        share one key, so only the sum counts; frames under scaled views share a key when they share the view list, and
+        then the sum is frames x views.  Results concatenated in frame order, stage times summed over the calls.
+        feed(dets, counts, first_frame) is called behind every engine call."""
         cfg = self.engine.cfg
-        S, cap = cfg.det_input, cfg.max_batch
+        cap = cfg.max_batch
         max_frames = max(1, (cfg.max_rois if cfg.max_rois > 0 else cfg.max_batch * cfg.max_det) // cfg.max_det)
-        groups, cur, used = [], [], 0
+        groups, cur, cur_key, used = [], [], None, 0
         for img in images:
             fh, fw = self.engine.frame_hw(img)
-            nv = len(tile_grid(S, fh, fw, self.tile_overlap, self.tile_full_frame))
-            if nv > cap:
-                raise ValueError(f"a {fw}x{fh} frame needs {nv} views, more than max_batch = {cap}")
-            if cur and (used + nv > cap or len(cur) >= max_frames):
-                groups.append(cur)
+            key, n = frame_views(fh, fw)
+            if n > cap:
+                raise ValueError(f"a {fw}x{fh} frame {verb} {n} views, more than max_batch = {cap}")
+            if cur and (key != cur_key or used + n > cap or len(cur) >= max_frames):
+                groups.append((cur, cur_key))
                 cur, used = [], 0
             cur.append(img)
-            used += nv
+            cur_key = key
+            used += n
         if cur:
-            groups.append(cur)
+            groups.append((cur, cur_key))
         parts, done = [], 0
-        for g in groups:
-            d, c, nd, t = self.engine.run_tiled(g, conf, iou, min_area, self.tile_overlap, self.tile_full_frame)
+        for g, key in groups:
+            d, c, nd, t = call(g, key)
             parts.append((d, c, nd, t, self.engine.last_det_conf_avg))
             if feed is not None:
                 feed(d[:len(g)], c[:len(g)], done)
@@ -1081,39 +1072,18 @@ class HybridPipeline:
         return (np.concatenate([p[0] for p in parts], 0), np.concatenate([p[1] for p in parts]),
                 np.concatenate([p[2] for p in parts]), timing)
 
+    def _run_tiled(self, images, conf, iou, min_area, feed=None):
+        """lp_run_tiled calls of consecutive frames whose views fit max_batch"""
+        S, ov, full = self.engine.cfg.det_input, self.tile_overlap, self.tile_full_frame
+        return self._run_grouped(images, feed, "needs", lambda fh, fw: (None, len(tile_grid(S, fh, fw, ov, full))),
+                                 lambda g, _: self.engine.run_tiled(g, conf, iou, min_area, ov, full))
+
     def _run_views(self, images, conf, iou, min_area, feed=None):
-        """run_batch's engine call with scaled views: consecutive frames that share a view list (view_tile: the grid of their
-        size) go to one lp_run_views call while frames x views fit max_batch and the ROIs fit max_rois; results concatenated
-        in frame order, stage times summed over the calls.  feed(dets, counts, first_frame) is called behind every engine call."""
-        cfg = self.engine.cfg
-        cap = cfg.max_batch
-        max_frames = max(1, (cfg.max_rois if cfg.max_rois > 0 else cfg.max_batch * cfg.max_det) // cfg.max_det)
-        groups, cur, cur_views = [], [], None
-        for img in images:
-            fh, fw = self.engine.frame_hw(img)
+        """lp_run_views calls of consecutive frames that share a view list (view_tile: the grid of their size) and fit max_batch"""
+        def frame_views(fh, fw):
             vs = self.views if self.views is not None else view_grid(self.view_tile, fh, fw, self.view_overlap, self.view_full_frame)
-            if len(vs) > cap:
-                raise ValueError(f"a {fw}x{fh} frame has {len(vs)} views, more than max_batch = {cap}")
-            if cur and (vs != cur_views or (len(cur) + 1) * len(vs) > cap or len(cur) >= max_frames):
-                groups.append((cur, cur_views))
-                cur = []
-            cur.append(img)
-            cur_views = vs
-        if cur:
-            groups.append((cur, cur_views))
-        parts, done = [], 0
-        for g, vs in groups:
-            d, c, nd, t = self.engine.run_views(g, vs, conf, iou, min_area)
-            parts.append((d, c, nd, t, self.engine.last_det_conf_avg))
-            if feed is not None:
-                feed(d[:len(g)], c[:len(g)], done)
-            done += len(g)
-        timing = LpTiming()
-        for f in ("t_detection", "t_roi_extract", "t_classification", "t_total"):
-            setattr(timing, f, sum(getattr(p[3], f) for p in parts))
-        self.engine.last_det_conf_avg = np.concatenate([p[4] for p in parts])
-        return (np.concatenate([p[0] for p in parts], 0), np.concatenate([p[1] for p in parts]),
-                np.concatenate([p[2] for p in parts]), timing)
+            return vs, len(vs)
+        return self._run_grouped(images, feed, "has", frame_views, lambda g, vs: self.engine.run_views(g, vs, conf, iou, min_area))
 
     def _track(self, dets, counts, stream_ids):
         """the call's records through the engine's tracker, at most max_batch frames per lp_track call, in frame order"""
