@@ -274,7 +274,7 @@ typedef struct lp_frame_format {
  * (0 for BGR8) and *frame_bytes, the bytes of one frame (H * W * 3 for BGR8); either may be NULL */
 int lp_frame_layout(const lp_frame_format* fmt, int H, int W, int64_t* uv_offset, int64_t* frame_bytes);
 /* the format of the frames given to the NEXT calls of lp_detect, lp_run_batch, lp_run_batch_device, lp_run_tiled,
- * lp_run_tiled_device, lp_run_views and lp_run_views_device; NULL = packed BGR (the default).  Copied; like lp_set_stream it is handle state.  Host frames in NV12
+ * lp_run_tiled_device, lp_run_views, lp_run_views_device, lp_run_focus and lp_run_focus_device; NULL = packed BGR (the default).  Copied; like lp_set_stream it is handle state.  Host frames in NV12
  * are frame_bytes each (frame_stride is ignored for them). */
 int lp_set_input_format(lp_handle* h, const lp_frame_format* fmt);
 /* the converter alone (tests): B host frames of one size (contiguous, frame_stride apart), uploaded byte_offset (0..63)
@@ -431,8 +431,8 @@ int lp_inventory_destroy(lp_handle* h);
 /* dev_dets, dev_counts, dev_tracks, B and stream_ids exactly as the preceding lp_track_device took and wrote them.
  * Asynchronous on the handle's stream, ordered behind that call with no event; any number of calls may be enqueued without a
  * synchronise.  crops = 1 asserts that frames 0..B-1 of this call are frames 0..B-1 of the last pipeline call on this handle
- * (lp_run_batch, lp_run_batch_device, lp_run_tiled, lp_run_tiled_device, lp_run_views, lp_run_views_device; the tiled
- * and the views ones index frames, not views), whose ROI
+ * (lp_run_batch, lp_run_batch_device, lp_run_tiled, lp_run_tiled_device, lp_run_views, lp_run_views_device, lp_run_focus,
+ * lp_run_focus_device; the tiled, the views and the focus ones index frames, not views), whose ROI
  * list and classifier input crops the handle still holds: record (b, slot) has a crop iff the ROI list names it among its
  * first `total` entries.  crops = 0 attaches no crops.  LP_ERR_STATE without a tracker or an inventory; LP_ERR_ARG for B
  * outside 1..max_batch, a stream id out of range, crops outside 0/1, crops = 1 with keep_crops = 0, or record buffers that
@@ -458,6 +458,70 @@ int lp_inventory_open(lp_handle* h, int stream, lp_sign* out, int cap, int* n);
  * them / download the last call's (crops, img, slot may be NULL; cap < *n is LP_ERR_ARG when any is given) */
 int lp_test_set_rois(lp_handle* h, const uint8_t* crops, const int* img, const int* slot, int R);
 int lp_debug_rois(lp_handle* h, uint8_t* crops, int* img, int* slot, int cap, int* n);
+
+/* ---- focus views: tracker-chosen windows and a sweep in the detector batch (additive to ABI 310) ---- */
+/* A focus plan connects the tracker to the scaled views: per frame the whole-frame view plus `slots` windows, chosen ON THE
+ * DEVICE from the tracker's state as the last enqueued lp_track_device left it -- native-resolution windows where the small
+ * tracked signs will be, the left-over slots swept over a window grid so that new signs are still picked up.  The cost per
+ * frame is fixed at 1 + slots views and no call synchronises, so the captured step replays while the windows move.
+ * The plan belongs to the tracker, like the inventory: lp_tracker_create called again and lp_tracker_destroy destroy it;
+ * lp_tracker_reset leaves it alone.  Per stream it keeps two int32, zero at creation and never reset: a sweep `cursor` and an
+ * `unserved` counter.  The frames of a call are grouped by stream exactly as lp_track_device groups them.  The j-th frame
+ * (j = 0, 1, ..) of a stream within one call, of size H x W (H, W >= 16) and letterbox ratio rf (the float ratio of the
+ * whole-frame view, lp_view_geometry of {-1, ..}), goes through the steps below.  All box arithmetic is fp32, every operation
+ * rounded on its own, nothing contracted (tests/focus_ref.py restates the rule in NumPy):
+ *   1 ask    for every live slot dt = (float)(missed + 1 + j); p = box + vel * dt per coordinate (motion = 0: p = box);
+ *            x1 = max(p0, 0), y1 = max(p1, 0), x2 = min(p2, (float)W), y2 = min(p3, (float)H); bw = x2 - x1, bh = y2 - y1,
+ *            m = max(bw, bh).  The track asks iff bw > 0 && bh > 0 && m * rf < small_px; a track with a NaN in p never asks.
+ *            Askers are ordered by hits descending; ties: lower slot first.
+ *   2 place  askers are taken in that order against the windows already placed for this frame.  An asker is covered by a
+ *            placed {x, y, w, h} iff (x == 0 || x1 >= (float)(x + border)) && (x + w == W || x2 <= (float)(x + w - border))
+ *            and the same two conditions in y.  A covered asker is skipped; an uncovered asker with no slot left adds 1 to
+ *            `unserved`; otherwise side = clamp((int)ceilf(margin * m), side_min, side_max), w = min(side, W),
+ *            h = min(side, H), cx = (int)floorf((x1 + x2) * 0.5f), x = min(max(cx - w / 2, 0), W - w), y likewise, and
+ *            {x, y, w, h} is placed.
+ *   3 sweep  (sweep = 1) G = the windows of lp_view_grid(side_min, sweep_overlap, 0, H, W), row-major, n = |G|.  A frame
+ *            that fits one window has no sweep.  Otherwise r = min(free slots, n): the windows G[(cursor + i) % n],
+ *            i = 0 .. r-1, follow the placed ones, and cursor = (cursor + r) % n.
+ *   4 empty  the slots left over are empty: reported as {0, 0, 0, 0}, and they contribute no candidate to the frame NMS.
+ * The views of a frame are the whole frame (view 0), then the slots in order; each window is a scaled view with the geometry
+ * of lp_view_geometry, bit for bit, and everything behind the gather is tiled inference's.  DESIGN.md 6g. */
+typedef struct lp_focus_config {
+  int slots;          /* 1..16 window slots per frame, behind the whole-frame view */
+  int side_min;       /* 16 <= side_min <= side_max; 0 = det_input */
+  int side_max;       /* <= 8 * det_input (the window gather's LDS rows always fit); 0 = 2 * det_input */
+  float margin;       /* >= 1: a window's side is margin x the box's longer side (default 2) */
+  float small_px;     /* > 0: a track asks for a window while its longer side in the letterboxed whole frame is below this (default 32) */
+  int border;         /* >= 0: a box is covered by a window only `border` pixels inside it (default 16) */
+  int sweep;          /* 0/1: free slots walk the tile grid (default 1) */
+  int sweep_overlap;  /* 0 <= v < side_min (default 0) */
+  int reserved[8];    /* zero */
+} lp_focus_config;
+
+void lp_focus_default_config(lp_focus_config* cfg);
+/* pure host, no handle, no device: LP_ERR_ARG for a value outside the ranges above (the zeros resolved with det_input), a
+ * non-zero reserved word or NULL */
+int lp_focus_config_check(const lp_focus_config* cfg, int det_input);
+/* LP_ERR_STATE without a tracker; calling it again replaces the plan (cursor and unserved restart at zero) */
+int lp_focus_create(lp_handle* h, const lp_focus_config* cfg);
+int lp_focus_destroy(lp_handle* h);
+/* the plan alone, synchronous: B frames of heights[b] x widths[b] (B <= max_batch), stream_ids as lp_track_device takes them;
+ * views receives [B * slots * 4] host ints {x, y, w, h}; advance = 0 leaves cursor and unserved as they were */
+int lp_focus_plan(lp_handle* h, int B, const int* heights, const int* widths, const int* stream_ids, int* views, int advance);
+/* synchronises; the two counters of a stream (either may be NULL) */
+int lp_focus_state(lp_handle* h, int stream, int* cursor, int* unserved);
+/* lp_run_batch_device over B equally sized frames resident in HBM, each seen through its whole-frame view and the plan's
+ * windows for its stream; dev_views (may be NULL) receives [B * slots * 4] int32, the windows used.  stream_ids is a HOST
+ * array (NULL: stream 0), read before the call returns.  Asynchronous: the plan is ordered on the handle's stream behind the
+ * last lp_track_device, with no synchronise.  LP_ERR_STATE without a tracker or a plan.  LP_ERR_ARG, before anything is
+ * enqueued and with the handle still usable: B * (1 + slots) > max_batch, a stream id out of range, a frame below 16 pixels,
+ * the frame NMS capacity exceeded (see tiled inference). */
+int lp_run_focus_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, const int* stream_ids,
+                        float conf, float iou, int min_area, void* dev_dets, void* dev_counts, void* dev_views);
+/* the same over B host frames of individual sizes, as lp_run_views; views (may be NULL) is a host array [B * slots * 4] */
+int lp_run_focus(lp_handle* h, const uint8_t* const* imgs, const int* heights, const int* widths, int B, const int* stream_ids,
+                 float conf, float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg,
+                 lp_timing* timing, int* views);
 
 /* ---- classifier alone ------------------------------------------------------------ */
 /* replaces PyTorchClassifier.predict_batch (e2e.py:378-396) for R host BGR crops of

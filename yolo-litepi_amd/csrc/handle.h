@@ -1,4 +1,4 @@
-// Internal to the C-ABI translation units (api.cpp, pipeline.cpp, pixfmt.cpp, views.cpp, tracking.cpp, inventory.cpp,
+// Internal to the C-ABI translation units (api.cpp, pipeline.cpp, pixfmt.cpp, views.cpp, tracking.cpp, inventory.cpp, focus.cpp,
 // test_hooks.cpp): the handle behind include/litepi.h's lp_handle, the captured-step cache, and the pipeline pieces the entry points share.
 #pragma once
 #include <algorithm>
@@ -60,6 +60,28 @@ struct Inventory {
   }
 };
 
+// Focus plan of a tracker (lp_focus_*; include/litepi.h): the per-stream sweep cursor and unserved counter stay in HBM between
+// calls.  Its call plans (the tracker's jobs and frame lists, then every frame's height, width and letterbox ratio) go through
+// a pinned -> device ring of its own, like the inventory's.  blob / vgeom remember the placeholder layout whose device tables
+// the plan kernel rewrites in place (focus.cpp: resident()).
+struct FocusPlan {
+  static constexpr int RING = 8;
+  lp_focus_config cfg;   // the zeros resolved
+  DevBuf state, plan_dev, d_views, d_dead;
+  int* plan_host = nullptr;   // pinned, RING slots of slot_ints
+  size_t slot_ints = 0;
+  hipEvent_t ev[RING] = {};
+  bool busy[RING] = {};
+  int next = 0;
+  std::vector<char> blob;
+  std::vector<ImgGeom> vgeom;
+  ~FocusPlan() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (plan_host) (void)hipHostFree(plan_host);
+  }
+};
+
 // Sign tracker of a handle (lp_tracker_*, lp_track*; include/litepi.h): the track table, the stream heads and the vote accumulators
 // stay in HBM between calls.  A call's per-stream frame lists are written into a slot of a pinned ring and copied from there
 // into the same slot of a device ring on the handle's stream (a pageable source would synchronise it); a slot is re-used only
@@ -67,6 +89,7 @@ struct Inventory {
 struct Tracker {
   static constexpr int RING = 8;
   std::unique_ptr<Inventory> inv;   // null until lp_inventory_create: no other path looks at it
+  std::unique_ptr<FocusPlan> focus; // null until lp_focus_create: no other path looks at it
   lp_track_config cfg;
   int nc = 1, max_det = 0, max_batch = 0;
   DevBuf table, heads, acc, scratch, plan_dev;
@@ -95,6 +118,8 @@ enum GraphKind {
   GK_TILED_DEVICE,                                // lp_run_tiled_device
   GK_VIEWS_FRONT, GK_VIEWS_ROI, GK_VIEWS_CLS,     // lp_run_views: view gather + detect + frame NMS, ROI resize, classifier
   GK_VIEWS_DEVICE,                                // lp_run_views_device
+  GK_FOCUS_FRONT, GK_FOCUS_ROI, GK_FOCUS_CLS,     // lp_run_focus: view gather + detect + mask + frame NMS, ROI resize, classifier
+  GK_FOCUS_DEVICE,                                // lp_run_focus_device
 };
 struct GraphKey {
   GraphKind kind;
@@ -302,5 +327,9 @@ void upload_tiles(lp_handle* h, const std::vector<ImgGeom>& fg, const ViewLayout
 // [V,S,S,3]; what the layout does not contain is not launched
 void enqueue_view_gather(const uint8_t* src, const ImgGeom* d_geom, const ViewWin* d_wins, uint8_t* dst, const ViewLayout& lay, int S,
                          hipStream_t st, Profiler* prof);
+// view gather + detector on the views + frame NMS (+ the ROI list when with_rois); dead (focus views only): view slots whose
+// candidates are dropped between the detector and the view sort
+void enqueue_view_front(lp_handle* h, const uint8_t* src, const ViewLayout& lay, int F, float conf, float iou, int min_area, lp_det* dets,
+                        int* counts, bool with_rois, Profiler* prof, const int* dead = nullptr);
 
 }  // namespace lp

@@ -229,6 +229,32 @@ void launch_inventory(const InvArgs& a, int n_jobs, hipStream_t st);
 // closes every open entry of `n` streams from `first` on into the log (LP_SIGN_FLUSHED); jobs / frames / records are not read
 void launch_inventory_flush(const InvArgs& a, int first, int n, hipStream_t st);
 
+// ---- focus_kernels.hip (tracker-chosen windows + sweep, include/litepi.h lp_focus_*) ----------
+struct FocusState { int cursor, unserved; };   // per stream, device resident between calls
+struct FocusArgs {
+  const TrackJob* jobs;     // [n_jobs] the tracker's call plan
+  const int* frames;        // batch indices of the call's frames, grouped by job
+  const int* fh;            // [B] frame heights, by batch index
+  const int* fw;            // [B] frame widths
+  const float* frf;         // [B] letterbox ratio of the whole frame (make_geom's float)
+  const TrackSlot* table;   // [n_streams][T]
+  FocusState* state;        // [n_streams]
+  int* views;               // [B][slots][4] or null
+  // the call's view tables (null for the plan alone): window slot k of frame b is ViewWin b * slots + k and view slot
+  // B + b * slots + k of geom / dead; the whole-frame views are slots 0 .. B-1
+  const ImgGeom* fgeom;     // [B] frame geometry (src_off)
+  ViewWin* vwin;
+  ImgGeom* geom;
+  int* dead;                // [V] 1: the view slot is empty, its candidates do not count
+  int B, T, S, motion, advance;
+  int slots, side_min, side_max, border, sweep, sweep_overlap;
+  float margin, small_px;
+};
+// one workgroup per job
+void launch_focus_plan(const FocusArgs& a, int n_jobs, hipStream_t st);
+// cand_count[v] = 0 for every view slot v < V with dead[v] (between the detector and the view sort)
+void launch_focus_mask(const int* dead, int* cand_count, int V, hipStream_t st);
+
 // ---- cls_kernels.hip ------------------------------------------------------------------
 // conv1 3x3/s2 (3->CO) + folded BN + ReLU on (x/255 - mean)/std of the uint8 RGB crops
 void launch_cls_stem(int prec, const uint8_t* rgb, const float* w /*[27][CO]*/, const float* bias, int CO,

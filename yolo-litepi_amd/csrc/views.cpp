@@ -190,9 +190,14 @@ void enqueue_view_gather(const uint8_t* src, const ImgGeom* d_geom, const ViewWi
 
 // the detector on the gathered views + view sort + frame NMS (+ the ROI list when with_rois)
 static void enqueue_view_detect(lp_handle* h, const ViewLayout& lay, int F, float conf, float iou, int min_area, lp_det* dets, int* counts,
-                                bool with_rois, Profiler* prof) {
+                                bool with_rois, Profiler* prof, const int* dead) {
   h->det->forward(h->d_lb.as<uint8_t>(), lay.V, h->d_geom.as<ImgGeom>(), conf, nullptr, h->d_cand.as<Cand>(), h->d_cand_count.as<int>(),
                   h->stream, prof);
+  if (dead) {   // focus views: an empty slot's view is all bars; whatever the detector made of it does not count
+    if (prof) prof->begin(h->stream);
+    launch_focus_mask(dead, h->d_cand_count.as<int>(), lay.V, h->stream);
+    if (prof) prof->end(h->stream, "focus_mask", "nms", 0.0, 0.0);
+  }
   FrameNmsArgs a;
   memset(&a, 0, sizeof(a));
   a.cand = h->d_cand.as<Cand>(); a.cand_count = h->d_cand_count.as<int>(); a.vcnt = h->d_vcnt.as<int>(); a.sorted = h->d_sorted.as<Cand>();
@@ -212,10 +217,10 @@ static void enqueue_view_detect(lp_handle* h, const ViewLayout& lay, int F, floa
 }
 
 // view gather + detector on the views + frame NMS (+ the ROI list when with_rois)
-static void enqueue_view_front(lp_handle* h, const uint8_t* src, const ViewLayout& lay, int F, float conf, float iou, int min_area, lp_det* dets,
-                               int* counts, bool with_rois, Profiler* prof) {
+void enqueue_view_front(lp_handle* h, const uint8_t* src, const ViewLayout& lay, int F, float conf, float iou, int min_area, lp_det* dets,
+                        int* counts, bool with_rois, Profiler* prof, const int* dead) {
   enqueue_view_gather(src, h->d_geom.as<ImgGeom>(), h->d_vwin.as<ViewWin>(), h->d_lb.as<uint8_t>(), lay, h->cfg.det_input, h->stream, prof);
-  enqueue_view_detect(h, lay, F, conf, iou, min_area, dets, counts, with_rois, prof);
+  enqueue_view_detect(h, lay, F, conf, iou, min_area, dets, counts, with_rois, prof, dead);
 }
 
 // ---- the two fronts ------------------------------------------------------------------------------------------------------------

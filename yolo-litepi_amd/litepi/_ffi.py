@@ -81,6 +81,11 @@ class LpSign(C.Structure):
                 ("det_class", C.c_int32), ("flags", C.c_int32)]
 
 
+class LpFocusConfig(C.Structure):
+    _fields_ = [("slots", C.c_int), ("side_min", C.c_int), ("side_max", C.c_int), ("margin", C.c_float), ("small_px", C.c_float),
+                ("border", C.c_int), ("sweep", C.c_int), ("sweep_overlap", C.c_int), ("reserved", C.c_int * 8)]
+
+
 LP_BEST_AREA, LP_BEST_DET_CONF, LP_BEST_CLS_CONF = 0, 1, 2
 LP_SIGN_HAS_CROP, LP_SIGN_FLUSHED = 1, 2
 # numpy view of lp_sign records
@@ -111,6 +116,8 @@ SYMBOLS = [
     "lp_track_device", "lp_track", "lp_tracker_snapshot",
     "lp_inventory_default_config", "lp_inventory_config_check", "lp_inventory_create", "lp_inventory_destroy", "lp_inventory_device",
     "lp_inventory", "lp_inventory_flush", "lp_inventory_drain", "lp_inventory_open", "lp_test_set_rois", "lp_debug_rois",
+    "lp_focus_default_config", "lp_focus_config_check", "lp_focus_create", "lp_focus_destroy", "lp_focus_plan", "lp_focus_state",
+    "lp_run_focus_device", "lp_run_focus",
 ]
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
 
@@ -200,8 +207,19 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_inventory_open.argtypes = [vp, C.c_int, vp, C.c_int, ip]
     lib.lp_test_set_rois.argtypes = [vp, vp, ip, ip, C.c_int]
     lib.lp_debug_rois.argtypes = [vp, vp, ip, ip, C.c_int, ip]
+    fcp = C.POINTER(LpFocusConfig)
+    lib.lp_focus_default_config.argtypes = [fcp]
+    lib.lp_focus_default_config.restype = None
+    lib.lp_focus_config_check.argtypes = [fcp, C.c_int]
+    lib.lp_focus_create.argtypes = [vp, fcp]
+    lib.lp_focus_destroy.argtypes = [vp]
+    lib.lp_focus_plan.argtypes = [vp, C.c_int, ip, ip, ip, ip, C.c_int]
+    lib.lp_focus_state.argtypes = [vp, C.c_int, ip, ip]
+    lib.lp_run_focus_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, C.c_float, C.c_float, C.c_int, vp, vp, vp]
+    lib.lp_run_focus.argtypes = [vp, u8pp, ip, ip, C.c_int, ip, C.c_float, C.c_float, C.c_int, vp, ip, ip, fp, C.POINTER(LpTiming), ip]
     for s in SYMBOLS:
-        if s not in ("lp_last_error", "lp_default_config", "lp_destroy", "lp_track_default_config", "lp_inventory_default_config"):
+        if s not in ("lp_last_error", "lp_default_config", "lp_destroy", "lp_track_default_config", "lp_inventory_default_config",
+                     "lp_focus_default_config"):
             getattr(lib, s).restype = C.c_int
     got = lib.lp_version()
     if got != ABI_VERSION:

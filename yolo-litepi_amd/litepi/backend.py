@@ -163,6 +163,27 @@ def inventory_config_check(cfg: Optional[LpInventoryConfig]) -> int:
     return lib.lp_inventory_config_check(C.byref(cfg) if cfg is not None else None)
 
 
+FOCUS_CONFIG_FIELDS = ("slots", "side_min", "side_max", "margin", "small_px", "border", "sweep", "sweep_overlap")
+
+
+def focus_config(**cfg) -> _ffi.LpFocusConfig:
+    """lp_focus_config with the library's defaults (lp_focus_default_config) and the given fields (host only, no GPU needed)."""
+    lib = _ffi.load_library()
+    c = _ffi.LpFocusConfig()
+    lib.lp_focus_default_config(C.byref(c))
+    for k, v in cfg.items():
+        if k not in FOCUS_CONFIG_FIELDS:
+            raise TypeError(f"unknown focus setting {k!r} (one of {FOCUS_CONFIG_FIELDS})")
+        setattr(c, k, float(v) if k in ("margin", "small_px") else int(v))
+    return c
+
+
+def focus_config_check(cfg: Optional[_ffi.LpFocusConfig], det_input: int) -> int:
+    """lp_focus_config_check's status for a configuration (host only, no GPU needed)."""
+    lib = _ffi.load_library()
+    return lib.lp_focus_config_check(C.byref(cfg) if cfg is not None else None, int(det_input))
+
+
 class Engine:
     """One GPU pipeline handle (not thread-safe; one per GPU)."""
 
@@ -345,12 +366,14 @@ class Engine:
         check(self.lib, self.lib.lp_tracker_create(self._h, C.byref(c)))
         self.track_cfg = c
         self.__dict__.pop("inv_cfg", None)   # the inventory belongs to the tracker it was created on
+        self.__dict__.pop("focus_cfg", None)   # and so does the focus plan
 
     def tracker_destroy(self) -> None:
         check(self.lib, self.lib.lp_tracker_destroy(self._h))
         if hasattr(self, "track_cfg"):
             del self.track_cfg
         self.__dict__.pop("inv_cfg", None)
+        self.__dict__.pop("focus_cfg", None)
 
     def tracker_reset(self, stream: int = -1) -> None:
         """Frees the tracks of one stream (-1: all); ids keep counting.  Asynchronous on the engine's stream."""
@@ -396,6 +419,64 @@ class Engine:
         check(self.lib, self.lib.lp_tracker_snapshot(self._h, int(stream), st.ctypes.data, n.value, C.byref(n), acc.ctypes.data,
                                                      C.byref(nid), C.byref(ovf)))
         return {"tracks": st, "acc": acc, "next_id": nid.value, "overflow": ovf.value}
+
+    # ---- focus views: tracker-chosen windows and a sweep ---------------------------------------
+    def focus_create(self, **cfg) -> None:
+        """One focus plan per tracker (lp_focus_create); calling it again replaces it.  Settings are lp_focus_config's fields:
+        slots, side_min, side_max, margin, small_px, border, sweep, sweep_overlap."""
+        c = focus_config(**cfg)
+        check(self.lib, self.lib.lp_focus_create(self._h, C.byref(c)))
+        self.focus_cfg = c
+
+    def focus_destroy(self) -> None:
+        check(self.lib, self.lib.lp_focus_destroy(self._h))
+        self.__dict__.pop("focus_cfg", None)
+
+    def _focus_slots(self) -> int:
+        """the slot count of the plan (without one the library refuses the call: any size will do)"""
+        return int(self.focus_cfg.slots) if hasattr(self, "focus_cfg") else 16
+
+    def focus_plan(self, heights, widths, stream_ids=None, advance: bool = True) -> np.ndarray:
+        """lp_focus_plan: the windows the plan chooses now for B frames of heights[b] x widths[b] -> int32 [B, slots, 4]
+        {x, y, w, h}, empty slots all zero.  advance=False leaves the cursor and the unserved counter alone.  Synchronous."""
+        hs, ws = np.ascontiguousarray(heights, dtype=np.int32), np.ascontiguousarray(widths, dtype=np.int32)
+        B = hs.shape[0]
+        if hs.shape != (B,) or ws.shape != (B,):
+            raise ValueError(f"heights and widths must hold one size per frame, got shapes {hs.shape} and {ws.shape}")
+        ids = self._stream_ids(stream_ids, B)
+        out = np.zeros((B, self._focus_slots(), 4), np.int32)
+        ip = C.POINTER(C.c_int)
+        check(self.lib, self.lib.lp_focus_plan(self._h, B, hs.ctypes.data_as(ip), ws.ctypes.data_as(ip),
+                                               None if ids is None else ids.ctypes.data_as(ip), out.ctypes.data_as(ip), int(bool(advance))))
+        return out
+
+    def focus_state(self, stream: int = 0) -> Dict[str, int]:
+        """{"cursor", "unserved"} of a stream (synchronises)."""
+        c, u = C.c_int(), C.c_int()
+        check(self.lib, self.lib.lp_focus_state(self._h, int(stream), C.byref(c), C.byref(u)))
+        return {"cursor": c.value, "unserved": u.value}
+
+    def run_focus(self, images: Sequence[np.ndarray], conf: float, iou: float, min_area: int, stream_ids=None):
+        """run_batch with every frame seen through the whole frame and its plan's windows (lp_run_focus): run_batch's return
+        values per frame, then the windows used, int32 [B, slots, 4]."""
+        B = len(images)
+        ids = self._stream_ids(stream_ids, B)
+        views = np.zeros((B, self._focus_slots(), 4), np.int32)
+        ip = C.POINTER(C.c_int)
+
+        def fn(h, ptrs, hs, ws, n, *rest):
+            return self.lib.lp_run_focus(h, ptrs, hs, ws, n, None if ids is None else ids.ctypes.data_as(ip), *rest, views.ctypes.data_as(ip))
+
+        return self._run_staged(fn, images, (), conf, iou, min_area) + (views,)
+
+    def run_focus_device(self, dev_imgs: int, B: int, H: int, W: int, conf: float, iou: float, min_area: int,
+                         dev_dets: int, dev_counts: int, stream_ids=None, dev_views: int = 0) -> None:
+        """lp_run_focus_device; dev_views (0: not wanted) receives [B * slots * 4] int32.  Asynchronous on the engine's stream."""
+        ids = self._stream_ids(stream_ids, B)
+        check(self.lib, self.lib.lp_run_focus_device(self._h, C.c_void_p(dev_imgs), B, H, W,
+                                                     None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int)), conf, iou,
+                                                     int(min_area), C.c_void_p(dev_dets), C.c_void_p(dev_counts),
+                                                     C.c_void_p(dev_views) if dev_views else None))
 
     # ---- sign inventory: one record and best crop per finished track ---------------------------
     def inventory_create(self, **cfg) -> None:
@@ -929,7 +1010,8 @@ class HybridPipeline:
                  max_batch: int = 1, max_det: int = 300, device: int = 0, max_rois: int = 0, numerics: str = "e2e",
                  tile_overlap: Optional[int] = None, tile_full_frame: bool = True, pixel_format: str = "bgr",
                  csc_matrix: str = "bt601", track: bool = False, track_config: Optional[Dict] = None, inventory=False,
-                 views=None, view_tile: Optional[int] = None, view_overlap: int = 0, view_full_frame: bool = True):
+                 views=None, view_tile: Optional[int] = None, view_overlap: int = 0, view_full_frame: bool = True,
+                 focus: Optional[int] = None, focus_config: Optional[Dict] = None):
         """inventory: True or a dict of lp_inventory_config's fields (max_signs, keep_crops, best, min_hits): every tracked call
         also feeds the engine's sign inventory, while the handle still holds that call's classifier crops; drain_signs() returns
         the finished signs.  Needs track.
@@ -943,7 +1025,11 @@ class HybridPipeline:
         with the letterboxed whole frame as an extra view when tile_full_frame.
         views: scaled views (lp_run_views): a list of (x, y, w, h) source windows and / or "full", each letterboxed into the
         detector batch at its own scale and applied to every frame; or view_tile (with view_overlap, view_full_frame): the
-        window grid of lp_view_grid for every frame's size.  Mutually exclusive with each other and with tile_overlap."""
+        window grid of lp_view_grid for every frame's size.  Mutually exclusive with each other and with tile_overlap.
+        focus: K = focus views (lp_run_focus): every frame is seen through the whole frame and K windows the engine's tracker
+        chooses on the device, the free ones swept over a window grid (focus_config: lp_focus_config's other fields).  Needs
+        track and a max_batch of at least 1 + K; mutually exclusive with tile_overlap, views and view_tile.  The windows of
+        the last run_batch are in last_focus_views."""
         self.tile_overlap, self.tile_full_frame = tile_overlap, bool(tile_full_frame)
         if sum(x is not None for x in (tile_overlap, views, view_tile)) > 1:
             raise ValueError("tile_overlap, views and view_tile are mutually exclusive")
@@ -952,6 +1038,20 @@ class HybridPipeline:
             raise ValueError("views needs at least one view")
         self.view_tile, self.view_overlap, self.view_full_frame = view_tile, int(view_overlap), bool(view_full_frame)
         self.view_mode = self.views is not None or view_tile is not None
+        self.focus = None if focus is None else int(focus)
+        if self.focus is not None:
+            if tile_overlap is not None or self.view_mode:
+                raise ValueError("focus is mutually exclusive with tile_overlap, views and view_tile")
+            if not (track or track_config is not None):
+                raise ValueError("focus needs a pipeline constructed with track=True or a track_config")
+            if max_batch < 1 + self.focus:
+                raise ValueError(f"focus = {self.focus} needs max_batch >= {1 + self.focus} (it is {max_batch})")
+            if "slots" in (focus_config or {}):
+                raise ValueError("focus_config: the number of slots is the focus argument")
+            if int(os.environ.get("LITEPI_DROPIN_LANES", "1")) > 1:
+                raise ValueError("focus: the upload lanes run on other handles than the tracker's; unset LITEPI_DROPIN_LANES")
+        elif focus_config is not None:
+            raise ValueError("focus_config needs focus")
         self.inventory = bool(inventory) or isinstance(inventory, dict)
         if self.inventory and not (track or track_config is not None):
             raise ValueError("inventory needs a pipeline constructed with track=True or a track_config")
@@ -973,6 +1073,9 @@ class HybridPipeline:
         self.track = bool(track)
         if self.track or track_config is not None:
             self.engine.tracker_create(**(track_config or {}))
+        self.last_focus_views: List = []
+        if self.focus is not None:
+            self.engine.focus_create(slots=self.focus, **(focus_config or {}))
         self.signs_dropped = 0
         if self.inventory:
             self.engine.inventory_create(**(inventory if isinstance(inventory, dict) else {}))
@@ -1058,6 +1161,10 @@ class HybridPipeline:
             used += n
         if cur:
             groups.append((cur, cur_key))
+        return self._run_groups(groups, feed, call)
+
+    def _run_groups(self, groups, feed, call):
+        """the engine calls of _run_grouped / _run_focus over (frames, key) groups, results concatenated in frame order"""
         parts, done = [], 0
         for g, key in groups:
             d, c, nd, t = call(g, key)
@@ -1084,6 +1191,31 @@ class HybridPipeline:
             vs = self.views if self.views is not None else view_grid(self.view_tile, fh, fw, self.view_overlap, self.view_full_frame)
             return vs, len(vs)
         return self._run_grouped(images, feed, "has", frame_views, lambda g, vs: self.engine.run_views(g, vs, conf, iou, min_area))
+
+    def _run_focus(self, images, conf, iou, min_area, feed, ids):
+        """lp_run_focus calls of consecutive frames: at most one frame per stream in a call, so that every frame is planned from
+        the tracker state of the frame before it (the feed runs behind every call), and 1 + focus views per frame within
+        max_batch.  The windows every frame was seen through are kept in last_focus_views, [slots][4] per frame."""
+        cfg = self.engine.cfg
+        per_call = min(cfg.max_batch // (1 + self.focus),
+                       max(1, (cfg.max_rois if cfg.max_rois > 0 else cfg.max_batch * cfg.max_det) // cfg.max_det))
+        groups, cur, cur_ids = [], [], []
+        for k, img in enumerate(images):
+            s = 0 if ids is None else int(ids[k])
+            if cur and (s in cur_ids or len(cur) >= per_call):
+                groups.append((cur, cur_ids))
+                cur, cur_ids = [], []
+            cur.append(img)
+            cur_ids.append(s)
+        if cur:
+            groups.append((cur, cur_ids))
+        self.last_focus_views = []
+
+        def call(g, g_ids):
+            d, c, nd, t, views = self.engine.run_focus(g, conf, iou, min_area, stream_ids=g_ids)
+            self.last_focus_views += views.tolist()
+            return d, c, nd, t
+        return self._run_groups(groups, feed, call)
 
     def _track(self, dets, counts, stream_ids):
         """the call's records through the engine's tracker, at most max_batch frames per lp_track call, in frame order"""
@@ -1126,6 +1258,7 @@ class HybridPipeline:
     def run_batch(self, images: Sequence[np.ndarray], conf_threshold: float = 0.5, iou_threshold: float = 0.45,
                   min_area: int = 100, stream_ids=None, track: Optional[bool] = None) -> List[Tuple[List[Dict], PipelineMetrics]]:
         """stream_ids: the tracker stream of every image (None: all stream 0); track: None = the constructor's setting.
+        With focus views, track=False still plans the windows from the tracker's state (and moves the sweep) but feeds it nothing.
         In tiled mode (and with scaled views) tracker and inventory are fed behind every engine call of the batch: if a later call of the batch
         fails, they have consumed the frames of the earlier ones although the caller gets no result for the batch."""
         do_track = self.track if track is None else bool(track)
@@ -1144,7 +1277,10 @@ class HybridPipeline:
                 raise
         t0 = time.perf_counter()
         try:
-            if self.tile_overlap is not None:
+            if self.focus is not None:
+                dets, counts, num_det, timing = self._run_focus(list(images), conf_threshold, iou_threshold, min_area, feed if do_track else None,
+                                                                None if stream_ids is None else self.engine._stream_ids(stream_ids, len(images)))
+            elif self.tile_overlap is not None:
                 dets, counts, num_det, timing = self._run_tiled(list(images), conf_threshold, iou_threshold, min_area, feed if do_track else None)
             elif self.view_mode:
                 dets, counts, num_det, timing = self._run_views(list(images), conf_threshold, iou_threshold, min_area, feed if do_track else None)
@@ -1160,7 +1296,7 @@ class HybridPipeline:
         tracks = None
         if do_track:
             B = len(images)
-            if self.tile_overlap is not None or self.view_mode:
+            if self.tile_overlap is not None or self.view_mode or self.focus is not None:
                 tracks = np.concatenate(fed, 0)
             elif self.inventory:   # one engine call on this handle
                 tracks = self._feed(dets[:B], counts[:B], ids, 0)

@@ -93,6 +93,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--views", type=str, default=None,
                    help='scaled views given one by one, applied to every frame: "full;x,y,w,h;..." (full = the letterboxed whole '
                         'frame; x,y,w,h = a source window in frame pixels, letterboxed to det_input at its own scale)')
+    p.add_argument("--focus", type=int, default=None,
+                   help="focus views (off when absent; needs --track): every frame is seen through the whole frame and this many "
+                        "windows the tracker chooses on the device -- native-resolution looks at the small tracked signs, the free "
+                        "ones swept over the frame -- and focus.csv lists the windows of every frame; excludes --tile_overlap, "
+                        "--view_tile and --views")
+    p.add_argument("--focus_side_max", type=int, default=0, help="focus views: the largest window side (0 = 2 x det_input)")
+    p.add_argument("--focus_margin", type=float, default=2.0, help="focus views: a window's side is this many times the box's longer side")
+    p.add_argument("--no_focus_sweep", action="store_true", help="focus views: leave the free window slots empty instead of sweeping the frame")
     p.add_argument("--raw_frames", type=str, default=None,
                    help="headerless file of concatenated video frames (ffmpeg -f rawvideo) evaluated instead of the images of --input; "
                         "needs --frame_size; frames are named frame_000001, frame_000002, ...")
@@ -372,11 +380,16 @@ def parse_views(text: str) -> List:
 
 
 def check_frame_args(args) -> None:
-    modes = [n for n in ("tile_overlap", "view_tile", "views") if getattr(args, n, None) is not None]
+    modes = [n for n in ("tile_overlap", "view_tile", "views", "focus") if getattr(args, n, None) is not None]
     if len(modes) > 1:
         raise SystemExit("--" + ", --".join(modes) + " exclude each other: one way of looking at a frame per run")
     if getattr(args, "views", None) is not None:
         parse_views(args.views)
+    if getattr(args, "focus", None) is not None:
+        if not getattr(args, "track", False):
+            raise SystemExit("--focus needs --track: the windows are chosen from the tracker's state")
+        if not 1 <= args.focus <= 16:
+            raise SystemExit(f"--focus {args.focus} outside 1..16 window slots")
     if getattr(args, "inventory", False) and not getattr(args, "track", False):
         raise SystemExit("--inventory needs --track: the inventory lists the tracker's finished tracks")
     if getattr(args, "track", False):   # tracking needs the frames of ONE sequence, all of them, in order, in one process
@@ -452,6 +465,11 @@ def run_evaluation(args) -> Dict:
         view_kw = dict(views=parse_views(args.views))
         max_batch = nb * len(view_kw["views"])
         max_rois = max_rois if max_rois > 0 else nb * max_det
+    if getattr(args, "focus", None) is not None:   # one whole-frame view and --focus windows per frame
+        view_kw = dict(focus=args.focus, focus_config=dict(side_max=args.focus_side_max, margin=args.focus_margin,
+                                                           sweep=0 if args.no_focus_sweep else 1))
+        max_batch = nb * (1 + args.focus)
+        max_rois = max_rois if max_rois > 0 else nb * max_det
     import contextlib
     import io
     # with --track off the pipeline is constructed and called exactly as before
@@ -492,7 +510,7 @@ def run_evaluation(args) -> Dict:
     files = files[lo:hi]
 
     all_preds, all_gts, bench_time, names = [], [], 0.0, []
-    track_rows, signs = [], []
+    track_rows, signs, focus_rows = [], [], []
     try:
         n_warm = args.warmup if args.warmup is not None else (10 if args.numerics == "e2e_optimize" else 0)
         if n_warm > 0:   # warmup_pipeline (e2e_optimize.py:552-570): random frame, conf 0.5
@@ -521,7 +539,11 @@ def run_evaluation(args) -> Dict:
             # the tracker is fed exactly once per frame: by the benchmark pass; the evaluation pass is not tracked
             bench = pipeline.run_batch(imgs, args.benchmark_conf, args.iou_threshold, args.min_area, **bench_kw)
             bench_time += sum(m.t_total for _, m in bench) / 1000.0
+            bench_views = list(getattr(pipeline, "last_focus_views", []))
             ev = bench if args.yolo_conf == args.benchmark_conf else pipeline.run_batch(imgs, args.yolo_conf, args.iou_threshold, args.min_area, **eval_kw)
+            if getattr(args, "focus", None) is not None:   # the windows of the benchmark pass, the one the tracker follows
+                for f, wins in zip(chunk, bench_views):
+                    focus_rows += [(f.index, k, *w) for k, w in enumerate(wins)]
             if args.track:
                 for f, (res, _) in zip(chunk, bench):
                     track_rows += [(f.index, r["track_id"], *r["bbox"], r["det_conf"], r["cls_class"], r["cls_conf"], r["track_cls"],
@@ -553,6 +575,14 @@ def run_evaluation(args) -> Dict:
             w.writerows(track_rows)
         confirmed = {r[1] for r in track_rows if r[-1] and r[1] > 0}
         say(f"Tracking: {len(confirmed)} confirmed tracks over {len(files)} frames ({len(track_rows)} detections) -> {out_dir / 'tracks.csv'}")
+    if getattr(args, "focus", None) is not None:
+        import csv
+        with open(out_dir / "focus.csv", "w", newline="") as fcsv:
+            w = csv.writer(fcsv)
+            w.writerow(("frame", "slot", "x", "y", "w", "h"))
+            w.writerows(focus_rows)
+        used = sum(1 for r in focus_rows if r[4] > 0)
+        say(f"Focus views: {used} windows in {len(focus_rows)} slots over {len(files)} frames -> {out_dir / 'focus.csv'}")
     if args.inventory:
         import csv
         from PIL import Image
