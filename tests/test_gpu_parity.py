@@ -462,7 +462,8 @@ def test_detector_fp16_out0(synth_models, preset, cap):
     amplifies logit rounding) + 2 %, and 0.5 px on average (20+ layers of fp16 rounding).
     cap: handle capacity -- below 4 images the planner keeps the layer-at-a-time plan, from 4 on v1 runs the whole-C2f
     launches (c2f_kernels.hip); both must meet the bound.  The Detect head ALONE (its own input map -> out0) is pinned far more
-    tightly, against a float64 reference with the kernel's rounding points, in test_gpu_head_float64.py."""
+    tightly, against a float64 reference with the kernel's rounding points, in test_gpu_head_float64.py, and every launch of
+    c2f_kernels.hip (whole-C2f, stride-2, SPPF: its own HBM input -> its output blob) in test_gpu_c2f_float64.py."""
     from litepi import Engine
     param, binf = synth_models[preset]
     rng = np.random.default_rng(1)

@@ -57,6 +57,7 @@ struct C2fLayer {
   C2fShape sh;
   int H = 0, W = 0;
   std::string name;
+  bool store_all = false;   // bisect mode (LITEPI_C2F_STORE_ALL=1, read by the planner at load): what the planner marks as stored is stored
   DevBuf d_w[C2F_NW], d_b[C2F_NW];
   size_t lds_bytes = 0;
   double macs_per_image = 0;

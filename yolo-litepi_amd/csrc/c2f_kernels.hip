@@ -1943,7 +1943,8 @@ void C2fLayer::launch(const IO& io, int N, hipStream_t st) const {
   CfgInfo ci;
   LP_CHECK(cfg_info(sh, ci), LP_ERR_STATE, "c2f %s: no configuration for this shape", name.c_str());
   a.tiles_x = W / ci.tw; a.tiles_y = H / ci.th;
-  static const bool store_all = getenv("LITEPI_C2F_STORE_ALL") != nullptr;   // bisect aid: every y segment goes to the concat buffer
+  // store_all: bisect aid, every y segment goes to the concat buffer.  The layer's own flag, set by the planner from the switch it
+  // read at load: a per-process read here could disagree with the blobs that load marked as stored
   static const int dbg_flags = getenv("LITEPI_C2F_DEBUG") ? atoi(getenv("LITEPI_C2F_DEBUG")) : 0;   // see Ctx::dbg
   a.debug_store = (store_all ? 1 : 0) | (dbg_flags & ~1);
   static const char* stamp_file = getenv("LITEPI_C2F_STAMPS");

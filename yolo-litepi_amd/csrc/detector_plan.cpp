@@ -717,6 +717,7 @@ void Planner::emit_c2f(const C2fMatch& m, int mode, const C2fShape& sh, int i0, 
   C2fLayer& cl = *d.c2fs_.back();
   cl.name = (i0 >= 0 ? L[i0].name + "+" : std::string()) + L[mode < 0 ? m.a[0] : m.cv1].name + ".." + L[m.cv2].name + (mode == 2 ? "+sppf" : "");
   cl.build(sh, Hh, Ww, src);
+  cl.store_all = sw.c2f_store_all;
   C2fIO io;
   io.src1 = mode < 0 ? m.t_cat : cinfo[m.cv1].tin;   // (unused by MODE -1: the module reads the concat buffer)
   if (mode >= 0 && sh.UP) { io.src0 = fuse_up[m.cv1]; io.up_c = sh.KA; }
