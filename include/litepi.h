@@ -227,6 +227,16 @@ int lp_view_grid(int tile, int overlap, int full_frame, int H, int W, int* n_vie
 /* The geometry of one view {x, y, w, h} of an H x W frame (pure host); every output may be NULL */
 int lp_view_geometry(int det_input, int H, int W, const int* view, float* ratio, float* pad_w, float* pad_h,
                      int* new_w, int* new_h, int* top, int* left);
+/* The letterbox of an H x W image into a det_h x det_w detector input (pure host; no handle, no device): the reference's
+ * letterbox(img, new_shape = (det_h, det_w)) (e2e.py:66-86), rows x columns, in doubles:
+ *   r = min(det_h / H, det_w / W);  new_w = rint(W * r);  new_h = rint(H * r);  dw = (det_w - new_w) / 2;  dh = (det_h - new_h) / 2
+ *   top = rint(dh - 0.1);  left = rint(dw - 0.1)      (rint: round half to even)
+ *   ratio = (float)r;  pad_w = (float)dw;  pad_h = (float)dh
+ * With det_h == det_w it is the whole-frame view of lp_view_geometry, bit for bit.  The handle itself still takes a square
+ * input only (lp_config::det_input): this is the geometry a rectangular detector input will use.  Every output
+ * may be NULL; LP_ERR_ARG for a non-positive size. */
+int lp_letterbox_geometry(int det_h, int det_w, int H, int W, float* ratio, float* pad_w, float* pad_h,
+                          int* new_w, int* new_h, int* top, int* left);
 /* lp_run_batch over B host frames, each seen through the n_views views (views: n_views x 4 ints): dets [B*max_det],
  * counts / num_det / det_conf_avg [B] per frame.  views = {-1, ..} alone gives lp_run_batch's result. */
 int lp_run_views(lp_handle* h, const uint8_t* const* imgs, const int* heights, const int* widths, int B,

@@ -329,6 +329,24 @@ int lp_view_geometry(int det_input, int H, int W, const int* view, float* ratio,
   LP_API_END
 }
 
+// the reference's letterbox(img, (det_h, det_w)) in Python doubles (e2e.py:72-83): make_geom's arithmetic with one side per axis
+int lp_letterbox_geometry(int det_h, int det_w, int H, int W, float* ratio, float* pad_w, float* pad_h, int* new_w, int* new_h, int* top,
+                          int* left) {
+  LP_API_BEGIN
+  LP_CHECK(det_h > 0 && det_w > 0 && H > 0 && W > 0, LP_ERR_ARG, "bad argument (detector input %dx%d, image %dx%d; rows x columns)", det_h, det_w, H, W);
+  const double r = std::min((double)det_h / H, (double)det_w / W);
+  const int nw = (int)std::nearbyint(W * r), nh = (int)std::nearbyint(H * r);
+  const double dw = (det_w - nw) / 2.0, dh = (det_h - nh) / 2.0;
+  if (ratio) *ratio = (float)r;
+  if (pad_w) *pad_w = (float)dw;
+  if (pad_h) *pad_h = (float)dh;
+  if (new_w) *new_w = nw;
+  if (new_h) *new_h = nh;
+  if (top) *top = (int)std::nearbyint(dh - 0.1);
+  if (left) *left = (int)std::nearbyint(dw - 0.1);
+  LP_API_END
+}
+
 int lp_run_tiled(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, const lp_tiling* tiling, float conf,
                  float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing) {
   LP_API_BEGIN

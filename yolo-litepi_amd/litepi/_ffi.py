@@ -118,6 +118,7 @@ SYMBOLS = [
     "lp_inventory", "lp_inventory_flush", "lp_inventory_drain", "lp_inventory_open", "lp_test_set_rois", "lp_debug_rois",
     "lp_focus_default_config", "lp_focus_config_check", "lp_focus_create", "lp_focus_destroy", "lp_focus_plan", "lp_focus_state",
     "lp_run_focus_device", "lp_run_focus",
+    "lp_letterbox_geometry",
 ]
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
 
@@ -177,6 +178,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_test_tile_views.argtypes = [vp, vp, C.c_int, C.c_int, tp, C.c_int, vp, C.c_int, ip]
     lib.lp_view_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int]
     lib.lp_view_geometry.argtypes = [C.c_int, C.c_int, C.c_int, ip, fp, fp, fp, ip, ip, ip, ip]
+    lib.lp_letterbox_geometry.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, ip, ip, ip, ip]
     lib.lp_run_views.argtypes = [vp, u8pp, ip, ip, C.c_int, ip, C.c_int, C.c_float, C.c_float, C.c_int, vp, ip, ip, fp, C.POINTER(LpTiming)]
     lib.lp_run_views_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp]
     lib.lp_test_view_windows.argtypes = [vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, vp, C.c_int]

@@ -115,6 +115,18 @@ def view_geometry(det_input: int, H: int, W: int, view) -> Dict[str, object]:
                 top=top.value, left=left.value)
 
 
+def letterbox_geometry(det_h: int, det_w: int, H: int, W: int) -> Dict[str, object]:
+    """The letterbox of an H x W image into a det_h x det_w detector input (lp_letterbox_geometry: host only), the reference's
+    letterbox(img, (det_h, det_w)): ratio, pad_w, pad_h (float32 values), new_w, new_h, top, left."""
+    lib = _ffi.load_library()
+    r, pw, ph = C.c_float(), C.c_float(), C.c_float()
+    nw, nh, top, left = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    check(lib, lib.lp_letterbox_geometry(int(det_h), int(det_w), int(H), int(W), C.byref(r), C.byref(pw), C.byref(ph), C.byref(nw),
+                                         C.byref(nh), C.byref(top), C.byref(left)))
+    return dict(ratio=np.float32(r.value), pad_w=np.float32(pw.value), pad_h=np.float32(ph.value), new_w=nw.value, new_h=nh.value,
+                top=top.value, left=left.value)
+
+
 TRACK_CONFIG_FIELDS = ("n_streams", "max_tracks", "iou_match", "max_age", "min_hits", "new_conf", "vote_decay", "class_gate", "motion")
 
 

@@ -226,22 +226,33 @@ class _Builder:
                     f.write(np.ascontiguousarray(op.data, "<f4").tobytes())
 
 
-def make_anchors(size: int, strides: Sequence[int] = (8, 16, 32)) -> Tuple[np.ndarray, np.ndarray]:
-    """Anchor points (grid units, +0.5) as [2, A] and per-anchor stride [A], levels in order."""
+def _size_hw(size) -> Tuple[int, int]:
+    """An input size as (rows, columns): an int is a square, a pair is (h, w)."""
+    if isinstance(size, (tuple, list)):
+        h, w = size
+        return int(h), int(w)
+    return int(size), int(size)
+
+
+def make_anchors(size, strides: Sequence[int] = (8, 16, 32)) -> Tuple[np.ndarray, np.ndarray]:
+    """Anchor points (grid units, +0.5) as [2, A] and per-anchor stride [A], levels in order; size: an int (square input) or
+    (rows, columns).  Within a level the anchors are row-major: anchor y * (w // s) + x is (x + 0.5, y + 0.5)."""
+    h, w = _size_hw(size)
     xs, ys, ss = [], [], []
     for s in strides:
-        n = size // s
-        gy, gx = np.meshgrid(np.arange(n, dtype=np.float32) + 0.5, np.arange(n, dtype=np.float32) + 0.5, indexing="ij")
+        nh, nw = h // s, w // s
+        gy, gx = np.meshgrid(np.arange(nh, dtype=np.float32) + 0.5, np.arange(nw, dtype=np.float32) + 0.5, indexing="ij")
         xs.append(gx.ravel())
         ys.append(gy.ravel())
-        ss.append(np.full(n * n, s, np.float32))
+        ss.append(np.full(nh * nw, s, np.float32))
     return np.stack([np.concatenate(xs), np.concatenate(ys)]), np.concatenate(ss)
 
 
 def export_detector(param_path: str, bin_path: str, preset: str = "v1", seed: int = 1234, nc: int = 1,
-                    reg_max: int = 16, size: int = 640, cls_bias: float = -4.0, gain: float = 2.0, box_ramp: float = 0.45,
+                    reg_max: int = 16, size=640, cls_bias: float = -4.0, gain: float = 2.0, box_ramp: float = 0.45,
                     spec: Optional[dict] = None) -> dict:
-    """Write a seeded random-weight detector; returns the spec used."""
+    """Write a seeded random-weight detector; returns the spec used.  size: an int (square input) or (rows, columns); it sets
+    only the anchor and stride tables and the Reshape extents of the Detect tail: one seed gives one set of weights at every size."""
     sp = dict(PRESETS[preset]) if spec is None else dict(spec)
     c1, c2, c3, c4, c5 = sp["c"]
     n = sp["n"]
@@ -280,7 +291,7 @@ def export_detector(param_path: str, bin_path: str, preset: str = "v1", seed: in
         level_cats.append(g.concat([b, c]))
     rs = []
     for cat, s in zip(level_cats, (8, 16, 32)):
-        hw = (size // s) ** 2
+        hw = (_size_hw(size)[0] // s) * (_size_hw(size)[1] // s)
         rs.append(g.raw("Reshape", "reshape", [cat], 1, f"0={hw} 1={4 * reg_max + nc}")[0])
     allc = g.raw("Concat", "cat", rs, 1, "0=1")[0]
     box, cls = g.raw("Slice", "split", [allc], 2, f"-23300=2,{4 * reg_max},{nc} 1=0")
@@ -341,7 +352,7 @@ def shift_cls_bias(param_path: str, bin_path: str, delta: float, nc: int = 1) ->
         f.write(bytes(blob))
 
 
-def seeded_bin_for_param(param_path: str, bin_path: str, seed: int = 1234, gain: float = 1.6, size: int = 640,
+def seeded_bin_for_param(param_path: str, bin_path: str, seed: int = 1234, gain: float = 1.6, size=640,
                          cls_bias: float = -2.0) -> None:
     """Write a seeded random fp32 ``.bin`` that matches an existing NCNN ``.param`` of the YOLOv8 family
     (same file layout as a real export: per Convolution a zero flag word, weights, optional bias; MemoryData
@@ -381,5 +392,5 @@ def seeded_bin_for_param(param_path: str, bin_path: str, seed: int = 1234, gain:
                 w, h = int(p.get(0, 0)), int(p.get(1, 0))
                 data = strides if h == 0 else anchors
                 if data.size != max(w, 1) * max(h, 1):
-                    raise ValueError(f"MemoryData {L['name']}: {w}x{h} does not match the {size}x{size} anchor grid")
+                    raise ValueError(f"MemoryData {L['name']}: {w}x{h} does not match the {'x'.join(str(v) for v in _size_hw(size))} anchor grid")
                 f.write(np.ascontiguousarray(data, "<f4").tobytes())
