@@ -49,7 +49,7 @@ typedef struct lp_config {
                         survive, the max_det highest scores over all classes stay, emitted class-ascending then
                         score-descending like the reference; set it to the anchor count for keep-all semantics */
   int num_classes;   /* classifier classes (e2e.py:353 default 58) */
-  int det_input;     /* detector input size (e2e.py:1040 --det_input_size, 640) */
+  int det_input;     /* detector input size (e2e.py:1040 --det_input_size, 640); with det_input_h set it is the width */
   int cls_input;     /* classifier input size (e2e.py:1041 --cls_input_size, 64) */
   int max_rois;      /* ROIs classified per call; 0 = max_batch * max_det = every kept box, as the reference
                         (e2e.py:493-497).  A smaller value that a batch exceeds makes lp_run_batch fail with
@@ -61,7 +61,12 @@ typedef struct lp_config {
                         1 = HybridPipelineOptimized (e2e_optimize.py:480-497, 386-390): clip to [0,w] x [0,h], drop empty
                             rectangles, cv2.resize INTER_LINEAR (no antialias).  PARITY UNPINNED (cv2 absent, no fixtures) */
   int cls_arch;      /* lp_cls_arch: classifier architecture (e2e.py:320-333 --clf_arch) */
-  int reserved[5];
+  int det_input_h;   /* detector input height for a rectangular input (the reference's letterbox(img, (rows, columns))):
+                        0 = square, det_input x det_input; otherwise a multiple of 32, at least 64 (LP_ERR_ARG).  Below,
+                        SH = det_input_h ? det_input_h : det_input and SW = det_input.  The frame-view families (tiled,
+                        views, focus) need SH == SW: LP_ERR_STATE otherwise.  Took reserved[0]: 0 is what every caller
+                        of ABI 310 passed.  DESIGN.md 6h */
+  int reserved[4];
 } lp_config;
 
 /* One detection, 32 bytes.  Mirrors one result dict of HybridPipeline.run
@@ -111,7 +116,7 @@ int lp_load_classifier_tensors(lp_handle* h, int n, const char* const* names,
 
 /* ---- detector parity hook ------------------------------------------------------- */
 /* replaces preprocess + ex.extract("out0") (e2e.py:222-238,305-307) for B images that are
- * already det_input x det_input: host uint8 BGR [B,S,S,3] -> host fp32 out0 [B,4+nc,A]. */
+ * already SH x SW (lp_config::det_input_h): host uint8 BGR [B,SH,SW,3] -> host fp32 out0 [B,4+nc,A]. */
 int lp_detect_raw(lp_handle* h, const uint8_t* bgr, int B, float* out0);
 
 /* ---- detector + NMS ------------------------------------------------------------- */
@@ -232,9 +237,9 @@ int lp_view_geometry(int det_input, int H, int W, const int* view, float* ratio,
  *   r = min(det_h / H, det_w / W);  new_w = rint(W * r);  new_h = rint(H * r);  dw = (det_w - new_w) / 2;  dh = (det_h - new_h) / 2
  *   top = rint(dh - 0.1);  left = rint(dw - 0.1)      (rint: round half to even)
  *   ratio = (float)r;  pad_w = (float)dw;  pad_h = (float)dh
- * With det_h == det_w it is the whole-frame view of lp_view_geometry, bit for bit.  The handle itself still takes a square
- * input only (lp_config::det_input): this is the geometry a rectangular detector input will use.  Every output
- * may be NULL; LP_ERR_ARG for a non-positive size. */
+ * With det_h == det_w it is the whole-frame view of lp_view_geometry, bit for bit.  It is the geometry a handle with
+ * lp_config::det_input_h = det_h and det_input = det_w letterboxes with (one arithmetic).  Every output may be
+ * NULL; LP_ERR_ARG for a non-positive size. */
 int lp_letterbox_geometry(int det_h, int det_w, int H, int W, float* ratio, float* pad_w, float* pad_h,
                           int* new_w, int* new_h, int* top, int* left);
 /* lp_run_batch over B host frames, each seen through the n_views views (views: n_views x 4 ints): dets [B*max_det],
@@ -581,9 +586,13 @@ int lp_test_nms_boxes(lp_handle* h, const float* boxes, const float* scores, con
 /* PIL-exact ROI resize alone: host BGR crops -> uint8 RGB [R,S,S,3]. */
 int lp_test_roi_resize(lp_handle* h, const uint8_t* const* rois, const int* heights,
                        const int* widths, int R, uint8_t* out_rgb);
-/* cv2-style letterbox alone: host BGR image -> uint8 BGR [S,S,3] + ratio/pad. */
+/* cv2-style letterbox alone: host BGR image -> uint8 BGR [SH,SW,3] + ratio/pad (lp_config::det_input_h). */
 int lp_test_letterbox(lp_handle* h, const uint8_t* img, int H, int W, uint8_t* out,
                       float* ratio, float* pad_w, float* pad_h);
+/* the same with the kernel named: 0 = the launcher's choice (the tiled kernel where its LDS rows fit, else the per-pixel
+ * kernel), 1 = the per-pixel kernel.  Both give the same bytes.  (additive to ABI 310) */
+int lp_test_letterbox_kernel(lp_handle* h, const uint8_t* img, int H, int W, int kernel, uint8_t* out,
+                             float* ratio, float* pad_w, float* pad_h);
 
 #ifdef __cplusplus
 }

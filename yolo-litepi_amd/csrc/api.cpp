@@ -138,6 +138,8 @@ int lp_create(const lp_config* cfg, lp_handle** out) {
   LP_CHECK(cfg && out, LP_ERR_ARG, "null argument");
   LP_CHECK(cfg->max_batch >= 1 && cfg->max_batch <= 1024 && cfg->max_det >= 1 && cfg->det_input % 32 == 0 && cfg->det_input >= 64,
            LP_ERR_ARG, "bad config (max_batch %d, max_det %d, det_input %d)", cfg->max_batch, cfg->max_det, cfg->det_input);
+  LP_CHECK(cfg->det_input_h == 0 || (cfg->det_input_h % 32 == 0 && cfg->det_input_h >= 64), LP_ERR_ARG,
+           "bad config (det_input_h %d: 0 for a square input, else a multiple of 32 and at least 64)", cfg->det_input_h);
   LP_CHECK((cfg->numerics == 0 || cfg->numerics == 1) && cfg->cls_arch >= 0 && cfg->cls_arch <= LP_CLS_EFFICIENTNET_B0, LP_ERR_ARG,
            "bad config (numerics %d, cls_arch %d)", cfg->numerics, cfg->cls_arch);
   int ndev = 0;
@@ -176,8 +178,7 @@ int lp_create(const lp_config* cfg, lp_handle** out) {
   h->stream = h->own_stream;
   for (auto& e : h->ev) LP_HIP(hipEventCreate(&e));
   h->d_geom.alloc((size_t)std::max(cfg->max_batch, h->max_rois) * sizeof(ImgGeom));
-  const int S = cfg->det_input;
-  h->d_lb.alloc((size_t)cfg->max_batch * S * S * 3, false);
+  h->d_lb.alloc((size_t)cfg->max_batch * h->det_h() * h->det_w() * 3, false);
   h->d_roi_base.alloc((size_t)(cfg->max_batch + 1) * 4);
   h->d_roi_total.alloc(32);  // total, unclamped total | accumulator, ticket (kernels.h RoiTable)
   h->d_roi_img.alloc((size_t)h->max_rois * 4);
@@ -210,7 +211,7 @@ int lp_load_detector_ncnn(lp_handle* h, const char* param_path, const char* bin_
   LP_API_BEGIN
   LP_CHECK(h && param_path && bin_path, LP_ERR_ARG, "null argument");
   LP_HIP(hipSetDevice(h->cfg.device));
-  std::unique_ptr<Detector> d(new Detector(h->cfg.precision, h->cfg.conv_impl, h->cfg.max_batch, h->cfg.det_input));
+  std::unique_ptr<Detector> d(new Detector(h->cfg.precision, h->cfg.conv_impl, h->cfg.max_batch, h->det_h(), h->det_w()));
   d->load(param_path, bin_path);
   h->drop_graphs();
   h->det = std::move(d);

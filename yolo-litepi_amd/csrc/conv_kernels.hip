@@ -13,6 +13,7 @@
 // those are 4 (x tiles) consecutive physical channels of one pixel -> vector stores.
 #include "common.h"
 #include "conv.h"
+#include "conv_bounds.h"
 #include <type_traits>
 
 namespace lp {
@@ -351,7 +352,9 @@ __device__ __forceinline__ void epilogue_tile(const ConvArgs& a, const floatx4 (
   const int chbase = ns * 16 * NT + g * 4 * NT;
   const int pix0 = (n * a.Hout + oy) * a.Wout + oxb;
   T* o = reinterpret_cast<T*>(a.out) + eoff(pix0, a.out_pitch) + chbase;
-  const T* r = a.res ? reinterpret_cast<const T*>(a.res) + eoff(pix0, a.res_pitch) + chbase : nullptr;
+  // the residual base stays inside the row when the whole strip lies right of the image (conv_bounds.h): its loads are discarded
+  const int rpix0 = (n * a.Hout + oy) * a.Wout + residual_base_col(oxb, a.Wout);
+  const T* r = a.res ? reinterpret_cast<const T*>(a.res) + eoff(rpix0, a.res_pitch) + chbase : nullptr;
   const int ostep = 4 * a.out_pitch, rstep = 4 * a.res_pitch;
   if (r) {
     // the residual quads of all five patches are requested before the first is used (unconditional, from clamped addresses:

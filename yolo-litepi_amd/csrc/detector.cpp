@@ -68,8 +68,8 @@ int Tensor::phys(int c) const {
   return -1;
 }
 
-Detector::Detector(int prec, int impl, int max_batch, int input_size)
-    : prec_(prec), impl_(impl), maxB_(max_batch), S_(input_size) {}
+Detector::Detector(int prec, int impl, int max_batch, int input_h, int input_w)
+    : prec_(prec), impl_(impl), maxB_(max_batch), SH_(input_h), SW_(input_w) {}
 
 View Detector::view(int t) const {
   const Tensor* T = &tensors_[t];
@@ -109,11 +109,11 @@ void Detector::forward(const uint8_t* imgs, int B, const ImgGeom* geom, float co
     std::string kname;
     switch (op.kind) {
       case DetOp::STEM:
-        stem_.launch(imgs, B, S_, S_, view(op.out), st);
+        stem_.launch(imgs, B, SH_, SW_, view(op.out), st);
         kname = std::string("stem_conv") + sfx;
         break;
       case DetOp::STEMBLOCK:
-        stem_.launch_block(imgs, B, S_, S_, *convs_[op.conv], view(op.out), st);
+        stem_.launch_block(imgs, B, SH_, SW_, *convs_[op.conv], view(op.out), st);
         kname = std::string(stem_.CO == 16 ? "stem_block16" : "stem_block") + sfx;
         break;
       case DetOp::CONV: {

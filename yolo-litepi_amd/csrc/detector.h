@@ -50,10 +50,10 @@ struct DetOp {
 
 class Detector {
  public:
-  Detector(int prec, int impl, int max_batch, int input_size);
+  Detector(int prec, int impl, int max_batch, int input_h, int input_w);
   void load(const std::string& param_path, const std::string& bin_path);
   bool loaded() const { return loaded_; }
-  // imgs: device uint8 BGR [B,S,S,3]; geom: device ImgGeom[B]; out0: optional device fp32 [B,4+nc,A].
+  // imgs: device uint8 BGR [B,SH,SW,3]; geom: device ImgGeom[B]; out0: optional device fp32 [B,4+nc,A].
   // Enqueues the forward pass + decode/conf filter; candidates land in cand/cand_count.
   void forward(const uint8_t* imgs, int B, const ImgGeom* geom, float conf, float* out0, Cand* cand, int* cand_count,
                hipStream_t st, Profiler* prof);
@@ -61,14 +61,15 @@ class Detector {
   int num_classes() const { return nc_; }
   int reg_max() const { return reg_max_; }
   double macs_per_image() const { return macs_; }
-  int input_size() const { return S_; }
+  int input_h() const { return SH_; }
+  int input_w() const { return SW_; }
   // test aid: copy a blob of the last forward to host as fp32 [B,C,H,W]
   void fetch_blob(const std::string& name, int B, std::vector<float>& out, int& C, int& H, int& W) const;
 
  private:
   friend struct Planner;   // detector_plan.cpp: builds the plan inside load()
   View view(int t) const;
-  int prec_, impl_, maxB_, S_;
+  int prec_, impl_, maxB_, SH_, SW_;   // the input: rows x columns
   int fwd_calls_ = 0;   // LITEPI_SKIP_OP diagnostic
   bool loaded_ = false;
   std::vector<Tensor> tensors_;

@@ -46,7 +46,7 @@ struct Planner {
 
   // ---- the detector being planned
   Detector& d;
-  const int prec_, impl_, maxB_, S_;
+  const int prec_, impl_, maxB_, SH_, SW_;
   std::vector<Tensor>& tensors_ = d.tensors_;
   std::map<std::string, int>& blob2tensor_ = d.blob2tensor_;
   std::vector<Buffer>& buffers_ = d.buffers_;
@@ -213,7 +213,7 @@ struct Planner {
 };
 
 Planner::Planner(Detector& det, const std::string& param, const std::string& bin)
-    : d(det), prec_(det.prec_), impl_(det.impl_), maxB_(det.maxB_), S_(det.S_), param_path(param), es(det.prec_ == LP_FP16 ? 2 : 4), esd((double)es) {
+    : d(det), prec_(det.prec_), impl_(det.impl_), maxB_(det.maxB_), SH_(det.SH_), SW_(det.SW_), param_path(param), es(det.prec_ == LP_FP16 ? 2 : 4), esd((double)es) {
   g.load(param, bin);
   n = (int)L.size();
   d.tensors_.clear(); d.blob2tensor_.clear(); d.buffers_.clear(); d.convs_.clear(); d.ops_.clear(); d.levels_.clear();
@@ -362,7 +362,7 @@ void Planner::make_tensors() {
       continue;
     }
     if (l.type == "Input") {
-      input_tensor = new_tensor(l.outputs[0], 3, S_, S_);
+      input_tensor = new_tensor(l.outputs[0], 3, SH_, SW_);
     } else if (l.type == "Convolution") {
       const int tin = get(l.inputs[0]);
       const int k = l.ipar(1, 1), s = l.ipar(3, 1), pad = l.ipar(4, 0), dil = l.ipar(2, 1);
@@ -1279,7 +1279,7 @@ void Planner::emit_concat_copies(int i) {
 //      the 320x320 stem map is never stored (StemLayer::launch_block; LITEPI_NO_STEMBLOCK=1: off)
 void Planner::fuse_stem_block() {
   if (sw.no_stemblock || ops_.size() < 2 || ops_[0].kind != DetOp::STEM || ops_[1].kind != DetOp::CONV || ops_[1].in != ops_[0].out ||
-      ops_[1].res >= 0 || S_ % 4 != 0 || canon_consumers[tensors_[ops_[0].out].name].size() != 1 ||
+      ops_[1].res >= 0 || SW_ % 4 != 0 || canon_consumers[tensors_[ops_[0].out].name].size() != 1 ||
       !d.stem_.block_supported(*convs_[ops_[1].conv]))
     return;
   const Tensor& TI = tensors_[ops_[0].in >= 0 ? ops_[0].in : input_tensor];
@@ -1331,12 +1331,13 @@ void Planner::build_detect_tail() {
   }
   // the NMS kernel packs the anchor index into 14 bits of its sort key and keeps every candidate of an image in one
   // workgroup's LDS: reject larger heads here, at load time, not on every call (a 1024x1024 input has 21504 anchors)
-  LP_CHECK(A_ <= 16384, LP_ERR_GRAPH, "Detect head with %d anchors: at most 16384 are supported (input size %d is too large)", A_, S_);
+  LP_CHECK(A_ <= 16384, LP_ERR_GRAPH, "Detect head with %d anchors: at most 16384 are supported (input size %dx%d is too large)", A_, SH_, SW_);
   LP_CHECK((int)anchors->data.size() == 2 * A_ && (int)strides->data.size() == A_, LP_ERR_GRAPH,
            "anchor tables (%zu, %zu) do not match %d anchors", anchors->data.size(), strides->data.size(), A_);
   for (auto& lv : levels_) {
     const float st = strides->data[lv.off];
-    LP_CHECK(st * lv.H == (float)S_, LP_ERR_GRAPH, "stride table does not match level %dx%d", lv.H, lv.W);
+    LP_CHECK(st * lv.H == (float)SH_ && st * lv.W == (float)SW_, LP_ERR_GRAPH, "stride table does not match level %dx%d of a %dx%d input", lv.H, lv.W,
+             SH_, SW_);
   }
   upload(d.d_anchors_, anchors->data);
   upload(d.d_strides_, strides->data);

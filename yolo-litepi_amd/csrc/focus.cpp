@@ -103,7 +103,7 @@ static void enqueue_focus_plan(lp_handle* h, int B, const int* hs, const int* ws
   float* frf = reinterpret_cast<float*>(fw + mb);
   for (int b = 0; b < B; ++b) {
     fh[b] = hs ? hs[b] : H; fw[b] = ws ? ws[b] : W;
-    frf[b] = make_geom(fh[b], fw[b], S, 0).ratio;
+    frf[b] = make_geom(fh[b], fw[b], S, S, 0).ratio;
   }
   int* dslot = p.plan_dev.as<int>() + (size_t)k * p.slot_ints;
   LP_HIP(hipMemcpyAsync(dslot, slot, p.slot_ints * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -166,6 +166,7 @@ int lp_focus_destroy(lp_handle* h) {
 int lp_focus_create(lp_handle* h, const lp_focus_config* cfg) {
   LP_API_BEGIN
   LP_CHECK(h, LP_ERR_ARG, "null handle");
+  check_square(h, "lp_focus_create");
   check_focus_config(cfg, h->cfg.det_input);
   LP_CHECK(h->trk, LP_ERR_STATE, "no tracker: call lp_tracker_create first");
   Tracker& t = *h->trk;
@@ -186,6 +187,7 @@ int lp_focus_create(lp_handle* h, const lp_focus_config* cfg) {
 
 int lp_focus_plan(lp_handle* h, int B, const int* heights, const int* widths, const int* stream_ids, int* views, int advance) {
   LP_API_BEGIN
+  check_square(h, "lp_focus_plan");
   FocusPlan& p = focus_of(h);
   const Tracker& t = *h->trk;
   LP_CHECK(heights && widths && views, LP_ERR_ARG, "null argument");
@@ -218,12 +220,13 @@ int lp_focus_state(lp_handle* h, int stream, int* cursor, int* unserved) {
 int lp_run_focus_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, const int* stream_ids, float conf, float iou, int min_area,
                         void* dev_dets, void* dev_counts, void* dev_views) {
   LP_API_BEGIN
+  check_square(h, "lp_run_focus_device");
   FocusPlan& p = focus_of(h);
   check_run_args(h, dev_imgs && dev_dets && dev_counts, B, false, min_area);
   check_focus_run(h, B, nullptr, nullptr, H, W, stream_ids);
   LP_HIP(hipSetDevice(h->cfg.device));
   std::vector<ImgGeom> fg(B);
-  for (int i = 0; i < B; ++i) fg[i] = make_geom(H, W, h->cfg.det_input, (long)i * H * W * 3);
+  for (int i = 0; i < B; ++i) fg[i] = make_geom(H, W, h->det_h(), h->det_w(), (long)i * H * W * 3);
   ViewLayout lay = focus_layout(h, p, fg);
   const bool nv = h->nv12();
   CscPlan csc;
@@ -251,12 +254,13 @@ int lp_run_focus_device(lp_handle* h, const void* dev_imgs, int B, int H, int W,
 int lp_run_focus(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, const int* stream_ids, float conf, float iou,
                  int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing, int* views) {
   LP_API_BEGIN
+  check_square(h, "lp_run_focus");
   FocusPlan& p = focus_of(h);
   check_run_args(h, imgs && hs && ws && dets && counts, B, true, min_area);
   check_focus_run(h, B, hs, ws, 0, 0, stream_ids);
   LP_HIP(hipSetDevice(h->cfg.device));
   std::vector<ImgGeom> fg(B);
-  for (int i = 0; i < B; ++i) fg[i] = make_geom(hs[i], ws[i], h->cfg.det_input, 0);
+  for (int i = 0; i < B; ++i) fg[i] = make_geom(hs[i], ws[i], h->det_h(), h->det_w(), 0);
   (void)focus_layout(h, p, fg);   // validates the call before anything is uploaded (the frames' offsets come with the upload)
   const bool nv = h->nv12();
   if (nv) {   // host frames: frame_stride does not apply

@@ -141,6 +141,9 @@ struct GraphEntry { GraphKey key; hipGraph_t graph = nullptr; hipGraphExec_t exe
 
 struct lp_handle {
   lp_config cfg;
+  // the detector input, rows x columns (lp_config::det_input_h: 0 = square)
+  int det_h() const { return cfg.det_input_h ? cfg.det_input_h : cfg.det_input; }
+  int det_w() const { return cfg.det_input; }
   std::unique_ptr<lp::Tracker> trk;   // null until lp_tracker_create: no other path looks at it
   void* comm = nullptr;        // ncclComm_t of lp_comm_init
   int comm_rank = 0, comm_world = 1;
@@ -241,14 +244,17 @@ namespace lp {
 
 // ---- pipeline pieces shared by the entry points (pipeline.cpp) -----------------------------------------------------------------
 // letterbox geometry exactly as the reference computes it in Python doubles (e2e.py:72-83)
-ImgGeom make_geom(int h, int w, int S, long src_off);
+// with one side per axis, (SH, SW) = (rows, columns); lp_letterbox_geometry returns its fields
+ImgGeom make_geom(int h, int w, int SH, int SW, long src_off);
+// the frame-view families (tiled, views, focus) take a square detector input: LP_ERR_STATE on a rectangular handle
+void check_square(const lp_handle* h, const char* what);
 Profiler* begin_profile(lp_handle* h);
 // the argument checks of lp_run_batch*, lp_run_tiled* and lp_run_views*: pointers, loaded models (host calls need the classifier),
 // batch size, and for host calls min_area
 void check_run_args(const lp_handle* h, bool pointers, int B, bool host, int min_area);
-// the letterbox of n images (geometry geoms on the host, d_geom on the device) into dst [n,S,S,3], booked as every source byte
+// the letterbox of n images (geometry geoms on the host, d_geom on the device) into dst [n,SH,SW,3], booked as every source byte
 // once + every output byte once
-void enqueue_letterbox(const uint8_t* src, const ImgGeom* d_geom, uint8_t* dst, const ImgGeom* geoms, int n, int S, hipStream_t st,
+void enqueue_letterbox(const uint8_t* src, const ImgGeom* d_geom, uint8_t* dst, const ImgGeom* geoms, int n, int SH, int SW, hipStream_t st,
                        Profiler* prof);
 // detector (+ optional letterbox) on images resident at src with geometry already uploaded
 void enqueue_detect(lp_handle* h, const uint8_t* src, const std::vector<ImgGeom>& geoms, int B, float conf, float* out0, Profiler* prof);

@@ -27,13 +27,13 @@ template <> struct VecT<float> { typedef floatx4 type; static constexpr int G = 
 // cv2 is absent from the build container: only the identity and pad-only cases are pinned.
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restrict__ src, const ImgGeom* __restrict__ geom,
-                                                        uint8_t* __restrict__ dst, int S) {
+                                                        uint8_t* __restrict__ dst, int SH, int SW) {
   const int n = blockIdx.y;
   const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= S * S) return;
-  const int oy = idx / S, ox = idx - oy * S;
+  if (idx >= SH * SW) return;
+  const int oy = idx / SW, ox = idx - oy * SW;
   const ImgGeom gm = geom[n];
-  uint8_t* o = dst + ((long)n * S * S + idx) * 3;
+  uint8_t* o = dst + ((long)n * SH * SW + idx) * 3;
   const int dy = oy - gm.top, dx = ox - gm.left;
   if (dy < 0 || dy >= gm.new_h || dx < 0 || dx >= gm.new_w) {
     o[0] = 114; o[1] = 114; o[2] = 114;
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restric
 #define LB_TH 8
 #define LB_TW 128
 __global__ __launch_bounds__(256) void letterbox_tiled_kernel(const uint8_t* __restrict__ src, const ImgGeom* __restrict__ geom,
-                                                              uint8_t* __restrict__ dst, int S, int row_cap) {
+                                                              uint8_t* __restrict__ dst, int SH, int SW, int row_cap) {
   extern __shared__ __attribute__((aligned(16))) uint8_t band[];   // [2 * LB_TH][row_cap]
   __shared__ int s_shift[2 * LB_TH];                                // byte index of source byte b0 inside an LDS row
   const int n = blockIdx.z, tid = threadIdx.x;
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void letterbox_tiled_kernel(const uint8_t* __r
   const uint8_t* im = src + gm.src_off;
   const bool resize = !(gm.new_w == gm.w && gm.new_h == gm.h);
   // columns of the resized image this tile covers, and the source byte span [b0, b1) they read
-  const int dxa = max(ox0 - gm.left, 0), dxb = min(min(ox0 + LB_TW, S) - gm.left, gm.new_w);   // [dxa, dxb)
+  const int dxa = max(ox0 - gm.left, 0), dxb = min(min(ox0 + LB_TW, SW) - gm.left, gm.new_w);   // [dxa, dxb)
   int b0 = 0, b1 = 0;
   if (dxa < dxb) {
     int sa, sb, t0, t1;
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void letterbox_tiled_kernel(const uint8_t* __r
   __syncthreads();
   // ---- resample: thread = (row j, four adjacent columns)
   const int j = tid >> 5, ox = ox0 + 4 * (tid & 31), oy = oy0 + j;
-  if (oy >= S || ox >= S) return;
+  if (oy >= SH || ox >= SW) return;
   const int dy = oy - gm.top;
   const bool rowin = dy >= 0 && dy < gm.new_h;
   int ay0 = 2048, ay1 = 0;
@@ -156,15 +156,16 @@ __global__ __launch_bounds__(256) void letterbox_tiled_kernel(const uint8_t* __r
       out[b >> 2] |= px[c] << (8 * (b & 3));
     }
   }
-  uint32_t* o = reinterpret_cast<uint32_t*>(dst + ((long)n * S * S + (long)oy * S + ox) * 3);   // 12-byte groups: 4-byte aligned (S % 4 == 0)
+  uint32_t* o = reinterpret_cast<uint32_t*>(dst + ((long)n * SH * SW + (long)oy * SW + ox) * 3);   // 12-byte groups: 4-byte aligned (SW % 4 == 0)
   o[0] = out[0]; o[1] = out[1]; o[2] = out[2];
 }
 
 // host_geoms (optional, the B geometries): lets the launcher size the tiled kernel's LDS rows; without them, or when a source
 // row span does not fit (down-scales beyond ~10x), the per-pixel kernel runs
-void launch_letterbox(const uint8_t* src, const ImgGeom* geom, uint8_t* dst, int B, int S, hipStream_t st, const ImgGeom* host_geoms) {
+void launch_letterbox(const uint8_t* src, const ImgGeom* geom, uint8_t* dst, int B, int SH, int SW, hipStream_t st,
+                      const ImgGeom* host_geoms) {
   static const bool no_tiled = getenv("LITEPI_LB_NAIVE") != nullptr;   // A/B switch
-  if (host_geoms && !no_tiled && S % 4 == 0) {
+  if (host_geoms && !no_tiled && SW % 4 == 0) {
     int cap = 0;
     for (int i = 0; i < B; ++i) {
       const ImgGeom& g = host_geoms[i];
@@ -173,14 +174,14 @@ void launch_letterbox(const uint8_t* src, const ImgGeom* geom, uint8_t* dst, int
       cap = std::max(cap, (span + 15) & ~15);
     }
     if ((size_t)cap * 2 * LB_TH <= 64 * 1024) {
-      dim3 grid(ceil_div(S, LB_TW), ceil_div(S, LB_TH), B);
-      LP_LAUNCH(letterbox_tiled_kernel, grid, dim3(256), (size_t)cap * 2 * LB_TH, st, src, geom, dst, S, cap);
+      dim3 grid(ceil_div(SW, LB_TW), ceil_div(SH, LB_TH), B);
+      LP_LAUNCH(letterbox_tiled_kernel, grid, dim3(256), (size_t)cap * 2 * LB_TH, st, src, geom, dst, SH, SW, cap);
       LP_HIP(hipGetLastError());
       return;
     }
   }
-  dim3 grid(ceil_div(S * S, 256), B);
-  LP_LAUNCH(letterbox_kernel, grid, dim3(256), 0, st, src, geom, dst, S);
+  dim3 grid(ceil_div(SH * SW, 256), B);
+  LP_LAUNCH(letterbox_kernel, grid, dim3(256), 0, st, src, geom, dst, SH, SW);
   LP_HIP(hipGetLastError());
 }
 

@@ -8,17 +8,24 @@ namespace lp {
 
 // letterbox geometry exactly as the reference computes it in Python doubles (e2e.py:72-83);
 // Python's round() is round-half-to-even == nearbyint in the default rounding mode.
-ImgGeom make_geom(int h, int w, int S, long src_off) {
+// One side per axis (the reference's new_shape = (rows, columns)); lp_letterbox_geometry returns this function's fields.
+ImgGeom make_geom(int h, int w, int SH, int SW, long src_off) {
   ImgGeom g;
   memset(&g, 0, sizeof(g));  // padding bytes too: geometry is compared with memcmp
-  const double r = std::min((double)S / h, (double)S / w);
+  const double r = std::min((double)SH / h, (double)SW / w);
   const int nw = (int)std::nearbyint(w * r), nh = (int)std::nearbyint(h * r);
-  const double dw = (S - nw) / 2.0, dh = (S - nh) / 2.0;
+  const double dw = (SW - nw) / 2.0, dh = (SH - nh) / 2.0;
   g.src_off = src_off; g.h = h; g.w = w; g.new_w = nw; g.new_h = nh;
   g.top = (int)std::nearbyint(dh - 0.1);
   g.left = (int)std::nearbyint(dw - 0.1);
   g.ratio = (float)r; g.pad_w = (float)dw; g.pad_h = (float)dh;
   return g;
+}
+
+void check_square(const lp_handle* h, const char* what) {
+  LP_CHECK(h, LP_ERR_ARG, "null argument");
+  LP_CHECK(h->det_h() == h->det_w(), LP_ERR_STATE, "%s needs a square detector input; this handle's is %dx%d (rows x columns, lp_config::det_input_h)",
+           what, h->det_h(), h->det_w());
 }
 
 Profiler* begin_profile(lp_handle* h) {
@@ -37,12 +44,12 @@ void check_run_args(const lp_handle* h, bool pointers, int B, bool host, int min
   LP_CHECK(!host || min_area >= 0, LP_ERR_ARG, "min_area must be >= 0");
 }
 
-void enqueue_letterbox(const uint8_t* src, const ImgGeom* d_geom, uint8_t* dst, const ImgGeom* geoms, int n, int S, hipStream_t st,
+void enqueue_letterbox(const uint8_t* src, const ImgGeom* d_geom, uint8_t* dst, const ImgGeom* geoms, int n, int SH, int SW, hipStream_t st,
                        Profiler* prof) {
   if (prof) prof->begin(st);
-  launch_letterbox(src, d_geom, dst, n, S, st, geoms);
+  launch_letterbox(src, d_geom, dst, n, SH, SW, st, geoms);
   if (prof) {
-    double bytes = (double)n * S * S * 3;
+    double bytes = (double)n * SH * SW * 3;
     for (int i = 0; i < n; ++i) bytes += (double)geoms[i].h * geoms[i].w * 3;
     prof->end(st, "letterbox_u8", "letterbox", 0.0, bytes);
   }
@@ -51,13 +58,13 @@ void enqueue_letterbox(const uint8_t* src, const ImgGeom* d_geom, uint8_t* dst, 
 // detector (+ optional letterbox) on images resident at src with geometry already uploaded
 void enqueue_detect(lp_handle* h, const uint8_t* src, const std::vector<ImgGeom>& geoms, int B, float conf, float* out0,
                     Profiler* prof) {
-  const int S = h->cfg.det_input;
+  const int SH = h->det_h(), SW = h->det_w();
   bool identity = true;
   for (int i = 0; i < B; ++i)
-    identity = identity && geoms[i].h == S && geoms[i].w == S && geoms[i].src_off == (long)i * S * S * 3;
+    identity = identity && geoms[i].h == SH && geoms[i].w == SW && geoms[i].src_off == (long)i * SH * SW * 3;
   const uint8_t* img = src;
   if (!identity) {
-    enqueue_letterbox(src, h->d_geom.as<ImgGeom>(), h->d_lb.as<uint8_t>(), geoms.data(), B, S, h->stream, prof);
+    enqueue_letterbox(src, h->d_geom.as<ImgGeom>(), h->d_lb.as<uint8_t>(), geoms.data(), B, SH, SW, h->stream, prof);
     img = h->d_lb.as<uint8_t>();
   }
   h->det->forward(img, B, h->d_geom.as<ImgGeom>(), conf, out0, h->d_cand.as<Cand>(), h->d_cand_count.as<int>(), h->stream, prof);
@@ -173,7 +180,7 @@ std::vector<ImgGeom> upload_images(lp_handle* h, const uint8_t* const* imgs, con
   size_t bgr_total = 0, total = 0;
   for (int i = 0; i < B; ++i) {
     LP_CHECK(imgs[i] && hs[i] > 0 && ws[i] > 0, LP_ERR_ARG, "image %d is empty", i);
-    g[i] = make_geom(hs[i], ws[i], h->cfg.det_input, (long)bgr_total);
+    g[i] = make_geom(hs[i], ws[i], h->det_h(), h->det_w(), (long)bgr_total);
     bgr_total = align16(bgr_total + (size_t)hs[i] * ws[i] * 3);
     if (nv) {
       const FrameLayout L = frame_layout(hf, hs[i], ws[i]);
@@ -304,12 +311,12 @@ int lp_detect_raw(lp_handle* h, const uint8_t* bgr, int B, float* out0) {
   LP_CHECK(h->det && h->det->loaded(), LP_ERR_STATE, "detector not loaded");
   LP_CHECK(B >= 1 && B <= h->cfg.max_batch, LP_ERR_ARG, "batch %d outside 1..%d", B, h->cfg.max_batch);
   LP_HIP(hipSetDevice(h->cfg.device));
-  const int S = h->cfg.det_input;
-  const size_t bytes = (size_t)B * S * S * 3;
+  const int SH = h->det_h(), SW = h->det_w();
+  const size_t bytes = (size_t)B * SH * SW * 3;
   h->ensure_src(bytes);
   LP_HIP(hipMemcpyAsync(h->d_src.p, bgr, bytes, hipMemcpyHostToDevice, h->stream));
   std::vector<ImgGeom> g(B);
-  for (int i = 0; i < B; ++i) g[i] = make_geom(S, S, S, (long)i * S * S * 3);
+  for (int i = 0; i < B; ++i) g[i] = make_geom(SH, SW, SH, SW, (long)i * SH * SW * 3);
   h->upload_geom(g);
   Profiler* prof = begin_profile(h);
   LP_HIP(hipMemsetAsync(h->d_cand_count.p, 0, (size_t)h->cfg.max_batch * 4, h->stream));
@@ -376,7 +383,7 @@ int lp_run_batch_device(lp_handle* h, const void* dev_imgs, int B, int H, int W,
   CscPlan csc;
   if (nv) csc = device_csc(h, dev_imgs, B, H, W, g);
   else
-    for (int i = 0; i < B; ++i) g[i] = make_geom(H, W, h->cfg.det_input, (long)i * H * W * 3);
+    for (int i = 0; i < B; ++i) g[i] = make_geom(H, W, h->det_h(), h->det_w(), (long)i * H * W * 3);
   h->upload_geom(g);
   Profiler* prof = begin_profile(h);
   const uint8_t* src = nv ? h->d_src.as<uint8_t>() : static_cast<const uint8_t*>(dev_imgs);

@@ -99,7 +99,7 @@ CscPlan device_csc(lp_handle* h, const void* dev_imgs, int B, int H, int W, std:
   const size_t fb = align16((size_t)H * W * 3);
   std::vector<CscFrame> tab(B);
   for (int i = 0; i < B; ++i) {
-    g[i] = make_geom(H, W, h->cfg.det_input, (long)(i * fb));
+    g[i] = make_geom(H, W, h->det_h(), h->det_w(), (long)(i * fb));
     tab[i] = CscFrame{(long)(i * L.stride), (long)L.uv_off, (long)(i * fb), H, W, L.pitch, 0};
   }
   h->ensure_src(fb * B);

@@ -54,6 +54,27 @@ void gather_one_frame(lp_handle* h, const uint8_t* img, const ImgGeom& frame, si
     LP_HIP(hipMemcpy(out + (size_t)k * vb, d_out.as<uint8_t>() + (size_t)lay.vslot[k] * vb, vb, hipMemcpyDeviceToHost));
 }
 
+// the letterbox of one host image on buffers of its own; kernel: 0 = the launcher's choice (the tiled kernel where its LDS rows
+// fit), 1 = the per-pixel kernel
+void test_letterbox(lp_handle* h, const uint8_t* img, int H, int W, uint8_t* out, float* ratio, float* pad_w, float* pad_h, int kernel) {
+  LP_CHECK(h && img && out && H > 0 && W > 0, LP_ERR_ARG, "bad argument");
+  LP_HIP(hipSetDevice(h->cfg.device));
+  const int SH = h->det_h(), SW = h->det_w();
+  ImgGeom g = make_geom(H, W, SH, SW, 0);
+  DevBuf d_src, d_geom, d_out;
+  d_src.alloc((size_t)H * W * 3);
+  LP_HIP(hipMemcpy(d_src.p, img, (size_t)H * W * 3, hipMemcpyHostToDevice));
+  d_geom.alloc(sizeof(g));
+  LP_HIP(hipMemcpy(d_geom.p, &g, sizeof(g), hipMemcpyHostToDevice));
+  d_out.alloc((size_t)SH * SW * 3);
+  launch_letterbox(d_src.as<uint8_t>(), d_geom.as<ImgGeom>(), d_out.as<uint8_t>(), 1, SH, SW, h->stream, kernel == 1 ? nullptr : &g);
+  LP_HIP(hipStreamSynchronize(h->stream));
+  LP_HIP(hipMemcpy(out, d_out.p, (size_t)SH * SW * 3, hipMemcpyDeviceToHost));
+  if (ratio) *ratio = g.ratio;
+  if (pad_w) *pad_w = g.pad_w;
+  if (pad_h) *pad_h = g.pad_h;
+}
+
 }  // namespace
 
 extern "C" {
@@ -117,9 +138,10 @@ int lp_test_tile_views(lp_handle* h, const uint8_t* img, int H, int W, const lp_
                        int* n_views) {
   LP_API_BEGIN
   LP_CHECK(h && img && n_views && H > 0 && W > 0 && byte_offset >= 0 && byte_offset < 64, LP_ERR_ARG, "bad argument");
+  check_square(h, "lp_test_tile_views");
   check_tiling(tiling, h->cfg.det_input);
   LP_HIP(hipSetDevice(h->cfg.device));
-  const std::vector<ImgGeom> fg(1, make_geom(H, W, h->cfg.det_input, byte_offset));
+  const std::vector<ImgGeom> fg(1, make_geom(H, W, h->det_h(), h->det_w(), byte_offset));
   const ViewLayout lay = view_layout(h, fg, tiled_views(h->cfg.det_input, *tiling, fg));
   *n_views = lay.V;
   LP_CHECK(!out || cap >= lay.V, LP_ERR_ARG, "%d views, room for %d", lay.V, cap);
@@ -131,8 +153,9 @@ int lp_test_view_windows(lp_handle* h, const uint8_t* img, int H, int W, const i
                          int cap) {
   LP_API_BEGIN
   LP_CHECK(h && img && out && H > 0 && W > 0 && byte_offset >= 0 && byte_offset < 64, LP_ERR_ARG, "bad argument");
+  check_square(h, "lp_test_view_windows");
   LP_HIP(hipSetDevice(h->cfg.device));
-  const std::vector<ImgGeom> fg(1, make_geom(H, W, h->cfg.det_input, byte_offset));
+  const std::vector<ImgGeom> fg(1, make_geom(H, W, h->det_h(), h->det_w(), byte_offset));
   const ViewLayout lay = view_layout(h, fg, listed_views(h, views, n_views, fg));
   LP_CHECK(cap >= lay.V, LP_ERR_ARG, "%d views, room for %d", lay.V, cap);
   // the frame is the whole allocation but for the offset in front: nothing the gather may read lies beyond it
@@ -352,22 +375,14 @@ int lp_test_roi_resize(lp_handle* h, const uint8_t* const* rois, const int* hs, 
 
 int lp_test_letterbox(lp_handle* h, const uint8_t* img, int H, int W, uint8_t* out, float* ratio, float* pad_w, float* pad_h) {
   LP_API_BEGIN
-  LP_CHECK(h && img && out && H > 0 && W > 0, LP_ERR_ARG, "bad argument");
-  LP_HIP(hipSetDevice(h->cfg.device));
-  const int S = h->cfg.det_input;
-  ImgGeom g = make_geom(H, W, S, 0);
-  DevBuf d_src, d_geom, d_out;
-  d_src.alloc((size_t)H * W * 3);
-  LP_HIP(hipMemcpy(d_src.p, img, (size_t)H * W * 3, hipMemcpyHostToDevice));
-  d_geom.alloc(sizeof(g));
-  LP_HIP(hipMemcpy(d_geom.p, &g, sizeof(g), hipMemcpyHostToDevice));
-  d_out.alloc((size_t)S * S * 3);
-  launch_letterbox(d_src.as<uint8_t>(), d_geom.as<ImgGeom>(), d_out.as<uint8_t>(), 1, S, h->stream, &g);
-  LP_HIP(hipStreamSynchronize(h->stream));
-  LP_HIP(hipMemcpy(out, d_out.p, (size_t)S * S * 3, hipMemcpyDeviceToHost));
-  if (ratio) *ratio = g.ratio;
-  if (pad_w) *pad_w = g.pad_w;
-  if (pad_h) *pad_h = g.pad_h;
+  test_letterbox(h, img, H, W, out, ratio, pad_w, pad_h, 0);
+  LP_API_END
+}
+
+int lp_test_letterbox_kernel(lp_handle* h, const uint8_t* img, int H, int W, int kernel, uint8_t* out, float* ratio, float* pad_w, float* pad_h) {
+  LP_API_BEGIN
+  LP_CHECK(kernel == 0 || kernel == 1, LP_ERR_ARG, "kernel %d is not 0 (launcher's choice) or 1 (per pixel)", kernel);
+  test_letterbox(h, img, H, W, out, ratio, pad_w, pad_h, kernel);
   LP_API_END
 }
 

@@ -85,7 +85,7 @@ FrameViews listed_views(const lp_handle* h, const int* views, int n_views, const
 // ---- the layout ----------------------------------------------------------------------------------------------------------------
 // geometry of the window {x, y, w, h} of a frame: make_geom of a h x w image, the pads moved by the window's origin
 static ImgGeom window_geom(const ImgGeom& frame, const std::array<int, 4>& win, int S) {
-  ImgGeom g = make_geom(win[3], win[2], S, frame.src_off);
+  ImgGeom g = make_geom(win[3], win[2], S, S, frame.src_off);
   const double r = std::min((double)S / win[3], (double)S / win[2]);
   const double dw = (S - g.new_w) / 2.0, dh = (S - g.new_h) / 2.0;
   g.h = frame.h; g.w = frame.w;   // boxes are clipped to the frame, ROIs are cut from it
@@ -171,7 +171,7 @@ void upload_tiles(lp_handle* h, const std::vector<ImgGeom>& fg, const ViewLayout
 void enqueue_view_gather(const uint8_t* src, const ImgGeom* d_geom, const ViewWin* d_wins, uint8_t* dst, const ViewLayout& lay, int S,
                          hipStream_t st, Profiler* prof) {
   const int nwin = (int)lay.wins.size();
-  if (lay.L > 0) enqueue_letterbox(src, d_geom, dst, lay.vgeom.data(), lay.L, S, st, prof);
+  if (lay.L > 0) enqueue_letterbox(src, d_geom, dst, lay.vgeom.data(), lay.L, S, S, st, prof);
   if (lay.C > 0) {
     if (prof) prof->begin(st);
     launch_crop_views(src, d_geom, dst, lay.L, lay.C, S, st);
@@ -237,7 +237,7 @@ static void run_views_host(lp_handle* h, const uint8_t* const* imgs, const int* 
   for (int i = 0; i < B; ++i) LP_CHECK(hs[i] > 0 && ws[i] > 0, LP_ERR_ARG, "frame %d is empty", i);
   LP_HIP(hipSetDevice(h->cfg.device));
   std::vector<ImgGeom> fg(B);
-  for (int i = 0; i < B; ++i) fg[i] = make_geom(hs[i], ws[i], h->cfg.det_input, 0);
+  for (int i = 0; i < B; ++i) fg[i] = make_geom(hs[i], ws[i], h->det_h(), h->det_w(), 0);
   // The layout is built twice, here and behind the upload: this one validates the call before anything is uploaded, from
   // geometry without the frames' offsets in d_src, which upload_images assigns.
   (void)layout_of(fg);
@@ -266,7 +266,7 @@ static void run_views_device(lp_handle* h, const void* dev_imgs, int B, int H, i
   LP_CHECK(H > 0 && W > 0, LP_ERR_ARG, "frames of %dx%d", W, H);
   LP_HIP(hipSetDevice(h->cfg.device));
   std::vector<ImgGeom> fg(B);
-  for (int i = 0; i < B; ++i) fg[i] = make_geom(H, W, h->cfg.det_input, (long)i * H * W * 3);
+  for (int i = 0; i < B; ++i) fg[i] = make_geom(H, W, h->det_h(), h->det_w(), (long)i * H * W * 3);
   ViewLayout lay = layout_of(fg);
   const bool nv = h->nv12();
   CscPlan csc;
@@ -317,7 +317,7 @@ int lp_view_geometry(int det_input, int H, int W, const int* view, float* ratio,
                      int* top, int* left) {
   LP_API_BEGIN
   LP_CHECK(view && det_input >= 1 && H > 0 && W > 0, LP_ERR_ARG, "bad argument (det_input %d, frame %dx%d)", det_input, H, W);
-  const ImgGeom frame = make_geom(H, W, det_input, 0);
+  const ImgGeom frame = make_geom(H, W, det_input, det_input, 0);
   const ImgGeom g = window_geom(frame, view_window(view, H, W, 0), det_input);
   if (ratio) *ratio = g.ratio;
   if (pad_w) *pad_w = g.pad_w;
@@ -329,27 +329,26 @@ int lp_view_geometry(int det_input, int H, int W, const int* view, float* ratio,
   LP_API_END
 }
 
-// the reference's letterbox(img, (det_h, det_w)) in Python doubles (e2e.py:72-83): make_geom's arithmetic with one side per axis
+// the reference's letterbox(img, (det_h, det_w)) in Python doubles (e2e.py:72-83): make_geom itself, what a handle of that input uses
 int lp_letterbox_geometry(int det_h, int det_w, int H, int W, float* ratio, float* pad_w, float* pad_h, int* new_w, int* new_h, int* top,
                           int* left) {
   LP_API_BEGIN
   LP_CHECK(det_h > 0 && det_w > 0 && H > 0 && W > 0, LP_ERR_ARG, "bad argument (detector input %dx%d, image %dx%d; rows x columns)", det_h, det_w, H, W);
-  const double r = std::min((double)det_h / H, (double)det_w / W);
-  const int nw = (int)std::nearbyint(W * r), nh = (int)std::nearbyint(H * r);
-  const double dw = (det_w - nw) / 2.0, dh = (det_h - nh) / 2.0;
-  if (ratio) *ratio = (float)r;
-  if (pad_w) *pad_w = (float)dw;
-  if (pad_h) *pad_h = (float)dh;
-  if (new_w) *new_w = nw;
-  if (new_h) *new_h = nh;
-  if (top) *top = (int)std::nearbyint(dh - 0.1);
-  if (left) *left = (int)std::nearbyint(dw - 0.1);
+  const ImgGeom g = make_geom(H, W, det_h, det_w, 0);
+  if (ratio) *ratio = g.ratio;
+  if (pad_w) *pad_w = g.pad_w;
+  if (pad_h) *pad_h = g.pad_h;
+  if (new_w) *new_w = g.new_w;
+  if (new_h) *new_h = g.new_h;
+  if (top) *top = g.top;
+  if (left) *left = g.left;
   LP_API_END
 }
 
 int lp_run_tiled(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, const lp_tiling* tiling, float conf,
                  float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing) {
   LP_API_BEGIN
+  check_square(h, "lp_run_tiled");
   run_views_host(h, imgs, hs, ws, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, GK_TILED_FRONT, GK_TILED_ROI,
                  GK_TILED_CLS, [&](const std::vector<ImgGeom>& fg) {
                    check_tiling(tiling, h->cfg.det_input);
@@ -361,6 +360,7 @@ int lp_run_tiled(lp_handle* h, const uint8_t* const* imgs, const int* hs, const 
 int lp_run_tiled_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, const lp_tiling* tiling, float conf, float iou,
                         int min_area, void* dev_dets, void* dev_counts) {
   LP_API_BEGIN
+  check_square(h, "lp_run_tiled_device");
   run_views_device(h, dev_imgs, B, H, W, conf, iou, min_area, dev_dets, dev_counts, GK_TILED_DEVICE, [&](const std::vector<ImgGeom>& fg) {
     check_tiling(tiling, h->cfg.det_input);
     return view_layout(h, fg, tiled_views(h->cfg.det_input, *tiling, fg));
@@ -371,6 +371,7 @@ int lp_run_tiled_device(lp_handle* h, const void* dev_imgs, int B, int H, int W,
 int lp_run_views(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, const int* views, int n_views, float conf,
                  float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing) {
   LP_API_BEGIN
+  check_square(h, "lp_run_views");
   run_views_host(h, imgs, hs, ws, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, GK_VIEWS_FRONT, GK_VIEWS_ROI,
                  GK_VIEWS_CLS, [&](const std::vector<ImgGeom>& fg) { return view_layout(h, fg, listed_views(h, views, n_views, fg)); });
   LP_API_END
@@ -379,6 +380,7 @@ int lp_run_views(lp_handle* h, const uint8_t* const* imgs, const int* hs, const 
 int lp_run_views_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, const int* views, int n_views, float conf, float iou,
                         int min_area, void* dev_dets, void* dev_counts) {
   LP_API_BEGIN
+  check_square(h, "lp_run_views_device");
   run_views_device(h, dev_imgs, B, H, W, conf, iou, min_area, dev_dets, dev_counts, GK_VIEWS_DEVICE,
                    [&](const std::vector<ImgGeom>& fg) { return view_layout(h, fg, listed_views(h, views, n_views, fg)); });
   LP_API_END

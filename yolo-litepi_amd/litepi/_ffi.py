@@ -19,7 +19,7 @@ LP_OK, LP_ERR_ARG, LP_ERR_IO, LP_ERR_GRAPH, LP_ERR_HIP, LP_ERR_STATE, LP_ERR_NOD
 class LpConfig(C.Structure):
     _fields_ = [("device", C.c_int), ("precision", C.c_int), ("max_batch", C.c_int), ("max_det", C.c_int),
                 ("num_classes", C.c_int), ("det_input", C.c_int), ("cls_input", C.c_int), ("max_rois", C.c_int),
-                ("conv_impl", C.c_int), ("numerics", C.c_int), ("cls_arch", C.c_int), ("reserved", C.c_int * 5)]
+                ("conv_impl", C.c_int), ("numerics", C.c_int), ("cls_arch", C.c_int), ("det_input_h", C.c_int), ("reserved", C.c_int * 4)]
 
 
 class LpDet(C.Structure):
@@ -118,7 +118,7 @@ SYMBOLS = [
     "lp_inventory", "lp_inventory_flush", "lp_inventory_drain", "lp_inventory_open", "lp_test_set_rois", "lp_debug_rois",
     "lp_focus_default_config", "lp_focus_config_check", "lp_focus_create", "lp_focus_destroy", "lp_focus_plan", "lp_focus_state",
     "lp_run_focus_device", "lp_run_focus",
-    "lp_letterbox_geometry",
+    "lp_letterbox_geometry", "lp_test_letterbox_kernel",
 ]
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
 
@@ -164,6 +164,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_test_nms_boxes.argtypes = [vp, fp, fp, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp, ip, ip, ip]
     lib.lp_test_roi_resize.argtypes = [vp, u8pp, ip, ip, C.c_int, vp]
     lib.lp_test_letterbox.argtypes = [vp, vp, C.c_int, C.c_int, vp, fp, fp, fp]
+    lib.lp_test_letterbox_kernel.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, fp, fp, fp]
     lib.lp_roi_overflow.argtypes = [vp, ip, ip]
     lib.lp_comm_unique_id.argtypes = [vp]
     lib.lp_comm_init.argtypes = [vp, vp, C.c_int, C.c_int]

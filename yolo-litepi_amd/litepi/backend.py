@@ -196,20 +196,39 @@ def focus_config_check(cfg: Optional[_ffi.LpFocusConfig], det_input: int) -> int
     return lib.lp_focus_config_check(C.byref(cfg) if cfg is not None else None, int(det_input))
 
 
+def det_input_hw(size) -> Tuple[int, int]:
+    """A detector input size as (rows, columns): an int is a square, a pair is the reference's letterbox shape (rows, columns)."""
+    if isinstance(size, (tuple, list, np.ndarray)):
+        if len(size) != 2:
+            raise ValueError(f"a detector input size is an int or (rows, columns), got {size!r}")
+        return int(size[0]), int(size[1])
+    return int(size), int(size)
+
+
+def _square_only(size, what: str) -> None:
+    h, w = det_input_hw(size)
+    if h != w:
+        raise ValueError(f"{what} needs a square detector input; got {h}x{w} (rows x columns): frame views on a rectangular "
+                         f"input are not supported")
+
+
 class Engine:
     """One GPU pipeline handle (not thread-safe; one per GPU)."""
 
     def __init__(self, precision: str = "fp16", max_batch: int = 1, max_det: int = 300, num_classes: int = 58,
-                 det_input: int = 640, cls_input: int = 64, device: int = 0, max_rois: int = 0, conv_impl: int = 0,
+                 det_input=640, cls_input: int = 64, device: int = 0, max_rois: int = 0, conv_impl: int = 0,
                  numerics: str = "e2e", cls_arch: str = "shufflenetv2"):
         """numerics: "e2e" = HybridPipeline of e2e.py (default), "e2e_optimize" = HybridPipelineOptimized of e2e_optimize.py
         (other ROI clip rule, cv2-linear ROI resize).  cls_arch: "shufflenetv2" | "resnet18" | "mobilenetv2" | "efficientnet"
-        (the four choices of build_classifier, e2e.py:320-333)."""
+        (the four choices of build_classifier, e2e.py:320-333).  det_input: an int (square) or (rows, columns), both multiples of
+        32 (lp_config::det_input_h); the frame-view calls (tiled, views, focus) need a square."""
         self.lib = _ffi.load_library()
         cfg = LpConfig()
         self.lib.lp_default_config(C.byref(cfg))
+        self.det_hw = det_input_hw(det_input)
         cfg.device, cfg.precision, cfg.max_batch, cfg.max_det = device, _PREC[precision], max_batch, max_det
-        cfg.num_classes, cfg.det_input, cfg.cls_input, cfg.max_rois, cfg.conv_impl = num_classes, det_input, cls_input, max_rois, conv_impl
+        cfg.num_classes, cfg.det_input, cfg.cls_input, cfg.max_rois, cfg.conv_impl = num_classes, self.det_hw[1], cls_input, max_rois, conv_impl
+        cfg.det_input_h = self.det_hw[0] if isinstance(det_input, (tuple, list, np.ndarray)) else 0   # (640, 640) = 640: the same handle
         cfg.numerics = {"e2e": 0, "e2e_optimize": 1}[numerics]
         cfg.cls_arch = {"shufflenetv2": 0, "resnet18": 1, "mobilenetv2": 2, "efficientnet": 3}[cls_arch]
         self.numerics, self.cls_arch = numerics, cls_arch
@@ -260,13 +279,13 @@ class Engine:
 
     # ---- inference ---------------------------------------------------------------------------
     def detect_raw(self, bgr: np.ndarray) -> np.ndarray:
-        """uint8 BGR [B,S,S,3] -> fp32 out0 [B,4+nc,A] (parity hook for ex.extract('out0'))."""
+        """uint8 BGR [B,SH,SW,3] -> fp32 out0 [B,4+nc,A] (parity hook for ex.extract('out0'))."""
         a = np.ascontiguousarray(bgr, dtype=np.uint8)
-        S = self.cfg.det_input
+        SH, SW = self.det_hw
         if a.ndim == 3:
             a = a[None]
-        if a.shape[1:] != (S, S, 3):
-            raise ValueError(f"detect_raw expects [B,{S},{S},3], got {a.shape}")
+        if a.shape[1:] != (SH, SW, 3):
+            raise ValueError(f"detect_raw expects [B,{SH},{SW},3], got {a.shape}")
         out = np.empty((a.shape[0], 4 + self.det_classes, self.num_anchors), np.float32)
         check(self.lib, self.lib.lp_detect_raw(self._h, a.ctypes.data, a.shape[0], out.ctypes.data))
         return out
@@ -718,13 +737,14 @@ class Engine:
         check(self.lib, self.lib.lp_test_roi_resize(self._h, ptrs, hs, ws, len(imgs), out.ctypes.data))
         return out
 
-    def test_letterbox(self, img: np.ndarray):
+    def test_letterbox(self, img: np.ndarray, per_pixel: bool = False):
+        """The letterbox alone -> (uint8 [SH, SW, 3], ratio, (pad_w, pad_h)); per_pixel: the per-pixel kernel instead of the
+        launcher's choice (the tiled kernel where its LDS rows fit)."""
         a = _as_bgr(img)
-        S = self.cfg.det_input
-        out = np.empty((S, S, 3), np.uint8)
+        out = np.empty((*self.det_hw, 3), np.uint8)
         r, pw, ph = C.c_float(), C.c_float(), C.c_float()
-        check(self.lib, self.lib.lp_test_letterbox(self._h, a.ctypes.data, a.shape[0], a.shape[1], out.ctypes.data,
-                                                   C.byref(r), C.byref(pw), C.byref(ph)))
+        check(self.lib, self.lib.lp_test_letterbox_kernel(self._h, a.ctypes.data, a.shape[0], a.shape[1], int(bool(per_pixel)),
+                                                          out.ctypes.data, C.byref(r), C.byref(pw), C.byref(ph)))
         return out, r.value, (pw.value, ph.value)
 
 
@@ -786,7 +806,7 @@ class NCNNDetector:
     """e2e.py:195-316.  ``use_gpu``/``num_threads`` are accepted and ignored (the detector always
     runs on the HIP device)."""
 
-    def __init__(self, param_path: str, bin_path: str, input_size: int = 640, use_gpu: bool = False, num_threads: int = 4,
+    def __init__(self, param_path: str, bin_path: str, input_size=640, use_gpu: bool = False, num_threads: int = 4,
                  input_name: str = "in0", output_name: str = "out0", *, precision: str = "fp16", max_batch: int = 1,
                  max_det: int = 300, device: int = 0, pixel_format: str = "bgr", csc_matrix: str = "bt601",
                  _engine: Optional[Engine] = None):
@@ -805,7 +825,7 @@ class NCNNDetector:
         except _ffi.LitepiError as e:  # e2e.py:213-216 raises RuntimeError on load failure
             raise RuntimeError(str(e)) from e
         print(f"  Device: HIP:{self.engine.cfg.device} ({self.engine.precision})")
-        print(f"  Input size: {input_size}x{input_size}")
+        print("  Input size: {}x{}".format(*reversed(det_input_hw(input_size))))
 
     def detect_batch(self, images: Sequence[np.ndarray], conf_threshold: float = 0.5, iou_threshold: float = 0.45):
         try:
@@ -1017,7 +1037,7 @@ class HybridPipeline:
     device handle, so detections never leave the GPU between the two stages."""
 
     def __init__(self, detector_param: str, detector_bin: str, classifier_path: str, classifier_arch: str,
-                 num_classes: int = 58, det_input_size: int = 640, cls_input_size: int = 64, use_gpu_detector: bool = False,
+                 num_classes: int = 58, det_input_size=640, cls_input_size: int = 64, use_gpu_detector: bool = False,
                  detector_threads: int = 4, classifier_device: str = "cpu", batch_size: int = 8, *, precision: str = "fp16",
                  max_batch: int = 1, max_det: int = 300, device: int = 0, max_rois: int = 0, numerics: str = "e2e",
                  tile_overlap: Optional[int] = None, tile_full_frame: bool = True, pixel_format: str = "bgr",
@@ -1041,7 +1061,12 @@ class HybridPipeline:
         focus: K = focus views (lp_run_focus): every frame is seen through the whole frame and K windows the engine's tracker
         chooses on the device, the free ones swept over a window grid (focus_config: lp_focus_config's other fields).  Needs
         track and a max_batch of at least 1 + K; mutually exclusive with tile_overlap, views and view_tile.  The windows of
-        the last run_batch are in last_focus_views."""
+        the last run_batch are in last_focus_views.
+        det_input_size: an int (square) or (rows, columns), e.g. (384, 640) for 16:9 video; tile_overlap, views, view_tile and
+        focus need a square."""
+        for name, value in (("tile_overlap", tile_overlap), ("views", views), ("view_tile", view_tile), ("focus", focus)):
+            if value is not None:
+                _square_only(det_input_size, name)
         self.tile_overlap, self.tile_full_frame = tile_overlap, bool(tile_full_frame)
         if sum(x is not None for x in (tile_overlap, views, view_tile)) > 1:
             raise ValueError("tile_overlap, views and view_tile are mutually exclusive")

@@ -51,7 +51,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--benchmark_conf", type=float, default=0.25)
     p.add_argument("--min_area", type=int, default=50)
     p.add_argument("--iou_threshold", type=float, default=0.45)
-    p.add_argument("--det_input_size", type=int, default=640)
+    p.add_argument("--det_input_size", type=det_input_size_arg, default=640,
+                   help="detector input: an integer (square) or ROWSxCOLUMNS, e.g. 384x640 for 16:9 video; both multiples of 32")
     p.add_argument("--cls_input_size", type=int, default=64)
     p.add_argument("--detector_threads", type=int, default=4, help="ignored (NCNN threads in the reference)")
     p.add_argument("--batch_size", type=int, default=8, help="kept for compatibility: all ROIs of a call are classified together")
@@ -124,9 +125,22 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-def num_anchors(det_input_size: int) -> int:
+def det_input_size_arg(text):
+    """--det_input_size: "640" -> 640, "384x640" -> (384, 640) (rows x columns)."""
+    t = str(text).strip().lower()
+    try:
+        if "x" in t:
+            rows, cols = t.split("x")
+            return int(rows), int(cols)
+        return int(t)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--det_input_size takes an integer or ROWSxCOLUMNS, got {text!r}") from None
+
+
+def num_anchors(det_input_size) -> int:
     """Anchor points of the Detect head on a square input: one per cell of the stride-8/16/32 grids (8400 at 640)."""
-    return sum(((det_input_size + s - 1) // s) ** 2 for s in (8, 16, 32))
+    h, w = (det_input_size if isinstance(det_input_size, (tuple, list)) else (det_input_size, det_input_size))
+    return sum(((int(h) + s - 1) // s) * ((int(w) + s - 1) // s) for s in (8, 16, 32))
 
 
 def load_class_names(path: str) -> List[str]:
@@ -383,6 +397,10 @@ def check_frame_args(args) -> None:
     modes = [n for n in ("tile_overlap", "view_tile", "views", "focus") if getattr(args, n, None) is not None]
     if len(modes) > 1:
         raise SystemExit("--" + ", --".join(modes) + " exclude each other: one way of looking at a frame per run")
+    size = getattr(args, "det_input_size", 640)
+    if modes and isinstance(size, tuple) and size[0] != size[1]:
+        raise SystemExit(f"--{modes[0]} needs a square --det_input_size (it is {size[0]}x{size[1]}): frame views on a rectangular "
+                         f"detector input are not supported")
     if getattr(args, "views", None) is not None:
         parse_views(args.views)
     if getattr(args, "focus", None) is not None:
