@@ -19,12 +19,16 @@ or a bug: name it from the kernel's code, do not widen a cap.
 Cases: v1 and v2 (export_detector(preset, seed=77, cls_bias=-2.0)) at 640 x 640 -- the smallest size at which the configurations
 run on more than one tile (80 x 80: 5 x 4 tiles of 16 x 20; 40 x 40: 2 x 2 tiles or 4 x 2 of 10 x 20; 20 x 20: two half-image
 tiles) and at which the whole-image configurations and sppf<192,96,192> exist --, an fp16 handle of capacity 4 holding 3 images,
-all images compared; the planner's switches that reach the other configurations (CASES).  LITEPI_NO_S2TAIL is read once per
-process: that case runs in one child process.  One further test per preset runs the bisect mode (LITEPI_C2F_STORE_ALL=1): out0
+all images compared; the planner's switches that reach the other configurations (CASES).  Every plan-time switch of
+c2f_kernels.hip, LITEPI_NO_S2TAIL among them, is read per load (PlanSwitches, detector_plan.cpp):
+test_switches_are_read_per_load pins that with three loads in this process; the c2f<16,2,32> case keeps the child process it was
+written with.  test_no_s2c_alone_on_v2 pins the plan of LITEPI_NO_S2C=1 alone on v2, whose load once claimed cv1 as the tail of a
+launch the switch forbids.  One further test per preset runs the bisect mode (LITEPI_C2F_STORE_ALL=1): out0
 byte-equal to the production run, and every intermediate the modules then store within the same two caps.
 
 MEAN_CAP (tests/c2f_ref.py) = 0.5 comes from the CPU stand-in (test_c2f_ref_cpu.py), not from the figures below.  MI355X, this
-module as committed, over all 87 launch rows of the eight tests: largest max d / max e 1.761 (c2f<96,1,288> behind
+module as committed, over all 95 launch rows of the ten tests (87 of the first eight, unchanged by the move of the switches into the
+planner, and the 8 of test_no_s2c_alone_on_v2: at most 1.387 and 0.1561 there): largest max d / max e 1.761 (c2f<96,1,288> behind
 LITEPI_NO_C2F_XCV1, cap 2), largest mean d / mean e 0.4345 (c2f<64,1,s2+128,sppf> behind LITEPI_C2F_XCV1; the stand-in measures
 0.41 on that span: one flipped rounding of s spreads through three 5 x 5 pools), smallest max e 1.84e-3 (floor 4.9e-4).  Bisect
 mode, 49 intermediates: largest max d / max e 1.098 and mean d / mean e 0.216 (SPPF's s of c2f<64,1,s2+128,sppf>); out0 byte-equal.
@@ -237,7 +241,32 @@ def test_bisect_mode_stores_what_the_modules_compute(preset, tmp_path_factory, m
         assert all(isinstance(blobs.get(b), np.ndarray) for b in ("75", "78", "79", "87", "90", "92", "95", "98", "101")), sorted(blobs)
 
 
-# A fresh process for the switch that is read once per process: out0, the launches and every blob of the table the plan hands out -> .npz
+def test_switches_are_read_per_load(tmp_path_factory, monkeypatch):
+    """Three loads of v1 in this process -- no switch, LITEPI_NO_S2TAIL=1, no switch: the stride-2 launch with its 1x1 tail is in the
+    first and third profiles and not in the second, and the first and third out0 are equal byte for byte.  (The switch used to be a
+    static of c2f_kernels.hip, latched by the first load of the process.)"""
+    m = _model("v1", tmp_path_factory)
+    runs = [_run(m, env, monkeypatch) for env in ({}, {"LITEPI_NO_S2TAIL": "1"}, {})]
+    has_tail = ["s2conv+1x1<16,32>_f16" in [n for n, _ in launches] for _, launches, _ in runs]
+    assert has_tail == [True, False, True], [[n for n, _ in launches if _is_ours(n)] for _, launches, _ in runs]
+    assert runs[0][0].tobytes() == runs[2][0].tobytes(), "out0 of the two loads without a switch differ"
+
+
+def test_no_s2c_alone_on_v2(tmp_path_factory, monkeypatch):
+    """LITEPI_NO_S2C=1 and no other switch on v2: the load succeeds, no stride-2 launch of c2f_kernels.hip is planned -- so cv1 of
+    the 80 x 80 module is not claimed as the tail of one either (the planner once claimed it without asking this switch and failed
+    the load in ConvLayer::attach_tail) --, and every remaining c2f< / sppf< launch stays within the two caps."""
+    m = _model("v2", tmp_path_factory)
+    out0, launches, blobs = _run(m, {"LITEPI_NO_S2C": "1"}, monkeypatch)
+    names = [n for n, _ in launches]
+    print("LITEPI_NO_S2C=1 v2:", [n for n in names if _is_ours(n)])
+    assert not [n for n in names if n.startswith("s2conv")], names
+    assert [n for n in names if n.startswith("c2f<")], names   # (the checks below are not vacuous)
+    _check(m, "v2-no_s2c", out0, launches, blobs, {})
+
+
+# A fresh process for the case that was written when LITEPI_NO_S2TAIL was latched per process (it is read per load now; the case
+# stays as it was): out0, the launches and every blob of the table the plan hands out -> .npz
 _CHILD = r"""
 import sys
 import numpy as np
@@ -266,8 +295,8 @@ np.savez(out, **res)
 
 
 def test_bb80_module_equals_float64_reference(tmp_path_factory, tmp_path):
-    """c2f<16,2,32>, the opt-in n = 2 module on the 80 x 80 map: LITEPI_C2F_BB80=1 enables it and LITEPI_NO_S2TAIL=1 (read once per
-    process) keeps its cv1 out of the stride-2 launch in front."""
+    """c2f<16,2,32>, the opt-in n = 2 module on the 80 x 80 map: LITEPI_C2F_BB80=1 enables it and LITEPI_NO_S2TAIL=1 keeps its cv1
+    out of the stride-2 launch in front."""
     preset, switches, required = CHILD_CASE
     m = _model(preset, tmp_path_factory)
     env = {k: v for k, v in os.environ.items() if k not in SWITCHES}

@@ -72,7 +72,10 @@ struct C2fLayer {
     const std::vector<float>*sp1 = nullptr, *sp1_b = nullptr;             // [C][COUT]
     const std::vector<float>*sp2 = nullptr, *sp2_b = nullptr;             // [COUT][4C]
   };
+  // supported / kernel_name(shape): pure functions of the shape.  Which configurations a load may use besides (LITEPI_C2F_BB80,
+  // LITEPI_C2F_SKIP) is the planner's business (Planner::c2f_ok)
   static bool supported(const C2fShape& s, int h, int w);
+  static std::string kernel_name(const C2fShape& s);   // "c2f<..>", or empty: no configuration for this shape
   bool cv2_from_lds() const;   // cv2 takes the last y segments from the LDS planes: they never reach the concat buffer
   void build(const C2fShape& s, int h, int w, const Src& src);
   struct IO {
@@ -81,23 +84,25 @@ struct C2fLayer {
     View cat2, out2;             // MODE == 2
   };
   void launch(const IO& io, int N, hipStream_t st) const;
-  std::string kernel_name() const;
+  std::string kernel_name() const { return kernel_name(sh); }
 };
 
 // Stand-alone 3x3 stride-2 conv + SiLU on the c2f machinery (s2conv_kernel): weights [cout][tap][cin] over physical channels
 struct S2ConvLayer {
   int Cin = 0, Cout = 0, H = 0, W = 0;   // H, W: OUTPUT map
-  bool lds_staged = false;               // s2lds_kernel (input tile in LDS: v2's Cin 24 / 48 / 96) instead of the gather kernel
-  int ksplit = 1;                        // its passes over the input channels
   bool has_tail = false;                 // a 1x1 conv + SiLU (C2f.cv1) on the accumulators: Cout -> Cout
+  // ((Cin, Cout, has_tail) is the key of the layer's configuration: build and launch look it up in the one table of c2f_kernels.hip)
   std::string name;
   DevBuf d_w, d_b, d_w2, d_b2;
+  // pure functions of the shape; the planner adds its switches (Planner::s2c_ok, s2c_tail_ok)
   static bool supported(int cin, int cout, int hout, int wout);
   static bool tail_supported(int cin, int cout, int cout2, int hout, int wout);
+  static bool lds_staged(int cin, int cout);   // the shape's kernel stages its input tile in LDS (s2lds_kernel: what LITEPI_NO_S2LDS turns off)
   // w_tail [cout][cout] (1x1), b_tail: the fused tail, or null
   void build(int cin, int cout, int hout, int wout, const std::vector<float>& w_taps, const std::vector<float>& bias,
              const std::vector<float>* w_tail = nullptr, const std::vector<float>* b_tail = nullptr);
   void launch(const View& in, const View& out, int N, hipStream_t st) const;
+  std::string kernel_name() const;
 };
 
 // SPPF in one launch (sppf_kernel): cv1 (1x1 + SiLU) -> three cascaded 5x5 max pools -> cv2 (1x1 + SiLU) over concat(s, p1, p2, p3),
@@ -112,6 +117,7 @@ struct SppfLayer {
   void build(int cin, int c, int cout, int h, int w, const std::vector<float>& w1, const std::vector<float>& b1, const std::vector<float>& w2,
              const std::vector<float>& b2);
   void launch(const View& in, const View& out, int N, hipStream_t st) const;
+  std::string kernel_name() const;
 };
 
 }  // namespace lp

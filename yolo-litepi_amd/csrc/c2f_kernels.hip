@@ -1130,6 +1130,9 @@ struct S2Cfg {
   static constexpr int KS2 = CIN_, COUT = COUT_, NW = 8, TH = TH_, TW = 20, F = 0, WPS = 2, C = 32;
   static constexpr int CT = COUT / 16, NT = min_c(CT, 4), CB = CT / NT, PT = cdiv_c(cdiv_c(TH * TW, 16), NW / CB);
   static constexpr int WBYTES = CT * 9 * (KS2 / 32) * 1024;
+  // what the host's table (for_each_s2cfg) reads from either stride-2 configuration type, under S2LCfg's names
+  static constexpr bool LDS_STAGED = false, TAIL = false;
+  static constexpr int CIN = CIN_, OSPLIT = 1, KSPLIT = 1, S = 9 * (KS2 / 32), LDS_BYTES = WBYTES;
 };
 template <class CFG>
 __global__ __launch_bounds__(CFG::NW * 64, 2) void s2conv_kernel(const C2fArgs a) {
@@ -1181,7 +1184,7 @@ template <int CIN_, int COUT_, int TH_, int OSPLIT_, int KSPLIT_ = 1, bool TAIL_
 struct S2LCfg {
   // TAIL: a 1x1 conv + SiLU on the result (C2f.cv1 behind the stride-2 conv: COUT -> COUT channels) runs on the accumulators --
   // a lane's 4 NT consecutive channels of a pixel ARE a K group of the next MFMA's pixel operand (conv_kernels.hip tail_store)
-  static constexpr bool TAIL = TAIL_;
+  static constexpr bool TAIL = TAIL_, LDS_STAGED = true;
   static constexpr int CIN = CIN_, COUT = COUT_, TH = TH_, TW = 20, NW = 8, OSPLIT = OSPLIT_, KSPLIT = KSPLIT_;
   static constexpr int COUTW = COUT / OSPLIT;   // output channels of one workgroup
   static constexpr int CINH = CIN / KSPLIT;     // input channels of one pass (Cin 96: two passes of 48 -- a 21 x 41 plane of 96 is 179 KB)
@@ -1353,10 +1356,10 @@ __global__ __launch_bounds__(CFG::NW * 64, 2) void s2lds_kernel(const C2fArgs a)
   }
 }
 typedef S2LCfg<24, 48, 10, 1> S2L24x48;   // yolo_plus model.ncnn.param:10 (conv_8: 24 -> 48 @80x80): 41 KB plane + 21 KB of weights
-typedef S2LCfg<48, 96, 10, 2> S2L48x96;   // :27 (conv_15: 48 -> 96 @40x40): 96 KB plane + 42 KB of weights, two workgroups per tile
-typedef S2LCfg<48, 48, 10, 1> S2L48x48;   // :129 (conv_37: 48 -> 48 @40x40)
-typedef S2LCfg<48, 96, 10, 2, 2> S2L48x96k2;   // the same in two passes of 24 input channels: 41 + 21 KB, two workgroups per CU
-typedef S2LCfg<48, 48, 10, 1, 2> S2L48x48k2;
+// (Cin 48 in two passes of 24 input channels: 41 KB plane + 21 KB of weights, two workgroups per CU.  The one-pass forms -- 96 KB plane +
+//  42 KB -- lost)
+typedef S2LCfg<48, 96, 10, 2, 2> S2L48x96k2;   // :27 (conv_15: 48 -> 96 @40x40), two workgroups per tile
+typedef S2LCfg<48, 48, 10, 1, 2> S2L48x48k2;   // :129 (conv_37: 48 -> 48 @40x40)
 // (v1's 32 -> 64 convs as S2LCfg<32, 64, 10, 1, 2>, two passes of 16 channels: 22.9 / 16.2 us against 22.0 / 14.0 for the gather kernel
 //  above -- at Cin 32 the tile copy costs what the gathers cost; they stay on s2conv_kernel)
 typedef S2LCfg<16, 32, 10, 1, 1, true> S2L16x32t;   // v1 model.ncnn.param:19-20 (conv_6 16 -> 32 @80x80 + conv_7 = C2f.cv1 32 -> 32 as its tail)
@@ -1366,7 +1369,6 @@ typedef S2LCfg<96, 192, 10, 4, 2> S2L96x192;   // :44 (conv_22: 96 -> 192 @20x20
 typedef S2LCfg<96, 96, 10, 2, 2> S2L96x96;     // :142 (conv_42: 96 -> 96 @20x20)
 
 typedef S2Cfg<32, 64> S2Cfg32x64;   // model.ncnn.param:41 (conv_15: 32 -> 64 @40x40) and :118 (conv_37)
-typedef S2Cfg<32, 64, 10> S2Cfg32x64h;   // half-height tiles: twice the workgroups (A/B: LITEPI_S2C_TH10=1)
 
 // ---- SPPF in one launch for widths whose planes do not fit the whole-image C2f kernel (v2: c = 96 @20x20, yolo_plus
 //      model.ncnn.param:75-87): cv1 (1x1 + SiLU) -> s in ONE LDS plane over the whole image -> cv2 accumulated over s and the three
@@ -1607,25 +1609,46 @@ struct LaunchFn {
   const C2fShape& s; const C2fArgs& a; hipStream_t st;
   template <class CFG> bool operator()() const { return try_launch<CFG>(s, a, st); }
 };
-// the configuration of a shape (build / launch / names: no switches -- a layer that was planned keeps its kernel)
+// the configuration of a shape.  No switches in this file's supported / build / launch / names: which configurations a load may
+// use is the planner's business (PlanSwitches, detector_plan.cpp), and a layer that was planned keeps its kernel
+// (v2's n = 2 backbone modules run as one launch each: 139 us against 150 for the four launches of the 80x80 one -- 145 before
+//  cv2 took y2 / y3 from the planes --, +1.5 % of the pipelined rate; 10-row tiles on the 40x40 map: 74 against 118)
 bool cfg_info(const C2fShape& s, CfgInfo& ci) { return for_each_cfg(InfoFn{s, ci}); }
-// .. and whether the PLANNER may use it (C2fLayer::supported): the A/B switches live here, read at plan time
-bool cfg_enabled(const C2fShape& s, CfgInfo& ci) {
-  // (CfgBb80, the n = 2 module on the 80x80 map, is opt-in: its halo-4 recompute of 16-channel layers is VALU work the
-  //  two-launch bottleneck plan does not have -- 65-75 us against 59; LITEPI_C2F_BB80=1 enables it for A/B runs)
-  if (!getenv("LITEPI_C2F_BB80") && s == CfgBb80::shape()) return false;
-  // (v2's n = 2 backbone modules run as one launch each: 139 us against 150 for the four launches of the 80x80 one -- 145 before
-  //  cv2 took y2 / y3 from the planes --, +1.5 % of the pipelined rate; 10-row tiles on the 40x40 map: 74 against 118)
-  if (!cfg_info(s, ci)) return false;
-  // A/B switch: LITEPI_C2F_SKIP=<configuration names separated by ';'> keeps those modules on the layer plan
-  if (const char* skip = getenv("LITEPI_C2F_SKIP")) {
-    const std::string list = std::string(";") + skip + ";", key = std::string(";") + ci.name + ";";
-    if (list.find(key) != std::string::npos) return false;
-  }
-  return true;
-}
 
 int gam_of(int g) { return ((g & 1) << 1) | (g >> 1); }
+
+// ---- K orders of the packed A fragments, each named once: (K step s, lane group g, element j) -> index into a row of the weight
+//      matrix, or -1 (zero).  A lane group holds K group gam(g) of its step (the LDS column permutation, top of the file).
+// 1x1: the row's ktot channels in order
+auto k_1x1(int ktot) {
+  return [ktot](int s, int g, int j) {
+    const int k = 32 * s + 8 * gam_of(g) + j;
+    return k < ktot ? k : -1;
+  };
+}
+// 3x3, rows [tap][cin], general order (C2fCfg::GK, S2LCfg): K group q = 4 s + gam -> (tap q / G, channel group q % G) over the
+// G = cin / ksplit / 8 groups of one pass; the steps of pass h (input channels h cin / ksplit ..) follow those of pass h - 1
+constexpr int steps_3x3_general(int cin, int ksplit = 1) { return (9 * (cin / ksplit / 8) + 3) / 4; }
+auto k_3x3_general(int cin, int ksplit = 1) {
+  const int cinh = cin / ksplit, G = cinh / 8, S = steps_3x3_general(cin, ksplit);
+  return [=](int s, int g, int j) {
+    const int h = s / S, q = 4 * (s % S) + gam_of(g);
+    return q < 9 * G ? (q / G) * cin + h * cinh + 8 * (q % G) + j : -1;
+  };
+}
+// 3x3, cin % 32 == 0: K step s -> (tap s / (cin / 32), 32-channel block s % (cin / 32))
+auto k_3x3_c32(int cin) {
+  const int spt = cin / 32;
+  return [=](int s, int g, int j) { return (s / spt) * cin + 32 * (s % spt) + 8 * gam_of(g) + j; };
+}
+// 3x3, 16 channels: a K step covers two taps (TA for the even lane groups, TB for the odd ones), five steps
+auto k_3x3_c16(int cin) {
+  return [=](int s, int g, int j) {
+    static const int TA[5] = {0, 3, 6, 1, 4}, TB[5] = {2, 5, 8, 7, -1};
+    const int tap = (g & 1) ? TB[s] : TA[s];
+    return tap < 0 ? -1 : tap * cin + 8 * (g >> 1) + j;
+  };
+}
 
 // A fragments of one phase: [channel block][K step][tile][lane][8 halfs]; lane (g = lane >> 4, m = lane & 15) holds
 // A[row m][K group g].  Rows are permuted so that a lane's D rows 4g .. 4g+3 of tiles 0 .. NT-1 are 4*NT consecutive
@@ -1660,6 +1683,13 @@ void put_bias(DevBuf& dst, const std::vector<float>* b, int cout) {
   dst.alloc(v.size() * 4, false);
   LP_HIP(hipMemcpy(dst.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
 }
+void pack_1x1(DevBuf& d, const std::vector<float>& wv, int cout, int ktot, int NT) { pack_phase(d, wv, cout, ktot, NT, (ktot + 31) / 32, k_1x1(ktot)); }
+// 3x3 weights [cout][tap][cin] in the order c3_phase / c3s2_phase read them at this width
+void pack_3x3(DevBuf& d, const std::vector<float>& wv, int cout, int cin, int NT) {
+  if (cin % 32 != 0 && cin != 16) pack_phase(d, wv, cout, 9 * cin, NT, steps_3x3_general(cin), k_3x3_general(cin));
+  else if (cin >= 32) pack_phase(d, wv, cout, 9 * cin, NT, 9 * (cin / 32), k_3x3_c32(cin));
+  else pack_phase(d, wv, cout, 9 * cin, NT, 5, k_3x3_c16(cin));
+}
 
 }  // namespace
 
@@ -1684,7 +1714,7 @@ static void dump_stamps(const char* file, const std::string& name, size_t nwg, h
 
 bool C2fLayer::supported(const C2fShape& s, int h, int w) {
   CfgInfo ci;
-  if (!cfg_enabled(s, ci)) return false;
+  if (!cfg_info(s, ci)) return false;
   if (h % ci.th != 0 || w % ci.tw != 0) return false;
   if (ci.perimg && (h != ci.th || w != ci.tw)) return false;
   if (s.UP && (h % 2 || w % 2)) return false;
@@ -1698,77 +1728,89 @@ void C2fLayer::build(const C2fShape& s, int h, int w, const Src& src) {
   LP_CHECK(cfg_info(s, ci), LP_ERR_STATE, "c2f: no configuration for this shape");
   lds_bytes = ci.lds;
   const int C = s.C;
-  auto pw_k = [](int ktot) {
-    return [ktot](int s_, int g, int j) {
-      const int k = 32 * s_ + 8 * gam_of(g) + j;
-      return k < ktot ? k : -1;
-    };
-  };
-  // 3x3: weights come as [cout][tap][cin]
-  auto c3_pack = [&](DevBuf& d, const std::vector<float>& wv, int cout, int cin, int NT) {
-    if (cin % 32 != 0 && cin != 16) {   // general packing (C2fCfg::GK): K group q = 4 s + gam -> (tap q / G, channel group q % G)
-      const int G = cin / 8, S = (9 * G + 3) / 4;
-      pack_phase(d, wv, cout, 9 * cin, NT, S, [&](int s_, int g, int j) {
-        const int q = 4 * s_ + gam_of(g);
-        return q < 9 * G ? (q / G) * cin + 8 * (q % G) + j : -1;
-      });
-    } else if (cin >= 32) {
-      const int spt = cin / 32;
-      pack_phase(d, wv, cout, 9 * cin, NT, 9 * spt, [&](int s_, int g, int j) { return (s_ / spt) * cin + 32 * (s_ % spt) + 8 * gam_of(g) + j; });
-    } else {
-      static const int TA[5] = {0, 3, 6, 1, 4}, TB[5] = {2, 5, 8, 7, -1};
-      pack_phase(d, wv, cout, 9 * cin, NT, 5, [&](int s_, int g, int j) {
-        const int tap = (g & 1) ? TB[s_] : TA[s_];
-        return tap < 0 ? -1 : tap * cin + 8 * (g >> 1) + j;
-      });
-    }
-  };
   const int K1 = s.KA + s.KB;
   if (s.MODE != -1) {   // (MODE -1: cv1 belongs to the launch in front)
-    pack_phase(d_w[C2F_W_CV1], *src.cv1, 2 * C, K1, ci.nt1, (K1 + 31) / 32, pw_k(K1));
+    pack_1x1(d_w[C2F_W_CV1], *src.cv1, 2 * C, K1, ci.nt1);
     put_bias(d_b[C2F_W_CV1], src.cv1_b, 2 * C);
   }
   const int ntm = ci.ntm;
   for (int k = 0; k < s.NB; ++k) {
-    c3_pack(d_w[C2F_W_A0 + 2 * k], *src.a[k], C, C, ntm);
+    pack_3x3(d_w[C2F_W_A0 + 2 * k], *src.a[k], C, C, ntm);
     put_bias(d_b[C2F_W_A0 + 2 * k], src.a_b[k], C);
-    c3_pack(d_w[C2F_W_B0 + 2 * k], *src.bb[k], C, C, ntm);
+    pack_3x3(d_w[C2F_W_B0 + 2 * k], *src.bb[k], C, C, ntm);
     put_bias(d_b[C2F_W_B0 + 2 * k], src.bb_b[k], C);
   }
   const int nt2 = ci.nt2;
   const int K2 = (2 + s.NB) * C;
-  pack_phase(d_w[C2F_W_CV2], *src.cv2, s.COUT, K2, nt2, (K2 + 31) / 32, pw_k(K2));
+  pack_1x1(d_w[C2F_W_CV2], *src.cv2, s.COUT, K2, nt2);
   put_bias(d_b[C2F_W_CV2], src.cv2_b, s.COUT);
   macs_per_image = ((s.MODE != -1 ? (double)2 * C * K1 : 0.0) + (double)s.NB * 2 * 9 * C * C + (double)s.COUT * K2) * h * w;
   if (s.MODE >= 1) {
-    c3_pack(d_w[C2F_W_S2], *src.s2, 2 * C, s.KS2, ci.nt_s2);   // NT_S2: every row tile in one wave
+    pack_3x3(d_w[C2F_W_S2], *src.s2, 2 * C, s.KS2, ci.nt_s2);   // NT_S2: every row tile in one wave
     put_bias(d_b[C2F_W_S2], src.s2_b, 2 * C);
     macs_per_image += 9.0 * s.KS2 * 2 * C * h * w;
   }
   if (s.MODE == 2) {
-    pack_phase(d_w[C2F_W_SP1], *src.sp1, C, s.COUT, ntm, (s.COUT + 31) / 32, pw_k(s.COUT));
+    pack_1x1(d_w[C2F_W_SP1], *src.sp1, C, s.COUT, ntm);
     put_bias(d_b[C2F_W_SP1], src.sp1_b, C);
-    pack_phase(d_w[C2F_W_SP2], *src.sp2, s.COUT, 4 * C, nt2, (4 * C + 31) / 32, pw_k(4 * C));
+    pack_1x1(d_w[C2F_W_SP2], *src.sp2, s.COUT, 4 * C, nt2);
     put_bias(d_b[C2F_W_SP2], src.sp2_b, s.COUT);
     macs_per_image += ((double)C * s.COUT + (double)s.COUT * 4 * C) * h * w;
   }
 }
 
-// the LDS-staged kernel's shapes (v2): s2lds_kernel<S2LCfg<..>>; LITEPI_NO_S2LDS=1 keeps them on conv3x3s2_direct (A/B)
-static bool s2lds_shape(int cin, int cout, int hout, int wout) {
-  static const bool off = getenv("LITEPI_NO_S2LDS") != nullptr;
-  static const bool off96 = getenv("LITEPI_NO_S2LDS96") != nullptr;
-  return !off && hout % 10 == 0 && wout % 20 == 0 &&
-         ((cin == 24 && cout == 48) || (cin == 48 && (cout == 96 || cout == 48)) || (!off96 && cin == 96 && (cout == 192 || cout == 96)) ||
-          (cin == 64 && cout == 128));
+// ---- the stride-2 launches: every instantiated configuration in one place, as for_each_cfg.  The key of an entry is
+//      (CIN, COUT, TAIL) of the type itself; supported, build and launch are lookups, so a shape cannot be in one and not in another.
+namespace {
+template <class F> bool for_each_s2cfg(F&& f) {
+  return f.template operator()<S2L24x48>() || f.template operator()<S2L48x96k2>() || f.template operator()<S2L48x48k2>() ||
+         f.template operator()<S2L64x128>() || f.template operator()<S2L96x192>() || f.template operator()<S2L96x96>() ||
+         f.template operator()<S2L16x32t>() || f.template operator()<S2L24x48t>() || f.template operator()<S2Cfg32x64>();
 }
-bool S2ConvLayer::tail_supported(int cin, int cout, int cout2, int hout, int wout) {
-  static const bool off = getenv("LITEPI_NO_S2LDS") != nullptr || getenv("LITEPI_NO_S2TAIL") != nullptr;
-  return !off && ((cin == 16 && cout == 32 && cout2 == 32) || (cin == 24 && cout == 48 && cout2 == 48)) && hout % 10 == 0 && wout % 20 == 0;
+// lds_staged: s2lds_kernel (input tile in LDS, general K order in KSPLIT passes); else s2conv_kernel (gather, cin % 32 == 0 order)
+struct S2Info { int th, tw, nt, ksplit, S; size_t lds; bool lds_staged; };
+struct S2InfoFn {
+  int cin, cout; bool tail; S2Info& si;
+  template <class CFG> bool operator()() const {
+    static_assert(!CFG::LDS_STAGED || CFG::S == steps_3x3_general(CFG::CIN, CFG::KSPLIT), "the kernel's K steps per pass are those of k_3x3_general");
+    if (cin != CFG::CIN || cout != CFG::COUT || tail != CFG::TAIL) return false;
+    si = S2Info{CFG::TH, CFG::TW, CFG::NT, CFG::KSPLIT, CFG::S, (size_t)CFG::LDS_BYTES, CFG::LDS_STAGED};
+    return true;
+  }
+};
+bool s2_info(int cin, int cout, bool tail, S2Info& si) { return for_each_s2cfg(S2InfoFn{cin, cout, tail, si}); }
+bool s2_fits(int cin, int cout, bool tail, int hout, int wout) {
+  S2Info si;
+  return s2_info(cin, cout, tail, si) && hout % si.th == 0 && wout % si.tw == 0;
 }
-bool S2ConvLayer::supported(int cin, int cout, int hout, int wout) {
-  return (cin == 32 && cout == 64 && hout % 20 == 0 && wout % 20 == 0) || s2lds_shape(cin, cout, hout, wout);
+struct S2LaunchFn {
+  const S2ConvLayer& l; C2fArgs& a; hipStream_t st; const char* stamp_file;
+  template <class CFG> bool operator()() const {
+    if (l.Cin != CFG::CIN || l.Cout != CFG::COUT || l.has_tail != CFG::TAIL) return false;
+    a.tiles_x = l.W / CFG::TW; a.tiles_y = l.H / CFG::TH;
+    const size_t nwg = (size_t)a.N * a.tiles_x * a.tiles_y * CFG::OSPLIT;
+    if (stamp_file && !CFG::LDS_STAGED) a.stamps = stamp_buffer(nwg);   // (the gather kernel alone writes stamps)
+    if constexpr (CFG::LDS_STAGED) {
+      set_max_dynamic_lds(reinterpret_cast<const void*>(&s2lds_kernel<CFG>), CFG::LDS_BYTES);
+      LP_LAUNCH(s2lds_kernel<CFG>, dim3((unsigned)nwg), dim3(CFG::NW * 64), CFG::LDS_BYTES, st, a);
+    } else {
+      set_max_dynamic_lds(reinterpret_cast<const void*>(&s2conv_kernel<CFG>), CFG::LDS_BYTES);
+      LP_LAUNCH(s2conv_kernel<CFG>, dim3((unsigned)nwg), dim3(CFG::NW * 64), CFG::LDS_BYTES, st, a);
+    }
+    LP_HIP(hipGetLastError());
+    if (a.stamps) dump_stamps(stamp_file, l.name, nwg, st);
+    return true;
+  }
+};
+}  // namespace
+
+bool S2ConvLayer::supported(int cin, int cout, int hout, int wout) { return s2_fits(cin, cout, false, hout, wout); }
+bool S2ConvLayer::tail_supported(int cin, int cout, int cout2, int hout, int wout) { return cout2 == cout && s2_fits(cin, cout, true, hout, wout); }
+bool S2ConvLayer::lds_staged(int cin, int cout) {
+  S2Info si;
+  return s2_info(cin, cout, false, si) && si.lds_staged;
 }
+std::string S2ConvLayer::kernel_name() const { return fmt(has_tail ? "s2conv+1x1<%d,%d>" : "s2conv<%d,%d>", Cin, Cout); }
 
 void S2ConvLayer::build(int cin, int cout, int hout, int wout, const std::vector<float>& w_taps, const std::vector<float>& bias,
                         const std::vector<float>* w_tail, const std::vector<float>* b_tail) {
@@ -1776,44 +1818,19 @@ void S2ConvLayer::build(int cin, int cout, int hout, int wout, const std::vector
            "s2conv: unsupported shape %d -> %d @%dx%d", cin, cout, hout, wout);
   Cin = cin; Cout = cout; H = hout; W = wout;
   has_tail = w_tail != nullptr;
-  if (has_tail) {   // S2L16x32t / S2L24x48t: one pass, general K packing, every channel tile in one block; the tail's K groups follow
-                    // the lanes' channel ownership: 4 NT consecutive channels per lane group g
-    lds_staged = true; ksplit = 1;
-    const int G = cin / 8, S = (9 * G + 3) / 4, nt = cout / 16;
-    pack_phase(d_w, w_taps, cout, 9 * cin, nt, S, [&](int s_, int g, int j) {
-      const int q = 4 * s_ + gam_of(g);
-      return q < 9 * G ? (q / G) * cin + 8 * (q % G) + j : -1;
-    });
-    put_bias(d_b, &bias, cout);
-    if (nt == 2) pack_phase(d_w2, *w_tail, cout, cout, 2, 1, [&](int, int g, int j) { return 8 * g + j; });
-    else pack_phase(d_w2, *w_tail, cout, cout, 3, 2, [&](int s_, int g, int j) { return s_ == 0 ? 12 * g + j : (j < 4 ? 12 * g + 8 + j : -1); });
-    put_bias(d_b2, b_tail, cout);
-    return;
-  }
-  lds_staged = s2lds_shape(cin, cout, hout, wout);
-  if (lds_staged) {   // general K packing (tap, 8-channel group), three channel tiles per block: S2LCfg / c3_phase's order;
-                      // Cin 96: two passes of 48 input channels, the second pass's steps behind the first's
-    ksplit = cin == 96 || cin == 64 || (cin == 48 && !getenv("LITEPI_S2LDS_K1")) ? 2 : 1;
-    const int cinh = cin / ksplit;
-    const int G = cinh / 8, S = (9 * G + 3) / 4;
-    const int nt = cin == 64 ? 4 : 3;   // S2LCfg::NT of the configuration launch() picks (64 -> 128: 64 output channels = 4 tiles per workgroup; else 48 = 3)
-    pack_phase(d_w, w_taps, cout, 9 * cin, nt, ksplit * S, [&](int s_, int g, int j) {
-      const int h = s_ / S, q = 4 * (s_ % S) + gam_of(g);
-      return q < 9 * G ? (q / G) * cin + h * cinh + 8 * (q % G) + j : -1;
-    });
-    put_bias(d_b, &bias, cout);
-    return;
-  }
-  const int spt = cin / 32, nt = S2Cfg32x64::NT;
-  pack_phase(d_w, w_taps, cout, 9 * cin, nt, 9 * spt, [&](int s_, int g, int j) { return (s_ / spt) * cin + 32 * (s_ % spt) + 8 * gam_of(g) + j; });
+  S2Info si;
+  LP_CHECK(s2_info(cin, cout, has_tail, si), LP_ERR_STATE, "s2conv: no configuration for %d -> %d", cin, cout);
+  // the entry's NT channel tiles per block and K steps.  LDS-staged: the general order in its KSPLIT passes (Cin 96: two passes of 48
+  // input channels, the second pass's steps behind the first's); the gather kernel: whole 32-channel blocks per tap
+  if (si.lds_staged) pack_phase(d_w, w_taps, cout, 9 * cin, si.nt, si.ksplit * si.S, k_3x3_general(cin, si.ksplit));
+  else pack_phase(d_w, w_taps, cout, 9 * cin, si.nt, si.S, k_3x3_c32(cin));
   put_bias(d_b, &bias, cout);
-}
-
-template <class CFG> static void launch_s2lds(const C2fArgs& a0, int N, int H, int W, hipStream_t st) {
-  C2fArgs a = a0;
-  a.tiles_x = W / CFG::TW; a.tiles_y = H / CFG::TH;
-  set_max_dynamic_lds(reinterpret_cast<const void*>(&s2lds_kernel<CFG>), CFG::LDS_BYTES);
-  LP_LAUNCH(s2lds_kernel<CFG>, dim3(N * a.tiles_x * a.tiles_y * CFG::OSPLIT), dim3(CFG::NW * 64), CFG::LDS_BYTES, st, a);
+  if (has_tail) {   // the tail's K groups follow the lanes' channel ownership: lane group g holds channels 4 NT g .. 4 NT (g + 1) - 1 of
+                    // its pixel, eight per K step (S2LCfg::TSTEPS; NT = 3: the second step's upper half is zero)
+    const int own = 4 * si.nt;
+    pack_phase(d_w2, *w_tail, cout, cout, si.nt, (own + 7) / 8, [own](int s, int g, int j) { return 8 * s + j < own ? own * g + 8 * s + j : -1; });
+    put_bias(d_b2, b_tail, cout);
+  }
 }
 
 void S2ConvLayer::launch(const View& in, const View& out, int N, hipStream_t st) const {
@@ -1827,60 +1844,27 @@ void S2ConvLayer::launch(const View& in, const View& out, int N, hipStream_t st)
   a.x = out.base; a.x_pitch = out.pitch;
   a.w[C2F_W_S2] = d_w.p; a.b[C2F_W_S2] = d_b.as<float>();
   a.N = N; a.H = H; a.W = W;
-  if (has_tail) {
-    a.w[C2F_W_CV1] = d_w2.p; a.b[C2F_W_CV1] = d_b2.as<float>();
-    if (Cin == 16) launch_s2lds<S2L16x32t>(a, N, H, W, st);
-    else launch_s2lds<S2L24x48t>(a, N, H, W, st);
-    LP_HIP(hipGetLastError());
-    return;
-  }
-  if (lds_staged) {
-    if (Cin == 64) launch_s2lds<S2L64x128>(a, N, H, W, st);
-    else if (Cin == 24) launch_s2lds<S2L24x48>(a, N, H, W, st);
-    else if (Cin == 96 && Cout == 192) launch_s2lds<S2L96x192>(a, N, H, W, st);
-    else if (Cin == 96) launch_s2lds<S2L96x96>(a, N, H, W, st);
-    else if (Cout == 96 && ksplit == 2) launch_s2lds<S2L48x96k2>(a, N, H, W, st);
-    else if (Cout == 96) launch_s2lds<S2L48x96>(a, N, H, W, st);
-    else if (ksplit == 2) launch_s2lds<S2L48x48k2>(a, N, H, W, st);
-    else launch_s2lds<S2L48x48>(a, N, H, W, st);
-    LP_HIP(hipGetLastError());
-    return;
-  }
-  static const bool th10 = getenv("LITEPI_S2C_TH10") != nullptr;
-  const bool half = th10 && H % 10 == 0;
-  a.tiles_x = W / 20; a.tiles_y = half ? H / 10 : H / 20;
-  typedef S2Cfg32x64 CFG;
+  if (has_tail) { a.w[C2F_W_CV1] = d_w2.p; a.b[C2F_W_CV1] = d_b2.as<float>(); }
   static const char* stamp_file = getenv("LITEPI_C2F_STAMPS");
-  if (stamp_file) a.stamps = stamp_buffer((size_t)N * a.tiles_x * a.tiles_y);
-  if (half) {
-    set_max_dynamic_lds(reinterpret_cast<const void*>(&s2conv_kernel<S2Cfg32x64h>), CFG::WBYTES);
-    LP_LAUNCH(s2conv_kernel<S2Cfg32x64h>, dim3(N * a.tiles_x * a.tiles_y), dim3(CFG::NW * 64), CFG::WBYTES, st, a);
-  } else {
-    set_max_dynamic_lds(reinterpret_cast<const void*>(&s2conv_kernel<CFG>), CFG::WBYTES);
-    LP_LAUNCH(s2conv_kernel<CFG>, dim3(N * a.tiles_x * a.tiles_y), dim3(CFG::NW * 64), CFG::WBYTES, st, a);
-  }
-  LP_HIP(hipGetLastError());
-  if (stamp_file) dump_stamps(stamp_file, name, (size_t)N * a.tiles_x * a.tiles_y, st);
+  const bool ok = for_each_s2cfg(S2LaunchFn{*this, a, st, stamp_file});
+  LP_CHECK(ok, LP_ERR_STATE, "s2conv %s: no kernel for this shape", name.c_str());
 }
 
+// ---- SPPF: one instantiated configuration.  supported / build / launch read this type only
+typedef SpCfgV2 SppfCfg;
+
 bool SppfLayer::supported(int cin, int c, int cout, int h, int w) {
-  static const bool off = getenv("LITEPI_NO_SPPF_FUSED") != nullptr;
-  return !off && cin == SpCfgV2::CIN && c == SpCfgV2::C && cout == SpCfgV2::COUT && h == 20 && w == 20;
+  return cin == SppfCfg::CIN && c == SppfCfg::C && cout == SppfCfg::COUT && h == SppfCfg::TH && w == SppfCfg::TW;
 }
+std::string SppfLayer::kernel_name() const { return fmt("sppf<%d,%d,%d>", Cin, C, Cout); }
 
 void SppfLayer::build(int cin, int c, int cout, int h, int w, const std::vector<float>& w1, const std::vector<float>& b1,
                       const std::vector<float>& w2, const std::vector<float>& b2) {
   LP_CHECK(supported(cin, c, cout, h, w), LP_ERR_STATE, "sppf: unsupported shape %d -> %d -> %d @%dx%d", cin, c, cout, h, w);
   Cin = cin; C = c; Cout = cout; H = h; W = w;
-  auto pw_k = [](int ktot) {
-    return [ktot](int s_, int g, int j) {
-      const int k = 32 * s_ + 8 * gam_of(g) + j;
-      return k < ktot ? k : -1;
-    };
-  };
-  pack_phase(d_w1, w1, c, cin, SpCfgV2::NT1, cin / 32, pw_k(cin));
+  pack_1x1(d_w1, w1, c, cin, SppfCfg::NT1);
   put_bias(d_b1, &b1, c);
-  pack_phase(d_w2, w2, cout, 4 * c, SpCfgV2::NT2, 4 * c / 32, pw_k(4 * c));
+  pack_1x1(d_w2, w2, cout, 4 * c, SppfCfg::NT2);
   put_bias(d_b2, &b2, cout);
   macs_per_image = ((double)c * cin + (double)cout * 4 * c) * h * w;
 }
@@ -1896,7 +1880,7 @@ void SppfLayer::launch(const View& in, const View& out, int N, hipStream_t st) c
   a.w[C2F_W_SP1] = d_w1.p; a.b[C2F_W_SP1] = d_b1.as<float>();
   a.w[C2F_W_SP2] = d_w2.p; a.b[C2F_W_SP2] = d_b2.as<float>();
   a.N = N; a.H = H; a.W = W; a.tiles_x = a.tiles_y = 1;
-  typedef SpCfgV2 CFG;
+  typedef SppfCfg CFG;
   set_max_dynamic_lds(reinterpret_cast<const void*>(&sppf_kernel<CFG>), CFG::LDS_BYTES);
   LP_LAUNCH(sppf_kernel<CFG>, dim3(N * CFG::OSPLIT), dim3(CFG::NW * 64), CFG::LDS_BYTES, st, a);
   LP_HIP(hipGetLastError());
@@ -1907,9 +1891,9 @@ bool C2fLayer::cv2_from_lds() const {
   return cfg_info(sh, ci) && ci.cv2_lds;
 }
 
-std::string C2fLayer::kernel_name() const {
+std::string C2fLayer::kernel_name(const C2fShape& s) {
   CfgInfo ci;
-  return cfg_info(sh, ci) ? ci.name : "c2f";
+  return cfg_info(s, ci) ? ci.name : "";
 }
 
 void C2fLayer::launch(const IO& io, int N, hipStream_t st) const {
@@ -1952,7 +1936,6 @@ void C2fLayer::launch(const IO& io, int N, hipStream_t st) const {
   const bool ok = for_each_cfg(LaunchFn{sh, a, st});
   LP_CHECK(ok, LP_ERR_STATE, "c2f %s: no kernel for this shape", name.c_str());
   LP_HIP(hipGetLastError());
-  if (stamp_file && getenv("LITEPI_C2F_TWICE")) for_each_cfg(LaunchFn{sh, a, st});   // diagnostic: the stamps of an immediate second launch (warm instruction cache)
   if (stamp_file) dump_stamps(stamp_file, name, (size_t)N * a.tiles_x * a.tiles_y, st);
 }
 

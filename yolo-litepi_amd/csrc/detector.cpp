@@ -192,11 +192,11 @@ void Detector::forward(const uint8_t* imgs, int B, const ImgGeom* geom, float co
       }
       case DetOp::SPPFUSED:
         sppfs_[op.conv]->launch(view(op.in), view(op.out), B, st);
-        kname = fmt("sppf<%d,%d,%d>", sppfs_[op.conv]->Cin, sppfs_[op.conv]->C, sppfs_[op.conv]->Cout) + sfx;
+        kname = sppfs_[op.conv]->kernel_name() + sfx;
         break;
       case DetOp::S2C:
         s2cs_[op.conv]->launch(view(op.in), view(op.out), B, st);
-        kname = fmt(s2cs_[op.conv]->has_tail ? "s2conv+1x1<%d,%d>" : "s2conv<%d,%d>", s2cs_[op.conv]->Cin, s2cs_[op.conv]->Cout) + sfx;
+        kname = s2cs_[op.conv]->kernel_name() + sfx;
         break;
       case DetOp::HEAD:
         heads_[op.conv]->launch(view(op.in), B, levels_[op.in2].off, A_, d_anchors_.as<float>(), d_strides_.as<float>(), d_dfl_.as<float>(), out0,

@@ -20,17 +20,28 @@
 
 namespace lp {
 
-// Every LITEPI_* switch the planner reads, read once at the top of a load.  (The launchers' own switches stay in the kernel files.)
+// Every LITEPI_* switch the planner reads, read once at the top of a load: a process may set one between two loads.  Every plan-time
+// switch of c2f_kernels.hip is here -- that file's supported() functions are pure functions of the shape, and the Planner's
+// c2f_ok / s2c_ok / s2c_tail_ok / sppf_ok combine them with these.  (The other kernel files' own switches stay in those files, as
+// do the diagnostics a launch reads: LITEPI_C2F_STAMPS, LITEPI_C2F_DEBUG.)
 struct PlanSwitches {
   static bool on(const char* name) { return getenv(name) != nullptr; }
   bool no_c2f = on("LITEPI_NO_C2F");             // whole-C2f / SPPF / stride-2 launches of c2f_kernels.hip off
+  // c2f<16,2,32>, the n = 2 module on the 80x80 map, is opt-in: its halo-4 recompute of 16-channel layers is VALU work the two-launch
+  // bottleneck plan does not have -- 65-75 us against 59; LITEPI_C2F_BB80=1 enables it for A/B runs
+  bool c2f_bb80 = on("LITEPI_C2F_BB80");
+  // LITEPI_C2F_SKIP=<configuration names separated by ';'> keeps those modules on the layer plan (A/B); held as ";name;name;"
+  std::string c2f_skip = getenv("LITEPI_C2F_SKIP") ? std::string(";") + getenv("LITEPI_C2F_SKIP") + ";" : std::string();
   // handles built for fewer than 4 images keep the layer plan: a whole-C2f launch is one long workgroup chain per tile, and with
   // a handful of tiles that chain is the latency -- batch-1 detect 0.475 ms against 0.43 ms
   int c2f_min_batch = getenv("LITEPI_C2F_MIN_BATCH") ? atoi(getenv("LITEPI_C2F_MIN_BATCH")) : 4;
   bool c2f_store_all = on("LITEPI_C2F_STORE_ALL");   // bisect mode: the modules store the intermediates they keep in LDS
   bool c2f_xcv1 = on("LITEPI_C2F_XCV1");         // cv1-less C2f behind a stride-2 conv + cv1 launch also where it is opt-in (v1)
   bool no_c2f_xcv1 = on("LITEPI_NO_C2F_XCV1");   // ... and off where it is the default (v2's 48-channel module)
-  bool no_s2c = on("LITEPI_NO_S2C");             // LDS-staged stride-2 kernels off
+  bool no_s2c = on("LITEPI_NO_S2C");             // stride-2 launches of c2f_kernels.hip off (with and without a tail)
+  bool no_s2lds = on("LITEPI_NO_S2LDS");         // ... only those on the LDS-staged kernel (A/B: they stay on conv3x3s2_direct)
+  bool no_s2tail = on("LITEPI_NO_S2TAIL");       // ... only those that carry a 1x1 tail
+  bool no_sppf_fused = on("LITEPI_NO_SPPF_FUSED");   // one-launch SPPF off
   bool no_sibling = on("LITEPI_NO_SIBLING");
   bool no_bneck = on("LITEPI_NO_BNECK");         // keeps the layer-at-a-time plan (A/B measurements)
   bool no_cv2fuse = on("LITEPI_NO_CV2FUSE");
@@ -166,6 +177,18 @@ struct Planner {
   bool match_sppf_chain(int j1, SppfChain& s);
   bool match_s2_front(int i, C2fMatch& m, int& xcat);
   C2fShape c2f_shape(const C2fMatch& m, int mode, int ks2);
+  // One predicate per kernel family of c2f_kernels.hip -- may THIS load emit the launch: the family's pure shape rule (c2f.h) and
+  // this load's switches.  Every rule that claims layers for such a launch asks one of these, and no rule asks c2f.h directly.
+  bool c2f_ok(const C2fShape& s, int h, int w) const {
+    if (!c2f_on || !C2fLayer::supported(s, h, w)) return false;
+    const std::string name = C2fLayer::kernel_name(s);
+    if (name == "c2f<16,2,32>" && !sw.c2f_bb80) return false;
+    return sw.c2f_skip.find(";" + name + ";") == std::string::npos;
+  }
+  bool s2c_ok(int cin, int cout, int hout, int wout) const {
+    return c2f_on && !sw.no_s2c && S2ConvLayer::supported(cin, cout, hout, wout) && !(sw.no_s2lds && S2ConvLayer::lds_staged(cin, cout));
+  }
+  bool sppf_ok(int cin, int c, int cout, int h, int w) const { return c2f_on && !sw.no_sppf_fused && SppfLayer::supported(cin, c, cout, h, w); }
   bool c2f_plain_ok(int i1);
   void emit_c2f(const C2fMatch& m, int mode, const C2fShape& sh, int i0, int xcat, const SppfChain* sp);
   void mark_inside_c2f(const C2fMatch& m, int mode, const C2fIO& io, const SppfChain* sp);
@@ -186,6 +209,7 @@ struct Planner {
   bool try_bottleneck(const ConvSite& c);
   std::optional<Cv2Match> match_bneck_cv2(int tin, int tfinal);
   void pick_1x1_tail(ConvSite& c);
+  bool s2c_tail_ok(const ConvSite& c, int tail, int tmid, int tout) const;   // (the stride-2 family's predicate for a conv WITH a tail)
   bool try_s2c_with_tail(const ConvSite& c);
   void emit_c2f_behind_tail(const ConvSite& c);
   bool try_s2c(const ConvSite& c);
@@ -599,7 +623,7 @@ bool Planner::c2f_plain_ok(int i1) {   // a stand-alone C2f launch exists for th
   C2fMatch m;
   if (!c2f_on || !match_c2f(i1, m)) return false;
   const Tensor& T = tensors_[cinfo[i1].tout];
-  return C2fLayer::supported(c2f_shape(m, 0, 0), T.H, T.W);
+  return c2f_ok(c2f_shape(m, 0, 0), T.H, T.W);
 }
 
 // The SPPF chain from its cv1 (layer j1, a 1x1 SiLU conv the caller has checked): three chained pools that nothing else reads,
@@ -685,9 +709,9 @@ bool Planner::try_c2f(int i) {
     if (ok) mode = 2;
   }
   C2fShape sh = c2f_shape(m, mode, i0 >= 0 ? L[i0].in_ch : 0);
-  if (!C2fLayer::supported(sh, Hh, Ww)) {
+  if (!c2f_ok(sh, Hh, Ww)) {
     if (mode == 2) { mode = 1; sh = c2f_shape(m, 1, L[i0].in_ch); }
-    if (!C2fLayer::supported(sh, Hh, Ww)) return false;   // (a stride-2 conv falls through to its own kernel; the module is tried again at its cv1)
+    if (!c2f_ok(sh, Hh, Ww)) return false;   // (a stride-2 conv falls through to its own kernel; the module is tried again at its cv1)
   }
   emit_c2f(m, mode, sh, i0, xcat, mode == 2 ? &sp : nullptr);
   return true;
@@ -791,7 +815,7 @@ bool Planner::try_sppf(int i) {
   const int j2 = sp.cv2, tc2 = sp.t_cat, tout = cinfo[j2].tout;
   if (tensors_[tout].segs.size() != 1 || feeds_add(tout)) return false;
   const int Hh = tensors_[ts].H, Ww = tensors_[ts].W;
-  if (!SppfLayer::supported(L[i].in_ch, c, L[j2].ipar(0), Hh, Ww)) return false;
+  if (!sppf_ok(L[i].in_ch, c, L[j2].ipar(0), Hh, Ww)) return false;
   d.sppfs_.emplace_back(new SppfLayer());
   SppfLayer& sl = *d.sppfs_.back();
   sl.name = L[i].name + "+pools+" + L[j2].name;
@@ -1006,12 +1030,12 @@ void Planner::pick_1x1_tail(ConvSite& c) {
   const bool b_feeds_add = feeds_add(tb);
   // (a C2f.cv1 that the whole-C2f launch computes itself is not folded into this conv)
   // (a stride-2 conv whose 1x1 consumer is the cv1 of a C2f module that can run WITHOUT its cv1 -- C2fShape::MODE -1 -- keeps
-  //  that cv1 as its tail on the LDS-staged kernel even though a whole-module launch exists: v2's 80x80 backbone module)
+  //  that cv1 as its tail on the LDS-staged kernel even though a whole-module launch exists: v2's 80x80 backbone module.  Claimed
+  //  only when try_s2c_with_tail will emit that launch, hence the same predicate: ConvLayer has no 48 -> 48 tail to fall back on)
   bool s2tail = false;
-  if (c2f_on && plain1x1 && c.s == 2 && !sw.no_c2f_xcv1 && tensors_[tout].Cp == 48 &&
-      S2ConvLayer::tail_supported(c.Cin, tensors_[tout].Cp, tensors_[tb].Cp, tensors_[tb].H, tensors_[tb].W)) {
+  if (plain1x1 && !sw.no_c2f_xcv1 && tensors_[tout].Cp == 48 && s2c_tail_ok(c, j, tout, tb)) {
     C2fMatch mx;
-    s2tail = match_c2f(j, mx) && C2fLayer::supported(c2f_shape(mx, -1, 0), tensors_[tb].H, tensors_[tb].W);
+    s2tail = match_c2f(j, mx) && c2f_ok(c2f_shape(mx, -1, 0), tensors_[tb].H, tensors_[tb].W);
   }
   if (plain1x1 && !b_feeds_add && (s2tail || (!c2f_plain_ok(j) && ConvLayer::tail_supported(c.k, c.s, tensors_[tout].Cp, tensors_[tb].Cp)))) {
     c.tail = j;
@@ -1021,15 +1045,19 @@ void Planner::pick_1x1_tail(ConvSite& c) {
   }
 }
 
+// May this load run stride-2 conv c with the 1x1 conv `tail` folded in as ONE launch of the LDS-staged kernel?  tmid: the conv's own
+// output, tout: the tail's.  Asked by pick_1x1_tail before it claims v2's cv1 as a tail, and by try_s2c_with_tail before it emits.
+bool Planner::s2c_tail_ok(const ConvSite& c, int tail, int tmid, int tout) const {
+  const int i = c.i, tin = c.tin, Cin = c.Cin, Cout = c.Cout;
+  return c2f_on && !sw.no_s2c && !sw.no_s2lds && !sw.no_s2tail && c.res < 0 && c.k == 3 && c.s == 2 && fused_act[i] == ACT_SILU &&
+         fused_act[tail] == ACT_SILU && !L[i].bias.empty() && !L[tail].bias.empty() && tin != input_tensor && tensors_[tin].Cp == Cin &&
+         tensors_[tmid].Cp == Cout && tensors_[tout].Cp == L[tail].ipar(0) && tensors_[tout].parent < 0 &&
+         S2ConvLayer::tail_supported(Cin, Cout, L[tail].ipar(0), tensors_[tout].H, tensors_[tout].W);
+}
+
 // a stride-2 conv WITH its folded 1x1 tail on the LDS-staged kernel (v1's conv_6 + conv_7: s2lds_kernel<S2L16x32t>)
 bool Planner::try_s2c_with_tail(const ConvSite& c) {
-  const int i = c.i, tin = c.tin, tout = c.tout, tail = c.tail, Cin = c.Cin, Cout = c.Cout;
-  const NcnnLayer& l = L[i];
-  if (!c2f_on || sw.no_s2c || tail < 0 || c.res >= 0 || c.k != 3 || c.s != 2 || fused_act[i] != ACT_SILU || fused_act[tail] != ACT_SILU ||
-      l.bias.empty() || L[tail].bias.empty() || tin == input_tensor || tensors_[tin].Cp != Cin || tensors_[c.tmid].Cp != Cout ||
-      tensors_[tout].Cp != L[tail].ipar(0) || tensors_[tout].parent >= 0 ||
-      !S2ConvLayer::tail_supported(Cin, Cout, L[tail].ipar(0), tensors_[tout].H, tensors_[tout].W))
-    return false;
+  if (c.tail < 0 || !s2c_tail_ok(c, c.tail, c.tmid, c.tout)) return false;
   emit_s2c(c);
   emit_c2f_behind_tail(c);
   return true;
@@ -1048,16 +1076,16 @@ void Planner::emit_c2f_behind_tail(const ConvSite& c) {
   if (!ok) return;
   const C2fShape sh = c2f_shape(m, -1, 0);
   const Tensor& T2 = tensors_[cinfo[m.cv2].tout];
-  if (C2fLayer::supported(sh, T2.H, T2.W)) emit_c2f(m, -1, sh, -1, -1, nullptr);
+  if (c2f_ok(sh, T2.H, T2.W)) emit_c2f(m, -1, sh, -1, -1, nullptr);
 }
 
 // a stride-2 conv without a folded tail whose shape the c2f machinery covers: s2conv_kernel (LITEPI_NO_S2C=1: off)
 bool Planner::try_s2c(const ConvSite& c) {
   const int i = c.i, tin = c.tin, tout = c.tout, Cin = c.Cin, Cout = c.Cout;
   const NcnnLayer& l = L[i];
-  if (!c2f_on || sw.no_s2c || c.tail >= 0 || c.res >= 0 || c.k != 3 || c.s != 2 || fused_act[i] != ACT_SILU || l.bias.empty() ||
+  if (c.tail >= 0 || c.res >= 0 || c.k != 3 || c.s != 2 || fused_act[i] != ACT_SILU || l.bias.empty() ||
       tin == input_tensor || tensors_[tin].Cp != Cin || tensors_[tout].Cp != Cout || tensors_[tout].segs.size() != 1 ||
-      !S2ConvLayer::supported(Cin, Cout, tensors_[tout].H, tensors_[tout].W))
+      !s2c_ok(Cin, Cout, tensors_[tout].H, tensors_[tout].W))
     return false;
   emit_s2c(c);
   return true;
