@@ -60,14 +60,20 @@ CONV_CASES = [
     (3, 2, 64, 128, 40, 40, 1, False),
     (3, 2, 16, 32, 33, 47, 1, False),
 ]
+# At N = 2 almost every CONV_CASES entry plans one channel tile per workgroup (NT = 1).  These run with N = 8 on an 80x80 output
+# map: Cout 32 / 48 / 64 plan NT = 2 / 3 / 4 in each kernel family (1x1, 3x3 stride 1, 3x3 stride 2), i.e. the other entries of
+# the dispatch tables of csrc/conv_plan.h -- tests/test_conv_plan_cpu.py asserts that these shapes plan exactly that
+DISPATCH_N = 8
+DISPATCH_CASES = [(k, s, 16, cout, 80 * s, 80 * s, 1, False) for k, s in ((1, 1), (3, 1), (3, 2)) for cout in (32, 48, 64)]
+_conv_id = lambda c: f"k{c[0]}s{c[1]}_{c[2]}to{c[3]}_{c[4]}x{c[5]}"
 
 
 @pytest.mark.parametrize("impl", [0, 1], ids=["mfma", "naive"])
 @pytest.mark.parametrize("case", CONV_CASES, ids=[f"k{c[0]}s{c[1]}_{c[2]}to{c[3]}_{c[4]}x{c[5]}" for c in CONV_CASES])
-def test_conv_fp32(eng32, case, impl):
+def test_conv_fp32(eng32, case, impl, n=2):
     k, s, cin, cout, H, W, act, use_res = case
     g = torch.Generator().manual_seed(hash(case) % 1000)
-    x = torch.randn(2, cin, H, W, generator=g)
+    x = torch.randn(n, cin, H, W, generator=g)
     w = torch.randn(cout, cin, k, k, generator=g) * (1.0 / (cin * k * k)) ** 0.5
     b = torch.randn(cout, generator=g) * 0.1
     ref = _act(F.conv2d(x, w, b, stride=s, padding=k // 2), act)
@@ -80,11 +86,11 @@ def test_conv_fp32(eng32, case, impl):
 
 
 @pytest.mark.parametrize("case", CONV_CASES, ids=[f"k{c[0]}s{c[1]}_{c[2]}to{c[3]}_{c[4]}x{c[5]}" for c in CONV_CASES])
-def test_conv_fp16(eng16, case):
+def test_conv_fp16(eng16, case, n=2):
     k, s, cin, cout, H, W, act, use_res = case
     g = torch.Generator().manual_seed(hash(case) % 1000)
     # inputs rounded to fp16 first: the only differences left are accumulation order and the fp16 output rounding
-    x = torch.randn(2, cin, H, W, generator=g).half().float()
+    x = torch.randn(n, cin, H, W, generator=g).half().float()
     w = (torch.randn(cout, cin, k, k, generator=g) * (1.0 / (cin * k * k)) ** 0.5).half().float()
     b = torch.randn(cout, generator=g) * 0.1
     ref = _act(F.conv2d(x, w, b, stride=s, padding=k // 2), act)
@@ -95,6 +101,16 @@ def test_conv_fp16(eng16, case):
     err = np.abs(y - ref.numpy())
     tol = 2e-3 + 2e-3 * np.abs(ref.numpy())  # one fp16 ulp of the output (2^-10 relative) + slack
     assert (err <= tol).all(), f"max abs err {err.max()}"
+
+
+@pytest.mark.parametrize("case", DISPATCH_CASES, ids=[_conv_id(c) for c in DISPATCH_CASES])
+def test_conv_dispatch_fp32(eng32, case):
+    test_conv_fp32(eng32, case, 0, n=DISPATCH_N)
+
+
+@pytest.mark.parametrize("case", DISPATCH_CASES, ids=[_conv_id(c) for c in DISPATCH_CASES])
+def test_conv_dispatch_fp16(eng16, case):
+    test_conv_fp16(eng16, case, n=DISPATCH_N)
 
 
 # ---------------------------------------------------------------------------- post-processing

@@ -60,8 +60,8 @@ def family(name):
     if "conv3x3s2_direct_kernel" in name:   # <T, NT, NP, T2, U>
         t2 = ints[2] if len(ints) > 2 else 0
         return ("conv3x3s2_direct+1x1<%d,%d>" % (ints[0], t2) if t2 else "conv3x3s2_direct<%d>" % ints[0]) + f16
-    if "conv3x3_mfma_kernel" in name:       # <T, NT, STRIDE, T2>
-        t2 = ints[2] if len(ints) > 2 else 0
+    if "conv3x3_mfma_kernel" in name:       # <T, NT, T2>
+        t2 = ints[1] if len(ints) > 1 else 0
         return ("conv3x3_mfma+1x1<%d,%d>" % (ints[0], t2) if t2 else "conv3x3_mfma<%d>" % ints[0]) + f16
     if "conv1x1_mfma_kernel" in name:       # <T, NT, NP, EPI, UPS>
         ups = "Lb1E" in name or ", true>" in name

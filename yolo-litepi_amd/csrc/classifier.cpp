@@ -301,7 +301,7 @@ void Classifier::forward(const uint8_t* rgb, const int* d_R, hipStream_t st, Pro
     P0();
     c.launch(io, st);
     const double px = (double)out.H * out.W;
-    P1(c.impl == IMPL_NAIVE ? "conv_naive" : "conv1x1_mfma", c.name, 2.0 * c.Cin * c.Cout * px,
+    P1(c.family_name(), c.name, 2.0 * c.Cin * c.Cout * px,
        px * (c.Cin + c.Cout * (x1 ? 2.0 : 1.0)) * esd);
   };
   auto run_dw = [&](int idx, const View& in, const View& out) {

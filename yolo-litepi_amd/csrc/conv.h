@@ -1,6 +1,7 @@
 // Host-side handles of the convolution kernels (conv_kernels.hip).
 #pragma once
 #include "common.h"
+#include "conv_plan.h"
 
 namespace lp {
 
@@ -16,15 +17,10 @@ struct ConvIO {
 };
 
 // One Convolution(+bias)(+activation)(+residual) layer with its device weights, packed for
-// the kernel family chosen at build time.
-struct ConvLayer {
+// the kernel family chosen at build time.  The MFMA tiling (NT, nsplits, CK, .., direct) is cplan::plan_conv's result.
+struct ConvLayer : cplan::ConvTiling {
   int prec = LP_FP16, impl = IMPL_MFMA;
   int k = 1, stride = 1, Cin = 0, Cout = 0, act = ACT_NONE;
-  // MFMA tiling
-  int NT = 1, nsplits = 1, CK = 0, CGc = 0, nchunks = 1, steps = 0, LW = 0, PS = 0, bwh = 2, bww = 2;
-  size_t lds_bytes = 0;
-  unsigned rcp_cg = 0, rcp_ps = 0, rcp_pcs = 0;  // 16-bit reciprocals of CGc, PS/16 and pieces per LDS tile row (3x3 kernel)
-  bool direct = false;  // 3x3 stride-2: gather B fragments from global memory (no LDS input tile)
   DevBuf d_w, d_bias;
   // fused 1x1 tail conv (second GEMM in the epilogue): 0 = none, else its 16-channel output tiles
   int T2 = 0, Cout2 = 0, act2 = ACT_NONE;
@@ -44,47 +40,45 @@ struct ConvLayer {
   // Fuse a following 1x1 conv (weights w2_phys [cout2][Cout] over physical channels) into this 3x3 layer.
   // Requires build(..., full_n = true) (one workgroup holds every intermediate channel).  The fused layer's
   // output view then has cout2 channels.
-  static bool tail_supported(int k, int stride, int cmid_phys, int cout2_phys);
+  static bool tail_supported(int k, int stride, int cmid_phys, int cout2_phys) { return cplan::conv_tail_supported(k, stride, cmid_phys, cout2_phys); }
   void attach_tail(int cout2_phys, int act2, const std::vector<float>& w2_phys, const std::vector<float>& bias2_phys);
   void launch(const ConvIO& io, hipStream_t st) const;
+  // profile names: the kernel family, and one name per instantiation (channel tiles NT, tail tiles T2, fused-upsample variant,
+  // as rocprofv3 lists them), both without the precision suffix
+  const char* family_name() const { return impl == IMPL_NAIVE ? "conv_naive" : direct ? "conv3x3s2_direct" : k == 3 ? "conv3x3_mfma" : "conv1x1_mfma"; }
+  std::string kernel_name(bool up = false) const;
 };
 
 // C2f bottleneck x + silu(conv3x3(silu(conv3x3(x)))) as ONE launch (bottleneck_mfma_kernel): the
 // intermediate lives in LDS.  The two ConvLayers only carry the packed weights (all of K in one chunk).
-struct BottleneckPair {
+// The tile, its LDS size and the cv2 tail's shape (TH, TW, LW, lds_bytes, T2, kg, sg, cl, PSA) are cplan::plan_bneck's result.
+struct BottleneckPair : cplan::BneckTiling {
   ConvLayer a, b;
-  int prec = LP_FP16, C = 0, NT = 1, TH = 8, TW = 40, LW = 0, PS = 0, CG = 0, steps = 0;
+  int prec = LP_FP16, C = 0, NT = 1, PS = 0, CG = 0, steps = 0;
   unsigned rcp_cg = 0, rcp_ps = 0, rcp_pcs = 0, rcp_w1 = 0, rcp_tw = 0;
-  size_t lds_bytes = 0;
   std::string name;
-  // optional fused C2f.cv2 (1x1 over concat[stored segments .., y_last]); y_last = this bottleneck's output
-  struct Cv2 {
-    int cat_global = 0;          // physical channels of the concat that precede y_last (read from the concat buffer)
-    int c3 = 0, act = ACT_NONE;  // cv2 output channels (physical), activation
+  // optional fused C2f.cv2 (1x1 over concat[stored segments .., y_last]); y_last = this bottleneck's output.  The base holds
+  // what the plan depends on: cat_global = physical channels of the concat that precede y_last (read from the concat buffer),
+  // c3 = cv2's physical output channels, in_is_last_stored (same buffer and pitch; C2f: y_n), and the planner's cl switch
+  struct Cv2 : cplan::BneckTail {
+    int act = ACT_NONE;
     const std::vector<float>* w = nullptr;  // fp32 [c3][cat_global + C] over physical concat channels
     const std::vector<float>* bias = nullptr;
-    bool in_is_last_stored = false;  // the bottleneck's input is the concat's last stored segment, same buffer and pitch (C2f: y_n)
   };
-  int T2 = 0, C3 = 0, act3 = ACT_NONE, kg = 0, sg = 0;
-  bool cl = false;   // "concat from LDS": the tile is staged with every stored segment, cv2 gathers from it (see the kernel)
-  int PSA = 0;       // its pixel pitch in LDS
-  // pixel tiles (of 16) per wave in conv_a / conv_b = the kernel's P1 / P2 template arguments
-  int p1() const { return (((TH + 2) * (TW + 2) + 15) / 16 + 3) / 4; }
-  int p2() const { return ((TH * TW + 15) / 16 + 3) / 4; }
+  int C3 = 0, act3 = ACT_NONE;
   DevBuf d_w3, d_b3;
   // can a C->C bottleneck on an h x w map (batch_hint images) run fused?  (LDS capacity, tile limits); cv2 = nullptr: without tail
-  static bool supported(int prec, int impl, int c_phys, int h, int w, int batch_hint, const Cv2* cv2 = nullptr);
+  static bool supported(int prec, int impl, int c_phys, int h, int w, int batch_hint, const Cv2* cv2 = nullptr) {
+    return impl == IMPL_MFMA && cplan::plan_bneck(prec, c_phys, h, w, batch_hint, cv2).ok;
+  }
   // weights as for ConvLayer::build: fp32 [C][9][C] over physical channels, bias [C]
   void build(int prec, int c_phys, const std::vector<float>& wa, const std::vector<float>& ba, const std::vector<float>& wb,
              const std::vector<float>& bb, int h, int w, int batch_hint, const Cv2* cv2 = nullptr);
   // without cv2: out = bottleneck output.  With cv2: cat = the concat buffer view (its leading cat_global channels are read),
   // out = cv2's output view; the bottleneck output itself is not stored.
   void launch(const View& in, const View& out, int N, hipStream_t st, const View* cat = nullptr) const;
- private:
-  // kg_cl > 0: try the CL variant with kg_cl staged K groups per pixel first (cl_out says whether it was taken)
-  static bool plan(int prec, int c_phys, int h, int w, int batch_hint, size_t extra_lds, bool tail, int& th, int& tw, int& lw, size_t& lds,
-                   int kg_cl = 0, bool* cl_out = nullptr, int* psa_out = nullptr);
-  static bool cv2_shape(int prec, int c_phys, const Cv2& cv2, int& t2, int& kg, int& sg);
+  // one name per kernel instantiation <NT, P1, P2, T2, SG> (what rocprofv3 lists as separate kernels), without the precision suffix
+  std::string kernel_name() const;
 };
 
 // First layer: 3x3 stride-2 conv reading the uint8 BGR image directly.
@@ -100,6 +94,7 @@ struct StemLayer {
   void launch(const uint8_t* img, int N, int Hin, int Win, const View& out, hipStream_t st) const;
   // stem + the following stride-2 3x3 conv (+ its fused 1x1 tail) in one launch (stem_block_kernel); out = the tail's output
   bool block_supported(const ConvLayer& c1) const;
+  const char* kernel_name(bool block) const { return !block ? "stem_conv" : CO == 16 ? "stem_block16" : "stem_block"; }
   void launch_block(const uint8_t* img, int N, int Hin, int Win, const ConvLayer& c1, const View& out, hipStream_t st) const;
 };
 

@@ -15,6 +15,8 @@
 #include "conv.h"
 #include "conv_bounds.h"
 #include <type_traits>
+#include <algorithm>
+#include <utility>
 
 namespace lp {
 
@@ -413,13 +415,13 @@ __device__ __forceinline__ void epilogue_flat(const ConvArgs& a, const floatx4 (
 }
 
 // ------------------------------------------------------------------------------------
-// 3x3 (pad 1, stride 1|2) implicit GEMM.  One workgroup = bwh x bww waves; each wave owns
+// 3x3 (pad 1, stride 1) implicit GEMM.  One workgroup = bwh x bww waves; each wave owns
 // a 4-row x 20-column strip of output pixels = five 4x4 patches (one MFMA column tile
 // each) x NT 16-channel tiles.  20 divides every level of a 640 input (160/80/40/20), so
 // no lane is wasted there; other sizes are masked.  Per K chunk (CK input channels) the
 // block stages the halo'd input tile and the chunk's weight fragments in LDS.
 // LDS image of the input: [IH][LW] pixels x PS bytes, PS and LW chosen by lds_pixel_slots /
-// lds_row_width so that a B-fragment ds_read_b128 (4x4 pixels x 4 K groups) is conflict-free.
+// lds_row_width (conv_plan.h) so that a B-fragment ds_read_b128 (4x4 pixels x 4 K groups) is conflict-free.
 // ------------------------------------------------------------------------------------
 // second launch-bound = waves per SIMD the register allocation must allow: the narrow variants run many
 // short-lived workgroups and live off occupancy (4 waves/SIMD = 128 VGPRs), the wide ones off MFMA tiles
@@ -428,7 +430,7 @@ __device__ __forceinline__ void epilogue_flat(const ConvArgs& a, const floatx4 (
   __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(gptr),          \
                                    (void __attribute__((address_space(3)))*)(lptr), 16, 0, 0)
 
-template <typename T, int NT, int STRIDE, int T2 = 0>
+template <typename T, int NT, int T2 = 0>
 __global__ __launch_bounds__(320, (NT <= 2 ? 4 : ((NT == 4 && (T2 > 0 || sizeof(T) == 4)) ? 2 : 3))) void conv3x3_mfma_kernel(const ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int G = Tr<T>::G;
@@ -446,8 +448,8 @@ __global__ __launch_bounds__(320, (NT <= 2 ? 4 : ((NT == 4 && (T2 > 0 || sizeof(
   const int n = a.tile_major ? blockIdx.y : blockIdx.x, ns = blockIdx.z;
   if (a.m_dyn && n >= *a.m_dyn) return;   // classifier layers: the grid is sized for the ROI capacity (block-uniform exit)
   const int oy0 = ty * TH, ox0 = tx * TW;
-  const int iy0 = oy0 * STRIDE - 1, ix0 = ox0 * STRIDE - 1;
-  const int IH = (TH - 1) * STRIDE + 3, IW = (TW - 1) * STRIDE + 3;
+  const int iy0 = oy0 - 1, ix0 = ox0 - 1;
+  const int IH = TH + 2, IW = TW + 2;
   const int Sc = a.steps_per_chunk, CGc = a.CGc, LW = a.LW, PS = a.PS;
 
   // LDS: [tap-offset table 512 B] then per buffer (two when the layer has several K chunks):
@@ -469,7 +471,7 @@ __global__ __launch_bounds__(320, (NT <= 2 ? 4 : ((NT == 4 && (T2 > 0 || sizeof(
 #pragma unroll
   for (int p = 0; p < 5; ++p) {
     const int lx = wx * 20 + p * 4 + (col & 3);
-    pbase[p] = ((ly * STRIDE) * LW + lx * STRIDE) * PS;
+    pbase[p] = (ly * LW + lx) * PS;
   }
   // Staging map.  The LDS image of a tile row is RS consecutive 16-byte slots = pixel pitch x LW, filled by
   // 1 KiB LDS-DMA pieces (64 lanes x 16 B, destination lane-linear).  The (row, piece) items of a chunk are dealt
@@ -1809,37 +1811,21 @@ __global__ __launch_bounds__(256) void stem_block16_kernel(const StemBlockArgs a
 }
 
 // ====================================================================================
-// Host side: weight packing and launch
+// Host side: weight packing and launch.  The tile and split arithmetic and the tables of instantiated variants are in
+// conv_plan.h (namespace cplan): a build() here is "plan, pack, upload", a launch() a lookup in the family's table.
 // ====================================================================================
-static size_t elem_size(int prec) { return prec == LP_FP16 ? 2 : 4; }
 static unsigned div_magic(int d) { return d <= 1 ? 0xffffffffu : (unsigned)((1ull << 32) / (unsigned)d); }
 static bool span_ok(int N, const View& v) { return !v.base || (double)N * v.H * v.W * v.pitch < 2147483648.0; }
+static unsigned rcp16_checked(int d, int range) {
+  const unsigned m = cplan::rcp16(d, range);
+  LP_CHECK(m != 0, LP_ERR_STATE, "reciprocal of %d not exact below %d", d, range);
+  return m;
+}
 
-// LDS geometry of the 3x3 input tile, found by enumerating the ds_read_b128 lane groups
-// ({0-3,12-15,20-27}, ...; MI355X_MICROARCH.md, LDS) over every K step: with cg channel groups
-// per pixel, a pixel pitch of p = (smallest value >= cg with p % 4 == 2) 16-byte slots and a row
-// width = 12 (mod 16) pixels make the 4x4-pixel x 4-K-group fragment read conflict-free (4 LDS
-// cycles); the former odd-pitch rule cost 8.  One group per pixel (cg = 1): pitch 1, row = 4 (mod 16).
-static int lds_pixel_slots(int cg, int stride = 1) {
-  if (cg <= 1) return 1;
-  int p = cg;
-  if (stride == 2) {  // patches of every other pixel: an odd pitch (and a row width = 4 mod 8) is the conflict-free one
-    while (p % 2 != 1) ++p;
-    return p;
-  }
-  while (p % 4 != 2) ++p;
-  return p;
-}
-static int lds_row_width(int iw, int cg, int stride = 1) {
-  int lw = iw;
-  if (stride == 2 && cg > 1) {
-    while (lw % 8 != 4) ++lw;
-    return lw;
-  }
-  const int want = cg <= 1 ? 4 : 12;
-  while (lw % 16 != want) ++lw;
-  return lw;
-}
+// f(integral_constant<size_t, i>) for every entry i of a cplan table until one returns true: the entry is a constant expression
+// inside f, so the kernels named there are the table's and no others
+template <class F, size_t... I> static bool any_entry(F&& f, std::index_sequence<I...>) { return (f(std::integral_constant<size_t, I>{}) || ...); }
+template <class E, size_t N, class F> static bool for_each_entry(const E (&)[N], F&& f) { return any_entry(f, std::make_index_sequence<N>{}); }
 
 static void put_elem(std::vector<uint8_t>& buf, size_t idx, int prec, float v) {
   if (prec == LP_FP16) {
@@ -1849,6 +1835,47 @@ static void put_elem(std::vector<uint8_t>& buf, size_t idx, int prec, float v) {
     memcpy(&buf[idx * 4], &v, 4);
   }
 }
+static void upload(DevBuf& d, const void* p, size_t bytes) {
+  d.alloc(bytes);
+  LP_HIP(hipMemcpy(d.p, p, bytes, hipMemcpyHostToDevice));
+}
+// bias of C channels (nullptr or shorter: zeros), padded to round_up(C, 64) + 64 floats so that every quad load is in bounds and
+// the buffer ends in 64 zeros (ConvArgs::zeros)
+static void upload_padded_bias(DevBuf& d, int C, const std::vector<float>* bias) {
+  std::vector<float> b(round_up(C, 64) + 64, 0.f);
+  for (int c = 0; c < C && bias && c < (int)bias->size(); ++c) b[c] = (*bias)[c];
+  upload(d, b.data(), b.size() * 4);
+}
+// A fragments [T2][sg + S2][lane][G] of a fused 1x1 tail to cout2 channels, weights w2 [cout2][row]: the last S2 K steps walk the
+// cmid intermediate channels a lane's accumulators hold -- lane group g, step s2, element j -> channel g * 4 * nt + G * s2 + j,
+// at column col0 of a weight row; the sg steps in front (BottleneckPair's cv2) walk kg stored K groups from column 0
+static std::vector<uint8_t> pack_tail(int prec, int nt, int cmid, int cout2, const std::vector<float>& w2, int row, int col0, int kg = 0, int sg = 0) {
+  const int G = cplan::group(prec), T2 = ceil_div(cout2, 16), ST = sg + cplan::tail_steps(prec, nt);
+  std::vector<uint8_t> buf((size_t)T2 * ST * 64 * 16, 0);
+  for (int t = 0; t < T2; ++t)
+    for (int s = 0; s < ST; ++s)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int g = lane >> 4, m = lane & 15, gm = m >> 2, r = m & 3;
+        const int oc = gm * 4 * T2 + t * 4 + r;  // same row permutation as the main GEMM, for vector stores
+        if (oc >= cout2) continue;
+        for (int j = 0; j < G; ++j) {
+          int ch;
+          if (s < sg) {
+            const int q = 4 * s + g;
+            if (q >= kg) continue;
+            ch = q * G + j;
+          } else {
+            const int s2 = s - sg;
+            if (G * s2 + j >= 4 * nt) continue;       // half-filled last K step (odd NT, fp16)
+            const int mid = g * 4 * nt + G * s2 + j;
+            if (mid >= cmid) continue;                // padding rows of a half-filled last channel tile
+            ch = col0 + mid;
+          }
+          put_elem(buf, ((size_t)(t * ST + s) * 64 + lane) * G + j, prec, w2[(size_t)oc * row + ch]);
+        }
+      }
+  return buf;
+}
 
 void ConvLayer::build(int prec_, int impl_, int k_, int stride_, int cin, int cout, int act_,
                       const std::vector<float>& w_phys, const std::vector<float>& bias_phys, int hout, int wout, int batch_hint,
@@ -1857,129 +1884,19 @@ void ConvLayer::build(int prec_, int impl_, int k_, int stride_, int cin, int co
   LP_CHECK(k == 1 || k == 3, LP_ERR_GRAPH, "conv kernel size %d unsupported", k);
   LP_CHECK(Cin % 8 == 0 && Cout % 8 == 0, LP_ERR_GRAPH, "physical channels must be multiples of 8");
   const int taps = k * k;
-  const int G = prec == LP_FP16 ? 8 : 4;
-  const size_t es = elem_size(prec);
-  const int tiles_total = ceil_div(Cout, 16);
+  const int G = cplan::group(prec);
   w_host = w_phys;
   b_host = bias_phys;
-
-  // bias, padded so every quad load is in bounds
-  std::vector<float> b(round_up(Cout, 64) + 64, 0.f);
-  for (int c = 0; c < Cout; ++c) b[c] = bias_phys.empty() ? 0.f : bias_phys[c];
-  d_bias.alloc(b.size() * 4);
-  LP_HIP(hipMemcpy(d_bias.p, b.data(), b.size() * 4, hipMemcpyHostToDevice));
+  upload_padded_bias(d_bias, Cout, &bias_phys);
 
   if (impl == IMPL_NAIVE) {
-    std::vector<uint8_t> buf((size_t)Cout * taps * Cin * es);
+    std::vector<uint8_t> buf((size_t)Cout * taps * Cin * (prec == LP_FP16 ? 2 : 4));
     for (size_t i = 0; i < (size_t)Cout * taps * Cin; ++i) put_elem(buf, i, prec, w_phys[i]);
-    d_w.alloc(buf.size());
-    LP_HIP(hipMemcpy(d_w.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
+    upload(d_w, buf.data(), buf.size());
     return;
   }
-
-  // channel tiles per block: 4 when the layer has plenty of pixel tiles; fewer (more channel splits -> more
-  // workgroups, but the input is read once per split) when the map is small.  The floor of 128 workgroups is
-  // measured on the pipelined benchmark (3 batches in flight share the GPU: 512 gave the best isolated layer
-  // times but 5 % less throughput; LITEPI_MIN_WGS overrides it for such sweeps)
-  auto pick_nt = [&](long pixel_blocks) {
-    if (full_n) return tiles_total;  // a fused tail needs every intermediate channel in one workgroup
-    int nt = tiles_total >= 4 ? 4 : tiles_total;
-    if (tiles_total % 4 != 0 && tiles_total > 4) nt = (tiles_total % 3 == 0) ? 3 : 4;
-    static const long min_wgs = getenv("LITEPI_MIN_WGS") ? atol(getenv("LITEPI_MIN_WGS")) : 128;
-    while (nt > 1 && pixel_blocks * ceil_div(tiles_total, nt) < min_wgs) nt = (nt == 4 && tiles_total % 4 == 0) ? 2 : nt - 1;
-    return nt;
-  };
-  const int B = batch_hint > 0 ? batch_hint : 1;
-
-  // stride-2: gather straight from global memory (conv3x3s2_direct_kernel).  LITEPI_S2_STAGED=<min Cin> routes deep-K
-  // layers without a fused tail through the LDS-staged kernel instead (A/B switch; slower since the gather kernel
-  // keeps its loads a few K steps ahead)
-  static const int s2_staged_min_cin = getenv("LITEPI_S2_STAGED") ? atoi(getenv("LITEPI_S2_STAGED")) : 1 << 30;
-  direct = (k == 3 && stride == 2) && (full_n || Cin < s2_staged_min_cin);
-  if (single_chunk) {
-    // weights only (BottleneckPair): every channel tile in one workgroup, all of K in one chunk
-    LP_CHECK(k == 3 && stride == 1, LP_ERR_STATE, "single-chunk packing is for 3x3 stride-1 layers");
-    direct = false;
-    NT = tiles_total; nsplits = 1; CK = Cin; CGc = Cin / G; nchunks = 1;
-    steps = ceil_div(taps * CGc, 4);
-    PS = lds_pixel_slots(CGc) * 16;
-    LP_CHECK(steps * 4 <= 128, LP_ERR_GRAPH, "conv3x3: too many K steps for one chunk");
-  } else if (direct) {
-    // stride-2: no input staging (see conv3x3s2_direct_kernel); all of K for this block's channel split in LDS
-    NT = pick_nt(ceil_div((long)B * hout * wout, 256));
-    CK = Cin;
-    CGc = Cin / G;
-    nchunks = 1;
-    steps = ceil_div(taps * CGc, 4);
-    while (!full_n && NT > 1 && (size_t)steps * NT * 1024 > 64 * 1024) --NT;
-    nsplits = ceil_div(tiles_total, NT);
-    lds_bytes = (size_t)steps * NT * 1024 + (size_t)steps * 4 * 8;  // weight fragments + K-group table
-    LP_CHECK(lds_bytes <= 160 * 1024, LP_ERR_GRAPH, "conv3x3/s2 weights do not fit LDS (%zu B)", lds_bytes);
-  } else if (k == 3) {
-    // Tile shape (bwh x bww waves of 4x20 pixels) and K chunk CK (multiple of 8, divides Cin):
-    // the halo'd input tile plus the chunk's weight fragments must fit the LDS budget (two
-    // workgroups per CU).  Priority: no idle lanes on this map, >= 16-channel chunks, then the
-    // largest workgroup (weights are staged once per workgroup), then the largest chunk.
-    const bool small_map = (hout <= 20 && wout <= 20);
-    const int cand[6][2] = {{5, 1}, {2, 2}, {2, 1}, {1, 2}, {4, 1}, {1, 1}};
-    static const size_t budget = (getenv("LITEPI_LDS_KB") ? atol(getenv("LITEPI_LDS_KB")) : 80) * 1024;
-    long best_score = -1;
-    CK = 8; bwh = 1; bww = 1; LW = 0; NT = 1;
-    for (int ci = 0; ci < 6; ++ci) {
-      const int h = cand[ci][0], w = cand[ci][1];
-      if (!small_map && (h == 5 || h == 4)) continue;
-      const int TH = 4 * h, TW = 20 * w;
-      const int IH = (TH - 1) * stride + 3, IW = (TW - 1) * stride + 3;
-      const int tiles = ceil_div(hout, TH) * ceil_div(wout, TW);
-      const int nt = pick_nt((long)tiles * B);
-      // K chunk: everything at once when it fits (one round trip, no K padding between chunks), else the
-      // largest chunk whose two buffers fit (the next chunk's LDS-DMA flies during this chunk's MFMAs)
-      int ck_fit = 0, lw = 0;
-      for (int ck = 8; ck <= Cin && ck <= 64; ck += 8) {
-        if (Cin % ck) continue;
-        const int cgc = ck / G;
-        const int l = lds_row_width(IW, cgc, stride);
-        const size_t one = (size_t)ceil_div(taps * cgc, 4) * nt * 1024 + (size_t)IH * l * lds_pixel_slots(cgc, stride) * 16;
-        const size_t lds = 512 + (ck == Cin ? one : 2 * one);
-        if (lds <= budget && ceil_div(taps * cgc, 4) * 4 <= 128 && ceil_div(l * lds_pixel_slots(cgc, stride), 64) <= 8) { ck_fit = ck; lw = l; }
-      }
-      if (!ck_fit) continue;
-      const int util = (int)(100.0 * hout * wout / ((double)tiles * TH * TW));
-      const long score = (util >= 95 ? 3 : util >= 80 ? 2 : util >= 60 ? 1 : 0) * 100000L +
-                         ((ck_fit >= 16 || ck_fit == Cin) ? 10000L : 0L) + (long)h * w * 1000L + ck_fit;
-      if (score > best_score) { best_score = score; CK = ck_fit; bwh = h; bww = w; LW = lw; NT = nt; }
-    }
-    LP_CHECK(best_score >= 0, LP_ERR_GRAPH, "conv3x3 %d->%d: no tile fits LDS", Cin, Cout);
-    nsplits = ceil_div(tiles_total, NT);
-    const int IH = (4 * bwh - 1) * stride + 3;
-    CGc = CK / G;
-    PS = lds_pixel_slots(CGc, stride) * 16;
-    nchunks = Cin / CK;
-    steps = ceil_div(taps * CGc, 4);
-    LP_CHECK(steps * 4 <= 128, LP_ERR_GRAPH, "conv3x3: too many K steps per chunk");
-    lds_bytes = 512 + (nchunks > 1 ? 2 : 1) * ((size_t)steps * NT * 1024 + (size_t)IH * LW * PS);
-    LP_CHECK(ceil_div(LW * (PS / 16), 64) <= 8, LP_ERR_GRAPH, "conv3x3: LDS tile row too wide");
-    auto rcp16 = [&](int d, int range) {  // x / d == (x * m) >> 16 for x < range (kernel prologue)
-      const unsigned m = (65536u + d - 1) / d;
-      for (int x = 0; x < range; ++x) LP_CHECK((int)((x * m) >> 16) == x / d, LP_ERR_STATE, "reciprocal of %d not exact at %d", d, x);
-      return m;
-    };
-    rcp_cg = rcp16(CGc, 128);
-    rcp_ps = rcp16(PS / 16, 512);
-    rcp_pcs = rcp16(ceil_div(LW * (PS / 16), 64), 1024);
-    LP_CHECK(lds_bytes <= 160 * 1024, LP_ERR_GRAPH, "conv3x3 tile does not fit LDS (%zu B)", lds_bytes);
-  } else {
-    NT = pick_nt(ceil_div((long)B * hout * wout, 256));
-    CK = Cin;
-    CGc = Cin / G;
-    nchunks = 1;
-    steps = ceil_div(CGc, 4);
-    // all K of this block's channel split stays in LDS: fewer channel tiles per block for deep K
-    while (NT > 1 && (size_t)steps * NT * 1024 > 96 * 1024) --NT;
-    nsplits = ceil_div(tiles_total, NT);
-    lds_bytes = (size_t)steps * NT * 1024;
-    LP_CHECK(lds_bytes <= 160 * 1024, LP_ERR_GRAPH, "conv1x1 weights do not fit LDS (%zu B)", lds_bytes);
-  }
+  static_cast<cplan::ConvTiling&>(*this) = cplan::plan_conv(prec, k, stride, Cin, Cout, hout, wout, batch_hint, full_n, single_chunk);
+  LP_CHECK(!plan_err, single_chunk ? LP_ERR_STATE : LP_ERR_GRAPH, "conv %s %d->%d on %dx%d: %s", name.c_str(), Cin, Cout, hout, wout, plan_err);
 
   // fragment-ordered weights: [split][chunk][step][tile][lane][G]
   const size_t nfrag = (size_t)nsplits * nchunks * steps * NT * 64;
@@ -2001,16 +1918,7 @@ void ConvLayer::build(int prec_, int impl_, int k_, int stride_, int cin, int co
               put_elem(buf, f * G + j, prec, w_phys[((size_t)oc * taps + tap) * Cin + ci]);
             }
           }
-  d_w.alloc(buf.size());
-  LP_HIP(hipMemcpy(d_w.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
-}
-
-bool ConvLayer::tail_supported(int k, int stride, int cmid_phys, int cout2_phys) {
-  if (k != 3 || cmid_phys % 8 != 0) return false;
-  const int nt = ceil_div(cmid_phys, 16), t2 = ceil_div(cout2_phys, 16);  // a half-filled last tile has zero weights and bias
-  if (stride == 1) return (nt == 4 && t2 == 4) || (nt == 2 && t2 == 1);
-  if (stride == 2) return (nt == 1 && t2 == 1) || (nt == 2 && t2 == 2) || (nt == 4 && t2 == 4);
-  return false;
+  upload(d_w, buf.data(), buf.size());
 }
 
 void ConvLayer::attach_tail(int cout2_phys, int act2_, const std::vector<float>& w2_phys, const std::vector<float>& bias2_phys) {
@@ -2021,67 +1929,60 @@ void ConvLayer::attach_tail(int cout2_phys, int act2_, const std::vector<float>&
   act2 = act2_;
   w2_host = w2_phys;
   b2_host = bias2_phys;
-  const int G = prec == LP_FP16 ? 8 : 4;
-  const int S2 = prec == LP_FP16 ? (NT + 1) / 2 : NT;
-  std::vector<uint8_t> buf((size_t)T2 * S2 * 64 * 16, 0);
-  for (int t = 0; t < T2; ++t)
-    for (int s2 = 0; s2 < S2; ++s2)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int g = lane >> 4, m = lane & 15, gm = m >> 2, r = m & 3;
-        const int oc = gm * 4 * T2 + t * 4 + r;  // same row permutation as the main GEMM, for vector stores
-        if (oc >= cout2_phys) continue;
-        for (int j = 0; j < G; ++j) {
-          if (G * s2 + j >= 4 * NT) continue;       // half-filled last K step (odd NT, fp16)
-          const int mid = g * 4 * NT + G * s2 + j;  // the intermediate channel this lane's accumulators hold at (s2, j)
-          if (mid >= Cout) continue;                // padding rows of a half-filled last channel tile
-          put_elem(buf, ((size_t)(t * S2 + s2) * 64 + lane) * G + j, prec, w2_phys[(size_t)oc * Cout + mid]);
-        }
-      }
-  d_w2.alloc(buf.size());
-  LP_HIP(hipMemcpy(d_w2.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
-  std::vector<float> b(round_up(cout2_phys, 64) + 64, 0.f);
-  for (int c = 0; c < cout2_phys && c < (int)bias2_phys.size(); ++c) b[c] = bias2_phys[c];
-  d_bias2.alloc(b.size() * 4);
-  LP_HIP(hipMemcpy(d_bias2.p, b.data(), b.size() * 4, hipMemcpyHostToDevice));
+  const std::vector<uint8_t> buf = pack_tail(prec, NT, Cout, cout2_phys, w2_phys, Cout, 0);
+  upload(d_w2, buf.data(), buf.size());
+  upload_padded_bias(d_bias2, cout2_phys, &bias2_phys);
 }
 
-template <typename T, int NT>
-static void launch3x3(const ConvArgs& a, int stride, dim3 grid, int threads, size_t lds, hipStream_t st) {
-  if (stride == 1) {
-    set_max_dynamic_lds(reinterpret_cast<const void*>(conv3x3_mfma_kernel<T, NT, 1>), 160 * 1024);
-    LP_LAUNCH((conv3x3_mfma_kernel<T, NT, 1>), grid, dim3(threads), lds, st, a);
-  } else {
-    set_max_dynamic_lds(reinterpret_cast<const void*>(conv3x3_mfma_kernel<T, NT, 2>), 160 * 1024);
-    LP_LAUNCH((conv3x3_mfma_kernel<T, NT, 2>), grid, dim3(threads), lds, st, a);
-  }
+std::string ConvLayer::kernel_name(bool up) const {
+  std::string s = std::string(family_name()) + (T2 ? "+1x1" : "");
+  if (impl != IMPL_NAIVE) s += T2 ? fmt("<%d,%d>", NT, T2) : (up ? fmt("<%d,up>", NT) : fmt("<%d>", NT));
+  return s;
 }
 
-template <typename T, int NT, int U>
-static void launch_s2_u(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  set_max_dynamic_lds(reinterpret_cast<const void*>(conv3x3s2_direct_kernel<T, NT, 4, 0, U>), 160 * 1024);
-  LP_LAUNCH((conv3x3s2_direct_kernel<T, NT, 4, 0, U>), grid, dim3(256), lds, st, a);
+// ---- ConvLayer::launch: one function per family, each a lookup of (NT, T2) in the family's table
+template <typename T> static bool launch_s2(const ConvLayer& L, const ConvArgs& a, dim3 grid, hipStream_t st) {
+  return for_each_entry(cplan::kConvS2, [&](auto i) {
+    constexpr cplan::Variant v = cplan::kConvS2[decltype(i)::value];
+    if (L.NT != v.nt || L.T2 != v.t2) return false;
+    if (cplan::s2_unroll(a.steps) == 4) {
+      set_max_dynamic_lds(reinterpret_cast<const void*>(conv3x3s2_direct_kernel<T, v.nt, 4, v.t2, 4>), 160 * 1024);
+      LP_LAUNCH((conv3x3s2_direct_kernel<T, v.nt, 4, v.t2, 4>), grid, dim3(256), L.lds_bytes, st, a);
+    } else {
+      set_max_dynamic_lds(reinterpret_cast<const void*>(conv3x3s2_direct_kernel<T, v.nt, 4, v.t2, 1>), 160 * 1024);
+      LP_LAUNCH((conv3x3s2_direct_kernel<T, v.nt, 4, v.t2, 1>), grid, dim3(256), L.lds_bytes, st, a);
+    }
+    return true;
+  });
 }
-template <typename T, int NT>
-static void launch_s2(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  if (a.steps >= 5) launch_s2_u<T, NT, 4>(a, grid, lds, st);
-  else launch_s2_u<T, NT, 1>(a, grid, lds, st);
+template <typename T> static bool launch_3x3(const ConvLayer& L, const ConvArgs& a, dim3 grid, hipStream_t st) {
+  return for_each_entry(cplan::kConv3x3, [&](auto i) {
+    constexpr cplan::Variant v = cplan::kConv3x3[decltype(i)::value];
+    if (L.NT != v.nt || L.T2 != v.t2) return false;
+    set_max_dynamic_lds(reinterpret_cast<const void*>(conv3x3_mfma_kernel<T, v.nt, v.t2>), 160 * 1024);
+    LP_LAUNCH((conv3x3_mfma_kernel<T, v.nt, v.t2>), grid, dim3(64 * L.bwh * L.bww), L.lds_bytes, st, a);
+    return true;
+  });
+}
+template <typename T, int EPI, bool UPS> static bool launch_1x1(const ConvLayer& L, const ConvArgs& a, dim3 grid, hipStream_t st) {
+  return for_each_entry(cplan::kConv1x1, [&](auto i) {
+    constexpr int nt = cplan::kConv1x1[decltype(i)::value];
+    if (L.NT != nt) return false;
+    set_max_dynamic_lds(reinterpret_cast<const void*>(conv1x1_mfma_kernel<T, nt, 4, EPI, UPS>), 160 * 1024);
+    LP_LAUNCH((conv1x1_mfma_kernel<T, nt, 4, EPI, UPS>), grid, dim3(256), L.lds_bytes, st, a);
+    return true;
+  });
+}
+template <typename T> static bool launch_1x1(const ConvLayer& L, const ConvArgs& a, dim3 grid, hipStream_t st) {
+  if (a.up) return launch_1x1<T, EPI_PLAIN, true>(L, a, grid, st);
+  if (a.x1) return launch_1x1<T, EPI_SHUFFLE, false>(L, a, grid, st);
+  return launch_1x1<T, EPI_PLAIN, false>(L, a, grid, st);
 }
 
-template <typename T, int NT, int NP, int EPI>
-static void launch1x1_(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  set_max_dynamic_lds(reinterpret_cast<const void*>(conv1x1_mfma_kernel<T, NT, NP, EPI>), 160 * 1024);
-  LP_LAUNCH((conv1x1_mfma_kernel<T, NT, NP, EPI>), grid, dim3(256), lds, st, a);
-}
-
-template <typename T, int NT>
-static void launch1x1(const ConvArgs& a, bool shuffle, dim3 grid, size_t lds, hipStream_t st) {
-  if (a.up) {
-    set_max_dynamic_lds(reinterpret_cast<const void*>(conv1x1_mfma_kernel<T, NT, 4, EPI_PLAIN, true>), 160 * 1024);
-    LP_LAUNCH((conv1x1_mfma_kernel<T, NT, 4, EPI_PLAIN, true>), grid, dim3(256), lds, st, a);
-  } else if (shuffle)
-    launch1x1_<T, NT, 4, EPI_SHUFFLE>(a, grid, lds, st);
-  else
-    launch1x1_<T, NT, 4, EPI_PLAIN>(a, grid, lds, st);
+// A/B switch: the block order from before the XCD-aware one (tile index fastest), a kernel argument of the 3x3 and bottleneck kernels
+static bool tile_major_order() {
+  static const bool on = getenv("LITEPI_TILE_MAJOR") != nullptr;
+  return on;
 }
 
 void ConvLayer::launch(const ConvIO& io, hipStream_t st) const {
@@ -2105,7 +2006,7 @@ void ConvLayer::launch(const ConvIO& io, hipStream_t st) const {
   a.zeros = d_bias.as<float>() + round_up(Cout, 64);  // the bias buffer ends in 64 zero floats
   LP_CHECK(io.in.C + (io.up.base ? io.up.C : 0) == Cin, LP_ERR_STATE, "conv input view has %d channels, layer expects %d", io.in.C, Cin);
   if (io.up.base) {
-    const int Gk = prec == LP_FP16 ? 8 : 4;
+    const int Gk = cplan::group(prec);
     LP_CHECK(k == 1 && impl == IMPL_MFMA && !io.x1.base && !io.m_dyn && !io.out_f32 && io.up.C % Gk == 0 && (io.up.pitch % Gk) == 0 &&
                  io.up.H * 2 == io.out.H && io.up.W * 2 == io.out.W, LP_ERR_STATE, "conv %s: fused upsample source does not fit", name.c_str());
     a.up = io.up.base; a.up_pitch = io.up.pitch; a.up_cg = io.up.C / Gk;
@@ -2125,303 +2026,123 @@ void ConvLayer::launch(const ConvIO& io, hipStream_t st) const {
     return;
   }
 
+  LP_CHECK(!T2 || !io.res.base, LP_ERR_STATE, "fused tail with residual unsupported");
+  const long ntiles = ((long)a.M + 255) / 256;
+  const dim3 flat_grid((unsigned)(ntiles < 4096 ? (ntiles > 0 ? ntiles : 1) : 4096), nsplits);   // 256-pixel blocks, grid-stride
+  bool ok;
   if (direct) {
     LP_CHECK(!io.x1.base && !io.out_f32, LP_ERR_STATE, "conv3x3/s2: unsupported epilogue");
-    const long ntiles = ((long)a.M + 255) / 256;
-    dim3 grid((unsigned)(ntiles < 4096 ? (ntiles > 0 ? ntiles : 1) : 4096), nsplits);
-#define LP_LD(TT)                                                                                      \
-  switch (NT) {                                                                                        \
-    case 1: launch_s2<TT, 1>(a, grid, lds_bytes, st); break;                                           \
-    case 2: launch_s2<TT, 2>(a, grid, lds_bytes, st); break;                                           \
-    case 3: launch_s2<TT, 3>(a, grid, lds_bytes, st); break;                                           \
-    default: launch_s2<TT, 4>(a, grid, lds_bytes, st); break;                                          \
-  }
-    if (T2) {
-      LP_CHECK(!io.res.base, LP_ERR_STATE, "fused tail with residual unsupported");
-#define LP_LDT_(TT, N_, T_, U_)                                                                                              \
-  {                                                                                                                          \
-    set_max_dynamic_lds(reinterpret_cast<const void*>(conv3x3s2_direct_kernel<TT, N_, 4, T_, U_>), 160 * 1024);                                                                                                              \
-    LP_LAUNCH((conv3x3s2_direct_kernel<TT, N_, 4, T_, U_>), grid, dim3(256), lds_bytes, st, a);                      \
-  }
-#define LP_LDT(TT, N_, T_)                               \
-  {                                                      \
-    if (a.steps >= 5) LP_LDT_(TT, N_, T_, 4) else LP_LDT_(TT, N_, T_, 1) \
-  }
-      if (NT == 1 && T2 == 1) { if (f16) LP_LDT(half_t, 1, 1) else LP_LDT(float, 1, 1) }
-      else if (NT == 2 && T2 == 2) { if (f16) LP_LDT(half_t, 2, 2) else LP_LDT(float, 2, 2) }
-      else if (NT == 4 && T2 == 4) { if (f16) LP_LDT(half_t, 4, 4) else LP_LDT(float, 4, 4) }
-      else throw Error(LP_ERR_STATE, "conv3x3/s2: unsupported fused tail shape");
-#undef LP_LDT_
-#undef LP_LDT
-    } else if (f16) { LP_LD(half_t) } else { LP_LD(float) }
-#undef LP_LD
+    ok = f16 ? launch_s2<half_t>(*this, a, flat_grid, st) : launch_s2<float>(*this, a, flat_grid, st);
   } else if (k == 3) {
-    LP_CHECK(!io.x1.base && !io.out_f32, LP_ERR_STATE, "conv3x3: unsupported epilogue");
-    const int TH = 4 * bwh, TW = 20 * bww;
-    a.tiles_x = ceil_div(a.Wout, TW);
-    a.tiles_y = ceil_div(a.Hout, TH);
-    static const bool tile_major = getenv("LITEPI_TILE_MAJOR") != nullptr;  // A/B switch: pre-XCD-aware block order
-    a.tile_major = tile_major;
+    LP_CHECK(!io.x1.base && !io.out_f32 && stride == 1, LP_ERR_STATE, "conv3x3: unsupported epilogue");
+    a.tiles_x = ceil_div(a.Wout, 20 * bww);
+    a.tiles_y = ceil_div(a.Hout, 4 * bwh);
+    a.tile_major = tile_major_order();
     dim3 grid(io.N, a.tiles_x * a.tiles_y, nsplits);
-    if (tile_major) grid = dim3(a.tiles_x * a.tiles_y, io.N, nsplits);
-    const int threads = 64 * bwh * bww;
-    // 16-bit reciprocals for the kernel's prologue: x / d == (x * ceil(65536 / d)) >> 16 on the ranges used
-    auto rcp16 = [&](int d, int range) {
-      const unsigned m = (65536u + d - 1) / d;
-      for (int x = 0; x < range; ++x) LP_CHECK((int)((x * m) >> 16) == x / d, LP_ERR_STATE, "reciprocal of %d not exact at %d", d, x);
-      return m;
-    };
-    a.rcp_tx = rcp16(a.tiles_x, a.tiles_x * a.tiles_y);
-    a.rcp_cg = rcp_cg; a.rcp_ps = rcp_ps; a.rcp_pcs = rcp_pcs;  // checked once in build()
-#define LP_L3(TT)                                                                  \
-  switch (NT) {                                                                    \
-    case 1: launch3x3<TT, 1>(a, stride, grid, threads, lds_bytes, st); break;      \
-    case 2: launch3x3<TT, 2>(a, stride, grid, threads, lds_bytes, st); break;      \
-    case 3: launch3x3<TT, 3>(a, stride, grid, threads, lds_bytes, st); break;      \
-    default: launch3x3<TT, 4>(a, stride, grid, threads, lds_bytes, st); break;     \
-  }
-    if (T2) {
-      LP_CHECK(!io.res.base && stride == 1, LP_ERR_STATE, "fused tail with residual unsupported");
-#define LP_L3T(TT, N_, T_)                                                                                              \
-  {                                                                                                                     \
-    set_max_dynamic_lds(reinterpret_cast<const void*>(conv3x3_mfma_kernel<TT, N_, 1, T_>), 160 * 1024);                                                                                                         \
-    LP_LAUNCH((conv3x3_mfma_kernel<TT, N_, 1, T_>), grid, dim3(threads), lds_bytes, st, a);                      \
-  }
-      if (NT == 4 && T2 == 4) { if (f16) LP_L3T(half_t, 4, 4) else LP_L3T(float, 4, 4) }
-      else if (NT == 2 && T2 == 1) { if (f16) LP_L3T(half_t, 2, 1) else LP_L3T(float, 2, 1) }
-      else throw Error(LP_ERR_STATE, "conv3x3: unsupported fused tail shape");
-#undef LP_L3T
-    } else if (f16) { LP_L3(half_t) } else { LP_L3(float) }
-#undef LP_L3
+    if (a.tile_major) grid = dim3(a.tiles_x * a.tiles_y, io.N, nsplits);
+    // 16-bit reciprocals for the kernel's prologue
+    a.rcp_tx = rcp16_checked(a.tiles_x, a.tiles_x * a.tiles_y);
+    a.rcp_cg = rcp_cg; a.rcp_ps = rcp_ps; a.rcp_pcs = rcp_pcs;  // checked once in plan_conv
+    ok = f16 ? launch_3x3<half_t>(*this, a, grid, st) : launch_3x3<float>(*this, a, grid, st);
   } else {
     LP_CHECK(stride == 1, LP_ERR_GRAPH, "strided 1x1 conv unsupported");
-    const long ntiles = ((long)a.M + 255) / 256;
-    dim3 grid((unsigned)(ntiles < 4096 ? (ntiles > 0 ? ntiles : 1) : 4096), nsplits);
+    dim3 grid = flat_grid;
     if (io.m_dyn) grid.x = 1024 / nsplits > 64 ? 1024 / nsplits : 64;
-    const bool shuffle = io.x1.base != nullptr;
-#define LP_L1(TT)                                                           \
-  switch (NT) {                                                             \
-    case 1: launch1x1<TT, 1>(a, shuffle, grid, lds_bytes, st); break;       \
-    case 2: launch1x1<TT, 2>(a, shuffle, grid, lds_bytes, st); break;       \
-    case 3: launch1x1<TT, 3>(a, shuffle, grid, lds_bytes, st); break;       \
-    default: launch1x1<TT, 4>(a, shuffle, grid, lds_bytes, st); break;      \
+    ok = f16 ? launch_1x1<half_t>(*this, a, grid, st) : launch_1x1<float>(*this, a, grid, st);
   }
-    if (f16) { LP_L1(half_t) } else { LP_L1(float) }
-#undef LP_L1
-  }
+  LP_CHECK(ok, LP_ERR_STATE, "conv %s: no %s kernel for NT %d, T2 %d", name.c_str(), family_name(), NT, T2);
   LP_HIP(hipGetLastError());
 }
 
 
 // ---- fused bottleneck pair ---------------------------------------------------------------------
-bool BottleneckPair::cv2_shape(int prec, int c, const Cv2& cv2, int& t2, int& kg, int& sg) {
-  const int G = prec == LP_FP16 ? 8 : 4;
-  const int nt = ceil_div(c, 16);
-  if (cv2.cat_global <= 0 || cv2.cat_global % G != 0 || cv2.c3 % 8 != 0) return false;
-  t2 = ceil_div(cv2.c3, 16);
-  kg = cv2.cat_global / G;
-  sg = ceil_div(kg, 4);
-  // kernel instantiations: NT = 1 with T2 in {1, 2}, NT = 2 with T2 in {2, 4}; at most 3 (fp16) / 6 (fp32) gathered K steps
-  if (!((nt == 1 && (t2 == 1 || t2 == 2)) || (nt == 2 && (t2 == 2 || t2 == 4)))) return false;
-  return sg <= (prec == LP_FP16 ? 3 : 6);
-}
-
-bool BottleneckPair::plan(int prec, int c, int h, int w, int batch_hint, size_t extra_lds, bool tail, int& th, int& tw, int& lw, size_t& lds,
-                          int kg_cl, bool* cl_out, int* psa_out) {
-  if (cl_out) *cl_out = false;
-  const int G = prec == LP_FP16 ? 8 : 4;
-  if (c % 8 != 0 || c > 64) return false;
-  const int nt = ceil_div(c, 16), cg = c / G;
-  if (nt > 4) return false;
-  const int steps = ceil_div(9 * cg, 4);
-  if (steps * 4 > 128) return false;
-  const int pss = lds_pixel_slots(cg);
-  // 20x40 / 10x20: 8 tiles on an 80x80 / 40x40 map -- 512 workgroups for a batch of 64, exactly two per CU, instead of 640 (2.5
-  // per CU: the CUs that get three decide the kernel time of these single-round grids)
-  const int cand[6][2] = {{20, 40}, {16, 40}, {10, 20}, {8, 40}, {8, 20}, {4, 20}};
-  const int B = batch_hint > 0 ? batch_hint : 1;
-  const bool sep = nt == 1;  // separate LDS region for the intermediate (see the kernel's SEP)
-  // CL pass first (the kernel's "concat from LDS" variant: fp16, one channel tile, at most one gathered K step, instantiated for
-  // the 16x40 and 8x40 tiles): taken when a tile keeps two workgroups per CU.  OPT-IN, LITEPI_BNECK_CL=1 (2: the 16x40 tile
-  // whatever its LDS size): it removes the re-reads of the concat buffer and is bit-equal, but the kernel is not traffic-bound --
-  // the larger tile costs a workgroup per CU and 53 -> 67 us (v1) / 91 -> 96 us (v2, 8x40 tiles), DESIGN.md section 7
-  const int cl_mode = getenv("LITEPI_BNECK_CL") ? atoi(getenv("LITEPI_BNECK_CL")) : 0;
-  const bool try_cl = cl_out && psa_out && kg_cl > cg && kg_cl <= 4 && cl_mode > 0 && prec == LP_FP16 && nt == 1 && tail;
-  for (int pass = try_cl ? 0 : 1; pass < 2; ++pass) {
-  const bool clp = pass == 0;
-  const int pssa = clp ? (kg_cl | 1) : pss;   // staged slots per pixel: odd = 16 consecutive pixels on 16 different 16-byte columns
-  long best = -1;
-  for (auto& cd : cand) {
-    const int TH = cd[0], TW = cd[1];
-    if (clp && !((TH == 16 || TH == 8) && TW == 40)) continue;
-    if (clp && cl_mode == 2 && TH != 16) continue;
-    if (clp && cl_mode == 3 && TH != 8) continue;    // (3: the 8x40 tile)
-    static const bool no_big = getenv("LITEPI_BNECK_SMALL") != nullptr;  // A/B switch
-    if (TH >= 16 && (nt != 1 || no_big)) continue;  // 12 + 10 (15 + 13) pixel tiles per wave: only the single-channel-tile variant has the registers
-    if (TH == 10 && nt > 2) continue;               // 5 + 4 pixel tiles per wave: instantiated for one and two channel tiles
-    // the balanced shapes pay only where they turn the grid into ONE full round (two workgroups on each of the 256 CUs of an
-    // MI355X); on larger grids the smaller tiles' extra rounds overlap better (160x160: 50 us with 16x40, 57 us with 20x40)
-    static const bool no_balanced = getenv("LITEPI_BNECK_NO_BALANCED") != nullptr;  // A/B switch
-    if ((TH == 20 || TH == 10) && (no_balanced || (long)ceil_div(h, TH) * ceil_div(w, TW) * B > 512)) continue;
-    if (tail && TH == 4) continue;                  // no cv2 instantiation for the smallest tile
-    int l = TW + 4;
-    if (cg <= 1) while (l % 16 != 2) ++l;  // one K group per pixel: 16 consecutive pixels x 4 taps conflict-free
-    if (ceil_div(l * pssa, 64) > (clp ? 4 : 8)) continue;
-    const size_t need = 512 + (size_t)2 * steps * nt * 1024 + extra_lds + (size_t)(TH + 4) * l * pssa * 16 + (size_t)(sep ? TH + 2 : 0) * l * pss * 16;
-    if (need > 150 * 1024) continue;
-    if (clp && cl_mode != 2 && need > 80 * 1024) continue;
-    const long tiles = (long)ceil_div(h, TH) * ceil_div(w, TW);
-    const int util = (int)(100.0 * h * w / ((double)tiles * TH * TW));
-    // enough workgroups to fill the chip first, then two workgroups per CU, then no idle lanes, then the larger tile
-    static const long bn_wgs = getenv("LITEPI_BNECK_WGS") ? atol(getenv("LITEPI_BNECK_WGS")) : 256;
-    if (clp && tiles * B < bn_wgs) continue;   // small batches keep the small tiles of the gather plan (latency: workgroups first)
-    const long score = (tiles * B >= bn_wgs ? 8 : tiles * B >= bn_wgs / 2 ? 4 : 0) * 1000L + (need <= 80 * 1024 ? 2000L : 0L) +
-                       (util >= 95 ? 500L : util >= 80 ? 250L : 0L) + TH * TW / 10;
-    if (score > best) { best = score; th = TH; tw = TW; lw = l; lds = need; }
-  }
-  if (best >= 0) {
-    if (clp) { *cl_out = true; *psa_out = pssa * 16; }
-    return true;
-  }
-  }
-  return false;
-}
-
-bool BottleneckPair::supported(int prec, int impl, int c_phys, int h, int w, int batch_hint, const Cv2* cv2) {
-  int th, tw, lw, t2 = 0, kg = 0, sg = 0;
-  size_t lds, extra = 0;
-  if (impl != IMPL_MFMA) return false;
-  if (cv2) {
-    if (!cv2_shape(prec, c_phys, *cv2, t2, kg, sg)) return false;
-    const int nt = ceil_div(c_phys, 16);
-    extra = (size_t)t2 * (sg + (prec == LP_FP16 ? (nt + 1) / 2 : nt)) * 1024;
-  }
-  return plan(prec, c_phys, h, w, batch_hint, extra, cv2 != nullptr, th, tw, lw, lds);
-}
-
 void BottleneckPair::build(int prec_, int c_phys, const std::vector<float>& wa, const std::vector<float>& ba,
                            const std::vector<float>& wb, const std::vector<float>& bb, int h, int w, int batch_hint, const Cv2* cv2) {
   prec = prec_; C = c_phys;
-  const int G = prec == LP_FP16 ? 8 : 4;
-  const int nt = ceil_div(C, 16);
-  const int SR = prec == LP_FP16 ? (nt + 1) / 2 : nt;
-  size_t extra = 0;
-  if (cv2) {
-    LP_CHECK(cv2_shape(prec, C, *cv2, T2, kg, sg), LP_ERR_GRAPH, "bottleneck %s: cv2 tail shape unsupported", name.c_str());
-    extra = (size_t)T2 * (sg + SR) * 1024;
-  }
-  LP_CHECK(plan(prec, C, h, w, batch_hint, extra, cv2 != nullptr, TH, TW, LW, lds_bytes, (cv2 && cv2->in_is_last_stored) ? kg : 0, &cl, &PSA),
-           LP_ERR_GRAPH, "bottleneck %d ch on %dx%d: no fused plan", C, h, w);
+  static_cast<cplan::BneckTiling&>(*this) = cplan::plan_bneck(prec, C, h, w, batch_hint, cv2);
+  LP_CHECK(ok, LP_ERR_GRAPH, "bottleneck %s, %d ch on %dx%d: no fused plan%s", name.c_str(), C, h, w, cv2 ? " for this cv2 tail" : "");
   a.name = name; b.name = name;
   a.build(prec, IMPL_MFMA, 3, 1, C, C, ACT_SILU, wa, ba, h, w, batch_hint, true, true);
   b.build(prec, IMPL_MFMA, 3, 1, C, C, ACT_SILU, wb, bb, h, w, batch_hint, true, true);
   NT = a.NT; CG = a.CGc; PS = a.PS; steps = a.steps;
-  auto rcp16 = [&](int d, int range) {
-    const unsigned m = (65536u + d - 1) / d;
-    for (int x = 0; x < range; ++x) LP_CHECK((int)((x * m) >> 16) == x / d, LP_ERR_STATE, "reciprocal of %d not exact at %d", d, x);
-    return m;
-  };
-  rcp_cg = rcp16(CG, 128);
+  rcp_cg = rcp16_checked(CG, 128);
   const int st_slots = (cl ? PSA : PS) / 16;   // slots per staged pixel
-  rcp_ps = rcp16(st_slots, 512);
-  rcp_pcs = rcp16(ceil_div(LW * st_slots, 64), 1024);
+  rcp_ps = rcp16_checked(st_slots, 512);
+  rcp_pcs = rcp16_checked(ceil_div(LW * st_slots, 64), 1024);
   LP_CHECK(!cl || steps <= 16, LP_ERR_STATE, "bottleneck CL: tap table too long");
-  rcp_w1 = rcp16(TW + 2, 1024);
-  rcp_tw = rcp16(TW, 1024);
-  LP_CHECK((TH + 2) * (TW + 2) <= p1() * 4 * 16 && TH * TW <= p2() * 4 * 16, LP_ERR_STATE, "bottleneck tile exceeds the kernel's pixel-tile budget");
+  rcp_w1 = rcp16_checked(TW + 2, 1024);
+  rcp_tw = rcp16_checked(TW, 1024);
   if (cv2) {
-    // cv2 fragments [T2][sg + SR][lane][G]: K steps 0..sg-1 walk the stored concat channels (group q = 4s+g), the
-    // last SR steps the channels this lane's accumulators hold (same mapping as ConvLayer::attach_tail)
+    // cv2 fragments [T2][sg + SR][lane][G]: K steps 0..sg-1 walk the stored concat channels (group q = 4s+g), the last SR steps
+    // the channels this lane's accumulators hold
     C3 = cv2->c3; act3 = cv2->act;
-    const int ccat = cv2->cat_global + C, ST = sg + SR;
-    std::vector<uint8_t> buf((size_t)T2 * ST * 64 * 16, 0);
-    for (int t = 0; t < T2; ++t)
-      for (int s = 0; s < ST; ++s)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int g = lane >> 4, m = lane & 15, gm = m >> 2, r = m & 3;
-          const int oc = gm * 4 * T2 + t * 4 + r;
-          if (oc >= C3) continue;
-          for (int j = 0; j < G; ++j) {
-            int ch;
-            if (s < sg) {
-              const int q = 4 * s + g;
-              if (q >= kg) continue;
-              ch = q * G + j;
-            } else {
-              const int s2 = s - sg;
-              if (G * s2 + j >= 4 * NT) continue;
-              const int mid = g * 4 * NT + G * s2 + j;
-              if (mid >= C) continue;
-              ch = cv2->cat_global + mid;
-            }
-            put_elem(buf, ((size_t)(t * ST + s) * 64 + lane) * G + j, prec, (*cv2->w)[(size_t)oc * ccat + ch]);
-          }
+    const std::vector<uint8_t> buf = pack_tail(prec, NT, C, C3, *cv2->w, cv2->cat_global + C, cv2->cat_global, kg, sg);
+    upload(d_w3, buf.data(), buf.size());
+    upload_padded_bias(d_b3, C3, cv2->bias);
+  }
+}
+
+// the gathered K steps of an fp16 cv2 tail are a template parameter (straight-line epilogue, see the kernel); fp32 and no tail: 0
+static int bneck_sg_arg(const BottleneckPair& bp) { return (bp.T2 > 0 && bp.prec == LP_FP16) ? bp.sg : 0; }
+
+std::string BottleneckPair::kernel_name() const {
+  const cplan::BneckTile* t = cplan::bneck_tile(TH, TW);
+  return fmt("bottleneck3x3x2<%d,%d,%d,%d,%d%s>", NT, t ? t->p1 : 0, t ? t->p2 : 0, T2, bneck_sg_arg(*this), cl ? ",cl" : "");
+}
+
+template <typename T, int NT, int P1, int P2, int T2, int SG, bool CL> static void launch_bneck_kernel(const BneckArgs& a, dim3 grid, size_t lds, hipStream_t st) {
+  set_max_dynamic_lds(reinterpret_cast<const void*>(bottleneck_mfma_kernel<T, NT, P1, P2, NT == 1, T2, SG, CL>), 160 * 1024);
+  LP_LAUNCH((bottleneck_mfma_kernel<T, NT, P1, P2, NT == 1, T2, SG, CL>), grid, dim3(256), lds, st, a);
+}
+// the tile's kernel with a cv2 tail: (NT, T2) from kBneckTails, SG 1..3 (fp16) or 0 (fp32), the CL variant on the tiles that have it
+template <typename T, int TILE, int SG> static bool launch_bneck_tail(const BottleneckPair& bp, const BneckArgs& a, dim3 grid, hipStream_t st) {
+  constexpr cplan::BneckTile t = cplan::kBneckTiles[TILE];
+  return for_each_entry(cplan::kBneckTails, [&](auto i) {
+    constexpr cplan::Variant v = cplan::kBneckTails[decltype(i)::value];
+    if constexpr (t.tail && v.nt <= t.max_nt) {
+      if (bp.NT != v.nt || bp.T2 != v.t2) return false;
+      if constexpr (t.cl && v.nt == 1 && SG == 1 && sizeof(T) == 2) {
+        if (bp.cl) {
+          launch_bneck_kernel<T, v.nt, t.p1, t.p2, v.t2, SG, true>(a, grid, bp.lds_bytes, st);
+          return true;
         }
-    d_w3.alloc(buf.size());
-    LP_HIP(hipMemcpy(d_w3.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
-    std::vector<float> b3(round_up(C3, 64) + 64, 0.f);
-    for (int c = 0; c < C3 && cv2->bias && c < (int)cv2->bias->size(); ++c) b3[c] = (*cv2->bias)[c];
-    d_b3.alloc(b3.size() * 4);
-    LP_HIP(hipMemcpy(d_b3.p, b3.data(), b3.size() * 4, hipMemcpyHostToDevice));
-  }
-}
-
-template <typename T, int NT, int P1, int P2, int T2, int SG>
-static void launch_bneck_sg(const BneckArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  constexpr bool SEP = NT == 1;
-  if constexpr (NT == 1 && T2 > 0 && SG == 1 && sizeof(T) == 2 && (P1 == 12 || P1 == 7)) {
-    if (a.PSA > 0) {   // the CL variant (BottleneckPair::plan)
-      set_max_dynamic_lds(reinterpret_cast<const void*>(bottleneck_mfma_kernel<T, NT, P1, P2, SEP, T2, SG, true>), 160 * 1024);
-      LP_LAUNCH((bottleneck_mfma_kernel<T, NT, P1, P2, SEP, T2, SG, true>), grid, dim3(256), lds, st, a);
-      return;
+      }
+      if (bp.cl) return false;
+      launch_bneck_kernel<T, v.nt, t.p1, t.p2, v.t2, SG, false>(a, grid, bp.lds_bytes, st);
+      return true;
+    } else {
+      return false;
     }
-  }
-  LP_CHECK(a.PSA == 0, LP_ERR_STATE, "bottleneck: no CL kernel for this shape");
-  set_max_dynamic_lds(reinterpret_cast<const void*>(bottleneck_mfma_kernel<T, NT, P1, P2, SEP, T2, SG>), 160 * 1024);
-  LP_LAUNCH((bottleneck_mfma_kernel<T, NT, P1, P2, SEP, T2, SG>), grid, dim3(256), lds, st, a);
+  });
 }
-// fp16 cv2 tails: the gathered K steps (1..3) are a template parameter (straight-line epilogue, see the kernel)
-template <typename T, int NT, int P1, int P2, int T2>
-static void launch_bneck_(const BneckArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  if constexpr (T2 > 0 && sizeof(T) == 2) {
-    if (a.sg == 1) return launch_bneck_sg<T, NT, P1, P2, T2, 1>(a, grid, lds, st);
-    if (a.sg == 2) return launch_bneck_sg<T, NT, P1, P2, T2, 2>(a, grid, lds, st);
-    if (a.sg == 3) return launch_bneck_sg<T, NT, P1, P2, T2, 3>(a, grid, lds, st);
-  }
-  launch_bneck_sg<T, NT, P1, P2, T2, 0>(a, grid, lds, st);
-}
-
-// cv2 tails exist for NT = 1 with T2 in {1, 2} and NT = 2 with T2 in {2, 4} (BottleneckPair::cv2_shape)
-template <typename T, int NT, int P1, int P2>
-static void launch_bneck_t(const BneckArgs& a, int t2, dim3 grid, size_t lds, hipStream_t st) {
-  if (t2 == 0) return launch_bneck_<T, NT, P1, P2, 0>(a, grid, lds, st);
-  if constexpr (NT == 1 && P1 != 3) {
-    if (t2 == 1) return launch_bneck_<T, NT, P1, P2, 1>(a, grid, lds, st);
-    if (t2 == 2) return launch_bneck_<T, NT, P1, P2, 2>(a, grid, lds, st);
-  }
-  if constexpr (NT == 2 && P1 != 3) {
-    if (t2 == 2) return launch_bneck_<T, NT, P1, P2, 2>(a, grid, lds, st);
-    if (t2 == 4) return launch_bneck_<T, NT, P1, P2, 4>(a, grid, lds, st);
-  }
-  throw Error(LP_ERR_STATE, "bottleneck: no kernel for this cv2 tail");
-}
-
-// pixel tiles per wave = ceil(ceil(region / 16) / 4 waves) for the tile shapes of plan()
-template <typename T, int NT>
-static void launch_bneck(const BneckArgs& a, int t2, dim3 grid, size_t lds, hipStream_t st) {
-  if (a.TH == 20 && a.TW == 40) {                                                        // 22x42 = 58 tiles, 20x40 = 50
-    if constexpr (NT == 1) launch_bneck_t<T, 1, 15, 13>(a, t2, grid, lds, st);
-    else throw Error(LP_ERR_STATE, "bottleneck: 20x40 tiles need NT == 1");
-  } else if (a.TH == 16 && a.TW == 40) {                                                 // 18x42 = 48 tiles, 16x40 = 40
-    if constexpr (NT == 1) launch_bneck_t<T, 1, 12, 10>(a, t2, grid, lds, st);
-    else throw Error(LP_ERR_STATE, "bottleneck: 16x40 tiles need NT == 1");
-  } else if (a.TH == 10 && a.TW == 20) {                                                 // 12x22 = 17 tiles, 10x20 = 13
-    if constexpr (NT <= 2) launch_bneck_t<T, NT, 5, 4>(a, t2, grid, lds, st);
-    else throw Error(LP_ERR_STATE, "bottleneck: 10x20 tiles need NT <= 2");
-  } else if (a.TH == 8 && a.TW == 40) launch_bneck_t<T, NT, 7, 5>(a, t2, grid, lds, st);  // 10x42 = 27 tiles, 8x40 = 20
-  else if (a.TH == 8 && a.TW == 20) launch_bneck_t<T, NT, 4, 3>(a, t2, grid, lds, st);    // 10x22 = 14 tiles, 8x20 = 10
-  else if (a.TH == 4 && a.TW == 20) launch_bneck_t<T, NT, 3, 2>(a, t2, grid, lds, st);    //  6x22 =  9 tiles, 4x20 = 5
-  else throw Error(LP_ERR_STATE, "bottleneck: no kernel for this tile shape");
+template <typename T> static bool launch_bneck(const BottleneckPair& bp, const BneckArgs& a, dim3 grid, hipStream_t st) {
+  return for_each_entry(cplan::kBneckTiles, [&](auto i) {
+    constexpr int TILE = (int)decltype(i)::value;
+    constexpr cplan::BneckTile t = cplan::kBneckTiles[TILE];
+    if (bp.TH != t.th || bp.TW != t.tw) return false;
+    if (bp.T2 == 0)
+      return for_each_entry(cplan::kBneckNT, [&](auto n) {
+        constexpr int nt = cplan::kBneckNT[decltype(n)::value];
+        if constexpr (nt <= t.max_nt) {
+          if (bp.NT != nt) return false;
+          launch_bneck_kernel<T, nt, t.p1, t.p2, 0, 0, false>(a, grid, bp.lds_bytes, st);
+          return true;
+        } else {
+          return false;
+        }
+      });
+    if constexpr (sizeof(T) == 2) {
+      static_assert(cplan::kBneckMaxSgF16 == 3, "one launch_bneck_tail line per SG");
+      switch (bp.sg) {
+        case 1: return launch_bneck_tail<T, TILE, 1>(bp, a, grid, st);
+        case 2: return launch_bneck_tail<T, TILE, 2>(bp, a, grid, st);
+        case 3: return launch_bneck_tail<T, TILE, 3>(bp, a, grid, st);
+        default: return false;
+      }
+    } else {
+      return bp.sg <= cplan::kBneckMaxSgF32 && launch_bneck_tail<T, TILE, 0>(bp, a, grid, st);
+    }
+  });
 }
 
 void BottleneckPair::launch(const View& in, const View& out, int N, hipStream_t st, const View* cat) const {
@@ -2441,7 +2162,7 @@ void BottleneckPair::launch(const View& in, const View& out, int N, hipStream_t 
     k.out = nullptr;
     if (cl) {
       const size_t es = prec == LP_FP16 ? 2 : 4;
-      LP_CHECK(reinterpret_cast<const char*>(in.base) == reinterpret_cast<const char*>(cat->base) + (size_t)(kg * (prec == LP_FP16 ? 8 : 4) - C) * es &&
+      LP_CHECK(reinterpret_cast<const char*>(in.base) == reinterpret_cast<const char*>(cat->base) + (size_t)(kg * cplan::group(prec) - C) * es &&
                    in.pitch == cat->pitch,
                LP_ERR_STATE, "bottleneck %s: planned with the input as the concat's last stored segment, launched with another view", name.c_str());
       k.PSA = PSA;
@@ -2450,14 +2171,11 @@ void BottleneckPair::launch(const View& in, const View& out, int N, hipStream_t 
     LP_CHECK(out.C >= C, LP_ERR_STATE, "bottleneck: output view too narrow");
   }
   const int tiles_y = ceil_div(in.H, TH);
-  const unsigned m = (65536u + k.tiles_x - 1) / k.tiles_x;
-  for (int x = 0; x < k.tiles_x * tiles_y; ++x) LP_CHECK((int)((x * m) >> 16) == x / k.tiles_x, LP_ERR_STATE, "tile reciprocal not exact");
-  k.rcp_tx = m; k.rcp_cg = rcp_cg; k.rcp_ps = rcp_ps; k.rcp_pcs = rcp_pcs; k.rcp_w1 = rcp_w1; k.rcp_tw = rcp_tw;
-  static const bool tile_major = getenv("LITEPI_TILE_MAJOR") != nullptr;
-  k.tile_major = tile_major;
+  k.rcp_tx = rcp16_checked(k.tiles_x, k.tiles_x * tiles_y);
+  k.rcp_cg = rcp_cg; k.rcp_ps = rcp_ps; k.rcp_pcs = rcp_pcs; k.rcp_w1 = rcp_w1; k.rcp_tw = rcp_tw;
+  k.tile_major = tile_major_order();
   dim3 grid(N, k.tiles_x * tiles_y);
-  if (tile_major) grid = dim3(k.tiles_x * tiles_y, N);
-  const bool f16 = prec == LP_FP16;
+  if (k.tile_major) grid = dim3(k.tiles_x * tiles_y, N);
   static const char* stamp_path = getenv("LITEPI_BNECK_STAMPS");
   DevBuf d_stamps;
   if (stamp_path && *stamp_path) {
@@ -2465,12 +2183,8 @@ void BottleneckPair::launch(const View& in, const View& out, int N, hipStream_t 
     LP_HIP(hipMemsetAsync(d_stamps.p, 0, (size_t)grid.x * grid.y * 16 * 8, st));
     k.stamps = d_stamps.as<unsigned long long>();
   }
-  switch (NT) {
-    case 1: if (f16) launch_bneck<half_t, 1>(k, T2, grid, lds_bytes, st); else launch_bneck<float, 1>(k, T2, grid, lds_bytes, st); break;
-    case 2: if (f16) launch_bneck<half_t, 2>(k, T2, grid, lds_bytes, st); else launch_bneck<float, 2>(k, T2, grid, lds_bytes, st); break;
-    case 3: if (f16) launch_bneck<half_t, 3>(k, T2, grid, lds_bytes, st); else launch_bneck<float, 3>(k, T2, grid, lds_bytes, st); break;
-    default: if (f16) launch_bneck<half_t, 4>(k, T2, grid, lds_bytes, st); else launch_bneck<float, 4>(k, T2, grid, lds_bytes, st); break;
-  }
+  const bool launched = prec == LP_FP16 ? launch_bneck<half_t>(*this, k, grid, st) : launch_bneck<float>(*this, k, grid, st);
+  LP_CHECK(launched, LP_ERR_STATE, "bottleneck %s: no kernel for tile %dx%d, NT %d, T2 %d, sg %d%s", name.c_str(), TH, TW, NT, T2, sg, cl ? ", cl" : "");
   LP_HIP(hipGetLastError());
   if (k.stamps) {  // diagnostic: dump [grid][16] stamps, one record per launch (tools/bneck_stamps.py)
     LP_HIP(hipStreamSynchronize(st));
@@ -2489,7 +2203,7 @@ void BottleneckPair::launch(const View& in, const View& out, int N, hipStream_t 
 void StemLayer::build(int prec_, int cout_phys, int act_, const std::vector<float>& w_bgr, const std::vector<float>& bias, int k_, int stride_, int pad_) {
   prec = prec_; CO = cout_phys; act = act_; k = k_; stride = stride_; pad = pad_;
   LP_CHECK((int)w_bgr.size() == k * k * 3 * CO, LP_ERR_GRAPH, "stem weights do not match a %dx%d kernel", k, k);
-  LP_CHECK(CO == 8 || CO == 16 || CO == 32, LP_ERR_GRAPH, "stem with %d output channels unsupported", CO);
+  LP_CHECK(std::find(std::begin(cplan::kStemCO), std::end(cplan::kStemCO), CO) != std::end(cplan::kStemCO), LP_ERR_GRAPH, "stem with %d output channels unsupported", CO);
   d_w.alloc(w_bgr.size() * 4);
   LP_HIP(hipMemcpy(d_w.p, w_bgr.data(), w_bgr.size() * 4, hipMemcpyHostToDevice));
   std::vector<float> b(CO, 0.f);
@@ -2571,11 +2285,7 @@ void StemLayer::launch_block(const uint8_t* img, int N, int Hin, int Win, const 
   a.H2 = out.H; a.W2 = out.W; a.out_pitch = out.pitch; a.C2 = c1.Cout2; a.act2 = c1.act2;
   LP_CHECK(a.H2 == (a.H1 + 1) / 2 && a.W2 == (a.W1 + 1) / 2 && out.C >= c1.Cout2, LP_ERR_STATE, "stem block: output view mismatch");
   dim3 grid(N, ceil_div(a.W2, SB_TW), ceil_div(a.H2, SB_TH));
-  static const int th16 = getenv("LITEPI_SB16_TH") ? atoi(getenv("LITEPI_SB16_TH")) : 8;   // A/B: output rows per workgroup of the v2 kernel
-  if (CO == 16 && th16 == 4) {
-    dim3 grid4(N, ceil_div(a.W2, 32), ceil_div(a.H2, 4));
-    LP_LAUNCH(stem_block16_kernel<4>, grid4, dim3(256), 0, st, a);
-  } else if (CO == 16) {
+  if (CO == 16) {
     LP_LAUNCH(stem_block16_kernel<8>, grid, dim3(256), 0, st, a);
   } else {
     LP_LAUNCH(stem_block_kernel, grid, dim3(256), 0, st, a);
@@ -2583,49 +2293,42 @@ void StemLayer::launch_block(const uint8_t* img, int N, int Hin, int Win, const 
   LP_HIP(hipGetLastError());
 }
 
+// the two generic stem kernels (LDS = true: stem_conv_lds_kernel, 3x3/s2/p1 on an aligned image), CO from kStemCO
+template <typename T, bool LDS> static bool launch_stem_generic(const StemLayer& S, const uint8_t* img, int N, int Hin, int Win, const View& out, hipStream_t st) {
+  return for_each_entry(cplan::kStemCO, [&](auto i) {
+    constexpr int co = cplan::kStemCO[decltype(i)::value];
+    if (S.CO != co) return false;
+    if constexpr (LDS) {
+      const dim3 grid(ceil_div(out.W, STEM_TW), ceil_div(out.H, STEM_TH), N);
+      LP_LAUNCH((stem_conv_lds_kernel<T, co>), grid, dim3(256), 0, st, img, reinterpret_cast<T*>(out.base), S.d_w.as<float>(), S.d_bias.as<float>(), N,
+                Hin, Win, out.H, out.W, out.pitch, S.act);
+    } else {
+      const dim3 grid((unsigned)(((long)N * out.H * out.W + 255) / 256));
+      LP_LAUNCH((stem_conv_kernel<T, co>), grid, dim3(256), 0, st, img, reinterpret_cast<T*>(out.base), S.d_w.as<float>(), S.d_bias.as<float>(), N,
+                Hin, Win, out.H, out.W, out.pitch, S.act, S.k, S.stride, S.pad);
+    }
+    return true;
+  });
+}
+
 void StemLayer::launch(const uint8_t* img, int N, int Hin, int Win, const View& out, hipStream_t st) const {
   const bool aligned = k == 3 && stride == 2 && pad == 1 && Win % 4 == 0 && (reinterpret_cast<uintptr_t>(img) & 3) == 0 &&
                        out.H == (Hin + 1) / 2 && out.W == (Win + 1) / 2;
-  static const bool no_mfma_stem = getenv("LITEPI_NO_MFMA_STEM") != nullptr;
-  if (aligned && d_afrag.p && !no_mfma_stem && CO == 16) {
-    dim3 g3(N, ceil_div(out.W, STEMM_TW), ceil_div(out.H, STEMM_TH));
-    LP_LAUNCH(stem_mfma16_kernel, g3, dim3(256), 0, st, img, reinterpret_cast<half_t*>(out.base),
-                       reinterpret_cast<const u32x4*>(d_afrag.p), d_bias.as<float>(), N, Hin, Win, out.H, out.W, out.pitch);
-    LP_HIP(hipGetLastError());
-    return;
-  }
-  if (aligned && d_afrag.p && !no_mfma_stem) {
-    dim3 g3(N, ceil_div(out.W, STEMM_TW), ceil_div(out.H, STEMM_TH));
-    LP_LAUNCH(stem_mfma_kernel, g3, dim3(256), 0, st, img, reinterpret_cast<half_t*>(out.base),
-                       reinterpret_cast<const u32x4*>(d_afrag.p), d_bias.as<float>(), N, Hin, Win, out.H, out.W, out.pitch);
-    LP_HIP(hipGetLastError());
-    return;
-  }
-  if (aligned) {
-    dim3 g2(ceil_div(out.W, STEM_TW), ceil_div(out.H, STEM_TH), N);
-#define LP_STL(TT, C)                                                                                            \
-  LP_LAUNCH((stem_conv_lds_kernel<TT, C>), g2, dim3(256), 0, st, img, reinterpret_cast<TT*>(out.base), \
-                     d_w.as<float>(), d_bias.as<float>(), N, Hin, Win, out.H, out.W, out.pitch, act)
-    if (prec == LP_FP16) {
-      if (CO == 8) LP_STL(half_t, 8); else if (CO == 16) LP_STL(half_t, 16); else LP_STL(half_t, 32);
-    } else {
-      if (CO == 8) LP_STL(float, 8); else if (CO == 16) LP_STL(float, 16); else LP_STL(float, 32);
-    }
-#undef LP_STL
-    LP_HIP(hipGetLastError());
-    return;
-  }
-  const long total = (long)N * out.H * out.W;
-  dim3 grid((unsigned)((total + 255) / 256));
-#define LP_ST(TT, C)                                                                                     \
-  LP_LAUNCH((stem_conv_kernel<TT, C>), grid, dim3(256), 0, st, img, reinterpret_cast<TT*>(out.base), \
-                     d_w.as<float>(), d_bias.as<float>(), N, Hin, Win, out.H, out.W, out.pitch, act, k, stride, pad)
-  if (prec == LP_FP16) {
-    if (CO == 8) LP_ST(half_t, 8); else if (CO == 16) LP_ST(half_t, 16); else LP_ST(half_t, 32);
+  bool ok = true;
+  if (aligned && d_afrag.p) {   // fp16, SiLU, 8 or 16 channels (build): the MFMA stems
+    const dim3 g3(N, ceil_div(out.W, STEMM_TW), ceil_div(out.H, STEMM_TH));
+    if (CO == 16)
+      LP_LAUNCH(stem_mfma16_kernel, g3, dim3(256), 0, st, img, reinterpret_cast<half_t*>(out.base),
+                reinterpret_cast<const u32x4*>(d_afrag.p), d_bias.as<float>(), N, Hin, Win, out.H, out.W, out.pitch);
+    else
+      LP_LAUNCH(stem_mfma_kernel, g3, dim3(256), 0, st, img, reinterpret_cast<half_t*>(out.base),
+                reinterpret_cast<const u32x4*>(d_afrag.p), d_bias.as<float>(), N, Hin, Win, out.H, out.W, out.pitch);
+  } else if (aligned) {
+    ok = prec == LP_FP16 ? launch_stem_generic<half_t, true>(*this, img, N, Hin, Win, out, st) : launch_stem_generic<float, true>(*this, img, N, Hin, Win, out, st);
   } else {
-    if (CO == 8) LP_ST(float, 8); else if (CO == 16) LP_ST(float, 16); else LP_ST(float, 32);
+    ok = prec == LP_FP16 ? launch_stem_generic<half_t, false>(*this, img, N, Hin, Win, out, st) : launch_stem_generic<float, false>(*this, img, N, Hin, Win, out, st);
   }
-#undef LP_ST
+  LP_CHECK(ok, LP_ERR_STATE, "stem: no kernel for %d output channels", CO);
   LP_HIP(hipGetLastError());
 }
 

@@ -1,0 +1,292 @@
+// Tile and split planner of the convolution kernels (conv_kernels.hip), and the tables of their instantiated variants.
+// Host-only and pure: no HIP, no allocation, no environment -- a plain C++ compiler builds it, and
+// tests/native/conv_plan_replay.cpp replays it against a recording (tests/golden/conv_plans.json).
+// ConvLayer and BottleneckPair (conv.h) derive from the two result structs; launch, tail_supported, attach_tail and the
+// bottleneck's tile filters look the variants up in the tables below, which are also what gets instantiated.
+#pragma once
+#include <cstddef>
+
+#include "../../include/litepi.h"
+
+namespace lp {
+namespace cplan {
+
+constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
+inline int group(int prec) { return prec == LP_FP16 ? 8 : 4; }   // channels per 16-byte K group
+
+// x / d == (x * m) >> 16 for every x < range (the kernels' prologues divide this way); 0: no such 16-bit reciprocal
+inline unsigned rcp16(int d, int range) {
+  const unsigned m = (65536u + d - 1) / d;
+  for (int x = 0; x < range; ++x)
+    if ((int)((x * m) >> 16) != x / d) return 0;
+  return m;
+}
+
+// ---- the instantiated variants, one table per kernel family ---------------------------------------------------------
+struct Variant { int nt, t2; };   // channel tiles per workgroup, 16-channel tiles of a fused 1x1 tail (0: no tail)
+// conv3x3_mfma_kernel<T, NT, T2>
+constexpr Variant kConv3x3[] = {{1, 0}, {2, 0}, {3, 0}, {4, 0}, {4, 4}, {2, 1}};
+// conv3x3s2_direct_kernel<T, NT, 4, T2, U>, U = s2_unroll(steps)
+constexpr Variant kConvS2[] = {{1, 0}, {2, 0}, {3, 0}, {4, 0}, {1, 1}, {2, 2}, {4, 4}};
+constexpr int s2_unroll(int steps) { return steps >= 5 ? 4 : 1; }
+// conv1x1_mfma_kernel<T, NT, 4, EPI, UPS>: every NT as plain, shuffle-epilogue and fused-upsample kernel
+constexpr int kConv1x1[] = {1, 2, 3, 4};
+// stem_conv_kernel / stem_conv_lds_kernel<T, CO>
+constexpr int kStemCO[] = {8, 16, 32};
+// bottleneck_mfma_kernel<T, NT, P1, P2, NT == 1, T2, SG, CL>: the tiles in the order the plan scores them (the first of equal
+// scores wins).  P1 / P2 = pixel tiles (of 16) per wave in conv_a / conv_b = ceil(ceil(region / 16) / 4 waves): 22x42 = 58 and
+// 20x40 = 50 tiles, 18x42 = 48 and 40, 12x22 = 17 and 13, 10x42 = 27 and 20, 10x22 = 14 and 10, 6x22 = 9 and 5.
+// max_nt: 12 + 10 (15 + 13) pixel tiles per wave leave registers for one channel tile only, 5 + 4 for two.
+// tail: has the cv2 instantiations of kBneckTails.  cl: also the "concat from LDS" variant (fp16, NT 1, SG 1).
+struct BneckTile { int th, tw, p1, p2, max_nt; bool tail, cl; };
+constexpr BneckTile kBneckTiles[] = {{20, 40, 15, 13, 1, true, false}, {16, 40, 12, 10, 1, true, true}, {10, 20, 5, 4, 2, true, false},
+                                     {8, 40, 7, 5, 4, true, true},     {8, 20, 4, 3, 4, true, false},   {4, 20, 3, 2, 4, false, false}};
+constexpr int kBneckNT[] = {1, 2, 3, 4};   // without a tail: every NT up to the tile's max_nt
+constexpr Variant kBneckTails[] = {{1, 1}, {1, 2}, {2, 2}, {2, 4}};
+constexpr bool bneck_tiles_fit() {   // the halo'd and the inner region of every tile fit P1 / P2 pixel tiles on each of the 4 waves
+  for (const BneckTile& t : kBneckTiles)
+    if (t.p1 != cdiv(cdiv((t.th + 2) * (t.tw + 2), 16), 4) || t.p2 != cdiv(cdiv(t.th * t.tw, 16), 4)) return false;
+  return true;
+}
+static_assert(bneck_tiles_fit(), "kBneckTiles: P1 / P2 do not match the tile");
+// gathered K steps of a cv2 tail: a template parameter 1..3 of the fp16 kernels (straight-line epilogue), a loop of at most 6
+// in the fp32 ones (SG = 0)
+constexpr int kBneckMaxSgF16 = 3, kBneckMaxSgF32 = 6;
+
+template <size_t N> inline bool has_variant(const Variant (&tbl)[N], int nt, int t2) {
+  for (const Variant& v : tbl)
+    if (v.nt == nt && v.t2 == t2) return true;
+  return false;
+}
+inline const BneckTile* bneck_tile(int th, int tw) {
+  for (const BneckTile& t : kBneckTiles)
+    if (t.th == th && t.tw == tw) return &t;
+  return nullptr;
+}
+
+// ---- constants of the heuristics --------------------------------------------------------------------------------------
+// floor of workgroups below which a layer takes fewer channel tiles per block.  Measured on the pipelined benchmark (3 batches
+// in flight share the GPU: 512 gave the best isolated layer times but 5 % less throughput)
+constexpr long kMinWorkgroups = 128;
+// LDS budget of a 3x3 stride-1 workgroup: input tile + weight fragments, two workgroups per CU
+constexpr size_t kConv3x3LdsBudget = 80 * 1024;
+// bottleneck: workgroups that fill the chip (one per CU of an MI355X); the hard LDS limit of a tile; the size up to which two
+// workgroups share a CU
+constexpr long kBneckWorkgroups = 256;
+constexpr size_t kBneckLdsMax = 150 * 1024, kBneckLdsTwoPerCu = 80 * 1024;
+
+// LDS geometry of the 3x3 input tile, found by enumerating the ds_read_b128 lane groups
+// ({0-3,12-15,20-27}, ...; MI355X_MICROARCH.md, LDS) over every K step: with cg channel groups
+// per pixel, a pixel pitch of p = (smallest value >= cg with p % 4 == 2) 16-byte slots and a row
+// width = 12 (mod 16) pixels make the 4x4-pixel x 4-K-group fragment read conflict-free (4 LDS
+// cycles); the former odd-pitch rule cost 8.  One group per pixel (cg = 1): pitch 1, row = 4 (mod 16).
+inline int lds_pixel_slots(int cg) {
+  if (cg <= 1) return 1;
+  int p = cg;
+  while (p % 4 != 2) ++p;
+  return p;
+}
+inline int lds_row_width(int iw, int cg) {
+  int lw = iw;
+  const int want = cg <= 1 ? 4 : 12;
+  while (lw % 16 != want) ++lw;
+  return lw;
+}
+
+// channel tiles per block: 4 when the layer has plenty of pixel tiles; fewer (more channel splits -> more
+// workgroups, but the input is read once per split) when the map is small
+inline int pick_nt(int tiles_total, bool full_n, long pixel_blocks) {
+  if (full_n) return tiles_total;  // a fused tail needs every intermediate channel in one workgroup
+  int nt = tiles_total >= 4 ? 4 : tiles_total;
+  if (tiles_total % 4 != 0 && tiles_total > 4) nt = (tiles_total % 3 == 0) ? 3 : 4;
+  while (nt > 1 && pixel_blocks * cdiv(tiles_total, nt) < kMinWorkgroups) nt = (nt == 4 && tiles_total % 4 == 0) ? 2 : nt - 1;
+  return nt;
+}
+
+// ---- ConvLayer's tiling ------------------------------------------------------------------------------------------------
+struct ConvTiling {
+  int NT = 1, nsplits = 1, CK = 0, CGc = 0, nchunks = 1, steps = 0, LW = 0, PS = 0, bwh = 2, bww = 2;
+  size_t lds_bytes = 0;
+  unsigned rcp_cg = 0, rcp_ps = 0, rcp_pcs = 0;  // 16-bit reciprocals of CGc, PS/16 and pieces per LDS tile row (3x3 kernel)
+  bool direct = false;  // 3x3 stride-2: gather B fragments from global memory (no LDS input tile)
+  const char* plan_err = nullptr;  // why the shape has no plan
+};
+
+// hout/wout: output map size and batch_hint: images (or ROIs) per call at capacity -- together they pick the tile shape and
+// the channel split.  full_n: every channel tile in one workgroup (fused tail); single_chunk: weights only (BottleneckPair)
+inline ConvTiling plan_conv(int prec, int k, int stride, int cin, int cout, int hout, int wout, int batch_hint, bool full_n, bool single_chunk) {
+  ConvTiling p;
+  const int taps = k * k, G = group(prec), tiles_total = cdiv(cout, 16);
+  const int B = batch_hint > 0 ? batch_hint : 1;
+  const long flat_blocks = cdiv((int)((long)B * hout * wout), 256);   // 256-pixel blocks of the flat-indexed kernels
+  p.direct = k == 3 && stride == 2 && !single_chunk;
+  if (single_chunk) {
+    // every channel tile in one workgroup, all of K in one chunk
+    if (k != 3 || stride != 1) { p.plan_err = "single-chunk packing is for 3x3 stride-1 layers"; return p; }
+    p.NT = tiles_total; p.nsplits = 1; p.CK = cin; p.CGc = cin / G; p.nchunks = 1;
+    p.steps = cdiv(taps * p.CGc, 4);
+    p.PS = lds_pixel_slots(p.CGc) * 16;
+    if (p.steps * 4 > 128) p.plan_err = "conv3x3: too many K steps for one chunk";
+  } else if (p.direct) {
+    // stride-2: no input staging (see conv3x3s2_direct_kernel); all of K for this block's channel split in LDS
+    p.NT = pick_nt(tiles_total, full_n, flat_blocks);
+    p.CK = cin;
+    p.CGc = cin / G;
+    p.nchunks = 1;
+    p.steps = cdiv(taps * p.CGc, 4);
+    while (!full_n && p.NT > 1 && (size_t)p.steps * p.NT * 1024 > 64 * 1024) --p.NT;
+    p.nsplits = cdiv(tiles_total, p.NT);
+    p.lds_bytes = (size_t)p.steps * p.NT * 1024 + (size_t)p.steps * 4 * 8;  // weight fragments + K-group table
+    if (p.lds_bytes > 160 * 1024) p.plan_err = "conv3x3/s2 weights do not fit LDS";
+  } else if (k == 3) {
+    // Tile shape (bwh x bww waves of 4x20 pixels) and K chunk CK (multiple of 8, divides Cin):
+    // the halo'd input tile plus the chunk's weight fragments must fit the LDS budget (two
+    // workgroups per CU).  Priority: no idle lanes on this map, >= 16-channel chunks, then the
+    // largest workgroup (weights are staged once per workgroup), then the largest chunk.
+    const bool small_map = (hout <= 20 && wout <= 20);
+    const int cand[6][2] = {{5, 1}, {2, 2}, {2, 1}, {1, 2}, {4, 1}, {1, 1}};
+    long best_score = -1;
+    p.CK = 8; p.bwh = 1; p.bww = 1; p.LW = 0; p.NT = 1;
+    for (int ci = 0; ci < 6; ++ci) {
+      const int h = cand[ci][0], w = cand[ci][1];
+      if (!small_map && (h == 5 || h == 4)) continue;
+      const int TH = 4 * h, TW = 20 * w;
+      const int IH = TH + 2, IW = TW + 2;
+      const int tiles = cdiv(hout, TH) * cdiv(wout, TW);
+      const int nt = pick_nt(tiles_total, full_n, (long)tiles * B);
+      // K chunk: everything at once when it fits (one round trip, no K padding between chunks), else the
+      // largest chunk whose two buffers fit (the next chunk's LDS-DMA flies during this chunk's MFMAs)
+      int ck_fit = 0, lw = 0;
+      for (int ck = 8; ck <= cin && ck <= 64; ck += 8) {
+        if (cin % ck) continue;
+        const int cgc = ck / G;
+        const int l = lds_row_width(IW, cgc);
+        const size_t one = (size_t)cdiv(taps * cgc, 4) * nt * 1024 + (size_t)IH * l * lds_pixel_slots(cgc) * 16;
+        const size_t lds = 512 + (ck == cin ? one : 2 * one);
+        if (lds <= kConv3x3LdsBudget && cdiv(taps * cgc, 4) * 4 <= 128 && cdiv(l * lds_pixel_slots(cgc), 64) <= 8) { ck_fit = ck; lw = l; }
+      }
+      if (!ck_fit) continue;
+      const int util = (int)(100.0 * hout * wout / ((double)tiles * TH * TW));
+      const long score = (util >= 95 ? 3 : util >= 80 ? 2 : util >= 60 ? 1 : 0) * 100000L +
+                         ((ck_fit >= 16 || ck_fit == cin) ? 10000L : 0L) + (long)h * w * 1000L + ck_fit;
+      if (score > best_score) { best_score = score; p.CK = ck_fit; p.bwh = h; p.bww = w; p.LW = lw; p.NT = nt; }
+    }
+    if (best_score < 0) { p.plan_err = "conv3x3: no tile fits LDS"; return p; }
+    p.nsplits = cdiv(tiles_total, p.NT);
+    const int IH = 4 * p.bwh + 2;
+    p.CGc = p.CK / G;
+    p.PS = lds_pixel_slots(p.CGc) * 16;
+    p.nchunks = cin / p.CK;
+    p.steps = cdiv(taps * p.CGc, 4);
+    p.lds_bytes = 512 + (p.nchunks > 1 ? 2 : 1) * ((size_t)p.steps * p.NT * 1024 + (size_t)IH * p.LW * p.PS);
+    p.rcp_cg = rcp16(p.CGc, 128);
+    p.rcp_ps = rcp16(p.PS / 16, 512);
+    p.rcp_pcs = rcp16(cdiv(p.LW * (p.PS / 16), 64), 1024);
+    if (p.steps * 4 > 128) p.plan_err = "conv3x3: too many K steps per chunk";
+    else if (cdiv(p.LW * (p.PS / 16), 64) > 8) p.plan_err = "conv3x3: LDS tile row too wide";
+    else if (!p.rcp_cg || !p.rcp_ps || !p.rcp_pcs) p.plan_err = "conv3x3: a prologue reciprocal is not exact";
+    else if (p.lds_bytes > 160 * 1024) p.plan_err = "conv3x3 tile does not fit LDS";
+  } else {
+    p.NT = pick_nt(tiles_total, full_n, flat_blocks);
+    p.CK = cin;
+    p.CGc = cin / G;
+    p.nchunks = 1;
+    p.steps = cdiv(p.CGc, 4);
+    // all K of this block's channel split stays in LDS: fewer channel tiles per block for deep K
+    while (p.NT > 1 && (size_t)p.steps * p.NT * 1024 > 96 * 1024) --p.NT;
+    p.nsplits = cdiv(tiles_total, p.NT);
+    p.lds_bytes = (size_t)p.steps * p.NT * 1024;
+    if (p.lds_bytes > 160 * 1024) p.plan_err = "conv1x1 weights do not fit LDS";
+  }
+  return p;
+}
+
+// can a 3x3 conv (stride 1 or 2) to cmid channels carry a fused 1x1 tail to cout2 channels?
+inline bool conv_tail_supported(int k, int stride, int cmid, int cout2) {
+  if (k != 3 || cmid % 8 != 0) return false;
+  const int nt = cdiv(cmid, 16), t2 = cdiv(cout2, 16);  // a half-filled last tile has zero weights and bias
+  return t2 > 0 && (stride == 1 ? has_variant(kConv3x3, nt, t2) : stride == 2 ? has_variant(kConvS2, nt, t2) : false);
+}
+// K steps of a fused 1x1 tail over the nt channel tiles the accumulators hold (odd NT, fp16: last step half filled)
+inline int tail_steps(int prec, int nt) { return prec == LP_FP16 ? (nt + 1) / 2 : nt; }
+
+// ---- BottleneckPair's tiling -------------------------------------------------------------------------------------------
+// fused C2f.cv2 of a bottleneck, as far as the plan depends on it
+struct BneckTail {
+  int cat_global = 0, c3 = 0;        // physical channels of the concat in front of y_last; cv2 output channels
+  bool in_is_last_stored = false;    // the bottleneck's input is the concat's last stored segment
+  bool cl = false;                   // try the "concat from LDS" variant first (LITEPI_BNECK_CL=1)
+};
+struct BneckTiling {
+  bool ok = false;
+  int TH = 8, TW = 40, LW = 0;
+  size_t lds_bytes = 0;
+  int T2 = 0, kg = 0, sg = 0;   // cv2: its 16-channel output tiles, stored K groups per pixel, gathered K steps
+  bool cl = false;              // "concat from LDS": the tile is staged with every stored segment, cv2 gathers from it (see the kernel)
+  int PSA = 0;                  // its pixel pitch in LDS
+};
+
+// a C -> C bottleneck on an h x w map (batch_hint images), tail = nullptr: without cv2.  !ok: no fused plan (LDS capacity, tile
+// limits, no instantiation for the tail)
+inline BneckTiling plan_bneck(int prec, int c, int h, int w, int batch_hint, const BneckTail* tail) {
+  BneckTiling p;
+  const int G = group(prec);
+  if (c % 8 != 0 || c > 64) return p;
+  const int nt = cdiv(c, 16), cg = c / G;
+  size_t extra_lds = 0;
+  if (tail) {
+    if (tail->cat_global <= 0 || tail->cat_global % G != 0 || tail->c3 % 8 != 0) return p;
+    p.T2 = cdiv(tail->c3, 16);
+    p.kg = tail->cat_global / G;
+    p.sg = cdiv(p.kg, 4);
+    if (!has_variant(kBneckTails, nt, p.T2) || p.sg > (prec == LP_FP16 ? kBneckMaxSgF16 : kBneckMaxSgF32)) return p;
+    extra_lds = (size_t)p.T2 * (p.sg + tail_steps(prec, nt)) * 1024;   // cv2's weight fragments
+  }
+  const int steps = cdiv(9 * cg, 4);
+  if (steps * 4 > 128) return p;
+  const int pss = lds_pixel_slots(cg);
+  const int B = batch_hint > 0 ? batch_hint : 1;
+  const bool sep = nt == 1;  // separate LDS region for the intermediate (see the kernel's SEP)
+  // CL pass first (the kernel's "concat from LDS" variant: fp16, one channel tile, at most one gathered K step): taken when a
+  // tile keeps two workgroups per CU.  OPT-IN: it removes the re-reads of the concat buffer and is bit-equal, but the kernel is
+  // not traffic-bound -- the larger tile costs a workgroup per CU and 53 -> 67 us (v1) / 91 -> 96 us (v2, 8x40 tiles), DESIGN.md
+  // section 7
+  const int kg_cl = (tail && tail->in_is_last_stored) ? p.kg : 0;
+  const bool try_cl = tail && tail->cl && kg_cl > cg && kg_cl <= 4 && prec == LP_FP16 && nt == 1;
+  for (int pass = try_cl ? 0 : 1; pass < 2; ++pass) {
+    const bool clp = pass == 0;
+    const int pssa = clp ? (kg_cl | 1) : pss;   // staged slots per pixel: odd = 16 consecutive pixels on 16 different 16-byte columns
+    long best = -1;
+    for (const BneckTile& t : kBneckTiles) {
+      const int TH = t.th, TW = t.tw;
+      if (nt > t.max_nt || (tail && !t.tail) || (clp && !t.cl)) continue;   // no such instantiation
+      // 20x40 / 10x20: 8 tiles on an 80x80 / 40x40 map -- 512 workgroups for a batch of 64, exactly two per CU, instead of 640
+      // (2.5 per CU: the CUs that get three decide the kernel time of these single-round grids).  These balanced shapes pay only
+      // where they turn the grid into ONE full round (two workgroups on each of the 256 CUs of an MI355X); on larger grids the
+      // smaller tiles' extra rounds overlap better (160x160: 50 us with 16x40, 57 us with 20x40)
+      if ((TH == 20 || TH == 10) && (long)cdiv(h, TH) * cdiv(w, TW) * B > 512) continue;
+      int l = TW + 4;
+      if (cg <= 1) while (l % 16 != 2) ++l;  // one K group per pixel: 16 consecutive pixels x 4 taps conflict-free
+      if (cdiv(l * pssa, 64) > (clp ? 4 : 8)) continue;
+      const size_t need = 512 + (size_t)2 * steps * nt * 1024 + extra_lds + (size_t)(TH + 4) * l * pssa * 16 + (size_t)(sep ? TH + 2 : 0) * l * pss * 16;
+      if (need > kBneckLdsMax) continue;
+      if (clp && need > kBneckLdsTwoPerCu) continue;
+      const long tiles = (long)cdiv(h, TH) * cdiv(w, TW);
+      const int util = (int)(100.0 * h * w / ((double)tiles * TH * TW));
+      // enough workgroups to fill the chip first, then two workgroups per CU, then no idle lanes, then the larger tile
+      if (clp && tiles * B < kBneckWorkgroups) continue;   // small batches keep the small tiles of the gather plan (latency: workgroups first)
+      const long score = (tiles * B >= kBneckWorkgroups ? 8 : tiles * B >= kBneckWorkgroups / 2 ? 4 : 0) * 1000L +
+                         (need <= kBneckLdsTwoPerCu ? 2000L : 0L) + (util >= 95 ? 500L : util >= 80 ? 250L : 0L) + TH * TW / 10;
+      if (score > best) { best = score; p.TH = TH; p.TW = TW; p.LW = l; p.lds_bytes = need; }
+    }
+    if (best >= 0) {
+      p.ok = true;
+      if (clp) { p.cl = true; p.PSA = pssa * 16; }
+      return p;
+    }
+  }
+  return p;
+}
+
+}  // namespace cplan
+}  // namespace lp

@@ -110,11 +110,11 @@ void Detector::forward(const uint8_t* imgs, int B, const ImgGeom* geom, float co
     switch (op.kind) {
       case DetOp::STEM:
         stem_.launch(imgs, B, SH_, SW_, view(op.out), st);
-        kname = std::string("stem_conv") + sfx;
+        kname = std::string(stem_.kernel_name(false)) + sfx;
         break;
       case DetOp::STEMBLOCK:
         stem_.launch_block(imgs, B, SH_, SW_, *convs_[op.conv], view(op.out), st);
-        kname = std::string(stem_.CO == 16 ? "stem_block16" : "stem_block") + sfx;
+        kname = std::string(stem_.kernel_name(true)) + sfx;
         break;
       case DetOp::CONV: {
         const ConvLayer& c = *convs_[op.conv];
@@ -127,10 +127,7 @@ void Detector::forward(const uint8_t* imgs, int B, const ImgGeom* geom, float co
           io.in.C -= io.up.C;
         }
         c.launch(io, st);
-        kname = std::string(c.impl == IMPL_NAIVE ? "conv_naive" : (c.direct ? "conv3x3s2_direct" : (c.k == 3 ? "conv3x3_mfma" : "conv1x1_mfma"))) + (c.T2 ? "+1x1" : "");
-        // one name per kernel instantiation (channel tiles NT, tail tiles T2, fused-upsample variant), as rocprofv3 lists them
-        if (c.impl != IMPL_NAIVE) kname += c.T2 ? fmt("<%d,%d>", c.NT, c.T2) : (op.in2 >= 0 ? fmt("<%d,up>", c.NT) : fmt("<%d>", c.NT));
-        kname += sfx;
+        kname = c.kernel_name(op.in2 >= 0) + sfx;
         break;
       }
       case DetOp::BNECK:
@@ -140,11 +137,7 @@ void Detector::forward(const uint8_t* imgs, int B, const ImgGeom* geom, float co
         } else {
           bnecks_[op.conv]->launch(view(op.in), view(op.out), B, st);
         }
-        {  // one name per kernel instantiation <NT, P1, P2, T2, SG> (what rocprofv3 lists as separate kernels)
-          const BottleneckPair& bp = *bnecks_[op.conv];
-          kname = fmt("bottleneck3x3x2<%d,%d,%d,%d,%d%s>", bp.NT, bp.p1(), bp.p2(), bp.T2, (bp.T2 > 0 && prec_ == LP_FP16) ? bp.sg : 0,
-                      bp.cl ? ",cl" : "") + sfx;
-        }
+        kname = bnecks_[op.conv]->kernel_name() + sfx;
         break;
       case DetOp::DWCONV:
         launch_dwconv3x3_act(prec_, view(op.in), view(op.out), dws_[op.conv].w.as<float>(), dws_[op.conv].b.as<float>(), dws_[op.conv].act, B, st);

@@ -22,8 +22,9 @@ namespace lp {
 
 // Every LITEPI_* switch the planner reads, read once at the top of a load: a process may set one between two loads.  Every plan-time
 // switch of c2f_kernels.hip is here -- that file's supported() functions are pure functions of the shape, and the Planner's
-// c2f_ok / s2c_ok / s2c_tail_ok / sppf_ok combine them with these.  (The other kernel files' own switches stay in those files, as
-// do the diagnostics a launch reads: LITEPI_C2F_STAMPS, LITEPI_C2F_DEBUG.)
+// c2f_ok / s2c_ok / s2c_tail_ok / sppf_ok combine them with these -- and so is conv_kernels.hip's one (bneck_cl): its planner
+// (conv_plan.h) reads no environment.  (head_kernels.hip's own switches stay in that file, as do what a launch reads: the
+// diagnostics LITEPI_C2F_STAMPS, LITEPI_C2F_DEBUG, LITEPI_BNECK_STAMPS, and the kernel argument LITEPI_TILE_MAJOR.)
 struct PlanSwitches {
   static bool on(const char* name) { return getenv(name) != nullptr; }
   bool no_c2f = on("LITEPI_NO_C2F");             // whole-C2f / SPPF / stride-2 launches of c2f_kernels.hip off
@@ -45,6 +46,9 @@ struct PlanSwitches {
   bool no_sibling = on("LITEPI_NO_SIBLING");
   bool no_bneck = on("LITEPI_NO_BNECK");         // keeps the layer-at-a-time plan (A/B measurements)
   bool no_cv2fuse = on("LITEPI_NO_CV2FUSE");
+  // LITEPI_BNECK_CL=1: a bottleneck + cv2 launch whose input is the concat's last stored segment stages the whole stored concat
+  // pixel and gathers cv2's K from LDS (opt-in: fewer HBM bytes, but slower; handed on in BottleneckPair::Cv2::cl)
+  bool bneck_cl = getenv("LITEPI_BNECK_CL") && atoi(getenv("LITEPI_BNECK_CL")) == 1;
   bool no_upfuse = on("LITEPI_NO_UPFUSE");
   bool no_stemblock = on("LITEPI_NO_STEMBLOCK");
   bool no_headfuse = on("LITEPI_NO_HEADFUSE");
@@ -1010,6 +1014,7 @@ std::optional<Planner::Cv2Match> Planner::match_bneck_cv2(int tin, int tfinal) {
     for (int k2 = 0; k2 < TI.parent_seg; ++k2) oi += round_up(P.segs[k2], 8);
   }
   f.cv2.in_is_last_stored = bi >= 0 && bi == TO.buf && oi == TO.off + glob - TI.Cp;
+  f.cv2.cl = sw.bneck_cl;
   if (!BottleneckPair::supported(prec_, impl_, TI.Cp, TI.H, TI.W, maxB_, &f.cv2)) return std::nullopt;
   f.conv = j3; f.t_cat = tO;
   repack(L[j3], TO, tensors_[t3], 0, f.cv2.c3, f.w, f.b);

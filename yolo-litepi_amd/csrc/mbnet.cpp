@@ -214,7 +214,7 @@ void MBNetClassifier::forward(const uint8_t* rgb, const int* d_R, hipStream_t st
     P0();
     c.launch(io, st);
     const double px = (double)out.H * out.W;
-    P1(c.impl == IMPL_NAIVE ? "conv_naive" : "conv1x1_mfma", c.name, 2.0 * c.Cin * c.Cout * px, (px * c.Cin + px * c.Cout * (res ? 2.0 : 1.0)) * esd);
+    P1(c.family_name(), c.name, 2.0 * c.Cin * c.Cout * px, (px * c.Cin + px * c.Cout * (res ? 2.0 : 1.0)) * esd);
   };
   // ReLU6 behind a pointwise conv: its epilogue applied ReLU, the cap follows in place
   auto cap6 = [&](const View& x, const std::string& layer) {

@@ -149,7 +149,7 @@ void ResNet18Classifier::forward(const uint8_t* rgb, const int* d_R, hipStream_t
     P0();
     c.launch(io, st);
     const double px = (double)out.H * out.W;
-    P1(c.impl == IMPL_NAIVE ? "conv_naive" : (c.stride == 2 ? "conv3x3s2_direct" : "conv3x3_mfma"), c.name, 2.0 * 9 * c.Cin * c.Cout * px,
+    P1(c.family_name(), c.name, 2.0 * 9 * c.Cin * c.Cout * px,
        ((double)in.H * in.W * c.Cin + px * c.Cout * (res ? 2.0 : 1.0)) * esd);
   };
   const int H1 = S_ / 2, H2 = S_ / 4;
@@ -190,7 +190,7 @@ void ResNet18Classifier::forward(const uint8_t* rgb, const int* d_R, hipStream_t
   io.in = mean; io.out = lg; io.N = maxR_; io.m_dyn = d_R; io.out_f32 = 1;
   P0();
   fc.launch(io, st);
-  P1(fc.impl == IMPL_NAIVE ? "conv_naive" : "conv1x1_mfma", "fc", 2.0 * 512 * fc.Cout, 512 * esd + fc.Cout * 4.0);
+  P1(fc.family_name(), "fc", 2.0 * 512 * fc.Cout, 512 * esd + fc.Cout * 4.0);
 }
 
 }  // namespace lp
