@@ -9,8 +9,8 @@ imported (the tests take the anchor grid from the exporter's ``make_anchors``).
 
 Rounding points (``head_out0`` flags), read off the kernels.  Every sum is fp32 on the device, float64 here.
 
-  weights      fp16, once: a property of the stored model, not an error of the kernel (HeadLayer::build's ``frag`` / ``frag16``
-               pack every weight with f32_to_f16, head_kernels.hip; ConvLayer packs its fragments the same way).  Biases stay
+  weights      fp16, once: a property of the stored model, not an error of the kernel (hplan::pack_head's ``frag`` / ``frag16``
+               pack every weight with f32_to_f16, head_plan.h; ConvLayer packs its fragments the same way).  Biases stay
                fp32: they initialise the fp32 accumulators (``bias16`` / ``biasA16``, head_kernels.hip) or are added to them
                (``act4(v, bias)``, conv_kernels.hip).
   round_mid    the two post-SiLU activations of each tower, fp16 round-to-nearest-even.

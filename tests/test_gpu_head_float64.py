@@ -15,8 +15,9 @@ shifted anchors and exchanged classes or biases break them.
 
 Cases: v1 and v2 at 320 x 320, batch 5, one class (whole-C2f plan; maps 40 / 20 / 10; masked last tile column on P3) and at
 352 x 352, batch 2, three classes (layer plan; maps 44 / 22 / 11; masked edges both ways; the best-of-classes path), each on the
-fused plan and on the three-launch plan (LITEPI_NO_HEADFUSE=1); v1 at 352 also behind LITEPI_HEAD_A32 / _2WG / _1WG, which are
-read once per process: one child process each, one after another.  All images of a batch are compared.
+fused plan and on the three-launch plan (LITEPI_NO_HEADFUSE=1); v1 at 352 also behind LITEPI_HEAD_A32 / _2WG / _1WG and v2 at 352
+behind LITEPI_HEAD_A32 (its three shapes without 16-pixel tiles, which any of the three switches selects), which are read per
+load: one child process each, one after another.  All images of a batch are compared.
 
 MEAN_CAP (tests/head_ref.py) = 0.25: the smallest power of two at or above twice the largest mean d / mean e measured on an MI355X
 over all cases, levels and row groups below (0.0641: v2-320x5-nc1, fused, P5, box rows; largest on score rows 0.0461), capped at 0.5.
@@ -59,6 +60,9 @@ MI355X, this module as committed (box rows in grid cells):
     v1-352x2-nc3  1WG             44   |    2.04e-03  1.30e-04  4.69e-04  3.37e-06  0.230  0.0259 |    3.43e-04  3.36e-06  3.49e-05  2.76e-08  0.102  0.0082
     v1-352x2-nc3  1WG             22   |    1.90e-03  1.26e-04  9.10e-04  6.24e-06  0.478  0.0496 |    1.17e-04  1.82e-06  1.47e-05  3.58e-08  0.126  0.0197
     v1-352x2-nc3  1WG             11   |    7.59e-04  7.48e-05  3.96e-05  9.51e-07  0.052  0.0127 |    1.08e-04  3.08e-06  7.91e-06  7.18e-08  0.073  0.0233
+    v2-352x2-nc3  A32             44   |    2.96e-03  1.56e-04  1.36e-03  6.19e-06  0.460  0.0398 |    2.95e-04  3.98e-06  3.70e-05  6.48e-08  0.125  0.0163
+    v2-352x2-nc3  A32             22   |    1.95e-03  1.73e-04  1.07e-03  4.88e-06  0.553  0.0282 |    9.99e-05  3.10e-06  1.93e-05  7.01e-08  0.193  0.0226
+    v2-352x2-nc3  A32             11   |    1.01e-03  1.38e-04  4.70e-04  5.03e-06  0.464  0.0364 |    2.95e-04  8.41e-06  1.50e-05  2.40e-07  0.051  0.0285
 """
 import os
 import subprocess
@@ -174,7 +178,7 @@ def test_head_equals_float64_reference_of_its_input(model, plan, monkeypatch):
     _check(model, out0, maps, plan == "three_launch", f"{_ids(model['param'])} {plan}")
 
 
-# A fresh process per kernel-shape switch (read once per process): the engine's out0, maps and launch names of the parent's model -> .npz
+# A fresh process per kernel-shape switch (read per load): the engine's out0, maps and launch names of the parent's model -> .npz
 _CHILD = r"""
 import sys
 import numpy as np
@@ -201,12 +205,16 @@ SWITCHES = {
     "LITEPI_HEAD_A32": ["head_fused<1,2,1,2,2,8>_f16", "head_fused<1,3,2,4,4,12>_f16", "head_fused<1,2,1,4,8,24>_f16"],
     "LITEPI_HEAD_2WG": ["head_fused<1,2,1,2,2,12>_f16", "head_fused<1,3,2,4,6,24>_f16", "head_fused<1,2,1,4,8,24>_f16"],
     "LITEPI_HEAD_1WG": ["head_fused<1,3,2,2,6,24>_f16", "head_fused<1,3,2,4,6,24>_f16", "head_fused<1,2,1,4,8,24>_f16"],
+    # v2 (two class row tiles, Cin 48 / 96 / 192): the three rows of the table without 16-pixel tiles
+    "v2:LITEPI_HEAD_A32": ["head_fused<2,3,2,3,3,24>_f16", "head_fused<2,2,1,3,6,24>_f16", "head_fused<2,1,1,5,6,24>_f16"],
 }
 
 
 @pytest.mark.parametrize("switch", list(SWITCHES))
 def test_switched_shapes_equal_float64_reference(tmp_path_factory, tmp_path, switch):
-    m = _build(("v1", 352, 2, 3), tmp_path_factory)
+    names_want = SWITCHES[switch]
+    preset, _, switch = switch.rpartition(":")
+    m = _build((preset or "v1", 352, 2, 3), tmp_path_factory)
     _, S, B, _ = m["param"]
     env = {k: v for k, v in os.environ.items() if not k.startswith("LITEPI_HEAD_") and k != "LITEPI_NO_HEADFUSE"}
     env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "yolo-litepi_amd"), ROOT, env.get("PYTHONPATH", "")])
@@ -217,5 +225,5 @@ def test_switched_shapes_equal_float64_reference(tmp_path_factory, tmp_path, swi
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     with np.load(out) as z:
         out0, maps, names = z["out0"], [z[f"map{i}"] for i in range(3)], [str(n) for n in z["names"]]
-    assert sorted(n for n in names if n.startswith("head_fused<")) == sorted(SWITCHES[switch]), names
+    assert sorted(n for n in names if n.startswith("head_fused<")) == sorted(names_want), names
     _check(m, out0, maps, False, f"{_ids(m['param'])} {switch}")

@@ -125,8 +125,8 @@ def test_device_path_eager_and_graph_replay(setup):
         assert np.array_equal(runs[0][0], runs[k][0]) and runs[0][1] == runs[k][1], f"call {k} differs from the first"
 
 
-# What a fresh process does for test_workgroups_leave_on_every_v1_shape: the kernel shape switches and LITEPI_HEAD_STAMPS are read
-# once per process, so each switch needs a process of its own.  LITEPI_HEAD_STAMPS makes every head launch append a record
+# What a fresh process does for test_workgroups_leave_on_every_v1_shape: the kernel shape switches are read per load, but
+# LITEPI_HEAD_STAMPS once per process, so each switch runs in a process of its own.  LITEPI_HEAD_STAMPS makes every head launch append a record
 # [magic, grid, H, N][grid][16] whose stamp 14 is 1 for a workgroup that left at the vote.
 _STAMP_SCRIPT = r"""
 import json, os, sys

@@ -4,7 +4,7 @@ the vote, in the workgroups that stay, from an input tile that is staged a secon
 channel still accumulates the same bias-initialised fp32 sum in the same K order, so nothing that the head emits may change by a
 bit: the comparison side is the merged stage A of the same build (``LITEPI_HEAD_MERGED_A=1``), the tolerance is zero.
 
-The switch is read once per process, so each side is a fresh child process; children run one after another.
+The switch is read per load; each side is a fresh child process, and children run one after another.
 
 Shapes (both presets: the three default shapes of v1 and v2's P3 and P4 have the split stage A, v2's P5 keeps the merged one; v2's
 P3 has an odd number of 16-channel groups per tap, so its zeroed guard slot behind the tile is staged again too): 320 x 320, batch 5 (whole-C2f plan; maps 40 / 20 / 10, a masked last tile

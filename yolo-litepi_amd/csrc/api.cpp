@@ -26,50 +26,6 @@ std::string fmt(const char* f, ...) {
   return std::string(buf);
 }
 
-uint16_t f32_to_f16(float f) {
-  uint32_t x;
-  memcpy(&x, &f, 4);
-  const uint32_t sign = (x >> 16) & 0x8000u;
-  const int32_t exp = (int32_t)((x >> 23) & 0xFF) - 127 + 15;
-  uint32_t man = x & 0x7FFFFFu;
-  if (((x >> 23) & 0xFF) == 0xFF) return (uint16_t)(sign | 0x7C00u | (man ? 0x200u : 0));
-  if (exp >= 31) return (uint16_t)(sign | 0x7C00u);
-  if (exp <= 0) {
-    if (exp < -10) return (uint16_t)sign;
-    man |= 0x800000u;
-    const int shift = 14 - exp;
-    uint32_t h = man >> shift;
-    const uint32_t rem = man & ((1u << shift) - 1), halfway = 1u << (shift - 1);
-    if (rem > halfway || (rem == halfway && (h & 1))) ++h;
-    return (uint16_t)(sign | h);
-  }
-  uint32_t h = ((uint32_t)exp << 10) | (man >> 13);
-  const uint32_t rem = man & 0x1FFFu;
-  if (rem > 0x1000u || (rem == 0x1000u && (h & 1))) ++h;
-  return (uint16_t)(sign | h);
-}
-
-float f16_to_f32(uint16_t h) {
-  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
-  uint32_t exp = (h >> 10) & 0x1F, man = h & 0x3FFu, x;
-  if (exp == 0) {
-    if (man == 0) {
-      x = sign;
-    } else {
-      int e = -1;
-      do { ++e; man <<= 1; } while (!(man & 0x400u));
-      x = sign | ((uint32_t)(127 - 15 - e) << 23) | ((man & 0x3FFu) << 13);
-    }
-  } else if (exp == 31) {
-    x = sign | 0x7F800000u | (man << 13);
-  } else {
-    x = sign | ((exp - 15 + 127) << 23) | (man << 13);
-  }
-  float f;
-  memcpy(&f, &x, 4);
-  return f;
-}
-
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device attribute: set it once per (device, kernel) and
 // check the result (a kernel that needs more than 64 KB of LDS fails to launch without it)
 void set_max_dynamic_lds(const void* fn, int bytes) {

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/litepi.h"
+#include "f16.h"   // f32_to_f16, f16_to_f32
 
 namespace lp {
 
@@ -100,10 +101,6 @@ struct DevBuf {
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-// fp32 <-> fp16 on the host (round-to-nearest-even; weights are converted once at load)
-uint16_t f32_to_f16(float f);
-float f16_to_f32(uint16_t h);
 
 // ---- a channel-slice view of an NHWC activation buffer ------------------------------
 struct View {

@@ -23,8 +23,9 @@ namespace lp {
 // Every LITEPI_* switch the planner reads, read once at the top of a load: a process may set one between two loads.  Every plan-time
 // switch of c2f_kernels.hip is here -- that file's supported() functions are pure functions of the shape, and the Planner's
 // c2f_ok / s2c_ok / s2c_tail_ok / sppf_ok combine them with these -- and so is conv_kernels.hip's one (bneck_cl): its planner
-// (conv_plan.h) reads no environment.  (head_kernels.hip's own switches stay in that file, as do what a launch reads: the
-// diagnostics LITEPI_C2F_STAMPS, LITEPI_C2F_DEBUG, LITEPI_BNECK_STAMPS, and the kernel argument LITEPI_TILE_MAJOR.)
+// (conv_plan.h) reads no environment -- and head_kernels.hip's five (head): its planner (head_plan.h) reads none either, and a
+// HeadLayer keeps the shape and the flags of the load that built it.  (What a launch reads stays in the kernels' files: the
+// diagnostics LITEPI_C2F_STAMPS, LITEPI_C2F_DEBUG, LITEPI_BNECK_STAMPS, LITEPI_HEAD_STAMPS, and the kernel argument LITEPI_TILE_MAJOR.)
 struct PlanSwitches {
   static bool on(const char* name) { return getenv(name) != nullptr; }
   bool no_c2f = on("LITEPI_NO_C2F");             // whole-C2f / SPPF / stride-2 launches of c2f_kernels.hip off
@@ -53,6 +54,10 @@ struct PlanSwitches {
   bool no_stemblock = on("LITEPI_NO_STEMBLOCK");
   bool no_headfuse = on("LITEPI_NO_HEADFUSE");
   bool headfuse_narrow = getenv("LITEPI_HEADFUSE") && strcmp(getenv("LITEPI_HEADFUSE"), "narrow") == 0;   // three-launch head for wide class towers (A/B)
+  // the fused head's kernel shapes: the merged stage A everywhere, round 3's stage A (32-pixel slots), round 2's two-workgroup
+  // shapes, the one-workgroup shapes; LITEPI_HEAD_FLAGS=<bits> is the kernel argument HeadArgs::flags
+  hplan::HeadSwitches head = {on("LITEPI_HEAD_MERGED_A"), on("LITEPI_HEAD_A32"), on("LITEPI_HEAD_2WG"), on("LITEPI_HEAD_1WG"),
+                              getenv("LITEPI_HEAD_FLAGS") ? atoi(getenv("LITEPI_HEAD_FLAGS")) : 0};
 };
 
 struct Planner {
@@ -1413,7 +1418,7 @@ bool Planner::match_head_level(const Level& lv, Trip& t) {
     const Tensor& ti = tensors_[ops_[oa].in];
     ok = ca.k == 3 && ca.stride == 1 && ca.T2 == 0 && ca.act == ACT_SILU && ca.Cout == 64 + cc.Cin && ops_[oa].res < 0 && ops_[oa].in2 < 0 &&
          ca.Cin == ti.Cp && !ca.b_host.empty() && tensors_[lv.cls].C == d.nc_ &&
-         HeadLayer::supported(ca.Cin, 64, cc.Cin, d.nc_, d.reg_max_, lv.H, lv.W);
+         HeadLayer::supported(ca.Cin, 64, cc.Cin, d.nc_, d.reg_max_, sw.head);
   }
   if (ok) t = {oa, ob, oc, cc.Cin, oproj};
   return ok;
@@ -1448,7 +1453,7 @@ void Planner::fuse_heads() {
     }
     d.heads_.emplace_back(new HeadLayer());
     d.heads_.back()->name = ops_[t.a].layer + "+" + ops_[t.b].layer + "+" + ops_[t.c].layer + "+decode";
-    d.heads_.back()->build(ca.Cin, t.c3, d.nc_, levels_[q].H, levels_[q].W, maxB_, src);
+    d.heads_.back()->build(ca.Cin, t.c3, d.nc_, levels_[q].H, levels_[q].W, sw.head, src);
     DetOp& op = ops_[t.a];
     op.kind = DetOp::HEAD; op.conv = (int)d.heads_.size() - 1; op.in2 = (int)q; op.out = -1;
     op.layer = d.heads_.back()->name;

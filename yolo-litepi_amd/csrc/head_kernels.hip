@@ -20,7 +20,7 @@
 // conf?) -> only then the box tower's stage B, the box projection and the decode.  A workgroup nobody voted in returns at the vote:
 // the box tower's second conv is 24 - 47 % of a level's MACs and a typical frame has a handful of candidates among 8400 anchors.
 // What is emitted is unchanged to the bit: the vote is emit_candidate's own test, and neither tower's arithmetic or order changes.
-// SPLIT stage A (HeadCfg::split_a: the default shapes except v2's P5; LITEPI_HEAD_MERGED_A=1 restores the merged one everywhere): the
+// SPLIT stage A (HeadVariant::split: the default shapes except v2's P5; LITEPI_HEAD_MERGED_A=1 restores the merged one everywhere): the
 // first conv is split by tower as well.  Order: stage A of the CLASS rows only (32*C3T of the 64 + 32*C3T output channels: a third of
 // the MFMAs, SiLUs and MID stores at v1, half at v2) -> class tower's stage B -> class projection -> vote -> and only in a workgroup
 // that stays: stage A of the BOX rows -> SiLU -> MID slots 0-7 -> box tower's stage B -> box projection -> decode.  A 16-row MFMA tile
@@ -44,7 +44,9 @@
 #include "post_dev.h"
 
 #include <algorithm>
+#include <array>
 #include <cstdlib>
+#include <utility>
 
 namespace lp {
 
@@ -378,7 +380,7 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
   // A16: lane = (column col, K group kg); column col of a 16-pixel tile holds pixel offset sig(col) -- even offsets for the lanes
   // {0-3, 12-15}, odd for {4-11} -- and K group kg reads channel slot gam(kg) = {0, 2, 1, 3} of the step's four: with the odd
   // pixel pitch every ds_read_b128 lane group then hits 16 distinct 16-byte slots (as c2f_kernels.hip; tiles that wrap a
-  // region row still collide two-way).  The weights are packed to match (HeadLayer::build).
+  // region row still collide two-way).  The weights are packed to match (hplan::pack_head).
   const int col16 = lane & 15, kg16 = lane >> 4;
   const int sig16 = col16 < 4 ? 2 * col16 : (col16 < 12 ? 2 * (col16 - 4) + 1 : 2 * (col16 - 8));
 #pragma unroll
@@ -399,7 +401,7 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
   // A16: one pass of the first convs over RTP row tiles per half-step (merged: all of them; split: the class tower's, or the box
   // tower's), NCP chunks of KSP half-steps.  K step = (tap, 32-channel block): ceil(KPT / 2) steps per tap, the byte offset kept
   // incrementally.  Cin = 16 (mod 32), v2's 48-channel P3: the last step of a tap reads one pixel's padding slot and the NEXT pixel's
-  // first slot as its channels Cin .. Cin + 15 -- their weights are zero (HeadLayer::build) and what is read is finite: activations,
+  // first slot as its channels Cin .. Cin + 15 -- their weights are zero (hplan::pack_head) and what is read is finite: activations,
   // or the zeroed guard slot behind the tile's last pixel
   auto stageA16 = [&](auto rtp_, auto ksp_, auto ncp_, auto stamp3_, auto& acc) {
     constexpr int RTP = decltype(rtp_)::value, KSP = decltype(ksp_)::value, NCP = decltype(ncp_)::value;
@@ -839,241 +841,35 @@ __global__ __launch_bounds__(256, (SLOTF == 8 ? 3 : (SLOTF == 12 ? 2 : 1))) void
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-// MFMA row rho of a 32-row tile carries physical channel 16*((rho>>2)&1) + 4*(rho>>3) + (rho&3): the D fragment of lane
-// half h then holds channels 16*h .. 16*h+15 in its 16 registers
-static inline int row_channel(int rho) { return 16 * ((rho >> 2) & 1) + 4 * (rho >> 3) + (rho & 3); }
-
-// (the workgroup's vote word needs no bytes of its own: it is the padding slot of MID pixel 0)
-static size_t head_lds(int th, int tw, int kpt, int c3t, int slotf, int ovl) {
-  const size_t in = ((size_t)(th + 4) * (tw + 4) * (2 * kpt + 1) * 16 + 1023) & ~(size_t)1023;
-  const size_t mid = ((size_t)(th + 2) * (tw + 2) * (4 * (2 + c3t) + 1) * 16 + 1023) & ~(size_t)1023;
-  if (slotf == 8) {   // MID overlays the input tile; slots 64 B short of 8 KiB (kchunk): 53,696 B = 42 LDS granules of 1280 B
-    const size_t in_b = (size_t)(th + 4) * (tw + 4) * (2 * kpt + 1) * 16, mid_b = (size_t)(th + 2) * (tw + 2) * (4 * (2 + c3t) + 1) * 16;
-    return (in_b > mid_b ? in_b : mid_b) + 2 * (size_t)(8192 - 64);
-  }
-  if (ovl) return (in > mid ? in : mid) + 2 * (size_t)slotf * 1024;
-  return in + mid + 2 * (size_t)slotf * 1024;
-}
-
-// One kernel configuration per (class row tiles, K steps per tap = Cin / 16): tile shape TH x TW, pixel tiles per wave in stage
-// A / B (ceil((TH+2)(TW+2)/32) <= 4*PA, ceil(TH*TW/32) <= 4*PB), 64-slot pieces per input-tile row, K steps per stage-A chunk
-// (a divisor of 9*KPT with (2+C3T)*KSA <= 24 fragments).  Chosen for LDS (input tile + first-conv image + 48 KiB ring <= 160
-// KiB) and for whole tiles on the 80 / 40 / 20 maps of a 640 input; other map sizes run the same shapes with masked edges.
-// slotf: fragments per weight-ring slot.  The v1 P3 entries with an 8 x 16 tile and one pixel tile per wave in stage B share a
-// CU: the VALU phases (SiLU epilogues, decode: transcendental-bound) and the prologue of one workgroup run under the MFMA phases
-// of the others -- with one workgroup per CU the matrix pipe idles through them.  slotf 12: two per CU (80 KiB, <= 256
-// registers; round 2).  slotf 8: THREE per CU (round 3: 98 us per launch against 112): MID overlays the input tile, 8-fragment
-// slots 64 bytes short of 8 KiB (the LDS granule is 1280 B: 42 granules = 53,760 B per workgroup is the limit, measured with
-// tools/ubench/lds_occupancy.hip; MID + two whole slots would be 53,824), the projections as two chunks, and 168 registers --
-// reached by requesting what only the decode needs (anchors, geometry, DFL weights) late: behind stage A at first, now behind the vote.
-struct HeadCfg { int c3t, kpt, th, tw, pa, pb, npc, ksa, slotf, ovl, a16, split_a; };
-// a16 (round 4): stage A on 16x16x32 MFMAs -- pa counts 16-pixel tiles per wave, ksa half-steps per chunk (one tap per chunk)
-// split_a (a16 only): the class tower's first conv alone in front of the vote, the box tower's behind it in the workgroups that stay
-// (LITEPI_HEAD_MERGED_A=1: the merged stage A on every shape); the chunk sizes of the two passes follow from the slot size (build)
-static const HeadCfg kHeadCfg[] = {
-    {1, 2, 8, 16, 3, 1, 2, 2, 8, 1, 1, 1},      // v1 P3: Cin 32, THREE workgroups per CU, stage A on 16-pixel tiles (12 for 180 pixels)
-    {1, 4, 10, 20, 5, 2, 4, 4, 12, 1, 1, 1},    // v1 P4: Cin 64, TWO workgroups per CU, 17 tiles of 16 for 264 pixels
-    {1, 8, 10, 10, 3, 1, 4, 8, 24, 0, 1, 1},    // v1 P5: Cin 128, 9 tiles of 16 for 144 pixels
-    {2, 3, 8, 16, 3, 1, 3, 2, 12, 1, 1, 1},  // v2 P3: Cin 48 (K padded to 64 per tap), 48-channel class tower, TWO workgroups per CU (73.5 KB)
-    {2, 6, 10, 10, 3, 1, 3, 2, 12, 1, 1, 1}, // v2 P4: Cin 96, 9 tiles of 16 for 144 pixels; MID over the input tile + 12-fragment slots: 64.8 KB, TWO per CU
-    {2, 12, 10, 10, 3, 1, 6, 6, 24, 1, 1, 0}, // v2 P5: Cin 192, 10 x 10 tiles (256 workgroups = one round; MID over the input tile: 126 KB); merged stage A: split measured slower
-    {1, 2, 8, 16, 2, 1, 2, 2, 8, 1, 0},      // v1 P3, round 3's shape: stage A on 32-pixel slots (LITEPI_HEAD_A32=1)
-    {1, 2, 8, 16, 2, 1, 2, 2, 12, 0, 0},     // v1 P3: Cin 32, two workgroups per CU (LITEPI_HEAD_2WG=1)
-    {1, 2, 16, 16, 3, 2, 2, 6, 24, 0, 0},    // v1 P3: Cin 32
-    {1, 4, 10, 20, 3, 2, 4, 4, 12, 1, 0},    // v1 P4: Cin 64, TWO workgroups per CU (MID over the input tile: 79.5 KB)
-    {1, 4, 10, 20, 3, 2, 4, 6, 24, 0, 0},    // v1 P4: Cin 64 (LITEPI_HEAD_2WG=1 / LITEPI_HEAD_1WG=1)
-    {1, 8, 10, 10, 2, 1, 4, 8, 24, 0, 0},    // v1 P5: Cin 128 (256 workgroups: the overlay shape at 76 KB changed nothing end to end)
-    {2, 3, 10, 20, 3, 2, 3, 3, 24, 0, 0},    // v2 P3: Cin 48
-    {2, 6, 10, 10, 2, 1, 3, 6, 24, 0, 0},    // v2 P4: Cin 96
-    {2, 12, 8, 8, 1, 1, 5, 6, 24, 0, 0},     // v2 P5: Cin 192
-};
-static const HeadCfg* find_cfg(int c3t, int kpt, bool* split_a = nullptr) {
-  static const bool merged_a = getenv("LITEPI_HEAD_MERGED_A") != nullptr;   // A/B switch: the merged stage A on every shape
-  static const bool one_wg = getenv("LITEPI_HEAD_1WG") != nullptr;   // A/B switches: the 16 x 16 one-workgroup shape,
-  static const bool two_wg = getenv("LITEPI_HEAD_2WG") != nullptr;   // the two-workgroup shape of round 2,
-  static const bool a32 = getenv("LITEPI_HEAD_A32") != nullptr;      // round 3's stage A (32-pixel slots)
-  for (auto& c : kHeadCfg)
-    if (c.c3t == c3t && c.kpt == kpt && !(one_wg && c.slotf <= 12) && !(c.ovl && two_wg) && !(c.a16 && (a32 || one_wg || two_wg))) {
-      if (split_a) *split_a = c.split_a && !merged_a;
-      return &c;
-    }
-  return nullptr;
-}
-
-bool HeadLayer::supported(int cin_phys, int c2, int c3, int nc, int reg_max, int h, int w) {
-  if (c2 != 64 || reg_max != 16 || nc < 1 || nc > 32 || c3 < 8 || c3 > 64 || c3 % 8 != 0) return false;
-  if (cin_phys % 16 != 0) return false;
-  (void)h; (void)w;
-  return find_cfg(c3 > 32 ? 2 : 1, cin_phys / 16) != nullptr;
-}
-
-void HeadLayer::build(int cin_phys, int c3_, int nc_, int h, int w, int batch_hint, const Src& s) {
-  Cin = cin_phys; c3 = c3_; nc = nc_; H = h; W = w;
-  C3T = c3 > 32 ? 2 : 1;
-  KPT = Cin / 16;
-  bool split = false;
-  const HeadCfg* cfg = find_cfg(C3T, KPT, &split);
-  LP_CHECK(cfg, LP_ERR_STATE, "Detect head %s: no kernel configuration for Cin %d", name.c_str(), Cin);
-  TH = cfg->th; TW = cfg->tw; PA = cfg->pa; PB = cfg->pb; NPC = cfg->npc; KSA = cfg->ksa; SLOTF = cfg->slotf; OVL = cfg->ovl; A16 = cfg->a16;
-  lds_bytes = head_lds(TH, TW, KPT, C3T, SLOTF, OVL);
-  const int RT = 2 + C3T, CM = 32 * C3T;
-  // chunks hold at most 24 fragments (one ring slot): stage A KSA K steps x RT row tiles, stage B box 12 x 2, class 18 x 1
-  // (12 x 2 for two class row tiles), projections 2 (4) and 8
-  LP_CHECK(KSA % 2 != 0 || 9 * KPT / KSA >= 2, LP_ERR_STATE, "Detect head %s: stage A needs two chunks", name.c_str());
-  const int SPT = (KPT + 1) / 2;   // A16: K steps of 32 channels per tap (Cin = 16 mod 32: the last one half zero weights)
-  // split stage A: a pass of RTP row tiles per half-step puts as many K steps (2 RTP fragments each) into a chunk as a slot addresses
-  // -- fragment 7 of an 8-fragment slot is not addressable -- and as divide the 9 SPT steps of the conv
-  SPLIT_A = cfg && A16 && split;
-  KSAC = NCAC = KSAB = NCAB = 0;
-  if (SPLIT_A) {
-    auto steps_per_chunk = [&](int rtp) {
-      int d = (SLOTF == 8 ? 7 : SLOTF) / (2 * rtp);
-      while (d > 1 && (9 * SPT) % d != 0) --d;
-      return d;
-    };
-    const int kc = steps_per_chunk(C3T), kb = steps_per_chunk(2);
-    LP_CHECK(kc >= 1 && kb >= 1, LP_ERR_STATE, "Detect head %s: a K step of the split stage A does not fit a ring slot", name.c_str());
-    KSAC = 2 * kc; NCAC = 9 * SPT / kc; KSAB = 2 * kb; NCAB = 9 * SPT / kb;
-  }
-  if (A16)   // a chunk is KSA half-steps = KSA / 2 K steps x two row halves; fragment 7 of an 8-fragment slot is not addressable
-    LP_CHECK(KSA % 2 == 0 && (9 * SPT) % (KSA / 2) == 0 && RT * KSA <= (SLOTF == 8 ? 7 : SLOTF) && (TH + 2) * (TW + 2) <= 64 * PA &&
-                 (KPT % 2 == 0 || (OVL && (size_t)(TH + 4) * (TW + 4) * (2 * KPT + 1) + 1 <= (size_t)(TH + 2) * (TW + 2) * (4 * RT + 1))), LP_ERR_STATE,   // (odd KPT: the zeroed guard slot behind the tile lies inside MID's span)
-             "Detect head %s: inconsistent 16-pixel-tile configuration", name.c_str());
-  LP_CHECK(lds_bytes <= (SLOTF == 8 ? 53760u : (SLOTF == 12 ? 80u * 1024 : 160u * 1024)) && ((TW + 4) * (2 * KPT + 1) + 63) / 64 == NPC &&
-               (A16 || ((9 * KPT) % KSA == 0 && RT * KSA <= SLOTF)) && TH + 4 <= (SLOTF <= 12 && !(OVL && SLOTF == 12) ? 12 : (OVL ? 16 : 20)) &&
-               (SLOTF == 8 || SLOTF == 12 || SLOTF == 24) &&
-               (SLOTF != 8 || C3T == 1) &&   // (fragment 7 of an 8-fragment slot: only the box tower's chunks and the box projection)
-               (A16 || (TH + 2) * (TW + 2) <= 128 * PA) && TH * TW <= 128 * PB, LP_ERR_STATE, "Detect head %s: inconsistent configuration", name.c_str());
-  (void)batch_hint;
-  std::vector<uint16_t> stream;
-  auto frag = [&](auto&& weight_of) {  // weight_of(row rho, k element e of the K step) -> float; appends one 1 KiB fragment
-    const size_t base = stream.size();
-    stream.resize(base + 512);
-    for (int lane = 0; lane < 64; ++lane)
-      for (int j = 0; j < 8; ++j) stream[base + lane * 8 + j] = f32_to_f16(weight_of(lane & 31, 8 * (lane >> 5) + j));
+// The shapes, their consistency conditions and the weight stream's layout are head_plan.h's (namespace hplan, host-only): build()
+// is "plan, pack, upload", launch() an index into hplan::kHeadVariants -- the rows of that table are the instantiations.
+void HeadLayer::build(int cin_phys, int c3_, int nc_, int h, int w, const hplan::HeadSwitches& sw, const Src& s) {
+  static_cast<hplan::HeadPlan&>(*this) = hplan::plan_head(cin_phys, 64, c3_, nc_, 16, sw);
+  LP_CHECK(ok, LP_ERR_STATE, "Detect head %s (Cin %d): %s", name.c_str(), cin_phys, plan_err);
+  H = h; W = w; flags = sw.flags;
+  const hplan::HeadPack pk = hplan::pack_head(*this, s);
+  LP_CHECK(!pk.pack_err, LP_ERR_STATE, "Detect head %s: %s", name.c_str(), pk.pack_err);
+  auto up = [](DevBuf& d, const void* p, size_t bytes, size_t slack) {
+    d.alloc(bytes + slack);
+    LP_HIP(hipMemcpy(d.p, p, bytes, hipMemcpyHostToDevice));
   };
-  coff.clear(); csz.clear(); cks.clear();
-  auto begin_chunk = [&]() { coff.push_back((unsigned short)(stream.size() / 512)); };
-  auto end_chunk = [&](int ksteps) {
-    const size_t nf = stream.size() / 512 - coff.back();
-    LP_CHECK(nf >= 1 && (int)nf <= SLOTF, LP_ERR_STATE, "Detect head: chunk of %zu fragments", nf);
-    csz.push_back((unsigned char)nf);
-    cks.push_back((unsigned char)ksteps);
-    stream.resize((size_t)(coff.back() + SLOTF) * 512, 0);   // every chunk is a whole slot image
-  };
-  const std::vector<float>& wa = *s.wa;  // [64 + c3][9][Cin]
-  // ---- stage A on 16x16x32 MFMAs: chunk = tap; K step (tap, q) covers input channels 32 q .. 32 q + 31; per K step two half-steps
-  //      of RT row tiles (16 rows each).  Fragment lane l: row l & 15 of the tile, K group kg = l >> 4 = channel slot gam(kg) =
-  //      {0, 2, 1, 3} of the step's four (the kernel's pixel fragments read the same slot order: conflict-free LDS reads).  Row r
-  //      of row tile R (= rh * RT + rt) is physical MID channel 32 (R >> 1) + 8 (r >> 2) + 4 (R & 1) + (r & 3): a lane's D
-  //      registers of tiles 2t | 2t+1 are then 8 consecutive channels of one pixel -> one 16-byte MID store.
-  auto frag16 = [&](auto&& weight_of) {  // weight_of(row r, k element e of the 32) -> float; appends one 1 KiB fragment
-    const size_t base = stream.size();
-    stream.resize(base + 512);
-    for (int lane = 0; lane < 64; ++lane)
-      for (int j = 0; j < 8; ++j) {
-        const int kg = lane >> 4, slot = (kg & 1) * 2 + (kg >> 1);
-        stream[base + lane * 8 + j] = f32_to_f16(weight_of(lane & 15, 8 * slot + j));
-      }
-  };
-  // one pass of the A16 first convs: RTP row tiles per half-step from row tile R0 on, KPC K steps per chunk
-  auto packA16 = [&](int R0, int RTP, int KPC) {
-    for (int ks = 0; ks < 9 * SPT; ++ks) {
-      const int tap = ks / SPT, q = ks % SPT;
-      if (ks % KPC == 0) begin_chunk();
-      for (int rh = 0; rh < 2; ++rh)
-        for (int rt = 0; rt < RTP; ++rt)
-          frag16([&](int r, int e) {
-            const int R = R0 + rh * RTP + rt;
-            const int c = 32 * (R >> 1) + 8 * (r >> 2) + 4 * (R & 1) + (r & 3);   // physical MID channel
-            const int src = c < 64 ? c : (c - 64 < c3 ? 64 + (c - 64) : -1);
-            return (src < 0 || 32 * q + e >= Cin) ? 0.f : wa[((size_t)src * 9 + tap) * Cin + 32 * q + e];
-          });
-      if (ks % KPC == KPC - 1) end_chunk(2 * KPC);
-    }
-  };
-  if (A16 && !SPLIT_A) packA16(0, RT, KSA / 2);
-  if (SPLIT_A) packA16(4, C3T, KSAC / 2);   // the class rows: row tiles 4 ..; the box rows follow the class projection
-  // ---- stage A: K step (tap, cg): element e = input channel 16*cg + e
-  for (int ks = 0; ks < (A16 ? 0 : 9 * KPT); ++ks) {
-    if (ks % KSA == 0) begin_chunk();
-    const int tap = ks / KPT, cg = ks % KPT;
-    for (int rt = 0; rt < RT; ++rt)
-      frag([&](int rho, int e) {
-        const int c = rt * 32 + row_channel(rho);          // physical MID channel
-        const int src = c < 64 ? c : (c - 64 < c3 ? 64 + (c - 64) : -1);
-        return src < 0 ? 0.f : wa[((size_t)src * 9 + tap) * Cin + 16 * cg + e];
-      });
-    if (ks % KSA == KSA - 1) end_chunk(KSA);
-  }
-  // ---- stage B class (in front of the box tower: the kernel runs it first): 2*C3T K steps per tap
-  {
-    const int per_tap = 2 * C3T, total = 9 * per_tap, per_chunk = C3T == 2 ? SLOTF / 2 : (SLOTF >= 18 ? 18 : 6);
-    for (int kq = 0; kq < total; ++kq) {
-      if (kq % per_chunk == 0) begin_chunk();
-      const int tap = kq / per_tap, cg = kq % per_tap;
-      for (int rt = 0; rt < C3T; ++rt)
-        frag([&](int rho, int e) {
-          const int co = rt * 32 + row_channel(rho), ci = 16 * cg + e;
-          return (co < c3 && ci < c3) ? (*s.wbc)[((size_t)co * 9 + tap) * c3 + ci] : 0.f;
-        });
-      if (kq % per_chunk == per_chunk - 1) end_chunk(per_chunk);
-    }
-  }
-  // ---- stage C: K step (mt, s): element e of lane half hh = mid channel 32*mt + 16*hh + 8*s + (e & 7), hh = e >> 3
-  auto box_proj = [&]() {
-    for (int rt = 0; rt < 2; ++rt)
-      for (int q = 0; q < 4; ++q)
-        frag([&](int rho, int e) {
-          const int mt = q >> 1, sq = q & 1;
-          const int ci = 32 * mt + 16 * (e >> 3) + 8 * sq + (e & 7);
-          return (*s.wpb)[(size_t)(rt * 32 + row_channel(rho)) * 64 + ci];
-        });
-  };
-  auto cls_proj = [&]() {
-    for (int q = 0; q < 2 * C3T; ++q)
-      frag([&](int rho, int e) {
-        const int mt = q >> 1, sq = q & 1;
-        const int ci = 32 * mt + 16 * (e >> 3) + 8 * sq + (e & 7), co = row_channel(rho);
-        return (co < nc && ci < c3) ? (*s.wpc)[(size_t)co * c3 + ci] : 0.f;
-      });
-  };
-  // stream order = consumption order: A chunks | class-B chunks | class projection | box-B chunks | box projection (a workgroup
-  // whose tile holds no candidate leaves behind the class projection); split stage A: class-A chunks | class-B chunks | class
-  // projection | box-A chunks | box-B chunks | box projection
-  begin_chunk(); cls_proj(); end_chunk(0);
-  if (SPLIT_A) packA16(0, 2, KSAB / 2);
-  // ---- stage B box: K step kq = (tap, cg), 4 per tap
-  const int KSB = SLOTF / 2;   // two row tiles per step
-  for (int kq = 0; kq < 36; ++kq) {
-    if (kq % KSB == 0) begin_chunk();
-    const int tap = kq >> 2, cg = kq & 3;
-    for (int rt = 0; rt < 2; ++rt)
-      frag([&](int rho, int e) { return (*s.wbb)[((size_t)(rt * 32 + row_channel(rho)) * 9 + tap) * 64 + 16 * cg + e]; });
-    if (kq % KSB == KSB - 1) end_chunk(KSB);
-  }
-  begin_chunk(); box_proj(); end_chunk(0);
-  nchunks = (int)coff.size();
-  {  // what the kernel's chunk counter walks through: stage A, the class tower, its projection, the box tower, its projection
-    const int ncA = SPLIT_A ? NCAC + NCAB : (A16 ? 9 * SPT / (KSA / 2) : 9 * KPT / KSA), ncC = C3T == 2 ? 36 / (SLOTF / 2) : 18 / (SLOTF >= 18 ? 18 : 6);
-    LP_CHECK(nchunks == ncA + ncC + 1 + 36 / (SLOTF / 2) + 1, LP_ERR_STATE, "Detect head %s: %d chunks in the weight stream", name.c_str(), nchunks);
-  }
-  LP_CHECK(nchunks <= 64 && stream.size() / 512 < 65536, LP_ERR_STATE, "Detect head: weight stream too long (%d chunks)", nchunks);
-  stream.resize(stream.size() + (size_t)2 * SLOTF * 512, 0);   // the ring requests two chunks past the end
-  d_stream.alloc(stream.size() * 2 + 64);   // (one copy: replicating the stream per XCD changed nothing -- it is L2-resident)
-  LP_HIP(hipMemcpy(d_stream.p, stream.data(), stream.size() * 2, hipMemcpyHostToDevice));
-  std::vector<float> bA(32 * RT + 16, 0.f), bB(32 * RT + 16, 0.f), bC(64 + 32 + 16, 0.f);
-  for (int c = 0; c < 64; ++c) { bA[c] = (*s.ba)[c]; bB[c] = s.bbb->empty() ? 0.f : (*s.bbb)[c]; bC[c] = s.bpb->empty() ? 0.f : (*s.bpb)[c]; }
-  for (int c = 0; c < c3; ++c) { bA[64 + c] = (*s.ba)[64 + c]; bB[64 + c] = s.bbc->empty() ? 0.f : (*s.bbc)[c]; }
-  for (int c = 0; c < nc; ++c) bC[64 + c] = s.bpc->empty() ? 0.f : (*s.bpc)[c];
-  auto up = [](DevBuf& d, const std::vector<float>& v) {
-    d.alloc(v.size() * 4);
-    LP_HIP(hipMemcpy(d.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-  };
-  up(d_biasA, bA); up(d_biasB, bB); up(d_biasC, bC);
-  (void)CM;
+  up(d_stream, pk.stream.data(), pk.stream.size() * 2, 64);   // (one copy: replicating the stream per XCD changed nothing -- it is L2-resident)
+  up(d_biasA, pk.biasA.data(), pk.biasA.size() * 4, 0);
+  up(d_biasB, pk.biasB.data(), pk.biasB.size() * 4, 0);
+  up(d_biasC, pk.biasC.data(), pk.biasC.size() * 4, 0);
   macs_per_image = (double)h * w * (9.0 * Cin * (64 + c3) + 9.0 * 64 * 64 + 9.0 * c3 * c3 + 64.0 * 64 + (double)c3 * nc);
 }
+
+// head_fused_kernel of row I of hplan::kHeadVariants
+template <size_t I> static void launch_variant(const HeadArgs& a, dim3 grid, size_t lds_bytes, hipStream_t st) {
+  constexpr hplan::HeadVariant v = hplan::kHeadVariants[I];
+  constexpr auto kernel = head_fused_kernel<v.c3t, v.pa, v.pb, v.npc(), v.ksa, v.slotf, v.nrw, v.ov, v.a16, v.nca(), v.ksac(), v.ncac(), v.ksab(), v.ncab()>;
+  set_max_dynamic_lds(reinterpret_cast<const void*>(kernel), 160 * 1024);
+  LP_LAUNCH(kernel, grid, dim3(256), lds_bytes, st, a);
+}
+using LaunchVariant = void (*)(const HeadArgs&, dim3, size_t, hipStream_t);
+template <size_t... I> static constexpr std::array<LaunchVariant, sizeof...(I)> launch_table(std::index_sequence<I...>) { return {{&launch_variant<I>...}}; }
+static constexpr auto kLaunchVariant = launch_table(std::make_index_sequence<hplan::kNumHeadVariants>{});
 
 void HeadLayer::launch(const View& in, int N, int anchor_off, int A, const float* anchors, const float* strides, const float* dfl_w,
                        float* out0, const ImgGeom* geom, Cand* cand, int* cand_count, float conf, hipStream_t st) const {
@@ -1087,11 +883,9 @@ void HeadLayer::launch(const View& in, int N, int anchor_off, int A, const float
   a.N = N; a.H = in.H; a.W = in.W; a.Cin = Cin;
   a.TH = TH; a.TW = TW; a.tiles_x = ceil_div(in.W, TW); a.ntiles = a.tiles_x * ceil_div(in.H, TH);
   a.KPT = KPT; a.nchunks = nchunks; a.A = A; a.nc = nc; a.anchor_off = anchor_off;
-  LP_CHECK(in.C == Cin && in.H == H && in.W == W && (int)coff.size() <= 64, LP_ERR_STATE,
-           "Detect head %s: view does not match the plan", name.c_str());
+  LP_CHECK(ok && in.C == Cin && in.H == H && in.W == W, LP_ERR_STATE, "Detect head %s: view does not match the plan", name.c_str());
   const dim3 grid((unsigned)(a.ntiles * N));
-  static const int head_flags = getenv("LITEPI_HEAD_FLAGS") ? atoi(getenv("LITEPI_HEAD_FLAGS")) : 0;
-  a.flags = head_flags;
+  a.flags = flags;
   static const char* stamp_path = getenv("LITEPI_HEAD_STAMPS");
   DevBuf d_stamps;
   if (stamp_path && *stamp_path) {
@@ -1099,61 +893,7 @@ void HeadLayer::launch(const View& in, int N, int anchor_off, int A, const float
     LP_HIP(hipMemsetAsync(d_stamps.p, 0, (size_t)grid.x * 16 * 8, st));   // a workgroup that leaves at the vote writes stamps 0-7, 14 and 15 only (10-13: the split stage A's box pass)
     a.stamps = d_stamps.as<unsigned long long>();
   }
-#define LP_HEAD(C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_)                                                                          \
-  {                                                                                                                               \
-    set_max_dynamic_lds(reinterpret_cast<const void*>(head_fused_kernel<C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_>), 160 * 1024); \
-    LP_LAUNCH((head_fused_kernel<C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_>), grid, dim3(256), lds_bytes, st, a);         \
-  }
-#define LP_HEAD2(C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_)                                                                          \
-  {                                                                                                                                    \
-    set_max_dynamic_lds(reinterpret_cast<const void*>(head_fused_kernel<C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_>), 160 * 1024); \
-    LP_LAUNCH((head_fused_kernel<C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_>), grid, dim3(256), lds_bytes, st, a);                 \
-  }
-#define LP_HEAD16(C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_)                                                                               \
-  {                                                                                                                                          \
-    set_max_dynamic_lds(reinterpret_cast<const void*>(head_fused_kernel<C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_, true>), 160 * 1024); \
-    LP_LAUNCH((head_fused_kernel<C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_, true>), grid, dim3(256), lds_bytes, st, a);                 \
-  }
-#define LP_HEAD16N(C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_, NCA_)                                                                               \
-  {                                                                                                                                                \
-    set_max_dynamic_lds(reinterpret_cast<const void*>(head_fused_kernel<C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_, true, NCA_>), 160 * 1024); \
-    LP_LAUNCH((head_fused_kernel<C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_, true, NCA_>), grid, dim3(256), lds_bytes, st, a);                 \
-  }
-  // split stage A: the kernel's chunk shapes of the two passes are template arguments; they must be what build() packed
-#define LP_HEAD16S(C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_, KSAC_, NCAC_, KSAB_, NCAB_)                                                      \
-  {                                                                                                                                                \
-    LP_CHECK(KSAC == KSAC_ && NCAC == NCAC_ && KSAB == KSAB_ && NCAB == NCAB_, LP_ERR_STATE, "Detect head %s: split stage A packed as %d x %d | %d x %d", \
-             name.c_str(), NCAC, KSAC, NCAB, KSAB);                                                                                                \
-    set_max_dynamic_lds(reinterpret_cast<const void*>(head_fused_kernel<C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_, true, 9, KSAC_, NCAC_, KSAB_, NCAB_>), 160 * 1024); \
-    LP_LAUNCH((head_fused_kernel<C3T_, PA_, PB_, NPC_, KSA_, SLOTF_, NRW_, OV_, true, 9, KSAC_, NCAC_, KSAB_, NCAB_>), grid, dim3(256), lds_bytes, st, a); \
-  }
-  if (SPLIT_A && C3T == 1 && KPT == 2) LP_HEAD16S(1, 3, 1, 2, 2, 8, 3, true, 6, 3, 2, 9)
-  else if (SPLIT_A && C3T == 1 && KPT == 4) LP_HEAD16S(1, 5, 2, 4, 4, 12, 4, true, 12, 3, 6, 6)
-  else if (SPLIT_A && C3T == 1 && KPT == 8) LP_HEAD16S(1, 3, 1, 4, 8, 24, 5, false, 24, 3, 12, 6)
-  else if (SPLIT_A && C3T == 2 && KPT == 3) LP_HEAD16S(2, 3, 1, 3, 2, 12, 3, true, 6, 6, 6, 6)
-  else if (SPLIT_A && C3T == 2 && KPT == 6) LP_HEAD16S(2, 3, 1, 3, 2, 12, 4, true, 6, 9, 6, 9)
-  else if (SPLIT_A) throw Error(LP_ERR_STATE, "Detect head: no split-stage-A kernel for this shape");
-  else if (A16 && C3T == 2 && KPT == 3) LP_HEAD16N(2, 3, 1, 3, 2, 12, 3, true, 18)
-  else if (A16 && C3T == 2 && KPT == 6) LP_HEAD16N(2, 3, 1, 3, 2, 12, 4, true, 27)
-  else if (A16 && C3T == 2 && KPT == 12) LP_HEAD16N(2, 3, 1, 6, 6, 24, 4, true, 18)
-  else if (A16 && KPT == 2) LP_HEAD16(1, 3, 1, 2, 2, 8, 3, true)
-  else if (A16 && KPT == 4) LP_HEAD16(1, 5, 2, 4, 4, 12, 4, true)
-  else if (A16 && KPT == 8) LP_HEAD16(1, 3, 1, 4, 8, 24, 5, false)
-  else if (C3T == 1 && KPT == 2 && SLOTF == 8) LP_HEAD(1, 2, 1, 2, 2, 8, 3)
-  else if (C3T == 1 && KPT == 2 && SLOTF == 12) LP_HEAD(1, 2, 1, 2, 2, 12, 3)
-  else if (C3T == 1 && KPT == 2) LP_HEAD(1, 3, 2, 2, 6, 24, 5)
-  else if (C3T == 1 && KPT == 4 && SLOTF == 12) LP_HEAD2(1, 3, 2, 4, 4, 12, 4, true)
-  else if (C3T == 1 && KPT == 4) LP_HEAD(1, 3, 2, 4, 6, 24, 5)
-  else if (C3T == 1 && KPT == 8) LP_HEAD(1, 2, 1, 4, 8, 24, 5)
-  else if (C3T == 2 && KPT == 3) LP_HEAD(2, 3, 2, 3, 3, 24, 5)
-  else if (C3T == 2 && KPT == 6) LP_HEAD(2, 2, 1, 3, 6, 24, 5)
-  else if (C3T == 2 && KPT == 12) LP_HEAD(2, 1, 1, 5, 6, 24, 5)
-  else throw Error(LP_ERR_STATE, "Detect head: no kernel configuration");
-#undef LP_HEAD
-#undef LP_HEAD2
-#undef LP_HEAD16
-#undef LP_HEAD16N
-#undef LP_HEAD16S
+  kLaunchVariant[variant](a, grid, lds_bytes, st);
   LP_HIP(hipGetLastError());
   if (a.stamps) {  // diagnostic: dump [grid][16] stamps, one record per launch
     LP_HIP(hipStreamSynchronize(st));
