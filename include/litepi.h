@@ -586,6 +586,11 @@ int lp_test_nms_boxes(lp_handle* h, const float* boxes, const float* scores, con
 /* PIL-exact ROI resize alone: host BGR crops -> uint8 RGB [R,S,S,3]. */
 int lp_test_roi_resize(lp_handle* h, const uint8_t* const* rois, const int* heights,
                        const int* widths, int R, uint8_t* out_rgb);
+/* The same kernel on R rectangles {x1, y1, x2, y2} (0 <= x1 < x2 <= W, 0 <= y1 < y2 <= H) of one host BGR frame, uploaded
+ * into a buffer of exactly H*W*3 bytes: ROIs at any x offset and row alignment, and at the buffer's two ends
+ * -> uint8 RGB [R,S,S,3].  (additive to ABI 310) */
+int lp_test_roi_resize_rects(lp_handle* h, const uint8_t* frame, int H, int W, const int* rects, int R,
+                             uint8_t* out_rgb);
 /* cv2-style letterbox alone: host BGR image -> uint8 BGR [SH,SW,3] + ratio/pad (lp_config::det_input_h). */
 int lp_test_letterbox(lp_handle* h, const uint8_t* img, int H, int W, uint8_t* out,
                       float* ratio, float* pad_w, float* pad_h);

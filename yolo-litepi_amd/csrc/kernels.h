@@ -152,8 +152,8 @@ struct RoiResizeArgs {
   int max_det, S;
   int linear;               // 0: PIL bilinear with antialias (e2e.py:366-370, 387), 1: cv2.resize INTER_LINEAR (e2e_optimize.py:388-390)
 };
+// one launch, four (ROI, 16-row strip) units per ROI over a grid of the device's resident workgroups; max_items bounds the ROI count
 void launch_roi_resize(const RoiResizeArgs& a, int max_items, hipStream_t st);
-size_t roi_resize_lds_bytes();
 
 // ---- csc_kernels.hip (NV12 frames -> the packed BGR frames the pipeline reads) ---------------
 struct CscFrame {      // one frame of a conversion call, device resident

@@ -373,6 +373,45 @@ int lp_test_roi_resize(lp_handle* h, const uint8_t* const* rois, const int* hs, 
   LP_API_END
 }
 
+// R rectangles of ONE frame: the frame's buffer is exactly H * W * 3 bytes, so a rectangle that touches a corner has the
+// buffer's first or last byte inside it, and an odd W puts the rows on all four alignments
+int lp_test_roi_resize_rects(lp_handle* h, const uint8_t* frame, int H, int W, const int* rects, int R, uint8_t* out_rgb) {
+  LP_API_BEGIN
+  LP_CHECK(h && frame && rects && out_rgb && H >= 1 && W >= 1 && R >= 1, LP_ERR_ARG, "bad argument");
+  LP_CHECK((long)H * W * 3 <= 0x7fffffffL, LP_ERR_ARG, "frame %d x %d too large", H, W);
+  for (int i = 0; i < R; ++i) {
+    const int* rc = rects + 4 * i;
+    LP_CHECK(rc[0] >= 0 && rc[0] < rc[2] && rc[2] <= W && rc[1] >= 0 && rc[1] < rc[3] && rc[3] <= H, LP_ERR_ARG,
+             "rectangle %d (%d, %d, %d, %d) is empty or leaves the %d x %d frame", i, rc[0], rc[1], rc[2], rc[3], W, H);
+  }
+  LP_HIP(hipSetDevice(h->cfg.device));
+  const int S = h->cfg.cls_input;
+  ImgGeom g;
+  memset(&g, 0, sizeof(g));
+  g.h = H; g.w = W;
+  std::vector<int> img(R, 0), slot(R);
+  for (int i = 0; i < R; ++i) slot[i] = i;
+  DevBuf d_src, d_geom, d_rects, d_img, d_slot, d_total, d_base, d_out;
+  d_src.alloc((size_t)H * W * 3, false);
+  LP_HIP(hipMemcpy(d_src.p, frame, (size_t)H * W * 3, hipMemcpyHostToDevice));
+  d_geom.alloc(sizeof(g)); LP_HIP(hipMemcpy(d_geom.p, &g, sizeof(g), hipMemcpyHostToDevice));
+  d_rects.alloc((size_t)R * 16); LP_HIP(hipMemcpy(d_rects.p, rects, (size_t)R * 16, hipMemcpyHostToDevice));
+  d_img.alloc((size_t)R * 4);
+  d_slot.alloc((size_t)R * 4); LP_HIP(hipMemcpy(d_slot.p, slot.data(), (size_t)R * 4, hipMemcpyHostToDevice));
+  d_total.alloc(16); LP_HIP(hipMemcpy(d_total.p, &R, 4, hipMemcpyHostToDevice));
+  d_base.alloc(16);
+  d_out.alloc((size_t)R * S * S * 3);
+  RoiResizeArgs r;
+  r.src = d_src.as<uint8_t>(); r.geom = d_geom.as<ImgGeom>(); r.rects = d_rects.as<int>();
+  r.tab.base = d_base.as<int>(); r.tab.total = d_total.as<int>(); r.tab.img = d_img.as<int>(); r.tab.slot = d_slot.as<int>();
+  r.tab.work = nullptr;
+  r.out = d_out.as<uint8_t>(); r.max_det = R; r.S = S; r.linear = h->cfg.numerics;
+  launch_roi_resize(r, R, h->stream);
+  LP_HIP(hipStreamSynchronize(h->stream));
+  LP_HIP(hipMemcpy(out_rgb, d_out.p, (size_t)R * S * S * 3, hipMemcpyDeviceToHost));
+  LP_API_END
+}
+
 int lp_test_letterbox(lp_handle* h, const uint8_t* img, int H, int W, uint8_t* out, float* ratio, float* pad_w, float* pad_h) {
   LP_API_BEGIN
   test_letterbox(h, img, H, W, out, ratio, pad_w, pad_h, 0);

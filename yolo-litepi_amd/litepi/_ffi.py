@@ -118,7 +118,7 @@ SYMBOLS = [
     "lp_inventory", "lp_inventory_flush", "lp_inventory_drain", "lp_inventory_open", "lp_test_set_rois", "lp_debug_rois",
     "lp_focus_default_config", "lp_focus_config_check", "lp_focus_create", "lp_focus_destroy", "lp_focus_plan", "lp_focus_state",
     "lp_run_focus_device", "lp_run_focus",
-    "lp_letterbox_geometry", "lp_test_letterbox_kernel",
+    "lp_letterbox_geometry", "lp_test_letterbox_kernel", "lp_test_roi_resize_rects",
 ]
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
 
@@ -163,6 +163,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                         C.c_float, C.c_float, C.c_int, C.c_int, vp, ip, ip, ip]
     lib.lp_test_nms_boxes.argtypes = [vp, fp, fp, ip, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp, ip, ip, ip]
     lib.lp_test_roi_resize.argtypes = [vp, u8pp, ip, ip, C.c_int, vp]
+    lib.lp_test_roi_resize_rects.argtypes = [vp, vp, C.c_int, C.c_int, ip, C.c_int, vp]
     lib.lp_test_letterbox.argtypes = [vp, vp, C.c_int, C.c_int, vp, fp, fp, fp]
     lib.lp_test_letterbox_kernel.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, fp, fp, fp]
     lib.lp_roi_overflow.argtypes = [vp, ip, ip]

@@ -737,6 +737,15 @@ class Engine:
         check(self.lib, self.lib.lp_test_roi_resize(self._h, ptrs, hs, ws, len(imgs), out.ctypes.data))
         return out
 
+    def test_roi_resize_rects(self, frame: np.ndarray, rects) -> np.ndarray:
+        """The ROI resize of (x1, y1, x2, y2) rectangles of one BGR frame -> uint8 RGB [R, S, S, 3]."""
+        a = _as_bgr(frame)
+        rc = np.ascontiguousarray(np.array(rects, dtype=np.int32).reshape(-1, 4))
+        S = self.cfg.cls_input
+        out = np.empty((len(rc), S, S, 3), np.uint8)
+        check(self.lib, self.lib.lp_test_roi_resize_rects(self._h, a.ctypes.data, a.shape[0], a.shape[1], _ip(rc), len(rc), out.ctypes.data))
+        return out
+
     def test_letterbox(self, img: np.ndarray, per_pixel: bool = False):
         """The letterbox alone -> (uint8 [SH, SW, 3], ratio, (pad_w, pad_h)); per_pixel: the per-pixel kernel instead of the
         launcher's choice (the tiled kernel where its LDS rows fit)."""
