@@ -107,6 +107,22 @@ void lp_destroy(lp_handle* h);
  * weight blob, checks it is a YOLOv8-family detector (Conv/Swish/C2f/SPPF/Detect+DFL),
  * BN already folded, and builds the device execution plan. */
 int lp_load_detector_ncnn(lp_handle* h, const char* param_path, const char* bin_path);
+/* The same from an ONNX export of the detector (what `yolo export format=onnx` writes and the reference's notebooks run through
+ * ONNX Runtime; opset 11 and later, fp32 initializers, static shapes, the raw Detect output): the file is read here (protobuf
+ * wire format, no dependency), lowered to the layers an NCNN export of the same model has, and planned as one: the same launches
+ * and the same bits.  Both forms behave like the NCNN loader: they replace the handle's detector and drop captured graphs;
+ * the model must have been exported at the handle's det_input_h x det_input.  LP_ERR_IO: the file cannot be read;
+ * LP_ERR_GRAPH: a truncated or malformed file, or a node outside the lowering rules (the message names the node and its op) --
+ * the handle keeps its previous detector.  The memory form reads [data, data + bytes); `name` (may be NULL) stands for the
+ * model in messages.  Tensor names are the ONNX ones (the lp_debug_blob names).  DESIGN.md 6i */
+int lp_load_detector_onnx(lp_handle* h, const char* onnx_path);
+int lp_load_detector_onnx_memory(lp_handle* h, const void* data, size_t bytes, const char* name);
+/* Pure host, no handle, no device: the lowered graph of a model file (bin_path NULL: model_path is an ONNX file; otherwise an
+ * NCNN .param / .bin pair) as text, one line per layer, names left out:
+ * "<type> <n_in> <n_out> <params sorted by id> <crc32 of weight> <crc32 of bias>" (a MemoryData's table stands where the weight
+ * does).  *needed receives the bytes the text takes with its terminator; out may be NULL (*needed only), else cap must hold it
+ * (LP_ERR_ARG). */
+int lp_detector_graph_describe(const char* model_path, const char* bin_path, char* out, size_t cap, size_t* needed);
 /* replaces build_classifier('shufflenetv2') + load_state_dict (e2e.py:331-340): takes the
  * torchvision shufflenet_v2_x1_0 state_dict as n named fp32 host tensors (PyTorch is used by
  * the caller only to read the .pth); BN is folded here. */

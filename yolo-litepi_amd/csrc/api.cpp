@@ -10,21 +10,13 @@
 
 #include "handle.h"
 #include "mbnet.h"
+#include "onnx_graph.h"
 #include "resnet.h"
 
 namespace lp {
 
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& s) { g_last_error = s; }
-
-std::string fmt(const char* f, ...) {
-  char buf[1024];
-  va_list ap;
-  va_start(ap, f);
-  vsnprintf(buf, sizeof(buf), f, ap);
-  va_end(ap);
-  return std::string(buf);
-}
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device attribute: set it once per (device, kernel) and
 // check the result (a kernel that needs more than 64 KB of LDS fails to launch without it)
@@ -163,16 +155,54 @@ void lp_destroy(lp_handle* h) {
   delete h;
 }
 
-int lp_load_detector_ncnn(lp_handle* h, const char* param_path, const char* bin_path) {
-  LP_API_BEGIN
-  LP_CHECK(h && param_path && bin_path, LP_ERR_ARG, "null argument");
+// Every detector loader ends here: the plan is built on a fresh Detector, so a graph the planner refuses leaves the handle's
+// model (and its captured graphs) as they were.
+static void install_detector(lp_handle* h, NcnnGraph&& g, const std::string& name) {
   LP_HIP(hipSetDevice(h->cfg.device));
   std::unique_ptr<Detector> d(new Detector(h->cfg.precision, h->cfg.conv_impl, h->cfg.max_batch, h->det_h(), h->det_w()));
-  d->load(param_path, bin_path);
+  d->load_graph(std::move(g), name);
   h->drop_graphs();
   h->det = std::move(d);
   h->alloc_post_buffers();
   LP_HIP(hipDeviceSynchronize());
+}
+
+int lp_load_detector_ncnn(lp_handle* h, const char* param_path, const char* bin_path) {
+  LP_API_BEGIN
+  LP_CHECK(h && param_path && bin_path, LP_ERR_ARG, "null argument");
+  NcnnGraph g;
+  g.load(param_path, bin_path);
+  install_detector(h, std::move(g), param_path);
+  LP_API_END
+}
+
+int lp_load_detector_onnx(lp_handle* h, const char* onnx_path) {
+  LP_API_BEGIN
+  LP_CHECK(h && onnx_path, LP_ERR_ARG, "null argument");
+  install_detector(h, onnx_file_to_graph(onnx_path), onnx_path);
+  LP_API_END
+}
+
+int lp_load_detector_onnx_memory(lp_handle* h, const void* data, size_t bytes, const char* name) {
+  LP_API_BEGIN
+  LP_CHECK(h && data && bytes > 0, LP_ERR_ARG, "null argument");
+  const std::string src = name && *name ? name : "<memory>";
+  install_detector(h, onnx_to_graph(data, bytes, src), src);
+  LP_API_END
+}
+
+int lp_detector_graph_describe(const char* model_path, const char* bin_path, char* out, size_t cap, size_t* needed) {
+  LP_API_BEGIN
+  LP_CHECK(model_path && needed, LP_ERR_ARG, "null argument");
+  NcnnGraph g;
+  if (bin_path) g.load(model_path, bin_path);
+  else g = onnx_file_to_graph(model_path);
+  const std::string text = g.describe();
+  *needed = text.size() + 1;
+  if (out) {
+    LP_CHECK(cap >= *needed, LP_ERR_ARG, "buffer of %zu bytes, %zu needed", cap, *needed);
+    memcpy(out, text.c_str(), *needed);
+  }
   LP_API_END
 }
 

@@ -14,18 +14,11 @@
 #include <vector>
 
 #include "../../include/litepi.h"
+#include "error.h"   // Error, fmt, LP_CHECK (host-pure: no HIP headers)
 #include "f16.h"   // f32_to_f16, f16_to_f32
 
 namespace lp {
 
-// ---- errors ---------------------------------------------------------------------
-struct Error : std::runtime_error {
-  int code;
-  Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-std::string fmt(const char* f, ...) __attribute__((format(printf, 1, 2)));
-void set_last_error(const std::string& s);
 // raise a kernel's dynamic-LDS limit once per (device, kernel); throws when the runtime refuses
 void set_max_dynamic_lds(const void* fn, int bytes);
 
@@ -59,11 +52,6 @@ bool print_launches();
       hipExtLaunchKernelGGL(kernel, grid, block, lds, st, lt_->e0, lt_->e1, 0, __VA_ARGS__);              \
     else                                                                                                   \
       hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);                                       \
-  } while (0)
-
-#define LP_CHECK(cond, code, ...)                                \
-  do {                                                           \
-    if (!(cond)) throw lp::Error(code, lp::fmt(__VA_ARGS__));    \
   } while (0)
 
 // ---- device memory ----------------------------------------------------------------

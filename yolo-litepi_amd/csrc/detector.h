@@ -52,6 +52,7 @@ class Detector {
  public:
   Detector(int prec, int impl, int max_batch, int input_h, int input_w);
   void load(const std::string& param_path, const std::string& bin_path);
+  void load_graph(NcnnGraph&& graph, const std::string& name);
   bool loaded() const { return loaded_; }
   // imgs: device uint8 BGR [B,SH,SW,3]; geom: device ImgGeom[B]; out0: optional device fp32 [B,4+nc,A].
   // Enqueues the forward pass + decode/conf filter; candidates land in cand/cand_count.

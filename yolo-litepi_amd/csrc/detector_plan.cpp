@@ -9,7 +9,8 @@
 // Channel counts that are not multiples of 8 (v2: 12-channel C2f halves) are padded per
 // segment; padding channels carry zero weights on both sides and stay zero.
 //
-// Detector::load (at the end of the file) runs the Planner's phases in order; emit_ops visits the layers in file order and
+// Detector::load_graph (at the end of the file; Detector::load reads an NCNN pair and calls it, the ONNX loaders hand it
+// onnx_graph.cpp's lowering) runs the Planner's phases in order; emit_ops visits the layers in file order and
 // tries the fusion rules of a Convolution in the fixed order of emit_convolution.
 #include "detector.h"
 #include <cstring>
@@ -114,9 +115,9 @@ struct Planner {
   bool c2f_on = false;
   std::vector<float> dfl;      // build_detect_tail
 
-  Planner(Detector& det, const std::string& param, const std::string& bin);
+  Planner(Detector& det, NcnnGraph&& graph, const std::string& source_name);
 
-  // phases, in the order Detector::load runs them
+  // phases, in the order Detector::load_graph runs them
   void find_detect_tail();
   void find_attention_blocks();
   void resolve_aliases_and_swish();
@@ -245,9 +246,9 @@ struct Planner {
   bool match_head_level(const Level& lv, Trip& t);
 };
 
-Planner::Planner(Detector& det, const std::string& param, const std::string& bin)
-    : d(det), prec_(det.prec_), impl_(det.impl_), maxB_(det.maxB_), SH_(det.SH_), SW_(det.SW_), param_path(param), es(det.prec_ == LP_FP16 ? 2 : 4), esd((double)es) {
-  g.load(param, bin);
+Planner::Planner(Detector& det, NcnnGraph&& graph, const std::string& source_name)
+    : d(det), prec_(det.prec_), impl_(det.impl_), maxB_(det.maxB_), SH_(det.SH_), SW_(det.SW_), param_path(source_name), g(std::move(graph)),
+      es(det.prec_ == LP_FP16 ? 2 : 4), esd((double)es) {
   n = (int)L.size();
   d.tensors_.clear(); d.blob2tensor_.clear(); d.buffers_.clear(); d.convs_.clear(); d.ops_.clear(); d.levels_.clear();
   d.bnecks_.clear(); d.dws_.clear(); d.attns_.clear(); d.heads_.clear(); d.c2fs_.clear(); d.c2f_io_.clear(); d.s2cs_.clear(); d.sppfs_.clear();
@@ -1470,7 +1471,14 @@ void Planner::fuse_heads() {
 }
 
 void Detector::load(const std::string& param_path, const std::string& bin_path) {
-  Planner p(*this, param_path, bin_path);   // reads the graph, then clears the previous plan
+  NcnnGraph g;
+  g.load(param_path, bin_path);
+  load_graph(std::move(g), param_path);
+}
+
+// The plan of a graph a reader has produced (ncnn_graph.cpp, onnx_graph.cpp); `name` stands for the model file in messages.
+void Detector::load_graph(NcnnGraph&& graph, const std::string& name) {
+  Planner p(*this, std::move(graph), name);   // clears the previous plan
   p.find_detect_tail();
   p.find_attention_blocks();
   p.resolve_aliases_and_swish();

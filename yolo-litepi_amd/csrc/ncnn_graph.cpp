@@ -105,4 +105,33 @@ void NcnnGraph::load(const std::string& param_path, const std::string& bin_path)
   LP_CHECK(off == blob.size(), LP_ERR_IO, "%s: %zu bytes consumed of %zu", bin_path.c_str(), off, blob.size());
 }
 
+static uint32_t crc32_of(const std::vector<float>& v) {   // zlib's CRC-32 of the values' bytes
+  static uint32_t table[256];
+  if (!table[1])
+    for (uint32_t i = 0; i < 256; ++i) {
+      uint32_t c = i;
+      for (int k = 0; k < 8; ++k) c = c & 1 ? 0xEDB88320u ^ (c >> 1) : c >> 1;
+      table[i] = c;
+    }
+  uint32_t c = 0xFFFFFFFFu;
+  const uint8_t* p = reinterpret_cast<const uint8_t*>(v.data());
+  for (size_t i = 0; i < v.size() * 4; ++i) c = table[(c ^ p[i]) & 0xFF] ^ (c >> 8);
+  return c ^ 0xFFFFFFFFu;
+}
+
+std::string NcnnGraph::describe() const {
+  std::string out;
+  for (auto& l : layers) {
+    out += fmt("%s %zu %zu", l.type.c_str(), l.inputs.size(), l.outputs.size());
+    for (auto& kv : l.params) out += fmt(" %d=%.9g", kv.first, kv.second);
+    for (auto& kv : l.arrays) {
+      out += fmt(" %d=[", -23300 - kv.first);
+      for (size_t i = 0; i < kv.second.size(); ++i) out += fmt(i ? ",%.9g" : "%.9g", kv.second[i]);
+      out += "]";
+    }
+    out += fmt(" %08x %08x\n", crc32_of(l.type == "MemoryData" ? l.data : l.weight), crc32_of(l.bias));
+  }
+  return out;
+}
+
 }  // namespace lp

@@ -1,7 +1,13 @@
 // NCNN .param/.bin reader (host).  Replaces ncnn.Net.load_param / load_model for the
 // detector graphs the reference ships (e2e.py:213-216; format: SURVEY Appendix C).
 #pragma once
-#include "common.h"
+#include <cstdint>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "error.h"
 
 namespace lp {
 
@@ -25,6 +31,9 @@ struct NcnnLayer {
 struct NcnnGraph {
   std::vector<NcnnLayer> layers;
   void load(const std::string& param_path, const std::string& bin_path);  // throws lp::Error(LP_ERR_IO / LP_ERR_GRAPH)
+  // one line per layer, names left out: "<type> <n_in> <n_out> <params sorted by id> <crc32 of weight> <crc32 of bias>" (a MemoryData's
+  // table stands where the weight does): two readers of one model can be compared without a device (lp_detector_graph_describe)
+  std::string describe() const;
 };
 
 }  // namespace lp

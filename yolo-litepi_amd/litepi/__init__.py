@@ -5,6 +5,6 @@ Importable as ``litepi`` once ``yolo-litepi_amd/`` is on ``sys.path`` (the repo-
 load the HIP library; constructing an ``Engine`` (or any of the drop-in classes) does, and fails
 loudly when it is missing -- there is no CPU fallback.
 """
-from .backend import Engine, HybridPipeline, NCNNDetector, PipelineMetrics, PyTorchClassifier  # noqa: F401
+from .backend import Engine, HybridPipeline, NCNNDetector, ONNXDetector, PipelineMetrics, PyTorchClassifier  # noqa: F401
 
-__all__ = ["Engine", "HybridPipeline", "NCNNDetector", "PipelineMetrics", "PyTorchClassifier"]
+__all__ = ["Engine", "HybridPipeline", "NCNNDetector", "ONNXDetector", "PipelineMetrics", "PyTorchClassifier"]

@@ -119,6 +119,7 @@ SYMBOLS = [
     "lp_focus_default_config", "lp_focus_config_check", "lp_focus_create", "lp_focus_destroy", "lp_focus_plan", "lp_focus_state",
     "lp_run_focus_device", "lp_run_focus",
     "lp_letterbox_geometry", "lp_test_letterbox_kernel", "lp_test_roi_resize_rects",
+    "lp_load_detector_onnx", "lp_load_detector_onnx_memory", "lp_detector_graph_describe",
 ]
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
 
@@ -145,6 +146,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_destroy.argtypes = [vp]
     lib.lp_destroy.restype = None
     lib.lp_load_detector_ncnn.argtypes = [vp, C.c_char_p, C.c_char_p]
+    lib.lp_load_detector_onnx.argtypes = [vp, C.c_char_p]
+    lib.lp_load_detector_onnx_memory.argtypes = [vp, vp, C.c_size_t, C.c_char_p]
+    lib.lp_detector_graph_describe.argtypes = [C.c_char_p, C.c_char_p, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.lp_load_classifier_tensors.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(vp), ip]
     lib.lp_detect_raw.argtypes = [vp, vp, C.c_int, vp]
     lib.lp_detect.argtypes = [vp, u8pp, ip, ip, C.c_int, C.c_float, C.c_float, vp, ip]

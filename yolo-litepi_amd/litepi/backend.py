@@ -196,6 +196,18 @@ def focus_config_check(cfg: Optional[_ffi.LpFocusConfig], det_input: int) -> int
     return lib.lp_focus_config_check(C.byref(cfg) if cfg is not None else None, int(det_input))
 
 
+def detector_graph_describe(model_path: str, bin_path: Optional[str] = None) -> List[str]:
+    """The layers a model file lowers to, one line each without names (lp_detector_graph_describe; no device needed):
+    "<type> <n_in> <n_out> <params> <crc32 of weight> <crc32 of bias>".  bin_path None: model_path is an ONNX file."""
+    lib = _ffi.load_library()
+    need = C.c_size_t()
+    m, bn = os.fsencode(model_path), None if bin_path is None else os.fsencode(bin_path)
+    check(lib, lib.lp_detector_graph_describe(m, bn, None, 0, C.byref(need)))
+    buf = C.create_string_buffer(need.value)
+    check(lib, lib.lp_detector_graph_describe(m, bn, buf, need.value, C.byref(need)))
+    return buf.value.decode().splitlines()
+
+
 def det_input_hw(size) -> Tuple[int, int]:
     """A detector input size as (rows, columns): an int is a square, a pair is the reference's letterbox shape (rows, columns)."""
     if isinstance(size, (tuple, list, np.ndarray)):
@@ -252,8 +264,26 @@ class Engine:
             pass
 
     # ---- models ---------------------------------------------------------------------------
-    def load_detector(self, param_path: str, bin_path: str) -> None:
+    def load_detector(self, param_path: str, bin_path: Optional[str] = None) -> None:
+        """An NCNN .param / .bin pair, or one .onnx file (load_detector_onnx)."""
+        if bin_path is None:
+            if not str(param_path).lower().endswith(".onnx"):
+                raise ValueError(f"load_detector({param_path!r}): one argument is an .onnx file; an NCNN model is a .param and a .bin")
+            return self.load_detector_onnx(param_path)
         check(self.lib, self.lib.lp_load_detector_ncnn(self._h, os.fsencode(param_path), os.fsencode(bin_path)))
+        self._detector_loaded()
+
+    def load_detector_onnx(self, onnx_path) -> None:
+        """An ONNX export of the detector (lp_load_detector_onnx), or the bytes of one (lp_load_detector_onnx_memory): the same
+        plan and the same results as the NCNN export of that model."""
+        if isinstance(onnx_path, (bytes, bytearray, memoryview)):
+            data = bytes(onnx_path)
+            check(self.lib, self.lib.lp_load_detector_onnx_memory(self._h, data, len(data), b"<memory>"))
+        else:
+            check(self.lib, self.lib.lp_load_detector_onnx(self._h, os.fsencode(onnx_path)))
+        self._detector_loaded()
+
+    def _detector_loaded(self) -> None:
         self.has_detector = True
         a, nc, rm, macs = C.c_int(), C.c_int(), C.c_int(), C.c_double()
         check(self.lib, self.lib.lp_detector_info(self._h, C.byref(a), C.byref(nc), C.byref(rm), C.byref(macs)))
@@ -815,7 +845,7 @@ class NCNNDetector:
     """e2e.py:195-316.  ``use_gpu``/``num_threads`` are accepted and ignored (the detector always
     runs on the HIP device)."""
 
-    def __init__(self, param_path: str, bin_path: str, input_size=640, use_gpu: bool = False, num_threads: int = 4,
+    def __init__(self, param_path: str, bin_path: Optional[str], input_size=640, use_gpu: bool = False, num_threads: int = 4,
                  input_name: str = "in0", output_name: str = "out0", *, precision: str = "fp16", max_batch: int = 1,
                  max_det: int = 300, device: int = 0, pixel_format: str = "bgr", csc_matrix: str = "bt601",
                  _engine: Optional[Engine] = None):
@@ -823,8 +853,9 @@ class NCNNDetector:
         self.input_name = input_name
         self.output_name = output_name
         print("[HIP Detector] Loading model...")
-        print(f"  Param: {param_path}")
-        print(f"  Bin: {bin_path}")
+        print(f"  {'Param' if bin_path is not None else 'ONNX'}: {param_path}")
+        if bin_path is not None:
+            print(f"  Bin: {bin_path}")
         self.engine = _engine or Engine(precision=precision, max_batch=max_batch, max_det=max_det, det_input=input_size,
                                         device=device)
         if _engine is None:
@@ -858,6 +889,15 @@ class NCNNDetector:
 
     def detect(self, image: np.ndarray, conf_threshold: float = 0.5, iou_threshold: float = 0.45):
         return self.detect_batch([image], conf_threshold, iou_threshold)[0]
+
+
+class ONNXDetector(NCNNDetector):
+    """NCNNDetector for an ONNX export of the detector (what the reference's notebooks run through ONNX Runtime): same
+    ``detect`` / ``detect_batch``, same results as the NCNN export of that model."""
+
+    def __init__(self, onnx_path: str, input_size=640, use_gpu: bool = False, num_threads: int = 4, input_name: str = "images",
+                 output_name: str = "output0", **kw):
+        super().__init__(onnx_path, None, input_size, use_gpu, num_threads, input_name, output_name, **kw)
 
 
 def load_classifier_state(model_path: Optional[str], num_classes: int, arch: str = "shufflenetv2"):
@@ -1045,7 +1085,7 @@ class HybridPipeline:
     """e2e.py:399-531 with one extra method, ``run_batch``.  Detector and classifier share one
     device handle, so detections never leave the GPU between the two stages."""
 
-    def __init__(self, detector_param: str, detector_bin: str, classifier_path: str, classifier_arch: str,
+    def __init__(self, detector_param: str, detector_bin: Optional[str], classifier_path: str, classifier_arch: str,
                  num_classes: int = 58, det_input_size=640, cls_input_size: int = 64, use_gpu_detector: bool = False,
                  detector_threads: int = 4, classifier_device: str = "cpu", batch_size: int = 8, *, precision: str = "fp16",
                  max_batch: int = 1, max_det: int = 300, device: int = 0, max_rois: int = 0, numerics: str = "e2e",
@@ -1053,7 +1093,8 @@ class HybridPipeline:
                  csc_matrix: str = "bt601", track: bool = False, track_config: Optional[Dict] = None, inventory=False,
                  views=None, view_tile: Optional[int] = None, view_overlap: int = 0, view_full_frame: bool = True,
                  focus: Optional[int] = None, focus_config: Optional[Dict] = None):
-        """inventory: True or a dict of lp_inventory_config's fields (max_signs, keep_crops, best, min_hits): every tracked call
+        """detector_param, detector_bin: an NCNN .param / .bin pair, or an .onnx file and None.
+        inventory: True or a dict of lp_inventory_config's fields (max_signs, keep_crops, best, min_hits): every tracked call
         also feeds the engine's sign inventory, while the handle still holds that call's classifier crops; drain_signs() returns
         the finished signs.  Needs track.
         track: run_batch also tracks the detections across calls (lp_track on the engine's tracker, created here with

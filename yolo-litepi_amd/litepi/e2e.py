@@ -40,6 +40,8 @@ def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="E2E HIP (MI355X) detector + classifier evaluation pipeline")
     p.add_argument("--detector_param", type=str, default="../convert/model/yolo_plus/yolo_plus_ncnn_model/model.ncnn.param")
     p.add_argument("--detector_bin", type=str, default="../convert/model/yolo_plus/yolo_plus_ncnn_model/model.ncnn.bin")
+    p.add_argument("--detector_onnx", type=str, default=None,
+                   help="an ONNX export of the detector; overrides --detector_param / --detector_bin")
     p.add_argument("--classifier", type=str, default="../weight/shufflenetv2.pth")
     p.add_argument("--clf_arch", type=str, choices=["resnet18", "efficientnet", "mobilenetv2", "shufflenetv2"], default="shufflenetv2")
     p.add_argument("--input", type=str, default="../Dataset/E2E/data_e2e_tt100k/images/test")
@@ -463,6 +465,8 @@ def run_evaluation(args) -> Dict:
 
     class_names = load_class_names(args.classes)
     num_classes = len(class_names)
+    if getattr(args, "detector_onnx", None):
+        args.detector_param, args.detector_bin = args.detector_onnx, None
     detector_name = Path(args.detector_param).stem
     combo = f"{detector_name}+{args.clf_arch}"
     say(f"\n{'=' * 60}\nMODEL COMBINATION: {combo}\n{'=' * 60}")
