@@ -599,11 +599,36 @@ __global__ __launch_bounds__(320, (NT <= 2 ? 4 : ((NT == 4 && (T2 > 0 || sizeof(
 // x at its offset inside the pixel, and cv2 takes its gathered K groups from the tile instead of from global memory.  The
 // halo read of x alone already pulled whole 64 / 128-byte lines, i.e. the neighbouring segments, through L2 (160x160 maps:
 // 2.7 reads of the concat buffer per output pixel); now it is read once, with the halo.
-#define BN_STAMP(k)                                                                                                   \
+// Addressing (the epilogues were mostly bookkeeping: of ~200 instructions per pixel tile of the cv2 tail about 50 were arithmetic):
+// a wave's pixel tiles walk a row-major region RW pixels wide, tile i holds the pixels p = (wave + 4 i) * 16 + col, so from one tile
+// to the next p grows by 64 = q64 * RW + r64 and (row, column) follow by adds and one compare.  Every offset that is linear in
+// (row, column) -- in LDS, in the image -- follows with one select and one add; nothing is divided per tile, and the only
+// multiplies left are the full-rate 24-bit ones that turn a pixel offset into a tensor's byte offset.
+struct TileWalk {
+  int x, y;
+  __device__ __forceinline__ bool next(int RW, int q64, int r64) {   // -> the column wrapped into the next row
+    x += r64;
+    const bool wrap = x >= RW;
+    x -= wrap ? RW : 0;
+    y += q64 + (wrap ? 1 : 0);
+    return wrap;
+  }
+};
+// a channel quad with every bit ANDed with m (all ones / zero: keep / +0.0)
+__device__ __forceinline__ half4 and_mask(half4 q, unsigned m) {
+  typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(half4, __builtin_bit_cast(u32x2_t, q) & m);
+}
+__device__ __forceinline__ floatx4 and_mask(floatx4 q, unsigned m) { return __builtin_bit_cast(floatx4, __builtin_bit_cast(u32x4, q) & m); }
+#define BN_STAMP(k)                                                                                                 \
   if (a.stamps && threadIdx.x == 0)                                                                                 \
     a.stamps[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + (k)] = ((k) == 0 || (k) == 15) ? wall_clock64() : clock64();
 template <typename T, int NT, int P1, int P2, bool SEP, int T2 = 0, int SG = 0, bool CL = false>
-__global__ __launch_bounds__(256, ((NT >= 4 || P1 >= 15 || (NT == 2 && P1 == 5)) ? 2 : 3)) void bottleneck_mfma_kernel(const BneckArgs a) {
+// (workgroups per CU the registers must allow: the 16x40 tile of an 8-channel fp16 bottleneck with its cv2 -- v1's 160x160 launch,
+//  39 KB of LDS -- runs FOUR per CU and must stay within 128 VGPRs: 127, no scratch.  The other instantiations keep the bound
+//  they had; DESIGN section 7 lists their register counts against the parent's)
+__global__ __launch_bounds__(256, ((NT >= 4 || P1 >= 15 || (NT == 2 && P1 == 5)) ? 2 : (sizeof(T) == 2 && NT == 1 && P1 == 12 && T2 == 1 && SG == 1) ? 4 : 3))
+void bottleneck_mfma_kernel(const BneckArgs a) {
   static_assert(!CL || (SEP && T2 > 0 && SG > 0), "CL: the staged tile must survive conv_a, and cv2's gather must be the straight-line form");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int G = Tr<T>::G;
@@ -621,7 +646,7 @@ __global__ __launch_bounds__(256, ((NT >= 4 || P1 >= 15 || (NT == 2 && P1 == 5))
   const int oy0 = ty * TH, ox0 = tx * TW;
   const int IH = TH + 4, IW = TW + 4, H1 = TH + 2, W1 = TW + 2;
   const int R1 = H1 * W1, R2 = TH * TW;
-  const int n1 = (R1 + 15) >> 4, n2 = (R2 + 15) >> 4;
+  const int n2 = (R2 + 15) >> 4;
 
   // LDS: [tap table 512 B][conv_a fragments S*NT KB][conv_b fragments S*NT KB][cv2 fragments][tile: input, later the intermediate]
   int* lds_toff = reinterpret_cast<int*>(smem);
@@ -710,15 +735,64 @@ __global__ __launch_bounds__(256, ((NT >= 4 || P1 >= 15 || (NT == 2 && P1 == 5))
     bias2[t] = *reinterpret_cast<const floatx4*>(a.b2 + g * 4 * NT + t * 4);
   }
 
-  // ---- conv_a over the (TH+2) x (TW+2) region
-  int pk1[P1], pb1[P1];  // (py << 16) | px of this lane's pixel in tile i (clamped inside the region); its LDS offset
+  // ---- what depends on the lane only
+  // A lane owns the 4 * NT channels from chbase on.  With one or two channel tiles they are all inside the layer or all outside it
+  // (C is a multiple of 8: plan_bneck), so ONE lane mask stands in front of a whole epilogue loop; with NT >= 3 the last lane that
+  // holds channels may hold fewer than 4 * NT of them and the test per channel quad stays.
+  constexpr bool CH_WHOLE = NT <= 2;
+  const int chbase = g * 4 * NT;
+  const bool chok = chbase < a.C;
+  const int c_lim = CH_WHOLE ? 0x7fffffff : a.C;   // handed to store_lane_at: its per-quad channel tests fold away
+  int xsel[NT];        // channel offset of quad t inside a pixel, quad 0 where the layer has no such channel (loads stay inside the pixel)
+  unsigned chm[NT];    // all ones / zero: the layer has quad t
 #pragma unroll
-  for (int i = 0; i < P1; ++i) {
-    int p = (wave + 4 * i) * 16 + col;
-    p = p < R1 ? p : R1 - 1;
-    const int py = (int)(((unsigned)p * a.rcp_w1) >> 16), px = p - py * W1;
-    pk1[i] = (py << 16) | px;
-    pb1[i] = (py * LW + px) * PSA;
+  for (int t = 0; t < NT; ++t) {
+    const bool qok = CH_WHOLE ? chok : chbase + t * 4 < a.C;
+    xsel[t] = qok ? chbase + t * 4 : 0;
+    chm[t] = qok ? 0xffffffffu : 0u;
+  }
+
+  // ---- conv_a over the (TH+2) x (TW+2) region
+  // pb1[i]: LDS offset of this lane's pixel of tile i in the staged tile (TileWalk: adds, no division per tile).  Only a wave's LAST
+  // tile can reach past the region (the tiles before it end below n1 - 1: n1 > 4 (P1 - 1), bneck_tiles_fit): there the lane is
+  // clamped to the region's last pixel and last1 says whether its pixel exists.  in1, bit i: the pixel lies inside the image (asked
+  // for on the map's border only).
+  const bool interior1 = oy0 >= 1 && ox0 >= 1 && oy0 + TH + 1 <= a.H && ox0 + TW + 1 <= a.W;
+  const int p0 = wave * 16 + col;   // this lane's pixel of tile 0; tile i: p0 + 64 i
+  const bool last1 = p0 + 64 * (P1 - 1) < R1;
+  int pb1[P1];
+  int pm1[CL ? P1 : 1];   // CL: the same pixel in the intermediate's own pitch (otherwise PSA == PS and pb1 serves)
+  unsigned in1 = 0xffffffffu;
+  {
+    const int q64 = (int)((64u * a.rcp_w1) >> 16), r64 = 64 - q64 * W1;
+    const int lrow = q64 * LW + r64;
+    int dP = lrow * PSA, dPw = dP + (LW - W1) * PSA, dM = lrow * PS, dMw = dM + (LW - W1) * PS;
+    // (opaque to the optimiser, as act4's constant: it factors the pitch out of the two steps and turns the select-and-add into a
+    //  64-bit multiply-add per tile otherwise)
+    asm("" : "+s"(dP), "+s"(dPw), "+s"(dM), "+s"(dMw));
+    TileWalk w;
+    w.y = (int)(__umul24(p0, a.rcp_w1) >> 16);
+    w.x = p0 - (int)__umul24(w.y, W1);
+    const int lp0 = (int)__umul24(w.y, LW) + w.x;
+    int pb = (int)__umul24(lp0, PSA), pm = (int)__umul24(lp0, PS);
+#pragma unroll
+    for (int i = 0; i < P1; ++i) {
+      if (i > 0) {
+        const bool wrap = w.next(W1, q64, r64);
+        pb += wrap ? dPw : dP;
+        if (CL) pm += wrap ? dMw : dM;
+      }
+      if (i == P1 - 1) {
+        pb = last1 ? pb : ((H1 - 1) * LW + W1 - 1) * PSA;
+        pm = last1 ? pm : ((H1 - 1) * LW + W1 - 1) * PS;
+      }
+      if (!interior1) {   // block-uniform
+        const bool inside = (unsigned)(w.y + oy0 - 1) < (unsigned)a.H && (unsigned)(w.x + ox0 - 1) < (unsigned)a.W;
+        in1 &= inside ? 0xffffffffu : ~(1u << i);
+      }
+      pb1[i] = pb;
+      if (CL) pm1[i] = pm;
+    }
   }
   floatx4 acc[NT][P1];
 #pragma unroll
@@ -748,49 +822,93 @@ __global__ __launch_bounds__(256, ((NT >= 4 || P1 >= 15 || (NT == 2 && P1 == 5))
     __builtin_amdgcn_s_barrier();
   }
   // (interior workgroups -- the conv_a region lies inside the map -- skip the per-pixel inside-the-image arithmetic:
-  //  a block-uniform branch around two copies of the loop)
+  //  a block-uniform branch around two copies of the loop.  Whole tiles store without a test; the wave's last tile asks whether its
+  //  pixel exists; the border form zeroes what lies outside the image -- conv_b's padding -- with an AND)
   auto write_mid = [&](auto interior_tag) {
     constexpr bool INTERIOR = decltype(interior_tag)::value;
 #pragma unroll
     for (int i = 0; i < P1; ++i) {
-      const int p = (wave + 4 * i) * 16 + col;
-      if (wave + 4 * i < n1 && p < R1) {
-        const int py = pk1[i] >> 16, px = pk1[i] & 0xffff;
-        bool inside = true;
-        if constexpr (!INTERIOR) {
-          const int gy = oy0 - 1 + py, gx = ox0 - 1 + px;
-          inside = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-        }
-        T* dst = reinterpret_cast<T*>(tile2 + (py * LW + px) * PS) + g * 4 * NT;
+      if (i == P1 - 1 && !last1) continue;
+      T* dst = reinterpret_cast<T*>(tile2 + (CL ? pm1[CL ? i : 0] : pb1[i])) + chbase;
+      const unsigned inside = INTERIOR ? 0xffffffffu : 0u - ((in1 >> i) & 1u);
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          if (g * 4 * NT + t * 4 < a.C) {
-            typename Tr<T>::quad q;
-            const floatx4 y = act4<T, ACT_SILU>(acc[t][i], bias1[t]);
+      for (int t = 0; t < NT; ++t) {
+        if (CH_WHOLE || chbase + t * 4 < a.C) {
+          typename Tr<T>::quad q;
+          const floatx4 y = act4<T, ACT_SILU>(acc[t][i], bias1[t]);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) q[r] = inside ? (T)y[r] : (T)0.f;
-            *reinterpret_cast<typename Tr<T>::quad*>(dst + t * 4) = q;
-          }
+          for (int r = 0; r < 4; ++r) q[r] = (T)y[r];
+          if constexpr (!INTERIOR) q = and_mask(q, inside);
+          *reinterpret_cast<typename Tr<T>::quad*>(dst + t * 4) = q;
         }
       }
+      __builtin_amdgcn_sched_barrier(0);   // one tile at a time (registers: see the cv2 tail)
     }
   };
-  if (oy0 >= 1 && ox0 >= 1 && oy0 + TH + 1 <= a.H && ox0 + TW + 1 <= a.W) write_mid(std::true_type{});
-  else write_mid(std::false_type{});
+  if (!CH_WHOLE || chok) {
+    if (interior1) write_mid(std::true_type{});
+    else write_mid(std::false_type{});
+  }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
   BN_STAMP(5)
   // ---- conv_b over the TH x TW output tile
-  int pk2[P2], pb2[P2];
+  // Everything the epilogue needs to know about this lane's pixel of tile i is computed here, once, by the same walk: its LDS
+  // offset in the intermediate (pb2; + xsh: x of the same pixel in the staged tile), its offset gp2 from the workgroup's first
+  // pixel in pixels -- a tensor's byte offset is one full-rate 24-bit multiply by its pitch where it is used, 32 bits: the planner
+  // keeps the fused plan only where N H W pitch sizeof(T) < 2^31, cplan::bneck_span_ok; one byte-offset array per tensor would
+  // need no multiply at all but cost the 160x160 launch its fourth workgroup per CU (156 VGPRs against 126) -- and in ok2, bit i,
+  // whether the pixel exists and lies inside the image.  An interior workgroup (the output tile inside the map) asks that of the
+  // wave's last tile only.  gp2 is 0 -- the workgroup's first pixel, always inside the image -- where the pixel is not valid.
+  const bool interior2 = oy0 + TH <= a.H && ox0 + TW <= a.W;
+  const bool last2 = p0 + 64 * (P2 - 1) < R2;
+  const int xsh = (2 * LW + 2) * PS;
+  int pb2[P2];
+  int pa2[CL ? P2 : 1];               // CL: the pixel in the staged tile (pitch PSA)
+  unsigned gp2[P2];                   // the pixel's offset from the workgroup's first pixel, in pixels
+  unsigned ok2 = 0xffffffffu;
+  const int out_pitch_b = (T2 > 0 ? a.out3_pitch : a.out_pitch) * (int)sizeof(T), cat_pitch_b = a.cat_pitch * (int)sizeof(T), in_pitch_b = a.in_pitch * (int)sizeof(T);
+  auto walk2 = [&](auto interior_tag) {
+    constexpr bool INTERIOR = decltype(interior_tag)::value;
+    const int q64 = (int)((64u * a.rcp_tw) >> 16), r64 = 64 - q64 * TW;
+    const int lrow = q64 * LW + r64, grow = q64 * a.W + r64;
+    int dP = lrow * PS, dPw = dP + (LW - TW) * PS, dA = lrow * PSA, dAw = dA + (LW - TW) * PSA;
+    unsigned dG = grow, dGw = grow + a.W - TW;
+    asm("" : "+s"(dP), "+s"(dPw), "+s"(dA), "+s"(dAw), "+s"(dG), "+s"(dGw));   // (opaque: see conv_a's walk)
+    const int hlim = a.H - oy0, wlim = a.W - ox0;
+    TileWalk w;
+    w.y = (int)(__umul24(p0, a.rcp_tw) >> 16);
+    w.x = p0 - (int)__umul24(w.y, TW);
+    int pb = (int)__umul24(__umul24(w.y, LW) + w.x, PS);
+    int pa = (int)__umul24(__umul24(w.y + 2, LW) + w.x + 2, PSA);
+    unsigned gp = __umul24(w.y, a.W) + w.x;
 #pragma unroll
-  for (int i = 0; i < P2; ++i) {
-    int p = (wave + 4 * i) * 16 + col;
-    p = p < R2 ? p : R2 - 1;
-    const int oy = (int)(((unsigned)p * a.rcp_tw) >> 16), ox = p - oy * TW;
-    pk2[i] = (oy << 16) | ox;
-    pb2[i] = (oy * LW + ox) * PS;
-  }
+    for (int i = 0; i < P2; ++i) {
+      if (i > 0) {
+        const bool wrap = w.next(TW, q64, r64);
+        pb += wrap ? dPw : dP;
+        gp += wrap ? dGw : dG;
+        if (CL) pa += wrap ? dAw : dA;
+      }
+      unsigned gpl = gp;   // what this tile uses
+      if (i == P2 - 1 || !INTERIOR) {
+        bool ok = i == P2 - 1 ? last2 : true;
+        if (i == P2 - 1) {   // (the walk ends here: the clamp may overwrite its state)
+          pb = ok ? pb : ((TH - 1) * LW + TW - 1) * PS;
+          pa = ok ? pa : ((TH + 1) * LW + TW + 1) * PSA;
+        }
+        if (!INTERIOR) ok = ok && w.y < hlim && w.x < wlim;
+        gpl = ok ? gp : 0u;
+        ok2 &= ok ? 0xffffffffu : ~(1u << i);
+      }
+      pb2[i] = pb;
+      gp2[i] = gpl;
+      if constexpr (CL) pa2[i] = pa;
+    }
+  };
+  if (interior2) walk2(std::true_type{});
+  else walk2(std::false_type{});
   floatx4 acc2[NT][P2];
 #pragma unroll
   for (int t = 0; t < NT; ++t)
@@ -810,21 +928,28 @@ __global__ __launch_bounds__(256, ((NT >= 4 || P1 >= 15 || (NT == 2 && P1 == 5))
   }
   BN_STAMP(6)
   // ---- epilogue: bias, SiLU, shortcut (x from the preserved input tile, or re-read from global memory)
-  const int chbase = g * 4 * NT;
+  //      Both forms of the epilogue exist twice, as write_mid does: an interior workgroup's whole tiles run without a test.
+  const size_t pix0 = (size_t)((n * a.H + oy0) * a.W + ox0);   // the workgroup's first pixel: wave-uniform bases, 32-bit lane offsets
+  const char* in0 = reinterpret_cast<const char*>(a.in) + pix0 * a.in_pitch * sizeof(T);
+  char* out0 = reinterpret_cast<char*>(T2 > 0 ? a.out3 : a.out) + pix0 * (size_t)out_pitch_b;
   if constexpr (T2 == 0) {
+    auto plain = [&](auto interior_tag) {
+      constexpr bool INTERIOR = decltype(interior_tag)::value;
 #pragma unroll
-    for (int i = 0; i < P2; ++i) {
-      const int p = (wave + 4 * i) * 16 + col;
-      const int gy = oy0 + (pk2[i] >> 16), gx = ox0 + (pk2[i] & 0xffff);
-      if (wave + 4 * i < n2 && p < R2 && gy < a.H && gx < a.W) {
-        const int pix = (n * a.H + gy) * a.W + gx;
+      for (int i = 0; i < P2; ++i) {
+        if ((i == P2 - 1 || !INTERIOR) && !((ok2 >> i) & 1u)) continue;
         floatx4 v[NT];
 #pragma unroll
         for (int t = 0; t < NT; ++t) v[t] = acc2[t][i];
-        const T* xres = SEP ? reinterpret_cast<const T*>(tile + (((pk2[i] >> 16) + 2) * LW + (pk2[i] & 0xffff) + 2) * PSA + c1off) + chbase
-                            : reinterpret_cast<const T*>(a.in) + eoff(pix, a.in_pitch) + chbase;
-        store_lane_at<T, NT, ACT_SILU>(reinterpret_cast<T*>(a.out) + eoff(pix, a.out_pitch) + chbase, xres, chbase, a.C, v, bias2);
+        const T* xres = SEP ? reinterpret_cast<const T*>(tile + pb2[i] + xsh) + chbase
+                            : reinterpret_cast<const T*>(in0 + __umul24(gp2[i], in_pitch_b)) + chbase;
+        store_lane_at<T, NT, ACT_SILU>(reinterpret_cast<T*>(out0 + __umul24(gp2[i], out_pitch_b)) + chbase, xres, chbase, c_lim, v, bias2);
+        __builtin_amdgcn_sched_barrier(0);   // one tile at a time (registers: see the cv2 tail)
       }
+    };
+    if (!CH_WHOLE || chok) {
+      if (interior2) plain(std::true_type{});
+      else plain(std::false_type{});
     }
   } else {
     // ---- ... and cv2 on concat[.., y_last]: per pixel tile, gather the stored segments, turn the accumulators into
@@ -839,12 +964,6 @@ __global__ __launch_bounds__(256, ((NT >= 4 || P1 >= 15 || (NT == 2 && P1 == 5))
     // (~600 cycles) does not cover a global load, and with the loads issued where they are used this loop WAS the kernel
     // (17-27 k of a workgroup's 40-50 k cycles: tools/bneck_stamps.py).
     constexpr int LA = P2 < 4 ? P2 : 4;
-    auto tile_pixel = [&](int i, bool& valid) {
-      const int p = (wave + 4 * i) * 16 + col;
-      const int gy = oy0 + (pk2[i] >> 16), gx = ox0 + (pk2[i] & 0xffff);
-      valid = wave + 4 * i < n2 && p < R2 && gy < a.H && gx < a.W;
-      return valid ? (n * a.H + gy) * a.W + gx : 0;
-    };
     // SG > 0 (fp16): the number of gathered K steps is a template parameter and this loop is straight-line code -- every
     // load unconditional from a valid address, masked by an AND where it is USED.  (A wave-uniform `if (s < a.sg)` or a
     // per-lane `if (valid)` around a load splits the basic block, the value must be complete at the block's end, and the
@@ -853,111 +972,133 @@ __global__ __launch_bounds__(256, ((NT >= 4 || P1 >= 15 || (NT == 2 && P1 == 5))
     constexpr int SGN = FLAT ? SG : SGMAX;
     // (without SEP the shortcut operand x comes from global memory too: requested with the concat segments, 8 bytes per channel
     //  quad, clamped to quad 0 past the layer's channels and masked by the channel test where it is used)
-    typename Tr<T>::quad xq[LA][NT];
-    auto request = [&](int i, u32x4 (&dst)[SGN], typename Tr<T>::quad (&xdst)[NT]) {
-      bool valid;
-      const int pix = tile_pixel(i, valid);
-      if (FLAT && !SEP) {
-        const T* xp = reinterpret_cast<const T*>(a.in) + eoff(pix, a.in_pitch);
+    // What depends on the lane only: the byte offset of its K group of gathered step s inside a pixel -- lanes whose group lies past
+    // the stored segments re-read group 0 of the SAME pixel (group `grp` of the last pixel of the last image would lie past the end
+    // of the buffer) -- and the mask that zeroes what they read where it is used.
+    unsigned gsel[FLAT ? SGN : 1], gmask[FLAT ? SGN : 1];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) xdst[t] = *reinterpret_cast<const typename Tr<T>::quad*>(xp + (chbase + t * 4 < a.C ? chbase + t * 4 : 0));
-      }
-      const T* catpix = reinterpret_cast<const T*>(a.cat) + eoff(pix, a.cat_pitch);
-      // CL: the same groups from the staged tile (the tile pixel is clamped inside the tile: always a valid address)
-      const char* ldspix = tile + (((pk2[i] >> 16) + 2) * LW + (pk2[i] & 0xffff) + 2) * PSA;
+    for (int s = 0; s < (FLAT ? SGN : 0); ++s) {
+      const int grp = 4 * s + g;   // K group = 8 (4) stored concat channels of the pixel, 16 bytes
+      gsel[s] = grp < a.kg ? grp * 16 : 0;
+      gmask[s] = grp < a.kg ? 0xffffffffu : 0u;
+    }
+    const char* cat0 = reinterpret_cast<const char*>(a.cat) + pix0 * a.cat_pitch * sizeof(T);
+    const bool ch3ok = T2 > 2 || g * 4 * T2 < a.C3;   // (C3 is a multiple of 8: up to two output tiles a lane's channels are all in or all out)
+    const int c3_lim = T2 <= 2 ? 0x7fffffff : a.C3;
+    auto tail = [&](auto interior_tag) {
+      constexpr bool INTERIOR = decltype(interior_tag)::value;
+      // is this lane's pixel of tile i one to compute and store?  (an interior workgroup's whole tiles: yes, at compile time)
+      auto tile_ok = [&](int i) { return (i < P2 - 1 && INTERIOR) || ((ok2 >> i) & 1u) != 0; };
+      typename Tr<T>::quad xq[LA][NT];
+      auto request = [&](int i, u32x4 (&dst)[SGN], typename Tr<T>::quad (&xdst)[NT]) {
+        if (FLAT && !SEP) {
+          const T* xp = reinterpret_cast<const T*>(in0 + __umul24(gp2[i], in_pitch_b));
 #pragma unroll
-      for (int s = 0; s < SGN; ++s) {
-        const int grp = 4 * s + g;   // K group = 8 (4) stored concat channels of the pixel
-        if constexpr (CL) {
-          dst[s] = *reinterpret_cast<const u32x4*>(ldspix + (grp < a.kg ? grp * 16 : 0));
-        } else if (FLAT) {
-          // lanes whose group lies past the stored segments re-read group 0 of the SAME pixel (masked where used): the address
-          // stays inside the pixel -- group `grp` of the last pixel of the last image would lie past the end of the buffer
-          dst[s] = *reinterpret_cast<const u32x4*>(catpix + (grp < a.kg ? grp * G : 0));
-        } else {
-          dst[s] = u32x4{0u, 0u, 0u, 0u};
-          if (s < a.sg && valid && grp < a.kg) dst[s] = *reinterpret_cast<const u32x4*>(catpix + grp * G);
+          for (int t = 0; t < NT; ++t) xdst[t] = *reinterpret_cast<const typename Tr<T>::quad*>(xp + xsel[t]);
         }
-      }
-    };
-    u32x4 bgq[LA][SGN];
+        const char* catpix = cat0 + __umul24(gp2[i], cat_pitch_b);
+        // CL: the same groups from the staged tile (the tile pixel is clamped inside the tile: always a valid address)
+        const char* ldspix = CL ? tile + pa2[CL ? i : 0] : tile;
 #pragma unroll
-    for (int i = 0; i < LA; ++i) request(i, bgq[i], xq[i]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < P2; ++i) {
-      if (!FLAT && wave + 4 * i >= n2) continue;  // wave-uniform
-      bool valid;
-      const int pix = tile_pixel(i, valid);
-      typename Tr<T>::frag bg[SGN];
-#pragma unroll
-      for (int s = 0; s < SGN; ++s) {
-        const unsigned m = (!FLAT || (valid && 4 * s + g < a.kg)) ? 0xffffffffu : 0u;
-        bg[s] = as_frag<T>(bgq[i % LA][s] & m);
-      }
-      typename Tr<T>::quad xqi[NT];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) xqi[t] = xq[i % LA][t];
-      if (i + LA < P2) {
-        request(i + LA, bgq[i % LA], xq[i % LA]);
-        __builtin_amdgcn_sched_barrier(0);   // keep the requests up here (the scheduler sinks loads to their first use)
-      }
-      // y_last: activation, round to T, add the shortcut, round again (= store_lane_at), kept as the register B operand
-      const T* xres = SEP ? reinterpret_cast<const T*>(tile + (((pk2[i] >> 16) + 2) * LW + (pk2[i] & 0xffff) + 2) * PSA + c1off) + chbase
-                          : reinterpret_cast<const T*>(a.in) + eoff(pix, a.in_pitch) + chbase;
-      T yl[NT][4];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        typename Tr<T>::quad xr;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) xr[r] = (T)0.f;
-        if (SEP) {  // x from the preserved LDS tile: always a valid address (the tile's pixel is clamped), masked by the add below
-          if (chbase + t * 4 < a.C) xr = *reinterpret_cast<const typename Tr<T>::quad*>(xres + t * 4);
-        } else if (FLAT) {
-          if (valid && chbase + t * 4 < a.C) xr = xqi[t];   // (a select on registers)
-        } else if (valid && chbase + t * 4 < a.C) xr = *reinterpret_cast<const typename Tr<T>::quad*>(xres + t * 4);
-        const floatx4 y = act4<T, ACT_SILU>(acc2[t][i], bias2[t]);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const T q = (T)y[r];
-          yl[t][r] = (T)((float)q + (float)xr[r]);
+        for (int s = 0; s < SGN; ++s) {
+          if constexpr (CL) {
+            dst[s] = *reinterpret_cast<const u32x4*>(ldspix + gsel[s]);
+          } else if constexpr (FLAT) {
+            dst[s] = *reinterpret_cast<const u32x4*>(catpix + gsel[s]);
+          } else {
+            dst[s] = u32x4{0u, 0u, 0u, 0u};
+            if (s < a.sg && tile_ok(i) && 4 * s + g < a.kg) dst[s] = *reinterpret_cast<const u32x4*>(catpix + (4 * s + g) * 16);
+          }
         }
-      }
-      typename Tr<T>::frag bq[SR];
-      if constexpr (sizeof(T) == 2) {
+      };
+      u32x4 bgq[LA][SGN];
 #pragma unroll
-        for (int s = 0; s < SR; ++s)
+      for (int i = 0; i < LA; ++i) request(i, bgq[i], xq[i]);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < P2; ++i) {
+        if (!FLAT && wave + 4 * i >= n2) continue;  // wave-uniform
+        const bool valid = tile_ok(i);
+        const unsigned vmask = (i < P2 - 1 && INTERIOR) ? 0xffffffffu : (valid ? 0xffffffffu : 0u);
+        typename Tr<T>::frag bg[SGN];
+#pragma unroll
+        for (int s = 0; s < SGN; ++s) {
+          if constexpr (FLAT) bg[s] = as_frag<T>(bgq[i % LA][s] & (gmask[s] & vmask));
+          else bg[s] = as_frag<T>(bgq[i % LA][s]);
+        }
+        typename Tr<T>::quad xqi[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) xqi[t] = xq[i % LA][t];
+        if (i + LA < P2) {
+          request(i + LA, bgq[i % LA], xq[i % LA]);
+          __builtin_amdgcn_sched_barrier(0);   // keep the requests up here (the scheduler sinks loads to their first use)
+        }
+        // y_last: activation, round to T, add the shortcut, round again (= store_lane_at), kept as the register B operand
+        T yl[NT][4];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          typename Tr<T>::quad xr;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) xr[r] = (T)0.f;
+          if (SEP) {
+            // x from the preserved LDS tile: always a valid address (the tile's pixel is clamped, the quad is one of the pixel's);
+            // lanes without channels get zero by an AND, not by a branch around the load
+            const char* xpix = CL ? tile + pa2[CL ? i : 0] + c1off : tile + pb2[i] + xsh;
+            xr = and_mask(*reinterpret_cast<const typename Tr<T>::quad*>(reinterpret_cast<const T*>(xpix) + xsel[t]), chm[t]);
+          } else if (FLAT) {
+            xr = and_mask(xqi[t], chm[t] & vmask);
+          } else if (valid && chm[t]) {
+            xr = *reinterpret_cast<const typename Tr<T>::quad*>(reinterpret_cast<const T*>(in0 + __umul24(gp2[i], in_pitch_b)) + chbase + t * 4);
+          }
+          const floatx4 y = act4<T, ACT_SILU>(acc2[t][i], bias2[t]);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            bq[s][r] = yl[2 * s][r];
-            bq[s][4 + r] = (2 * s + 1 < NT) ? yl[(2 * s + 1 < NT) ? 2 * s + 1 : 0][r] : (T)0.f;
+            const T q = (T)y[r];
+            yl[t][r] = (T)((float)q + (float)xr[r]);
           }
-      } else {
+        }
+        typename Tr<T>::frag bq[SR];
+        if constexpr (sizeof(T) == 2) {
+#pragma unroll
+          for (int s = 0; s < SR; ++s)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              bq[s][r] = yl[2 * s][r];
+              bq[s][4 + r] = (2 * s + 1 < NT) ? yl[(2 * s + 1 < NT) ? 2 * s + 1 : 0][r] : (T)0.f;
+            }
+        } else {
+#pragma unroll
+          for (int s = 0; s < SR; ++s)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) bq[s][r] = yl[s][r];
+        }
+        floatx4 o[T2];
+#pragma unroll
+        for (int t = 0; t < T2; ++t) o[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < SGN; ++s) {
+          if (FLAT || s < a.sg) {
+#pragma unroll
+            for (int t = 0; t < T2; ++t) o[t] = Tr<T>::mma(as_frag<T>(lds_w3[(t * ST + s) * 64 + lane]), bg[s], o[t]);
+          }
+        }
 #pragma unroll
         for (int s = 0; s < SR; ++s)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) bq[s][r] = yl[s][r];
-      }
-      floatx4 o[T2];
-#pragma unroll
-      for (int t = 0; t < T2; ++t) o[t] = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < SGN; ++s) {
-        if (FLAT || s < a.sg) {
-#pragma unroll
-          for (int t = 0; t < T2; ++t) o[t] = Tr<T>::mma(as_frag<T>(lds_w3[(t * ST + s) * 64 + lane]), bg[s], o[t]);
+          for (int t = 0; t < T2; ++t) o[t] = Tr<T>::mma(as_frag<T>(lds_w3[(t * ST + sg_n + s) * 64 + lane]), bq[s], o[t]);
+        if (valid && ch3ok) {   // one lane mask per tile: pixel and channels
+          T* o3 = reinterpret_cast<T*>(out0 + __umul24(gp2[i], out_pitch_b)) + g * 4 * T2;
+          if (a.act3 == ACT_SILU) store_lane_at<T, T2, ACT_SILU>(o3, nullptr, g * 4 * T2, c3_lim, o, bias3);
+          else store_lane_at<T, T2, ACT_NONE>(o3, nullptr, g * 4 * T2, c3_lim, o, bias3);
         }
+        // one tile at a time: without the branches that used to end every tile the scheduler interleaves the tiles and keeps
+        // their temporaries alive side by side (156 VGPRs against 126 at 160x160: a workgroup per CU)
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" ::: "memory");   // (and cv2's fragments are read again per tile, not kept in registers for all of them)
       }
-#pragma unroll
-      for (int s = 0; s < SR; ++s)
-#pragma unroll
-        for (int t = 0; t < T2; ++t) o[t] = Tr<T>::mma(as_frag<T>(lds_w3[(t * ST + sg_n + s) * 64 + lane]), bq[s], o[t]);
-      if (valid) {
-        T* o3 = reinterpret_cast<T*>(a.out3) + eoff(pix, a.out3_pitch) + g * 4 * T2;
-        if (a.act3 == ACT_SILU) store_lane_at<T, T2, ACT_SILU>(o3, nullptr, g * 4 * T2, a.C3, o, bias3);
-        else store_lane_at<T, T2, ACT_NONE>(o3, nullptr, g * 4 * T2, a.C3, o, bias3);
-      }
-    }
+    };
+    if (interior2) tail(std::true_type{});
+    else tail(std::false_type{});
   }
   BN_STAMP(7)
   BN_STAMP(15)
@@ -2148,7 +2289,9 @@ template <typename T> static bool launch_bneck(const BottleneckPair& bp, const B
 void BottleneckPair::launch(const View& in, const View& out, int N, hipStream_t st, const View* cat) const {
   LP_CHECK(in.C == C && in.H == out.H && in.W == out.W, LP_ERR_STATE, "bottleneck: view mismatch");
   LP_CHECK((in.pitch % 8) == 0 && (out.pitch % 4) == 0, LP_ERR_STATE, "unaligned channel pitch");
-  LP_CHECK(span_ok(N, in) && span_ok(N, out) && (!cat || span_ok(N, *cat)), LP_ERR_ARG, "bottleneck: a tensor of batch %d exceeds 2^31 elements", N);
+  const int es = prec == LP_FP16 ? 2 : 4;
+  auto bytes_ok = [&](const View& v) { return !v.base || cplan::bneck_span_ok(N, v.H, v.W, v.pitch, es); };   // 32-bit byte offsets in the kernel
+  LP_CHECK(bytes_ok(in) && bytes_ok(out) && (!cat || bytes_ok(*cat)), LP_ERR_ARG, "bottleneck: a tensor of batch %d exceeds 2^31 bytes", N);
   BneckArgs k;
   memset(&k, 0, sizeof(k));
   k.in = in.base; k.out = out.base; k.w1 = a.d_w.p; k.w2 = b.d_w.p; k.b1 = a.d_bias.as<float>(); k.b2 = b.d_bias.as<float>();

@@ -226,6 +226,13 @@ struct BneckTiling {
   int PSA = 0;                  // its pixel pitch in LDS
 };
 
+// bottleneck_mfma_kernel addresses a tensor by a wave-uniform base and 32-bit BYTE offsets: a buffer of n images of h x w pixels,
+// `pitch` elements of elem_bytes apart, may be one of its tensors only below 2^31 bytes.  The planner asks this at load time for the
+// handle's capacity and keeps the layer plan otherwise; BottleneckPair::launch asks it again for the views it is given.
+inline bool bneck_span_ok(long n, long h, long w, long pitch, int elem_bytes) {
+  return (double)n * (double)h * (double)w * (double)pitch * elem_bytes < 2147483648.0;
+}
+
 // a C -> C bottleneck on an h x w map (batch_hint images), tail = nullptr: without cv2.  !ok: no fused plan (LDS capacity, tile
 // limits, no instantiation for the tail)
 inline BneckTiling plan_bneck(int prec, int c, int h, int w, int batch_hint, const BneckTail* tail) {

@@ -972,6 +972,14 @@ bool Planner::try_bottleneck(const ConvSite& c) {
   const int jc = f ? f->conv : -1, tcat = f ? f->t_cat : -1;
   const int tdst = jc >= 0 ? cinfo[jc].tout : tfinal;
   ensure_buffer(tdst);
+  // the kernel's 32-bit byte offsets: every buffer it indexes must stay below 2^31 bytes at the handle's capacity, else the layer plan
+  auto span_ok = [&](int t) {
+    if (t < 0) return true;
+    const Tensor& X = tensors_[t];
+    const int bi = X.parent >= 0 ? tensors_[X.parent].buf : X.buf;
+    return bi < 0 || cplan::bneck_span_ok(maxB_, X.H, X.W, buffers_[bi].Cp, (int)esd);
+  };
+  if (!span_ok(tin) || !span_ok(tdst) || !span_ok(tcat)) return false;
   std::vector<float> wa, ba, wb, bb;
   repack(l, TI, tensors_[tout], 0, tensors_[tout].Cp, wa, ba);
   repack(lb, tensors_[tout], tensors_[tfinal], 0, tensors_[tfinal].Cp, wb, bb);
