@@ -213,10 +213,51 @@ int lp_run_tiled_device(lp_handle* h, const void* dev_imgs, int B, int H, int W,
                         float conf, float iou, int min_area, void* dev_dets, void* dev_counts);
 /* The frame NMS alone (tests): n host candidates of one orig_h x orig_w frame, xyxy in frame pixels, each tagged with its
  * view (0 .. n_views-1) and anchor (0 .. 16383, unique within a view); dets / rects / count / num_det as lp_test_nms_boxes.
- * max_det <= 0: keep every survivor. */
+ * max_det <= 0: keep every survivor.  The handle's lp_set_view_merge setting applies. */
 int lp_test_nms_views(lp_handle* h, const float* boxes, const float* scores, const int* classes, const int* views,
                       const int* anchors, int n, int n_views, int orig_h, int orig_w, float iou, int min_area, int max_det,
                       lp_det* dets, int* rects, int* count, int* num_det);
+
+/* ---- frame NMS of views: match metric and box-union merge (additive to ABI 310) ---- */
+/* The per-class greedy NMS above is the reference's single-image rule.  On overlapping views it leaves a sign that a view
+ * border cuts as a second box inside the whole one (their IoU is small), or lets the cut box replace the whole one.  This
+ * handle setting changes how the frame NMS of lp_run_tiled*, lp_run_views*, lp_run_focus* and lp_test_nms_views matches and
+ * what it emits; lp_detect, lp_run_batch and lp_run_batch_device keep the reference's rule.  Everywhere these comments say
+ * that one view gives lp_run_batch's result, that holds for the DEFAULT setting only: the setting applies to every frame,
+ * a frame with a single view included.
+ *   The candidates of a frame keep their order O: class ascending, score descending, view descending, anchor descending.
+ *   thr = threshold if threshold > 0, else the call's iou.  All arithmetic is fp32, every operation rounded on its own, in
+ *   the order written; keeper i, later candidate j, a = (x2 - x1) * (y2 - y1):
+ *     w = max(0, min(ix2, jx2) - max(ix1, jx1));  h likewise;  inter = w * h
+ *     LP_MATCH_IOU:  m = inter / (((ai + aj) - inter) + 1e-6f)
+ *     LP_MATCH_IOS:  m = inter / (min(ai, aj) + 1e-6f)
+ *     matched  iff  !(m <= thr)
+ *   Walk O: the first candidate not yet absorbed becomes a keeper i; every later candidate j of i's class that is not yet
+ *   absorbed and matches is absorbed by i.  The match always uses i's OWN box, never the growing union, so a candidate
+ *   belongs to the first keeper in O that matches it.  The walk is not iterated: a ~ b, b ~ c, a !~ c gives a (with b) and c.
+ *   LP_MERGE_SUPPRESS: the keeper is emitted with its own box (with LP_MATCH_IOU: the reference's rule, the default).
+ *   LP_MERGE_UNION   : the emitted box is (min x1, min y1, max x2, max y2) over the keeper and everything it absorbed;
+ *                      score, class and the (score, view, anchor) key stay the keeper's.
+ *   The emitted boxes then go through max_det over the keepers' keys, the ROI rectangle and min_area filter, counts /
+ *   num_det / the mean pre-filter score over the keepers, and the ROI list, as before.  DESIGN.md 6j. */
+enum lp_match { LP_MATCH_IOU = 0, LP_MATCH_IOS = 1 };
+enum lp_merge { LP_MERGE_SUPPRESS = 0, LP_MERGE_UNION = 1 };
+typedef struct lp_view_merge {
+  int metric;        /* lp_match */
+  int mode;          /* lp_merge */
+  float threshold;   /* 0 <= threshold < 1; 0 = the call's iou */
+  int reserved[5];   /* zero */
+} lp_view_merge;     /* 32 bytes */
+/* LP_MATCH_IOU, LP_MERGE_SUPPRESS, threshold 0 */
+void lp_view_merge_default(lp_view_merge* cfg);
+/* pure host, no handle, no device: LP_ERR_ARG for an unknown enum value, a threshold that is NaN, negative or >= 1, a
+ * non-zero reserved word or a NULL pointer */
+int lp_view_merge_check(const lp_view_merge* cfg);
+/* the merge of the NEXT calls of lp_run_tiled, lp_run_tiled_device, lp_run_views, lp_run_views_device, lp_run_focus,
+ * lp_run_focus_device and lp_test_nms_views; NULL = the default.  Checked as by lp_view_merge_check before the handle is
+ * touched.  Copied; handle state like lp_set_input_format.  A change drops nothing but makes the view families capture
+ * their steps anew. */
+int lp_set_view_merge(lp_handle* h, const lp_view_merge* cfg);
 
 /* The view gather alone (tests): the views of one host H x W frame, uploaded byte_offset (0..63) bytes past an aligned
  * address, in the frame's view order -> out [n_views, S, S, 3] uint8 BGR (may be NULL: *n_views only). */

@@ -2,6 +2,7 @@
 """Tiled inference throughput (DESIGN.md "Tiled inference").
 
     python tools/tile_bench.py [--frames 3] [--steps 50] [--warmup 10] [--out profiles/tile_bench.json]
+                               [--view_match iou|ios] [--view_merge nms|union] [--conf 0.25] [--skip_profile]
 
 Times lp_run_tiled_device on TT100K-shape 2048x2048 frames (synth.config4_images, grain 8) in fp16 with overlap 128 and
 full_frame 1 -- 17 views per frame -- on a 64-view handle, and in the same process, as the baseline, lp_run_batch_device on
@@ -9,6 +10,11 @@ the same 640x640 views (each frame's letterbox and 16 crops, cut on the host).  
 rounds each, the better round reported, and the kept counts of both are printed.  Seeded synthetic v1 detector whose class bias puts ~8 candidates per view over conf 0.25
 (bench.py's calibration); random ShuffleNetV2 classifier.  One profiled call per conf (0.25, 0.001) gives the new launches'
 times (lp_profile_read).  Prints one JSON line.
+
+--view_match / --view_merge set the frame NMS's merge of the views (Engine.set_view_merge; absent: the handle is not touched).
+For a kernel trace of frame_nms at ONE confidence, --conf sets the confidence of the timed tiled calls and
+--skip_profile leaves out the two profiled calls at 0.25 and 0.001:
+    rocprofv3 --kernel-trace --stats -d out -- python tools/tile_bench.py --conf 0.001 --skip_profile --steps 20 --warmup 5
 """
 import argparse
 import json
@@ -43,6 +49,10 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--view_match", choices=["iou", "ios"], default=None)
+    ap.add_argument("--view_merge", choices=["nms", "union"], default=None)
+    ap.add_argument("--conf", type=float, default=0.25, help="confidence of the timed tiled calls")
+    ap.add_argument("--skip_profile", action="store_true", help="no profiled calls at 0.25 / 0.001 (for a kernel trace at --conf alone)")
     a = ap.parse_args()
     import torch
     from litepi import Engine, ncnn_export, synth
@@ -62,6 +72,8 @@ def main():
     ncnn_export.shift_cls_bias(p, b, float(np.log(0.25 / 0.75) - mid))
     e.load_detector(p, b)
     e.load_classifier(random_shufflenet_state(58, seed=3))
+    if a.view_match is not None or a.view_merge is not None:
+        e.set_view_merge(a.view_match or "iou", a.view_merge or "nms")
     B = a.frames
     d_frames = torch.from_numpy(frames).cuda()
     # baseline input: the very views the tiled path makes of these frames (the letterboxed frame + its 16 crops each), so both
@@ -74,7 +86,7 @@ def main():
     dd = torch.zeros(64 * 300 * 32, dtype=torch.uint8, device="cuda")
     dc = torch.zeros(3 * 64, dtype=torch.int32, device="cuda")
 
-    def tiled(conf=0.25):
+    def tiled(conf=a.conf):
         e.run_tiled_device(d_frames.data_ptr(), B, 2048, 2048, conf, 0.45, 50, dd.data_ptr(), dc.data_ptr(), 128, True)
 
     def plain():
@@ -89,7 +101,7 @@ def main():
     e.synchronize()
     base_kept = dc.cpu().numpy()[n_views:2 * n_views]
     prof = {}
-    for conf in (0.25, 0.001):
+    for conf in () if a.skip_profile else (0.25, 0.001):
         tiled(conf)
         e.synchronize()
         e.profile_next(True)
@@ -100,11 +112,15 @@ def main():
         prof[str(conf)] = {n: dict(ms=round(r["ms"], 4), gbs=round(r["bytes"] / (r["ms"] * 1e6), 1) if r["bytes"] else None)
                            for n, r in recs.items()}
         prof[str(conf)]["kept_per_frame"] = kept
+    tiled()
+    e.synchronize()
+    kept_timed = dc.cpu().numpy()[B:2 * B].tolist()
     e.close()
-    crop = prof["0.25"].get("tile_crop_u8", {})
+    crop = prof.get("0.25", {}).get("tile_crop_u8", {})
     t_plain_rounds = t_plain
     t_best, t_plain = min(t_tiled), min(t_plain)
     res = dict(workload=f"{B} x 2048x2048 frames, fp16, overlap 128, full_frame 1 ({n_views} views), 64-view handle",
+               view_merge=[a.view_match or "iou", a.view_merge or "nms"], conf=a.conf, kept_per_frame=kept_timed,
                tiled_ms_per_call=round(t_best * 1e3, 3), tiled_ms_rounds=[round(t * 1e3, 3) for t in t_tiled],
                tiled_frames_per_s=round(B / t_best, 1),
                baseline_ms_per_call=round(t_plain * 1e3, 3), baseline_ms_rounds=[round(t * 1e3, 3) for t in t_plain_rounds],

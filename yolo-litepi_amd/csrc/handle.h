@@ -165,6 +165,7 @@ struct lp_handle {
   lp::DevBuf d_fgeom, d_ftab, d_vcnt;
   lp::DevBuf d_vwin;   // scaled views (lp_run_views*): the window table, [max_batch] ViewWin; allocated on first use
   std::vector<char> tile_cache;
+  lp_view_merge vmerge = {};   // lp_set_view_merge: how the frame NMS merges a frame's views (zeros: the reference's rule)
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // staged host pass: start, after the ROI resize, after the front, end
   int last_roi_count = 0;
   // ---- input pixel format (lp_set_input_format).  NV12 frames are converted into d_src, which then holds exactly the packed
@@ -321,6 +322,8 @@ struct ViewLayout {
   int L = 0, C = 0, V = 0, max_views = 0;
 };
 void check_tiling(const lp_tiling* t, int S);
+void check_view_merge(const lp_view_merge* m);
+void apply_view_merge(const lp_handle* h, float iou, FrameNmsArgs& a);
 // the frames' views under tiling (lp_tile_grid of every frame) / through one list of {x, y, w, h} views, validated against every frame
 FrameViews tiled_views(int S, const lp_tiling& t, const std::vector<ImgGeom>& fg);
 FrameViews listed_views(const lp_handle* h, const int* views, int n_views, const std::vector<ImgGeom>& fg);

@@ -132,6 +132,7 @@ struct FrameNmsArgs {
   int max_rois;
   int roi_rule;
   int no_small;
+  int metric, mode;       // lp_match / lp_merge (lp_set_view_merge); 0, 0 = the reference's rule.  iou then holds the resolved threshold
 };
 // per-view sort (one workgroup per view slot, V slots), then the merged per-class greedy NMS of every frame (one workgroup
 // per frame; max_views bounds the views of one frame: it sizes the LDS flag masks)

@@ -70,6 +70,38 @@ __device__ __forceinline__ bool nms_suppressed(float ix1, float iy1, float ix2, 
   const float iou = __fdiv_rn(inter, __fadd_rn(__fsub_rn(__fadd_rn(ai, aj), inter), 1e-6f));
   return !(iou <= thr);
 }
+// the match of the frame NMS of views (lp_set_view_merge): IOS = false is nms_suppressed itself; IOS = true divides by the
+// smaller of the two areas, so a box cut by a view border matches the whole box it lies in
+template <bool IOS>
+__device__ __forceinline__ bool view_matched(float ix1, float iy1, float ix2, float iy2, float ai, float jx1, float jy1, float jx2,
+                                             float jy2, float thr) {
+  if (!IOS) return nms_suppressed(ix1, iy1, ix2, iy2, ai, jx1, jy1, jx2, jy2, thr);
+  const float aj = __fmul_rn(__fsub_rn(jx2, jx1), __fsub_rn(jy2, jy1));
+  const float w = fmaxf(0.f, __fsub_rn(fminf(ix2, jx2), fmaxf(ix1, jx1)));
+  const float h = fmaxf(0.f, __fsub_rn(fminf(iy2, jy2), fmaxf(iy1, jy1)));
+  const float inter = __fmul_rn(w, h);
+  const float ios = __fdiv_rn(inter, __fadd_rn(fminf(ai, aj), 1e-6f));
+  return !(ios <= thr);
+}
+// min / max of the 64 lanes' values, in every lane (float min and max commute: the order of the steps does not show)
+__device__ __forceinline__ float wave_min(float v) {
+  for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off));
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
+// LDS atomic min / max of floats through their bit patterns: a non-negative float orders like its int pattern, a negative
+// one like its unsigned pattern reversed, so either sign is exact (no NaN: candidates are clipped coordinates)
+__device__ __forceinline__ void lds_min_f32(float* p, float v) {
+  if (v >= 0.f) atomicMin(reinterpret_cast<int*>(p), __float_as_int(v));
+  else atomicMax(reinterpret_cast<unsigned*>(p), __float_as_uint(v));
+}
+__device__ __forceinline__ void lds_max_f32(float* p, float v) {
+  if (v >= 0.f) atomicMax(reinterpret_cast<int*>(p), __float_as_int(v));
+  else atomicMin(reinterpret_cast<unsigned*>(p), __float_as_uint(v));
+}
 
 // exclusive prefix sum of one int per thread over the workgroup (NMS_THREADS = 16 waves); returns the total via *total
 __device__ __forceinline__ int block_exclusive_scan(int v, int* s_wave /*[17]*/, int* total) {

@@ -127,7 +127,8 @@ int lp_test_nms_views(lp_handle* h, const float* boxes, const float* scores, con
   a.cand = d_cand.as<Cand>(); a.cand_count = d_cnt.as<int>(); a.vcnt = d_vcnt.as<int>(); a.sorted = d_sorted.as<Cand>();
   a.frames = d_fr.as<TileFrame>(); a.vslot = d_vslot.as<int>();
   a.dets = d_dets.as<lp_det>(); a.counts = d_counts.as<int>(); a.rects = d_rects.as<int>(); a.fgeom = d_geom.as<ImgGeom>();
-  a.A = A; a.max_det = max_det; a.nc = nc; a.iou = iou; a.min_area = min_area; a.roi_rule = h->cfg.numerics;
+  a.A = A; a.max_det = max_det; a.nc = nc; a.min_area = min_area; a.roi_rule = h->cfg.numerics;
+  apply_view_merge(h, iou, a);
   launch_view_sort(a, n_views, h->stream);
   launch_frame_nms(a, 1, n_views, h->stream);
   read_one_image(h, d_dets, d_counts, d_rects, dets, rects, count, num_det);

@@ -333,7 +333,9 @@ __device__ __forceinline__ void frame_emit(const FrameNmsArgs& a, int f, int o, 
 
 // At most 64 candidates in the whole frame, none of which max_det can cut (the usual frame at conf 0.25): ONE wave.  Lane t
 // holds candidate t of the concatenation; its rank in the merged order is counted against the other 63 lanes with shuffles,
-// the records are gathered by rank, then the ballot sweep, ROI rule and compaction of nms_small.
+// the records are gathered by rank, then the ballot sweep, ROI rule and compaction of nms_small.  IOS / UNI: the match metric and
+// the box-union merge of lp_set_view_merge; a keeper's union is reduced over the ballot of the lanes it absorbs.
+template <bool IOS, bool UNI>
 __device__ __forceinline__ void frame_nms_small(const FrameNmsArgs& a, int f, const TileFrame& fr, int cnt, int nframes) {
   const int lane = threadIdx.x & 63;
   Cand c;
@@ -366,6 +368,7 @@ __device__ __forceinline__ void frame_nms_small(const FrameNmsArgs& a, int f, co
   unsigned long long alive = __ballot(valid);
   unsigned long long todo = alive, kept = 0ull;
   const float thr = a.iou;
+  float ux1 = bj.x1, uy1 = bj.y1, ux2 = bj.x2, uy2 = bj.y2;   // UNI: this lane's box grown by what it absorbs as a keeper
   while (todo) {  // wave-uniform
     const int i = __ffsll((long long)todo) - 1;
     todo &= todo - 1;
@@ -373,11 +376,17 @@ __device__ __forceinline__ void frame_nms_small(const FrameNmsArgs& a, int f, co
     const float ix1 = __shfl(bj.x1, i), iy1 = __shfl(bj.y1, i), ix2 = __shfl(bj.x2, i), iy2 = __shfl(bj.y2, i);
     const float ai = __shfl(aj, i);
     const int ic = __shfl(bj.cls, i);
-    const bool sup = lane > i && ((alive >> lane) & 1ull) && bj.cls == ic && nms_suppressed(ix1, iy1, ix2, iy2, ai, bj.x1, bj.y1, bj.x2, bj.y2, thr);
+    const bool sup = lane > i && ((alive >> lane) & 1ull) && bj.cls == ic && view_matched<IOS>(ix1, iy1, ix2, iy2, ai, bj.x1, bj.y1, bj.x2, bj.y2, thr);
     const unsigned long long m = __ballot(sup);
     alive &= ~m;
     todo &= ~m;
+    if (UNI && m) {   // wave-uniform
+      const float mx1 = wave_min(sup ? bj.x1 : INFINITY), my1 = wave_min(sup ? bj.y1 : INFINITY);
+      const float mx2 = wave_max(sup ? bj.x2 : -INFINITY), my2 = wave_max(sup ? bj.y2 : -INFINITY);
+      if (lane == i) { ux1 = fminf(ux1, mx1); uy1 = fminf(uy1, my1); ux2 = fmaxf(ux2, mx2); uy2 = fmaxf(uy2, my2); }
+    }
   }
+  if (UNI) { bj.x1 = ux1; bj.y1 = uy1; bj.x2 = ux2; bj.y2 = uy2; }   // only the keepers' boxes are read from here on
   const bool is_kept = (kept >> lane) & 1ull;
   const int nsel = __popcll(kept);
   const ImgGeom gm = a.fgeom[f];
@@ -405,11 +414,18 @@ __device__ __forceinline__ void frame_nms_small(const FrameNmsArgs& a, int f, co
 //      written to the frame's contiguous region of `cand` (free since step 1), its view index in Cand::pad;
 //   2. the chunk-of-64 ballot sweep of nms_kernel, removed / kept flags as bit masks in LDS;
 //   3. max_det over (score, view, anchor), ROI rectangles, order-preserving compaction, the frame's slice of the ROI list.
+// IOS: the match is intersection over the smaller area.  UNI: a keeper's emitted box is the union of its own and of every box
+// it absorbs.  Matching always uses the keeper's OWN box (s_chunk); the union grows in s_union -- over the ballot in the wave-0
+// loop, by LDS atomics from the thread that owns j in the outer phase -- and is written over the keeper's record in merged[]
+// once the chunk's outer phase is done: no later chunk reads an earlier chunk's keepers, the final phases read the union.
+// <false, false> is the reference's rule (e2e.py:89-119).
 // ------------------------------------------------------------------------------------
+template <bool IOS, bool UNI>
 __global__ __launch_bounds__(NMS_THREADS) void frame_nms_kernel(const FrameNmsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ int s_wave[NMS_THREADS / 64 + 1];
   __shared__ float s_chunk[64 * 6];
+  __shared__ float s_union[UNI ? 64 * 4 : 1];
   __shared__ int s_nk, s_base;
   __shared__ double s_red[NMS_THREADS / 64];
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -417,7 +433,7 @@ __global__ __launch_bounds__(NMS_THREADS) void frame_nms_kernel(const FrameNmsAr
   int cnt = 0;
   for (int k = 0; k < fr.nviews; ++k) cnt += a.vcnt[a.vslot[fr.view0 + k]];
   if (cnt <= 64 && cnt <= a.max_det && !a.no_small) {   // block-uniform
-    if (wave == 0) frame_nms_small(a, f, fr, cnt, (int)gridDim.x);
+    if (wave == 0) frame_nms_small<IOS, UNI>(a, f, fr, cnt, (int)gridDim.x);
     return;
   }
   const int nwords = (cnt + 31) >> 5;
@@ -448,6 +464,7 @@ __global__ __launch_bounds__(NMS_THREADS) void frame_nms_kernel(const FrameNmsAr
   const float thr = a.iou;
   const bool single_class = a.nc <= 1;
   for (int c0 = 0; c0 < cnt; c0 += 64) {
+    unsigned long long kept = 0ull;   // wave 0: the chunk's keepers
     if (wave == 0) {
       const int j = c0 + lane;
       const bool valid = j < cnt;
@@ -456,7 +473,8 @@ __global__ __launch_bounds__(NMS_THREADS) void frame_nms_kernel(const FrameNmsAr
       if (valid) bj = merged[j];
       const float aj = __fmul_rn(__fsub_rn(bj.x2, bj.x1), __fsub_rn(bj.y2, bj.y1));
       unsigned long long alive = __ballot(valid && !((removed[valid ? (j >> 5) : 0] >> (j & 31)) & 1u));
-      unsigned long long todo = alive, kept = 0ull;
+      unsigned long long todo = alive;
+      float ux1 = bj.x1, uy1 = bj.y1, ux2 = bj.x2, uy2 = bj.y2;
       int room = single_class ? a.max_det - nkeep : 0x7fffffff;
       while (todo && room > 0) {  // wave-uniform
         const int i = __ffsll((long long)todo) - 1;
@@ -467,15 +485,24 @@ __global__ __launch_bounds__(NMS_THREADS) void frame_nms_kernel(const FrameNmsAr
         const float ai = __shfl(aj, i);
         const int ic = __shfl(bj.cls, i);
         const bool sup = lane > i && ((alive >> lane) & 1ull) && bj.cls == ic &&
-                         nms_suppressed(ix1, iy1, ix2, iy2, ai, bj.x1, bj.y1, bj.x2, bj.y2, thr);
+                         view_matched<IOS>(ix1, iy1, ix2, iy2, ai, bj.x1, bj.y1, bj.x2, bj.y2, thr);
         const unsigned long long m = __ballot(sup);
         alive &= ~m;
         todo &= ~m;
+        if (UNI && m) {   // wave-uniform
+          const float mx1 = wave_min(sup ? bj.x1 : INFINITY), my1 = wave_min(sup ? bj.y1 : INFINITY);
+          const float mx2 = wave_max(sup ? bj.x2 : -INFINITY), my2 = wave_max(sup ? bj.y2 : -INFINITY);
+          if (lane == i) { ux1 = fminf(ux1, mx1); uy1 = fminf(uy1, my1); ux2 = fmaxf(ux2, mx2); uy2 = fmaxf(uy2, my2); }
+        }
       }
       if ((kept >> lane) & 1ull) {
         const int idx = __popcll(kept & ((1ull << lane) - 1ull));
         float* cb = s_chunk + idx * 6;
         cb[0] = bj.x1; cb[1] = bj.y1; cb[2] = bj.x2; cb[3] = bj.y2; cb[4] = aj; cb[5] = __int_as_float(bj.cls);
+        if (UNI) {
+          float* ub = s_union + idx * 4;
+          ub[0] = ux1; ub[1] = uy1; ub[2] = ux2; ub[3] = uy2;
+        }
       }
       if (lane == 0) {   // c0 is a multiple of 64: the chunk owns two whole words of the kept mask
         keptm[c0 >> 5] = (unsigned)kept;
@@ -486,20 +513,35 @@ __global__ __launch_bounds__(NMS_THREADS) void frame_nms_kernel(const FrameNmsAr
     __syncthreads();
     const int nk = s_nk;
     nkeep += nk;
-    if (single_class && nkeep >= a.max_det) break;
+    // one class: max_det keepers are all there will be.  The union of this last chunk's keepers still needs its outer phase.
+    const bool full = single_class && nkeep >= a.max_det;
+    if (!UNI && full) break;
     for (int j = c0 + 64 + tid; j < cnt; j += NMS_THREADS) {
       if ((removed[j >> 5] >> (j & 31)) & 1u) continue;
       const Cand bj = merged[j];
       for (int k = 0; k < nk; ++k) {
         const float* cb = s_chunk + k * 6;
         if (__float_as_int(cb[5]) != bj.cls) continue;
-        if (nms_suppressed(cb[0], cb[1], cb[2], cb[3], cb[4], bj.x1, bj.y1, bj.x2, bj.y2, thr)) {
+        if (view_matched<IOS>(cb[0], cb[1], cb[2], cb[3], cb[4], bj.x1, bj.y1, bj.x2, bj.y2, thr)) {
           atomicOr(&removed[j >> 5], 1u << (j & 31));
+          if (UNI) {   // the FIRST matching keeper of the chunk takes j
+            float* ub = s_union + k * 4;
+            lds_min_f32(ub + 0, bj.x1); lds_min_f32(ub + 1, bj.y1); lds_max_f32(ub + 2, bj.x2); lds_max_f32(ub + 3, bj.y2);
+          }
           break;
         }
       }
     }
     __syncthreads();
+    if (UNI) {
+      if ((kept >> lane) & 1ull) {   // wave 0 only: the other waves' kept is 0
+        const float* ub = s_union + __popcll(kept & ((1ull << lane) - 1ull)) * 4;
+        Cand* m = merged + c0 + lane;
+        m->x1 = ub[0]; m->y1 = ub[1]; m->x2 = ub[2]; m->y2 = ub[3];
+      }
+      __threadfence_block();
+      if (full) break;
+    }
   }
   __syncthreads();
 
@@ -571,14 +613,25 @@ void launch_view_sort(const FrameNmsArgs& a, int V, hipStream_t st) {
   LP_HIP(hipGetLastError());
 }
 
+template <bool IOS, bool UNI>
+static void launch_frame_nms_as(const FrameNmsArgs& b, int F, size_t lds, hipStream_t st) {
+  set_max_dynamic_lds(reinterpret_cast<const void*>(frame_nms_kernel<IOS, UNI>), FRAME_NMS_LDS_CAP);
+  LP_LAUNCH((frame_nms_kernel<IOS, UNI>), dim3(F), dim3(NMS_THREADS), lds, st, b);
+}
+
 void launch_frame_nms(const FrameNmsArgs& a, int F, int max_views, hipStream_t st) {
   LP_CHECK(max_views >= 1 && max_views <= 1024, LP_ERR_ARG, "frame NMS: %d views in one frame (1..1024)", max_views);
   const size_t lds = frame_nms_lds_bytes(max_views * a.A);
   LP_CHECK(lds <= FRAME_NMS_LDS_CAP, LP_ERR_ARG, "frame NMS: a frame of %d views x %d anchors exceeds the LDS flag capacity", max_views, a.A);
-  set_max_dynamic_lds(reinterpret_cast<const void*>(frame_nms_kernel), FRAME_NMS_LDS_CAP);
   FrameNmsArgs b = a;
   b.no_small = getenv("LITEPI_NMS_NO_SMALL") != nullptr ? 1 : a.no_small;   // as launch_nms: A/B switch + the path-equivalence test
-  LP_LAUNCH(frame_nms_kernel, dim3(F), dim3(NMS_THREADS), lds, st, b);
+  LP_CHECK((a.metric == 0 || a.metric == 1) && (a.mode == 0 || a.mode == 1), LP_ERR_ARG, "frame NMS: metric %d / mode %d", a.metric, a.mode);
+  switch (a.metric * 2 + a.mode) {   // chosen on the host: the default instantiation carries none of the merge
+    case 0: launch_frame_nms_as<false, false>(b, F, lds, st); break;
+    case 1: launch_frame_nms_as<false, true>(b, F, lds, st); break;
+    case 2: launch_frame_nms_as<true, false>(b, F, lds, st); break;
+    default: launch_frame_nms_as<true, true>(b, F, lds, st); break;
+  }
   LP_HIP(hipGetLastError());
 }
 

@@ -47,6 +47,23 @@ void check_tiling(const lp_tiling* t, int S) {
   LP_CHECK(t->full_frame == 0 || t->full_frame == 1, LP_ERR_ARG, "tiling full_frame must be 0 or 1 (got %d)", t->full_frame);
 }
 
+// lp_view_merge_check's rule; NULL is an error here (lp_set_view_merge resolves it to the default first)
+void check_view_merge(const lp_view_merge* m) {
+  LP_CHECK(m, LP_ERR_ARG, "null view merge");
+  LP_CHECK(m->metric == LP_MATCH_IOU || m->metric == LP_MATCH_IOS, LP_ERR_ARG, "view merge: unknown metric %d", m->metric);
+  LP_CHECK(m->mode == LP_MERGE_SUPPRESS || m->mode == LP_MERGE_UNION, LP_ERR_ARG, "view merge: unknown mode %d", m->mode);
+  LP_CHECK(m->threshold >= 0.f && m->threshold < 1.f, LP_ERR_ARG, "view merge: threshold %g outside [0, 1) (0 = the call's iou)",
+           (double)m->threshold);   // NaN fails both comparisons
+  for (int r : m->reserved) LP_CHECK(r == 0, LP_ERR_ARG, "view merge: non-zero reserved word");
+}
+
+// the handle's merge setting in a frame NMS launch: metric, mode and the threshold in place of the call's iou
+void apply_view_merge(const lp_handle* h, float iou, FrameNmsArgs& a) {
+  a.metric = h->vmerge.metric;
+  a.mode = h->vmerge.mode;
+  a.iou = h->vmerge.threshold > 0.f ? h->vmerge.threshold : iou;
+}
+
 // ---- a call's frames as view lists ---------------------------------------------------------------------------------------------
 FrameViews tiled_views(int S, const lp_tiling& t, const std::vector<ImgGeom>& fg) {
   FrameViews per(fg.size());
@@ -204,7 +221,8 @@ static void enqueue_view_detect(lp_handle* h, const ViewLayout& lay, int F, floa
   a.frames = h->d_ftab.as<TileFrame>();
   a.vslot = reinterpret_cast<const int*>(h->d_ftab.as<char>() + (size_t)h->cfg.max_batch * sizeof(TileFrame));
   a.dets = dets; a.counts = counts; a.rects = h->d_rects.as<int>(); a.fgeom = h->d_fgeom.as<ImgGeom>();
-  a.A = h->det->num_anchors(); a.max_det = h->cfg.max_det; a.nc = h->det->num_classes(); a.iou = iou; a.min_area = min_area;
+  a.A = h->det->num_anchors(); a.max_det = h->cfg.max_det; a.nc = h->det->num_classes(); a.min_area = min_area;
+  apply_view_merge(h, iou, a);
   if (with_rois) a.tab = h->roi_table();
   a.max_rois = h->max_rois;
   a.roi_rule = h->cfg.numerics;
@@ -342,6 +360,29 @@ int lp_letterbox_geometry(int det_h, int det_w, int H, int W, float* ratio, floa
   if (new_h) *new_h = g.new_h;
   if (top) *top = g.top;
   if (left) *left = g.left;
+  LP_API_END
+}
+
+void lp_view_merge_default(lp_view_merge* cfg) {
+  if (cfg) memset(cfg, 0, sizeof(*cfg));   // LP_MATCH_IOU, LP_MERGE_SUPPRESS, the call's iou
+}
+
+int lp_view_merge_check(const lp_view_merge* cfg) {
+  LP_API_BEGIN
+  check_view_merge(cfg);
+  LP_API_END
+}
+
+int lp_set_view_merge(lp_handle* h, const lp_view_merge* cfg) {
+  LP_API_BEGIN
+  LP_CHECK(h, LP_ERR_ARG, "null handle");
+  if (cfg) check_view_merge(cfg);
+  const lp_view_merge def = {};
+  const lp_view_merge next = cfg ? *cfg : def;
+  if (memcmp(&next, &h->vmerge, sizeof(next)) != 0) {
+    h->vmerge = next;
+    ++h->geom_ver;   // captured steps of the view families hold the old instantiation and threshold
+  }
   LP_API_END
 }
 

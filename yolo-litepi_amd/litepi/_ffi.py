@@ -41,6 +41,12 @@ class LpTiling(C.Structure):
     _fields_ = [("overlap", C.c_int), ("full_frame", C.c_int), ("reserved", C.c_int * 6)]
 
 
+class LpViewMerge(C.Structure):
+    _fields_ = [("metric", C.c_int), ("mode", C.c_int), ("threshold", C.c_float), ("reserved", C.c_int * 5)]
+
+
+LP_MATCH_IOU, LP_MATCH_IOS = 0, 1
+LP_MERGE_SUPPRESS, LP_MERGE_UNION = 0, 1
 LP_PIX_BGR8, LP_PIX_NV12 = 0, 1
 LP_CSC_BT601_LIMITED, LP_CSC_BT709_LIMITED = 0, 1
 
@@ -120,6 +126,7 @@ SYMBOLS = [
     "lp_run_focus_device", "lp_run_focus",
     "lp_letterbox_geometry", "lp_test_letterbox_kernel", "lp_test_roi_resize_rects",
     "lp_load_detector_onnx", "lp_load_detector_onnx_memory", "lp_detector_graph_describe",
+    "lp_view_merge_default", "lp_view_merge_check", "lp_set_view_merge",
 ]
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
 
@@ -225,9 +232,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_focus_state.argtypes = [vp, C.c_int, ip, ip]
     lib.lp_run_focus_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, C.c_float, C.c_float, C.c_int, vp, vp, vp]
     lib.lp_run_focus.argtypes = [vp, u8pp, ip, ip, C.c_int, ip, C.c_float, C.c_float, C.c_int, vp, ip, ip, fp, C.POINTER(LpTiming), ip]
+    vmp = C.POINTER(LpViewMerge)
+    lib.lp_view_merge_default.argtypes = [vmp]
+    lib.lp_view_merge_default.restype = None
+    lib.lp_view_merge_check.argtypes = [vmp]
+    lib.lp_set_view_merge.argtypes = [vp, vmp]
     for s in SYMBOLS:
         if s not in ("lp_last_error", "lp_default_config", "lp_destroy", "lp_track_default_config", "lp_inventory_default_config",
-                     "lp_focus_default_config"):
+                     "lp_focus_default_config", "lp_view_merge_default"):
             getattr(lib, s).restype = C.c_int
     got = lib.lp_version()
     if got != ABI_VERSION:

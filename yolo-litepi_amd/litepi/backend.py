@@ -178,6 +178,27 @@ def inventory_config_check(cfg: Optional[LpInventoryConfig]) -> int:
 FOCUS_CONFIG_FIELDS = ("slots", "side_min", "side_max", "margin", "small_px", "border", "sweep", "sweep_overlap")
 
 
+VIEW_MATCHES = {"iou": _ffi.LP_MATCH_IOU, "ios": _ffi.LP_MATCH_IOS}
+VIEW_MERGES = {"nms": _ffi.LP_MERGE_SUPPRESS, "union": _ffi.LP_MERGE_UNION}
+
+
+def view_merge_config(match: str = "iou", merge: str = "nms", threshold: float = 0.0) -> _ffi.LpViewMerge:
+    """lp_view_merge from the names of its settings (host only, no GPU needed); ValueError for an unknown name."""
+    if match not in VIEW_MATCHES:
+        raise ValueError(f"unknown view match {match!r} (one of {sorted(VIEW_MATCHES)})")
+    if merge not in VIEW_MERGES:
+        raise ValueError(f"unknown view merge {merge!r} (one of {sorted(VIEW_MERGES)})")
+    m = _ffi.LpViewMerge()
+    m.metric, m.mode, m.threshold = VIEW_MATCHES[match], VIEW_MERGES[merge], float(threshold)
+    return m
+
+
+def view_merge_check(cfg: Optional[_ffi.LpViewMerge]) -> int:
+    """lp_view_merge_check's status for a setting (host only, no GPU needed)."""
+    lib = _ffi.load_library()
+    return lib.lp_view_merge_check(C.byref(cfg) if cfg is not None else None)
+
+
 def focus_config(**cfg) -> _ffi.LpFocusConfig:
     """lp_focus_config with the library's defaults (lp_focus_default_config) and the given fields (host only, no GPU needed)."""
     lib = _ffi.load_library()
@@ -332,6 +353,15 @@ class Engine:
 
     def frame_layout(self, H: int, W: int, **fmt) -> Tuple[int, int]:
         return frame_layout(H, W, **fmt)
+
+    # ---- frame NMS of views ----------------------------------------------------------------------
+    def set_view_merge(self, match: str = "iou", merge: str = "nms", threshold: float = 0.0) -> None:
+        """How the frame NMS of the next run_tiled / run_views / run_focus calls, their device twins and test_nms_views merges a
+        frame's views (lp_set_view_merge).  match: "iou" or "ios" (intersection over the smaller box); merge: "nms" (the keeper's
+        own box) or "union" (the box around the keeper and everything it absorbs); threshold: 0 = the call's iou."""
+        m = view_merge_config(match, merge, threshold)
+        check(self.lib, self.lib.lp_set_view_merge(self._h, C.byref(m)))
+        self.view_merge = (match, merge, float(threshold))
 
     def frame_hw(self, frame: np.ndarray) -> Tuple[int, int]:
         """(H, W) of a host frame in the engine's pixel format."""
@@ -1092,7 +1122,8 @@ class HybridPipeline:
                  tile_overlap: Optional[int] = None, tile_full_frame: bool = True, pixel_format: str = "bgr",
                  csc_matrix: str = "bt601", track: bool = False, track_config: Optional[Dict] = None, inventory=False,
                  views=None, view_tile: Optional[int] = None, view_overlap: int = 0, view_full_frame: bool = True,
-                 focus: Optional[int] = None, focus_config: Optional[Dict] = None):
+                 focus: Optional[int] = None, focus_config: Optional[Dict] = None, view_match: Optional[str] = None,
+                 view_merge: Optional[str] = None, view_match_thr: Optional[float] = None):
         """detector_param, detector_bin: an NCNN .param / .bin pair, or an .onnx file and None.
         inventory: True or a dict of lp_inventory_config's fields (max_signs, keep_crops, best, min_hits): every tracked call
         also feeds the engine's sign inventory, while the handle still holds that call's classifier crops; drain_signs() returns
@@ -1112,8 +1143,19 @@ class HybridPipeline:
         chooses on the device, the free ones swept over a window grid (focus_config: lp_focus_config's other fields).  Needs
         track and a max_batch of at least 1 + K; mutually exclusive with tile_overlap, views and view_tile.  The windows of
         the last run_batch are in last_focus_views.
+        view_match, view_merge, view_match_thr: how one frame's views are merged (Engine.set_view_merge): "ios" matches a box a
+        view border cut with the whole box it lies in, "union" emits the box around a keeper and everything it absorbed.  Valid
+        only together with tile_overlap, views, view_tile or focus.
         det_input_size: an int (square) or (rows, columns), e.g. (384, 640) for 16:9 video; tile_overlap, views, view_tile and
         focus need a square."""
+        merge_set = [n for n, v in (("view_match", view_match), ("view_merge", view_merge), ("view_match_thr", view_match_thr)) if v is not None]
+        if merge_set and all(v is None for v in (tile_overlap, views, view_tile, focus)):
+            raise ValueError(f"{', '.join(merge_set)} need one of tile_overlap, views, view_tile or focus: a frame seen through one "
+                             f"letterboxed view has nothing to merge")
+        if merge_set:
+            vm = view_merge_config(view_match or "iou", view_merge or "nms", 0.0 if view_match_thr is None else view_match_thr)
+            if view_merge_check(vm) != 0:
+                raise ValueError(f"view_match_thr {view_match_thr!r} outside [0, 1)")
         for name, value in (("tile_overlap", tile_overlap), ("views", views), ("view_tile", view_tile), ("focus", focus)):
             if value is not None:
                 _square_only(det_input_size, name)
@@ -1152,6 +1194,8 @@ class HybridPipeline:
                              numerics=numerics, cls_arch=classifier_arch if classifier_arch in CLS_ARCHS else "shufflenetv2")
         self.engine.set_input_format(pixel_format, csc_matrix)
         self.pixel_format, self.csc_matrix = pixel_format, csc_matrix
+        if merge_set:
+            self.engine.set_view_merge(view_match or "iou", view_merge or "nms", 0.0 if view_match_thr is None else view_match_thr)
         self.detector = NCNNDetector(detector_param, detector_bin, det_input_size, use_gpu_detector, detector_threads,
                                      _engine=self.engine)
         self.classifier = PyTorchClassifier(classifier_path, classifier_arch, num_classes, cls_input_size, classifier_device,

@@ -104,6 +104,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--focus_side_max", type=int, default=0, help="focus views: the largest window side (0 = 2 x det_input)")
     p.add_argument("--focus_margin", type=float, default=2.0, help="focus views: a window's side is this many times the box's longer side")
     p.add_argument("--no_focus_sweep", action="store_true", help="focus views: leave the free window slots empty instead of sweeping the frame")
+    p.add_argument("--view_match", type=str, choices=["iou", "ios"], default=None,
+                   help="how the boxes of one frame's views are matched (needs --tile_overlap, --view_tile, --views or --focus): iou = the "
+                        "reference's rule; ios = intersection over the smaller box, which pairs a sign cut by a view border with the whole one")
+    p.add_argument("--view_merge", type=str, choices=["nms", "union"], default=None,
+                   help="what a match does: nms = the lower box is dropped; union = the kept box grows to cover what it absorbed")
+    p.add_argument("--view_match_thr", type=float, default=None, help="threshold of --view_match (absent or 0: --iou_threshold)")
     p.add_argument("--raw_frames", type=str, default=None,
                    help="headerless file of concatenated video frames (ffmpeg -f rawvideo) evaluated instead of the images of --input; "
                         "needs --frame_size; frames are named frame_000001, frame_000002, ...")
@@ -399,6 +405,13 @@ def check_frame_args(args) -> None:
     modes = [n for n in ("tile_overlap", "view_tile", "views", "focus") if getattr(args, n, None) is not None]
     if len(modes) > 1:
         raise SystemExit("--" + ", --".join(modes) + " exclude each other: one way of looking at a frame per run")
+    merge_set = [n for n in ("view_match", "view_merge", "view_match_thr") if getattr(args, n, None) is not None]
+    if merge_set and not modes:
+        raise SystemExit("--" + ", --".join(merge_set) + " need one of --tile_overlap, --view_tile, --views or --focus: a frame seen "
+                         "through one letterboxed view has nothing to merge")
+    thr = getattr(args, "view_match_thr", None)
+    if thr is not None and not 0.0 <= thr < 1.0:
+        raise SystemExit(f"--view_match_thr {thr} outside [0, 1)")
     size = getattr(args, "det_input_size", 640)
     if modes and isinstance(size, tuple) and size[0] != size[1]:
         raise SystemExit(f"--{modes[0]} needs a square --det_input_size (it is {size[0]}x{size[1]}): frame views on a rectangular "
@@ -492,6 +505,9 @@ def run_evaluation(args) -> Dict:
                                                            sweep=0 if args.no_focus_sweep else 1))
         max_batch = nb * (1 + args.focus)
         max_rois = max_rois if max_rois > 0 else nb * max_det
+    for name in ("view_match", "view_merge", "view_match_thr"):   # absent: the pipeline is constructed exactly as before
+        if getattr(args, name, None) is not None:
+            view_kw[name] = getattr(args, name)
     import contextlib
     import io
     # with --track off the pipeline is constructed and called exactly as before
