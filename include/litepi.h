@@ -354,6 +354,54 @@ int lp_set_input_format(lp_handle* h, const lp_frame_format* fmt);
 int lp_test_convert_frames(lp_handle* h, const uint8_t* frames, int B, int H, int W, const lp_frame_format* fmt,
                            int byte_offset, uint8_t* out_bgr);
 
+/* ---- decoder surfaces in place (additive to ABI 310) --------------------------------- */
+/* A decoder pool hands out every frame as a surface of its own: its own device address, often a separate chroma allocation,
+ * a pitch per plane, cameras of different sizes side by side, 10-bit streams as P010.  The calls below take such surfaces
+ * where the decoder left them: the first launch of the step converts them into the handle-owned packed BGR frames and the
+ * step runs unchanged on those, so the result is DEFINED as the result of lp_run_batch_device / lp_run_views_device on the
+ * packed BGR frames the conversion gives, byte for byte; tracker, inventory and lp_set_view_merge work behind it unchanged.
+ *   - `surfaces` is a HOST array of B records; it is read before the call returns.
+ *   - The call is asynchronous on the handle's stream, like lp_run_batch_device: the caller keeps the surfaces' memory alive
+ *     and unwritten until the stream has passed the call.
+ *   - The handle's lp_set_input_format state is neither read nor changed.
+ *   - The surfaces' addresses and pitches are data of the step, not part of its identity: surfaces that rotate through a
+ *     pool replay one captured step, with no host synchronisation in the steady state.
+ *   - lp_run_surfaces_device takes surfaces of individual sizes and runs on rectangular handles (lp_config::det_input_h);
+ *     lp_run_views_surfaces_device needs every surface of one size and is LP_ERR_STATE on a rectangular handle, like its twin.
+ *   - LP_SURF_NV12: 8-bit samples; exactly the formula and constants of lp_frame_format above (BT.601 / BT.709 limited range,
+ *     20-bit fixed point).
+ *   - LP_SURF_P010: 16-bit little-endian samples with the value in the high bits.  Only the HIGH BYTE of each sample is
+ *     read: Y = s >> 8, likewise U and V, then the NV12 formula.  The low byte may hold anything, so P016 surfaces are taken
+ *     the same way.  This is truncation (10 bits dropped to 8 without dither); it is this project's contract.
+ *   - LP_ERR_ARG before anything is enqueued, the handle staying usable, for: a NULL fmt or surfaces; an unknown pixfmt or
+ *     matrix; a non-zero reserved word; B outside 1..max_batch; a NULL plane; an odd or non-positive height or width; a
+ *     negative pitch; a non-zero pitch below the row's bytes (W for NV12, 2 * W for P010, both planes); for P010 an odd plane
+ *     address or an odd pitch; unequal sizes in the views variant.  Any address and any pitch are otherwise allowed.
+ * DESIGN.md 6k. */
+enum lp_surface_pixfmt { LP_SURF_NV12 = 1, LP_SURF_P010 = 2 };
+typedef struct lp_surface {          /* 48 bytes; one decoded frame where the decoder left it */
+  const void* plane[2];  /* DEVICE addresses: [0] luma rows, [1] interleaved chroma rows, U first */
+  int pitch[2];          /* bytes per row of each plane; 0 = tight */
+  int height, width;     /* luma size in pixels, both even */
+  int reserved[4];       /* zero */
+} lp_surface;
+typedef struct lp_surface_format { int pixfmt; /* lp_surface_pixfmt */ int matrix; /* lp_csc */ int reserved[6]; /* zero */ } lp_surface_format;
+
+/* pure host, no handle, no device: every rule above that needs no handle (B >= 1) */
+int lp_surfaces_check(const lp_surface_format* fmt, const lp_surface* s, int B);
+/* the plain pipeline (what lp_run_batch_device does) on B surfaces of individual sizes */
+int lp_run_surfaces_device(lp_handle* h, const lp_surface_format* fmt, const lp_surface* surfaces, int B, float conf, float iou,
+                           int min_area, void* dev_dets, void* dev_counts);
+/* what lp_run_views_device does; every surface of one size */
+int lp_run_views_surfaces_device(lp_handle* h, const lp_surface_format* fmt, const lp_surface* surfaces, int B, const int* views,
+                                 int n_views, float conf, float iou, int min_area, void* dev_dets, void* dev_counts);
+/* the converter alone (tests) on device surfaces -> the packed BGR frames, downloaded one after another (H * W * 3 bytes
+ * each); its output sits between guard zones that are checked, as in lp_test_convert_frames.  Synchronous. */
+int lp_test_convert_surfaces(lp_handle* h, const lp_surface_format* fmt, const lp_surface* surfaces, int B, uint8_t* out_bgr);
+/* captured steps of the handle: entries in the cache, and since lp_create the calls that ran eagerly / were captured / were
+ * replayed; any pointer may be NULL */
+int lp_graph_stats(lp_handle* h, int* entries, int64_t* eager, int64_t* captures, int64_t* replays);
+
 /* ---- sign tracking across frames (additive to ABI 310) ------------------------------ */
 /* A tracker turns the per-frame lp_det records of a frame SEQUENCE into identities with a voted class.  It consumes the
  * records where lp_run_batch_device / lp_run_tiled_device left them, on the handle's stream, and keeps its track table in

@@ -120,6 +120,8 @@ enum GraphKind {
   GK_VIEWS_DEVICE,                                // lp_run_views_device
   GK_FOCUS_FRONT, GK_FOCUS_ROI, GK_FOCUS_CLS,     // lp_run_focus: view gather + detect + mask + frame NMS, ROI resize, classifier
   GK_FOCUS_DEVICE,                                // lp_run_focus_device
+  GK_SURFACES_DEVICE,                             // lp_run_surfaces_device
+  GK_VIEWS_SURFACES_DEVICE,                       // lp_run_views_surfaces_device
 };
 struct GraphKey {
   GraphKind kind;
@@ -135,6 +137,24 @@ struct GraphKey {
            uv_offset == o.uv_offset && frame_stride == o.frame_stride;
   }
 };
+// Decoder surfaces (lp_run_surfaces_device, lp_run_views_surfaces_device; surfaces.cpp): the converter of every captured step
+// reads ONE device table at a fixed address, so a surface's address and pitches are data and not part of a step's identity.
+// A call writes its records into the next slot of a pinned ring and copies them to the table on the handle's stream, in front
+// of the step: stream order keeps every call's table apart.  A pinned slot is re-used only after the event recorded behind
+// its copy (waited on when the ring wraps, never otherwise).
+struct SurfaceRing {
+  static constexpr int RING = 8;
+  DevBuf table;                  // [max_batch] SurfFrame
+  SurfFrame* host = nullptr;     // pinned, RING slots of max_batch records
+  hipEvent_t ev[RING] = {};
+  SurfaceSlots<RING> slots;      // which slot is next and whether its event has to be waited for (surface_plan.h)
+  ~SurfaceRing() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (host) (void)hipHostFree(host);
+  }
+};
+
 struct GraphEntry { GraphKey key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; bool failed = false; unsigned long stamp = 0; };
 
 }  // namespace lp
@@ -185,7 +205,9 @@ struct lp_handle {
       ++geom_ver;
     }
   }
+  std::unique_ptr<lp::SurfaceRing> surf;   // null until the first surfaces call: no other path looks at it
   std::vector<lp::GraphEntry> graphs;   // captured steps (run_or_capture)
+  int64_t n_eager = 0, n_captures = 0, n_replays = 0;   // lp_graph_stats: calls of run_or_capture by what they did
   int geom_ver = 0;
   unsigned long graph_clock = 0;
   void drop_graphs() {

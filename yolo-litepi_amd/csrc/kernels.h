@@ -2,6 +2,7 @@
 // cls_kernels.hip).  All launches are asynchronous on the given stream.
 #pragma once
 #include "common.h"
+#include "surface_plan.h"
 
 namespace lp {
 
@@ -167,6 +168,9 @@ struct CscFrame {      // one frame of a conversion call, device resident
 struct CscCoef { int cy, cvr, cug, cvg, cub; };   // 20-bit fixed point (include/litepi.h lp_csc)
 // B frames in one launch; max_blocks = the largest (h / 2) * ceil(w / 16) of the table (2-row x 16-pixel blocks of a frame)
 void launch_nv12_to_bgr(const uint8_t* src, const CscFrame* frames, uint8_t* dst, int B, int max_blocks, int matrix, hipStream_t st);
+// the per-frame record of a surfaces call: SurfFrame (surface_plan.h)
+// B surfaces in one launch; max_blocks as above; p010: 16-bit samples whose high byte is taken, else NV12
+void launch_surfaces_to_bgr(const SurfFrame* frames, uint8_t* dst, int B, int max_blocks, bool p010, int matrix, hipStream_t st);
 
 // ---- track_kernels.hip (sign tracking across frames, include/litepi.h lp_track_*) --------------
 typedef struct lp_track TrackRec;   // (the plain name is the entry point)

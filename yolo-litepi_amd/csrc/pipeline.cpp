@@ -125,7 +125,7 @@ void enqueue_classify(lp_handle* h, const uint8_t* src, int B, lp_det* dets, flo
 // second time, replay the graph from then on.
 void run_or_capture(lp_handle* h, const GraphKey& key, bool allow, const std::function<void()>& enqueue) {
   static const bool disabled = getenv("LITEPI_NO_GRAPH") != nullptr;
-  if (disabled || !allow) { enqueue(); return; }
+  if (disabled || !allow) { ++h->n_eager; enqueue(); return; }
   GraphEntry* e = nullptr;
   for (auto& g : h->graphs)
     if (g.key == key) { e = &g; break; }
@@ -142,13 +142,15 @@ void run_or_capture(lp_handle* h, const GraphKey& key, bool allow, const std::fu
     ne.key = key;
     ne.stamp = ++h->graph_clock;
     h->graphs.push_back(ne);
+    ++h->n_eager;
     enqueue();
     return;
   }
   e->stamp = ++h->graph_clock;
-  if (e->failed) { enqueue(); return; }
+  if (e->failed) { ++h->n_eager; enqueue(); return; }
+  const bool replay = e->exec != nullptr;
   if (!e->exec) {
-    if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { e->failed = true; enqueue(); return; }
+    if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { e->failed = true; ++h->n_eager; enqueue(); return; }
     bool ok = true;
     std::string err;
     try { enqueue(); } catch (const lp::Error& ex) { ok = false; err = ex.what(); }
@@ -160,12 +162,14 @@ void run_or_capture(lp_handle* h, const GraphKey& key, bool allow, const std::fu
       (void)hipGetLastError();
       e->failed = true;
       LP_CHECK(err.empty(), LP_ERR_STATE, "%s", err.c_str());
+      ++h->n_eager;
       enqueue();
       return;
     }
     e->graph = graph;
   }
   LP_HIP(hipGraphLaunch(e->exec, h->stream));
+  ++(replay ? h->n_replays : h->n_captures);   // lp_graph_stats: the call that captured a step also launched it once
 }
 
 // upload B host images of individual sizes into d_src (NV12 frames: into d_raw, with the plan of their conversion into d_src

@@ -56,6 +56,17 @@ class LpFrameFormat(C.Structure):
                 ("frame_stride", C.c_int64), ("reserved", C.c_int * 6)]
 
 
+LP_SURF_NV12, LP_SURF_P010 = 1, 2
+
+
+class LpSurface(C.Structure):
+    _fields_ = [("plane", C.c_void_p * 2), ("pitch", C.c_int * 2), ("height", C.c_int), ("width", C.c_int), ("reserved", C.c_int * 4)]
+
+
+class LpSurfaceFormat(C.Structure):
+    _fields_ = [("pixfmt", C.c_int), ("matrix", C.c_int), ("reserved", C.c_int * 6)]
+
+
 class LpTrackConfig(C.Structure):
     _fields_ = [("n_streams", C.c_int), ("max_tracks", C.c_int), ("iou_match", C.c_float), ("max_age", C.c_int),
                 ("min_hits", C.c_int), ("new_conf", C.c_float), ("vote_decay", C.c_float), ("class_gate", C.c_int),
@@ -127,6 +138,7 @@ SYMBOLS = [
     "lp_letterbox_geometry", "lp_test_letterbox_kernel", "lp_test_roi_resize_rects",
     "lp_load_detector_onnx", "lp_load_detector_onnx_memory", "lp_detector_graph_describe",
     "lp_view_merge_default", "lp_view_merge_check", "lp_set_view_merge",
+    "lp_surfaces_check", "lp_run_surfaces_device", "lp_run_views_surfaces_device", "lp_test_convert_surfaces", "lp_graph_stats",
 ]
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
 
@@ -237,6 +249,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_view_merge_default.restype = None
     lib.lp_view_merge_check.argtypes = [vmp]
     lib.lp_set_view_merge.argtypes = [vp, vmp]
+    sfp, sp = C.POINTER(LpSurfaceFormat), C.POINTER(LpSurface)
+    lib.lp_surfaces_check.argtypes = [sfp, sp, C.c_int]
+    lib.lp_run_surfaces_device.argtypes = [vp, sfp, sp, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp]
+    lib.lp_run_views_surfaces_device.argtypes = [vp, sfp, sp, C.c_int, ip, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp]
+    lib.lp_test_convert_surfaces.argtypes = [vp, sfp, sp, C.c_int, vp]
+    lib.lp_graph_stats.argtypes = [vp, ip, i64p, i64p, i64p]
     for s in SYMBOLS:
         if s not in ("lp_last_error", "lp_default_config", "lp_destroy", "lp_track_default_config", "lp_inventory_default_config",
                      "lp_focus_default_config", "lp_view_merge_default"):

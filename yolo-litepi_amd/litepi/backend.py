@@ -20,6 +20,7 @@ from . import _ffi
 from ._ffi import (DET_DTYPE, SIGN_DTYPE, TRACK_DTYPE, TRACK_STATE_DTYPE, LpConfig, LpFrameFormat, LpInventoryConfig, LpKernelTime, LpTiming,
                    LpTiling, LpTrackConfig, check)
 from .pixfmt import CSC_MATRICES, PIXEL_FORMATS, nv12_frame_hw
+from .surfaces import Surface, surface_array, surface_format, surface_from_tensors, surfaces_check  # noqa: F401  (re-exported)
 
 _PREC = {"fp32": _ffi.LP_FP32, "fp16": _ffi.LP_FP16, "float32": _ffi.LP_FP32, "float16": _ffi.LP_FP16, "half": _ffi.LP_FP16}
 
@@ -449,6 +450,28 @@ class Engine:
         check(self.lib, self.lib.lp_run_views_device(self._h, C.c_void_p(dev_imgs), B, H, W, _ip(v), len(v), conf, iou, int(min_area),
                                                      C.c_void_p(dev_dets), C.c_void_p(dev_counts)))
 
+    # ---- decoder surfaces in place -------------------------------------------------------------
+    def run_surfaces_device(self, surfaces: Sequence[Surface], conf: float, iou: float, min_area: int, dev_dets: int, dev_counts: int,
+                            pixfmt: str = "nv12", matrix: str = "bt601") -> None:
+        """run_batch_device on decoder surfaces of individual sizes, converted on the device where they lie
+        (lp_run_surfaces_device).  Asynchronous: keep the surfaces alive and unwritten until the stream has passed the call."""
+        f, arr = surface_format(pixfmt, matrix), surface_array(surfaces)
+        check(self.lib, self.lib.lp_run_surfaces_device(self._h, C.byref(f), arr, len(arr), conf, iou, int(min_area),
+                                                        C.c_void_p(dev_dets), C.c_void_p(dev_counts)))
+
+    def run_views_surfaces_device(self, surfaces: Sequence[Surface], views, conf: float, iou: float, min_area: int, dev_dets: int,
+                                  dev_counts: int, pixfmt: str = "nv12", matrix: str = "bt601") -> None:
+        """run_views_device on decoder surfaces of one size (lp_run_views_surfaces_device)."""
+        f, arr, v = surface_format(pixfmt, matrix), surface_array(surfaces), _view_array(views)
+        check(self.lib, self.lib.lp_run_views_surfaces_device(self._h, C.byref(f), arr, len(arr), _ip(v), len(v), conf, iou, int(min_area),
+                                                              C.c_void_p(dev_dets), C.c_void_p(dev_counts)))
+
+    def graph_stats(self) -> Dict[str, int]:
+        """Captured steps of the engine (lp_graph_stats): entries in the cache, and the calls run eagerly / captured / replayed."""
+        n, e, c, r = C.c_int(), C.c_int64(), C.c_int64(), C.c_int64()
+        check(self.lib, self.lib.lp_graph_stats(self._h, C.byref(n), C.byref(e), C.byref(c), C.byref(r)))
+        return {"entries": n.value, "eager": e.value, "captures": c.value, "replays": r.value}
+
     # ---- sign tracking across frames ----------------------------------------------------------
     def tracker_create(self, **cfg) -> None:
         """One tracker per engine (lp_tracker_create); calling it again replaces the tracker and restarts the ids.  Settings are
@@ -789,6 +812,17 @@ class Engine:
         check(self.lib, self.lib.lp_test_convert_frames(self._h, a.ctypes.data, int(B), int(H), int(W), C.byref(f), int(byte_offset),
                                                         out.ctypes.data))
         return out
+
+    def test_convert_surfaces(self, surfaces: Sequence[Surface], pixfmt: str = "nv12", matrix: str = "bt601") -> List[np.ndarray]:
+        """The surface converter alone (lp_test_convert_surfaces): device surfaces -> one uint8 BGR [H, W, 3] array each."""
+        surfaces = list(surfaces)
+        f, arr = surface_format(pixfmt, matrix), surface_array(surfaces)
+        surfaces_check(surfaces, pixfmt, matrix)   # the sizes below are the output's: nothing unchecked sizes a buffer
+        nb = [s.height * s.width * 3 for s in surfaces]
+        out = np.empty(sum(nb), np.uint8)
+        check(self.lib, self.lib.lp_test_convert_surfaces(self._h, C.byref(f), arr, len(arr), out.ctypes.data))
+        offs = np.concatenate([[0], np.cumsum(nb)])
+        return [out[offs[i]:offs[i + 1]].reshape(s.height, s.width, 3) for i, s in enumerate(surfaces)]
 
     def test_roi_resize(self, rois: Sequence[np.ndarray]) -> np.ndarray:
         imgs, ptrs, hs, ws = self._img_args(rois)
