@@ -579,6 +579,77 @@ int lp_inventory_open(lp_handle* h, int stream, lp_sign* out, int cap, int* n);
 int lp_test_set_rois(lp_handle* h, const uint8_t* crops, const int* img, const int* slot, int R);
 int lp_debug_rois(lp_handle* h, uint8_t* crops, int* img, int* slot, int cap, int* n);
 
+/* ---- evidence store: a context picture of each sign's best sighting (additive to ABI 310) ---- */
+/* The crop of an lp_sign is the classifier's input: the box alone, squashed to a square, RGB.  The evidence store adds what a
+ * person reviewing the list needs: per open entry an E x E BGR picture of the best sighting's SURROUNDINGS, cut from the
+ * native frame on the device, carried into the log when the entry closes and drained with the sign.  It belongs to the
+ * inventory as the inventory belongs to the tracker: lp_inventory_create called again, lp_inventory_destroy,
+ * lp_tracker_create called again and lp_tracker_destroy destroy it.  Without a store nothing changes: no existing path gains
+ * a launch, a device branch or a buffer.
+ * The rule extends step 4 of the inventory's rule and changes nothing else.  When a sighting becomes an entry's best (the
+ * first sighting, or q > best_quality), box, best_frame and crop are replaced as above, and with a store:
+ *   crops = 0 for the call: LP_SIGN_HAS_EVIDENCE is cleared for that sighting (its window is zeros)
+ *   crops = 1: with the frame of that record H x W and its box {x1, y1, x2, y2}, all fp32, every operation rounded on its
+ *     own, nothing contracted, fmaxf / fminf returning the non-NaN operand:
+ *       bw = x2 - x1;  bh = y2 - y1
+ *       has  = H >= 16 && W >= 16 && bw > 0 && bh > 0            (false for a NaN)
+ *       side = (int)fminf(fmaxf(ceilf(scale * fmaxf(bw, bh)), 16.f), 16384.f)
+ *       w = min(side, W);  h = min(side, H)
+ *       cx = (int)fminf(fmaxf(floorf((x1 + x2) * 0.5f), 0.f), (float)W);   cy likewise with y and H
+ *       x = min(max(cx - w / 2, 0), W - w);   y likewise
+ *     LP_SIGN_HAS_EVIDENCE is set iff has (else the window is zeros), and the entry's picture becomes the scaled view of
+ *     window {x, y, w, h} of that frame for a detector input of E: the geometry of lp_view_geometry(E, H, W, win, ...), the
+ *     bytes of the window gather of lp_run_views (tests/views_ref.make_view(frame, E, win)[0]), 114 in the bars.
+ *   This is the focus plan's `place` step with side_min = 16, a fixed side_max and margin = scale.  No ROI crop is needed: a
+ *   record that min_area or max_rois left unclassified still gets a picture.  The resampling is plain bilinear like every
+ *   view: a window many times E is aliased; an antialiased resample is out of scope.
+ * "The frame" of record (b, i) is frame b of the last pipeline call on the handle: the call's BGR frames for lp_run_batch*,
+ * the native frame (never a view) for the tiled, views and focus families, the converted BGR frame the handle holds for
+ * NV12 and surface calls.  For the *_device entry points with BGR frames the pictures are cut from the CALLER'S buffer: it
+ * must stay alive and unwritten until the stream has passed the lp_inventory* call.
+ * An entry that closes is logged with its picture and window; lp_inventory_flush does the same.
+ * How it runs: with a store the inventory's launch only decides and appends what is to be moved to one compact list; a
+ * second plain launch behind it moves the pixels: 256 workers x E / 8 bands of 8 picture rows, each worker walking the list
+ * with the workers' stride (an empty list costs the launch alone) -- first gallery -> log for entries that closed with a best from an earlier call,
+ * then frame -> gallery for open entries whose final best lies in this call and frame -> log for entries that took a best
+ * and closed within the call.  A best replaced again within the call is never rendered.  No host synchronisation; any
+ * number of calls may be in flight.  tests/evidence_ref.py restates the rule in NumPy.  DESIGN.md 6l. */
+typedef struct lp_evidence_config {   /* 32 bytes */
+  int size;          /* E: side of the picture, a multiple of 16, 32..256 (default 128) */
+  float scale;       /* 1 <= scale <= 16: the window's side is scale x the box's longer side (default 2) */
+  int reserved[6];   /* zero */
+} lp_evidence_config;
+#define LP_SIGN_HAS_EVIDENCE 4
+
+void lp_evidence_default_config(lp_evidence_config* cfg);
+/* pure host: LP_ERR_ARG for a value out of range, a NaN scale, a non-zero reserved word or NULL */
+int lp_evidence_config_check(const lp_evidence_config* cfg);
+/* pure host: the rule's window of `box` {x1, y1, x2, y2} on an H x W frame into win {x, y, w, h} (zeros without a picture)
+ * and *has; the same header function the kernel runs (csrc/evidence_window.h).  LP_ERR_ARG for a bad configuration, NULL,
+ * or H, W < 1 */
+int lp_evidence_window(const lp_evidence_config* cfg, int H, int W, const float* box, int* win, int* has);
+/* LP_ERR_STATE without an inventory, LP_ERR_ARG when the inventory has keep_crops = 0; calling it again replaces the store
+ * (open entries keep their records and lose their pictures: their flag is cleared).  Memory: a gallery of
+ * n_streams x max_tracks x 3 E^2 bytes and a log of max_signs x (3 E^2 + 16) bytes, plus 48 bytes per (stream, track) and
+ * 32 per (max_batch x max_det) record of work tables.  At the defaults (E = 128: 48 KB a picture; 1 stream x 64 tracks,
+ * max_signs 4096) 3 MB + 192 MB; at E = 64, 0.75 MB + 48 MB; at the limits (E = 256, 192 KB a picture) a log of
+ * max_signs = 1 << 20 would be 192 GB: size max_signs to the drain interval. */
+int lp_evidence_create(lp_handle* h, const lp_evidence_config* cfg);
+int lp_evidence_destroy(lp_handle* h);
+/* lp_inventory_drain, and additionally evidence [*n, E, E, 3] uint8 BGR (the frames' byte order) and windows [*n, 4]
+ * {x, y, w, h}; both zeros for a sign without LP_SIGN_HAS_EVIDENCE; either may be NULL.  LP_ERR_STATE without a store.
+ * lp_inventory_drain keeps working on a handle with a store: it drains the signs and discards their pictures. */
+int lp_inventory_drain_evidence(lp_handle* h, lp_sign* out, uint8_t* crops, uint8_t* evidence, int* windows, int cap, int* n,
+                                int* dropped);
+/* synchronises; the pictures [*n, E, E, 3] and windows [*n, 4] of a stream's open entries in slot order, parallel to
+ * lp_inventory_open (either may be NULL; cap < *n is LP_ERR_ARG when any is given) */
+int lp_evidence_open(lp_handle* h, int stream, uint8_t* evidence, int* windows, int cap, int* n);
+/* test hook: put B host BGR frames [B, H, W, 3] of one size into the handle, with their frame geometry, as lp_run_batch
+ * would leave them: lp_inventory(..., crops = 1) behind lp_test_set_rois then runs without a model.  With a store,
+ * lp_inventory*(crops = 1) is LP_ERR_STATE while the handle remembers fewer than B frames; a call that reuses the handle's
+ * frame buffers without being a pipeline call (lp_detect, lp_detect_raw, lp_classify) makes it forget them. */
+int lp_test_set_frames(lp_handle* h, const uint8_t* frames, int B, int H, int W);
+
 /* ---- focus views: tracker-chosen windows and a sweep in the detector batch (additive to ABI 310) ---- */
 /* A focus plan connects the tracker to the scaled views: per frame the whole-frame view plus `slots` windows, chosen ON THE
  * DEVICE from the tracker's state as the last enqueued lp_track_device left it -- native-resolution windows where the small

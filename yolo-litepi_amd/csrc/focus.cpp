@@ -239,6 +239,7 @@ int lp_run_focus_device(lp_handle* h, const void* dev_imgs, int B, int H, int W,
   enqueue_focus_plan(h, B, nullptr, nullptr, H, W, stream_ids, static_cast<int*>(dev_views), true, 1, prof);
   const uint8_t* src = nv ? h->d_src.as<uint8_t>() : static_cast<const uint8_t*>(dev_imgs);
   const bool classify = h->cls && h->cls->loaded();
+  h->remember_frames(src, h->d_fgeom.as<ImgGeom>(), B);
   GraphKey key{GK_FOCUS_DEVICE, B, h->geom_ver, min_area, dev_imgs, dev_dets, dev_counts, conf, iou};
   key_format(h, csc, key);
   run_or_capture(h, key, prof == nullptr, [&]() {

@@ -42,8 +42,18 @@ inline int plan_stream_jobs(int* slot, int max_batch, int B, const int* stream_i
 // Sign inventory of a tracker (lp_inventory_*; include/litepi.h): entries, frame counters, the gallery of best crops and the
 // log of finished signs stay in HBM between calls.  Its call plans go through a pinned -> device ring of its own, built like
 // the tracker's: the tracker's ring keeps its re-use timing.
+// Evidence store of an inventory (lp_evidence_*; include/litepi.h): per entry the E x E BGR picture of its best sighting's
+// surroundings and that picture's window; the same per logged sign; and the job list the deciding kernel leaves for the
+// picture launch (kernels.h, EvJob).
+struct Evidence {
+  lp_evidence_config cfg;
+  size_t pic_bytes = 0;
+  DevBuf gallery, log_pics, win, log_win, jobs, n_jobs;
+};
+
 struct Inventory {
   static constexpr int RING = 8;
+  std::unique_ptr<Evidence> evid;   // null until lp_evidence_create: no other path looks at it
   lp_inventory_config cfg;
   int min_hits = 0, crop_bytes = 0;
   DevBuf entries, frame_no, head, log, log_crops, gallery, roi_of, plan_dev;
@@ -188,6 +198,16 @@ struct lp_handle {
   lp_view_merge vmerge = {};   // lp_set_view_merge: how the frame NMS merges a frame's views (zeros: the reference's rule)
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // staged host pass: start, after the ROI resize, after the front, end
   int last_roi_count = 0;
+  // where the last pipeline call's BGR frames and their geometry are (host bookkeeping; the evidence store reads them behind
+  // lp_inventory*(crops = 1)).  Whatever rewrites or reallocates d_src or d_geom (ensure_src, upload_geom: every entry point
+  // that does so, lp_detect* and lp_classify included) forgets them first; the pipeline entry points remember their own
+  // frames afterwards, so a store never reads a table or a buffer that a later call of another kind has replaced
+  // (lp_inventory*(crops = 1) is then LP_ERR_STATE).  d_tframes / d_tgeom: the frames of lp_test_set_frames, allocated on first use
+  const uint8_t* last_frames = nullptr;
+  const lp::ImgGeom* last_fgeom = nullptr;
+  int last_nframes = 0;
+  lp::DevBuf d_tframes, d_tgeom;
+  void remember_frames(const uint8_t* src, const lp::ImgGeom* geom, int B) { last_frames = src; last_fgeom = geom; last_nframes = B; }
   // ---- input pixel format (lp_set_input_format).  NV12 frames are converted into d_src, which then holds exactly the packed
   //      BGR frames a BGR call would have put there; host NV12 frames are uploaded into d_raw first.  The converter reads its
   //      per-frame geometry from one of four table slots in d_csc: a slot's content never changes while a captured step may
@@ -225,6 +245,7 @@ struct lp_handle {
     return t;
   }
   void ensure_src(size_t bytes) {
+    remember_frames(nullptr, nullptr, 0);   // d_src is about to be rewritten
     if (d_src.bytes < bytes) {
       d_src.alloc(bytes + bytes / 4, false);
       ++geom_ver;  // captured steps hold the old address
@@ -241,6 +262,7 @@ struct lp_handle {
     d_out0.alloc((size_t)B * (4 + nc) * A * 4, false);
   }
   void upload_geom(const std::vector<lp::ImgGeom>& g) {
+    remember_frames(nullptr, nullptr, 0);   // d_geom now describes this call's images
     bool same = g.size() == geom_cache.size() && (g.empty() || memcmp(g.data(), geom_cache.data(), g.size() * sizeof(lp::ImgGeom)) == 0);
     if (same) return;
     LP_HIP(hipMemcpyAsync(d_geom.p, g.data(), g.size() * sizeof(lp::ImgGeom), hipMemcpyHostToDevice, stream));

@@ -9,6 +9,7 @@
 #include <climits>
 
 #include "common.h"
+#include "evidence_window.h"
 #include "kernels.h"
 
 namespace lp {
@@ -16,6 +17,7 @@ namespace lp {
 #define INV_LANES 64
 #define INV_MAXT 256                  // lp_track_config::max_tracks <= 256
 #define INV_CHUNKS (INV_MAXT / INV_LANES)
+#define EV_WORKERS 256                // list workers of the picture launch (x E / 8 bands)
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
@@ -31,8 +33,17 @@ __device__ __forceinline__ void copy_crop(uint8_t* dst, const uint8_t* src, int 
   for (int q = lane; q < bytes / 16; q += INV_LANES) d[q] = s[q];
 }
 
+// the evidence store's per-slot scalars in LDS (EV only): the window of the entry's best, the batch index of the frame that
+// holds a best taken in this call (-1: the picture is in the gallery, or there is none), the log position the slot's
+// gallery picture goes to (-1: none)
+enum { EV_X, EV_Y, EV_W, EV_H, EV_B, EV_COPY, EV_N };
+
 // frames == nullptr: flush the stream (every open entry closes, LP_SIGN_FLUSHED; the frame counter stays)
-__device__ __forceinline__ void inventory_stream(const InvArgs& a, int stream, const int* frames, int nframes) {
+// EV: the deciding variant of a handle with an evidence store (kernels.h, EvArgs).
+// With EV = false nothing of `e` is read and the code is the kernel's of before.
+template <bool EV>
+__device__ __forceinline__ void inventory_stream(const InvArgs& a, const EvArgs& e, int stream, const int* frames, int nframes) {
+  __shared__ int s_ev[EV_N][EV ? INV_MAXT : 1];
   __shared__ int s_w[W_N][INV_MAXT];   // the entries' signs, structure of arrays
   __shared__ int s_open[INV_MAXT], s_missed[INV_MAXT];
   __shared__ int s_sight[INV_MAXT];    // per frame: the lowest record index that names the slot, INT_MAX = not sighted
@@ -50,6 +61,11 @@ __device__ __forceinline__ void inventory_stream(const InvArgs& a, int stream, c
 #pragma unroll
     for (int k = 0; k < 4; ++k) { s_w[4 * k][s] = q[k].x; s_w[4 * k + 1][s] = q[k].y; s_w[4 * k + 2][s] = q[k].z; s_w[4 * k + 3][s] = q[k].w; }
     s_open[s] = q[4].x; s_missed[s] = q[4].y;
+    if constexpr (EV) {
+      const i32x4 w = *reinterpret_cast<const i32x4*>(e.win + ((size_t)stream * T + s) * 4);
+      s_ev[EV_X][s] = w.x; s_ev[EV_Y][s] = w.y; s_ev[EV_W][s] = w.z; s_ev[EV_H][s] = w.w;
+      s_ev[EV_B][s] = -1; s_ev[EV_COPY][s] = -1;
+    }
   }
   const int t0 = a.frame_no[stream];
   int roi_total = 0;
@@ -117,6 +133,19 @@ __device__ __forceinline__ void inventory_stream(const InvArgs& a, int stream, c
 #pragma unroll
             for (int k = 0; k < 4; ++k)
               o[k] = i32x4{s_w[4 * k][s], s_w[4 * k + 1][s], s_w[4 * k + 2][s], s_w[4 * k + 3][s] | (k == 3 && flush ? LP_SIGN_FLUSHED : 0)};
+            if constexpr (EV) {   // the window goes with the sign; the pixels are the picture launch's
+              const bool pic = (s_w[W_FLAGS][s] & LP_SIGN_HAS_EVIDENCE) != 0;
+              const i32x4 w = pic ? i32x4{s_ev[EV_X][s], s_ev[EV_Y][s], s_ev[EV_W][s], s_ev[EV_H][s]} : i32x4{0, 0, 0, 0};
+              *reinterpret_cast<i32x4*>(e.log_win + (size_t)pos * 4) = w;
+              if (pic && s_ev[EV_B][s] >= 0) {   // the best lies in this call: frame -> log
+                const int k = atomicAdd(e.n_jobs, 1);
+                if (k >= 0 && k < e.cap_jobs) {
+                  i32x4* j = reinterpret_cast<i32x4*>(e.jobs + k);
+                  j[0] = i32x4{-1, s_ev[EV_B][s], w.x, w.y};
+                  j[1] = i32x4{w.z, w.w, -1, pos};
+                }
+              } else if (pic) s_ev[EV_COPY][s] = pos;   // gallery -> log
+            }
           }
         }
         if (gal && a.log_crops) {
@@ -160,6 +189,17 @@ __device__ __forceinline__ void inventory_stream(const InvArgs& a, int stream, c
             if (r >= 0 && r < roi_total && a.roi_img[r] == b && a.roi_slot[r] == idx) roi = r;
           }
           s_w[W_FLAGS][s] = roi >= 0 ? LP_SIGN_HAS_CROP : 0;
+          if constexpr (EV) {
+            EvWindow wn = {0, 0, 0, 0};
+            bool pic = false;
+            if (e.frames) {
+              const ImgGeom* g = e.fgeom + b;
+              pic = evidence_window(e.scale, g->h, g->w, __int_as_float(d0.x), __int_as_float(d0.y), __int_as_float(d0.z), __int_as_float(d0.w), &wn);
+            }
+            s_ev[EV_X][s] = wn.x; s_ev[EV_Y][s] = wn.y; s_ev[EV_W][s] = wn.w; s_ev[EV_H][s] = wn.h;
+            s_ev[EV_B][s] = pic ? b : -1;
+            if (pic) s_w[W_FLAGS][s] |= LP_SIGN_HAS_EVIDENCE;
+          }
         }
       }
       s_roi[s] = roi;
@@ -183,17 +223,40 @@ __device__ __forceinline__ void inventory_stream(const InvArgs& a, int stream, c
 #pragma unroll
     for (int k = 0; k < 4; ++k) p[k] = i32x4{s_w[4 * k][s], s_w[4 * k + 1][s], s_w[4 * k + 2][s], s_w[4 * k + 3][s]};
     p[4] = i32x4{s_open[s], s_missed[s], 0, 0};
+    if constexpr (EV) {
+      const i32x4 w = i32x4{s_ev[EV_X][s], s_ev[EV_Y][s], s_ev[EV_W][s], s_ev[EV_H][s]};
+      *reinterpret_cast<i32x4*>(e.win + ((size_t)stream * T + s) * 4) = w;
+      const int b = s_open[s] ? s_ev[EV_B][s] : -1;
+      if (s_ev[EV_COPY][s] >= 0 || b >= 0) {
+        const int k = atomicAdd(e.n_jobs, 1);
+        if (k >= 0 && k < e.cap_jobs) {
+          i32x4* j = reinterpret_cast<i32x4*>(e.jobs + k);
+          j[0] = i32x4{s_ev[EV_COPY][s], b, w.x, w.y};
+          j[1] = i32x4{w.z, w.w, stream * T + s, -1};
+        }
+      }
+    }
   }
   if (!flush && lane == 0) a.frame_no[stream] = t0 + nframes;
 }
 
 __global__ __launch_bounds__(INV_LANES) void inventory_kernel(const InvArgs a) {
   const TrackJob job = a.jobs[blockIdx.x];
-  inventory_stream(a, job.stream, a.frames + job.first, job.nframes);
+  inventory_stream<false>(a, EvArgs{}, job.stream, a.frames + job.first, job.nframes);
 }
 
 __global__ __launch_bounds__(INV_LANES) void inventory_flush_kernel(const InvArgs a, int first) {
-  inventory_stream(a, first + blockIdx.x, nullptr, 0);
+  inventory_stream<false>(a, EvArgs{}, first + blockIdx.x, nullptr, 0);
+}
+
+// the deciding variants of a handle with an evidence store
+__global__ __launch_bounds__(INV_LANES) void inventory_evidence_kernel(const InvArgs a, const EvArgs e) {
+  const TrackJob job = a.jobs[blockIdx.x];
+  inventory_stream<true>(a, e, job.stream, a.frames + job.first, job.nframes);
+}
+
+__global__ __launch_bounds__(INV_LANES) void inventory_flush_evidence_kernel(const InvArgs a, const EvArgs e, int first) {
+  inventory_stream<true>(a, e, first + blockIdx.x, nullptr, 0);
 }
 
 // record -> ROI index of the call's ROI list; entries of earlier calls stay and are recognised as stale by the reader
@@ -226,6 +289,27 @@ void launch_inventory_flush(const InvArgs& a, int first, int n, hipStream_t st) 
   check_inventory_args(a);
   LP_LAUNCH(inventory_flush_kernel, dim3(n), dim3(INV_LANES), 0, st, a, first);
   LP_HIP(hipGetLastError());
+}
+
+void launch_inventory_evidence(const InvArgs& a, const EvArgs& e, int n_jobs, hipStream_t st) {
+  if (n_jobs <= 0) return;
+  check_inventory_args(a);
+  if (a.roi_rgb) {
+    LP_LAUNCH(inventory_roi_scatter_kernel, dim3(ceil_div(std::max(a.max_rois, 1), 256)), dim3(256), 0, st, a);
+  }
+  LP_HIP(hipMemsetAsync(e.n_jobs, 0, sizeof(int), st));
+  LP_LAUNCH(inventory_evidence_kernel, dim3(n_jobs), dim3(INV_LANES), 0, st, a, e);
+  LP_HIP(hipGetLastError());
+  launch_evidence_pictures(e, std::min(e.cap_jobs, EV_WORKERS), st);
+}
+
+void launch_inventory_flush_evidence(const InvArgs& a, const EvArgs& e, int first, int n, hipStream_t st) {
+  if (n <= 0) return;
+  check_inventory_args(a);
+  LP_HIP(hipMemsetAsync(e.n_jobs, 0, sizeof(int), st));
+  LP_LAUNCH(inventory_flush_evidence_kernel, dim3(n), dim3(INV_LANES), 0, st, a, e, first);
+  LP_HIP(hipGetLastError());
+  launch_evidence_pictures(e, std::min(n * a.T, EV_WORKERS), st);   // a flush only copies: the pictures are all in the gallery
 }
 
 }  // namespace lp

@@ -235,6 +235,36 @@ void launch_inventory(const InvArgs& a, int n_jobs, hipStream_t st);
 // closes every open entry of `n` streams from `first` on into the log (LP_SIGN_FLUSHED); jobs / frames / records are not read
 void launch_inventory_flush(const InvArgs& a, int first, int n, hipStream_t st);
 
+// ---- evidence_kernels.hip (a context picture of each sign's best sighting, include/litepi.h lp_evidence_*) ----
+// Decide, then copy: the deciding variant of the inventory's kernel moves no pixel; it appends the work of the picture launch
+// behind it to one compact list (one atomic per record).  A record can ask for two things, in this order: copy the gallery
+// picture `gal` to log position copy_pos (an entry that closed with a best from an earlier call), and render window
+// {x, y, w, h} of frame b into gallery picture `gal` (an entry still open whose final best lies in this call) or, with
+// log_pos >= 0, into the log (an entry that took a best and closed within the call).  A best that was replaced again
+// appears nowhere.  At most one record per (stream, slot) and one per record of the call.
+struct EvJob { int copy_pos, b, x, y, w, h, gal, log_pos; };   // copy_pos / b / log_pos: -1 = not asked for; gal = stream * T + slot
+struct EvArgs {
+  const uint8_t* frames;    // the last pipeline call's BGR frames; null: crops = 0, no sighting of this call gets a picture
+  const ImgGeom* fgeom;     // [B] their geometry (src_off, h, w); rows are 3 * w bytes apart
+  int* win;                 // [n_streams][T][4] window of every entry's best (zeros without LP_SIGN_HAS_EVIDENCE)
+  int* log_win;             // [max_signs][4]
+  uint8_t* gallery;         // [n_streams][T][3 E^2]
+  uint8_t* log_pics;        // [max_signs][3 E^2]
+  EvJob* jobs;              // [cap_jobs]
+  int* n_jobs;              // records offered to `jobs` in this call (zeroed in front of the deciding launch)
+  int cap_jobs;             // n_streams * T + max_batch * max_det
+  int E;
+  float scale;
+};
+// the picture launch: `workers` x E / 8 workgroups; a worker walks the list with the workers' stride, one band of 8 picture
+// rows per workgroup, and leaves at once when the list is empty.  A record's copy comes before its render, in the same
+// workgroup over the same bytes: a slot closed and reused within one call ends with the old entry's picture in the log and
+// the new entry's in the gallery.
+void launch_evidence_pictures(const EvArgs& e, int workers, hipStream_t st);
+// launch_inventory / launch_inventory_flush with the deciding kernel, then the picture launch
+void launch_inventory_evidence(const InvArgs& a, const EvArgs& e, int n_jobs, hipStream_t st);
+void launch_inventory_flush_evidence(const InvArgs& a, const EvArgs& e, int first, int n, hipStream_t st);
+
 // ---- focus_kernels.hip (tracker-chosen windows + sweep, include/litepi.h lp_focus_*) ----------
 struct FocusState { int cursor, unserved; };   // per stream, device resident between calls
 struct FocusArgs {

@@ -250,6 +250,7 @@ void run_host_pass(lp_handle* h, int B, float conf, float iou, int min_area, lp_
   Profiler* prof = begin_profile(h);
   const uint8_t* src = h->d_src.as<uint8_t>();
   lp_det* d_dets = h->d_dets.as<lp_det>();
+  h->remember_frames(src, roi_geom ? roi_geom : h->d_geom.as<ImgGeom>(), B);
   // three captured pieces with the stage-boundary events between them (PipelineMetrics wants detection, ROI extraction and
   // classification times separately, e2e.py:452-499); the colour conversion of NV12 frames is booked under detection
   GraphKey k1{front_kind, B, h->geom_ver, min_area, h->d_src.p, h->d_dets.p, h->d_counts.p, conf, iou}, k2 = k1, k3 = k1;
@@ -392,6 +393,7 @@ int lp_run_batch_device(lp_handle* h, const void* dev_imgs, int B, int H, int W,
   Profiler* prof = begin_profile(h);
   const uint8_t* src = nv ? h->d_src.as<uint8_t>() : static_cast<const uint8_t*>(dev_imgs);
   const bool classify = h->cls && h->cls->loaded();
+  h->remember_frames(src, h->d_geom.as<ImgGeom>(), B);
   GraphKey key{GK_BATCH_DEVICE, B, h->geom_ver, min_area, dev_imgs, dev_dets, dev_counts, conf, iou};
   key_format(h, csc, key);
   run_or_capture(h, key, prof == nullptr, [&]() {

@@ -97,6 +97,7 @@ int lp_run_surfaces_device(lp_handle* h, const lp_surface_format* fmt, const lp_
   Profiler* prof = begin_profile(h);
   const uint8_t* src = h->d_src.as<uint8_t>();
   const bool classify = h->cls && h->cls->loaded();
+  h->remember_frames(src, h->d_geom.as<ImgGeom>(), B);
   const GraphKey key = surface_key(h, GK_SURFACES_DEVICE, *fmt, B, min_area, dev_dets, dev_counts, conf, iou);
   run_or_capture(h, key, prof == nullptr, [&]() {
     enqueue_surfaces(h, plan, prof);
@@ -124,6 +125,7 @@ int lp_run_views_surfaces_device(lp_handle* h, const lp_surface_format* fmt, con
   Profiler* prof = begin_profile(h);
   const uint8_t* src = h->d_src.as<uint8_t>();
   const bool classify = h->cls && h->cls->loaded();
+  h->remember_frames(src, h->d_fgeom.as<ImgGeom>(), B);
   const GraphKey key = surface_key(h, GK_VIEWS_SURFACES_DEVICE, *fmt, B, min_area, dev_dets, dev_counts, conf, iou);
   run_or_capture(h, key, prof == nullptr, [&]() {
     enqueue_surfaces(h, plan, prof);

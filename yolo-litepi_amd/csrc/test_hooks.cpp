@@ -444,6 +444,24 @@ int lp_test_set_rois(lp_handle* h, const uint8_t* crops, const int* img, const i
   LP_API_END
 }
 
+int lp_test_set_frames(lp_handle* h, const uint8_t* frames, int B, int H, int W) {
+  LP_API_BEGIN
+  LP_CHECK(h && frames, LP_ERR_ARG, "null argument");
+  LP_CHECK(B >= 1 && B <= h->cfg.max_batch && H >= 1 && W >= 1 && H <= 16384 && W <= 16384, LP_ERR_ARG, "%d frames of %dx%d", B, W, H);
+  LP_HIP(hipSetDevice(h->cfg.device));
+  LP_HIP(hipStreamSynchronize(h->stream));
+  const size_t fb = (size_t)H * W * 3;
+  std::vector<ImgGeom> g(B);
+  for (int i = 0; i < B; ++i) g[i] = make_geom(H, W, h->det_h(), h->det_w(), (long)(i * fb));
+  h->remember_frames(nullptr, nullptr, 0);
+  if (h->d_tframes.bytes < B * fb) h->d_tframes.alloc(B * fb, false);
+  if (h->d_tgeom.bytes < B * sizeof(ImgGeom)) h->d_tgeom.alloc((size_t)h->cfg.max_batch * sizeof(ImgGeom));
+  LP_HIP(hipMemcpy(h->d_tframes.p, frames, B * fb, hipMemcpyHostToDevice));
+  LP_HIP(hipMemcpy(h->d_tgeom.p, g.data(), B * sizeof(ImgGeom), hipMemcpyHostToDevice));
+  h->remember_frames(h->d_tframes.as<uint8_t>(), h->d_tgeom.as<ImgGeom>(), B);
+  LP_API_END
+}
+
 int lp_debug_rois(lp_handle* h, uint8_t* crops, int* img, int* slot, int cap, int* n) {
   LP_API_BEGIN
   LP_CHECK(h && n, LP_ERR_ARG, "null argument");

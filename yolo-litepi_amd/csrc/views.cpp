@@ -296,6 +296,7 @@ static void run_views_device(lp_handle* h, const void* dev_imgs, int B, int H, i
   Profiler* prof = begin_profile(h);
   const uint8_t* src = nv ? h->d_src.as<uint8_t>() : static_cast<const uint8_t*>(dev_imgs);
   const bool classify = h->cls && h->cls->loaded();
+  h->remember_frames(src, h->d_fgeom.as<ImgGeom>(), B);
   GraphKey key{kind, B, h->geom_ver, min_area, dev_imgs, dev_dets, dev_counts, conf, iou};
   key_format(h, csc, key);
   run_or_capture(h, key, prof == nullptr, [&]() {

@@ -98,13 +98,17 @@ class LpSign(C.Structure):
                 ("det_class", C.c_int32), ("flags", C.c_int32)]
 
 
+class LpEvidenceConfig(C.Structure):
+    _fields_ = [("size", C.c_int), ("scale", C.c_float), ("reserved", C.c_int * 6)]
+
+
 class LpFocusConfig(C.Structure):
     _fields_ = [("slots", C.c_int), ("side_min", C.c_int), ("side_max", C.c_int), ("margin", C.c_float), ("small_px", C.c_float),
                 ("border", C.c_int), ("sweep", C.c_int), ("sweep_overlap", C.c_int), ("reserved", C.c_int * 8)]
 
 
 LP_BEST_AREA, LP_BEST_DET_CONF, LP_BEST_CLS_CONF = 0, 1, 2
-LP_SIGN_HAS_CROP, LP_SIGN_FLUSHED = 1, 2
+LP_SIGN_HAS_CROP, LP_SIGN_FLUSHED, LP_SIGN_HAS_EVIDENCE = 1, 2, 4
 # numpy view of lp_sign records
 SIGN_DTYPE = [("stream", "<i4"), ("track_id", "<i4"), ("first_frame", "<i4"), ("last_frame", "<i4"), ("hits", "<i4"), ("voted_class", "<i4"),
               ("voted_conf", "<f4"), ("vote_weight", "<f4"), ("best_frame", "<i4"), ("best_quality", "<f4"), ("x1", "<f4"), ("y1", "<f4"),
@@ -133,6 +137,8 @@ SYMBOLS = [
     "lp_track_device", "lp_track", "lp_tracker_snapshot",
     "lp_inventory_default_config", "lp_inventory_config_check", "lp_inventory_create", "lp_inventory_destroy", "lp_inventory_device",
     "lp_inventory", "lp_inventory_flush", "lp_inventory_drain", "lp_inventory_open", "lp_test_set_rois", "lp_debug_rois",
+    "lp_evidence_default_config", "lp_evidence_config_check", "lp_evidence_window", "lp_evidence_create", "lp_evidence_destroy",
+    "lp_inventory_drain_evidence", "lp_evidence_open", "lp_test_set_frames",
     "lp_focus_default_config", "lp_focus_config_check", "lp_focus_create", "lp_focus_destroy", "lp_focus_plan", "lp_focus_state",
     "lp_run_focus_device", "lp_run_focus",
     "lp_letterbox_geometry", "lp_test_letterbox_kernel", "lp_test_roi_resize_rects",
@@ -234,6 +240,16 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_inventory_open.argtypes = [vp, C.c_int, vp, C.c_int, ip]
     lib.lp_test_set_rois.argtypes = [vp, vp, ip, ip, C.c_int]
     lib.lp_debug_rois.argtypes = [vp, vp, ip, ip, C.c_int, ip]
+    ecp = C.POINTER(LpEvidenceConfig)
+    lib.lp_evidence_default_config.argtypes = [ecp]
+    lib.lp_evidence_default_config.restype = None
+    lib.lp_evidence_config_check.argtypes = [ecp]
+    lib.lp_evidence_window.argtypes = [ecp, C.c_int, C.c_int, fp, ip, ip]
+    lib.lp_evidence_create.argtypes = [vp, ecp]
+    lib.lp_evidence_destroy.argtypes = [vp]
+    lib.lp_inventory_drain_evidence.argtypes = [vp, vp, vp, vp, vp, C.c_int, ip, ip]
+    lib.lp_evidence_open.argtypes = [vp, C.c_int, vp, vp, C.c_int, ip]
+    lib.lp_test_set_frames.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     fcp = C.POINTER(LpFocusConfig)
     lib.lp_focus_default_config.argtypes = [fcp]
     lib.lp_focus_default_config.restype = None
@@ -257,7 +273,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_graph_stats.argtypes = [vp, ip, i64p, i64p, i64p]
     for s in SYMBOLS:
         if s not in ("lp_last_error", "lp_default_config", "lp_destroy", "lp_track_default_config", "lp_inventory_default_config",
-                     "lp_focus_default_config", "lp_view_merge_default"):
+                     "lp_evidence_default_config", "lp_focus_default_config", "lp_view_merge_default"):
             getattr(lib, s).restype = C.c_int
     got = lib.lp_version()
     if got != ABI_VERSION:

@@ -176,6 +176,36 @@ def inventory_config_check(cfg: Optional[LpInventoryConfig]) -> int:
     return lib.lp_inventory_config_check(C.byref(cfg) if cfg is not None else None)
 
 
+EVIDENCE_CONFIG_FIELDS = ("size", "scale")
+
+
+def evidence_config(**cfg) -> _ffi.LpEvidenceConfig:
+    """lp_evidence_config with the library's defaults and the given fields (host only, no GPU needed)."""
+    lib = _ffi.load_library()
+    c = _ffi.LpEvidenceConfig()
+    lib.lp_evidence_default_config(C.byref(c))
+    for k, v in cfg.items():
+        if k not in EVIDENCE_CONFIG_FIELDS:
+            raise TypeError(f"unknown evidence setting {k!r} (one of {EVIDENCE_CONFIG_FIELDS})")
+        setattr(c, k, float(v) if k == "scale" else int(v))
+    return c
+
+
+def evidence_config_check(cfg: Optional[_ffi.LpEvidenceConfig]) -> int:
+    """lp_evidence_config_check's status for a configuration (host only, no GPU needed)."""
+    lib = _ffi.load_library()
+    return lib.lp_evidence_config_check(C.byref(cfg) if cfg is not None else None)
+
+
+def evidence_window(cfg: _ffi.LpEvidenceConfig, H: int, W: int, box) -> Tuple[Tuple[int, int, int, int], bool]:
+    """lp_evidence_window: ((x, y, w, h), has) of box (x1, y1, x2, y2) on an H x W frame (host only, no GPU needed)."""
+    lib = _ffi.load_library()
+    b = np.ascontiguousarray(box, dtype=np.float32).reshape(4)
+    win, has = np.zeros(4, np.int32), C.c_int()
+    check(lib, lib.lp_evidence_window(C.byref(cfg), int(H), int(W), b.ctypes.data_as(C.POINTER(C.c_float)), _ip(win), C.byref(has)))
+    return tuple(int(v) for v in win), bool(has.value)
+
+
 FOCUS_CONFIG_FIELDS = ("slots", "side_min", "side_max", "margin", "small_px", "border", "sweep", "sweep_overlap")
 
 
@@ -480,6 +510,7 @@ class Engine:
         check(self.lib, self.lib.lp_tracker_create(self._h, C.byref(c)))
         self.track_cfg = c
         self.__dict__.pop("inv_cfg", None)   # the inventory belongs to the tracker it was created on
+        self.__dict__.pop("ev_cfg", None)    # and the evidence store to the inventory
         self.__dict__.pop("focus_cfg", None)   # and so does the focus plan
 
     def tracker_destroy(self) -> None:
@@ -487,6 +518,7 @@ class Engine:
         if hasattr(self, "track_cfg"):
             del self.track_cfg
         self.__dict__.pop("inv_cfg", None)
+        self.__dict__.pop("ev_cfg", None)
         self.__dict__.pop("focus_cfg", None)
 
     def tracker_reset(self, stream: int = -1) -> None:
@@ -599,10 +631,12 @@ class Engine:
         c = inventory_config(**cfg)
         check(self.lib, self.lib.lp_inventory_create(self._h, C.byref(c)))
         self.inv_cfg = c
+        self.__dict__.pop("ev_cfg", None)
 
     def inventory_destroy(self) -> None:
         check(self.lib, self.lib.lp_inventory_destroy(self._h))
         self.__dict__.pop("inv_cfg", None)
+        self.__dict__.pop("ev_cfg", None)
 
     def inventory(self, dets: np.ndarray, counts, tracks: np.ndarray, stream_ids=None, crops: bool = False) -> None:
         """lp_inventory on host records: dets [B, max_det] lp_det, counts [B], tracks [B, max_det] lp_track as track() returned
@@ -647,6 +681,48 @@ class Engine:
         out = np.zeros(n.value, dtype=SIGN_DTYPE)
         check(self.lib, self.lib.lp_inventory_open(self._h, int(stream), out.ctypes.data, n.value, C.byref(n)))
         return out
+
+    # ---- evidence store: a context picture of each sign's best sighting ---------------------------
+    def evidence_create(self, size: int = 128, scale: float = 2.0) -> None:
+        """One evidence store per inventory (lp_evidence_create); calling it again replaces it.  size: side E of the BGR pictures
+        (a multiple of 16 in 32..256); scale: the window's side is scale x the box's longer side (1..16)."""
+        c = evidence_config(size=size, scale=scale)
+        check(self.lib, self.lib.lp_evidence_create(self._h, C.byref(c)))
+        self.ev_cfg = c
+
+    def evidence_destroy(self) -> None:
+        check(self.lib, self.lib.lp_evidence_destroy(self._h))
+        self.__dict__.pop("ev_cfg", None)
+
+    def inventory_drain_evidence(self, crops: bool = True):
+        """inventory_drain with the pictures: (signs [n], crops [n, S, S, 3] RGB or None, evidence [n, E, E, 3] uint8 BGR,
+        windows [n, 4] int32 {x, y, w, h}, dropped); evidence and windows are zeros for a sign without LP_SIGN_HAS_EVIDENCE."""
+        n, dropped = C.c_int(), C.c_int()
+        check(self.lib, self.lib.lp_inventory_drain_evidence(self._h, None, None, None, None, 0, C.byref(n), C.byref(dropped)))
+        S, E = self.cfg.cls_input, self.ev_cfg.size
+        signs = np.zeros(n.value, dtype=SIGN_DTYPE)
+        pix = np.zeros((n.value, S, S, 3), np.uint8) if crops else None
+        ev, win = np.zeros((n.value, E, E, 3), np.uint8), np.zeros((n.value, 4), np.int32)
+        check(self.lib, self.lib.lp_inventory_drain_evidence(self._h, signs.ctypes.data, None if pix is None else pix.ctypes.data, ev.ctypes.data,
+                                                             win.ctypes.data, n.value, C.byref(n), C.byref(dropped)))
+        return signs, pix, ev, win, dropped.value
+
+    def evidence_open(self, stream: int = 0):
+        """The pictures [n, E, E, 3] and windows [n, 4] of a stream's open entries in slot order, parallel to inventory_open
+        (synchronises)."""
+        n = C.c_int()
+        check(self.lib, self.lib.lp_evidence_open(self._h, int(stream), None, None, 0, C.byref(n)))
+        E = self.ev_cfg.size
+        ev, win = np.zeros((n.value, E, E, 3), np.uint8), np.zeros((n.value, 4), np.int32)
+        check(self.lib, self.lib.lp_evidence_open(self._h, int(stream), ev.ctypes.data, win.ctypes.data, n.value, C.byref(n)))
+        return ev, win
+
+    def test_set_frames(self, frames: np.ndarray) -> None:
+        """lp_test_set_frames: host BGR frames [B, H, W, 3] of one size, as lp_run_batch would leave them in the handle."""
+        f = np.ascontiguousarray(frames, dtype=np.uint8)
+        if f.ndim != 4 or f.shape[3] != 3:
+            raise ValueError(f"frames must be [B, H, W, 3], got {f.shape}")
+        check(self.lib, self.lib.lp_test_set_frames(self._h, f.ctypes.data, f.shape[0], f.shape[1], f.shape[2]))
 
     def test_set_rois(self, crops: np.ndarray, img, slot) -> None:
         """lp_test_set_rois: a ROI list (img[r], slot[r]) and its crops [R, S, S, 3] as a pipeline call would leave them."""
@@ -1157,11 +1233,14 @@ class HybridPipeline:
                  csc_matrix: str = "bt601", track: bool = False, track_config: Optional[Dict] = None, inventory=False,
                  views=None, view_tile: Optional[int] = None, view_overlap: int = 0, view_full_frame: bool = True,
                  focus: Optional[int] = None, focus_config: Optional[Dict] = None, view_match: Optional[str] = None,
-                 view_merge: Optional[str] = None, view_match_thr: Optional[float] = None):
+                 view_merge: Optional[str] = None, view_match_thr: Optional[float] = None, evidence=None):
         """detector_param, detector_bin: an NCNN .param / .bin pair, or an .onnx file and None.
         inventory: True or a dict of lp_inventory_config's fields (max_signs, keep_crops, best, min_hits): every tracked call
         also feeds the engine's sign inventory, while the handle still holds that call's classifier crops; drain_signs() returns
         the finished signs.  Needs track.
+        evidence: an int E or a dict {"size": E, "scale": s} (lp_evidence_config): the inventory also keeps an E x E BGR picture
+        of the surroundings of every sign's best sighting, cut from the native frame (Engine.evidence_create); drain_signs()
+        dicts then gain evidence and evidence_window.  Needs inventory (with keep_crops).
         track: run_batch also tracks the detections across calls (lp_track on the engine's tracker, created here with
         track_config: lp_track_config's fields); every result dict then gains track_id, track_hits, track_age, track_cls,
         track_cls_conf and track_confirmed.  The frames of consecutive calls are a sequence (per stream id).
@@ -1220,6 +1299,16 @@ class HybridPipeline:
             raise ValueError("inventory needs a pipeline constructed with track=True or a track_config")
         if self.inventory and int(os.environ.get("LITEPI_DROPIN_LANES", "1")) > 1:
             raise ValueError("inventory: the upload lanes keep their crops on other handles; unset LITEPI_DROPIN_LANES")
+        self.evidence = None
+        if evidence is not None and evidence is not False:
+            if not self.inventory:
+                raise ValueError("evidence needs a pipeline constructed with inventory=True")
+            ev = dict(evidence) if isinstance(evidence, dict) else {"size": int(evidence)}
+            if evidence_config_check(evidence_config(**ev)) != 0:
+                raise ValueError(f"evidence {evidence!r}: size must be a multiple of 16 in 32..256 and scale in 1..16")
+            if isinstance(inventory, dict) and not int(inventory.get("keep_crops", 1)):
+                raise ValueError("evidence needs an inventory with keep_crops")
+            self.evidence = ev
         print("\n" + "=" * 70)
         print("HYBRID PIPELINE: HIP Detector + HIP Classifier (MI355X)")
         print("=" * 70)
@@ -1244,6 +1333,8 @@ class HybridPipeline:
         self.signs_dropped = 0
         if self.inventory:
             self.engine.inventory_create(**(inventory if isinstance(inventory, dict) else {}))
+        if self.evidence is not None:
+            self.engine.evidence_create(**self.evidence)
         # ---- upload lanes (an experiment kept behind LITEPI_DROPIN_LANES=<n>, off by default: measured SLOWER, 3.2-3.6 ms per
         # 64-frame call against 2.7-2.9 for one handle -- four 16-frame passes cost 1.4 ms of kernels instead of 0.9 and four
         # sets of copy workers fight over the cores; walking a large batch in chunks inside lp_run_batch gained nothing either
@@ -1401,13 +1492,18 @@ class HybridPipeline:
     def drain_signs(self, flush: bool = False) -> List[Dict]:
         """The signs finished since the last call, one dict per track: stream, track_id, first_frame, last_frame, hits, cls,
         cls_conf (the final vote), bbox, det_class, best_frame (of the best sighting), crop (the classifier's RGB input crop of
-        the best sighting, or None), flushed.  flush: first close every open track (the end of a video).  The signs lost to a
-        full log are counted in signs_dropped."""
+        the best sighting, or None), flushed; with evidence also evidence (the [E, E, 3] BGR picture of the best sighting's
+        surroundings, or None) and evidence_window (x, y, w, h in the frame, or None).  flush: first close every open track
+        (the end of a video).  The signs lost to a full log are counted in signs_dropped."""
         if not self.inventory:
             raise ValueError("drain_signs needs a pipeline constructed with inventory=True")
         if flush:
             self.engine.inventory_flush(-1)
-        signs, crops, dropped = self.engine.inventory_drain(crops=bool(self.engine.inv_cfg.keep_crops))
+        pics = wins = None
+        if self.evidence is not None:
+            signs, crops, pics, wins, dropped = self.engine.inventory_drain_evidence(crops=bool(self.engine.inv_cfg.keep_crops))
+        else:
+            signs, crops, dropped = self.engine.inventory_drain(crops=bool(self.engine.inv_cfg.keep_crops))
         self.signs_dropped += dropped
         boxes = np.stack([signs["x1"], signs["y1"], signs["x2"], signs["y2"]], 1).astype(int).tolist()
         out = []
@@ -1418,6 +1514,10 @@ class HybridPipeline:
                         "hits": rec["hits"], "cls": rec["voted_class"], "cls_conf": rec["voted_conf"], "bbox": tuple(boxes[k]),
                         "det_class": rec["det_class"], "best_frame": rec["best_frame"], "crop": crops[k].copy() if has else None,
                         "flushed": bool(rec["flags"] & _ffi.LP_SIGN_FLUSHED)})
+            if pics is not None:
+                pic = bool(rec["flags"] & _ffi.LP_SIGN_HAS_EVIDENCE)
+                out[-1]["evidence"] = pics[k].copy() if pic else None
+                out[-1]["evidence_window"] = tuple(int(v) for v in wins[k]) if pic else None
         return out
 
     def run_batch(self, images: Sequence[np.ndarray], conf_threshold: float = 0.5, iou_threshold: float = 0.45,

@@ -126,6 +126,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "and the classifier's input crop of the best sighting as signs/sign_<stream>_<track>.png; collected on the device")
     p.add_argument("--inventory_best", choices=["area", "det_conf", "cls_conf"], default="area",
                    help="what makes a sighting the best of its track")
+    p.add_argument("--inventory_evidence", type=int, default=None, metavar="E",
+                   help="with --track --inventory: also keep an E x E BGR picture of the surroundings of every sign's best sighting "
+                        "(a multiple of 16 in 32..256), written as signs/sign_<stream>_<track>_evidence.png; signs.csv gains the "
+                        "picture's window in the frame")
+    p.add_argument("--inventory_evidence_scale", type=float, default=None, metavar="S",
+                   help="side of the picture's window as a multiple of the box's longer side, 1..16 (default 2)")
     p.add_argument("--track_iou", type=float, default=0.3, help="a detection matches a track when their IoU exceeds this")
     p.add_argument("--track_max_age", type=int, default=5, help="frames a track may stay unmatched before it is dropped")
     p.add_argument("--track_min_hits", type=int, default=3, help="matched frames after which a track counts as confirmed")
@@ -381,6 +387,7 @@ TRACKS_CSV_COLUMNS = ("frame", "track_id", "x1", "y1", "x2", "y2", "det_conf", "
 
 SIGNS_CSV_COLUMNS = ("stream", "track_id", "first_frame", "last_frame", "hits", "voted_class", "voted_conf", "best_frame", "x1", "y1", "x2",
                      "y2", "det_class", "flushed", "crop")
+EVIDENCE_CSV_COLUMNS = ("evidence_x", "evidence_y", "evidence_w", "evidence_h")   # --inventory_evidence: the picture's window, at the end
 
 
 def parse_views(text: str) -> List:
@@ -425,6 +432,16 @@ def check_frame_args(args) -> None:
             raise SystemExit(f"--focus {args.focus} outside 1..16 window slots")
     if getattr(args, "inventory", False) and not getattr(args, "track", False):
         raise SystemExit("--inventory needs --track: the inventory lists the tracker's finished tracks")
+    if getattr(args, "inventory_evidence", None) is not None or getattr(args, "inventory_evidence_scale", None) is not None:
+        if not (getattr(args, "track", False) and getattr(args, "inventory", False)):
+            raise SystemExit("--inventory_evidence needs --track --inventory: the pictures belong to the inventory's signs")
+        if getattr(args, "inventory_evidence", None) is None:
+            raise SystemExit("--inventory_evidence_scale needs --inventory_evidence E")
+        E, S = args.inventory_evidence, getattr(args, "inventory_evidence_scale", None)
+        if not (32 <= E <= 256 and E % 16 == 0):
+            raise SystemExit(f"--inventory_evidence {E} is no multiple of 16 in 32..256")
+        if S is not None and not 1.0 <= S <= 16.0:
+            raise SystemExit(f"--inventory_evidence_scale {S} outside 1..16")
     if getattr(args, "track", False):   # tracking needs the frames of ONE sequence, all of them, in order, in one process
         if not args.raw_frames:
             raise SystemExit("--track needs --raw_frames: the frames of a raw file are a sequence, the images of --input are not")
@@ -514,6 +531,11 @@ def run_evaluation(args) -> Dict:
     track_kw = dict(track=True, track_config=dict(iou_match=args.track_iou, max_age=args.track_max_age, min_hits=args.track_min_hits)) if args.track else {}
     if args.inventory:
         track_kw["inventory"] = dict(best=args.inventory_best)
+    evidence_on = args.inventory and getattr(args, "inventory_evidence", None) is not None
+    if evidence_on:   # absent: the pipeline is constructed exactly as before
+        track_kw["evidence"] = dict(size=args.inventory_evidence)
+        if getattr(args, "inventory_evidence_scale", None) is not None:
+            track_kw["evidence"]["scale"] = args.inventory_evidence_scale
     bench_kw, eval_kw = (dict(track=True), dict(track=False)) if args.track else ({}, {})
     with contextlib.redirect_stdout(io.StringIO()) if rank != 0 else contextlib.nullcontext():   # one banner, rank 0's
         pipeline = HybridPipeline(args.detector_param, args.detector_bin, args.classifier, args.clf_arch, num_classes,
@@ -628,14 +650,20 @@ def run_evaluation(args) -> Dict:
         crop_dir.mkdir(parents=True, exist_ok=True)
         with open(out_dir / "signs.csv", "w", newline="") as fcsv:
             w = csv.writer(fcsv)
-            w.writerow(SIGNS_CSV_COLUMNS)
+            w.writerow(SIGNS_CSV_COLUMNS + (EVIDENCE_CSV_COLUMNS if evidence_on else ()))
             for s in signs:
                 name = ""
                 if s["crop"] is not None:
                     name = f"signs/sign_{s['stream']}_{s['track_id']}.png"
                     Image.fromarray(s["crop"], "RGB").save(out_dir / name)
+                win = ()
+                if evidence_on:
+                    win = s["evidence_window"] or ("", "", "", "")
+                    if s["evidence"] is not None:   # BGR, the frames' byte order -> the PNG's RGB
+                        Image.fromarray(np.ascontiguousarray(s["evidence"][:, :, ::-1]), "RGB").save(
+                            out_dir / f"signs/sign_{s['stream']}_{s['track_id']}_evidence.png")
                 w.writerow((s["stream"], s["track_id"], s["first_frame"], s["last_frame"], s["hits"], s["cls"], s["cls_conf"], s["best_frame"],
-                            *s["bbox"], s["det_class"], int(s["flushed"]), name))
+                            *s["bbox"], s["det_class"], int(s["flushed"]), name, *win))
         say(f"Inventory: {len(signs)} signs ({sum(s['crop'] is not None for s in signs)} with a crop, {pipeline.signs_dropped} dropped) "
             f"-> {out_dir / 'signs.csv'}")
     rank_times = [bench_time]
