@@ -1,6 +1,6 @@
-// Host-only check of csrc/surface_plan.h, built with a plain g++ under -fsanitize=address,undefined (tests/test_surface_plan_cpu.py):
+// Host-only check of csrc/surface_plan.h and csrc/ring_slots.h, built with a plain g++ under -fsanitize=address,undefined (tests/test_surface_plan_cpu.py):
 // the argument rules of include/litepi.h on exact-sized arrays, the table records of seeded random surface sets, and the pinned
-// ring's slot policy against a model of the copies in flight.  Prints one line per section and "OK"; any failure is a message on
+// rings' slot policy (RingSlots, behind every PlanRing) against a model of the copies in flight.  Prints one line per section and "OK"; any failure is a message on
 // stderr and a non-zero exit.
 #include <cstdio>
 #include <cstdlib>
@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "ring_slots.h"
 #include "surface_plan.h"
 
 namespace lp {
@@ -139,7 +140,7 @@ int main() {
   // ---- the ring: a slot is never written while its copy may be in flight, and nothing waits before the ring wraps
   {
     constexpr int RING = 8;
-    SurfaceSlots<RING> slots;
+    RingSlots<RING> slots;
     int in_flight[RING];   // the call whose copy last read the slot, -1: none or waited for
     for (int& v : in_flight) v = -1;
     int waits = 0;

@@ -92,6 +92,13 @@ def test_run_batch_device_matches_host_path(tmp_path, monkeypatch, no_graph):
             with torch.cuda.stream(st):
                 total += _check_device_call(eng, dev_imgs[j], res, refs[j], f"call {call} (buffer {j}, {'no graph' if no_graph else 'graph'})")
         print(f"device path == host path on 8 calls, {total} records compared")
+        # LITEPI_NO_GRAPH is read when the handle is created, so this leg is eager whatever an earlier handle of the process saw
+        stats = eng.graph_stats()
+        print(f"graph stats ({'no graph' if no_graph else 'graph'}): {stats}")
+        if no_graph:
+            assert stats["captures"] == 0 and stats["replays"] == 0 and stats["eager"] == 8, stats
+        else:   # two input buffers alternate: first sight, capture, then two replays each
+            assert stats == dict(entries=2, eager=2, captures=2, replays=4), stats
     finally:
         eng.close()
         ref_eng.close()

@@ -1,8 +1,8 @@
-"""The host logic of the decoder-surface front (csrc/surface_plan.h) without a device or Python in the loop.
+"""The host logic of the decoder-surface front (csrc/surface_plan.h) and of the plan rings (csrc/ring_slots.h) without a device or Python in the loop.
 
-tests/native/surface_plan_check.cpp includes the header alone, built with a plain g++ under -fsanitize=address,undefined: the
+tests/native/surface_plan_check.cpp includes the two headers alone, built with a plain g++ under -fsanitize=address,undefined: the
 argument rules of include/litepi.h on exact-sized arrays, the converter's table records (pitches resolved, the `aligned` flag,
-max_blocks) for 2000 seeded surface sets, and the slot policy of the pinned ring against a model of the copies in flight."""
+max_blocks) for 2000 seeded surface sets, and the slot policy of the pinned rings against a model of the copies in flight."""
 import os
 import shutil
 import subprocess

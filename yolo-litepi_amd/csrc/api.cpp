@@ -98,7 +98,10 @@ int lp_create(const lp_config* cfg, lp_handle** out) {
   LP_HIP(hipGetDeviceProperties(&prop, cfg->device));
   if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
     throw Error(LP_ERR_NODEVICE, fmt("device %d is %s; this library is built for gfx950 only", cfg->device, prop.gcnArchName));
-  // the two measurement diagnostics make every pass after a handle's first return STALE results with LP_OK: never silently
+  std::unique_ptr<lp_handle> h(new lp_handle());
+  h->cfg = *cfg;
+  // the run path's switches, as this handle's environment has them (RunOptions).  The two measurement diagnostics make every
+  // pass after a handle's first return STALE results with LP_OK: never silently
   {
     static bool warned = false;
     const char *ss = getenv("LITEPI_SKIP_STAGE"), *so = getenv("LITEPI_SKIP_OP");
@@ -108,9 +111,12 @@ int lp_create(const lp_config* cfg, lp_handle** out) {
                       "detector launch is LEFT OUT of every pass after a handle's first; results are stale and must not be used\n",
               ss ? ss : "", so ? so : "");
     }
+    const char *ut = getenv("LITEPI_UPLOAD_THREADS"), *ug = getenv("LITEPI_UPLOAD_GROUP_MB");
+    h->opt.no_graph = getenv("LITEPI_NO_GRAPH") != nullptr;
+    if (ss) h->opt.skip_stage = ss;
+    if (ut) h->opt.upload_threads = atoi(ut);
+    if (ug) h->opt.upload_group_mb = (size_t)atol(ug);
   }
-  std::unique_ptr<lp_handle> h(new lp_handle());
-  h->cfg = *cfg;
   // every kept box is a ROI (the reference classifies all of them, e2e.py:493-497): the default capacity can not overflow
   h->max_rois = cfg->max_rois > 0 ? cfg->max_rois : cfg->max_batch * cfg->max_det;
   // the classifier's widest per-ROI tensor must stay below 2^31 elements (32-bit element offsets in the conv kernels): say so

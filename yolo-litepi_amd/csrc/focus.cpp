@@ -40,13 +40,6 @@ static FocusPlan& focus_of(lp_handle* h) {
   return *h->trk->focus;
 }
 
-static void check_streams(const Tracker& t, int B, const int* stream_ids) {
-  if (stream_ids)
-    for (int b = 0; b < B; ++b)
-      LP_CHECK(stream_ids[b] >= 0 && stream_ids[b] < t.cfg.n_streams, LP_ERR_ARG, "stream_ids[%d] = %d outside 0..%d", b, stream_ids[b],
-               t.cfg.n_streams - 1);
-}
-
 // ---- the device tables ---------------------------------------------------------------------------------------------------------
 // While the plan kernel owns the window table and the windows' geometry, the handle's two host mirrors hold a mark no upload
 // can equal: any other path re-uploads (and so invalidates the captured steps), and a focus call knows its tables are still
@@ -94,9 +87,9 @@ static void enqueue_focus_plan(lp_handle* h, int B, const int* hs, const int* ws
                                bool tables, int advance, Profiler* prof) {
   Tracker& t = *h->trk;
   FocusPlan& p = *t.focus;
-  const int k = p.next, mb = t.max_batch, S = h->cfg.det_input;
-  if (p.busy[k]) LP_HIP(hipEventSynchronize(p.ev[k]));
-  int* slot = p.plan_host + (size_t)k * p.slot_ints;
+  const int mb = t.max_batch, S = h->cfg.det_input;
+  const PlanRing::Slot rs = p.ring.acquire();
+  int* slot = static_cast<int*>(rs.host);
   const int n_jobs = plan_stream_jobs(slot, mb, B, stream_ids);
   int* fh = slot + (size_t)mb * 5;
   int* fw = fh + mb;
@@ -105,8 +98,8 @@ static void enqueue_focus_plan(lp_handle* h, int B, const int* hs, const int* ws
     fh[b] = hs ? hs[b] : H; fw[b] = ws ? ws[b] : W;
     frf[b] = make_geom(fh[b], fw[b], S, S, 0).ratio;
   }
-  int* dslot = p.plan_dev.as<int>() + (size_t)k * p.slot_ints;
-  LP_HIP(hipMemcpyAsync(dslot, slot, p.slot_ints * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  const int* dslot = static_cast<const int*>(rs.dev);
+  p.ring.upload(rs, p.ring.slot_bytes, h->stream);
   FocusArgs a;
   memset(&a, 0, sizeof(a));
   a.jobs = reinterpret_cast<const TrackJob*>(dslot); a.frames = dslot + (size_t)mb * 4;
@@ -121,9 +114,7 @@ static void enqueue_focus_plan(lp_handle* h, int B, const int* hs, const int* ws
   if (prof) prof->begin(h->stream);
   launch_focus_plan(a, n_jobs, h->stream);
   if (prof) prof->end(h->stream, "focus_plan", "focus_plan", 0.0, 0.0);
-  LP_HIP(hipEventRecord(p.ev[k], h->stream));
-  p.busy[k] = true;
-  p.next = (k + 1) % FocusPlan::RING;
+  p.ring.release(rs, h->stream);
 }
 
 // what both run calls check before anything is enqueued
@@ -131,7 +122,7 @@ static void check_focus_run(lp_handle* h, int B, const int* hs, const int* ws, i
   const FocusPlan& p = focus_of(h);
   LP_CHECK((long)B * (1 + p.cfg.slots) <= h->cfg.max_batch, LP_ERR_ARG, "%d frames need %ld views (1 + %d slots each), more than max_batch = %d",
            B, (long)B * (1 + p.cfg.slots), p.cfg.slots, h->cfg.max_batch);
-  check_streams(*h->trk, B, stream_ids);
+  check_stream_ids(*h->trk, B, stream_ids);
   for (int b = 0; b < B; ++b) {
     const int fh = hs ? hs[b] : H, fw = ws ? ws[b] : W;
     LP_CHECK(fh >= 16 && fw >= 16, LP_ERR_ARG, "frame %d is %dx%d: focus views need at least 16 pixels a side", b, fw, fh);
@@ -177,10 +168,7 @@ int lp_focus_create(lp_handle* h, const lp_focus_config* cfg) {
   p->state.alloc((size_t)t.cfg.n_streams * sizeof(FocusState));
   p->d_views.alloc((size_t)t.max_batch * 16 * 4 * sizeof(int));
   p->d_dead.alloc((size_t)t.max_batch * sizeof(int));
-  p->slot_ints = (size_t)t.max_batch * 8;
-  p->plan_dev.alloc(FocusPlan::RING * p->slot_ints * sizeof(int));
-  LP_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->plan_host), FocusPlan::RING * p->slot_ints * sizeof(int), hipHostMallocDefault));
-  for (auto& e : p->ev) LP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  p->ring.create((size_t)t.max_batch * 8 * sizeof(int));
   t.focus = std::move(p);   // its first call uploads its tables: the steps captured under a replaced plan go with them
   LP_API_END
 }
@@ -193,7 +181,7 @@ int lp_focus_plan(lp_handle* h, int B, const int* heights, const int* widths, co
   LP_CHECK(heights && widths && views, LP_ERR_ARG, "null argument");
   LP_CHECK(B >= 1 && B <= t.max_batch, LP_ERR_ARG, "batch %d outside 1..%d", B, t.max_batch);
   LP_CHECK(advance == 0 || advance == 1, LP_ERR_ARG, "advance %d is not 0 or 1", advance);
-  check_streams(t, B, stream_ids);
+  check_stream_ids(t, B, stream_ids);
   for (int b = 0; b < B; ++b)
     LP_CHECK(heights[b] >= 16 && widths[b] >= 16, LP_ERR_ARG, "frame %d is %dx%d: focus views need at least 16 pixels a side", b, widths[b],
              heights[b]);
@@ -225,30 +213,16 @@ int lp_run_focus_device(lp_handle* h, const void* dev_imgs, int B, int H, int W,
   check_run_args(h, dev_imgs && dev_dets && dev_counts, B, false, min_area);
   check_focus_run(h, B, nullptr, nullptr, H, W, stream_ids);
   LP_HIP(hipSetDevice(h->cfg.device));
-  std::vector<ImgGeom> fg(B);
-  for (int i = 0; i < B; ++i) fg[i] = make_geom(H, W, h->det_h(), h->det_w(), (long)i * H * W * 3);
-  ViewLayout lay = focus_layout(h, p, fg);
-  const bool nv = h->nv12();
+  std::vector<ImgGeom> fg;
   CscPlan csc;
-  if (nv) {   // device_csc checks the format before it sizes d_src; the converted frames sit at 16-byte aligned offsets
-    csc = device_csc(h, dev_imgs, B, H, W, fg);
-    lay = focus_layout(h, p, fg);
-  }
+  const ViewLayout lay =
+      device_view_frames(h, dev_imgs, B, H, W, [&](const std::vector<ImgGeom>& g) { return focus_layout(h, p, g); }, fg, csc);
   upload_focus_tables(h, p, fg, lay);
-  Profiler* prof = begin_profile(h);
-  enqueue_focus_plan(h, B, nullptr, nullptr, H, W, stream_ids, static_cast<int*>(dev_views), true, 1, prof);
-  const uint8_t* src = nv ? h->d_src.as<uint8_t>() : static_cast<const uint8_t*>(dev_imgs);
-  const bool classify = h->cls && h->cls->loaded();
-  h->remember_frames(src, h->d_fgeom.as<ImgGeom>(), B);
-  GraphKey key{GK_FOCUS_DEVICE, B, h->geom_ver, min_area, dev_imgs, dev_dets, dev_counts, conf, iou};
-  key_format(h, csc, key);
-  run_or_capture(h, key, prof == nullptr, [&]() {
-    if (nv) enqueue_csc(h, static_cast<const uint8_t*>(dev_imgs), csc, prof);
-    enqueue_view_front(h, src, lay, B, conf, iou, classify ? min_area : -1, static_cast<lp_det*>(dev_dets), static_cast<int*>(dev_counts),
-                       classify, prof, p.d_dead.as<int>());
-    if (classify) enqueue_classify(h, src, B, static_cast<lp_det*>(dev_dets), nullptr, nullptr, nullptr, prof, 0, h->d_fgeom.as<ImgGeom>());
-  });
-  if (prof) prof->enabled = false;  // records are collected by lp_profile_read after the caller synchronises
+  const FrameSource frames = device_frames(h, dev_imgs, csc);
+  run_device_pass(h, GK_FOCUS_DEVICE, B, conf, iou, min_area, dev_dets, dev_counts, frames,
+                  view_front(h, frames.src, lay, B, conf, iou, p.d_dead.as<int>()), [&](Profiler* prof) {
+                    enqueue_focus_plan(h, B, nullptr, nullptr, H, W, stream_ids, static_cast<int*>(dev_views), true, 1, prof);
+                  });
   LP_API_END
 }
 
@@ -260,18 +234,10 @@ int lp_run_focus(lp_handle* h, const uint8_t* const* imgs, const int* hs, const 
   check_run_args(h, imgs && hs && ws && dets && counts, B, true, min_area);
   check_focus_run(h, B, hs, ws, 0, 0, stream_ids);
   LP_HIP(hipSetDevice(h->cfg.device));
-  std::vector<ImgGeom> fg(B);
-  for (int i = 0; i < B; ++i) fg[i] = make_geom(hs[i], ws[i], h->det_h(), h->det_w(), 0);
-  (void)focus_layout(h, p, fg);   // validates the call before anything is uploaded (the frames' offsets come with the upload)
-  const bool nv = h->nv12();
-  if (nv) {   // host frames: frame_stride does not apply
-    lp_frame_format hf = h->fmt;
-    hf.frame_stride = 0;
-    for (int i = 0; i < B; ++i) (void)frame_layout(hf, hs[i], ws[i]);
-  }
+  std::vector<ImgGeom> fg;
   CscPlan csc;
-  fg = upload_images(h, imgs, hs, ws, B, &csc);
-  const ViewLayout lay = focus_layout(h, p, fg);
+  const ViewLayout lay =
+      upload_view_frames(h, imgs, hs, ws, B, [&](const std::vector<ImgGeom>& g) { return focus_layout(h, p, g); }, fg, csc);
   upload_focus_tables(h, p, fg, lay);
   // the plan launch stays outside the captured front (the staged pass's profile starts behind it: only lp_run_focus_device
   // books it); the windows are read back first, so that a ROI overflow reported by the pass still delivers them
@@ -280,12 +246,8 @@ int lp_run_focus(lp_handle* h, const uint8_t* const* imgs, const int* hs, const 
     LP_HIP(hipMemcpyAsync(views, p.d_views.p, (size_t)B * p.cfg.slots * 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     LP_HIP(hipStreamSynchronize(h->stream));   // the destination is the caller's pageable memory
   }
-  run_host_pass(h, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, csc, GK_FOCUS_FRONT, GK_FOCUS_ROI, GK_FOCUS_CLS,
-                [&](Profiler* pr) {
-                  if (nv) enqueue_csc(h, h->d_raw.as<uint8_t>(), csc, pr);
-                  enqueue_view_front(h, h->d_src.as<uint8_t>(), lay, B, conf, iou, min_area, h->d_dets.as<lp_det>(), h->d_counts.as<int>(), true,
-                                     pr, p.d_dead.as<int>());
-                }, h->d_fgeom.as<ImgGeom>());
+  run_host_pass(h, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, csc, GK_FOCUS_FRONT,
+                view_front(h, h->d_src.as<uint8_t>(), lay, B, conf, iou, p.d_dead.as<int>()));
   LP_API_END
 }
 

@@ -12,11 +12,13 @@
 #include "copy_pool.h"
 #include "detector.h"
 #include "kernels.h"
+#include "ring_slots.h"
 
 namespace lp {
 
-// The call plan both rings carry (one slot: up to max_batch TrackJobs, then the max_batch frame indices): one job per stream
-// present in the call, in order of first appearance; its frames in batch order.  Returns the number of jobs.
+// The call plan the tracker's, the inventory's and the focus plan's rings carry (one slot: up to max_batch TrackJobs, then the
+// max_batch frame indices): one job per stream present in the call, in order of first appearance; its frames in batch order.
+// Returns the number of jobs.
 inline int plan_stream_jobs(int* slot, int max_batch, int B, const int* stream_ids) {
   TrackJob* jobs = reinterpret_cast<TrackJob*>(slot);
   int* frames = slot + (size_t)max_batch * (sizeof(TrackJob) / sizeof(int));
@@ -39,9 +41,51 @@ inline int plan_stream_jobs(int* slot, int max_batch, int B, const int* stream_i
   return n_jobs;
 }
 
+// The one pinned -> device plan ring.  A call's plan (the tracker's, the inventory's and the focus plan's stream jobs and frame
+// lists, a surfaces call's table records) is written into a slot of a pinned block and copied from there to the device on the
+// handle's stream (a pageable source would synchronise it).  dev_slots = RING: every pinned slot has a device slot of its
+// own, and the event is recorded behind the launch that read it (tracker, inventory, focus).  dev_slots = 1: every captured
+// step reads ONE device table at a fixed address, rewritten in stream order in front of the step, and the event is recorded
+// behind the copy (surfaces).  Which slot comes next and whether its event has to be waited for is RingSlots' policy
+// (ring_slots.h): only a slot still marked busy waits, i.e. once the ring has wrapped.
+struct PlanRing {
+  static constexpr int RING = 8;
+  struct Slot { int index; void* host; void* dev; };
+  DevBuf dev;             // dev_slots slots of slot_bytes
+  char* host = nullptr;   // pinned, RING slots of slot_bytes
+  size_t slot_bytes = 0;
+  int dev_slots = RING;
+  hipEvent_t ev[RING] = {};
+  RingSlots<RING> slots;
+  void create(size_t bytes, int n_dev = RING) {
+    slot_bytes = bytes; dev_slots = n_dev;
+    dev.alloc((size_t)n_dev * bytes);
+    LP_HIP(hipHostMalloc(reinterpret_cast<void**>(&host), RING * bytes, hipHostMallocDefault));
+    for (auto& e : ev) LP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  // the next slot, free to be written (independent of any stream: it waits on the host, and only where the policy says so)
+  Slot acquire() {
+    bool wait = false;
+    const int k = slots.take(&wait);
+    if (wait) LP_HIP(hipEventSynchronize(ev[k]));
+    return Slot{k, host + (size_t)k * slot_bytes, dev.as<char>() + (size_t)(dev_slots == RING ? k : 0) * slot_bytes};
+  }
+  void upload(const Slot& s, size_t bytes, hipStream_t st) { LP_HIP(hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, st)); }
+  // behind whatever read the slot last on st: the slot is re-used only after this point of the stream
+  void release(const Slot& s, hipStream_t st) {
+    LP_HIP(hipEventRecord(ev[s.index], st));
+    slots.mark(s.index);
+  }
+  ~PlanRing() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (host) (void)hipHostFree(host);
+  }
+};
+
 // Sign inventory of a tracker (lp_inventory_*; include/litepi.h): entries, frame counters, the gallery of best crops and the
-// log of finished signs stay in HBM between calls.  Its call plans go through a pinned -> device ring of its own, built like
-// the tracker's: the tracker's ring keeps its re-use timing.
+// log of finished signs stay in HBM between calls.  Its call plans go through a plan ring of its own: the tracker's ring keeps
+// its re-use timing.
 // Evidence store of an inventory (lp_evidence_*; include/litepi.h): per entry the E x E BGR picture of its best sighting's
 // surroundings and that picture's window; the same per logged sign; and the job list the deciding kernel leaves for the
 // picture launch (kernels.h, EvJob).
@@ -52,74 +96,52 @@ struct Evidence {
 };
 
 struct Inventory {
-  static constexpr int RING = 8;
   std::unique_ptr<Evidence> evid;   // null until lp_evidence_create: no other path looks at it
   lp_inventory_config cfg;
   int min_hits = 0, crop_bytes = 0;
-  DevBuf entries, frame_no, head, log, log_crops, gallery, roi_of, plan_dev;
+  DevBuf entries, frame_no, head, log, log_crops, gallery, roi_of;
   DevBuf d_dets, d_counts, d_tracks;   // lp_inventory (host records): allocated on first use
-  int* plan_host = nullptr;            // pinned, RING slots of slot_ints
-  size_t slot_ints = 0;
-  hipEvent_t ev[RING] = {};
-  bool busy[RING] = {};
-  int next = 0;
-  ~Inventory() {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (plan_host) (void)hipHostFree(plan_host);
-  }
+  PlanRing ring;                       // a slot: the tracker's plan (plan_stream_jobs)
 };
 
 // Focus plan of a tracker (lp_focus_*; include/litepi.h): the per-stream sweep cursor and unserved counter stay in HBM between
 // calls.  Its call plans (the tracker's jobs and frame lists, then every frame's height, width and letterbox ratio) go through
-// a pinned -> device ring of its own, like the inventory's.  blob / vgeom remember the placeholder layout whose device tables
-// the plan kernel rewrites in place (focus.cpp: resident()).
+// a plan ring of its own.  blob / vgeom remember the placeholder layout whose device tables the plan kernel rewrites in place
+// (focus.cpp: upload_focus_tables).
 struct FocusPlan {
-  static constexpr int RING = 8;
   lp_focus_config cfg;   // the zeros resolved
-  DevBuf state, plan_dev, d_views, d_dead;
-  int* plan_host = nullptr;   // pinned, RING slots of slot_ints
-  size_t slot_ints = 0;
-  hipEvent_t ev[RING] = {};
-  bool busy[RING] = {};
-  int next = 0;
+  DevBuf state, d_views, d_dead;
+  PlanRing ring;
   std::vector<char> blob;
   std::vector<ImgGeom> vgeom;
-  ~FocusPlan() {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (plan_host) (void)hipHostFree(plan_host);
-  }
 };
 
 // Sign tracker of a handle (lp_tracker_*, lp_track*; include/litepi.h): the track table, the stream heads and the vote accumulators
-// stay in HBM between calls.  A call's per-stream frame lists are written into a slot of a pinned ring and copied from there
-// into the same slot of a device ring on the handle's stream (a pageable source would synchronise it); a slot is re-used only
-// after the event recorded behind the launch that read it.
+// stay in HBM between calls.  A call's per-stream frame lists go through its plan ring.
 struct Tracker {
-  static constexpr int RING = 8;
   std::unique_ptr<Inventory> inv;   // null until lp_inventory_create: no other path looks at it
   std::unique_ptr<FocusPlan> focus; // null until lp_focus_create: no other path looks at it
   lp_track_config cfg;
   int nc = 1, max_det = 0, max_batch = 0;
-  DevBuf table, heads, acc, scratch, plan_dev;
+  DevBuf table, heads, acc, scratch;
   DevBuf d_dets, d_counts, d_tracks;   // lp_track (host records): allocated on first use
-  int* plan_host = nullptr;            // pinned, RING slots of slot_ints
-  size_t slot_ints = 0;
-  hipEvent_t ev[RING] = {};
-  bool busy[RING] = {};
-  int next = 0;
-  ~Tracker() {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (plan_host) (void)hipHostFree(plan_host);
-  }
+  PlanRing ring;                       // a slot: up to max_batch jobs, then the max_batch frame indices (plan_stream_jobs)
 };
+
+// a call's stream ids against the tracker's streams (tracker, inventory and focus calls)
+inline void check_stream_ids(const Tracker& t, int B, const int* stream_ids) {
+  if (stream_ids)
+    for (int b = 0; b < B; ++b)
+      LP_CHECK(stream_ids[b] >= 0 && stream_ids[b] < t.cfg.n_streams, LP_ERR_ARG, "stream_ids[%d] = %d outside 0..%d", b, stream_ids[b],
+               t.cfg.n_streams - 1);
+}
 
 // ---- captured steps: the launch sequence of a call is a pure function of (entry point, buffers, batch, geometry,
 //      thresholds), so the second call with the same key is captured into a hipGraph and later calls replay it
-//      (one hipGraphLaunch instead of ~40 kernel launches on the host).  LITEPI_NO_GRAPH=1 keeps every call eager.
+//      (one hipGraphLaunch instead of ~40 kernel launches on the host).  LITEPI_NO_GRAPH=1 keeps every call of a handle
+//      created under it eager (RunOptions).
 // One enumerator per captured piece: a key of another piece never compares equal, so no entry point replays another's step.
+// A host entry point's three pieces are consecutive: run_host_pass takes the front's and counts on.
 enum GraphKind {
   GK_BATCH_DEVICE,                                // lp_run_batch_device
   GK_DETECT,                                      // lp_detect
@@ -147,30 +169,23 @@ struct GraphKey {
            uv_offset == o.uv_offset && frame_stride == o.frame_stride;
   }
 };
-// Decoder surfaces (lp_run_surfaces_device, lp_run_views_surfaces_device; surfaces.cpp): the converter of every captured step
-// reads ONE device table at a fixed address, so a surface's address and pitches are data and not part of a step's identity.
-// A call writes its records into the next slot of a pinned ring and copies them to the table on the handle's stream, in front
-// of the step: stream order keeps every call's table apart.  A pinned slot is re-used only after the event recorded behind
-// its copy (waited on when the ring wraps, never otherwise).
-struct SurfaceRing {
-  static constexpr int RING = 8;
-  DevBuf table;                  // [max_batch] SurfFrame
-  SurfFrame* host = nullptr;     // pinned, RING slots of max_batch records
-  hipEvent_t ev[RING] = {};
-  SurfaceSlots<RING> slots;      // which slot is next and whether its event has to be waited for (surface_plan.h)
-  ~SurfaceRing() {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (host) (void)hipHostFree(host);
-  }
-};
-
 struct GraphEntry { GraphKey key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; bool failed = false; unsigned long stamp = 0; };
+
+// The run path's environment switches, read once per handle in lp_create: LITEPI_NO_GRAPH (every call eager),
+// LITEPI_SKIP_STAGE=nms|roi|cls (diagnostic, pipeline.cpp: skip_stage), LITEPI_UPLOAD_THREADS (copy workers of the host upload,
+// <= 0: none) and LITEPI_UPLOAD_GROUP_MB (its group size).
+struct RunOptions {
+  bool no_graph = false;
+  std::string skip_stage;
+  int upload_threads = 8;
+  size_t upload_group_mb = 10;
+};
 
 }  // namespace lp
 
 struct lp_handle {
   lp_config cfg;
+  lp::RunOptions opt;
   // the detector input, rows x columns (lp_config::det_input_h: 0 = square)
   int det_h() const { return cfg.det_input_h ? cfg.det_input_h : cfg.det_input; }
   int det_w() const { return cfg.det_input; }
@@ -225,7 +240,9 @@ struct lp_handle {
       ++geom_ver;
     }
   }
-  std::unique_ptr<lp::SurfaceRing> surf;   // null until the first surfaces call: no other path looks at it
+  // Decoder surfaces (lp_run_surfaces_device, lp_run_views_surfaces_device; surfaces.cpp): a plan ring with one device table,
+  // [max_batch] SurfFrame.  A surface's address and pitches are data in that table and not part of a step's identity.
+  std::unique_ptr<lp::PlanRing> surf;   // null until the first surfaces call: no other path looks at it
   std::vector<lp::GraphEntry> graphs;   // captured steps (run_or_capture)
   int64_t n_eager = 0, n_captures = 0, n_replays = 0;   // lp_graph_stats: calls of run_or_capture by what they did
   int geom_ver = 0;
@@ -312,6 +329,28 @@ void enqueue_classify(lp_handle* h, const uint8_t* src, int B, lp_det* dets, flo
 // eager the first time a key is seen, captured into a hipGraph the second time, replayed from then on
 void run_or_capture(lp_handle* h, const GraphKey& key, bool allow, const std::function<void()>& enqueue);
 
+// ---- the two passes every lp_run_* entry point ends in (pipeline.cpp) -------------------------------------------------------------
+// Where a call's packed BGR frames are once `convert` has run (empty: they are there already), and the graph key fields the
+// source owns: p0 and the format fields.  device_frames (pixfmt.cpp) and surface_frames (surfaces.cpp) make them.
+struct FrameSource {
+  const uint8_t* src = nullptr;
+  std::function<void(Profiler*)> convert;
+  GraphKey key = {};
+};
+// What runs on those frames: detect + NMS (plain_front) or view gather + detect + frame NMS (view_front), writing records and
+// counts; with_rois: also the ROI list the classifier stage consumes.  roi_geom: the geometry the ROI stage reads the frames
+// with (nullptr: d_geom).  A front refers to the geometry or layout it was made from: it lives no longer than they do.
+struct Front {
+  std::function<void(Profiler*, lp_det* dets, int* counts, int min_area, bool with_rois)> run;
+  const ImgGeom* roi_geom = nullptr;
+};
+Front plain_front(lp_handle* h, const uint8_t* src, const std::vector<ImgGeom>& geoms, int B, float conf, float iou);
+// The device pass of every lp_run_*_device entry point, called behind the entry point's last check and upload: one captured
+// step (conversion, front, and ROI resize + classifier when one is loaded) under the key {kind, the call, the source's
+// fields}.  before: enqueued in front of the step, outside the capture, inside the profile (the focus plan launch).
+void run_device_pass(lp_handle* h, GraphKind kind, int B, float conf, float iou, int min_area, void* dev_dets, void* dev_counts,
+                     const FrameSource& frames, const Front& front, const std::function<void(Profiler*)>& before = nullptr);
+
 // ---- input pixel format (pixfmt.cpp) -------------------------------------------------------------------------------------------
 // the layout of one H x W frame with the zeros resolved
 struct FrameLayout { int pitch; int64_t uv_off, frame_bytes, stride; };
@@ -329,17 +368,19 @@ CscPlan plan_csc(lp_handle* h, std::vector<CscFrame>& tab, const void* src);
 void enqueue_csc(lp_handle* h, const uint8_t* src, const CscPlan& p, Profiler* prof);
 void key_format(const lp_handle* h, const CscPlan& p, GraphKey& k);
 CscPlan device_csc(lp_handle* h, const void* dev_imgs, int B, int H, int W, std::vector<ImgGeom>& g);
+// the frames of a lp_*_device call as a frame source: packed BGR in place, NV12 converted into d_src under csc
+FrameSource device_frames(lp_handle* h, const void* dev_imgs, const CscPlan& csc);
 
 // ---- host frames (pipeline.cpp) ------------------------------------------------------------------------------------------------
 // upload B host images of individual sizes into d_src (NV12 frames: into d_raw, with the plan of their conversion into d_src
 // in *csc); returns their geometry
 std::vector<ImgGeom> upload_images(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, CscPlan* csc = nullptr);
-// The staged host pass of lp_run_batch, lp_run_tiled and lp_run_views: `front` (colour conversion + detect + NMS of either kind), the ROI
-// resize reading roi_geom (nullptr: d_geom) and the classifier as three captured pieces with the stage events between them,
-// then records, counts and timing back on the host.  An overflow of max_rois is reported last: the records are delivered.
+// The staged host pass of lp_run_batch, lp_run_tiled, lp_run_views and lp_run_focus on the frames upload_images left: the colour
+// conversion under csc + `front`, the ROI resize and the classifier as three captured pieces (front_kind and the two
+// enumerators behind it) with the stage events between them, then records, counts and timing back on the host.  An overflow
+// of max_rois is reported last: the records are delivered.
 void run_host_pass(lp_handle* h, int B, float conf, float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg,
-                   lp_timing* timing, const CscPlan& csc, GraphKind front_kind, GraphKind roi_kind, GraphKind cls_kind,
-                   const std::function<void(Profiler*)>& front, const ImgGeom* roi_geom);
+                   lp_timing* timing, const CscPlan& csc, GraphKind front_kind, const Front& front);
 // R crops as R "images" whose single ROI is the whole crop (lp_classify, lp_test_roi_resize): geometry at 16-byte aligned
 // offsets, one rectangle each, img[i] = i, slot 0; total = bytes of the packed crops
 struct CropRois {
@@ -384,5 +425,18 @@ void enqueue_view_gather(const uint8_t* src, const ImgGeom* d_geom, const ViewWi
 // candidates are dropped between the detector and the view sort
 void enqueue_view_front(lp_handle* h, const uint8_t* src, const ViewLayout& lay, int F, float conf, float iou, int min_area, lp_det* dets,
                         int* counts, bool with_rois, Profiler* prof, const int* dead = nullptr);
+Front view_front(lp_handle* h, const uint8_t* src, const ViewLayout& lay, int F, float conf, float iou, const int* dead = nullptr);
+// What a view entry point brings along: its frames' geometry -> the call's layout (its own argument checks included).
+// Everything is validated in one order: the shared arguments, the layout against every frame, the NV12 format; only then is
+// anything uploaded or allocated.
+using LayoutFn = std::function<ViewLayout(const std::vector<ImgGeom>&)>;
+// Host frames of a view call: the layout dry-run on geometry without offsets (upload_images assigns them), the NV12 format
+// check, the upload into d_src (fg, csc), and the layout of the uploaded frames.
+ViewLayout upload_view_frames(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, const LayoutFn& layout_of,
+                              std::vector<ImgGeom>& fg, CscPlan& csc);
+// Device frames of a view call: B packed H x W frames; NV12 frames get their conversion plan (device_csc checks the format
+// before it sizes d_src) and the layout is built again on the converted frames' 16-byte aligned offsets.
+ViewLayout device_view_frames(lp_handle* h, const void* dev_imgs, int B, int H, int W, const LayoutFn& layout_of, std::vector<ImgGeom>& fg,
+                              CscPlan& csc);
 
 }  // namespace lp

@@ -75,10 +75,7 @@ static void check_inventory_call(lp_handle* h, int B, const int* stream_ids, int
   const Inventory& v = inventory_of(h);
   const Tracker& t = *h->trk;
   LP_CHECK(B >= 1 && B <= t.max_batch, LP_ERR_ARG, "batch %d outside 1..%d", B, t.max_batch);
-  if (stream_ids)
-    for (int b = 0; b < B; ++b)
-      LP_CHECK(stream_ids[b] >= 0 && stream_ids[b] < t.cfg.n_streams, LP_ERR_ARG, "stream_ids[%d] = %d outside 0..%d", b, stream_ids[b],
-               t.cfg.n_streams - 1);
+  check_stream_ids(t, B, stream_ids);
   LP_CHECK(crops == 0 || crops == 1, LP_ERR_ARG, "crops %d is not 0 or 1", crops);
   LP_CHECK(!crops || v.cfg.keep_crops, LP_ERR_ARG, "crops = 1 on an inventory created with keep_crops = 0");
   LP_CHECK(!crops || !v.evid || (h->last_frames && h->last_fgeom && h->last_nframes >= B), LP_ERR_STATE,
@@ -94,12 +91,10 @@ static void enqueue_inventory(lp_handle* h, const void* dev_dets, const void* de
   LP_CHECK(((uintptr_t)dev_dets | (uintptr_t)dev_tracks) % 16 == 0 && (uintptr_t)dev_counts % 4 == 0, LP_ERR_ARG,
            "the record buffers must be 16-byte aligned");
   LP_HIP(hipSetDevice(h->cfg.device));
-  const int k = v.next;
-  if (v.busy[k]) LP_HIP(hipEventSynchronize(v.ev[k]));
-  int* slot = v.plan_host + (size_t)k * v.slot_ints;
-  const int n_jobs = plan_stream_jobs(slot, t.max_batch, B, stream_ids);   // the tracker's plan
-  int* dslot = v.plan_dev.as<int>() + (size_t)k * v.slot_ints;
-  LP_HIP(hipMemcpyAsync(dslot, slot, v.slot_ints * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  const PlanRing::Slot rs = v.ring.acquire();
+  const int n_jobs = plan_stream_jobs(static_cast<int*>(rs.host), t.max_batch, B, stream_ids);   // the tracker's plan
+  const int* dslot = static_cast<const int*>(rs.dev);
+  v.ring.upload(rs, v.ring.slot_bytes, h->stream);
   InvArgs a = base_args(h);
   a.dets = static_cast<const lp_det*>(dev_dets); a.counts = static_cast<const int*>(dev_counts); a.tracks = static_cast<const TrackRec*>(dev_tracks);
   a.jobs = reinterpret_cast<const TrackJob*>(dslot); a.frames = dslot + (size_t)t.max_batch * (sizeof(TrackJob) / sizeof(int));
@@ -115,9 +110,7 @@ static void enqueue_inventory(lp_handle* h, const void* dev_dets, const void* de
   } else {
     launch_inventory(a, n_jobs, h->stream);
   }
-  LP_HIP(hipEventRecord(v.ev[k], h->stream));
-  v.busy[k] = true;
-  v.next = (k + 1) % Inventory::RING;
+  v.ring.release(rs, h->stream);
 }
 
 // the first n entries of the log (signs, and their crops when wanted) after a synchronise
@@ -206,10 +199,7 @@ int lp_inventory_create(lp_handle* h, const lp_inventory_config* cfg) {
     v->gallery.alloc(NS * T * v->crop_bytes, false);
     v->roi_of.alloc((size_t)t.max_batch * t.max_det * sizeof(int));
   }
-  v->slot_ints = (size_t)t.max_batch * (sizeof(TrackJob) / sizeof(int) + 1);
-  v->plan_dev.alloc(Inventory::RING * v->slot_ints * sizeof(int));
-  LP_HIP(hipHostMalloc(reinterpret_cast<void**>(&v->plan_host), Inventory::RING * v->slot_ints * sizeof(int), hipHostMallocDefault));
-  for (auto& e : v->ev) LP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  v->ring.create((size_t)t.max_batch * (sizeof(TrackJob) + sizeof(int)));
   t.inv = std::move(v);
   LP_API_END
 }

@@ -1,6 +1,5 @@
 // The pipeline pieces the entry points share, the host upload path, the staged host pass, and the untiled entry points.
 #include <cmath>
-#include <cstdlib>
 
 #include "handle.h"
 
@@ -73,8 +72,7 @@ void enqueue_detect(lp_handle* h, const uint8_t* src, const std::vector<ImgGeom>
 // Diagnostic only (tools/marginal_cost.sh): LITEPI_SKIP_STAGE=nms|roi|cls leaves that stage out of every pass after the handle's
 // first (its outputs stay in the handle's buffers): the marginal cost of the stage in a pipelined step.  Results are stale.
 static bool skip_stage(const lp_handle* h, const char* name, const Profiler* prof) {
-  static const char* s = getenv("LITEPI_SKIP_STAGE");
-  return s && !prof && h->graph_clock > 1 && strcmp(s, name) == 0;
+  return !prof && h->graph_clock > 1 && h->opt.skip_stage == name;
 }
 
 // NMS + ROI rectangles; with_rois: also the batch-wide ROI list the classifier stage consumes
@@ -124,8 +122,7 @@ void enqueue_classify(lp_handle* h, const uint8_t* src, int B, lp_det* dets, flo
 // seen -- that call also performs every one-time set-up (LDS attributes, lazy packing) --, capture it into a hipGraph the
 // second time, replay the graph from then on.
 void run_or_capture(lp_handle* h, const GraphKey& key, bool allow, const std::function<void()>& enqueue) {
-  static const bool disabled = getenv("LITEPI_NO_GRAPH") != nullptr;
-  if (disabled || !allow) { ++h->n_eager; enqueue(); return; }
+  if (h->opt.no_graph || !allow) { ++h->n_eager; enqueue(); return; }
   GraphEntry* e = nullptr;
   for (auto& g : h->graphs)
     if (g.key == key) { e = &g; break; }
@@ -205,7 +202,7 @@ std::vector<ImgGeom> upload_images(lp_handle* h, const uint8_t* const* imgs, con
     *csc = plan_csc(h, tab, dst);
   }
   // small uploads (a single frame: the batch-1 latency path) go straight from the caller's memory
-  static const int n_threads = getenv("LITEPI_UPLOAD_THREADS") ? atoi(getenv("LITEPI_UPLOAD_THREADS")) : 8;
+  const int n_threads = h->opt.upload_threads;
   if (n_threads <= 0 || B < 4 || total < ((size_t)4 << 20)) {
     for (int i = 0; i < B; ++i)
       LP_HIP(hipMemcpyAsync(dst + off[i], imgs[i], nb[i], hipMemcpyHostToDevice, h->stream));
@@ -222,7 +219,7 @@ std::vector<ImgGeom> upload_images(lp_handle* h, const uint8_t* const* imgs, con
   // into slices so that every worker has a share
   std::vector<CopyPool::Job> jobs;
   // (the first groups are small: nothing overlaps the first group's copy, the link idles until it is staged)
-  static const size_t group_mb = getenv("LITEPI_UPLOAD_GROUP_MB") ? (size_t)atol(getenv("LITEPI_UPLOAD_GROUP_MB")) : 10;
+  const size_t group_mb = h->opt.upload_group_mb;
   const size_t slice = (size_t)1 << 20;
   int i0 = 0, ngroup = 0;
   while (i0 < B) {
@@ -244,20 +241,50 @@ std::vector<ImgGeom> upload_images(lp_handle* h, const uint8_t* const* imgs, con
   return g;
 }
 
+Front plain_front(lp_handle* h, const uint8_t* src, const std::vector<ImgGeom>& geoms, int B, float conf, float iou) {
+  Front f;
+  f.run = [=, &geoms](Profiler* prof, lp_det* dets, int* counts, int min_area, bool with_rois) {
+    enqueue_detect(h, src, geoms, B, conf, nullptr, prof);
+    enqueue_nms(h, B, iou, min_area, dets, counts, with_rois, prof);
+  };
+  return f;
+}
+
+void run_device_pass(lp_handle* h, GraphKind kind, int B, float conf, float iou, int min_area, void* dev_dets, void* dev_counts,
+                     const FrameSource& frames, const Front& front, const std::function<void(Profiler*)>& before) {
+  Profiler* prof = begin_profile(h);
+  if (before) before(prof);
+  const bool classify = h->cls && h->cls->loaded();
+  lp_det* dets = static_cast<lp_det*>(dev_dets);
+  h->remember_frames(frames.src, front.roi_geom ? front.roi_geom : h->d_geom.as<ImgGeom>(), B);
+  GraphKey key = frames.key;
+  key.kind = kind; key.B = B; key.geom_ver = h->geom_ver; key.min_area = min_area; key.p1 = dev_dets; key.p2 = dev_counts;
+  key.conf = conf; key.iou = iou;
+  run_or_capture(h, key, prof == nullptr, [&]() {
+    if (frames.convert) frames.convert(prof);
+    front.run(prof, dets, static_cast<int*>(dev_counts), classify ? min_area : -1, classify);
+    if (classify) enqueue_classify(h, frames.src, B, dets, nullptr, nullptr, nullptr, prof, 0, front.roi_geom);
+  });
+  if (prof) prof->enabled = false;  // records are collected by lp_profile_read after the caller synchronises
+}
+
 void run_host_pass(lp_handle* h, int B, float conf, float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg,
-                   lp_timing* timing, const CscPlan& csc, GraphKind front_kind, GraphKind roi_kind, GraphKind cls_kind,
-                   const std::function<void(Profiler*)>& front, const ImgGeom* roi_geom) {
+                   lp_timing* timing, const CscPlan& csc, GraphKind front_kind, const Front& front) {
   Profiler* prof = begin_profile(h);
   const uint8_t* src = h->d_src.as<uint8_t>();
   lp_det* d_dets = h->d_dets.as<lp_det>();
+  const ImgGeom* roi_geom = front.roi_geom;
   h->remember_frames(src, roi_geom ? roi_geom : h->d_geom.as<ImgGeom>(), B);
   // three captured pieces with the stage-boundary events between them (PipelineMetrics wants detection, ROI extraction and
   // classification times separately, e2e.py:452-499); the colour conversion of NV12 frames is booked under detection
   GraphKey k1{front_kind, B, h->geom_ver, min_area, h->d_src.p, h->d_dets.p, h->d_counts.p, conf, iou}, k2 = k1, k3 = k1;
-  k2.kind = roi_kind; k3.kind = cls_kind;
+  k2.kind = GraphKind(front_kind + 1); k3.kind = GraphKind(front_kind + 2);
   key_format(h, csc, k1);   // the conversion is part of the front only
   LP_HIP(hipEventRecord(h->ev[0], h->stream));
-  run_or_capture(h, k1, prof == nullptr, [&]() { front(prof); });
+  run_or_capture(h, k1, prof == nullptr, [&]() {
+    if (h->nv12()) enqueue_csc(h, h->d_raw.as<uint8_t>(), csc, prof);
+    front.run(prof, d_dets, h->d_counts.as<int>(), min_area, true);
+  });
   LP_HIP(hipEventRecord(h->ev[2], h->stream));
   run_or_capture(h, k2, prof == nullptr, [&]() { enqueue_classify(h, src, B, d_dets, nullptr, nullptr, nullptr, prof, 1, roi_geom); });
   LP_HIP(hipEventRecord(h->ev[1], h->stream));
@@ -364,16 +391,11 @@ int lp_run_batch(lp_handle* h, const uint8_t* const* imgs, const int* hs, const 
   LP_API_BEGIN
   check_run_args(h, imgs && hs && ws && dets && counts, B, true, min_area);
   LP_HIP(hipSetDevice(h->cfg.device));
-  const bool nv = h->nv12();
   CscPlan csc;
   std::vector<ImgGeom> g = upload_images(h, imgs, hs, ws, B, &csc);
   h->upload_geom(g);
-  run_host_pass(h, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, csc, GK_BATCH_FRONT, GK_BATCH_ROI, GK_BATCH_CLS,
-                [&](Profiler* prof) {
-                  if (nv) enqueue_csc(h, h->d_raw.as<uint8_t>(), csc, prof);
-                  enqueue_detect(h, h->d_src.as<uint8_t>(), g, B, conf, nullptr, prof);
-                  enqueue_nms(h, B, iou, min_area, h->d_dets.as<lp_det>(), h->d_counts.as<int>(), true, prof);
-                }, nullptr);
+  run_host_pass(h, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, csc, GK_BATCH_FRONT,
+                plain_front(h, h->d_src.as<uint8_t>(), g, B, conf, iou));
   LP_API_END
 }
 
@@ -384,25 +406,13 @@ int lp_run_batch_device(lp_handle* h, const void* dev_imgs, int B, int H, int W,
   LP_CHECK(H > 0 && W > 0, LP_ERR_ARG, "frames of %dx%d", W, H);
   LP_HIP(hipSetDevice(h->cfg.device));
   std::vector<ImgGeom> g(B);
-  const bool nv = h->nv12();
   CscPlan csc;
-  if (nv) csc = device_csc(h, dev_imgs, B, H, W, g);
+  if (h->nv12()) csc = device_csc(h, dev_imgs, B, H, W, g);
   else
     for (int i = 0; i < B; ++i) g[i] = make_geom(H, W, h->det_h(), h->det_w(), (long)i * H * W * 3);
   h->upload_geom(g);
-  Profiler* prof = begin_profile(h);
-  const uint8_t* src = nv ? h->d_src.as<uint8_t>() : static_cast<const uint8_t*>(dev_imgs);
-  const bool classify = h->cls && h->cls->loaded();
-  h->remember_frames(src, h->d_geom.as<ImgGeom>(), B);
-  GraphKey key{GK_BATCH_DEVICE, B, h->geom_ver, min_area, dev_imgs, dev_dets, dev_counts, conf, iou};
-  key_format(h, csc, key);
-  run_or_capture(h, key, prof == nullptr, [&]() {
-    if (nv) enqueue_csc(h, static_cast<const uint8_t*>(dev_imgs), csc, prof);
-    enqueue_detect(h, src, g, B, conf, nullptr, prof);
-    enqueue_nms(h, B, iou, classify ? min_area : -1, static_cast<lp_det*>(dev_dets), static_cast<int*>(dev_counts), classify, prof);
-    if (classify) enqueue_classify(h, src, B, static_cast<lp_det*>(dev_dets), nullptr, nullptr, nullptr, prof);
-  });
-  if (prof) prof->enabled = false;  // records are collected by lp_profile_read after the caller synchronises
+  const FrameSource frames = device_frames(h, dev_imgs, csc);
+  run_device_pass(h, GK_BATCH_DEVICE, B, conf, iou, min_area, dev_dets, dev_counts, frames, plain_front(h, frames.src, g, B, conf, iou));
   LP_API_END
 }
 

@@ -106,6 +106,16 @@ CscPlan device_csc(lp_handle* h, const void* dev_imgs, int B, int H, int W, std:
   return plan_csc(h, tab, dev_imgs);
 }
 
+FrameSource device_frames(lp_handle* h, const void* dev_imgs, const CscPlan& csc) {
+  const uint8_t* imgs = static_cast<const uint8_t*>(dev_imgs);
+  FrameSource f;
+  f.src = h->nv12() ? h->d_src.as<uint8_t>() : imgs;
+  if (h->nv12()) f.convert = [=](Profiler* prof) { enqueue_csc(h, imgs, csc, prof); };
+  f.key.p0 = dev_imgs;
+  key_format(h, csc, f.key);
+  return f;
+}
+
 }  // namespace lp
 
 using namespace lp;

@@ -1,5 +1,6 @@
-// Decoder surfaces (include/litepi.h lp_surface): the argument rules, the converter's per-frame record and the
-// slot policy of the pinned ring.  Host-pure (no HIP headers): tests/native/surface_plan_check.cpp builds on this alone.
+// Decoder surfaces (include/litepi.h lp_surface): the argument rules and the converter's per-frame record
+// (the slot policy of its pinned ring is ring_slots.h).  Host-pure (no HIP headers): tests/native/surface_plan_check.cpp builds
+// on the two headers alone.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -73,22 +74,5 @@ inline int fill_surface_table(const lp_surface_format& fmt, const lp_surface* s,
   }
   return max_blocks;
 }
-
-// Slot policy of the pinned ring: a call takes the next slot round-robin; the slot's previous copy has to be waited for only
-// if the slot is still marked busy, i.e. once the ring has wrapped.  take() returns the slot and whether its event must be
-// waited on before the slot is written; the caller marks it busy again behind the new copy (mark()).
-template <int RING>
-struct SurfaceSlots {
-  bool busy[RING] = {};
-  int next = 0;
-  int take(bool* wait) {
-    const int slot = next;
-    next = (next + 1) % RING;
-    *wait = busy[slot];
-    busy[slot] = false;
-    return slot;
-  }
-  void mark(int slot) { busy[slot] = true; }
-};
 
 }  // namespace lp

@@ -1,5 +1,6 @@
-// Decoder surfaces in place (include/litepi.h lp_surface): the pinned -> device table ring, the two entry points
-// and the converter's test hook.  The argument rules, the table's records and the ring's slot policy are surface_plan.h.
+// Decoder surfaces in place (include/litepi.h lp_surface): the staging of a call's table through the handle's plan
+// ring (handle.h: PlanRing, one device table), the two entry points and the converter's test hook.  The argument rules and the
+// table's records are surface_plan.h.
 // A surface's addresses and pitches reach the converter through one device table at a fixed address, rewritten in stream order
 // in front of every step: they are data, not part of a captured step's identity, so surfaces that rotate through a decoder
 // pool replay one step and never synchronise the host.
@@ -20,18 +21,13 @@ struct SurfPlan {
 // step.  Called after every check and after ensure_src: the destination address is final.
 SurfPlan stage_surfaces(lp_handle* h, const lp_surface_format& fmt, const lp_surface* s, int B, const std::vector<ImgGeom>& g) {
   if (!h->surf) {
-    std::unique_ptr<SurfaceRing> ring(new SurfaceRing);
-    ring->table.alloc((size_t)h->cfg.max_batch * sizeof(SurfFrame));
-    LP_HIP(hipHostMalloc(reinterpret_cast<void**>(&ring->host), (size_t)SurfaceRing::RING * h->cfg.max_batch * sizeof(SurfFrame),
-                         hipHostMallocDefault));
-    for (auto& e : ring->ev) LP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    std::unique_ptr<PlanRing> ring(new PlanRing);
+    ring->create((size_t)h->cfg.max_batch * sizeof(SurfFrame), 1);
     h->surf = std::move(ring);
   }
-  SurfaceRing& r = *h->surf;
-  bool wait = false;
-  const int slot = r.slots.take(&wait);
-  if (wait) LP_HIP(hipEventSynchronize(r.ev[slot]));   // the ring wrapped: the copy that read this slot RING calls ago has long gone
-  SurfFrame* rec = r.host + (size_t)slot * h->cfg.max_batch;
+  PlanRing& r = *h->surf;
+  const PlanRing::Slot slot = r.acquire();   // waits only once the ring has wrapped: the copy that read the slot has long gone
+  SurfFrame* rec = static_cast<SurfFrame*>(slot.host);
   std::vector<long> off(B);
   SurfPlan p;
   p.B = B; p.matrix = fmt.matrix; p.p010 = fmt.pixfmt == LP_SURF_P010;
@@ -40,15 +36,14 @@ SurfPlan stage_surfaces(lp_handle* h, const lp_surface_format& fmt, const lp_sur
     p.bytes += (double)s[i].height * s[i].width * (1.5 * surface_sample_bytes(fmt.pixfmt) + 3.0);
   }
   p.max_blocks = fill_surface_table(fmt, s, B, h->d_src.p, off.data(), rec);
-  LP_HIP(hipMemcpyAsync(r.table.p, rec, (size_t)B * sizeof(SurfFrame), hipMemcpyHostToDevice, h->stream));
-  LP_HIP(hipEventRecord(r.ev[slot], h->stream));
-  r.slots.mark(slot);
+  r.upload(slot, (size_t)B * sizeof(SurfFrame), h->stream);
+  r.release(slot, h->stream);
   return p;
 }
 
 void enqueue_surfaces(lp_handle* h, const SurfPlan& p, Profiler* prof) {
   if (prof) prof->begin(h->stream);
-  launch_surfaces_to_bgr(h->surf->table.as<SurfFrame>(), h->d_src.as<uint8_t>(), p.B, p.max_blocks, p.p010, p.matrix, h->stream);
+  launch_surfaces_to_bgr(h->surf->dev.as<SurfFrame>(), h->d_src.as<uint8_t>(), p.B, p.max_blocks, p.p010, p.matrix, h->stream);
   if (prof) prof->end(h->stream, p.p010 ? "surfaces_to_bgr_p010" : "surfaces_to_bgr", "csc", 0.0, p.bytes);
 }
 
@@ -62,13 +57,15 @@ size_t surface_geometry(const lp_handle* h, const lp_surface* s, int B, std::vec
   return total;
 }
 
-GraphKey surface_key(const lp_handle* h, GraphKind kind, const lp_surface_format& fmt, int B, int min_area, void* dev_dets, void* dev_counts,
-                     float conf, float iou) {
-  // no surface address, pitch or table generation: the table's content is data.  Sizes are in geom_ver (upload_geom), the
-  // destination's address too (ensure_src).
-  GraphKey key{kind, B, h->geom_ver, min_area, nullptr, dev_dets, dev_counts, conf, iou};
-  key.pixfmt = fmt.pixfmt; key.matrix = fmt.matrix;
-  return key;
+// the staged surfaces as a frame source: converted into d_src by the step's first launch.  Its key fields hold no surface
+// address, pitch or table generation (p0 stays null): the table's content is data.  Sizes are in geom_ver (upload_geom), the
+// destination's address too (ensure_src).
+FrameSource surface_frames(lp_handle* h, const lp_surface_format& fmt, const SurfPlan& plan) {
+  FrameSource f;
+  f.src = h->d_src.as<uint8_t>();
+  f.convert = [=](Profiler* prof) { enqueue_surfaces(h, plan, prof); };
+  f.key.pixfmt = fmt.pixfmt; f.key.matrix = fmt.matrix;
+  return f;
 }
 
 }  // namespace
@@ -93,19 +90,8 @@ int lp_run_surfaces_device(lp_handle* h, const lp_surface_format* fmt, const lp_
   std::vector<ImgGeom> g(B);
   h->ensure_src(surface_geometry(h, surfaces, B, g));
   h->upload_geom(g);
-  const SurfPlan plan = stage_surfaces(h, *fmt, surfaces, B, g);
-  Profiler* prof = begin_profile(h);
-  const uint8_t* src = h->d_src.as<uint8_t>();
-  const bool classify = h->cls && h->cls->loaded();
-  h->remember_frames(src, h->d_geom.as<ImgGeom>(), B);
-  const GraphKey key = surface_key(h, GK_SURFACES_DEVICE, *fmt, B, min_area, dev_dets, dev_counts, conf, iou);
-  run_or_capture(h, key, prof == nullptr, [&]() {
-    enqueue_surfaces(h, plan, prof);
-    enqueue_detect(h, src, g, B, conf, nullptr, prof);
-    enqueue_nms(h, B, iou, classify ? min_area : -1, static_cast<lp_det*>(dev_dets), static_cast<int*>(dev_counts), classify, prof);
-    if (classify) enqueue_classify(h, src, B, static_cast<lp_det*>(dev_dets), nullptr, nullptr, nullptr, prof);
-  });
-  if (prof) prof->enabled = false;  // records are collected by lp_profile_read after the caller synchronises
+  const FrameSource frames = surface_frames(h, *fmt, stage_surfaces(h, *fmt, surfaces, B, g));
+  run_device_pass(h, GK_SURFACES_DEVICE, B, conf, iou, min_area, dev_dets, dev_counts, frames, plain_front(h, frames.src, g, B, conf, iou));
   LP_API_END
 }
 
@@ -121,19 +107,9 @@ int lp_run_views_surfaces_device(lp_handle* h, const lp_surface_format* fmt, con
   const ViewLayout lay = view_layout(h, fg, listed_views(h, views, n_views, fg));   // validated before anything is sized or enqueued
   h->ensure_src(total);
   upload_tiles(h, fg, lay);
-  const SurfPlan plan = stage_surfaces(h, *fmt, surfaces, B, fg);
-  Profiler* prof = begin_profile(h);
-  const uint8_t* src = h->d_src.as<uint8_t>();
-  const bool classify = h->cls && h->cls->loaded();
-  h->remember_frames(src, h->d_fgeom.as<ImgGeom>(), B);
-  const GraphKey key = surface_key(h, GK_VIEWS_SURFACES_DEVICE, *fmt, B, min_area, dev_dets, dev_counts, conf, iou);
-  run_or_capture(h, key, prof == nullptr, [&]() {
-    enqueue_surfaces(h, plan, prof);
-    enqueue_view_front(h, src, lay, B, conf, iou, classify ? min_area : -1, static_cast<lp_det*>(dev_dets), static_cast<int*>(dev_counts),
-                       classify, prof);
-    if (classify) enqueue_classify(h, src, B, static_cast<lp_det*>(dev_dets), nullptr, nullptr, nullptr, prof, 0, h->d_fgeom.as<ImgGeom>());
-  });
-  if (prof) prof->enabled = false;  // records are collected by lp_profile_read after the caller synchronises
+  const FrameSource frames = surface_frames(h, *fmt, stage_surfaces(h, *fmt, surfaces, B, fg));
+  run_device_pass(h, GK_VIEWS_SURFACES_DEVICE, B, conf, iou, min_area, dev_dets, dev_counts, frames,
+                  view_front(h, frames.src, lay, B, conf, iou));
   LP_API_END
 }
 

@@ -61,11 +61,7 @@ int lp_tracker_create(lp_handle* h, const lp_track_config* cfg) {
   t->heads.alloc(S * sizeof(TrackHead));
   LP_HIP(hipMemcpy(t->heads.p, heads.data(), S * sizeof(TrackHead), hipMemcpyHostToDevice));
   if (t->max_det > LP_TRACK_KEY_LDS) t->scratch.alloc((size_t)t->max_batch * 2 * t->max_det * sizeof(unsigned), false);
-  // a ring slot: up to max_batch jobs, then the max_batch frame indices
-  t->slot_ints = (size_t)t->max_batch * (sizeof(TrackJob) / sizeof(int) + 1);
-  t->plan_dev.alloc(Tracker::RING * t->slot_ints * sizeof(int));
-  LP_HIP(hipHostMalloc(reinterpret_cast<void**>(&t->plan_host), Tracker::RING * t->slot_ints * sizeof(int), hipHostMallocDefault));
-  for (auto& e : t->ev) LP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  t->ring.create((size_t)t->max_batch * (sizeof(TrackJob) + sizeof(int)));
   h->trk = std::move(t);
   LP_API_END
 }
@@ -86,10 +82,7 @@ static void check_track_call(lp_handle* h, int B, const int* stream_ids) {
   LP_CHECK(h->trk, LP_ERR_STATE, "no tracker: call lp_tracker_create first");
   const Tracker& t = *h->trk;
   LP_CHECK(B >= 1 && B <= t.max_batch, LP_ERR_ARG, "batch %d outside 1..%d", B, t.max_batch);
-  if (stream_ids)
-    for (int b = 0; b < B; ++b)
-      LP_CHECK(stream_ids[b] >= 0 && stream_ids[b] < t.cfg.n_streams, LP_ERR_ARG, "stream_ids[%d] = %d outside 0..%d", b, stream_ids[b],
-               t.cfg.n_streams - 1);
+  check_stream_ids(t, B, stream_ids);
 }
 
 static void enqueue_track(lp_handle* h, const void* dev_dets, const void* dev_counts, int B, const int* stream_ids, void* dev_tracks) {
@@ -98,12 +91,10 @@ static void enqueue_track(lp_handle* h, const void* dev_dets, const void* dev_co
   LP_CHECK(((uintptr_t)dev_dets | (uintptr_t)dev_tracks) % 16 == 0 && (uintptr_t)dev_counts % 4 == 0, LP_ERR_ARG,
            "the record buffers must be 16-byte aligned");
   LP_HIP(hipSetDevice(h->cfg.device));
-  const int k = t.next;
-  if (t.busy[k]) LP_HIP(hipEventSynchronize(t.ev[k]));
-  int* slot = t.plan_host + (size_t)k * t.slot_ints;
-  const int n_jobs = plan_stream_jobs(slot, t.max_batch, B, stream_ids);
-  int* dslot = t.plan_dev.as<int>() + (size_t)k * t.slot_ints;
-  LP_HIP(hipMemcpyAsync(dslot, slot, t.slot_ints * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  const PlanRing::Slot rs = t.ring.acquire();
+  const int n_jobs = plan_stream_jobs(static_cast<int*>(rs.host), t.max_batch, B, stream_ids);
+  const int* dslot = static_cast<const int*>(rs.dev);
+  t.ring.upload(rs, t.ring.slot_bytes, h->stream);
   TrackArgs a;
   a.dets = static_cast<const lp_det*>(dev_dets); a.counts = static_cast<const int*>(dev_counts); a.out = static_cast<TrackRec*>(dev_tracks);
   a.jobs = reinterpret_cast<const TrackJob*>(dslot); a.frames = dslot + (size_t)t.max_batch * (sizeof(TrackJob) / sizeof(int));
@@ -111,9 +102,7 @@ static void enqueue_track(lp_handle* h, const void* dev_dets, const void* dev_co
   a.max_det = t.max_det; a.T = t.cfg.max_tracks; a.nc = t.nc; a.iou_match = t.cfg.iou_match; a.max_age = t.cfg.max_age;
   a.min_hits = t.cfg.min_hits; a.new_conf = t.cfg.new_conf; a.decay = t.cfg.vote_decay; a.class_gate = t.cfg.class_gate; a.motion = t.cfg.motion;
   launch_track(a, n_jobs, h->stream);
-  LP_HIP(hipEventRecord(t.ev[k], h->stream));
-  t.busy[k] = true;
-  t.next = (k + 1) % Tracker::RING;
+  t.ring.release(rs, h->stream);
 }
 
 int lp_track_device(lp_handle* h, const void* dev_dets, const void* dev_counts, int B, const int* stream_ids, void* dev_tracks) {

@@ -41,6 +41,17 @@ static void write_views(const std::vector<std::array<int, 4>>& v, int* n_views, 
     for (int k = 0; k < 4; ++k) views[4 * i + k] = v[i][k];
 }
 
+// the optional outputs of lp_view_geometry and lp_letterbox_geometry
+static void write_geometry(const ImgGeom& g, float* ratio, float* pad_w, float* pad_h, int* new_w, int* new_h, int* top, int* left) {
+  if (ratio) *ratio = g.ratio;
+  if (pad_w) *pad_w = g.pad_w;
+  if (pad_h) *pad_h = g.pad_h;
+  if (new_w) *new_w = g.new_w;
+  if (new_h) *new_h = g.new_h;
+  if (top) *top = g.top;
+  if (left) *left = g.left;
+}
+
 void check_tiling(const lp_tiling* t, int S) {
   LP_CHECK(t, LP_ERR_ARG, "null tiling");
   LP_CHECK(t->overlap >= 0 && t->overlap < S, LP_ERR_ARG, "tiling overlap %d outside 0..%d", t->overlap, S - 1);
@@ -241,71 +252,68 @@ void enqueue_view_front(lp_handle* h, const uint8_t* src, const ViewLayout& lay,
   enqueue_view_detect(h, lay, F, conf, iou, min_area, dets, counts, with_rois, prof, dead);
 }
 
-// ---- the two fronts ------------------------------------------------------------------------------------------------------------
-// What an entry point brings along: its frames' geometry -> the call's layout (its own argument checks included).  Everything
-// is validated in one order: the shared arguments, the layout against every frame, the NV12 format; only then is anything
-// uploaded or allocated.
-using LayoutFn = std::function<ViewLayout(const std::vector<ImgGeom>&)>;
+Front view_front(lp_handle* h, const uint8_t* src, const ViewLayout& lay, int F, float conf, float iou, const int* dead) {
+  Front f;
+  f.run = [=, &lay](Profiler* prof, lp_det* dets, int* counts, int min_area, bool with_rois) {
+    enqueue_view_front(h, src, lay, F, conf, iou, min_area, dets, counts, with_rois, prof, dead);
+  };
+  f.roi_geom = h->d_fgeom.as<ImgGeom>();
+  return f;
+}
 
-// the staged host call of lp_run_tiled and lp_run_views
-static void run_views_host(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, float conf, float iou, int min_area,
-                           lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing, GraphKind front_kind,
-                           GraphKind roi_kind, GraphKind cls_kind, const LayoutFn& layout_of) {
-  check_run_args(h, imgs && hs && ws && dets && counts, B, true, min_area);
-  for (int i = 0; i < B; ++i) LP_CHECK(hs[i] > 0 && ws[i] > 0, LP_ERR_ARG, "frame %d is empty", i);
-  LP_HIP(hipSetDevice(h->cfg.device));
-  std::vector<ImgGeom> fg(B);
+// ---- a view call's frames ------------------------------------------------------------------------------------------------------
+ViewLayout upload_view_frames(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, const LayoutFn& layout_of,
+                              std::vector<ImgGeom>& fg, CscPlan& csc) {
+  fg.resize(B);
   for (int i = 0; i < B; ++i) fg[i] = make_geom(hs[i], ws[i], h->det_h(), h->det_w(), 0);
-  // The layout is built twice, here and behind the upload: this one validates the call before anything is uploaded, from
-  // geometry without the frames' offsets in d_src, which upload_images assigns.
-  (void)layout_of(fg);
-  const bool nv = h->nv12();
-  if (nv) {   // host frames: frame_stride does not apply
+  (void)layout_of(fg);   // validates the call before anything is uploaded
+  if (h->nv12()) {   // host frames: frame_stride does not apply
     lp_frame_format hf = h->fmt;
     hf.frame_stride = 0;
     for (int i = 0; i < B; ++i) (void)frame_layout(hf, hs[i], ws[i]);
   }
-  CscPlan csc;
   fg = upload_images(h, imgs, hs, ws, B, &csc);
-  const ViewLayout lay = layout_of(fg);
-  upload_tiles(h, fg, lay);
-  run_host_pass(h, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, csc, front_kind, roi_kind, cls_kind,
-                [&](Profiler* prof) {
-                  if (nv) enqueue_csc(h, h->d_raw.as<uint8_t>(), csc, prof);
-                  enqueue_view_front(h, h->d_src.as<uint8_t>(), lay, B, conf, iou, min_area, h->d_dets.as<lp_det>(), h->d_counts.as<int>(), true,
-                                     prof);
-                }, h->d_fgeom.as<ImgGeom>());
+  return layout_of(fg);
 }
 
-// the device call of lp_run_tiled_device and lp_run_views_device
+ViewLayout device_view_frames(lp_handle* h, const void* dev_imgs, int B, int H, int W, const LayoutFn& layout_of, std::vector<ImgGeom>& fg,
+                              CscPlan& csc) {
+  fg.resize(B);
+  for (int i = 0; i < B; ++i) fg[i] = make_geom(H, W, h->det_h(), h->det_w(), (long)i * H * W * 3);
+  ViewLayout lay = layout_of(fg);
+  if (h->nv12()) {
+    csc = device_csc(h, dev_imgs, B, H, W, fg);
+    lay = layout_of(fg);
+  }
+  return lay;
+}
+
+// ---- the two entries of lp_run_tiled* and lp_run_views* -------------------------------------------------------------------------
+static void run_views_host(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, float conf, float iou, int min_area,
+                           lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing, GraphKind front_kind,
+                           const LayoutFn& layout_of) {
+  check_run_args(h, imgs && hs && ws && dets && counts, B, true, min_area);
+  for (int i = 0; i < B; ++i) LP_CHECK(hs[i] > 0 && ws[i] > 0, LP_ERR_ARG, "frame %d is empty", i);
+  LP_HIP(hipSetDevice(h->cfg.device));
+  std::vector<ImgGeom> fg;
+  CscPlan csc;
+  const ViewLayout lay = upload_view_frames(h, imgs, hs, ws, B, layout_of, fg, csc);
+  upload_tiles(h, fg, lay);
+  run_host_pass(h, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, csc, front_kind,
+                view_front(h, h->d_src.as<uint8_t>(), lay, B, conf, iou));
+}
+
 static void run_views_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, float conf, float iou, int min_area, void* dev_dets,
                              void* dev_counts, GraphKind kind, const LayoutFn& layout_of) {
   check_run_args(h, dev_imgs && dev_dets && dev_counts, B, false, min_area);
   LP_CHECK(H > 0 && W > 0, LP_ERR_ARG, "frames of %dx%d", W, H);
   LP_HIP(hipSetDevice(h->cfg.device));
-  std::vector<ImgGeom> fg(B);
-  for (int i = 0; i < B; ++i) fg[i] = make_geom(H, W, h->det_h(), h->det_w(), (long)i * H * W * 3);
-  ViewLayout lay = layout_of(fg);
-  const bool nv = h->nv12();
+  std::vector<ImgGeom> fg;
   CscPlan csc;
-  if (nv) {   // device_csc checks the format before it sizes d_src; the converted frames sit at 16-byte aligned offsets
-    csc = device_csc(h, dev_imgs, B, H, W, fg);
-    lay = layout_of(fg);
-  }
+  const ViewLayout lay = device_view_frames(h, dev_imgs, B, H, W, layout_of, fg, csc);
   upload_tiles(h, fg, lay);
-  Profiler* prof = begin_profile(h);
-  const uint8_t* src = nv ? h->d_src.as<uint8_t>() : static_cast<const uint8_t*>(dev_imgs);
-  const bool classify = h->cls && h->cls->loaded();
-  h->remember_frames(src, h->d_fgeom.as<ImgGeom>(), B);
-  GraphKey key{kind, B, h->geom_ver, min_area, dev_imgs, dev_dets, dev_counts, conf, iou};
-  key_format(h, csc, key);
-  run_or_capture(h, key, prof == nullptr, [&]() {
-    if (nv) enqueue_csc(h, static_cast<const uint8_t*>(dev_imgs), csc, prof);
-    enqueue_view_front(h, src, lay, B, conf, iou, classify ? min_area : -1, static_cast<lp_det*>(dev_dets), static_cast<int*>(dev_counts),
-                       classify, prof);
-    if (classify) enqueue_classify(h, src, B, static_cast<lp_det*>(dev_dets), nullptr, nullptr, nullptr, prof, 0, h->d_fgeom.as<ImgGeom>());
-  });
-  if (prof) prof->enabled = false;  // records are collected by lp_profile_read after the caller synchronises
+  const FrameSource frames = device_frames(h, dev_imgs, csc);
+  run_device_pass(h, kind, B, conf, iou, min_area, dev_dets, dev_counts, frames, view_front(h, frames.src, lay, B, conf, iou));
 }
 
 }  // namespace lp
@@ -338,13 +346,7 @@ int lp_view_geometry(int det_input, int H, int W, const int* view, float* ratio,
   LP_CHECK(view && det_input >= 1 && H > 0 && W > 0, LP_ERR_ARG, "bad argument (det_input %d, frame %dx%d)", det_input, H, W);
   const ImgGeom frame = make_geom(H, W, det_input, det_input, 0);
   const ImgGeom g = window_geom(frame, view_window(view, H, W, 0), det_input);
-  if (ratio) *ratio = g.ratio;
-  if (pad_w) *pad_w = g.pad_w;
-  if (pad_h) *pad_h = g.pad_h;
-  if (new_w) *new_w = g.new_w;
-  if (new_h) *new_h = g.new_h;
-  if (top) *top = g.top;
-  if (left) *left = g.left;
+  write_geometry(g, ratio, pad_w, pad_h, new_w, new_h, top, left);
   LP_API_END
 }
 
@@ -354,13 +356,7 @@ int lp_letterbox_geometry(int det_h, int det_w, int H, int W, float* ratio, floa
   LP_API_BEGIN
   LP_CHECK(det_h > 0 && det_w > 0 && H > 0 && W > 0, LP_ERR_ARG, "bad argument (detector input %dx%d, image %dx%d; rows x columns)", det_h, det_w, H, W);
   const ImgGeom g = make_geom(H, W, det_h, det_w, 0);
-  if (ratio) *ratio = g.ratio;
-  if (pad_w) *pad_w = g.pad_w;
-  if (pad_h) *pad_h = g.pad_h;
-  if (new_w) *new_w = g.new_w;
-  if (new_h) *new_h = g.new_h;
-  if (top) *top = g.top;
-  if (left) *left = g.left;
+  write_geometry(g, ratio, pad_w, pad_h, new_w, new_h, top, left);
   LP_API_END
 }
 
@@ -391,8 +387,8 @@ int lp_run_tiled(lp_handle* h, const uint8_t* const* imgs, const int* hs, const 
                  float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing) {
   LP_API_BEGIN
   check_square(h, "lp_run_tiled");
-  run_views_host(h, imgs, hs, ws, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, GK_TILED_FRONT, GK_TILED_ROI,
-                 GK_TILED_CLS, [&](const std::vector<ImgGeom>& fg) {
+  run_views_host(h, imgs, hs, ws, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, GK_TILED_FRONT,
+                 [&](const std::vector<ImgGeom>& fg) {
                    check_tiling(tiling, h->cfg.det_input);
                    return view_layout(h, fg, tiled_views(h->cfg.det_input, *tiling, fg));
                  });
@@ -414,8 +410,8 @@ int lp_run_views(lp_handle* h, const uint8_t* const* imgs, const int* hs, const 
                  float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing) {
   LP_API_BEGIN
   check_square(h, "lp_run_views");
-  run_views_host(h, imgs, hs, ws, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, GK_VIEWS_FRONT, GK_VIEWS_ROI,
-                 GK_VIEWS_CLS, [&](const std::vector<ImgGeom>& fg) { return view_layout(h, fg, listed_views(h, views, n_views, fg)); });
+  run_views_host(h, imgs, hs, ws, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, GK_VIEWS_FRONT,
+                 [&](const std::vector<ImgGeom>& fg) { return view_layout(h, fg, listed_views(h, views, n_views, fg)); });
   LP_API_END
 }
 
