@@ -714,6 +714,65 @@ int lp_run_focus(lp_handle* h, const uint8_t* const* imgs, const int* heights, c
                  float conf, float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg,
                  lp_timing* timing, int* views);
 
+/* ---- class distributions: top-k per detection and a distribution vote (additive to ABI 310) ---- */
+/* The classifier computes a softmax over num_classes for every ROI; lp_det carries its arg-max only.  With top-k switched on,
+ * every pipeline call also leaves, per detection, the k most probable classes with their probabilities in a handle-owned
+ * device buffer of max_batch * max_det lp_topk records, parallel to lp_det: record i of frame b describes dets[b*max_det+i]
+ * (for the tiled, views and focus families b indexes frames, not views, as the ROI list does).
+ * The selection rule, for a ROI with distribution p[0..nc): p is the fp32 softmax the classifier computed, the numbers
+ * lp_classify returns.  The classes are ordered by p descending, ties by class ascending.  With m = min(k, nc), entry j < m
+ * holds the j-th class and its p unchanged (selection only, no arithmetic); entries j >= m hold cls = -1, prob = 0.  So
+ * cls[0] == lp_det::cls_class and prob[0] has the bits of lp_det::cls_conf: the arg-max of every classifier path breaks ties
+ * towards the lower class.  The comparator is one header for host and device (csrc/topk_select.h); p is expected to hold
+ * no NaN.
+ * A pipeline call over B frames (lp_run_batch*, lp_run_tiled*, lp_run_views*, lp_run_focus*, lp_run_surfaces_device,
+ * lp_run_views_surfaces_device) writes all B * max_det records of its frames, in the same captured step, and leaves the
+ * records of frames >= B alone: every ROI among the first `classified` ROIs of the ROI list (lp_roi_overflow) gets its top-k
+ * at (roi_img[r], roi_slot[r]); every other record is EMPTY (all cls = -1, all prob = 0): records beyond the kept count,
+ * records a user-set max_rois left unclassified, the whole call when no classifier is loaded.  The buffer holds the last
+ * pipeline call's records, like the ROI list; a consumer enqueued on the handle's stream behind the call sees them, a caller
+ * that wants to keep them copies them on the stream.  lp_detect, lp_detect_raw and lp_classify neither read nor write it.
+ * In the host entry points the work is booked in t_classification.
+ * How it runs: a plain clear launch over the B * max_det records, then the select launch: one wave per ROI, the row of
+ * probabilities staged in LDS once, k rounds of a wave-wide maximum over 64-bit keys (value bits high, inverted class low),
+ * each round restricted to keys below the previous winner.  The live ROI count is read on the device: no host
+ * synchronisation.  While off (the default) nothing changes: the classifier gets no probability pointer, and no launch,
+ * buffer or device branch is added; a handle switched on and off again runs the launches it ran before.  DESIGN.md 6m. */
+#define LP_TOPK_MAX 8
+typedef struct lp_topk { int32_t cls[LP_TOPK_MAX]; float prob[LP_TOPK_MAX]; } lp_topk;   /* 64 bytes, parallel to lp_det */
+
+/* k in 1..8 switches top-k on, 0 off (the default); anything else is LP_ERR_ARG.  The buffer is allocated at the first
+ * enable.  A change of k makes the run families capture their steps anew, as lp_set_view_merge does. */
+int lp_topk_enable(lp_handle* h, int k);
+/* the buffer's device address (stable until lp_destroy) and k; either may be NULL.  LP_ERR_STATE while off. */
+int lp_topk_buffer(lp_handle* h, const void** dev_topk, int* k);
+/* synchronises; the first B * max_det records.  LP_ERR_STATE while off, LP_ERR_ARG for B outside 1..max_batch. */
+int lp_topk_read(lp_handle* h, lp_topk* out, int B);
+/* pure host, no handle, no device: the rule above on one distribution p[0..nc).  LP_ERR_ARG for NULL, nc < 1 or k outside 1..8 */
+int lp_topk_select(const float* p, int nc, int k, lp_topk* out);
+/* The tracker fed the distribution: lp_track_device / lp_track with another vote, everything else (ordering, asynchrony,
+ * errors) as theirs.  dev_topk is [B * max_det] lp_topk, 16-byte aligned: lp_topk_buffer's address or any device buffer; NULL
+ * or a misaligned address is LP_ERR_ARG before anything is enqueued.  Steps 3 and 5 of the tracker's rule use, for a
+ * detection with record t (fp32, every operation rounded on its own, nothing contracted):
+ *   votes  iff  0 <= t.cls[0] < num_classes        (lp_det::cls_class / cls_conf are not read)
+ *   valid j:    0 <= t.cls[j] < num_classes, j = 0..7 in order; other entries are skipped
+ *   acc[c] *= vote_decay  for every class c
+ *   s = 0;  for valid j in order: s = s + t.prob[j]
+ *   wsum = wsum * vote_decay + s
+ *   for valid j in order: acc[t.cls[j]] += t.prob[j]      (a class named twice is added twice, in j order)
+ * A birth starts from acc = 0, wsum = 0 and votes the same way.  Both vote forms work on the same accumulators: a tracker may
+ * be fed by either call from frame to frame, and one valid entry (cls_class, cls_conf) gives lp_track_device's result bit for
+ * bit.  tests/topk_ref.py restates both rules in NumPy. */
+int lp_track_topk_device(lp_handle* h, const void* dev_dets, const void* dev_counts, const void* dev_topk, int B,
+                         const int* stream_ids, void* dev_tracks);
+/* the same on host records (uploads, runs the same kernel, downloads; synchronous) */
+int lp_track_topk(lp_handle* h, const lp_det* dets, const int* counts, const lp_topk* topk, int B, const int* stream_ids,
+                  struct lp_track* tracks);
+/* test hook (needs top-k on): uploads probs [R, num_classes] where the classifier leaves them, installs the ROI list
+ * (img[r], slot[r]) with total = classified = R, runs clear + select for B frames and downloads B * max_det records.
+ * LP_ERR_ARG for R > max_rois or an img / slot out of range. */
+int lp_test_topk(lp_handle* h, const float* probs, int R, const int* img, const int* slot, int B, lp_topk* out);
+
 /* ---- classifier alone ------------------------------------------------------------ */
 /* replaces PyTorchClassifier.predict_batch (e2e.py:378-396) for R host BGR crops of
  * individual sizes: ids [R], probs [R*num_classes] (softmax). */

@@ -1,5 +1,5 @@
 // Internal to the C-ABI translation units (api.cpp, pipeline.cpp, pixfmt.cpp, views.cpp, tracking.cpp, inventory.cpp, focus.cpp,
-// test_hooks.cpp): the handle behind include/litepi.h's lp_handle, the captured-step cache, and the pipeline pieces the entry points share.
+// topk.cpp, test_hooks.cpp): the handle behind include/litepi.h's lp_handle, the captured-step cache, and the pipeline pieces the entry points share.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -125,6 +125,7 @@ struct Tracker {
   int nc = 1, max_det = 0, max_batch = 0;
   DevBuf table, heads, acc, scratch;
   DevBuf d_dets, d_counts, d_tracks;   // lp_track (host records): allocated on first use
+  DevBuf d_topk;                       // lp_track_topk (host records): allocated on first use
   PlanRing ring;                       // a slot: up to max_batch jobs, then the max_batch frame indices (plan_stream_jobs)
 };
 
@@ -213,6 +214,10 @@ struct lp_handle {
   lp_view_merge vmerge = {};   // lp_set_view_merge: how the frame NMS merges a frame's views (zeros: the reference's rule)
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // staged host pass: start, after the ROI resize, after the front, end
   int last_roi_count = 0;
+  // top-k of the class distribution per detection (lp_topk_enable): k (0 = off) and the [max_batch * max_det] lp_topk records,
+  // allocated at the first enable and kept until lp_destroy.  While k == 0 no path looks at either.
+  int topk_k = 0;
+  lp::DevBuf d_topk;
   // where the last pipeline call's BGR frames and their geometry are (host bookkeeping; the evidence store reads them behind
   // lp_inventory*(crops = 1)).  Whatever rewrites or reallocates d_src or d_geom (ensure_src, upload_geom: every entry point
   // that does so, lp_detect* and lp_classify included) forgets them first; the pipeline entry points remember their own
@@ -326,6 +331,9 @@ void enqueue_nms(lp_handle* h, int B, float iou, int min_area, lp_det* dets, int
 // geom: the images' geometry (default d_geom; the tiled path passes its frame geometry)
 void enqueue_classify(lp_handle* h, const uint8_t* src, int B, lp_det* dets, float* probs, int* ids, float* conf, Profiler* prof, int stage = 0,
                       const ImgGeom* geom = nullptr);
+// top-k on: clear the B * max_det records of the call's frames, then (classify: a classifier ran and left its probabilities in
+// d_probs) the select over the classified ROIs; two plain launches.  Never called while top-k is off.
+void enqueue_topk(lp_handle* h, int B, bool classify, Profiler* prof);
 // eager the first time a key is seen, captured into a hipGraph the second time, replayed from then on
 void run_or_capture(lp_handle* h, const GraphKey& key, bool allow, const std::function<void()>& enqueue);
 

@@ -198,10 +198,27 @@ struct TrackArgs {
   int max_age, min_hits;
   float new_conf, decay;
   int class_gate, motion;
+  const lp_topk* topk;      // [B * max_det] or null: the distribution vote (lp_track_topk*) instead of (cls_class, cls_conf)
 };
+// topk == null runs the kernel of lp_track*, topk != null its distribution-vote instantiation
 void launch_track(const TrackArgs& a, int n_jobs, hipStream_t st);
 // frees every slot of `n` streams from `first` on (next_id and the overflow counter stay)
 void launch_track_reset(TrackSlot* table, int T, int first, int n, hipStream_t st);
+
+// ---- topk_kernels.hip (top-k of the classifier's distribution per detection, include/litepi.h lp_topk) ----
+struct TopkArgs {
+  const float* probs;       // [max_rois][nc] softmax rows as the classifier wrote them
+  const int* total;         // RoiTable::total: the classified ROI count, read on the device
+  const int* roi_img;       // [max_rois]
+  const int* roi_slot;      // [max_rois]
+  lp_topk* out;             // [B * max_det]
+  int nc, k, B, max_det;
+  int cap;                  // min(max_rois, B * max_det): bounds the ROI count and sizes the grid
+};
+// the empty record (cls = -1, prob = 0) into n_records records
+void launch_topk_clear(lp_topk* out, int n_records, hipStream_t st);
+// one wave per classified ROI: its top-k at (roi_img[r], roi_slot[r]); a ROI naming a record outside [B, max_det) is skipped
+void launch_topk_select(const TopkArgs& a, hipStream_t st);
 
 // ---- inventory_kernels.hip (one record + best crop per finished track, include/litepi.h lp_inventory_*) ----
 struct InvEntry {      // one slot of a stream's inventory, 80 bytes, device resident between calls

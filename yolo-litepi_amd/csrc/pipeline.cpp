@@ -118,6 +118,22 @@ void enqueue_classify(lp_handle* h, const uint8_t* src, int B, lp_det* dets, flo
   }
 }
 
+void enqueue_topk(lp_handle* h, int B, bool classify, Profiler* prof) {
+  lp_topk* out = h->d_topk.as<lp_topk>();
+  if (prof) prof->begin(h->stream);
+  launch_topk_clear(out, B * h->cfg.max_det, h->stream);
+  if (prof) prof->end(h->stream, "topk_clear", "topk", 0.0, (double)B * h->cfg.max_det * sizeof(lp_topk));
+  if (!classify) return;
+  RoiTable tab = h->roi_table();
+  TopkArgs a;
+  a.probs = h->d_probs.as<float>(); a.total = tab.total; a.roi_img = tab.img; a.roi_slot = tab.slot; a.out = out;
+  a.nc = h->cls->num_classes(); a.k = h->topk_k; a.B = B; a.max_det = h->cfg.max_det;
+  a.cap = std::min(h->max_rois, B * h->cfg.max_det);
+  if (prof) prof->begin(h->stream);
+  launch_topk_select(a, h->stream);
+  if (prof) prof->end(h->stream, "topk_select", "topk", 0.0, (double)a.nc * 4 + sizeof(lp_topk), true);
+}
+
 // Run `enqueue` (kernel launches on h->stream only: no allocation, no synchronisation) eagerly the first time a key is
 // seen -- that call also performs every one-time set-up (LDS attributes, lazy packing) --, capture it into a hipGraph the
 // second time, replay the graph from then on.
@@ -255,6 +271,7 @@ void run_device_pass(lp_handle* h, GraphKind kind, int B, float conf, float iou,
   Profiler* prof = begin_profile(h);
   if (before) before(prof);
   const bool classify = h->cls && h->cls->loaded();
+  const bool topk = h->topk_k > 0;   // lp_topk_enable: the step also fills the handle's lp_topk records
   lp_det* dets = static_cast<lp_det*>(dev_dets);
   h->remember_frames(frames.src, front.roi_geom ? front.roi_geom : h->d_geom.as<ImgGeom>(), B);
   GraphKey key = frames.key;
@@ -263,7 +280,8 @@ void run_device_pass(lp_handle* h, GraphKind kind, int B, float conf, float iou,
   run_or_capture(h, key, prof == nullptr, [&]() {
     if (frames.convert) frames.convert(prof);
     front.run(prof, dets, static_cast<int*>(dev_counts), classify ? min_area : -1, classify);
-    if (classify) enqueue_classify(h, frames.src, B, dets, nullptr, nullptr, nullptr, prof, 0, front.roi_geom);
+    if (classify) enqueue_classify(h, frames.src, B, dets, topk ? h->d_probs.as<float>() : nullptr, nullptr, nullptr, prof, 0, front.roi_geom);
+    if (topk) enqueue_topk(h, B, classify, prof);
   });
   if (prof) prof->enabled = false;  // records are collected by lp_profile_read after the caller synchronises
 }
@@ -288,7 +306,11 @@ void run_host_pass(lp_handle* h, int B, float conf, float iou, int min_area, lp_
   LP_HIP(hipEventRecord(h->ev[2], h->stream));
   run_or_capture(h, k2, prof == nullptr, [&]() { enqueue_classify(h, src, B, d_dets, nullptr, nullptr, nullptr, prof, 1, roi_geom); });
   LP_HIP(hipEventRecord(h->ev[1], h->stream));
-  run_or_capture(h, k3, prof == nullptr, [&]() { enqueue_classify(h, src, B, d_dets, nullptr, nullptr, nullptr, prof, 2, roi_geom); });
+  const bool topk = h->topk_k > 0;   // lp_topk_enable: part of the classification piece
+  run_or_capture(h, k3, prof == nullptr, [&]() {
+    enqueue_classify(h, src, B, d_dets, topk ? h->d_probs.as<float>() : nullptr, nullptr, nullptr, prof, 2, roi_geom);
+    if (topk) enqueue_topk(h, B, true, prof);
+  });
   LP_HIP(hipEventRecord(h->ev[3], h->stream));
   LP_HIP(hipMemcpyAsync(dets, h->d_dets.p, (size_t)B * h->cfg.max_det * sizeof(lp_det), hipMemcpyDeviceToHost, h->stream));
   std::vector<int> cnt(3 * B);

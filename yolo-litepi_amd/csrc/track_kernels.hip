@@ -47,6 +47,31 @@ __device__ __forceinline__ float track_iou(float ix1, float iy1, float ix2, floa
 
 __device__ __forceinline__ int lanes_below(unsigned long long m, int lane) { return __popcll(m & ((1ull << lane) - 1ull)); }
 
+// The distribution vote of lp_track_topk* (include/litepi.h): a detection's lp_topk record, always read from memory at the
+// detection's own index (frames beyond TRK_DET_LDS included).
+struct TopkVote { int cls[LP_TOPK_MAX]; float prob[LP_TOPK_MAX]; };
+
+__device__ __forceinline__ TopkVote load_topk(const lp_topk* t) {
+  const i32x4* p = reinterpret_cast<const i32x4*>(t);
+  const i32x4 c0 = p[0], c1 = p[1], q0 = p[2], q1 = p[3];
+  TopkVote v;
+  v.cls[0] = c0.x; v.cls[1] = c0.y; v.cls[2] = c0.z; v.cls[3] = c0.w; v.cls[4] = c1.x; v.cls[5] = c1.y; v.cls[6] = c1.z; v.cls[7] = c1.w;
+  v.prob[0] = __int_as_float(q0.x); v.prob[1] = __int_as_float(q0.y); v.prob[2] = __int_as_float(q0.z); v.prob[3] = __int_as_float(q0.w);
+  v.prob[4] = __int_as_float(q1.x); v.prob[5] = __int_as_float(q1.y); v.prob[6] = __int_as_float(q1.z); v.prob[7] = __int_as_float(q1.w);
+  return v;
+}
+__device__ __forceinline__ bool topk_votes(const TopkVote& v, int nc) { return v.cls[0] >= 0 && v.cls[0] < nc; }
+// s = 0; for valid j in order: s = s + prob[j]
+__device__ __forceinline__ float topk_weight(const TopkVote& v, int nc) {
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < LP_TOPK_MAX; ++j)
+    if (v.cls[j] >= 0 && v.cls[j] < nc) s = __fadd_rn(s, v.prob[j]);
+  return s;
+}
+
+// TOPK = false: the vote of lp_track* on (cls_class, cls_conf), a.topk is not looked at; TOPK = true: the distribution vote
+template <bool TOPK>
 __global__ __launch_bounds__(TRK_LANES) void track_kernel(const TrackArgs a) {
   // per-track state of the stream, structure of arrays
   __shared__ float s_box[4][TRK_MAXT], s_vel[4][TRK_MAXT], s_pred[4][TRK_MAXT], s_wsum[TRK_MAXT];
@@ -90,6 +115,7 @@ __global__ __launch_bounds__(TRK_LANES) void track_kernel(const TrackArgs a) {
     const int n = min(max(n_next, 0), max_det);
     const lp_det* fdets = a.dets + (size_t)b * max_det;
     TrackRec* fout = a.out + (size_t)b * max_det;
+    const lp_topk* ftopk = TOPK ? a.topk + (size_t)b * max_det : nullptr;
     // sort key + assignment: LDS, or the job's slice of the scratch buffer for a frame of more than TRK_KEYS detections
     unsigned* keys = s_key;
     int* asg = s_asg;
@@ -206,7 +232,13 @@ __global__ __launch_bounds__(TRK_LANES) void track_kernel(const TrackArgs a) {
             s_box[k][bi] = db[k];
           }
           s_hits[bi] += 1; s_missed[bi] = 0; s_claimed[bi] = 1;
-          if (r.ccls >= 0 && r.ccls < nc) {
+          if (TOPK) {
+            const TopkVote tv = load_topk(ftopk + d);
+            if (topk_votes(tv, nc)) {
+              s_wsum[bi] = __fadd_rn(__fmul_rn(s_wsum[bi], a.decay), topk_weight(tv, nc));
+              s_vote[bi] = 1;
+            }
+          } else if (r.ccls >= 0 && r.ccls < nc) {
             s_wsum[bi] = __fadd_rn(__fmul_rn(s_wsum[bi], a.decay), r.cconf);
             s_vote[bi] = 1;
           }
@@ -260,8 +292,14 @@ __global__ __launch_bounds__(TRK_LANES) void track_kernel(const TrackArgs a) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) s_vel[k][s] = 0.f;
         s_id[s] = next_id + rank; s_hits[s] = 1; s_missed[s] = 0; s_age[s] = 0; s_cls[s] = r.dcls;
-        const bool vote = r.ccls >= 0 && r.ccls < nc;
-        s_wsum[s] = vote ? __fadd_rn(__fmul_rn(0.f, a.decay), r.cconf) : 0.f;
+        bool vote = r.ccls >= 0 && r.ccls < nc;
+        float weight = r.cconf;
+        if (TOPK) {
+          const TopkVote tv = load_topk(ftopk + i);
+          vote = topk_votes(tv, nc);
+          weight = topk_weight(tv, nc);
+        }
+        s_wsum[s] = vote ? __fadd_rn(__fmul_rn(0.f, a.decay), weight) : 0.f;
         s_vote[s] = vote ? 1 : 0;
         s_live[s] = 1; s_claimed[s] = 1; s_born[s] = 1;
         asg[i] = s;
@@ -292,7 +330,13 @@ __global__ __launch_bounds__(TRK_LANES) void track_kernel(const TrackArgs a) {
         float cconf;
         if (i < TRK_DET_LDS) { ccls = s_det[i][1].z; cconf = __int_as_float(s_det[i][1].w); }
         else { ccls = fdets[i].cls_class; cconf = fdets[i].cls_conf; }
-        const bool vote = ccls >= 0 && ccls < nc, is_born = s_born[s] != 0;
+        bool vote = ccls >= 0 && ccls < nc;
+        const bool is_born = s_born[s] != 0;
+        TopkVote tv = {};
+        if (TOPK) {
+          tv = load_topk(ftopk + i);
+          vote = topk_votes(tv, nc);
+        }
         float* row = accs + (size_t)s * nc;
         int bc = -1;
         float bvv = 0.f;
@@ -300,7 +344,11 @@ __global__ __launch_bounds__(TRK_LANES) void track_kernel(const TrackArgs a) {
           float v = is_born ? 0.f : row[c];
           if (vote) {
             v = __fmul_rn(v, a.decay);
-            if (c == ccls) v = __fadd_rn(v, cconf);
+            if (TOPK) {
+#pragma unroll
+              for (int j = 0; j < LP_TOPK_MAX; ++j)
+                if (tv.cls[j] == c) v = __fadd_rn(v, tv.prob[j]);   // c is in range: an invalid entry names no c
+            } else if (c == ccls) v = __fadd_rn(v, cconf);
           }
           if (vote || is_born) row[c] = v;
           if (bc < 0 || v > bvv) { bc = c; bvv = v; }
@@ -346,7 +394,8 @@ void launch_track(const TrackArgs& a, int n_jobs, hipStream_t st) {
   if (n_jobs <= 0) return;
   LP_CHECK(a.T >= 1 && a.T <= TRK_MAXT && a.nc >= 1 && a.max_det >= 1, LP_ERR_ARG, "bad tracker shape (max_tracks %d, classes %d)", a.T, a.nc);
   LP_CHECK(a.max_det <= LP_TRACK_KEY_LDS || a.scratch, LP_ERR_STATE, "the tracker has no scratch buffer for max_det %d", a.max_det);
-  LP_LAUNCH(track_kernel, dim3(n_jobs), dim3(TRK_LANES), 0, st, a);
+  if (a.topk) LP_LAUNCH(track_kernel<true>, dim3(n_jobs), dim3(TRK_LANES), 0, st, a);
+  else LP_LAUNCH(track_kernel<false>, dim3(n_jobs), dim3(TRK_LANES), 0, st, a);
   LP_HIP(hipGetLastError());
 }
 

@@ -85,10 +85,12 @@ static void check_track_call(lp_handle* h, int B, const int* stream_ids) {
   check_stream_ids(t, B, stream_ids);
 }
 
-static void enqueue_track(lp_handle* h, const void* dev_dets, const void* dev_counts, int B, const int* stream_ids, void* dev_tracks) {
+// dev_topk: null for the vote on (cls_class, cls_conf), else the [B * max_det] lp_topk records of the distribution vote
+static void enqueue_track(lp_handle* h, const void* dev_dets, const void* dev_counts, int B, const int* stream_ids, void* dev_tracks,
+                          const void* dev_topk = nullptr) {
   check_track_call(h, B, stream_ids);
   Tracker& t = *h->trk;
-  LP_CHECK(((uintptr_t)dev_dets | (uintptr_t)dev_tracks) % 16 == 0 && (uintptr_t)dev_counts % 4 == 0, LP_ERR_ARG,
+  LP_CHECK(((uintptr_t)dev_dets | (uintptr_t)dev_tracks | (uintptr_t)dev_topk) % 16 == 0 && (uintptr_t)dev_counts % 4 == 0, LP_ERR_ARG,
            "the record buffers must be 16-byte aligned");
   LP_HIP(hipSetDevice(h->cfg.device));
   const PlanRing::Slot rs = t.ring.acquire();
@@ -101,6 +103,7 @@ static void enqueue_track(lp_handle* h, const void* dev_dets, const void* dev_co
   a.table = t.table.as<TrackSlot>(); a.heads = t.heads.as<TrackHead>(); a.acc = t.acc.as<float>(); a.scratch = t.scratch.as<unsigned>();
   a.max_det = t.max_det; a.T = t.cfg.max_tracks; a.nc = t.nc; a.iou_match = t.cfg.iou_match; a.max_age = t.cfg.max_age;
   a.min_hits = t.cfg.min_hits; a.new_conf = t.cfg.new_conf; a.decay = t.cfg.vote_decay; a.class_gate = t.cfg.class_gate; a.motion = t.cfg.motion;
+  a.topk = static_cast<const lp_topk*>(dev_topk);
   launch_track(a, n_jobs, h->stream);
   t.ring.release(rs, h->stream);
 }
@@ -114,11 +117,19 @@ int lp_track_device(lp_handle* h, const void* dev_dets, const void* dev_counts, 
   LP_API_END
 }
 
-int lp_track(lp_handle* h, const lp_det* dets, const int* counts, int B, const int* stream_ids, struct lp_track* tracks) {
+int lp_track_topk_device(lp_handle* h, const void* dev_dets, const void* dev_counts, const void* dev_topk, int B, const int* stream_ids,
+                         void* dev_tracks) {
   LP_API_BEGIN
   LP_CHECK(h, LP_ERR_ARG, "null handle");
   LP_CHECK(h->trk, LP_ERR_STATE, "no tracker: call lp_tracker_create first");
-  LP_CHECK(dets && counts && tracks, LP_ERR_ARG, "null argument");
+  LP_CHECK(dev_dets && dev_counts && dev_topk && dev_tracks, LP_ERR_ARG, "null argument");
+  enqueue_track(h, dev_dets, dev_counts, B, stream_ids, dev_tracks, dev_topk);
+  LP_API_END
+}
+
+// lp_track and lp_track_topk (topk != null): upload, the device call, download
+static void track_host(lp_handle* h, const lp_det* dets, const int* counts, const lp_topk* topk, int B, const int* stream_ids,
+                       struct lp_track* tracks) {
   check_track_call(h, B, stream_ids);   // every argument error before the first copy is enqueued
   Tracker& t = *h->trk;
   LP_HIP(hipSetDevice(h->cfg.device));
@@ -128,10 +139,12 @@ int lp_track(lp_handle* h, const lp_det* dets, const int* counts, int B, const i
     t.d_counts.alloc((size_t)t.max_batch * sizeof(int));
     t.d_tracks.alloc(cap * sizeof(TrackRec));
   }
+  if (topk && !t.d_topk.p) t.d_topk.alloc(cap * sizeof(lp_topk));
   LP_HIP(hipMemcpyAsync(t.d_dets.p, dets, used * sizeof(lp_det), hipMemcpyHostToDevice, h->stream));
   LP_HIP(hipMemcpyAsync(t.d_counts.p, counts, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  if (topk) LP_HIP(hipMemcpyAsync(t.d_topk.p, topk, used * sizeof(lp_topk), hipMemcpyHostToDevice, h->stream));
   LP_HIP(hipStreamSynchronize(h->stream));   // the sources are the caller's pageable memory
-  enqueue_track(h, t.d_dets.p, t.d_counts.p, B, stream_ids, t.d_tracks.p);
+  enqueue_track(h, t.d_dets.p, t.d_counts.p, B, stream_ids, t.d_tracks.p, topk ? t.d_topk.p : nullptr);
   for (int b = 0; b < B; ++b) {   // only the first count[b] records of a frame are results: nothing else is copied or written
     const int n = std::min(std::max(counts[b], 0), t.max_det);
     if (n > 0)
@@ -139,6 +152,24 @@ int lp_track(lp_handle* h, const lp_det* dets, const int* counts, int B, const i
                             hipMemcpyDeviceToHost, h->stream));
   }
   LP_HIP(hipStreamSynchronize(h->stream));
+}
+
+int lp_track(lp_handle* h, const lp_det* dets, const int* counts, int B, const int* stream_ids, struct lp_track* tracks) {
+  LP_API_BEGIN
+  LP_CHECK(h, LP_ERR_ARG, "null handle");
+  LP_CHECK(h->trk, LP_ERR_STATE, "no tracker: call lp_tracker_create first");
+  LP_CHECK(dets && counts && tracks, LP_ERR_ARG, "null argument");
+  track_host(h, dets, counts, nullptr, B, stream_ids, tracks);
+  LP_API_END
+}
+
+int lp_track_topk(lp_handle* h, const lp_det* dets, const int* counts, const lp_topk* topk, int B, const int* stream_ids,
+                  struct lp_track* tracks) {
+  LP_API_BEGIN
+  LP_CHECK(h, LP_ERR_ARG, "null handle");
+  LP_CHECK(h->trk, LP_ERR_STATE, "no tracker: call lp_tracker_create first");
+  LP_CHECK(dets && counts && topk && tracks, LP_ERR_ARG, "null argument");
+  track_host(h, dets, counts, topk, B, stream_ids, tracks);
   LP_API_END
 }
 

@@ -124,6 +124,17 @@ TRACK_STATE_DTYPE = [("slot", "<i4"), ("track_id", "<i4"), ("x1", "<f4"), ("y1",
 DET_DTYPE = [("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("det_conf", "<f4"), ("det_class", "<i4"),
              ("cls_class", "<i4"), ("cls_conf", "<f4")]
 
+LP_TOPK_MAX = 8
+
+
+class LpTopk(C.Structure):
+    """lp_topk, 64 bytes, parallel to lp_det: the k most probable classes of a detection; unused entries cls = -1, prob = 0"""
+    _fields_ = [("cls", C.c_int32 * LP_TOPK_MAX), ("prob", C.c_float * LP_TOPK_MAX)]
+
+
+# numpy view of lp_topk records
+TOPK_DTYPE = [("cls", "<i4", (LP_TOPK_MAX,)), ("prob", "<f4", (LP_TOPK_MAX,))]
+
 SYMBOLS = [
     "lp_last_error", "lp_version", "lp_default_config", "lp_create", "lp_destroy", "lp_load_detector_ncnn",
     "lp_load_classifier_tensors", "lp_detect_raw", "lp_detect", "lp_run_batch", "lp_run_batch_device", "lp_classify",
@@ -145,6 +156,7 @@ SYMBOLS = [
     "lp_load_detector_onnx", "lp_load_detector_onnx_memory", "lp_detector_graph_describe",
     "lp_view_merge_default", "lp_view_merge_check", "lp_set_view_merge",
     "lp_surfaces_check", "lp_run_surfaces_device", "lp_run_views_surfaces_device", "lp_test_convert_surfaces", "lp_graph_stats",
+    "lp_topk_enable", "lp_topk_buffer", "lp_topk_read", "lp_topk_select", "lp_track_topk_device", "lp_track_topk", "lp_test_topk",
 ]
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
 
@@ -271,6 +283,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_run_views_surfaces_device.argtypes = [vp, sfp, sp, C.c_int, ip, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp]
     lib.lp_test_convert_surfaces.argtypes = [vp, sfp, sp, C.c_int, vp]
     lib.lp_graph_stats.argtypes = [vp, ip, i64p, i64p, i64p]
+    lib.lp_topk_enable.argtypes = [vp, C.c_int]
+    lib.lp_topk_buffer.argtypes = [vp, C.POINTER(vp), ip]
+    lib.lp_topk_read.argtypes = [vp, vp, C.c_int]
+    lib.lp_topk_select.argtypes = [fp, C.c_int, C.c_int, C.POINTER(LpTopk)]
+    lib.lp_track_topk_device.argtypes = [vp, vp, vp, vp, C.c_int, ip, vp]
+    lib.lp_track_topk.argtypes = [vp, vp, ip, vp, C.c_int, ip, vp]
+    lib.lp_test_topk.argtypes = [vp, fp, C.c_int, ip, ip, C.c_int, vp]
     for s in SYMBOLS:
         if s not in ("lp_last_error", "lp_default_config", "lp_destroy", "lp_track_default_config", "lp_inventory_default_config",
                      "lp_evidence_default_config", "lp_focus_default_config", "lp_view_merge_default"):

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _ffi
-from ._ffi import (DET_DTYPE, SIGN_DTYPE, TRACK_DTYPE, TRACK_STATE_DTYPE, LpConfig, LpFrameFormat, LpInventoryConfig, LpKernelTime, LpTiming,
+from ._ffi import (DET_DTYPE, SIGN_DTYPE, TOPK_DTYPE, TRACK_DTYPE, TRACK_STATE_DTYPE, LpConfig, LpFrameFormat, LpInventoryConfig, LpKernelTime, LpTiming,
                    LpTiling, LpTrackConfig, check)
 from .pixfmt import CSC_MATRICES, PIXEL_FORMATS, nv12_frame_hw
 from .surfaces import Surface, surface_array, surface_format, surface_from_tensors, surfaces_check  # noqa: F401  (re-exported)
@@ -147,6 +147,31 @@ def track_config_check(cfg: Optional[LpTrackConfig]) -> int:
     """lp_track_config_check's status for a configuration (host only, no GPU needed)."""
     lib = _ffi.load_library()
     return lib.lp_track_config_check(C.byref(cfg) if cfg is not None else None)
+
+
+def topk_select(p, k: int) -> np.ndarray:
+    """lp_topk_select (host only, no GPU needed): the top-k selection rule on one distribution p [nc] -> one TOPK_DTYPE
+    record; LitepiError(LP_ERR_ARG) for an empty p or k outside 1..8."""
+    lib = _ffi.load_library()
+    a = np.ascontiguousarray(p, dtype=np.float32).reshape(-1)
+    out = np.zeros(1, dtype=TOPK_DTYPE)
+    check(lib, lib.lp_topk_select(a.ctypes.data_as(C.POINTER(C.c_float)), len(a), int(k), C.cast(out.ctypes.data, C.POINTER(_ffi.LpTopk))))
+    return out[0]
+
+
+TRACK_VOTES = ("top1", "distribution")
+
+
+def check_topk_options(topk, track_vote: str, track: bool) -> int:
+    """the rules HybridPipeline and the CLI share for topk / track_vote; returns k (0 = off).  ValueError names both options."""
+    k = 0 if topk is None else int(topk)
+    if not 0 <= k <= _ffi.LP_TOPK_MAX:
+        raise ValueError(f"topk = {topk!r} outside 0..{_ffi.LP_TOPK_MAX}")
+    if track_vote not in TRACK_VOTES:
+        raise ValueError(f"track_vote = {track_vote!r} is not one of {TRACK_VOTES}")
+    if track_vote == "distribution" and not (track and k >= 1):
+        raise ValueError("track_vote='distribution' needs track=True and topk >= 1 (--track_vote distribution needs --track and --topk K)")
+    return k
 
 
 INVENTORY_CONFIG_FIELDS = ("max_signs", "keep_crops", "best", "min_hits")
@@ -565,6 +590,73 @@ class Engine:
         check(self.lib, self.lib.lp_tracker_snapshot(self._h, int(stream), st.ctypes.data, n.value, C.byref(n), acc.ctypes.data,
                                                      C.byref(nid), C.byref(ovf)))
         return {"tracks": st, "acc": acc, "next_id": nid.value, "overflow": ovf.value}
+
+    # ---- class distributions: top-k per detection and the distribution vote --------------------
+    def topk_enable(self, k: int) -> None:
+        """lp_topk_enable: k in 1..8 = every pipeline call also leaves the k most probable classes of every detection in the
+        engine's lp_topk buffer (topk_read, topk_buffer); 0 = off (the default)."""
+        check(self.lib, self.lib.lp_topk_enable(self._h, int(k)))
+        self.topk_k = int(k)
+
+    def topk_buffer(self) -> Tuple[int, int]:
+        """(device address of the [max_batch * max_det] lp_topk records, k); the address is stable for the engine's life."""
+        p, k = C.c_void_p(), C.c_int()
+        check(self.lib, self.lib.lp_topk_buffer(self._h, C.byref(p), C.byref(k)))
+        return int(p.value or 0), k.value
+
+    def topk_read(self, B: int) -> np.ndarray:
+        """lp_topk_read (synchronises): the last pipeline call's records of its first B frames, (B, max_det) TOPK_DTYPE --
+        cls (8,) i4 and prob (8,) f4, parallel to the lp_det records; unused entries cls = -1, prob = 0."""
+        out = np.zeros((max(int(B), 0), self.cfg.max_det), dtype=TOPK_DTYPE)
+        check(self.lib, self.lib.lp_topk_read(self._h, out.ctypes.data, int(B)))
+        return out
+
+    def topk_select(self, p, k: int) -> np.ndarray:
+        """lp_topk_select (host only): the selection rule on one distribution p [nc] -> one TOPK_DTYPE record."""
+        return topk_select(p, k)
+
+    def _topk_records(self, topk, B: int) -> np.ndarray:
+        t = np.ascontiguousarray(topk, dtype=TOPK_DTYPE).reshape(-1, self.cfg.max_det)
+        if t.shape[0] != B:
+            raise ValueError(f"topk must hold max_det records per frame ({B} frames), got shape {np.shape(topk)}")
+        return t
+
+    def track_topk(self, dets: np.ndarray, counts, topk, stream_ids=None) -> np.ndarray:
+        """lp_track_topk: track() with the distribution vote -- every detection votes with its lp_topk record (topk [B, max_det]
+        TOPK_DTYPE, as topk_read returns them) instead of (cls_class, cls_conf).  Synchronous."""
+        d = np.ascontiguousarray(dets, dtype=DET_DTYPE).reshape(-1, self.cfg.max_det)
+        B = d.shape[0]
+        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+        if cnt.shape != (B,):
+            raise ValueError(f"counts must hold one count per frame ({B}), got shape {cnt.shape}")
+        t = self._topk_records(topk, B)
+        ids = self._stream_ids(stream_ids, B)
+        out = np.zeros((B, self.cfg.max_det), dtype=TRACK_DTYPE)
+        ip = C.POINTER(C.c_int)
+        check(self.lib, self.lib.lp_track_topk(self._h, d.ctypes.data, cnt.ctypes.data_as(ip), t.ctypes.data, B,
+                                               None if ids is None else ids.ctypes.data_as(ip), out.ctypes.data))
+        return out
+
+    def track_topk_device(self, dev_dets: int, dev_counts: int, dev_topk: int, B: int, dev_tracks: int, stream_ids=None) -> None:
+        """lp_track_topk_device: track_device() with the distribution vote; dev_topk is topk_buffer()'s address or any device
+        buffer of [B * max_det] lp_topk records.  Asynchronous on the engine's stream."""
+        ids = self._stream_ids(stream_ids, B)
+        check(self.lib, self.lib.lp_track_topk_device(self._h, C.c_void_p(dev_dets), C.c_void_p(dev_counts), C.c_void_p(dev_topk), int(B),
+                                                      None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int)), C.c_void_p(dev_tracks)))
+
+    def test_topk(self, probs, img, slot, B: int) -> np.ndarray:
+        """lp_test_topk: probs [R, num_classes] as the classifier would leave them and the ROI list (img[r], slot[r]) through the
+        clear + select launches for B frames -> (B, max_det) TOPK_DTYPE records.  Needs top-k on."""
+        nc = max(self.cfg.num_classes, 1)
+        p = np.ascontiguousarray(probs, dtype=np.float32).reshape(-1, nc)
+        i, s = np.ascontiguousarray(img, dtype=np.int32), np.ascontiguousarray(slot, dtype=np.int32)
+        if i.shape != (len(p),) or s.shape != (len(p),):
+            raise ValueError("img and slot must hold one entry per row of probs")
+        out = np.zeros((max(int(B), 0), self.cfg.max_det), dtype=TOPK_DTYPE)
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        check(self.lib, self.lib.lp_test_topk(self._h, p.ctypes.data_as(fp), len(p), i.ctypes.data_as(ip), s.ctypes.data_as(ip), int(B),
+                                              out.ctypes.data))
+        return out
 
     # ---- focus views: tracker-chosen windows and a sweep ---------------------------------------
     def focus_create(self, **cfg) -> None:
@@ -1233,7 +1325,8 @@ class HybridPipeline:
                  csc_matrix: str = "bt601", track: bool = False, track_config: Optional[Dict] = None, inventory=False,
                  views=None, view_tile: Optional[int] = None, view_overlap: int = 0, view_full_frame: bool = True,
                  focus: Optional[int] = None, focus_config: Optional[Dict] = None, view_match: Optional[str] = None,
-                 view_merge: Optional[str] = None, view_match_thr: Optional[float] = None, evidence=None):
+                 view_merge: Optional[str] = None, view_match_thr: Optional[float] = None, evidence=None,
+                 topk: Optional[int] = None, track_vote: str = "top1"):
         """detector_param, detector_bin: an NCNN .param / .bin pair, or an .onnx file and None.
         inventory: True or a dict of lp_inventory_config's fields (max_signs, keep_crops, best, min_hits): every tracked call
         also feeds the engine's sign inventory, while the handle still holds that call's classifier crops; drain_signs() returns
@@ -1260,7 +1353,13 @@ class HybridPipeline:
         view border cut with the whole box it lies in, "union" emits the box around a keeper and everything it absorbed.  Valid
         only together with tile_overlap, views, view_tile or focus.
         det_input_size: an int (square) or (rows, columns), e.g. (384, 640) for 16:9 video; tile_overlap, views, view_tile and
-        focus need a square."""
+        focus need a square.
+        topk: K in 1..8 (Engine.topk_enable): every result dict gains "cls_topk", the [(class, prob), ...] of the detection's K
+        most probable classes in descending order ([] for an unclassified detection); cls_topk[0] is (cls_class, cls_conf).
+        track_vote: "top1" = a detection adds (cls_class, cls_conf) to its track's vote; "distribution" = it adds its K most
+        probable classes, each with its probability (lp_track_topk).  "distribution" needs track and topk >= 1."""
+        self.topk = check_topk_options(topk, track_vote, bool(track) or track_config is not None)
+        self.track_vote = track_vote
         merge_set = [n for n, v in (("view_match", view_match), ("view_merge", view_merge), ("view_match_thr", view_match_thr)) if v is not None]
         if merge_set and all(v is None for v in (tile_overlap, views, view_tile, focus)):
             raise ValueError(f"{', '.join(merge_set)} need one of tile_overlap, views, view_tile or focus: a frame seen through one "
@@ -1317,6 +1416,9 @@ class HybridPipeline:
                              numerics=numerics, cls_arch=classifier_arch if classifier_arch in CLS_ARCHS else "shufflenetv2")
         self.engine.set_input_format(pixel_format, csc_matrix)
         self.pixel_format, self.csc_matrix = pixel_format, csc_matrix
+        if self.topk:
+            self.engine.topk_enable(self.topk)
+        self._topk_parts: List[np.ndarray] = []   # the lp_topk records of a run_batch's engine calls, in frame order
         if merge_set:
             self.engine.set_view_merge(view_match or "iou", view_merge or "nms", 0.0 if view_match_thr is None else view_match_thr)
         self.detector = NCNNDetector(detector_param, detector_bin, det_input_size, use_gpu_detector, detector_threads,
@@ -1356,6 +1458,8 @@ class HybridPipeline:
                            cls_input=cls_input_size, device=device, max_rois=lane_rois, numerics=numerics, cls_arch=self.engine.cls_arch)
                 e.load_detector(detector_param, detector_bin)
                 e.load_classifier(self.classifier.state_dict)
+                if self.topk:
+                    e.topk_enable(self.topk)
                 self._lanes.append(e)
             self._lane_pool = ThreadPoolExecutor(max_workers=n_lanes, thread_name_prefix="litepi-lane")
             self._lane_cap = lane_cap
@@ -1381,7 +1485,7 @@ class HybridPipeline:
             k, lo, hi = arg
             e = self._lanes[k]
             d, c, nd, t = e.run_batch(images[lo:hi], conf, iou, min_area)
-            return d, c, nd, t, e.last_det_conf_avg
+            return d, c, nd, t, e.last_det_conf_avg, (e.topk_read(hi - lo) if self.topk else None)
 
         parts = list(self._lane_pool.map(one, slices))
         dets = np.concatenate([p[0] for p in parts], 0)
@@ -1391,6 +1495,8 @@ class HybridPipeline:
         for f in ("t_detection", "t_roi_extract", "t_classification", "t_total"):   # the lanes run side by side: the longest one
             setattr(timing, f, max(getattr(p[3], f) for p in parts))
         self.engine.last_det_conf_avg = np.concatenate([p[4] for p in parts])
+        if self.topk:
+            self._topk_parts = [p[5] for p in parts]
         return dets, counts, num_det, timing
 
     def _run_grouped(self, images, feed, verb, frame_views, call):
@@ -1425,6 +1531,8 @@ class HybridPipeline:
         for g, key in groups:
             d, c, nd, t = call(g, key)
             parts.append((d, c, nd, t, self.engine.last_det_conf_avg))
+            if self.topk:   # the buffer holds the last engine call's records: read before the next call replaces them
+                self._topk_parts.append(self.engine.topk_read(len(g)))
             if feed is not None:
                 feed(d[:len(g)], c[:len(g)], done)
             done += len(g)
@@ -1473,18 +1581,25 @@ class HybridPipeline:
             return d, c, nd, t
         return self._run_groups(groups, feed, call)
 
-    def _track(self, dets, counts, stream_ids):
+    def _track_call(self, dets, counts, ids, topk):
+        """one tracker call under the pipeline's vote: lp_track, or lp_track_topk on the frames' lp_topk records"""
+        if self.track_vote == "distribution":
+            return self.engine.track_topk(dets, counts, topk, ids)
+        return self.engine.track(dets, counts, ids)
+
+    def _track(self, dets, counts, stream_ids, topk=None):
         """the call's records through the engine's tracker, at most max_batch frames per lp_track call, in frame order"""
         B, cap = len(counts), self.engine.cfg.max_batch
         ids = None if stream_ids is None else np.asarray(stream_ids, dtype=np.int32)
-        parts = [self.engine.track(dets[i:i + cap], counts[i:i + cap], None if ids is None else ids[i:i + cap]) for i in range(0, B, cap)]
+        parts = [self._track_call(dets[i:i + cap], counts[i:i + cap], None if ids is None else ids[i:i + cap],
+                                  None if topk is None else topk[i:i + cap]) for i in range(0, B, cap)]
         return np.concatenate(parts, 0)
 
-    def _feed(self, dets, counts, stream_ids, first):
+    def _feed(self, dets, counts, stream_ids, first, topk=None):
         """one engine call's records through the tracker and, while the handle still holds that call's crops, the inventory"""
         cnt = np.asarray(counts, dtype=np.int32)
         ids = None if stream_ids is None else stream_ids[first:first + len(cnt)]
-        tracks = self.engine.track(dets, cnt, ids)
+        tracks = self._track_call(dets, cnt, ids, topk)
         if self.inventory:
             self.engine.inventory(dets, cnt, tracks, ids, crops=bool(self.engine.inv_cfg.keep_crops))
         return tracks
@@ -1536,10 +1651,11 @@ class HybridPipeline:
 
         def feed(d, c, first):   # a failure of the tracker or the inventory is never taken for an engine failure below
             try:
-                fed.append(self._feed(d, c, ids, first))
+                fed.append(self._feed(d, c, ids, first, self._topk_parts[-1] if self.topk else None))
             except _ffi.LitepiError as e:
                 e.from_feed = True
                 raise
+        self._topk_parts = []
         t0 = time.perf_counter()
         try:
             if self.focus is not None:
@@ -1553,20 +1669,23 @@ class HybridPipeline:
                 dets, counts, num_det, timing = self._run_lanes(list(images), conf_threshold, iou_threshold, min_area)
             else:
                 dets, counts, num_det, timing = self.engine.run_batch(images, conf_threshold, iou_threshold, min_area)
+                if self.topk:
+                    self._topk_parts.append(self.engine.topk_read(len(images)))
         except _ffi.LitepiError as e:
             if e.code != _ffi.LP_ERR_HIP or getattr(e, "from_feed", False):  # misuse / capacity errors are raised, only an engine failure yields "nothing found"
                 raise
             print(f"[HIP Pipeline] engine failure, returning no detections: {e}")
             return [([], PipelineMetrics()) for _ in images]
         tracks = None
+        topk = np.concatenate(self._topk_parts, 0) if self.topk else None
         if do_track:
             B = len(images)
             if self.tile_overlap is not None or self.view_mode or self.focus is not None:
                 tracks = np.concatenate(fed, 0)
             elif self.inventory:   # one engine call on this handle
-                tracks = self._feed(dets[:B], counts[:B], ids, 0)
+                tracks = self._feed(dets[:B], counts[:B], ids, 0, topk)
             else:
-                tracks = self._track(dets[:B], np.asarray(counts[:B], dtype=np.int32), stream_ids)
+                tracks = self._track(dets[:B], np.asarray(counts[:B], dtype=np.int32), stream_ids, topk)
         wall_ms = (time.perf_counter() - t0) * 1000.0   # t_total ends here; system metrics are sampled after it (e2e.py:505-516)
         conf_avg = self.engine.last_det_conf_avg
         sysm = _system_metrics()
@@ -1593,6 +1712,9 @@ class HybridPipeline:
         t_det, t_roi, t_cls, t_tot = timing.t_detection / B, timing.t_roi_extract / B, timing.t_classification / B, wall_ms / B
         fps = 1000.0 / t_tot if t_tot > 0 else 0
         cpu_p, mem_mb, temp = sysm
+        if topk is not None:   # the valid entries of every used record, [(class, prob), ...]
+            ku = topk[:B][np.arange(topk.shape[1])[None, :] < cnt_a[:, None]]
+            topk_cols = [[(c, p) for c, p in zip(cs, ps) if c >= 0] for cs, ps in zip(ku["cls"].tolist(), ku["prob"].astype(np.float64).tolist())]
         if tracks is not None:
             tu = tracks[:B][np.arange(tracks.shape[1])[None, :] < cnt_a[:, None]]
             trk_cols = list(zip(tu["track_id"].tolist(), tu["hits"].tolist(), tu["age"].tolist(), tu["voted_class"].tolist(),
@@ -1613,6 +1735,9 @@ class HybridPipeline:
                 e = pos + n
                 results = [{"bbox": bb, "det_class": dc, "det_conf": df, "cls_class": cc, "cls_conf": cf, "time_det": td, "time_cls": tc}
                            for bb, dc, df, cc, cf in zip(boxes[pos:e], det_cls[pos:e], det_cf[pos:e], cls_cls[pos:e], cls_cf[pos:e])]
+                if topk is not None:
+                    for r, tk in zip(results, topk_cols[pos:e]):
+                        r["cls_topk"] = tk
                 if tracks is not None:
                     for r, (tid, th, ta, tc_, tcc, tok) in zip(results, trk_cols[pos:e]):
                         r.update(track_id=tid, track_hits=th, track_age=ta, track_cls=tc_, track_cls_conf=tcc, track_confirmed=tok)

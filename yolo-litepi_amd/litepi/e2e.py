@@ -135,6 +135,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--track_iou", type=float, default=0.3, help="a detection matches a track when their IoU exceeds this")
     p.add_argument("--track_max_age", type=int, default=5, help="frames a track may stay unmatched before it is dropped")
     p.add_argument("--track_min_hits", type=int, default=3, help="matched frames after which a track counts as confirmed")
+    p.add_argument("--topk", type=int, default=None, metavar="K",
+                   help="off when absent: every result also carries the K (1..8) most probable classes of the classifier's "
+                        "distribution with their probabilities (cls_topk); the CSV files and the overlays stay as they are")
+    p.add_argument("--track_vote", type=str, choices=["top1", "distribution"], default="top1",
+                   help="with --track: what a detection adds to its track's class vote -- top1: its arg-max class and confidence; "
+                        "distribution: its K most probable classes, each with its probability (needs --topk K)")
     p.add_argument("--no_jit", action="store_true", help="accepted and ignored: there is no TorchScript on this path (e2e_optimize.py:884)")
     return p
 
@@ -430,6 +436,12 @@ def check_frame_args(args) -> None:
             raise SystemExit("--focus needs --track: the windows are chosen from the tracker's state")
         if not 1 <= args.focus <= 16:
             raise SystemExit(f"--focus {args.focus} outside 1..16 window slots")
+    topk, vote = getattr(args, "topk", None), getattr(args, "track_vote", "top1")
+    if topk is not None and not 1 <= topk <= 8:
+        raise SystemExit(f"--topk {topk} outside 1..8 classes per detection")
+    if vote == "distribution" and not (getattr(args, "track", False) and topk is not None):
+        raise SystemExit("--track_vote distribution needs --track and --topk K: the tracker then votes with every detection's "
+                         "K most probable classes")
     if getattr(args, "inventory", False) and not getattr(args, "track", False):
         raise SystemExit("--inventory needs --track: the inventory lists the tracker's finished tracks")
     if getattr(args, "inventory_evidence", None) is not None or getattr(args, "inventory_evidence_scale", None) is not None:
@@ -536,6 +548,10 @@ def run_evaluation(args) -> Dict:
         track_kw["evidence"] = dict(size=args.inventory_evidence)
         if getattr(args, "inventory_evidence_scale", None) is not None:
             track_kw["evidence"]["scale"] = args.inventory_evidence_scale
+    if getattr(args, "topk", None) is not None:   # absent: the pipeline is constructed exactly as before
+        track_kw["topk"] = args.topk
+        if getattr(args, "track_vote", "top1") != "top1":
+            track_kw["track_vote"] = args.track_vote
     bench_kw, eval_kw = (dict(track=True), dict(track=False)) if args.track else ({}, {})
     with contextlib.redirect_stdout(io.StringIO()) if rank != 0 else contextlib.nullcontext():   # one banner, rank 0's
         pipeline = HybridPipeline(args.detector_param, args.detector_bin, args.classifier, args.clf_arch, num_classes,
