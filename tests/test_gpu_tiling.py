@@ -152,6 +152,133 @@ def test_nms_views_union_beyond_one_lds_sort(eng32):
     _check_nms_views(eng32, b, s, c, v, a, 3)
 
 
+def _one_view_candidates(n, nc, seed):
+    """n clustered candidates of one view with exact score ties, anchors = their indices; every seventh box is a few pixels
+    small, so that min_area 50 drops some and passes others"""
+    rng = np.random.default_rng(seed)
+    b, s, c, v, _ = _random_views(rng, 1, n, nc)
+    small = np.arange(3, n, 7)
+    b[small, 2:] = b[small, :2] + rng.uniform(3, 9, (len(small), 2)).astype(np.float32)
+    return b, s, c, v, np.arange(n, dtype=np.int32)
+
+
+def _same_from_both_hooks(eng, cand, max_det, min_area, H=2048, W=2048):
+    """the image NMS (test_nms_boxes) and the frame NMS of ONE view (test_nms_views) on the same list: byte-equal records,
+    rects and counts, and both equal to the oracle (per-class reference NMS, its tie rule, then the ROI rule)"""
+    from oracle import postprocess_ref as P
+    b, s, c, v, a = cand
+    img = eng.test_nms_boxes(b, s, c, (H, W), 0.45, min_area, max_det or 0)
+    frm = eng.test_nms_views(b, s, c, v, a, 1, (H, W), 0.45, min_area, max_det or 0)
+    assert img[2] == frm[2] and len(img[0]) == len(frm[0])
+    assert img[0].tobytes() == frm[0].tobytes(), "records differ between the image NMS and the one-view frame NMS"
+    assert np.array_equal(img[1], frm[1])
+    k = T.merge(b, s, c, v, a, 0.45, max_det)
+    assert img[2] == len(k)
+    rects, valid = P.roi_rects(b[k], H, W, min_area)
+    kv = k[valid]
+    d = img[0]
+    assert len(d) == len(kv)
+    got = np.stack([d["x1"], d["y1"], d["x2"], d["y2"]], 1) if len(d) else np.zeros((0, 4), np.float32)
+    assert np.array_equal(got.view(np.uint32), b[kv].view(np.uint32)), "boxes / order differ from the oracle"
+    assert np.array_equal(d["det_conf"].view(np.uint32), s[kv].view(np.uint32)) and np.array_equal(d["det_class"], c[kv])
+    assert np.array_equal(img[1], rects)
+    return len(k), len(kv)
+
+
+@pytest.mark.parametrize("nc", [1, 3])
+def test_one_view_frame_nms_is_the_image_nms(eng32, monkeypatch, nc):
+    """the image NMS is the one-view case of the frame NMS: one core (nms_dev.h) behind both hooks.  Counts around the one-wave
+    limit and the chunk size; max_det 0 (keep all) and a max_det below the survivors (nc 1: the sweep's early exit, nc 3: the
+    threshold-key cut); counts <= 64 also with the one-wave path switched off."""
+    dropped = 0
+    for n in (0, 1, 64, 65, 128, 129, 200, 700):
+        cand = _one_view_candidates(n, nc, 100 * nc + n)
+        nk, nv = _same_from_both_hooks(eng32, cand, None, 50)
+        dropped += nk - nv
+        cuts = [None] + ([max(1, nk // 2)] if nk >= 2 else [])   # (0 or 1 survivors: no max_det lies below them)
+        for max_det in cuts[1:]:
+            assert _same_from_both_hooks(eng32, cand, max_det, 50)[0] == max_det
+        if n <= 64:
+            monkeypatch.setenv("LITEPI_NMS_NO_SMALL", "1")
+            try:
+                for max_det in cuts:
+                    _same_from_both_hooks(eng32, cand, max_det, 50)
+            finally:
+                monkeypatch.delenv("LITEPI_NMS_NO_SMALL")
+    assert dropped >= 1, "min_area dropped nothing: the filter is not exercised"
+
+
+def _chunk_clusters(n, seed):
+    """n candidates of two classes with distinct scores, view-major over three views: n // 8 disjoint cluster heads hold the top
+    scores, every other box is a jittered copy of a random head with a lower score.  In the sweep's order the heads come first
+    in their class and take members from every later chunk of 64; members that escape their head become keepers further back.
+    Class 0 is a quarter of the clusters, so class 1's heads still lie in the first chunk and its members reach to the end."""
+    rng = np.random.default_rng(seed)
+    nh = max(2, n // 8)
+    gx, gy = np.divmod(np.arange(nh), 6)
+    heads = np.stack([gx * 70 + 10, gy * 70 + 10, gx * 70 + 50, gy * 70 + 50], 1).astype(np.float32)
+    of = rng.integers(0, nh, n - nh)
+    jit = rng.normal(0, 5, (n - nh, 4)).astype(np.float32)
+    b = np.concatenate([heads, heads[of] + jit]).clip(0, 2048).astype(np.float32)
+    c = np.concatenate([np.arange(nh) % 4 != 0, of % 4 != 0]).astype(np.int32)
+    s = np.linspace(0.99, 0.30, n).astype(np.float32)
+    s[nh:] = s[nh:][rng.permutation(n - nh)]
+    p = rng.permutation(n)   # candidate order says nothing about the score
+    b, s, c = b[p], s[p], c[p]
+    v = np.sort(np.arange(n) % 3).astype(np.int32)
+    a = np.concatenate([np.arange((v == k).sum()) for k in range(3)]).astype(np.int32)
+    return b, s, c, v, a
+
+
+def _cross_chunk(cand, metric):
+    """from the oracle alone: the largest distance, in chunks of 64 of the sweep's order, between an absorbed box and its keeper"""
+    import view_merge_ref as VM
+    pos = np.empty(len(cand[1]), np.int64)
+    pos[VM.order(*cand[1:])] = np.arange(len(pos))
+    _, _, owner = VM.merge(*cand, 0.45, None, metric, VM.SUPPRESS, owners=True)
+    return int((pos // 64 - pos[owner] // 64).max())
+
+
+@pytest.mark.parametrize("n", [65, 127, 128, 129, 193])
+def test_nms_chunk_boundaries(eng32, n):
+    """a keeper of chunk k suppresses (and, under union, absorbs) boxes of chunks k + 1 and, where the list has a third chunk,
+    k + 2: the outer phase of the sweep.  The image kernel against the reference's NMS, the frame kernel under all four
+    (match, merge) settings against view_merge_ref."""
+    import view_merge_ref as VM
+    from oracle import postprocess_ref as P
+    cand = _chunk_clusters(n, 40 + n)
+    b, s, c, v, a = cand
+    assert len(np.unique(s)) == n
+    reach = min(2, (n - 1) // 64)
+    for metric in (VM.IOU, VM.IOS):
+        assert _cross_chunk(cand, metric) >= reach, "no keeper reaches that far: the case is vacuous"
+    # the image kernel: one view, anchors = indices; the scores are distinct, so the order is the same
+    k = T.merge(b, s, c, np.zeros(n, np.int32), np.arange(n), 0.45)
+    assert np.array_equal(k, T.merge(b, s, c, v, a, 0.45)) and 2 <= len(k) < n
+    d, _, num = eng32.test_nms_boxes(b, s, c, (2048, 2048), 0.45, -1, 0)
+    assert num == len(k) == len(d)
+    assert np.array_equal(np.stack([d["x1"], d["y1"], d["x2"], d["y2"]], 1).view(np.uint32), b[k].view(np.uint32))
+    assert np.array_equal(d["det_conf"].view(np.uint32), s[k].view(np.uint32)) and np.array_equal(d["det_class"], c[k])
+    _check_nms_views(eng32, b, s, c, v, a, 3)
+    for match, metric in (("iou", VM.IOU), ("ios", VM.IOS)):
+        for merge, mode in (("nms", VM.SUPPRESS), ("union", VM.UNION)):
+            eng32.set_view_merge(match, merge, 0.0)
+            try:
+                d, _, num = eng32.test_nms_views(b, s, c, v, a, 3, (2048, 2048), 0.45, -1, 0)
+            finally:
+                eng32.set_view_merge()
+            kk, out = VM.merge(b, s, c, v, a, 0.45, None, metric, mode)
+            assert num == len(kk) == len(d), f"{match}+{merge}"
+            assert np.array_equal(np.stack([d["x1"], d["y1"], d["x2"], d["y2"]], 1).view(np.uint32), out.view(np.uint32)), f"{match}+{merge}"
+            assert np.array_equal(d["det_conf"].view(np.uint32), s[kk].view(np.uint32)) and np.array_equal(d["det_class"], c[kk])
+            if mode == VM.UNION:   # a grown box whose absorbed boxes lie in a later chunk than the keeper
+                pos = np.empty(n, np.int64)
+                pos[VM.order(s, c, v, a)] = np.arange(n)
+                owner = VM.merge(b, s, c, v, a, 0.45, None, metric, mode, owners=True)[2]
+                far = [i for i, o in zip(kk, out) if (o != b[i]).any() and (pos[owner == i] // 64 > pos[i] // 64).any()]
+                assert far, f"{match}+union: no union reaches into a later chunk"
+
+
 # ---------------------------------------------------------------------------- 3. fp32 end to end against the tiling oracle
 @pytest.mark.parametrize("full_frame", [1, 0])
 def test_tiled_fp32_end_to_end_vs_oracle(models, full_frame):

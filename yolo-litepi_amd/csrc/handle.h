@@ -325,6 +325,10 @@ void enqueue_letterbox(const uint8_t* src, const ImgGeom* d_geom, uint8_t* dst, 
                        Profiler* prof);
 // detector (+ optional letterbox) on images resident at src with geometry already uploaded
 void enqueue_detect(lp_handle* h, const uint8_t* src, const std::vector<ImgGeom>& geoms, int B, float conf, float* out0, Profiler* prof);
+// the arguments the image NMS and the frame NMS share: results into dets / counts / rects, A anchors of nc classes; the ROI
+// rule, the ROI list (with_rois) and its capacity are the handle's
+NmsCommon nms_common(lp_handle* h, lp_det* dets, int* counts, int* rects, int A, int nc, int max_det, float iou, int min_area,
+                     bool with_rois);
 // NMS + ROI rectangles; with_rois: also the batch-wide ROI list the classifier stage consumes
 void enqueue_nms(lp_handle* h, int B, float iou, int min_area, lp_det* dets, int* counts, bool with_rois, Profiler* prof);
 // PIL resize + classifier + softmax over the ROI list; stage 0 = both halves, 1 = only the ROI resize, 2 = only the classifier;

@@ -73,14 +73,11 @@ struct RoiTable {
   int* work;      // [2] accumulator + ticket of the NMS blocks (zero between calls)
 };
 
-struct NmsArgs {
-  const Cand* cand;       // [N][A]
-  int* cand_count;        // [N]   (reset to 0 by the kernel for the next call)
-  Cand* sorted;           // [N][A] scratch
+// what the image NMS and the frame NMS of views share (nms_dev.h): results, limits, the ROI rule and the ROI list
+struct NmsCommon {
   lp_det* dets;           // [N][max_det]
   int* counts;            // [3N]: kept-after-filter, kept-before-filter, float bits of the mean score before the filter
   int* rects;             // [N][max_det][4] int ROI rectangles of the kept boxes
-  const ImgGeom* geom;
   int A, max_det, nc;
   float iou;
   int min_area;           // < 0: no ROI filter (lp_detect semantics)
@@ -88,6 +85,16 @@ struct NmsArgs {
   int max_rois;
   int roi_rule;           // 0: e2e.py:465-473, 1: e2e_optimize.py:480-497 (lp_config::numerics)
   int no_small;           // A/B + tests (LITEPI_NMS_NO_SMALL=1): every image takes the general path
+};
+// no_small as a launch sees it: set in the arguments or by LITEPI_NMS_NO_SMALL
+int nms_no_small(int no_small);
+
+struct NmsArgs {
+  const Cand* cand;       // [N][A]
+  int* cand_count;        // [N]   (reset to 0 by the kernel for the next call)
+  Cand* sorted;           // [N][A] scratch
+  const ImgGeom* geom;    // [N]
+  NmsCommon c;            // per image
 };
 // per-class greedy NMS (e2e.py:89-119,280-296) + ROI clip / area filter (e2e.py:465-473) + the batch's ROI list
 void launch_nms(const NmsArgs& a, int N, hipStream_t st);
@@ -122,18 +129,9 @@ struct FrameNmsArgs {
   Cand* sorted;           // [V][A] per-view sorted candidates
   const TileFrame* frames;  // [F]
   const int* vslot;       // [V]   view batch slot of the frames' views, frame-major
-  lp_det* dets;           // [F][max_det]
-  int* counts;            // [3F] as NmsArgs::counts, per frame
-  int* rects;             // [F][max_det][4]
   const ImgGeom* fgeom;   // [F] frame geometry (size, src_off)
-  int A, max_det, nc;
-  float iou;
-  int min_area;
-  RoiTable tab;
-  int max_rois;
-  int roi_rule;
-  int no_small;
-  int metric, mode;       // lp_match / lp_merge (lp_set_view_merge); 0, 0 = the reference's rule.  iou then holds the resolved threshold
+  NmsCommon c;            // per frame; iou holds the resolved threshold of lp_set_view_merge
+  int metric, mode;       // lp_match / lp_merge (lp_set_view_merge); 0, 0 = the reference's rule
 };
 // per-view sort (one workgroup per view slot, V slots), then the merged per-class greedy NMS of every frame (one workgroup
 // per frame; max_views bounds the views of one frame: it sizes the LDS flag masks)

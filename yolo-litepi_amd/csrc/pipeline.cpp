@@ -75,16 +75,25 @@ static bool skip_stage(const lp_handle* h, const char* name, const Profiler* pro
   return !prof && h->graph_clock > 1 && h->opt.skip_stage == name;
 }
 
+NmsCommon nms_common(lp_handle* h, lp_det* dets, int* counts, int* rects, int A, int nc, int max_det, float iou, int min_area,
+                     bool with_rois) {
+  NmsCommon c;
+  memset(&c, 0, sizeof(c));
+  c.dets = dets; c.counts = counts; c.rects = rects;
+  c.A = A; c.max_det = max_det; c.nc = nc; c.iou = iou; c.min_area = min_area;
+  if (with_rois) c.tab = h->roi_table();
+  c.max_rois = h->max_rois;
+  c.roi_rule = h->cfg.numerics;
+  return c;
+}
+
 // NMS + ROI rectangles; with_rois: also the batch-wide ROI list the classifier stage consumes
 void enqueue_nms(lp_handle* h, int B, float iou, int min_area, lp_det* dets, int* counts, bool with_rois, Profiler* prof) {
   NmsArgs a;
   memset(&a, 0, sizeof(a));
   a.cand = h->d_cand.as<Cand>(); a.cand_count = h->d_cand_count.as<int>(); a.sorted = h->d_sorted.as<Cand>();
-  a.dets = dets; a.counts = counts; a.rects = h->d_rects.as<int>(); a.geom = h->d_geom.as<ImgGeom>();
-  a.A = h->det->num_anchors(); a.max_det = h->cfg.max_det; a.nc = h->det->num_classes(); a.iou = iou; a.min_area = min_area;
-  if (with_rois) a.tab = h->roi_table();
-  a.max_rois = h->max_rois;
-  a.roi_rule = h->cfg.numerics;
+  a.geom = h->d_geom.as<ImgGeom>();
+  a.c = nms_common(h, dets, counts, h->d_rects.as<int>(), h->det->num_anchors(), h->det->num_classes(), h->cfg.max_det, iou, min_area, with_rois);
   if (skip_stage(h, "nms", prof)) return;
   if (prof) prof->begin(h->stream);
   launch_nms(a, B, h->stream);

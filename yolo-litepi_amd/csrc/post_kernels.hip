@@ -6,6 +6,7 @@
 // so that for the same out0 tensor the kept set is identical to the NumPy result.
 #include "common.h"
 #include "kernels.h"
+#include "nms_dev.h"
 #include "post_dev.h"
 #include <atomic>
 #include <cstdlib>
@@ -124,42 +125,26 @@ void launch_filter_out0(const float* out0, int nc, int A, const ImgGeom* geom, C
 }
 
 // ------------------------------------------------------------------------------------
-// Per-class greedy NMS, one workgroup per image.
-//   1. key = (0xFFFF - class, score bits, anchor): a descending bitonic sort in LDS gives
-//      class ascending, score descending, ties -> higher anchor first (the order a stable
-//      ascending argsort reversed gives; e2e.py:96).
-//   2. greedy sweep over the sorted boxes in chunks of 64 (one box per lane of wave 0): inside a
-//      chunk the survivors are found with wave64 ballot masks -- box i, still alive, suppresses
-//      every later lane of its class with IoU > thr, the ballot of those lanes clears them from
-//      the alive mask, no barrier; the chunk's survivors then suppress all later chunks in
-//      parallel over the workgroup (one barrier pair per 64 boxes instead of one per kept box).
-//      IoU is the reference's fp32 expression inter / (area_i + area_j - inter + 1e-6)
-//      (e2e.py:106-116) in its operation order, so the kept set is the NumPy one.
-//   3. max_det: the reference keeps every survivor.  When more than max_det survive, the
-//      max_det highest-scoring ones (over all classes) stay and are emitted in the reference's
-//      class-major order; with a single class that is the head of the list, so the sweep stops early.
-//   4. ROI rectangle (int truncation, clip) and area filter (e2e.py:465-473) of the kept
-//      boxes, order-preserving compaction into the lp_det records, and -- when a ROI table is
-//      given -- the image's slice of the batch-wide ROI list (one atomicAdd per image).
+// Per-class greedy NMS, one workgroup per image: the image front end of the core in nms_dev.h.  The candidates are sorted by
+// nms_key (class ascending, score descending, ties -> higher anchor first) and handed to nms_finish<false, false>: the
+// reference's rule, the one-view case of the frame NMS (tile_kernels.hip).
 // ------------------------------------------------------------------------------------
-size_t nms_lds_bytes(int A) {
+size_t nms_lds_bytes(int A) {   // the sort's keys; the general path's flag masks overlay them once the sort is done
   int npad = 1;
   while (npad < A) npad <<= 1;
-  return (size_t)npad * 8 + (size_t)round_up(A, 16) + 16;
+  return (size_t)npad * 8 + 16;
 }
 
-// At most 64 candidates (the usual image: a handful of anchors pass conf 0.25), none of which max_det can cut: ONE wave does the whole image
-// in registers -- lane i loads candidate i, the 64 keys are bitonic-sorted with lane shuffles (21 compare-exchange steps, the
-// source lane travels with the key), the records are gathered from their source lanes, then the same __ballot sweep, ROI
-// rule, compaction and ROI-list bookkeeping as the general path below: identical results (same keys, same arithmetic), none of
-// its ~12 sixteen-wave barriers, LDS passes and global round trips (scratch `sorted`, binary search).  25 -> ~8 us per launch.
+// One-wave path (nms_small_tail): lane i loads candidate i, the 64 keys are bitonic-sorted with lane shuffles (21
+// compare-exchange steps, the source lane travels with the key), the records are gathered from their source lanes.
+// Same keys as the LDS sort, so the same order.  25 -> ~8 us per launch.
 __device__ __forceinline__ void nms_small(const NmsArgs& a, int n, int cnt, int nimg) {
   const int lane = threadIdx.x & 63;
-  const Cand* cand = a.cand + (long)n * a.A;
+  const Cand* cand = a.cand + (long)n * a.c.A;
   Cand c;
   c.x1 = c.y1 = c.x2 = c.y2 = c.score = 0.f; c.cls = -1; c.anchor = 0; c.pad = 0;
   if (lane < cnt) c = cand[lane];
-  unsigned long long key = lane < cnt ? nms_key(c) : 0ull;   // (a real key is never 0: that would take class 65535)
+  unsigned long long key = lane < cnt ? nms_key(c) : 0ull;   // the zero keys of the empty lanes sort behind every real one
   int src = lane;
   // (rolled on purpose: one wave executes this once per image, from a cold instruction cache -- 21 unrolled stages were ~2.5 KB of
   //  straight-line code, each 64-byte line a fetch from L2 that nothing hides)
@@ -179,265 +164,38 @@ __device__ __forceinline__ void nms_small(const NmsArgs& a, int n, int cnt, int 
   Cand bj;
   bj.x1 = __shfl(c.x1, src); bj.y1 = __shfl(c.y1, src); bj.x2 = __shfl(c.x2, src); bj.y2 = __shfl(c.y2, src);
   bj.score = __shfl(c.score, src); bj.cls = __shfl(c.cls, src); bj.anchor = __shfl(c.anchor, src); bj.pad = 0;
-  const bool valid = lane < cnt;   // the zero keys of the empty lanes sort behind every real one
-  const float aj = __fmul_rn(__fsub_rn(bj.x2, bj.x1), __fsub_rn(bj.y2, bj.y1));
-  unsigned long long alive = __ballot(valid);
-  unsigned long long todo = alive, kept = 0ull;
-  const float thr = a.iou;
-  while (todo) {  // wave-uniform
-    const int i = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    kept |= 1ull << i;
-    const float ix1 = __shfl(bj.x1, i), iy1 = __shfl(bj.y1, i), ix2 = __shfl(bj.x2, i), iy2 = __shfl(bj.y2, i);
-    const float ai = __shfl(aj, i);
-    const int ic = __shfl(bj.cls, i);
-    const bool sup = lane > i && ((alive >> lane) & 1ull) && bj.cls == ic && nms_suppressed(ix1, iy1, ix2, iy2, ai, bj.x1, bj.y1, bj.x2, bj.y2, thr);
-    const unsigned long long m = __ballot(sup);
-    alive &= ~m;
-    todo &= ~m;
-  }
-  const bool is_kept = (kept >> lane) & 1ull;
-  const int nsel = __popcll(kept);   // <= cnt <= max_det: nothing to cut
-  const ImgGeom gm = a.geom[n];
-  int x1 = 0, y1 = 0, x2 = 0, y2 = 0;
-  const bool ok = is_kept && roi_rect(bj, gm, a.roi_rule, a.min_area, x1, y1, x2, y2);
-  const unsigned long long okm = __ballot(ok);
-  const int o = __popcll(okm & ((1ull << lane) - 1ull)), run = __popcll(okm);
-  double ssum = is_kept ? (double)bj.score : 0.0;
-  for (int off = 32; off > 0; off >>= 1) ssum += __shfl_xor(ssum, off);
-  int base = 0;
-  if (lane == 0) {
-    a.counts[n] = run;
-    a.counts[nimg + n] = nsel;
-    reinterpret_cast<float*>(a.counts)[2 * nimg + n] = nsel > 0 ? (float)(ssum / (double)nsel) : 0.f;
-    a.cand_count[n] = 0;  // ready for the next call
-    if (a.tab.total) {   // (the ROI list protocol of the general path)
-      base = atomicAdd(a.tab.work, run);
-      int one = 1;
-      asm volatile("" : "+v"(one) : "v"(base));
-      const int ticket = atomicAdd(a.tab.work + 1, one);
-      if (ticket == nimg - 1) {
-        const int raw = atomicExch(a.tab.work, 0);
-        atomicExch(a.tab.work + 1, 0);
-        a.tab.total[0] = raw < a.max_rois ? raw : a.max_rois;
-        a.tab.total[1] = raw;
-      }
-    }
-  }
-  base = __shfl(base, 0);
-  if (ok) {
-    lp_det d;
-    d.x1 = bj.x1; d.y1 = bj.y1; d.x2 = bj.x2; d.y2 = bj.y2; d.det_conf = bj.score; d.det_class = bj.cls;
-    d.cls_class = -1; d.cls_conf = 0.f;
-    a.dets[(long)n * a.max_det + o] = d;
-    int* rects = a.rects + ((long)n * a.max_det + o) * 4;
-    rects[0] = x1; rects[1] = y1; rects[2] = x2; rects[3] = y2;
-    if (a.tab.total && base + o < a.max_rois) { a.tab.img[base + o] = n; a.tab.slot[base + o] = o; }
-  }
+  nms_small_tail<false, false>(a.c, a.geom[n], n, nimg, bj, cnt);
+  if (lane == 0) a.cand_count[n] = 0;  // ready for the next call
 }
 
 __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ int s_wave[NMS_THREADS / 64 + 1];
-  __shared__ float s_chunk[64 * 6];  // kept boxes of the current chunk: x1, y1, x2, y2, area, class bits
-  __shared__ int s_nk, s_base;
-  __shared__ double s_red[NMS_THREADS / 64];
-  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = blockIdx.x;
   int cnt = a.cand_count[n];
-  cnt = cnt > a.A ? a.A : cnt;
-  if (cnt <= 64 && cnt <= a.max_det && !a.no_small) {   // block-uniform: the other 15 waves leave before any barrier
-    if (wave == 0) nms_small(a, n, cnt, (int)gridDim.x);
+  cnt = cnt > a.c.A ? a.c.A : cnt;
+  if (cnt <= 64 && cnt <= a.c.max_det && !a.c.no_small) {   // block-uniform: the other 15 waves leave before any barrier
+    if (threadIdx.x < 64) nms_small(a, n, cnt, (int)gridDim.x);
     return;
   }
-  int npad = 1;
-  while (npad < a.A) npad <<= 1;
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);
-  unsigned char* removed = reinterpret_cast<unsigned char*>(smem + (size_t)npad * 8);
-  const Cand* cand = a.cand + (long)n * a.A;
-  Cand* sorted = a.sorted + (long)n * a.A;
-  int nsort = 1;
-  while (nsort < cnt) nsort <<= 1;
+  Cand* sorted = a.sorted + (long)n * a.c.A;
+  nms_sort_to(reinterpret_cast<unsigned long long*>(smem), a.cand + (long)n * a.c.A, sorted, cnt);
+  __syncthreads();   // the keys are dead from here on
+  nms_finish<false, false>(a.c, a.geom[n], sorted, cnt, n, (int)gridDim.x, reinterpret_cast<unsigned*>(smem));
+  if (threadIdx.x == 0) a.cand_count[n] = 0;  // ready for the next call
+}
 
-  for (int i = tid; i < nsort; i += NMS_THREADS) keys[i] = i < cnt ? nms_key(cand[i]) : 0ull;
-  __syncthreads();
-  for (int k = 2; k <= nsort; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < nsort; i += NMS_THREADS) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long x = keys[i], y = keys[ixj];
-          const bool desc = (i & k) == 0;
-          if (desc ? (x < y) : (x > y)) { keys[i] = y; keys[ixj] = x; }
-        }
-      }
-      __syncthreads();
-    }
-  }
-  // keys are sorted; rebuild the records in sorted order.  The slot of a key inside cand[]
-  // is not stored in it, so each candidate finds its own rank by binary search.
-  for (int i = tid; i < cnt; i += NMS_THREADS) {
-    const Cand c = cand[i];
-    const unsigned long long k = nms_key(c);
-    int lo = 0, hi = cnt - 1;
-    while (lo < hi) {  // descending order
-      const int mid = (lo + hi) >> 1;
-      if (keys[mid] > k) lo = mid + 1; else hi = mid;
-    }
-    sorted[lo] = c;
-    removed[i] = 0;
-  }
-  __syncthreads();
-  __threadfence_block();
-
-  // ---- greedy sweep, 64 boxes per step
-  int* keep = reinterpret_cast<int*>(keys);  // keys are dead from here on
-  int nkeep = 0;
-  const float thr = a.iou;
-  const bool single_class = a.nc <= 1;
-  for (int c0 = 0; c0 < cnt; c0 += 64) {
-    if (wave == 0) {
-      const int j = c0 + lane;
-      const bool valid = j < cnt;
-      Cand bj;
-      bj.x1 = bj.y1 = bj.x2 = bj.y2 = 0.f; bj.cls = -1;
-      if (valid) bj = sorted[j];
-      const float aj = __fmul_rn(__fsub_rn(bj.x2, bj.x1), __fsub_rn(bj.y2, bj.y1));
-      unsigned long long alive = __ballot(valid && !removed[valid ? j : 0]);
-      unsigned long long todo = alive, kept = 0ull;
-      int room = single_class ? a.max_det - nkeep : 0x7fffffff;
-      while (todo && room > 0) {  // wave-uniform
-        const int i = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        kept |= 1ull << i;
-        --room;
-        const float ix1 = __shfl(bj.x1, i), iy1 = __shfl(bj.y1, i), ix2 = __shfl(bj.x2, i), iy2 = __shfl(bj.y2, i);
-        const float ai = __shfl(aj, i);
-        const int ic = __shfl(bj.cls, i);
-        const bool sup = lane > i && ((alive >> lane) & 1ull) && bj.cls == ic &&
-                         nms_suppressed(ix1, iy1, ix2, iy2, ai, bj.x1, bj.y1, bj.x2, bj.y2, thr);
-        const unsigned long long m = __ballot(sup);
-        alive &= ~m;
-        todo &= ~m;
-      }
-      if ((kept >> lane) & 1ull) {
-        const int idx = __popcll(kept & ((1ull << lane) - 1ull));
-        keep[nkeep + idx] = j;
-        float* cb = s_chunk + idx * 6;
-        cb[0] = bj.x1; cb[1] = bj.y1; cb[2] = bj.x2; cb[3] = bj.y2; cb[4] = aj; cb[5] = __int_as_float(bj.cls);
-      }
-      if (lane == 0) s_nk = __popcll(kept);
-    }
-    __syncthreads();
-    const int nk = s_nk;
-    nkeep += nk;
-    // single class: (class, score) order is score order, so the first max_det kept boxes are the answer
-    if (single_class && nkeep >= a.max_det) break;
-    for (int j = c0 + 64 + tid; j < cnt; j += NMS_THREADS) {
-      if (removed[j]) continue;
-      const Cand bj = sorted[j];
-      for (int k = 0; k < nk; ++k) {
-        const float* cb = s_chunk + k * 6;
-        if (__float_as_int(cb[5]) != bj.cls) continue;
-        if (nms_suppressed(cb[0], cb[1], cb[2], cb[3], cb[4], bj.x1, bj.y1, bj.x2, bj.y2, thr)) { removed[j] = 1; break; }
-      }
-    }
-    __syncthreads();
-  }
-  __syncthreads();
-
-  // ---- more survivors than max_det (several classes): the max_det best scores stay.  The (score, anchor) key is
-  //      unique inside an image, so the threshold key T with exactly max_det keys >= T exists; found bit by bit.
-  unsigned long long T = 0ull;
-  int nsel = nkeep;
-  if (nkeep > a.max_det) {
-    if (single_class) {
-      nsel = a.max_det;  // head of the list
-    } else {
-      for (int bit = 45; bit >= 0; --bit) {
-        const unsigned long long candT = T | (1ull << bit);
-        int c = 0;
-        for (int k = tid; k < nkeep; k += NMS_THREADS) c += nms_score_key(sorted[keep[k]]) >= candT ? 1 : 0;
-        int tot;
-        (void)block_exclusive_scan(c, s_wave, &tot);
-        if (tot >= a.max_det) T = candT;
-      }
-      nsel = a.max_det;
-    }
-  }
-  const bool by_key = nkeep > a.max_det && !single_class;
-  const int nlist = by_key ? nkeep : nsel;
-
-  // ---- ROI rectangle + area filter, order-preserving compaction
-  const ImgGeom gm = a.geom[n];
-  const int per = (nlist + NMS_THREADS - 1) / NMS_THREADS;
-  const int k0 = tid * per, k1 = (k0 + per < nlist) ? k0 + per : nlist;
-  int nvalid = 0;
-  double ssum = 0.0;
-  for (int k = k0; k < k1; ++k) {
-    const Cand c = sorted[keep[k]];
-    if (by_key && nms_score_key(c) < T) continue;
-    ssum += (double)c.score;
-    int x1, y1, x2, y2;
-    nvalid += roi_rect(c, gm, a.roi_rule, a.min_area, x1, y1, x2, y2) ? 1 : 0;
-  }
-  int run;
-  int o = block_exclusive_scan(nvalid, s_wave, &run);
-  // mean detector confidence over ALL kept boxes, before the area filter (PipelineMetrics.det_confidence_avg, e2e.py:456-457)
-  for (int off = 32; off > 0; off >>= 1) ssum += __shfl_xor(ssum, off);
-  if (lane == 0) s_red[wave] = ssum;
-  __syncthreads();
-  if (tid == 0) {
-    double tot = 0.0;
-    for (int w = 0; w < NMS_THREADS / 64; ++w) tot += s_red[w];
-    a.counts[n] = run;
-    a.counts[gridDim.x + n] = nsel;
-    reinterpret_cast<float*>(a.counts)[2 * gridDim.x + n] = nsel > 0 ? (float)(tot / (double)nsel) : 0.f;
-    a.cand_count[n] = 0;  // ready for the next call
-    // the image's slice of the batch-wide ROI list: work[0] accumulates, the block that draws the last ticket
-    // (work[1]) publishes the clamped total for the classifier kernels and re-arms both words for the next call.
-    // The ticket is issued only after the slice's add has RETURNED, so the last ticket implies every add is done.
-    int base = 0;
-    if (a.tab.total) {
-      base = atomicAdd(a.tab.work, run);
-      int one = 1;
-      asm volatile("" : "+v"(one) : "v"(base));
-      const int ticket = atomicAdd(a.tab.work + 1, one);
-      if (ticket == (int)gridDim.x - 1) {
-        const int raw = atomicExch(a.tab.work, 0);
-        atomicExch(a.tab.work + 1, 0);
-        a.tab.total[0] = raw < a.max_rois ? raw : a.max_rois;
-        a.tab.total[1] = raw;  // unclamped: the host checks it against the capacity
-      }
-    }
-    s_base = base;
-  }
-  __syncthreads();
-  const int base = s_base;
-  lp_det* dets = a.dets + (long)n * a.max_det;
-  int* rects = a.rects + (long)n * a.max_det * 4;
-  for (int k = k0; k < k1; ++k) {
-    const Cand c = sorted[keep[k]];
-    if (by_key && nms_score_key(c) < T) continue;
-    int x1, y1, x2, y2;
-    if (!roi_rect(c, gm, a.roi_rule, a.min_area, x1, y1, x2, y2)) continue;
-    lp_det d;
-    d.x1 = c.x1; d.y1 = c.y1; d.x2 = c.x2; d.y2 = c.y2; d.det_conf = c.score; d.det_class = c.cls;
-    d.cls_class = -1; d.cls_conf = 0.f;
-    dets[o] = d;
-    rects[o * 4 + 0] = x1; rects[o * 4 + 1] = y1; rects[o * 4 + 2] = x2; rects[o * 4 + 3] = y2;
-    if (a.tab.total && base + o < a.max_rois) { a.tab.img[base + o] = n; a.tab.slot[base + o] = o; }
-    ++o;
-  }
+int nms_no_small(int no_small) {
+  // A/B switch + the path-equivalence tests (read per enqueue: a captured graph keeps what it saw)
+  return getenv("LITEPI_NMS_NO_SMALL") != nullptr ? 1 : no_small;
 }
 
 void launch_nms(const NmsArgs& a, int N, hipStream_t st) {
   set_max_dynamic_lds(reinterpret_cast<const void*>(nms_kernel), 150 * 1024);
-  const size_t lds = nms_lds_bytes(a.A);
-  LP_CHECK(lds <= 150 * 1024, LP_ERR_STATE, "NMS: %d anchors exceed the LDS sort capacity", a.A);
-  LP_CHECK(a.A <= 16384, LP_ERR_STATE, "NMS: anchor index needs more than 14 key bits");
-  const bool no_small = getenv("LITEPI_NMS_NO_SMALL") != nullptr;   // A/B switch + the path-equivalence test (read per enqueue: a captured graph keeps what it saw)
+  const size_t lds = nms_lds_bytes(a.c.A);
+  LP_CHECK(lds <= 150 * 1024, LP_ERR_STATE, "NMS: %d anchors exceed the LDS sort capacity", a.c.A);
+  LP_CHECK(a.c.A <= 16384, LP_ERR_STATE, "NMS: anchor index needs more than 14 key bits");
   NmsArgs b = a;
-  b.no_small = no_small ? 1 : a.no_small;
+  b.c.no_small = nms_no_small(a.c.no_small);
   LP_LAUNCH(nms_kernel, dim3(N), dim3(NMS_THREADS), lds, st, b);
   LP_HIP(hipGetLastError());
 }

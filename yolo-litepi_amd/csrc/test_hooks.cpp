@@ -26,9 +26,8 @@ void nms_one_image(lp_handle* h, const DevBuf& d_geom, const DevBuf& d_cand, con
   d_dets.alloc((size_t)max_det * sizeof(lp_det)); d_counts.alloc(16); d_rects.alloc((size_t)max_det * 16);
   NmsArgs a;
   memset(&a, 0, sizeof(a));
-  a.cand = d_cand.as<Cand>(); a.cand_count = d_cnt.as<int>(); a.sorted = d_sorted.as<Cand>(); a.dets = d_dets.as<lp_det>();
-  a.counts = d_counts.as<int>(); a.rects = d_rects.as<int>(); a.geom = d_geom.as<ImgGeom>(); a.A = A; a.max_det = max_det; a.nc = nc;
-  a.iou = iou; a.min_area = min_area; a.roi_rule = h->cfg.numerics;
+  a.cand = d_cand.as<Cand>(); a.cand_count = d_cnt.as<int>(); a.sorted = d_sorted.as<Cand>(); a.geom = d_geom.as<ImgGeom>();
+  a.c = nms_common(h, d_dets.as<lp_det>(), d_counts.as<int>(), d_rects.as<int>(), A, nc, max_det, iou, min_area, false);
   launch_nms(a, 1, h->stream);
   read_one_image(h, d_dets, d_counts, d_rects, dets, rects, count, num_det);
 }
@@ -126,8 +125,8 @@ int lp_test_nms_views(lp_handle* h, const float* boxes, const float* scores, con
   memset(&a, 0, sizeof(a));
   a.cand = d_cand.as<Cand>(); a.cand_count = d_cnt.as<int>(); a.vcnt = d_vcnt.as<int>(); a.sorted = d_sorted.as<Cand>();
   a.frames = d_fr.as<TileFrame>(); a.vslot = d_vslot.as<int>();
-  a.dets = d_dets.as<lp_det>(); a.counts = d_counts.as<int>(); a.rects = d_rects.as<int>(); a.fgeom = d_geom.as<ImgGeom>();
-  a.A = A; a.max_det = max_det; a.nc = nc; a.min_area = min_area; a.roi_rule = h->cfg.numerics;
+  a.fgeom = d_geom.as<ImgGeom>();
+  a.c = nms_common(h, d_dets.as<lp_det>(), d_counts.as<int>(), d_rects.as<int>(), A, nc, max_det, iou, min_area, false);
   apply_view_merge(h, iou, a);
   launch_view_sort(a, n_views, h->stream);
   launch_frame_nms(a, 1, n_views, h->stream);

@@ -5,9 +5,9 @@
 // the letterbox of any window of a frame.
 #include "common.h"
 #include "kernels.h"
+#include "nms_dev.h"
 #include "post_dev.h"
 #include <algorithm>
-#include <cstdlib>
 
 namespace lp {
 
@@ -228,48 +228,19 @@ void launch_window_views(const uint8_t* src, const ViewWin* wins, uint8_t* dst, 
 }
 
 // ------------------------------------------------------------------------------------
-// Frame NMS, step 1: one workgroup per view sorts the view's candidates by the key of nms_kernel
-// (0xFFFF - class, score, anchor) with the same descending bitonic sort in LDS, writes them in that order to the view's slice
-// of `sorted`, records the view's count and re-arms cand_count for the next call.
+// Frame NMS of views: the frame front end of the core in nms_dev.h.
+// Step 1: one workgroup per view sorts the view's candidates with nms_kernel's sort (nms_sort_to) into the view's slice of
+// `sorted`, records the view's count and re-arms cand_count for the next call.
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NMS_THREADS) void view_sort_kernel(const FrameNmsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int v = blockIdx.x, tid = threadIdx.x;
+  const int v = blockIdx.x;
   int cnt = a.cand_count[v];
-  cnt = cnt > a.A ? a.A : cnt;
+  cnt = cnt > a.c.A ? a.c.A : cnt;
   __syncthreads();
-  if (tid == 0) { a.vcnt[v] = cnt; a.cand_count[v] = 0; }
+  if (threadIdx.x == 0) { a.vcnt[v] = cnt; a.cand_count[v] = 0; }
   if (cnt == 0) return;
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);
-  const Cand* cand = a.cand + (long)v * a.A;
-  Cand* sorted = a.sorted + (long)v * a.A;
-  int nsort = 1;
-  while (nsort < cnt) nsort <<= 1;
-  for (int i = tid; i < nsort; i += NMS_THREADS) keys[i] = i < cnt ? nms_key(cand[i]) : 0ull;
-  __syncthreads();
-  for (int k = 2; k <= nsort; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < nsort; i += NMS_THREADS) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long x = keys[i], y = keys[ixj];
-          const bool desc = (i & k) == 0;
-          if (desc ? (x < y) : (x > y)) { keys[i] = y; keys[ixj] = x; }
-        }
-      }
-      __syncthreads();
-    }
-  }
-  for (int i = tid; i < cnt; i += NMS_THREADS) {   // each record finds its rank by binary search (keys are unique in a view)
-    const Cand c = cand[i];
-    const unsigned long long k = nms_key(c);
-    int lo = 0, hi = cnt - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (keys[mid] > k) lo = mid + 1; else hi = mid;
-    }
-    sorted[lo] = c;
-  }
+  nms_sort_to(reinterpret_cast<unsigned long long*>(smem), a.cand + (long)v * a.c.A, a.sorted + (long)v * a.c.A, cnt);
 }
 
 // records of another view's descending list [0, n) that precede a candidate of (class, score) key k = nms_key >> 14: those
@@ -285,12 +256,6 @@ __device__ __forceinline__ int count_before(const Cand* list, int n, unsigned lo
   return lo;
 }
 
-// score-major key of a kept box over a frame: (score, view, anchor), unique inside a frame (views < 1024, anchors < 16384)
-__device__ __forceinline__ unsigned long long frame_score_key(const Cand& c) {
-  return ((unsigned long long)__float_as_uint(c.score) << 24) | ((unsigned long long)(c.pad & 0x3FF) << 14) |
-         (unsigned long long)(c.anchor & 0x3FFF);
-}
-
 // candidate t of a frame's view-major concatenation: view k, position p inside the view's sorted list
 __device__ __forceinline__ void frame_locate(const FrameNmsArgs& a, const TileFrame& fr, int t, int& k, int& p) {
   k = 0;
@@ -303,38 +268,8 @@ __device__ __forceinline__ void frame_locate(const FrameNmsArgs& a, const TileFr
   }
 }
 
-// ROI list bookkeeping of one frame (the protocol of nms_kernel: the block that draws the last ticket publishes the total)
-__device__ __forceinline__ int frame_roi_slice(const FrameNmsArgs& a, int run, int nframes) {
-  int base = 0;
-  if (a.tab.total) {
-    base = atomicAdd(a.tab.work, run);
-    int one = 1;
-    asm volatile("" : "+v"(one) : "v"(base));
-    const int ticket = atomicAdd(a.tab.work + 1, one);
-    if (ticket == nframes - 1) {
-      const int raw = atomicExch(a.tab.work, 0);
-      atomicExch(a.tab.work + 1, 0);
-      a.tab.total[0] = raw < a.max_rois ? raw : a.max_rois;
-      a.tab.total[1] = raw;
-    }
-  }
-  return base;
-}
-
-__device__ __forceinline__ void frame_emit(const FrameNmsArgs& a, int f, int o, int base, const Cand& c, int x1, int y1, int x2, int y2) {
-  lp_det d;
-  d.x1 = c.x1; d.y1 = c.y1; d.x2 = c.x2; d.y2 = c.y2; d.det_conf = c.score; d.det_class = c.cls;
-  d.cls_class = -1; d.cls_conf = 0.f;
-  a.dets[(long)f * a.max_det + o] = d;
-  int* rects = a.rects + ((long)f * a.max_det + o) * 4;
-  rects[0] = x1; rects[1] = y1; rects[2] = x2; rects[3] = y2;
-  if (a.tab.total && base + o < a.max_rois) { a.tab.img[base + o] = f; a.tab.slot[base + o] = o; }
-}
-
-// At most 64 candidates in the whole frame, none of which max_det can cut (the usual frame at conf 0.25): ONE wave.  Lane t
-// holds candidate t of the concatenation; its rank in the merged order is counted against the other 63 lanes with shuffles,
-// the records are gathered by rank, then the ballot sweep, ROI rule and compaction of nms_small.  IOS / UNI: the match metric and
-// the box-union merge of lp_set_view_merge; a keeper's union is reduced over the ballot of the lanes it absorbs.
+// One-wave path (nms_small_tail): lane t holds candidate t of the concatenation; its rank in the merged order is counted
+// against the other 63 lanes with shuffles, the records are gathered by rank.
 template <bool IOS, bool UNI>
 __device__ __forceinline__ void frame_nms_small(const FrameNmsArgs& a, int f, const TileFrame& fr, int cnt, int nframes) {
   const int lane = threadIdx.x & 63;
@@ -344,7 +279,7 @@ __device__ __forceinline__ void frame_nms_small(const FrameNmsArgs& a, int f, co
   if (lane < cnt) {
     int p;
     frame_locate(a, fr, lane, view, p);
-    c = a.sorted[(long)a.vslot[fr.view0 + view] * a.A + p];
+    c = a.sorted[(long)a.vslot[fr.view0 + view] * a.c.A + p];
     c.pad = view;
   }
   const unsigned long long key = lane < cnt ? nms_key(c) : 0ull;
@@ -363,251 +298,51 @@ __device__ __forceinline__ void frame_nms_small(const FrameNmsArgs& a, int f, co
   Cand bj;
   bj.x1 = __shfl(c.x1, src); bj.y1 = __shfl(c.y1, src); bj.x2 = __shfl(c.x2, src); bj.y2 = __shfl(c.y2, src);
   bj.score = __shfl(c.score, src); bj.cls = __shfl(c.cls, src); bj.anchor = __shfl(c.anchor, src); bj.pad = __shfl(c.pad, src);
-  const bool valid = lane < cnt;
-  const float aj = __fmul_rn(__fsub_rn(bj.x2, bj.x1), __fsub_rn(bj.y2, bj.y1));
-  unsigned long long alive = __ballot(valid);
-  unsigned long long todo = alive, kept = 0ull;
-  const float thr = a.iou;
-  float ux1 = bj.x1, uy1 = bj.y1, ux2 = bj.x2, uy2 = bj.y2;   // UNI: this lane's box grown by what it absorbs as a keeper
-  while (todo) {  // wave-uniform
-    const int i = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    kept |= 1ull << i;
-    const float ix1 = __shfl(bj.x1, i), iy1 = __shfl(bj.y1, i), ix2 = __shfl(bj.x2, i), iy2 = __shfl(bj.y2, i);
-    const float ai = __shfl(aj, i);
-    const int ic = __shfl(bj.cls, i);
-    const bool sup = lane > i && ((alive >> lane) & 1ull) && bj.cls == ic && view_matched<IOS>(ix1, iy1, ix2, iy2, ai, bj.x1, bj.y1, bj.x2, bj.y2, thr);
-    const unsigned long long m = __ballot(sup);
-    alive &= ~m;
-    todo &= ~m;
-    if (UNI && m) {   // wave-uniform
-      const float mx1 = wave_min(sup ? bj.x1 : INFINITY), my1 = wave_min(sup ? bj.y1 : INFINITY);
-      const float mx2 = wave_max(sup ? bj.x2 : -INFINITY), my2 = wave_max(sup ? bj.y2 : -INFINITY);
-      if (lane == i) { ux1 = fminf(ux1, mx1); uy1 = fminf(uy1, my1); ux2 = fmaxf(ux2, mx2); uy2 = fmaxf(uy2, my2); }
-    }
-  }
-  if (UNI) { bj.x1 = ux1; bj.y1 = uy1; bj.x2 = ux2; bj.y2 = uy2; }   // only the keepers' boxes are read from here on
-  const bool is_kept = (kept >> lane) & 1ull;
-  const int nsel = __popcll(kept);
-  const ImgGeom gm = a.fgeom[f];
-  int x1 = 0, y1 = 0, x2 = 0, y2 = 0;
-  const bool ok = is_kept && roi_rect(bj, gm, a.roi_rule, a.min_area, x1, y1, x2, y2);
-  const unsigned long long okm = __ballot(ok);
-  const int o = __popcll(okm & ((1ull << lane) - 1ull)), run = __popcll(okm);
-  double ssum = is_kept ? (double)bj.score : 0.0;
-  for (int off = 32; off > 0; off >>= 1) ssum += __shfl_xor(ssum, off);
-  int base = 0;
-  if (lane == 0) {
-    a.counts[f] = run;
-    a.counts[nframes + f] = nsel;
-    reinterpret_cast<float*>(a.counts)[2 * nframes + f] = nsel > 0 ? (float)(ssum / (double)nsel) : 0.f;
-    base = frame_roi_slice(a, run, nframes);
-  }
-  base = __shfl(base, 0);
-  if (ok) frame_emit(a, f, o, base, bj, x1, y1, x2, y2);
+  nms_small_tail<IOS, UNI>(a.c, a.fgeom[f], f, nframes, bj, cnt);
 }
 
 // ------------------------------------------------------------------------------------
-// Frame NMS, step 2: one workgroup per frame.
-//   1. merge: candidate p of view k finds its rank in the union by binary search in the frame's other sorted lists -- the
-//      order is (class asc, score desc, view desc, anchor desc): nms_kernel's order with the view above the anchor -- and is
-//      written to the frame's contiguous region of `cand` (free since step 1), its view index in Cand::pad;
-//   2. the chunk-of-64 ballot sweep of nms_kernel, removed / kept flags as bit masks in LDS;
-//   3. max_det over (score, view, anchor), ROI rectangles, order-preserving compaction, the frame's slice of the ROI list.
-// IOS: the match is intersection over the smaller area.  UNI: a keeper's emitted box is the union of its own and of every box
-// it absorbs.  Matching always uses the keeper's OWN box (s_chunk); the union grows in s_union -- over the ballot in the wave-0
-// loop, by LDS atomics from the thread that owns j in the outer phase -- and is written over the keeper's record in merged[]
-// once the chunk's outer phase is done: no later chunk reads an earlier chunk's keepers, the final phases read the union.
-// <false, false> is the reference's rule (e2e.py:89-119).
+// Step 2: one workgroup per frame.  Merge: candidate p of view k finds its rank in the union by binary search in the frame's
+// other sorted lists -- the order is (class asc, score desc, view desc, anchor desc): nms_kernel's order with the view above
+// the anchor -- and is written to the frame's contiguous region of `cand` (free since step 1), its view index in Cand::pad.
+// Then nms_finish.  IOS: the match is intersection over the smaller area.  UNI: a keeper's emitted box is the union of its own
+// and of every box it absorbs.  <false, false> is the reference's rule (e2e.py:89-119).
 // ------------------------------------------------------------------------------------
 template <bool IOS, bool UNI>
 __global__ __launch_bounds__(NMS_THREADS) void frame_nms_kernel(const FrameNmsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ int s_wave[NMS_THREADS / 64 + 1];
-  __shared__ float s_chunk[64 * 6];
-  __shared__ float s_union[UNI ? 64 * 4 : 1];
-  __shared__ int s_nk, s_base;
-  __shared__ double s_red[NMS_THREADS / 64];
-  const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int f = blockIdx.x;
   const TileFrame fr = a.frames[f];
   int cnt = 0;
   for (int k = 0; k < fr.nviews; ++k) cnt += a.vcnt[a.vslot[fr.view0 + k]];
-  if (cnt <= 64 && cnt <= a.max_det && !a.no_small) {   // block-uniform
-    if (wave == 0) frame_nms_small<IOS, UNI>(a, f, fr, cnt, (int)gridDim.x);
+  if (cnt <= 64 && cnt <= a.c.max_det && !a.c.no_small) {   // block-uniform
+    if (threadIdx.x < 64) frame_nms_small<IOS, UNI>(a, f, fr, cnt, (int)gridDim.x);
     return;
   }
-  const int nwords = (cnt + 31) >> 5;
-  unsigned* removed = reinterpret_cast<unsigned*>(smem);
-  unsigned* keptm = removed + nwords;
-  for (int i = tid; i < 2 * nwords; i += NMS_THREADS) removed[i] = 0u;
-  // ---- merge
-  Cand* merged = a.cand + (long)fr.view0 * a.A;
-  for (int t = tid; t < cnt; t += NMS_THREADS) {
+  Cand* merged = a.cand + (long)fr.view0 * a.c.A;
+  for (int t = threadIdx.x; t < cnt; t += NMS_THREADS) {
     int k, p;
     frame_locate(a, fr, t, k, p);
-    Cand c = a.sorted[(long)a.vslot[fr.view0 + k] * a.A + p];
+    Cand c = a.sorted[(long)a.vslot[fr.view0 + k] * a.c.A + p];
     const unsigned long long key = nms_key(c);
     int rank = p;
     for (int u = 0; u < fr.nviews; ++u) {
       if (u == k) continue;
       const int su = a.vslot[fr.view0 + u];
-      rank += count_before(a.sorted + (long)su * a.A, a.vcnt[su], key >> 14, u > k);
+      rank += count_before(a.sorted + (long)su * a.c.A, a.vcnt[su], key >> 14, u > k);
     }
     c.pad = k;
     merged[rank] = c;
   }
-  __threadfence_block();
-  __syncthreads();
-
-  // ---- greedy sweep, 64 boxes per step
-  int nkeep = 0;
-  const float thr = a.iou;
-  const bool single_class = a.nc <= 1;
-  for (int c0 = 0; c0 < cnt; c0 += 64) {
-    unsigned long long kept = 0ull;   // wave 0: the chunk's keepers
-    if (wave == 0) {
-      const int j = c0 + lane;
-      const bool valid = j < cnt;
-      Cand bj;
-      bj.x1 = bj.y1 = bj.x2 = bj.y2 = 0.f; bj.cls = -1;
-      if (valid) bj = merged[j];
-      const float aj = __fmul_rn(__fsub_rn(bj.x2, bj.x1), __fsub_rn(bj.y2, bj.y1));
-      unsigned long long alive = __ballot(valid && !((removed[valid ? (j >> 5) : 0] >> (j & 31)) & 1u));
-      unsigned long long todo = alive;
-      float ux1 = bj.x1, uy1 = bj.y1, ux2 = bj.x2, uy2 = bj.y2;
-      int room = single_class ? a.max_det - nkeep : 0x7fffffff;
-      while (todo && room > 0) {  // wave-uniform
-        const int i = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        kept |= 1ull << i;
-        --room;
-        const float ix1 = __shfl(bj.x1, i), iy1 = __shfl(bj.y1, i), ix2 = __shfl(bj.x2, i), iy2 = __shfl(bj.y2, i);
-        const float ai = __shfl(aj, i);
-        const int ic = __shfl(bj.cls, i);
-        const bool sup = lane > i && ((alive >> lane) & 1ull) && bj.cls == ic &&
-                         view_matched<IOS>(ix1, iy1, ix2, iy2, ai, bj.x1, bj.y1, bj.x2, bj.y2, thr);
-        const unsigned long long m = __ballot(sup);
-        alive &= ~m;
-        todo &= ~m;
-        if (UNI && m) {   // wave-uniform
-          const float mx1 = wave_min(sup ? bj.x1 : INFINITY), my1 = wave_min(sup ? bj.y1 : INFINITY);
-          const float mx2 = wave_max(sup ? bj.x2 : -INFINITY), my2 = wave_max(sup ? bj.y2 : -INFINITY);
-          if (lane == i) { ux1 = fminf(ux1, mx1); uy1 = fminf(uy1, my1); ux2 = fmaxf(ux2, mx2); uy2 = fmaxf(uy2, my2); }
-        }
-      }
-      if ((kept >> lane) & 1ull) {
-        const int idx = __popcll(kept & ((1ull << lane) - 1ull));
-        float* cb = s_chunk + idx * 6;
-        cb[0] = bj.x1; cb[1] = bj.y1; cb[2] = bj.x2; cb[3] = bj.y2; cb[4] = aj; cb[5] = __int_as_float(bj.cls);
-        if (UNI) {
-          float* ub = s_union + idx * 4;
-          ub[0] = ux1; ub[1] = uy1; ub[2] = ux2; ub[3] = uy2;
-        }
-      }
-      if (lane == 0) {   // c0 is a multiple of 64: the chunk owns two whole words of the kept mask
-        keptm[c0 >> 5] = (unsigned)kept;
-        if ((c0 >> 5) + 1 < nwords) keptm[(c0 >> 5) + 1] = (unsigned)(kept >> 32);
-        s_nk = __popcll(kept);
-      }
-    }
-    __syncthreads();
-    const int nk = s_nk;
-    nkeep += nk;
-    // one class: max_det keepers are all there will be.  The union of this last chunk's keepers still needs its outer phase.
-    const bool full = single_class && nkeep >= a.max_det;
-    if (!UNI && full) break;
-    for (int j = c0 + 64 + tid; j < cnt; j += NMS_THREADS) {
-      if ((removed[j >> 5] >> (j & 31)) & 1u) continue;
-      const Cand bj = merged[j];
-      for (int k = 0; k < nk; ++k) {
-        const float* cb = s_chunk + k * 6;
-        if (__float_as_int(cb[5]) != bj.cls) continue;
-        if (view_matched<IOS>(cb[0], cb[1], cb[2], cb[3], cb[4], bj.x1, bj.y1, bj.x2, bj.y2, thr)) {
-          atomicOr(&removed[j >> 5], 1u << (j & 31));
-          if (UNI) {   // the FIRST matching keeper of the chunk takes j
-            float* ub = s_union + k * 4;
-            lds_min_f32(ub + 0, bj.x1); lds_min_f32(ub + 1, bj.y1); lds_max_f32(ub + 2, bj.x2); lds_max_f32(ub + 3, bj.y2);
-          }
-          break;
-        }
-      }
-    }
-    __syncthreads();
-    if (UNI) {
-      if ((kept >> lane) & 1ull) {   // wave 0 only: the other waves' kept is 0
-        const float* ub = s_union + __popcll(kept & ((1ull << lane) - 1ull)) * 4;
-        Cand* m = merged + c0 + lane;
-        m->x1 = ub[0]; m->y1 = ub[1]; m->x2 = ub[2]; m->y2 = ub[3];
-      }
-      __threadfence_block();
-      if (full) break;
-    }
-  }
-  __syncthreads();
-
-  // ---- more survivors than max_det (several classes; one class never keeps more): the max_det best (score, view, anchor) keys
-  unsigned long long T = 0ull;
-  int nsel = nkeep;
-  const bool by_key = nkeep > a.max_det;
-  if (by_key) {
-    for (int bit = 55; bit >= 0; --bit) {
-      const unsigned long long candT = T | (1ull << bit);
-      int c = 0;
-      for (int j = tid; j < cnt; j += NMS_THREADS)
-        if ((keptm[j >> 5] >> (j & 31)) & 1u) c += frame_score_key(merged[j]) >= candT ? 1 : 0;
-      int tot;
-      (void)block_exclusive_scan(c, s_wave, &tot);
-      if (tot >= a.max_det) T = candT;
-    }
-    nsel = a.max_det;
-  }
-
-  // ---- ROI rectangle + area filter, order-preserving compaction
-  const ImgGeom gm = a.fgeom[f];
-  const int per = (cnt + NMS_THREADS - 1) / NMS_THREADS;
-  const int k0 = tid * per, k1 = (k0 + per < cnt) ? k0 + per : cnt;
-  int nvalid = 0;
-  double ssum = 0.0;
-  for (int k = k0; k < k1; ++k) {
-    if (!((keptm[k >> 5] >> (k & 31)) & 1u)) continue;
-    const Cand c = merged[k];
-    if (by_key && frame_score_key(c) < T) continue;
-    ssum += (double)c.score;
-    int x1, y1, x2, y2;
-    nvalid += roi_rect(c, gm, a.roi_rule, a.min_area, x1, y1, x2, y2) ? 1 : 0;
-  }
-  int run;
-  int o = block_exclusive_scan(nvalid, s_wave, &run);
-  for (int off = 32; off > 0; off >>= 1) ssum += __shfl_xor(ssum, off);
-  if (lane == 0) s_red[wave] = ssum;
-  __syncthreads();
-  if (tid == 0) {
-    double tot = 0.0;
-    for (int w = 0; w < NMS_THREADS / 64; ++w) tot += s_red[w];
-    a.counts[f] = run;
-    a.counts[gridDim.x + f] = nsel;
-    reinterpret_cast<float*>(a.counts)[2 * gridDim.x + f] = nsel > 0 ? (float)(tot / (double)nsel) : 0.f;
-    s_base = frame_roi_slice(a, run, (int)gridDim.x);
-  }
-  __syncthreads();
-  const int base = s_base;
-  for (int k = k0; k < k1; ++k) {
-    if (!((keptm[k >> 5] >> (k & 31)) & 1u)) continue;
-    const Cand c = merged[k];
-    if (by_key && frame_score_key(c) < T) continue;
-    int x1, y1, x2, y2;
-    if (!roi_rect(c, gm, a.roi_rule, a.min_area, x1, y1, x2, y2)) continue;
-    frame_emit(a, f, o, base, c, x1, y1, x2, y2);
-    ++o;
-  }
+  nms_finish<IOS, UNI>(a.c, a.fgeom[f], merged, cnt, f, (int)gridDim.x, reinterpret_cast<unsigned*>(smem));
 }
 
 size_t frame_nms_lds_bytes(int max_union) { return (size_t)2 * 4 * ((max_union + 31) / 32) + 16; }
 
 void launch_view_sort(const FrameNmsArgs& a, int V, hipStream_t st) {
-  LP_CHECK(a.A <= 16384, LP_ERR_STATE, "frame NMS: anchor index needs more than 14 key bits");
-  const size_t lds = nms_lds_bytes(a.A);
-  LP_CHECK(lds <= 150 * 1024, LP_ERR_STATE, "frame NMS: %d anchors exceed the LDS sort capacity", a.A);
+  LP_CHECK(a.c.A <= 16384, LP_ERR_STATE, "frame NMS: anchor index needs more than 14 key bits");
+  const size_t lds = nms_lds_bytes(a.c.A);
+  LP_CHECK(lds <= 150 * 1024, LP_ERR_STATE, "frame NMS: %d anchors exceed the LDS sort capacity", a.c.A);
   set_max_dynamic_lds(reinterpret_cast<const void*>(view_sort_kernel), 150 * 1024);
   LP_LAUNCH(view_sort_kernel, dim3(V), dim3(NMS_THREADS), lds, st, a);
   LP_HIP(hipGetLastError());
@@ -621,10 +356,10 @@ static void launch_frame_nms_as(const FrameNmsArgs& b, int F, size_t lds, hipStr
 
 void launch_frame_nms(const FrameNmsArgs& a, int F, int max_views, hipStream_t st) {
   LP_CHECK(max_views >= 1 && max_views <= 1024, LP_ERR_ARG, "frame NMS: %d views in one frame (1..1024)", max_views);
-  const size_t lds = frame_nms_lds_bytes(max_views * a.A);
-  LP_CHECK(lds <= FRAME_NMS_LDS_CAP, LP_ERR_ARG, "frame NMS: a frame of %d views x %d anchors exceeds the LDS flag capacity", max_views, a.A);
+  const size_t lds = frame_nms_lds_bytes(max_views * a.c.A);
+  LP_CHECK(lds <= FRAME_NMS_LDS_CAP, LP_ERR_ARG, "frame NMS: a frame of %d views x %d anchors exceeds the LDS flag capacity", max_views, a.c.A);
   FrameNmsArgs b = a;
-  b.no_small = getenv("LITEPI_NMS_NO_SMALL") != nullptr ? 1 : a.no_small;   // as launch_nms: A/B switch + the path-equivalence test
+  b.c.no_small = nms_no_small(a.c.no_small);
   LP_CHECK((a.metric == 0 || a.metric == 1) && (a.mode == 0 || a.mode == 1), LP_ERR_ARG, "frame NMS: metric %d / mode %d", a.metric, a.mode);
   switch (a.metric * 2 + a.mode) {   // chosen on the host: the default instantiation carries none of the merge
     case 0: launch_frame_nms_as<false, false>(b, F, lds, st); break;

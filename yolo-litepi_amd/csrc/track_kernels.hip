@@ -36,7 +36,7 @@ __device__ __forceinline__ unsigned conf_key(float conf) {
   return k ? k : 1u;
 }
 
-// nms_suppressed's IoU (post_dev.h) with the detection as i and the predicted box as j
+// nms_suppressed's IoU (nms_dev.h) with the detection as i and the predicted box as j
 __device__ __forceinline__ float track_iou(float ix1, float iy1, float ix2, float iy2, float ai, float jx1, float jy1, float jx2, float jy2) {
   const float aj = __fmul_rn(__fsub_rn(jx2, jx1), __fsub_rn(jy2, jy1));
   const float w = fmaxf(0.f, __fsub_rn(fminf(ix2, jx2), fmaxf(ix1, jx1)));

@@ -72,7 +72,7 @@ void check_view_merge(const lp_view_merge* m) {
 void apply_view_merge(const lp_handle* h, float iou, FrameNmsArgs& a) {
   a.metric = h->vmerge.metric;
   a.mode = h->vmerge.mode;
-  a.iou = h->vmerge.threshold > 0.f ? h->vmerge.threshold : iou;
+  a.c.iou = h->vmerge.threshold > 0.f ? h->vmerge.threshold : iou;
 }
 
 // ---- a call's frames as view lists ---------------------------------------------------------------------------------------------
@@ -231,12 +231,9 @@ static void enqueue_view_detect(lp_handle* h, const ViewLayout& lay, int F, floa
   a.cand = h->d_cand.as<Cand>(); a.cand_count = h->d_cand_count.as<int>(); a.vcnt = h->d_vcnt.as<int>(); a.sorted = h->d_sorted.as<Cand>();
   a.frames = h->d_ftab.as<TileFrame>();
   a.vslot = reinterpret_cast<const int*>(h->d_ftab.as<char>() + (size_t)h->cfg.max_batch * sizeof(TileFrame));
-  a.dets = dets; a.counts = counts; a.rects = h->d_rects.as<int>(); a.fgeom = h->d_fgeom.as<ImgGeom>();
-  a.A = h->det->num_anchors(); a.max_det = h->cfg.max_det; a.nc = h->det->num_classes(); a.min_area = min_area;
+  a.fgeom = h->d_fgeom.as<ImgGeom>();
+  a.c = nms_common(h, dets, counts, h->d_rects.as<int>(), h->det->num_anchors(), h->det->num_classes(), h->cfg.max_det, iou, min_area, with_rois);
   apply_view_merge(h, iou, a);
-  if (with_rois) a.tab = h->roi_table();
-  a.max_rois = h->max_rois;
-  a.roi_rule = h->cfg.numerics;
   if (prof) prof->begin(h->stream);
   launch_view_sort(a, lay.V, h->stream);
   if (prof) prof->end(h->stream, "view_sort", "nms", 0.0, 0.0);
