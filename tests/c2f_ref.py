@@ -9,16 +9,16 @@ that pin those fp16 launches to their own HBM input (test_c2f_ref_cpu.py, test_g
 
 Rounding points (``round_act``), read off the kernels.  Every sum is fp32 on the device (MFMA accumulators), float64 here.
 
-  weights      fp16, once: a property of the stored model (``pack_phase`` packs every fragment as halfs).  Biases stay fp32: they
+  weights      fp16, once: a property of the stored model (``pack_phase`` of c2f_plan.h packs every fragment as halfs).  Biases stay fp32: they
                are added to the fp32 accumulators (``silu4(acc[t][i], bv[t])``: ``v = v + b``).
   Swish        every Swish output, fp16 round-to-nearest-even.  c2f_kernel: each epilogue converts its SiLU values with
-               ``to_half<NT>(v, h)`` before the store -- the entry conv's x (``store_h<NT>(xo + ..)``), cv1's y0 | y1
+               ``to_half<NT>(v, h)`` before the store -- the entry conv's x (``GlobalEpi``: ``store_h<NT>(base + ..)``), cv1's y0 | y1
                (``store_h<NT>(P0 + (fy * LW + fx) * PS0 + chb * 2, h)`` and the concat buffer), a_k (``epi_a``: ``store_h<NT>(P1
                + ..)``), cv2 (``epi_cv2``: ``store_h<NT>(out + ..)``; the whole-image configurations also put those halfs back
                into the planes: "the output (2c = COUT channels) also replaces y_NB | y_{NB+1} in the planes -- SPPF.cv1's
                input"), SPPF.cv1's s (``store_h<NT>(P0 + ((rg.fy0 + py) * LW + rg.fx0 + px) * PS + chb * 2, h)``) and SPPF.cv2
                (``store_h<NT>(out2 + ..)``).
-               s2conv_kernel: ``to_half<NT>(v, h)`` then ``store_h<NT>(xo + ..)``.
+               s2conv_kernel: the same ``GlobalEpi``, ``to_half<NT>(v, h)`` then ``store_h<NT>(base + ..)``.
                s2lds_kernel: ``for (int t = 0; t < NT; ++t) v[t] = silu4(acc[t][i], bv[t]); .. to_half<NT>(v, hh);`` and, with
                the 1x1 tail, "out2 = silu(W2 . fp16(silu(conv)) + b2)": ``bq[0][j] = hh[j]`` is the B operand of the tail's
                MFMA, ``v[t] = silu4(o, b2v[t]); .. to_half<NT>(v, hh);`` its output.

@@ -382,15 +382,15 @@ def test_pmc_tool_maps_rocprof_kernel_names_to_the_library_profile_names():
     spec = importlib.util.spec_from_file_location("pmc_traffic", os.path.join(ROOT, "tools", "pmc_traffic.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    ns = "lp::(anonymous namespace)::"
+    ns, cp = "lp::(anonymous namespace)::", "lp::c2fplan::"   # the kernels of c2f_kernels.hip, the configuration types of c2f_plan.h
     cases = {
-        f"void {ns}c2f_kernel<{ns}C2fCfg<24, 2, 0, 48, false, 48, -1, 0, 20, 8, true, 0, false, 8> >(lp::C2fArgs)": "c2f<24,2,y0y1>_f16",
-        f"void {ns}c2f_kernel<{ns}C2fCfg<48, 1, 192, 96, true, 96, 0, 0, 20, 8, false, 0, false, 0> >(lp::C2fArgs)": "c2f<48,1,up192+96>_f16",
-        f"void {ns}c2f_kernel<{ns}C2fCfg<64, 1, 0, 128, false, 128, 2, 64, 20, 8, true, 0, false, 0> >(lp::C2fArgs)": "c2f<64,1,s2+128,sppf>_f16",
-        f"void {ns}s2lds_kernel<{ns}S2LCfg<16, 32, 10, 1, 1, true> >(lp::C2fArgs)": "s2conv+1x1<16,32>_f16",
-        f"void {ns}s2lds_kernel<{ns}S2LCfg<96, 192, 10, 4, 2, false> >(lp::C2fArgs)": "s2conv<96,192>_f16",
-        f"void {ns}s2conv_kernel<{ns}S2Cfg<32, 64, 20> >(lp::C2fArgs)": "s2conv<32,64>_f16",
-        f"void {ns}sppf_kernel<{ns}SpCfg<96, 192, 192, 2> >(lp::C2fArgs)": "sppf<192,96,192>_f16",
+        f"void {ns}c2f_kernel<{cp}C2fCfg<24, 2, 0, 48, false, 48, -1, 0, 20, true, 8> >(lp::C2fArgs)": "c2f<24,2,y0y1>_f16",
+        f"void {ns}c2f_kernel<{cp}C2fCfg<48, 1, 192, 96, true, 96, 0, 0, 20, false, 0> >(lp::C2fArgs)": "c2f<48,1,up192+96>_f16",
+        f"void {ns}c2f_kernel<{cp}C2fCfg<64, 1, 0, 128, false, 128, 2, 64, 20, true, 0> >(lp::C2fArgs)": "c2f<64,1,s2+128,sppf>_f16",
+        f"void {ns}s2lds_kernel<{cp}S2LCfg<16, 32, 10, 1, 1, true> >(lp::C2fArgs)": "s2conv+1x1<16,32>_f16",
+        f"void {ns}s2lds_kernel<{cp}S2LCfg<96, 192, 10, 4, 2, false> >(lp::C2fArgs)": "s2conv<96,192>_f16",
+        f"void {ns}s2conv_kernel<{cp}S2Cfg<32, 64, 20> >(lp::C2fArgs)": "s2conv<32,64>_f16",
+        f"void {ns}sppf_kernel<{cp}SpCfg<96, 192, 192, 2> >(lp::C2fArgs)": "sppf<192,96,192>_f16",
         "void lp::stem_block16_kernel<8>(lp::StemBlockArgs)": "stem_block16_f16",
         "lp::stem_block_kernel(lp::StemBlockArgs)": "stem_block_f16",
         "void lp::head_fused_kernel<2, 3, 1, 3, 2, 12, 3, true, true, 18>(lp::HeadArgs)": "head_fused<2,3,1,3,2,12>a16k3_f16",

@@ -28,7 +28,7 @@ def family(name):
         m = re.search(r"SpCfg<(\d+), *(\d+), *(\d+)", name)
         v = [int(m.group(i)) for i in (1, 2, 3)] if m else (ints + [0, 0, 0])[:3]
         return "sppf<%d,%d,%d>_f16" % (v[1], v[0], v[2])
-    if "c2f_kernel" in name:   # C2fCfg<C, NB, KA, KB, UP, COUT, MODE, KS2, TH, NW>: the profiler's name is CfgName of c2f_kernels.hip
+    if "c2f_kernel" in name:   # C2fCfg<C, NB, KA, KB, UP, COUT, MODE, KS2, TH, AW, NWT>: the profiler's name is c2f_name of c2f_plan.h
         m = re.search(r"C2fCfg<([^>]*)>", name)
         if m:
             t = [x.strip() for x in m.group(1).split(",")]

@@ -6,11 +6,10 @@
 // and, on the 20x20 level where a whole image fits one workgroup, also the stride-2 3x3 conv in front of it
 // and the SPPF module behind it (cv1 -> three cascaded 5x5 max pools -> cv2).
 #pragma once
+#include "c2f_plan.h"   // shape keys, configurations, predicates and packers (host-pure)
 #include "common.h"
 
 namespace lp {
-
-enum { C2F_W_S2 = 0, C2F_W_CV1, C2F_W_A0, C2F_W_B0, C2F_W_A1, C2F_W_B1, C2F_W_CV2, C2F_W_SP1, C2F_W_SP2, C2F_NW };
 
 struct C2fArgs {
   const void* src0;   // cv1 input, first K segment (KA channels); UP: a half-resolution tensor read at (y/2, x/2)
@@ -37,22 +36,6 @@ struct C2fArgs {
   unsigned long long* stamps;  // diagnostic only (LITEPI_C2F_STAMPS=<file>): 16 clock stamps per workgroup
 };
 
-// Shape key of an instantiated kernel configuration
-struct C2fShape {
-  int C = 0;      // hidden channels c of the module (cv1 produces 2c, every bottleneck conv is c -> c)
-  int NB = 1;     // bottlenecks
-  int KA = 0;     // cv1 input channels taken from src0 (0: none)
-  int KB = 0;     // cv1 input channels taken from src1
-  int UP = 0;     // src0 is half resolution (fused Interp nearest x2)
-  int COUT = 0;   // cv2 output channels
-  int MODE = 0;   // 0: C2f; 1: stride-2 3x3 entry conv + C2f (whole image per workgroup); 2: entry conv + C2f + SPPF;
-                  // -1: C2f without its cv1 (y0 | y1 already in the concat buffer: the stride-2 conv in front ran cv1 as its tail)
-  int KS2 = 0;    // input channels of the entry conv
-  bool operator==(const C2fShape& o) const {
-    return C == o.C && NB == o.NB && KA == o.KA && KB == o.KB && UP == o.UP && COUT == o.COUT && MODE == o.MODE && KS2 == o.KS2;
-  }
-};
-
 struct C2fLayer {
   C2fShape sh;
   int H = 0, W = 0;
@@ -62,21 +45,12 @@ struct C2fLayer {
   size_t lds_bytes = 0;
   double macs_per_image = 0;
 
-  // fp32 weights over physical channels (here physical == logical: the supported shapes have no padded segments)
-  struct Src {
-    const std::vector<float>*cv1 = nullptr, *cv1_b = nullptr;             // [2C][KA + KB]
-    const std::vector<float>*a[2] = {nullptr, nullptr}, *a_b[2] = {nullptr, nullptr};  // [C][9][C]
-    const std::vector<float>*bb[2] = {nullptr, nullptr}, *bb_b[2] = {nullptr, nullptr};
-    const std::vector<float>*cv2 = nullptr, *cv2_b = nullptr;             // [COUT][(2 + NB) C]
-    const std::vector<float>*s2 = nullptr, *s2_b = nullptr;               // [XC][9][KS2]
-    const std::vector<float>*sp1 = nullptr, *sp1_b = nullptr;             // [C][COUT]
-    const std::vector<float>*sp2 = nullptr, *sp2_b = nullptr;             // [COUT][4C]
-  };
-  // supported / kernel_name(shape): pure functions of the shape.  Which configurations a load may use besides (LITEPI_C2F_BB80,
-  // LITEPI_C2F_SKIP) is the planner's business (Planner::c2f_ok)
-  static bool supported(const C2fShape& s, int h, int w);
-  static std::string kernel_name(const C2fShape& s);   // "c2f<..>", or empty: no configuration for this shape
-  bool cv2_from_lds() const;   // cv2 takes the last y segments from the LDS planes: they never reach the concat buffer
+  using Src = c2fplan::C2fSrc;   // fp32 weights over physical channels
+  // supported / kernel_name(shape): pure functions of the shape (c2f_plan.h).  Which configurations a load may use besides
+  // (LITEPI_C2F_BB80, LITEPI_C2F_SKIP) is the planner's business (Planner::c2f_ok)
+  static bool supported(const C2fShape& s, int h, int w) { return c2fplan::c2f_supported(s, h, w); }
+  static std::string kernel_name(const C2fShape& s) { return c2fplan::c2f_kernel_name(s); }   // "c2f<..>", or empty: no configuration for this shape
+  bool cv2_from_lds() const { return c2fplan::c2f_cv2_from_lds(sh); }   // cv2 takes the last y segments from the LDS planes: they never reach the concat buffer
   void build(const C2fShape& s, int h, int w, const Src& src);
   struct IO {
     View src0, src1, cat, out;   // src0.base == nullptr when KA == 0
@@ -91,18 +65,18 @@ struct C2fLayer {
 struct S2ConvLayer {
   int Cin = 0, Cout = 0, H = 0, W = 0;   // H, W: OUTPUT map
   bool has_tail = false;                 // a 1x1 conv + SiLU (C2f.cv1) on the accumulators: Cout -> Cout
-  // ((Cin, Cout, has_tail) is the key of the layer's configuration: build and launch look it up in the one table of c2f_kernels.hip)
+  // ((Cin, Cout, has_tail) is the key of the layer's configuration: build and launch look it up in the one table of c2f_plan.h)
   std::string name;
   DevBuf d_w, d_b, d_w2, d_b2;
   // pure functions of the shape; the planner adds its switches (Planner::s2c_ok, s2c_tail_ok)
-  static bool supported(int cin, int cout, int hout, int wout);
-  static bool tail_supported(int cin, int cout, int cout2, int hout, int wout);
-  static bool lds_staged(int cin, int cout);   // the shape's kernel stages its input tile in LDS (s2lds_kernel: what LITEPI_NO_S2LDS turns off)
+  static bool supported(int cin, int cout, int hout, int wout) { return c2fplan::s2_supported(cin, cout, hout, wout); }
+  static bool tail_supported(int cin, int cout, int cout2, int hout, int wout) { return c2fplan::s2_tail_supported(cin, cout, cout2, hout, wout); }
+  static bool lds_staged(int cin, int cout) { return c2fplan::s2_lds_staged(cin, cout); }   // the shape's kernel stages its input tile in LDS (s2lds_kernel: what LITEPI_NO_S2LDS turns off)
   // w_tail [cout][cout] (1x1), b_tail: the fused tail, or null
   void build(int cin, int cout, int hout, int wout, const std::vector<float>& w_taps, const std::vector<float>& bias,
              const std::vector<float>* w_tail = nullptr, const std::vector<float>* b_tail = nullptr);
   void launch(const View& in, const View& out, int N, hipStream_t st) const;
-  std::string kernel_name() const;
+  std::string kernel_name() const { return c2fplan::s2_name(Cin, Cout, has_tail); }
 };
 
 // SPPF in one launch (sppf_kernel): cv1 (1x1 + SiLU) -> three cascaded 5x5 max pools -> cv2 (1x1 + SiLU) over concat(s, p1, p2, p3),
@@ -112,12 +86,12 @@ struct SppfLayer {
   std::string name;
   DevBuf d_w1, d_b1, d_w2, d_b2;
   double macs_per_image = 0;
-  static bool supported(int cin, int c, int cout, int h, int w);
+  static bool supported(int cin, int c, int cout, int h, int w) { return c2fplan::sppf_supported(cin, c, cout, h, w); }
   // w1 [c][cin], w2 [cout][4 c] over physical channels, fp32
   void build(int cin, int c, int cout, int h, int w, const std::vector<float>& w1, const std::vector<float>& b1, const std::vector<float>& w2,
              const std::vector<float>& b2);
   void launch(const View& in, const View& out, int N, hipStream_t st) const;
-  std::string kernel_name() const;
+  std::string kernel_name() const { return c2fplan::sppf_name(Cin, C, Cout); }
 };
 
 }  // namespace lp

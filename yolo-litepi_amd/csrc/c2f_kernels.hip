@@ -40,102 +40,9 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
+using namespace c2fplan;   // configurations, rows, predicates and packers: c2f_plan.h
+
 namespace {
-
-constexpr int cdiv_c(int a, int b) { return (a + b - 1) / b; }
-constexpr int min_c(int a, int b) { return a < b ? a : b; }
-constexpr int max_c(int a, int b) { return a > b ? a : b; }
-// how many K steps of pixel fragments from global memory a 1x1 phase keeps in flight (C2fCfg::DEEP): as many as ~180
-// registers of fragments + accumulators allow.  (Measured neutral: cv1 of the c = 24 module at depth 5 instead of 2, and of
-// v1's c = 16 FPN module at 3 instead of 2, ran in the same 82 / 46 us -- a K step's 1.3 k cycles are not one exposed round
-// trip, the fetch path is busy with the eight waves' streams whatever the depth.  Kept for v2's configurations.)
-constexpr int deep_depth(int S, int NT, int PT, bool ldsw) {
-  int d = 2;
-  for (int t = 3; t <= 6 && t <= S; ++t)
-    if ((t * (PT + (ldsw ? 0 : NT)) + (ldsw ? 2 * NT : 0) + NT * PT) * 4 <= 180) d = t;
-  return d;
-}
-
-template <int C_, int NB_, int KA_, int KB_, bool UP_, int COUT_, int MODE_, int KS2_, int TH_ = 20, int NW_PERIMG = 8, bool AW_ = true, int WPS_ = 0,
-          bool DEEP_ = false, int NWT_ = 0>
-struct C2fCfg {
-  static constexpr int C = C_, NB = NB_, KA = KA_, KB = KB_, COUT = COUT_, MODE = MODE_, KS2 = KS2_;
-  static constexpr bool UP = UP_;
-  static constexpr bool PERIMG = MODE_ >= 1;   // the tile is the whole image: no halo recompute, a 1-pixel zero ring
-  // MODE -1: the module WITHOUT cv1 -- the launch in front (the stride-2 conv with cv1 as its 1x1 tail, s2lds_kernel) wrote y0 | y1
-  // into the concat buffer; y1 (+ halo) is copied into plane 0.  For n = 2 modules cv1 on the halo-4 region was 2x its work.
-  static constexpr bool XCV1 = MODE_ == -1;
-  // waves per workgroup.  c = 16: four, so that two workgroups (LDS allows it) share a CU at one wave each per SIMD with
-  // the whole register file -- two independent workgroups drift out of phase and cover each other's epilogues and waits;
-  // eight waves under a 128-register cap spilled in every epilogue
-  // whole-image configurations: NW_PERIMG = 8.  (Four waves with the whole register file each -- every wave streams its
-  // channel block's weights from L2 itself, so halving the waves halves that traffic -- measured slower: 112 vs 100 us for
-  // the backbone kernel; one wave per SIMD exposes every LDS and L2 latency.)
-  // (NWT_: a tile configuration of c < 32 whose LDS allows only ONE workgroup per CU runs eight waves like the wide ones)
-  static constexpr int NW = MODE_ >= 1 ? NW_PERIMG : (NWT_ > 0 ? NWT_ : (C_ >= 32 ? 8 : 4));
-  static constexpr int TH = TH_, TW = 20;
-  static constexpr int F = PERIMG ? 1 : 2 * NB;  // frame margin around the tile
-  static constexpr int LW = TW + 2 * F, LH = TH + 2 * F;
-  // general K packing of the 3x3 convs (v2's widths c = 24 / 48: a tap is not a whole number of 32-channel K steps): K group
-  // q = 4 s + gam -> (tap q / (c/8), channel group q % (c/8)), a per-lane table of LDS offsets (c3_phase)
-  static constexpr bool GK = C % 32 != 0 && C != 16;
-  static constexpr bool DEEP = DEEP_ || GK || C == 96;   // (v2's configurations, A/B variants of v1's: deep_depth)
-  // bytes per LDS pixel of a c-channel plane: an odd number of 16-byte slots.  c % 16 != 0 (c = 24: 48 B = 3 slots): no pad at
-  // all -- the lanes that own the 8 padding rows of the second channel tile skip their stores
-  static constexpr int PS = C % 16 != 0 ? 2 * C : 2 * C + 16;
-  // c = 16, one bottleneck: plane 0 holds cv1's whole output y0 | y1 (2c channels per pixel), so that cv2's first K step
-  // (32 channels) is one plane-0 read and the module's concat buffer is never touched: no global round trip of y0 .. y2
-  static constexpr bool Y01 = C == 16 && NB == 1 && MODE_ == 0;
-  static constexpr int PS0 = Y01 ? 4 * C + 16 : PS;   // plane 0 pixel pitch
-  static constexpr int Y1OFF = Y01 ? 2 * C : 0;       // byte offset of y1 inside a plane-0 pixel
-  static constexpr int PLANE0 = LW * LH * PS0, PLANE = LW * LH * PS;
-  static constexpr int XC = 2 * C;               // output channels of the entry conv
-  // how far each phase's region extends beyond the tile
-  static constexpr int e_cv1 = PERIMG ? 0 : 2 * NB;
-  static constexpr int e_a(int k) { return PERIMG ? 0 : 2 * (NB - k) - 1; }
-  static constexpr int e_b(int k) { return PERIMG ? 0 : 2 * (NB - k) - 2; }
-  static constexpr int npt(int e) { return cdiv_c((TH + 2 * e) * (TW + 2 * e), 16); }
-  // block shapes (NT channel tiles x PT pixel tiles per wave, CB channel blocks): one round of blocks per phase, two
-  // where one would not fit the register file (cap_pt)
-  static constexpr int MAXT = (MODE_ >= 1 && NW_PERIMG == 4) ? 52 : 20;   // accumulator tiles a wave can hold
-  static constexpr int cap_pt(int nt, int pt) { return nt * pt > (nt == 3 ? 21 : MAXT) ? cdiv_c(pt, 2) : pt; }
-  // (whole-image configurations: cv1's fragments are staged in plane 1, which nothing uses before the first bottleneck conv,
-  //  and a wave holds every output channel of two pixel tiles -- as the entry conv, see WB_S2)
-  static constexpr bool W1_LDS = PERIMG;
-  // (channel tiles in threes where the count allows it -- v2's 48 / 96 / 192 channels: NT = 3, a lane owns 12 consecutive channels)
-  static constexpr int CT1 = 2 * C / 16, NT1 = W1_LDS ? CT1 : (CT1 % 3 == 0 ? 3 : min_c(CT1, 4)), CB1 = CT1 / NT1,
-                       PT1 = W1_LDS ? 2 : cap_pt(NT1, cdiv_c(npt(e_cv1), NW / CB1));
-  static constexpr int CTM = cdiv_c(C, 16), NTM = CTM % 3 == 0 ? 3 : min_c(CTM, 2), CBM = CTM / NTM;
-  static constexpr int ptm(int e) { return cdiv_c(npt(e), NW / CBM); }
-  static constexpr int CT2 = COUT / 16, NT2 = CT2 % 3 == 0 ? 3 : (CT2 >= 2 ? CT2 / 2 : 1), CB2 = CT2 / NT2, PT2 = cap_pt(NT2, cdiv_c(npt(0), NW / CB2));
-  static constexpr int PT2W = cdiv_c(npt(0), NW / CB2);   // whole-image cv2: one round of blocks (pw_sync_phase)
-  static constexpr int NTS = NTM, CBS = CBM, PTS = cdiv_c(npt(0), NW / CBS);  // SPPF.cv1 (c outputs)
-  static constexpr int WPS = WPS_ > 0 ? WPS_ : (NW == 4 && MODE_ >= 1 ? 1 : 2);   // waves per SIMD the register allocation must allow
-  // cv2 reads y_NB and y_{NB+1} from the LDS planes (whole K steps need c >= 32); the earlier segments from the concat buffer
-  // cv2's K steps straddle the concat's segments (c = 24 / 48; c = 16 with two bottlenecks: 32 channels of y0 | y1 from the concat
-  // buffer, y2 and y3 from the planes): pw_gk_phase's per-lane source table
-  static constexpr bool CV2_TAB = GK || (C == 16 && NB == 2);
-  static constexpr bool CV2_LDS = C >= 32 || Y01 || CV2_TAB;
-  static constexpr int K2G = Y01 ? 0 : (CV2_LDS ? NB * C : (2 + NB) * C);
-  // weights staged in LDS (tile configurations): fragment bytes of every phase, in execution order
-  static constexpr bool AW = !PERIMG && AW_;
-  static constexpr int c3_steps = GK ? cdiv_c(9 * (C / 8), 4) : (C >= 32 ? 9 * (C / 32) : 5);
-  static constexpr int WB_CV1 = CT1 * cdiv_c(KA + KB, 32) * 1024, WB_M = CTM * c3_steps * 1024, WB_CV2 = CT2 * cdiv_c((2 + NB) * C, 32) * 1024;
-  static constexpr int WSLOT = AW ? max_c(WB_CV1, max_c(WB_M, WB_CV2)) : 0;
-  // whole-image configurations: the entry conv runs before anything lives in the planes, so ALL of its fragments are staged
-  // in LDS (144 KB for 64 -> 128 channels) and a wave holds every output channel of its pixels (NT = all row tiles): each
-  // pixel fragment is gathered from global memory exactly once per workgroup.  With the weights streamed from L2 by every
-  // wave this phase moved 2 MB through the CU's L1 and took 88 k of the kernel's 230 k cycles.
-  static constexpr int NT_S2 = XC / 16, PT_S2 = 2;
-  static constexpr int WB_S2 = PERIMG ? NT_S2 * 9 * (KS2 / 32) * 1024 : 0;
-  static constexpr int LDS_BYTES = max_c(PLANE0 + PLANE + 2 * WSLOT, WB_S2);
-  static_assert(!W1_LDS || WB_CV1 <= PLANE, "cv1's fragments are staged in plane 1");
-  static C2fShape shape() {
-    C2fShape s;
-    s.C = C; s.NB = NB; s.KA = KA; s.KB = KB; s.UP = UP ? 1 : 0; s.COUT = COUT; s.MODE = MODE; s.KS2 = KS2;
-    return s;
-  }
-};
 
 struct Ctx {
   int n, oy0, ox0, H, W;
@@ -261,6 +168,21 @@ template <int NT> __device__ __forceinline__ void to_half(const floatx4 (&v)[NT]
     for (int r = 0; r < 4; ++r) h[4 * t + r] = (half_t)v[t][r];
 }
 
+// Epilogue of a phase whose output goes to a global NHWC tensor and nowhere else: this lane's 4*NT activated channels of region
+// pixel (py, px) -> base + pixel * pitch * 2 + channel * 2.  The stride-2 convs (c3s2_phase: the entry conv of the whole-image
+// configurations, s2conv_kernel) use it; the other global-store epilogues of c2f_kernel keep their lambdas, since cv2, SPPF.cv1's
+// debug store, sppf_tail and the concat stores of cv1 / epi_b through this form changed the register allocation of their kernels.
+template <int NT> struct GlobalEpi {
+  const Ctx& cx; const Rg& rg; char* const& base; const int& pitch;
+  __device__ __forceinline__ void operator()(int cb, bool ok, int py, int px, const floatx4 (&v)[NT]) const {
+    const int chb = cb * 16 * NT + 4 * NT * cx.g;
+    half_t h[4 * NT];
+    to_half<NT>(v, h);
+    const int gpix = (cx.n * cx.H + rg.gy0 + py) * cx.W + rg.gx0 + px;
+    if (ok) store_h<NT>(base + (size_t)((unsigned)gpix * (unsigned)pitch) * 2 + chb * 2, h);
+  }
+};
+
 // K loop of one block: acc[t][i] += A(step s, tile t) . B(step s, pixel tile i).  DA / DB register sets for the A / B
 // fragments: step s + D - 1 is requested before the MFMAs of step s (static indices after unrolling); fix() runs on a
 // step's B fragments right before they are consumed (border masks of the stride-2 gather: applied at the load they would
@@ -355,8 +277,7 @@ __device__ __forceinline__ void pw_phase(const Ctx& cx, const Rg& rg, const char
     for (int t = 0; t < NT; ++t) bv[t] = *reinterpret_cast<const floatx4*>(bias + cb * 16 * NT + 4 * NT * cx.g + 4 * t);
     // (whole-image cv1: 8 waves on the CU and a handful of K steps -- the pixel fragments of up to 5 steps ahead are in flight,
     //  at depth 3 the K loop ran at the L2 round trip: 18 B/clk for the CU)
-    constexpr int DB = CFG::DEEP ? deep_depth(S, NT, PT, LDSW)
-                                 : ((CFG::PERIMG && LDSW) ? min_c(S, 5) : (((NT * PT <= 20 && CFG::C >= 32) || (CFG::WPS == 1 && NT * PT <= 28)) ? 3 : 2));
+    constexpr int DB = CFG::DEEP ? deep_depth(S, NT, PT, LDSW) : ((CFG::PERIMG && LDSW) ? min_c(S, 5) : ((NT * PT <= 20 && CFG::C >= 32) ? 3 : 2));
     constexpr int DA = LDSW ? 2 : DB;
     if (stamp0 >= 0) { C2F_ISTAMP(stamp0) }
     kloop<S, DA, DB, NT, PT>(
@@ -680,7 +601,7 @@ __device__ __forceinline__ void c3s2_phase(const Ctx& cx, const Rg& rg, const ch
     floatx4 bv[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) bv[t] = *reinterpret_cast<const floatx4*>(bias + cb * 16 * NT + 4 * NT * cx.g + 4 * t);
-    constexpr int D = (LDSW && PT <= 2) ? 5 : ((NT * PT <= 20 || (CFG::WPS == 1 && NT * PT <= 28)) ? 3 : 2);
+    constexpr int D = (LDSW && PT <= 2) ? 5 : (NT * PT <= 20 ? 3 : 2);
     if (blk == 0) { C2F_ISTAMP(8) }
     kloop<S, (LDSW ? 2 : D), D, NT, PT>(
         acc, [&](int s, half8(&af)[NT]) { wsrc.template load<NT>(woff, s, af); },
@@ -917,14 +838,7 @@ __global__ __launch_bounds__(CFG::NW * 64, CFG::WPS) void c2f_kernel(const C2fAr
     char* xo = reinterpret_cast<char*>(a.x);
     wg_sync();
     c3s2_phase<CFG, CFG::NT_S2, 1, CFG::PT_S2, true>(cx, rg, reinterpret_cast<const char*>(a.s2_in), a.s2_pitch, ASrc<true>{smem}, a.b[C2F_W_S2],
-                                                     [&](int cb, bool ok, int py, int px, const floatx4(&v)[CFG::NT_S2]) {
-                                                       constexpr int NT = CFG::NT_S2;
-                                                       const int chb = cb * 16 * NT + 4 * NT * cx.g;
-                                                       half_t h[4 * NT];
-                                                       to_half<NT>(v, h);
-                                                       const int gpix = (cx.n * cx.H + rg.gy0 + py) * cx.W + rg.gx0 + px;
-                                                       if (ok) store_h<NT>(xo + (size_t)((unsigned)gpix * (unsigned)a.x_pitch) * 2 + chb * 2, h);
-                                                     });
+                                                     GlobalEpi<CFG::NT_S2>{cx, rg, xo, a.x_pitch});
     wg_sync();
   }
   // pixels outside the image must read as zero (the convs' padding): they are never written, so clear the planes once.
@@ -1125,15 +1039,6 @@ __global__ __launch_bounds__(CFG::NW * 64, CFG::WPS) void c2f_kernel(const C2fAr
 // ---- stand-alone 3x3 stride-2 conv + SiLU (the downsampling convs between the modules, model.ncnn.param:41,118): one
 //      workgroup per 20 x 20 output tile, the weights staged once in LDS, the pixel operand gathered from global memory
 //      (every input pixel is touched by 2.25 taps on average; the tile's neighbours share them through L1 / L2).
-template <int CIN_, int COUT_, int TH_ = 20>
-struct S2Cfg {
-  static constexpr int KS2 = CIN_, COUT = COUT_, NW = 8, TH = TH_, TW = 20, F = 0, WPS = 2, C = 32;
-  static constexpr int CT = COUT / 16, NT = min_c(CT, 4), CB = CT / NT, PT = cdiv_c(cdiv_c(TH * TW, 16), NW / CB);
-  static constexpr int WBYTES = CT * 9 * (KS2 / 32) * 1024;
-  // what the host's table (for_each_s2cfg) reads from either stride-2 configuration type, under S2LCfg's names
-  static constexpr bool LDS_STAGED = false, TAIL = false;
-  static constexpr int CIN = CIN_, OSPLIT = 1, KSPLIT = 1, S = 9 * (KS2 / 32), LDS_BYTES = WBYTES;
-};
 template <class CFG>
 __global__ __launch_bounds__(CFG::NW * 64, 2) void s2conv_kernel(const C2fArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1161,14 +1066,7 @@ __global__ __launch_bounds__(CFG::NW * 64, 2) void s2conv_kernel(const C2fArgs a
   C2F_STAMP(2)
   char* xo = reinterpret_cast<char*>(a.x);
   c3s2_phase<CFG, CFG::NT, CFG::CB, CFG::PT, true>(cx, rg, reinterpret_cast<const char*>(a.s2_in), a.s2_pitch, ASrc<true>{smem}, a.b[C2F_W_S2],
-                                                  [&](int cb, bool ok, int py, int px, const floatx4(&v)[CFG::NT]) {
-                                                    constexpr int NT = CFG::NT;
-                                                    const int chb = cb * 16 * NT + 4 * NT * cx.g;
-                                                    half_t h[4 * NT];
-                                                    to_half<NT>(v, h);
-                                                    const int gpix = (cx.n * cx.H + rg.gy0 + py) * cx.W + rg.gx0 + px;
-                                                    if (ok) store_h<NT>(xo + (size_t)((unsigned)gpix * (unsigned)a.x_pitch) * 2 + chb * 2, h);
-                                                  });
+                                                  GlobalEpi<CFG::NT>{cx, rg, xo, a.x_pitch});
   C2F_STAMP(7)
   C2F_STAMP(15)
 }
@@ -1180,29 +1078,6 @@ __global__ __launch_bounds__(CFG::NW * 64, 2) void s2conv_kernel(const C2fArgs a
 //      packing for Cin 24 / 48 (c3_pack's order), the weights of this workgroup's output channels in a second LDS region.
 //      OSPLIT workgroups share an output tile (each stages the input tile and computes COUT / OSPLIT channels) when the whole
 //      weight set would not fit beside the plane.
-template <int CIN_, int COUT_, int TH_, int OSPLIT_, int KSPLIT_ = 1, bool TAIL_ = false>
-struct S2LCfg {
-  // TAIL: a 1x1 conv + SiLU on the result (C2f.cv1 behind the stride-2 conv: COUT -> COUT channels) runs on the accumulators --
-  // a lane's 4 NT consecutive channels of a pixel ARE a K group of the next MFMA's pixel operand (conv_kernels.hip tail_store)
-  static constexpr bool TAIL = TAIL_, LDS_STAGED = true;
-  static constexpr int CIN = CIN_, COUT = COUT_, TH = TH_, TW = 20, NW = 8, OSPLIT = OSPLIT_, KSPLIT = KSPLIT_;
-  static constexpr int COUTW = COUT / OSPLIT;   // output channels of one workgroup
-  static constexpr int CINH = CIN / KSPLIT;     // input channels of one pass (Cin 96: two passes of 48 -- a 21 x 41 plane of 96 is 179 KB)
-  static constexpr int CT = COUTW / 16, NT = CT % 3 == 0 ? 3 : min_c(CT, 4), CB = CT / NT;
-  static constexpr bool GK = CINH % 32 != 0;
-  static constexpr int G = CINH / 8, S = GK ? cdiv_c(9 * G, 4) : 9 * (CINH / 32);   // K groups per tap, K steps per pass
-  static constexpr int IH = 2 * TH + 1, IW = 2 * TW + 1, LW = IW;
-  static constexpr int PS = CINH % 16 != 0 ? 2 * CINH : 2 * CINH + 16;   // an odd number of 16-byte slots (C2fCfg::PS)
-  static constexpr int PLANE = ((IH * LW * PS + 1023) / 1024) * 1024, WBYTES = CT * S * 1024, LDS_BYTES = PLANE + WBYTES;
-  static constexpr int NPT = cdiv_c(TH * TW, 16), PT = cdiv_c(NPT, NW / CB), NBLK = cdiv_c(NPT, PT) * CB;
-  static_assert(COUT % (16 * OSPLIT) == 0 && COUTW % (16 * NT) == 0 && NW % CB == 0 && CIN % (8 * KSPLIT) == 0 && LDS_BYTES <= 160 * 1024 && NBLK <= NW,
-                "s2lds: shape (one block per wave: the accumulators live across the passes)");
-  static_assert(CB == 1 || KSPLIT == 1, "the packed weights are [channel block][all K steps]: a pass is contiguous only for one block");
-  // (NT = 2: a lane's 8 channels are one K group, one K step; NT = 3: its 12 channels are K group g of step 0 and the first half of
-  //  K group g of step 1, whose second half is zero -- the tail's weights are packed to that order, S2ConvLayer::build)
-  static constexpr int TSTEPS = NT == 3 ? 2 : 1;
-  static_assert(!TAIL || (OSPLIT == 1 && CB == 1 && ((NT == 2 && COUT == 32) || (NT == 3 && COUT == 48))), "tail: the workgroup holds every channel of a pixel");
-};
 template <class CFG>
 __global__ __launch_bounds__(CFG::NW * 64, 2) void s2lds_kernel(const C2fArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1355,39 +1230,12 @@ __global__ __launch_bounds__(CFG::NW * 64, 2) void s2lds_kernel(const C2fArgs a)
     }
   }
 }
-typedef S2LCfg<24, 48, 10, 1> S2L24x48;   // yolo_plus model.ncnn.param:10 (conv_8: 24 -> 48 @80x80): 41 KB plane + 21 KB of weights
-// (Cin 48 in two passes of 24 input channels: 41 KB plane + 21 KB of weights, two workgroups per CU.  The one-pass forms -- 96 KB plane +
-//  42 KB -- lost)
-typedef S2LCfg<48, 96, 10, 2, 2> S2L48x96k2;   // :27 (conv_15: 48 -> 96 @40x40), two workgroups per tile
-typedef S2LCfg<48, 48, 10, 1, 2> S2L48x48k2;   // :129 (conv_37: 48 -> 48 @40x40)
-// (v1's 32 -> 64 convs as S2LCfg<32, 64, 10, 1, 2>, two passes of 16 channels: 22.9 / 16.2 us against 22.0 / 14.0 for the gather kernel
-//  above -- at Cin 32 the tile copy costs what the gathers cost; they stay on s2conv_kernel)
-typedef S2LCfg<16, 32, 10, 1, 1, true> S2L16x32t;   // v1 model.ncnn.param:19-20 (conv_6 16 -> 32 @80x80 + conv_7 = C2f.cv1 32 -> 32 as its tail)
-typedef S2LCfg<24, 48, 10, 1, 1, true> S2L24x48t;   // v2 :10-11 (conv_8 24 -> 48 @80x80 + conv_9 = C2f.cv1 48 -> 48 as its tail)
-typedef S2LCfg<64, 128, 10, 2, 2> S2L64x128;   // v1's 64 -> 128 convs @20x20 (model.ncnn.param:62, :134) when they do not ride in the whole-image kernels
-typedef S2LCfg<96, 192, 10, 4, 2> S2L96x192;   // :44 (conv_22: 96 -> 192 @20x20): two passes of 48 input channels, four workgroups per tile
-typedef S2LCfg<96, 96, 10, 2, 2> S2L96x96;     // :142 (conv_42: 96 -> 96 @20x20)
-
-typedef S2Cfg<32, 64> S2Cfg32x64;   // model.ncnn.param:41 (conv_15: 32 -> 64 @40x40) and :118 (conv_37)
-
 // ---- SPPF in one launch for widths whose planes do not fit the whole-image C2f kernel (v2: c = 96 @20x20, yolo_plus
 //      model.ncnn.param:75-87): cv1 (1x1 + SiLU) -> s in ONE LDS plane over the whole image -> cv2 accumulated over s and the three
 //      cascaded 5x5 max pools as they replace each other in that plane (sppf_tail's scheme).  The pools run IN PLACE: a thread
 //      owns ten outputs of one line and channel group, loads their fourteen inputs, and stores behind a workgroup barrier
 //      (pool_phase needs a second plane; two planes of 96 channels are 166 KB).  OSPLIT workgroups share an image: each
 //      computes s and the pools itself (cheap) and COUT / OSPLIT channels of cv2.  Weights from L2.
-template <int C_, int CIN_, int COUT_, int OSPLIT_>
-struct SpCfg {
-  static constexpr int C = C_, CIN = CIN_, COUT = COUT_, OSPLIT = OSPLIT_, COUTW = COUT / OSPLIT, NW = 8, TH = 20, TW = 20, F = 0, LW = 20;
-  static constexpr int PS = 2 * C + 16;
-  static constexpr bool PERIMG = false, DEEP = true;
-  static constexpr int WPS = 2;
-  static constexpr int NT1 = 3, CB1 = C / 48, PT1 = cdiv_c(25, NW / CB1);
-  static constexpr int NT2 = 3, CB2 = COUTW / 48, PT2 = cdiv_c(25, NW / CB2);
-  static constexpr int SPT = C / 32, LDS_BYTES = TH * TW * PS;
-  static_assert(C % 96 == 0 && CIN % 32 == 0 && COUTW % 48 == 0 && NW % CB1 == 0 && NW % CB2 == 0 && CB2 * cdiv_c(25, PT2) <= NW && NT2 * PT2 <= 28,
-                "sppf: shape (one block per wave in cv2: the accumulators live across the pools)");
-};
 template <class CFG>
 __device__ __forceinline__ void pool_inplace(char* P0) {
   constexpr int CG = CFG::C / 8, LW = CFG::LW, PS = CFG::PS;
@@ -1523,188 +1371,42 @@ __global__ __launch_bounds__(CFG::NW * 64, 2) void sppf_kernel(const C2fArgs a) 
     }
   }
 }
-typedef SpCfg<96, 192, 192, 2> SpCfgV2;   // yolo_plus model.ncnn.param:75-87 (conv_27, three pools, conv_28): 83 KB plane, two workgroups per image
-
-// ---- instantiated configurations (YOLO-LitePi v1 widths; model.ncnn.param line of the module's cv1) ----------------------
-typedef C2fCfg<32, 1, 128, 64, true, 64, 0, 0> CfgNeck40;    // :90  up(P5) | P4 -> C2f(n=1) @40x40
-typedef C2fCfg<16, 1, 64, 32, true, 32, 0, 0, 16> CfgNeck80;     // :105 up(F4) | P3 -> C2f(n=1) @80x80
-typedef C2fCfg<32, 1, 0, 128, false, 64, 0, 0> CfgPan40;     // :121 conv_37 | F4 -> C2f(n=1) @40x40
-typedef C2fCfg<64, 1, 0, 256, false, 128, 1, 64> CfgPan20;   // :134-147 conv_42 (s2) | P5 -> C2f(n=1) @20x20
-typedef C2fCfg<64, 1, 0, 128, false, 128, 2, 64> CfgBb20;    // :62-85 conv_22 (s2) -> C2f(n=1) -> SPPF @20x20
-typedef C2fCfg<16, 2, 0, 32, false, 32, 0, 0, 16> CfgBb80;       // :22-38 C2f(n=2) @80x80
-typedef C2fCfg<32, 2, 0, 64, false, 64, 0, 0> CfgBb40;       // :43-59 C2f(n=2) @40x40
-// YOLO-LitePi v2 widths (src/tt100k/convert/model/yolo_plus/yolo_plus_ncnn_model/model.ncnn.param, line of the module's cv1).
-// c = 48 / 96: the phases' weights do not fit beside the planes -- every wave streams its channel block's fragments from L2 (AW off)
-typedef C2fCfg<48, 1, 192, 96, true, 96, 0, 0, 20, 8, false> CfgV2Neck40;   // :101 up(P5) | P4 -> C2f(n=1) @40x40
-typedef C2fCfg<48, 1, 0, 144, false, 96, 0, 0, 20, 8, false> CfgV2Pan40;    // :132 conv_37 | F4 -> C2f(n=1) @40x40
-typedef C2fCfg<24, 1, 96, 48, true, 48, 0, 0, 16> CfgV2Neck80;              // :116 up(F4) | P3 -> C2f(n=1) @80x80
-typedef C2fCfg<96, 1, 0, 192, false, 192, 0, 0, 10, 8, false> CfgV2Bb20;    // :63 C2f(n=1) @20x20, two half-image tiles
-typedef C2fCfg<96, 1, 0, 288, false, 192, 0, 0, 10, 8, false> CfgV2Pan20;   // :145 conv_42 | P5 -> C2f(n=1) @20x20, two half-image tiles
-typedef C2fCfg<24, 2, 0, 48, false, 48, -1, 0, 20, 8, true, 0, false, 8> CfgV2Bb80x;   // v2 :13-26 C2f(n=2) @80x80 without cv1 (as CfgBb80x)
-typedef C2fCfg<16, 2, 0, 32, false, 32, -1, 0, 16> CfgBb80x;     // v1 :22-38 C2f(n=2) @80x80 WITHOUT cv1 (MODE -1: cv1 is the tail of the stride-2 conv in front)
-typedef C2fCfg<64, 1, 0, 256, false, 128, 0, 0, 10, 8, false> CfgPan20h;    // v1's PAN 20x20 module WITHOUT its entry conv on two half-image tiles (A/B:
-typedef C2fCfg<64, 1, 0, 128, false, 128, 0, 0, 10, 8, false> CfgBb20h;     //  LITEPI_C2F_SKIP of the whole-image configurations), and the backbone's
-typedef C2fCfg<24, 2, 0, 48, false, 48, 0, 0, 20, 8, true, 0, false, 8> CfgV2Bb80;   // :13 C2f(n=2) @80x80 (halo 4; 103 KB: ONE workgroup per CU, so eight waves
-                                                                                     // and 20-row tiles: 130 -> 123 -> 119 us; the n = 1 module on the same shape: 91 vs 80 us for two 4-wave workgroups)
-typedef C2fCfg<48, 2, 0, 96, false, 96, 0, 0, 10, 8, false> CfgV2Bb40;      // :30 C2f(n=2) @40x40 (halo 4, 10-row tiles)
-
-template <class CFG> struct CfgName;
-#define C2F_NAME(T, s) \
-  template <> struct CfgName<T> { static const char* get() { return s; } };
-C2F_NAME(CfgNeck40, "c2f<32,1,up128+64>")
-C2F_NAME(CfgNeck80, "c2f<16,1,up64+32>")
-C2F_NAME(CfgPan40, "c2f<32,1,128>")
-C2F_NAME(CfgPan20, "c2f<64,1,s2+256>")
-C2F_NAME(CfgBb20, "c2f<64,1,s2+128,sppf>")
-C2F_NAME(CfgBb80, "c2f<16,2,32>")
-C2F_NAME(CfgBb40, "c2f<32,2,64>")
-C2F_NAME(CfgV2Neck40, "c2f<48,1,up192+96>")
-C2F_NAME(CfgV2Pan40, "c2f<48,1,144>")
-C2F_NAME(CfgV2Neck80, "c2f<24,1,up96+48>")
-C2F_NAME(CfgV2Bb20, "c2f<96,1,192>")
-C2F_NAME(CfgV2Pan20, "c2f<96,1,288>")
-C2F_NAME(CfgV2Bb80, "c2f<24,2,48>")
-C2F_NAME(CfgBb80x, "c2f<16,2,y0y1>")
-C2F_NAME(CfgV2Bb80x, "c2f<24,2,y0y1>")
-C2F_NAME(CfgPan20h, "c2f<64,1,256>")
-C2F_NAME(CfgBb20h, "c2f<64,1,128>")
-C2F_NAME(CfgV2Bb40, "c2f<48,2,96>")
-
-template <class CFG> size_t cfg_lds() { return (size_t)CFG::LDS_BYTES; }
-
+// launch() is an index into the for_each_* lists of c2f_plan.h: the type whose key is the layer's
 template <class CFG> bool try_launch(const C2fShape& s, const C2fArgs& a, hipStream_t st) {
   if (!(s == CFG::shape())) return false;
-  const size_t lds = cfg_lds<CFG>();
-  set_max_dynamic_lds(reinterpret_cast<const void*>(&c2f_kernel<CFG>), (int)lds);
+  set_max_dynamic_lds(reinterpret_cast<const void*>(&c2f_kernel<CFG>), CFG::LDS_BYTES);
   const int grid = a.N * a.tiles_x * a.tiles_y;
-  LP_LAUNCH(c2f_kernel<CFG>, dim3(grid), dim3(CFG::NW * 64), lds, st, a);
+  LP_LAUNCH(c2f_kernel<CFG>, dim3(grid), dim3(CFG::NW * 64), (size_t)CFG::LDS_BYTES, st, a);
   return true;
 }
-struct CfgInfo { size_t lds; const char* name; bool perimg, gk, cv2_lds; int th, tw, nt1, ntm, nt2, nt_s2; };
-template <class CFG> bool try_info(const C2fShape& s, CfgInfo& ci) {
-  if (!(s == CFG::shape())) return false;
-  ci.lds = cfg_lds<CFG>();
-  ci.name = CfgName<CFG>::get();
-  ci.perimg = CFG::PERIMG;
-  ci.gk = CFG::GK;
-  ci.cv2_lds = CFG::CV2_LDS;
-  ci.th = CFG::TH; ci.tw = CFG::TW;
-  ci.nt1 = CFG::NT1; ci.ntm = CFG::NTM; ci.nt2 = CFG::NT2; ci.nt_s2 = CFG::NT_S2;
-  return true;
-}
-// every instantiated configuration, in one place: f.template operator()<CFG>() until one returns true
-template <class F> bool for_each_cfg(F&& f) {
-  return f.template operator()<CfgNeck40>() || f.template operator()<CfgNeck80>() || f.template operator()<CfgPan40>() ||
-         f.template operator()<CfgPan20>() || f.template operator()<CfgBb20>() || f.template operator()<CfgBb80>() ||
-         f.template operator()<CfgBb40>() || f.template operator()<CfgV2Neck40>() || f.template operator()<CfgV2Pan40>() ||
-         f.template operator()<CfgV2Neck80>() || f.template operator()<CfgV2Bb20>() || f.template operator()<CfgV2Pan20>() ||
-         f.template operator()<CfgV2Bb80>() || f.template operator()<CfgV2Bb40>() || f.template operator()<CfgPan20h>() ||
-         f.template operator()<CfgBb20h>() || f.template operator()<CfgBb80x>() || f.template operator()<CfgV2Bb80x>();
-}
-struct InfoFn {
-  const C2fShape& s; CfgInfo& ci;
-  template <class CFG> bool operator()() const { return try_info<CFG>(s, ci); }
-};
 struct LaunchFn {
   const C2fShape& s; const C2fArgs& a; hipStream_t st;
   template <class CFG> bool operator()() const { return try_launch<CFG>(s, a, st); }
 };
-// the configuration of a shape.  No switches in this file's supported / build / launch / names: which configurations a load may
-// use is the planner's business (PlanSwitches, detector_plan.cpp), and a layer that was planned keeps its kernel
-// (v2's n = 2 backbone modules run as one launch each: 139 us against 150 for the four launches of the 80x80 one -- 145 before
-//  cv2 took y2 / y3 from the planes --, +1.5 % of the pipelined rate; 10-row tiles on the 40x40 map: 74 against 118)
-bool cfg_info(const C2fShape& s, CfgInfo& ci) { return for_each_cfg(InfoFn{s, ci}); }
 
-int gam_of(int g) { return ((g & 1) << 1) | (g >> 1); }
-
-// ---- K orders of the packed A fragments, each named once: (K step s, lane group g, element j) -> index into a row of the weight
-//      matrix, or -1 (zero).  A lane group holds K group gam(g) of its step (the LDS column permutation, top of the file).
-// 1x1: the row's ktot channels in order
-auto k_1x1(int ktot) {
-  return [ktot](int s, int g, int j) {
-    const int k = 32 * s + 8 * gam_of(g) + j;
-    return k < ktot ? k : -1;
-  };
+// build(): what the packers of c2f_plan.h return, on the device (an empty vector: the launch does not use the slot)
+template <class T> void upload(DevBuf& dst, const std::vector<T>& v) {
+  if (v.empty()) return;
+  dst.alloc(v.size() * sizeof(T), false);
+  LP_HIP(hipMemcpy(dst.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
 }
-// 3x3, rows [tap][cin], general order (C2fCfg::GK, S2LCfg): K group q = 4 s + gam -> (tap q / G, channel group q % G) over the
-// G = cin / ksplit / 8 groups of one pass; the steps of pass h (input channels h cin / ksplit ..) follow those of pass h - 1
-constexpr int steps_3x3_general(int cin, int ksplit = 1) { return (9 * (cin / ksplit / 8) + 3) / 4; }
-auto k_3x3_general(int cin, int ksplit = 1) {
-  const int cinh = cin / ksplit, G = cinh / 8, S = steps_3x3_general(cin, ksplit);
-  return [=](int s, int g, int j) {
-    const int h = s / S, q = 4 * (s % S) + gam_of(g);
-    return q < 9 * G ? (q / G) * cin + h * cinh + 8 * (q % G) + j : -1;
-  };
-}
-// 3x3, cin % 32 == 0: K step s -> (tap s / (cin / 32), 32-channel block s % (cin / 32))
-auto k_3x3_c32(int cin) {
-  const int spt = cin / 32;
-  return [=](int s, int g, int j) { return (s / spt) * cin + 32 * (s % spt) + 8 * gam_of(g) + j; };
-}
-// 3x3, 16 channels: a K step covers two taps (TA for the even lane groups, TB for the odd ones), five steps
-auto k_3x3_c16(int cin) {
-  return [=](int s, int g, int j) {
-    static const int TA[5] = {0, 3, 6, 1, 4}, TB[5] = {2, 5, 8, 7, -1};
-    const int tap = (g & 1) ? TB[s] : TA[s];
-    return tap < 0 ? -1 : tap * cin + 8 * (g >> 1) + j;
-  };
-}
-
-// A fragments of one phase: [channel block][K step][tile][lane][8 halfs]; lane (g = lane >> 4, m = lane & 15) holds
-// A[row m][K group g].  Rows are permuted so that a lane's D rows 4g .. 4g+3 of tiles 0 .. NT-1 are 4*NT consecutive
-// channels (vector stores).  kidx(s, g, j) -> index into the K axis of Wm ([cout][ktot]) or -1 (zero).
-template <class KIDX>
-void pack_phase(DevBuf& dst, const std::vector<float>& Wm, int cout, int ktot, int NT, int S, KIDX&& kidx) {
-  LP_CHECK((int)Wm.size() == cout * ktot, LP_ERR_STATE, "c2f: weight matrix %zu != %d x %d", Wm.size(), cout, ktot);
-  const int CB = (cout + 16 * NT - 1) / (16 * NT);   // (rows past cout: the zero padding of the last channel tile)
-  std::vector<uint16_t> buf((size_t)CB * S * NT * 64 * 8, 0);
-  for (int cb = 0; cb < CB; ++cb)
-    for (int s = 0; s < S; ++s)
-      for (int t = 0; t < NT; ++t)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int g = lane >> 4, m = lane & 15, gm = m >> 2, r = m & 3;
-          const int oc = cb * 16 * NT + gm * 4 * NT + t * 4 + r;
-          const size_t f = ((((size_t)cb * S + s) * NT + t) * 64 + lane) * 8;
-          if (oc >= cout) continue;
-          for (int j = 0; j < 8; ++j) {
-            const int k = kidx(s, g, j);
-            if (k >= 0) buf[f + j] = f32_to_f16(Wm[(size_t)oc * ktot + k]);
-          }
-        }
-  dst.alloc(buf.size() * 2, false);
-  LP_HIP(hipMemcpy(dst.p, buf.data(), buf.size() * 2, hipMemcpyHostToDevice));
-}
-void put_bias(DevBuf& dst, const std::vector<float>* b, int cout) {
-  std::vector<float> v(cout + 64, 0.f);
-  if (b) {
-    LP_CHECK((int)b->size() >= cout, LP_ERR_STATE, "c2f: bias vector too short");
-    for (int c = 0; c < cout; ++c) v[c] = (*b)[c];
-  }
-  dst.alloc(v.size() * 4, false);
-  LP_HIP(hipMemcpy(dst.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-}
-void pack_1x1(DevBuf& d, const std::vector<float>& wv, int cout, int ktot, int NT) { pack_phase(d, wv, cout, ktot, NT, (ktot + 31) / 32, k_1x1(ktot)); }
-// 3x3 weights [cout][tap][cin] in the order c3_phase / c3s2_phase read them at this width
-void pack_3x3(DevBuf& d, const std::vector<float>& wv, int cout, int cin, int NT) {
-  if (cin % 32 != 0 && cin != 16) pack_phase(d, wv, cout, 9 * cin, NT, steps_3x3_general(cin), k_3x3_general(cin));
-  else if (cin >= 32) pack_phase(d, wv, cout, 9 * cin, NT, 9 * (cin / 32), k_3x3_c32(cin));
-  else pack_phase(d, wv, cout, 9 * cin, NT, 5, k_3x3_c16(cin));
-}
-
-}  // namespace
 
 // diagnostic stamps (LITEPI_C2F_STAMPS=<file>): 16 words per workgroup, appended to the file after the launch
-static DevBuf g_stamp_buf;
-static unsigned long long* stamp_buffer(size_t nwg) {
+const char* stamp_file() {
+  static const char* file = getenv("LITEPI_C2F_STAMPS");
+  return file;
+}
+DevBuf g_stamp_buf;
+unsigned long long* stamp_buffer(size_t nwg) {
   if (g_stamp_buf.bytes < nwg * 16 * 8) g_stamp_buf.alloc(nwg * 16 * 8);
   LP_HIP(hipMemset(g_stamp_buf.p, 0, nwg * 16 * 8));
   return g_stamp_buf.as<unsigned long long>();
 }
-static void dump_stamps(const char* file, const std::string& name, size_t nwg, hipStream_t st) {
+void dump_stamps(const std::string& name, size_t nwg, hipStream_t st) {
   LP_HIP(hipStreamSynchronize(st));
   std::vector<unsigned long long> hst(nwg * 16);
   LP_HIP(hipMemcpy(hst.data(), g_stamp_buf.p, nwg * 16 * 8, hipMemcpyDeviceToHost));
-  FILE* f = fopen(file, "a");
+  FILE* f = fopen(stamp_file(), "a");
   if (!f) return;
   fprintf(f, "# %s %zu\n", name.c_str(), nwg);
   for (size_t i = 0; i < nwg; ++i)
@@ -1712,84 +1414,13 @@ static void dump_stamps(const char* file, const std::string& name, size_t nwg, h
   fclose(f);
 }
 
-bool C2fLayer::supported(const C2fShape& s, int h, int w) {
-  CfgInfo ci;
-  if (!cfg_info(s, ci)) return false;
-  if (h % ci.th != 0 || w % ci.tw != 0) return false;
-  if (ci.perimg && (h != ci.th || w != ci.tw)) return false;
-  if (s.UP && (h % 2 || w % 2)) return false;
-  return ci.lds <= 160 * 1024;
-}
-
-void C2fLayer::build(const C2fShape& s, int h, int w, const Src& src) {
-  LP_CHECK(supported(s, h, w), LP_ERR_STATE, "c2f: unsupported shape");
-  sh = s; H = h; W = w;
-  CfgInfo ci;
-  LP_CHECK(cfg_info(s, ci), LP_ERR_STATE, "c2f: no configuration for this shape");
-  lds_bytes = ci.lds;
-  const int C = s.C;
-  const int K1 = s.KA + s.KB;
-  if (s.MODE != -1) {   // (MODE -1: cv1 belongs to the launch in front)
-    pack_1x1(d_w[C2F_W_CV1], *src.cv1, 2 * C, K1, ci.nt1);
-    put_bias(d_b[C2F_W_CV1], src.cv1_b, 2 * C);
-  }
-  const int ntm = ci.ntm;
-  for (int k = 0; k < s.NB; ++k) {
-    pack_3x3(d_w[C2F_W_A0 + 2 * k], *src.a[k], C, C, ntm);
-    put_bias(d_b[C2F_W_A0 + 2 * k], src.a_b[k], C);
-    pack_3x3(d_w[C2F_W_B0 + 2 * k], *src.bb[k], C, C, ntm);
-    put_bias(d_b[C2F_W_B0 + 2 * k], src.bb_b[k], C);
-  }
-  const int nt2 = ci.nt2;
-  const int K2 = (2 + s.NB) * C;
-  pack_1x1(d_w[C2F_W_CV2], *src.cv2, s.COUT, K2, nt2);
-  put_bias(d_b[C2F_W_CV2], src.cv2_b, s.COUT);
-  macs_per_image = ((s.MODE != -1 ? (double)2 * C * K1 : 0.0) + (double)s.NB * 2 * 9 * C * C + (double)s.COUT * K2) * h * w;
-  if (s.MODE >= 1) {
-    pack_3x3(d_w[C2F_W_S2], *src.s2, 2 * C, s.KS2, ci.nt_s2);   // NT_S2: every row tile in one wave
-    put_bias(d_b[C2F_W_S2], src.s2_b, 2 * C);
-    macs_per_image += 9.0 * s.KS2 * 2 * C * h * w;
-  }
-  if (s.MODE == 2) {
-    pack_1x1(d_w[C2F_W_SP1], *src.sp1, C, s.COUT, ntm);
-    put_bias(d_b[C2F_W_SP1], src.sp1_b, C);
-    pack_1x1(d_w[C2F_W_SP2], *src.sp2, s.COUT, 4 * C, nt2);
-    put_bias(d_b[C2F_W_SP2], src.sp2_b, s.COUT);
-    macs_per_image += ((double)C * s.COUT + (double)s.COUT * 4 * C) * h * w;
-  }
-}
-
-// ---- the stride-2 launches: every instantiated configuration in one place, as for_each_cfg.  The key of an entry is
-//      (CIN, COUT, TAIL) of the type itself; supported, build and launch are lookups, so a shape cannot be in one and not in another.
-namespace {
-template <class F> bool for_each_s2cfg(F&& f) {
-  return f.template operator()<S2L24x48>() || f.template operator()<S2L48x96k2>() || f.template operator()<S2L48x48k2>() ||
-         f.template operator()<S2L64x128>() || f.template operator()<S2L96x192>() || f.template operator()<S2L96x96>() ||
-         f.template operator()<S2L16x32t>() || f.template operator()<S2L24x48t>() || f.template operator()<S2Cfg32x64>();
-}
-// lds_staged: s2lds_kernel (input tile in LDS, general K order in KSPLIT passes); else s2conv_kernel (gather, cin % 32 == 0 order)
-struct S2Info { int th, tw, nt, ksplit, S; size_t lds; bool lds_staged; };
-struct S2InfoFn {
-  int cin, cout; bool tail; S2Info& si;
-  template <class CFG> bool operator()() const {
-    static_assert(!CFG::LDS_STAGED || CFG::S == steps_3x3_general(CFG::CIN, CFG::KSPLIT), "the kernel's K steps per pass are those of k_3x3_general");
-    if (cin != CFG::CIN || cout != CFG::COUT || tail != CFG::TAIL) return false;
-    si = S2Info{CFG::TH, CFG::TW, CFG::NT, CFG::KSPLIT, CFG::S, (size_t)CFG::LDS_BYTES, CFG::LDS_STAGED};
-    return true;
-  }
-};
-bool s2_info(int cin, int cout, bool tail, S2Info& si) { return for_each_s2cfg(S2InfoFn{cin, cout, tail, si}); }
-bool s2_fits(int cin, int cout, bool tail, int hout, int wout) {
-  S2Info si;
-  return s2_info(cin, cout, tail, si) && hout % si.th == 0 && wout % si.tw == 0;
-}
 struct S2LaunchFn {
-  const S2ConvLayer& l; C2fArgs& a; hipStream_t st; const char* stamp_file;
+  const S2ConvLayer& l; C2fArgs& a; hipStream_t st;
   template <class CFG> bool operator()() const {
     if (l.Cin != CFG::CIN || l.Cout != CFG::COUT || l.has_tail != CFG::TAIL) return false;
     a.tiles_x = l.W / CFG::TW; a.tiles_y = l.H / CFG::TH;
     const size_t nwg = (size_t)a.N * a.tiles_x * a.tiles_y * CFG::OSPLIT;
-    if (stamp_file && !CFG::LDS_STAGED) a.stamps = stamp_buffer(nwg);   // (the gather kernel alone writes stamps)
+    if (stamp_file() && !CFG::LDS_STAGED) a.stamps = stamp_buffer(nwg);   // (the gather kernel alone writes stamps)
     if constexpr (CFG::LDS_STAGED) {
       set_max_dynamic_lds(reinterpret_cast<const void*>(&s2lds_kernel<CFG>), CFG::LDS_BYTES);
       LP_LAUNCH(s2lds_kernel<CFG>, dim3((unsigned)nwg), dim3(CFG::NW * 64), CFG::LDS_BYTES, st, a);
@@ -1798,19 +1429,24 @@ struct S2LaunchFn {
       LP_LAUNCH(s2conv_kernel<CFG>, dim3((unsigned)nwg), dim3(CFG::NW * 64), CFG::LDS_BYTES, st, a);
     }
     LP_HIP(hipGetLastError());
-    if (a.stamps) dump_stamps(stamp_file, l.name, nwg, st);
+    if (a.stamps) dump_stamps(l.name, nwg, st);
     return true;
   }
 };
+
 }  // namespace
 
-bool S2ConvLayer::supported(int cin, int cout, int hout, int wout) { return s2_fits(cin, cout, false, hout, wout); }
-bool S2ConvLayer::tail_supported(int cin, int cout, int cout2, int hout, int wout) { return cout2 == cout && s2_fits(cin, cout, true, hout, wout); }
-bool S2ConvLayer::lds_staged(int cin, int cout) {
-  S2Info si;
-  return s2_info(cin, cout, false, si) && si.lds_staged;
+void C2fLayer::build(const C2fShape& s, int h, int w, const Src& src) {
+  LP_CHECK(supported(s, h, w), LP_ERR_STATE, "c2f: unsupported shape");
+  sh = s; H = h; W = w;
+  const C2fPack p = pack_c2f(s, h, w, src);
+  lds_bytes = p.lds_bytes;
+  macs_per_image = p.macs_per_image;
+  for (int i = 0; i < C2F_NW; ++i) {
+    upload(d_w[i], p.w[i]);
+    upload(d_b[i], p.b[i]);
+  }
 }
-std::string S2ConvLayer::kernel_name() const { return fmt(has_tail ? "s2conv+1x1<%d,%d>" : "s2conv<%d,%d>", Cin, Cout); }
 
 void S2ConvLayer::build(int cin, int cout, int hout, int wout, const std::vector<float>& w_taps, const std::vector<float>& bias,
                         const std::vector<float>* w_tail, const std::vector<float>* b_tail) {
@@ -1818,19 +1454,11 @@ void S2ConvLayer::build(int cin, int cout, int hout, int wout, const std::vector
            "s2conv: unsupported shape %d -> %d @%dx%d", cin, cout, hout, wout);
   Cin = cin; Cout = cout; H = hout; W = wout;
   has_tail = w_tail != nullptr;
-  S2Info si;
-  LP_CHECK(s2_info(cin, cout, has_tail, si), LP_ERR_STATE, "s2conv: no configuration for %d -> %d", cin, cout);
-  // the entry's NT channel tiles per block and K steps.  LDS-staged: the general order in its KSPLIT passes (Cin 96: two passes of 48
-  // input channels, the second pass's steps behind the first's); the gather kernel: whole 32-channel blocks per tap
-  if (si.lds_staged) pack_phase(d_w, w_taps, cout, 9 * cin, si.nt, si.ksplit * si.S, k_3x3_general(cin, si.ksplit));
-  else pack_phase(d_w, w_taps, cout, 9 * cin, si.nt, si.S, k_3x3_c32(cin));
-  put_bias(d_b, &bias, cout);
-  if (has_tail) {   // the tail's K groups follow the lanes' channel ownership: lane group g holds channels 4 NT g .. 4 NT (g + 1) - 1 of
-                    // its pixel, eight per K step (S2LCfg::TSTEPS; NT = 3: the second step's upper half is zero)
-    const int own = 4 * si.nt;
-    pack_phase(d_w2, *w_tail, cout, cout, si.nt, (own + 7) / 8, [own](int s, int g, int j) { return 8 * s + j < own ? own * g + 8 * s + j : -1; });
-    put_bias(d_b2, b_tail, cout);
-  }
+  const S2Pack p = pack_s2(cin, cout, w_taps, bias, w_tail, b_tail);
+  upload(d_w, p.w);
+  upload(d_b, p.b);
+  upload(d_w2, p.w2);
+  upload(d_b2, p.b2);
 }
 
 void S2ConvLayer::launch(const View& in, const View& out, int N, hipStream_t st) const {
@@ -1845,28 +1473,20 @@ void S2ConvLayer::launch(const View& in, const View& out, int N, hipStream_t st)
   a.w[C2F_W_S2] = d_w.p; a.b[C2F_W_S2] = d_b.as<float>();
   a.N = N; a.H = H; a.W = W;
   if (has_tail) { a.w[C2F_W_CV1] = d_w2.p; a.b[C2F_W_CV1] = d_b2.as<float>(); }
-  static const char* stamp_file = getenv("LITEPI_C2F_STAMPS");
-  const bool ok = for_each_s2cfg(S2LaunchFn{*this, a, st, stamp_file});
+  const bool ok = for_each_s2cfg(S2LaunchFn{*this, a, st});
   LP_CHECK(ok, LP_ERR_STATE, "s2conv %s: no kernel for this shape", name.c_str());
 }
-
-// ---- SPPF: one instantiated configuration.  supported / build / launch read this type only
-typedef SpCfgV2 SppfCfg;
-
-bool SppfLayer::supported(int cin, int c, int cout, int h, int w) {
-  return cin == SppfCfg::CIN && c == SppfCfg::C && cout == SppfCfg::COUT && h == SppfCfg::TH && w == SppfCfg::TW;
-}
-std::string SppfLayer::kernel_name() const { return fmt("sppf<%d,%d,%d>", Cin, C, Cout); }
 
 void SppfLayer::build(int cin, int c, int cout, int h, int w, const std::vector<float>& w1, const std::vector<float>& b1,
                       const std::vector<float>& w2, const std::vector<float>& b2) {
   LP_CHECK(supported(cin, c, cout, h, w), LP_ERR_STATE, "sppf: unsupported shape %d -> %d -> %d @%dx%d", cin, c, cout, h, w);
   Cin = cin; C = c; Cout = cout; H = h; W = w;
-  pack_1x1(d_w1, w1, c, cin, SppfCfg::NT1);
-  put_bias(d_b1, &b1, c);
-  pack_1x1(d_w2, w2, cout, 4 * c, SppfCfg::NT2);
-  put_bias(d_b2, &b2, cout);
-  macs_per_image = ((double)c * cin + (double)cout * 4 * c) * h * w;
+  const SppfPack p = pack_sppf(cin, c, cout, h, w, w1, b1, w2, b2);
+  macs_per_image = p.macs_per_image;
+  upload(d_w1, p.w1);
+  upload(d_b1, p.b1);
+  upload(d_w2, p.w2);
+  upload(d_b2, p.b2);
 }
 
 void SppfLayer::launch(const View& in, const View& out, int N, hipStream_t st) const {
@@ -1884,16 +1504,6 @@ void SppfLayer::launch(const View& in, const View& out, int N, hipStream_t st) c
   set_max_dynamic_lds(reinterpret_cast<const void*>(&sppf_kernel<CFG>), CFG::LDS_BYTES);
   LP_LAUNCH(sppf_kernel<CFG>, dim3(N * CFG::OSPLIT), dim3(CFG::NW * 64), CFG::LDS_BYTES, st, a);
   LP_HIP(hipGetLastError());
-}
-
-bool C2fLayer::cv2_from_lds() const {
-  CfgInfo ci;
-  return cfg_info(sh, ci) && ci.cv2_lds;
-}
-
-std::string C2fLayer::kernel_name(const C2fShape& s) {
-  CfgInfo ci;
-  return cfg_info(s, ci) ? ci.name : "";
 }
 
 void C2fLayer::launch(const IO& io, int N, hipStream_t st) const {
@@ -1924,19 +1534,19 @@ void C2fLayer::launch(const IO& io, int N, hipStream_t st) const {
     a.out2 = io.out2.base; a.out2_pitch = io.out2.pitch;
   }
   a.N = N; a.H = H; a.W = W;
-  CfgInfo ci;
-  LP_CHECK(cfg_info(sh, ci), LP_ERR_STATE, "c2f %s: no configuration for this shape", name.c_str());
-  a.tiles_x = W / ci.tw; a.tiles_y = H / ci.th;
+  const C2fRow* row = find_c2f(sh);
+  LP_CHECK(row, LP_ERR_STATE, "c2f %s: no configuration for this shape", name.c_str());
+  a.tiles_x = W / row->tw; a.tiles_y = H / row->th;
   // store_all: bisect aid, every y segment goes to the concat buffer.  The layer's own flag, set by the planner from the switch it
   // read at load: a per-process read here could disagree with the blobs that load marked as stored
   static const int dbg_flags = getenv("LITEPI_C2F_DEBUG") ? atoi(getenv("LITEPI_C2F_DEBUG")) : 0;   // see Ctx::dbg
   a.debug_store = (store_all ? 1 : 0) | (dbg_flags & ~1);
-  static const char* stamp_file = getenv("LITEPI_C2F_STAMPS");
-  if (stamp_file) a.stamps = stamp_buffer((size_t)N * a.tiles_x * a.tiles_y);
+  const size_t nwg = (size_t)N * a.tiles_x * a.tiles_y;
+  if (stamp_file()) a.stamps = stamp_buffer(nwg);
   const bool ok = for_each_cfg(LaunchFn{sh, a, st});
   LP_CHECK(ok, LP_ERR_STATE, "c2f %s: no kernel for this shape", name.c_str());
   LP_HIP(hipGetLastError());
-  if (stamp_file) dump_stamps(stamp_file, name, (size_t)N * a.tiles_x * a.tiles_y, st);
+  if (a.stamps) dump_stamps(name, nwg, st);
 }
 
 }  // namespace lp
