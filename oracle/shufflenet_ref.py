@@ -137,24 +137,23 @@ def logp_module(model: nn.Module, x: np.ndarray, dtype=torch.float64) -> np.ndar
 
 # One fp16 rounding recipe per GPU path of the fp16 classifier.  Everything not listed stays float64.
 #   w16      pointwise (1x1 conv, conv5, fc) weights rounded to fp16: cls_net.hip / cls_fused.hip read them from
-#            pack_fused_pw (cls_fused.hip:352-366), the layer-at-a-time MFMA and naive kernels from ConvLayer::build
-#            (conv_kernels.hip:1825-1857, put_elem).  Depthwise weights and every bias stay fp32 (upload_f32,
-#            classifier.cpp:116; add_dw, classifier.cpp:44-53): not rounded.
+#            pack_fused_pw (cls_plan.h), the layer-at-a-time MFMA and naive kernels from ConvLayer::build
+#            (conv_kernels.hip, put_elem).  Depthwise weights and every bias stay fp32 (upload_f32, add_dw,
+#            classifier.cpp): not rounded.
 #   acts     every stored activation rounded: stem output, depthwise outputs, pointwise outputs (both shuffle halves).
-#            cls_net.hip: store_relu :85, dwconv :133, stage2.0/3.0/4.0 shuffle stores :433 :475-476 :612-613, s1_block
-#            :256 (the maxpool :391 and the x_lo copy :255 move stored fp16 values: nothing new to round); the 8 KB
-#            hand-off cls_front -> cls_back (:485) copies the fp16 LDS image X3, already rounded.  Layer-at-a-time:
-#            cls_stem_kernel (cls_kernels.hip:60), dwconv3x3_kernel (:226), conv_naive_kernel (conv_kernels.hip:1203,
-#            1211), the MFMA pointwise epilogues, shuffle_stage_kernel (cls_fused.hip:111, :140, :164).
-#   stem     "u8": cls_net.hip's MFMA stem (:323-373) multiplies the uint8 bytes by fp16(w / 255 / 0.34) and adds
-#            bias - 0.18 / 0.34 * (sum of the weights of the taps inside the image) in fp32 (pack_cls_stem, cls_net.hip:746-774);
-#            "f32": cls_stem_kernel (cls_kernels.hip:51-54): fp32 weights on the fp32-normalised input, nothing rounded
+#            cls_dev.h: store_relu; cls_net.hip: dwconv, the stage2.0/3.0/4.0 shuffle stores, s1_block (the maxpool and
+#            the x_lo copy move stored fp16 values: nothing new to round); the 8 KB hand-off cls_front -> cls_back
+#            copies the fp16 LDS image X3, already rounded.  Layer-at-a-time: cls_stem_kernel, dwconv3x3_kernel
+#            (cls_kernels.hip), conv_naive_kernel (conv_kernels.hip), the MFMA pointwise epilogues,
+#            shuffle_stage_kernel (cls_fused.hip).
+#   stem     "u8": cls_net.hip's MFMA stem multiplies the uint8 bytes by fp16(w / 255 / 0.34) and adds
+#            bias - 0.18 / 0.34 * (sum of the weights of the taps inside the image) in fp32 (pack_cls_stem, cls_plan.h);
+#            "f32": cls_stem_kernel (cls_kernels.hip): fp32 weights on the fp32-normalised input, nothing rounded
 #            but its output.
-#   conv5    "mean": conv5 + ReLU in fp32, averaged in fp32, only the mean rounded (cls_net.hip:654-657,
-#            cls_fused.hip:272-275); "store": conv5's ReLU output stored as fp16 (ConvLayer epilogue, classifier.cpp:438),
-#            then spatial_mean_kernel averages the rounded values and rounds the mean (cls_kernels.hip:257-264,
-#            classifier.cpp:440).
-#   Logits and softmax are fp32 on every path (out_f32, classifier.cpp:444; LG, cls_net.hip:683): not rounded.
+#   conv5    "mean": conv5 + ReLU in fp32, averaged in fp32, only the mean rounded (conv5_mean_store, cls_dev.h, in
+#            cls_back and cls_head_fused); "store": conv5's ReLU output stored as fp16 (ConvLayer epilogue), then
+#            spatial_mean_kernel averages the rounded values and rounds the mean (cls_kernels.hip).
+#   Logits and softmax are fp32 on every path (out_f32 of the fc ConvLayer; LG in cls_back / cls_head_fused): not rounded.
 RECIPES = {
     # A: default fp16 path, cls_front + cls_back (cls_net.hip)
     "fused": dict(w16=True, acts=True, stem="u8", conv5="mean"),
@@ -166,7 +165,7 @@ RECIPES = {
 
 
 def fold_bn(sd, conv: str, bn: str) -> Tuple[torch.Tensor, torch.Tensor]:
-    """conv (no bias) + BatchNorm(eval, eps 1e-5) -> (weight, bias) in float64, as classifier.cpp:65-85."""
+    """conv (no bias) + BatchNorm(eval, eps 1e-5) -> (weight, bias) in float64, as fold() of csrc/cls_plan.h."""
     w = sd[conv + ".weight"].double()
     s = sd[bn + ".weight"].double() / torch.sqrt(sd[bn + ".running_var"].double() + 1e-5)
     return w * s.view(-1, 1, 1, 1), sd[bn + ".bias"].double() - sd[bn + ".running_mean"].double() * s

@@ -1,5 +1,4 @@
-"""Shared inputs of the classifier tests (tests/test_gpu_classifier.py, tests/test_classifier_cpu.py and the child process
-tests/cls_layerwise_child.py): the 64-ROI pool, the seeded index sequences of the ROI-count cases, the tie-making weights,
+"""Shared inputs of the classifier tests (tests/test_gpu_classifier.py and tests/test_classifier_cpu.py): the 64-ROI pool, the seeded index sequences of the ROI-count cases, the tie-making weights,
 and one runner that executes a list of classify calls on one handle.  Not a test module (no test_ prefix)."""
 from __future__ import annotations
 
@@ -19,8 +18,8 @@ TIE_PAIRS = [(3, 40), (5, 69)]   # different lanes of the softmax wave / the sam
 
 
 def _gen_rois(rng, n):
-    """The generator of tests/test_gpu_parity.py::_rois (seeded noise crops 10..89 px a side), restated so that CPU tests and
-    the child process need not import a GPU test module."""
+    """The generator of tests/test_gpu_parity.py::_rois (seeded noise crops 10..89 px a side), restated so that CPU tests
+    need not import a GPU test module."""
     out = []
     for _ in range(n):
         h, w = int(rng.integers(10, 90)), int(rng.integers(10, 90))
@@ -76,17 +75,24 @@ def tie_state_dict(sd, pair, ref_logp: np.ndarray):
     return out
 
 
-def run_job(job: dict, rois: Sequence[np.ndarray]) -> dict:
+def run_job(job: dict, rois: Sequence[np.ndarray], monkeypatch=None) -> dict:
     """One handle: Engine(precision, max_batch=1, max_det=max_rois=cap), load job['sd'], then one classify call per entry of
     job['calls'] (pool indices; an entry longer than cap is classified in chunks of cap).  The first call is profiled.  A
-    LitepiError at load or at any call ends the job: its text is returned under 'error'."""
+    LitepiError at load or at any call ends the job: its text is returned under 'error'.  job['load_env'] (optional) is set in
+    the environment around load_classifier alone, through pytest's monkeypatch."""
     from litepi import Engine, _ffi
     cap = job["cap"]
     res = {"ids": [], "probs": [], "names": [], "error": ""}
     e = Engine(precision=job["prec"], max_batch=1, max_det=cap, num_classes=job["nc"], max_rois=cap,
                conv_impl=job.get("impl", 0), cls_arch=job.get("arch", "shufflenetv2"))
     try:
-        e.load_classifier(job["sd"])
+        if job.get("load_env"):
+            with monkeypatch.context() as m:
+                for k, v in job["load_env"].items():
+                    m.setenv(k, v)
+                e.load_classifier(job["sd"])
+        else:
+            e.load_classifier(job["sd"])
         for n, call in enumerate(job["calls"]):
             ids, probs = [], []
             for c0 in range(0, len(call), cap):

@@ -11,17 +11,13 @@ p_ref the float64 module (oracle/shufflenet_ref.py).  Bounds:
 
 Paths, each proved by the kernel names the profiler saw on its first call:
   A fp16 default (cls_front_f16 + cls_back_f16)       B fp16 LITEPI_CLS_LAYERWISE=1 (shuffle_stage_fused_f16,
-  C fp16 conv_impl=1 (conv_naive_f16)                   cls_head_fused_f16; child process, tests/cls_layerwise_child.py)
+  C fp16 conv_impl=1 (conv_naive_f16)                   cls_head_fused_f16; the switch is read once per load_classifier)
   D fp32 conv_impl=0 (conv1x1_mfma_f32)               E fp32 conv_impl=1 (conv_naive_f32)
 
 Within one handle no kernel reduces across ROIs, so a ROI's probabilities and id must be bit-equal whatever batch it sits
 in: the ROI-count cases (grid-stride passes past 1024 ROIs included) and the pipeline's scatter into detection records are
 checked that way."""
 import functools
-import os
-import pickle
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -31,8 +27,6 @@ import classifier_pool as CP
 from oracle import shufflenet_ref as S
 
 pytestmark = pytest.mark.gpu
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
 
 # path: (precision, conv_impl, emulation recipe (None: fp32), kernel names that must have run)
 PATHS = {
@@ -85,7 +79,7 @@ def _np_sd(sd):
 def _job(path, nc, cap, calls, sd=None, arch="shufflenetv2"):
     prec, impl = PATHS[path][:2]
     return dict(prec=prec, impl=impl, nc=nc, cap=cap, calls=[np.asarray(c, np.int64) for c in calls],
-                sd=_np_sd(_sd(nc) if sd is None else sd), arch=arch)
+                sd=_np_sd(_sd(nc) if sd is None else sd), arch=arch, load_env=LAYERWISE_ENV if path == "B" else {})
 
 
 def _count_calls(cap, R):
@@ -95,10 +89,12 @@ def _count_calls(cap, R):
     return [np.arange(64), idx] + [idx[k:k + 1] for k in ks], idx, ks
 
 
-def _run(path, job):
-    if path == "B":
-        raise AssertionError("path B runs in the child process (fixture layerwise)")
-    return CP.run_job(job, _pool())
+LAYERWISE_ENV = {"LITEPI_CLS_LAYERWISE": "1"}   # set around load_classifier only: Classifier::load reads it once per load
+
+
+def _run(path, job, monkeypatch=None):
+    assert bool(job["load_env"]) == (path == "B")
+    return CP.run_job(job, _pool(), monkeypatch)
 
 
 def _check_names(path, res):
@@ -224,59 +220,66 @@ B_JOBS = {
 }
 
 
-@pytest.fixture(scope="module")
-def layerwise(tmp_path_factory):
-    """Every path-B job in ONE child process with LITEPI_CLS_LAYERWISE=1 (a function-level static of classifier.cpp: only a
-    fresh process sees it).  A non-zero exit fails with the child's stderr."""
-    d = tmp_path_factory.mktemp("layerwise")
-    names, jobs = list(B_JOBS), []
-    for name in names:
-        nc, cap, pair, calls = B_JOBS[name]
-        sd = CP.tie_state_dict(_sd(nc), pair, _ref(nc)) if pair else None
-        jobs.append(_job("B", nc, cap, calls, sd=sd))
-    with open(d / "jobs.pkl", "wb") as f:
-        pickle.dump({"rois": _pool(), "jobs": jobs}, f)
-    env = dict(os.environ, LITEPI_CLS_LAYERWISE="1")
-    p = subprocess.run([sys.executable, os.path.join(_HERE, "cls_layerwise_child.py"), str(d / "jobs.pkl"), str(d / "out.npz")],
-                       env=env, capture_output=True, text=True, timeout=300)
-    if p.returncode != 0:
-        pytest.fail(f"layer-at-a-time child exited with {p.returncode}:\n{p.stderr[-4000:]}")
-    out = {}
-    with np.load(d / "out.npz") as z:
-        for j, name in enumerate(names):
-            n = len(jobs[j]["calls"])
-            out[name] = dict(ids=[z[f"j{j}_ids{k}"] for k in range(n) if f"j{j}_ids{k}" in z.files],
-                             probs=[z[f"j{j}_probs{k}"] for k in range(n) if f"j{j}_probs{k}" in z.files],
-                             names=[str(s) for s in z[f"j{j}_names"]], error=str(z[f"j{j}_error"]))
-    return out
+def _run_b(name, monkeypatch):
+    nc, cap, pair, calls = B_JOBS[name]
+    sd = CP.tie_state_dict(_sd(nc), pair, _ref(nc)) if pair else None
+    return _run("B", _job("B", nc, cap, calls, sd=sd), monkeypatch)
 
 
 @pytest.mark.parametrize("nc", [91, 256])
-def test_layerwise_pool_vs_float64(layerwise, nc):
-    res = layerwise[f"pool-{nc}"]
+def test_layerwise_pool_vs_float64(monkeypatch, nc):
+    res = _run_b(f"pool-{nc}", monkeypatch)
     _check_names("B", res)
     _check_vs_ref(f"path B {nc} classes", res["probs"][0], res["ids"][0], _ref(nc), _bound(nc, "B"))
 
 
-def test_layerwise_too_many_classes_refused(layerwise):
+def test_layerwise_too_many_classes_refused(monkeypatch):
     """cls_head_fused accepts nc_p <= 256: 257 classes must be refused, never answered."""
-    res = layerwise["refuse-257"]
+    res = _run_b("refuse-257", monkeypatch)
     print(f"CLS path B 257 classes: {res['error']!r}")
     assert res["error"] and not res["probs"]
 
 
 @pytest.mark.parametrize("pair", CP.TIE_PAIRS, ids=lambda p: f"{p[0]}-{p[1]}")
-def test_layerwise_argmax_ties(layerwise, pair):
-    res = layerwise[f"tie-{pair[0]}-{pair[1]}"]
+def test_layerwise_argmax_ties(monkeypatch, pair):
+    res = _run_b(f"tie-{pair[0]}-{pair[1]}", monkeypatch)
     _check_names("B", res)
     _check_ties("path B", res, pair)
 
 
 @pytest.mark.parametrize("cap,R", CP.OTHER_CASES, ids=[f"{c}-{r}" for c, r in CP.OTHER_CASES])
-def test_layerwise_roi_count_invariance(layerwise, cap, R):
-    res = layerwise[f"count-{cap}-{R}"]
+def test_layerwise_roi_count_invariance(monkeypatch, cap, R):
+    res = _run_b(f"count-{cap}-{R}", monkeypatch)
     _check_names("B", res)
     _check_counts("path B", res, cap, R, _ref(91), _bound(91, "B"))
+
+
+def test_plan_is_chosen_per_load(monkeypatch):
+    """Two handles in one process (capacity 64, 91 classes), the first loaded with LITEPI_CLS_LAYERWISE set and the second
+    without, called alternately twice each on the pool: each handle's profiler names are its own plan's (PATHS) on every call, and
+    its second result is bit-equal to its first."""
+    from litepi import Engine
+    sd, rois = _np_sd(_sd(91)), _pool()
+    engines, got = {}, {"B": [], "A": []}
+    try:
+        for path in "BA":
+            engines[path] = Engine(precision="fp16", max_batch=1, max_det=64, num_classes=91, max_rois=64, conv_impl=0, cls_arch="shufflenetv2")
+            with monkeypatch.context() as m:
+                m.delenv("LITEPI_CLS_LAYERWISE", raising=False)
+                if path == "B":
+                    m.setenv("LITEPI_CLS_LAYERWISE", "1")
+                engines[path].load_classifier(sd)
+        for _ in range(2):
+            for path, e in engines.items():
+                e.profile_next(True)
+                ids, probs = e.classify(rois)
+                _check_names(path, dict(error="", names=sorted({k["name"] for k in e.profile_read()})))
+                got[path].append((ids, probs))
+    finally:
+        for e in engines.values():
+            e.close()
+    for path, ((ids0, p0), (ids1, p1)) in got.items():
+        assert p0.shape == (64, 91) and (ids0 == ids1).all() and _bits_equal(p0, p1).all(), f"path {path}: the second call differs from the first"
 
 
 # ------------------------------------------------------------------------------------- routing through the pipeline

@@ -6,11 +6,9 @@
 #include "common.h"
 #include "kernels.h"
 
-namespace lp {
+#include "cls_dev.h"   // vector types, the softmax / arg-max tail
 
-typedef _Float16 half_t;
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
+namespace lp {
 
 template <typename T> struct VecT;
 template <> struct VecT<half_t> { typedef half8 type; static constexpr int G = 8; };
@@ -429,8 +427,7 @@ void launch_mb_eltwise(int prec, const View& x, const View* scale, float cap, co
 }
 
 // ------------------------------------------------------------------------------------
-// softmax(dim=1) + argmax (e2e.py:394-396), one wavefront per ROI (classes strided over lanes,
-// wave-level max / sum / arg-max reductions)
+// softmax(dim=1) + argmax (e2e.py:394-396), one wavefront per ROI: the tail of cls_dev.h on logits in global memory
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void softmax_argmax_kernel(const float* __restrict__ logits, int pitch, int nc,
                                                              float* __restrict__ probs, int* __restrict__ ids,
@@ -441,34 +438,7 @@ __global__ __launch_bounds__(256) void softmax_argmax_kernel(const float* __rest
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = (gridDim.x * 256) >> 6;
   for (int r = wave; r < R; r += nwaves) {
-    const float* l = logits + (long)r * pitch;
-    float mx = -INFINITY;
-    for (int c = lane; c < nc; c += 64) mx = fmaxf(mx, l[c]);
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    float sum = 0.f;
-    for (int c = lane; c < nc; c += 64) sum += expf(l[c] - mx);
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    float best = -1.f;
-    int best_c = 0x7fffffff;
-    for (int c = lane; c < nc; c += 64) {
-      const float p = expf(l[c] - mx) / sum;
-      if (probs) probs[(long)r * nc + c] = p;
-      if (p > best) { best = p; best_c = c; }  // first maximum within the lane (ascending c)
-    }
-    for (int o = 32; o > 0; o >>= 1) {  // first maximum across lanes: larger p, then smaller class index
-      const float ob = __shfl_xor(best, o);
-      const int oc = __shfl_xor(best_c, o);
-      if (ob > best || (ob == best && oc < best_c)) { best = ob; best_c = oc; }
-    }
-    if (lane == 0) {
-      if (ids) ids[r] = best_c;
-      if (conf) conf[r] = best;
-      if (dets) {
-        lp_det* d = dets + (long)roi_img[r] * max_det + roi_slot[r];
-        d->cls_class = best_c;
-        d->cls_conf = best;
-      }
-    }
+    cls_tail_row(logits + (long)r * pitch, nc, r, lane, probs, ids, conf, dets, max_det, roi_img, roi_slot);
   }
 }
 

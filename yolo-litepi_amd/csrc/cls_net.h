@@ -46,18 +46,10 @@ struct ClsBackArgs {
   const float* b5;       // [1024]
   const u32x4_t* wfc;    // fc A fragments [nc_p/16][32][64]
   const float* bfc;      // [nc_p]
-  float* probs;          // optional [R, nc]
-  int* ids;              // optional [R]
-  float* logits;         // optional [R, logits_pitch]
-  lp_det* dets;          // optional: scatter (class, confidence) through the ROI table
-  const int* roi_img;
-  const int* roi_slot;
-  int max_det, nc, nc_p, logits_pitch;
+  ClsOut out;            // nc_p <= 560 (clsplan::cls_back_supports)
 };
 
 void launch_cls_front(const ClsFrontArgs& a, int max_items, hipStream_t st);
 void launch_cls_back(const ClsBackArgs& a, int max_items, hipStream_t st);
-// conv1 for the MFMA stem: w [24][3][3][3] (torch layout, BN folded), bias [24] -> fragments + the four bias cases
-void pack_cls_stem(const std::vector<float>& w_oihw, const std::vector<float>& bias, std::vector<uint16_t>& frags, std::vector<float>& bias_cases);
 
 }  // namespace lp

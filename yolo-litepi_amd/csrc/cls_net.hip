@@ -18,77 +18,17 @@
 // 24-channel images of cls_front have 48-byte rows, three slots as they are.
 #include "cls_net.h"
 
-namespace lp {
+#include "cls_dev.h"   // vector types, wload / gemm_acc / store_relu / shuffle_phys, conv5 epilogue, fc tile, softmax tail
 
-typedef _Float16 half_t;
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+namespace lp {
 
 #define CN_THREADS 512
 #define CN_WAVES 8
 
-// ShuffleNetV2 x1.0 geometry (checked on the host against the state_dict)
-#define BF2 58
-#define BFP2 64
-#define BF3 116
-#define BFP3 128
-#define BF4 232
-#define BFP4 240
-
-// ---- small device helpers -----------------------------------------------------------------------------------------
-template <int SMAX>
-__device__ __forceinline__ void wload(u32x4 (&af)[SMAX], const u32x4_t* __restrict__ w, int t, int S, int lane) {
-#pragma unroll
-  for (int s = 0; s < SMAX; ++s) {
-    af[s] = u32x4{0u, 0u, 0u, 0u};
-    if (s < S) af[s] = w[((size_t)t * S + s) * 64 + lane];
-  }
-}
-
-// acc[p] (+)= W(tile) . X[pixels p0 + 16p .. +15]: K steps s0 .. s0+SMAX-1 of the fragments in af; Kp = physical
-// channels of the LDS rows (K groups past it are row padding / the next row: never read)
-template <int SMAX, int PT>
-__device__ __forceinline__ void gemm_acc(const u32x4 (&af)[SMAX], int S, int s0, const char* bsrc, int brow, int Kp, int p0, int lane,
-                                         floatx4 (&acc)[PT]) {
-  const int g = lane >> 4, col = lane & 15;
-#pragma unroll
-  for (int s = 0; s < SMAX; ++s) {
-    if (s < S) {
-      const half8 a = __builtin_bit_cast(half8, af[s]);
-      const int kg = 4 * (s0 + s) + g;
-#pragma unroll
-      for (int p = 0; p < PT; ++p) {
-        u32x4 v = u32x4{0u, 0u, 0u, 0u};
-        if (kg * 8 < Kp) v = *reinterpret_cast<const u32x4*>(bsrc + (p0 + p * 16 + col) * brow + kg * 16);
-        acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, __builtin_bit_cast(half8, v), acc[p], 0, 0, 0);
-      }
-    }
-  }
-}
-
-template <int PT> __device__ __forceinline__ void zero_acc(floatx4 (&acc)[PT]) {
-#pragma unroll
-  for (int p = 0; p < PT; ++p) acc[p] = floatx4{0.f, 0.f, 0.f, 0.f};
-}
-
-// relu(acc + bias) of tile t -> fp16 LDS image dst[pixel][channel]
-template <int PT>
-__device__ __forceinline__ void store_relu(char* dst, int drow, int p0, int t, const float* __restrict__ bias, const floatx4 (&acc)[PT],
-                                           int lane) {
-  const int g = lane >> 4, col = lane & 15;
-  const int ch0 = t * 16 + 4 * g;
-  const floatx4 b = *reinterpret_cast<const floatx4*>(bias + ch0);
-#pragma unroll
-  for (int p = 0; p < PT; ++p) {
-    half4 q;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) q[i] = (half_t)fmaxf(acc[p][i] + b[i], 0.f);
-    *reinterpret_cast<half4*>(dst + (p0 + p * 16 + col) * drow + ch0 * 2) = q;
-  }
-}
+// logical / padded channels of one half of the stage 2, 3, 4 tensors
+constexpr int BF2 = clsplan::half_c(0), BFP2 = clsplan::half_cp(0);
+constexpr int BF3 = clsplan::half_c(1), BFP3 = clsplan::half_cp(1);
+constexpr int BF4 = clsplan::half_c(2), BFP4 = clsplan::half_cp(2);
 
 // depthwise 3x3 (pad 1, stride STRIDE) + bias over C physical channels of nroi stacked WIN x WIN maps (fp32 accumulate,
 // weights fp32 [9][C] straight from L1/L2: 288 B per item, shared by every workgroup)
@@ -137,9 +77,6 @@ __device__ __forceinline__ void dwconv(const char* in, int irow, char* out, int 
     *reinterpret_cast<half8*>(out + px * orow + cg * 16) = o;
   }
 }
-
-// channel_shuffle(cat(a, b), 2): logical channel 2c = a[c], 2c+1 = b[c]; each half of the stage tensor is padded to bfp
-__device__ __forceinline__ int shuffle_phys(int l, int bf, int bfp) { return l < bf ? l : bfp + (l - bf); }
 
 // pointwise biases of a stage's stride-1 blocks -> LDS [NB][2][BFP] (b1 | b2), once per stage: read from global where they
 // are used (right behind a GEMM) each was an exposed L2 round trip, two per block.  The caller's next barrier publishes them.
@@ -300,6 +237,12 @@ static_assert(CF_IN + 12288 + 16 <= CF_R0SZ && 256 * CF_POOLROW <= CF_R0SZ && CF
 static_assert(256 * CF_T1ROW + 64 * CF_POOLROW <= CF_R1SZ && CF_SB + CF_S3SET <= CF_R1 + CF_R1SZ, "cls_front R1");
 static_assert(32 * 32 * 48 <= CF_R1SZ + 17408, "STEM must fit R1 + R2");
 static_assert(CF_LDS + CF_DW + CF_BI + CF_S2 <= 81920, "cls_front: two workgroups per CU need <= 80 KB of LDS each");
+static_assert(CF_POOLROW == clsplan::stage_in_cp(0) * 2 && CF_T1ROW == BFP2 * 2 + 16 && CF_X2ROW == clsplan::stage_cp(0) * 2 + 16 &&
+              CF_X3ROW == clsplan::stage_cp(1) * 2 + 16, "cls_front: LDS rows against the network's widths");
+static_assert(CF_DW == 10 * BFP2 * 4 && CF_BI == (clsplan::kStageRepeats[0] - 1) * 2 * BFP2 * 4 && CF_S2 == (10 * clsplan::stage_in_cp(0) + 10 * BFP2) * 4 &&
+              CF_S3SET == 10 * BFP3 * 4 && clsplan::stage_in_cp(1) == BFP3, "cls_front: staged parameters against the network's widths");
+static_assert(clsplan::kInput * clsplan::kInput * 3 == 12288 && clsplan::kStemSide == 32 && clsplan::kPoolSide == 16 && clsplan::stage_side(0) == 8 &&
+              clsplan::stage_side(1) == 4, "cls_front: map sides");
 
 __global__ __launch_bounds__(CN_THREADS, 4) void cls_front_kernel(const ClsFrontArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -551,7 +494,11 @@ __global__ __launch_bounds__(CN_THREADS, 4) void cls_front_kernel(const ClsFront
 #define CB_T3ROW 272   /* 128 ch x 2 + 16 */
 #define CB_T4ROW 496   /* 240 ch x 2 + 16 */
 #define CB_X4ROW 976   /* 480 ch x 2 + 16 */
-#define CB_MROW 2064   /* 1024 ch x 2 + 16 */
+static_assert(CB_RB == 64 * CF_X3ROW && CB_T3ROW == BFP3 * 2 + 16 && CB_T4ROW == BFP4 * 2 + 16 && CB_X4ROW == clsplan::stage_cp(2) * 2 + 16 &&
+              CB_X4 - CB_RC == clsplan::kBackRC && clsplan::stage_side(2) == 2, "cls_back: LDS layout against the network's widths");
+static_assert(CB_DW == 10 * BFP4 * 4 && CB_BI3 == (clsplan::kStageRepeats[1] - 1) * 2 * BFP3 * 4 &&
+              CB_BI == CB_BI3 + (clsplan::kStageRepeats[2] - 1) * 2 * BFP4 * 4 && CB_S2 == (10 * clsplan::stage_in_cp(2) + 10 * BFP4) * 4,
+              "cls_back: staged parameters against the network's widths");
 
 __global__ __launch_bounds__(CN_THREADS) void cls_back_kernel(const ClsBackArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -673,7 +620,7 @@ __global__ __launch_bounds__(CN_THREADS) void cls_back_kernel(const ClsBackArgs 
 
     // ================= conv5 1x1 (464 -> 1024) + ReLU, mean over the 2x2 map =================
     char* Mn = RC;                                              // [4 ROIs][1024] fp16
-    float* LG = reinterpret_cast<float*>(RC + 4 * CB_MROW);     // [4][nc_p] fp32 logits
+    float* LG = reinterpret_cast<float*>(RC + 4 * clsplan::kMeanRow);     // [4][nc_p] fp32 logits
     {
       // 64 output tiles, 8 per wave; K = 480 physical channels = 15 steps in two chunks; the next tile's first chunk is
       // requested before this tile's MFMAs
@@ -690,78 +637,15 @@ __global__ __launch_bounds__(CN_THREADS) void cls_back_kernel(const ClsBackArgs 
         gemm_acc<8, 1>(fa, 8, 0, X4, CB_X4ROW, 480, 0, lane, acc);
         if (tq + 1 < 8) wload<8>(fa, a.w5 + (size_t)(t + 1) * 15 * 64, 0, 8, lane);
         gemm_acc<8, 1>(fb, 7, 8, X4, CB_X4ROW, 480, 0, lane, acc);
-        const int ch0 = t * 16 + 4 * g;
-        const floatx4 bias = *reinterpret_cast<const floatx4*>(a.b5 + ch0);
-        half4 q;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float v = fmaxf(acc[0][i] + bias[i], 0.f);
-          v += __shfl_xor(v, 1);   // pixels 4r..4r+3 of ROI r sit on 4 adjacent lanes
-          v += __shfl_xor(v, 2);
-          q[i] = (half_t)(v * 0.25f);
-        }
-        if ((col & 3) == 0) *reinterpret_cast<half4*>(Mn + (col >> 2) * CB_MROW + ch0 * 2) = q;
+        conv5_mean_store<4>(Mn, t, a.b5, acc, lane);
       }
     }
     __syncthreads();
     // ================= fc: logits[roi][class] = Wfc . mean + b =================
-    {
-      const int Tfc = a.nc_p >> 4;
-      for (int t = wave; t < Tfc; t += CN_WAVES) {
-        floatx4 acc = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-        for (int s0 = 0; s0 < 32; s0 += 8) {
-          u32x4 af[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) af[u] = a.wfc[((size_t)t * 32 + s0 + u) * 64 + lane];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            u32x4 v = u32x4{0u, 0u, 0u, 0u};
-            if (col < 4) v = *reinterpret_cast<const u32x4*>(Mn + col * CB_MROW + (4 * (s0 + u) + g) * 16);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, af[u]), __builtin_bit_cast(half8, v), acc, 0, 0, 0);
-          }
-        }
-        const int c0 = t * 16 + 4 * g;
-        if (col < 4) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) LG[col * a.nc_p + c0 + i] = acc[i] + a.bfc[c0 + i];
-        }
-      }
-    }
+    for (int t = wave; t < (a.out.nc_p >> 4); t += CN_WAVES) fc_tile<4>(LG, Mn, a.wfc, a.bfc, a.out.nc_p, t, lane);
     __syncthreads();
-    // ================= softmax + arg-max (e2e.py:394-396), one wave per ROI; scatter into the detection records =====
-    if (wave < nroi) {
-      const int r = roi0 + wave;
-      const float* l = LG + wave * a.nc_p;
-      float mx = -INFINITY;
-      for (int c = lane; c < a.nc; c += 64) mx = fmaxf(mx, l[c]);
-      for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-      float sum = 0.f;
-      for (int c = lane; c < a.nc; c += 64) sum += expf(l[c] - mx);
-      for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-      float best = -1.f;
-      int best_c = 0x7fffffff;
-      for (int c = lane; c < a.nc; c += 64) {
-        const float pr = expf(l[c] - mx) / sum;
-        if (a.probs) a.probs[(long)r * a.nc + c] = pr;
-        if (pr > best) { best = pr; best_c = c; }
-      }
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o);
-        const int oc = __shfl_xor(best_c, o);
-        if (ob > best || (ob == best && oc < best_c)) { best = ob; best_c = oc; }
-      }
-      if (lane == 0) {
-        if (a.ids) a.ids[r] = best_c;
-        if (a.dets) {
-          lp_det* d = a.dets + (long)a.roi_img[r] * a.max_det + a.roi_slot[r];
-          d->cls_class = best_c;
-          d->cls_conf = best;
-        }
-      }
-      if (a.logits)
-        for (int c = lane; c < a.nc; c += 64) a.logits[(long)r * a.logits_pitch + c] = l[c];
-    }
+    // ================= softmax + arg-max, one wave per ROI; scatter into the detection records =====
+    if (wave < nroi) cls_tail(LG + wave * a.out.nc_p, roi0 + wave, lane, a.out);
     __syncthreads();
   }
 }
@@ -775,46 +659,14 @@ void launch_cls_front(const ClsFrontArgs& a, int max_items, hipStream_t st) {
 }
 
 void launch_cls_back(const ClsBackArgs& a, int max_items, hipStream_t st) {
-  LP_CHECK(a.nc_p % 16 == 0 && a.nc_p <= 1024 && (size_t)4 * CB_MROW + (size_t)4 * a.nc_p * 4 <= 17408, LP_ERR_STATE,
-           "fused classifier: %d classes do not fit the logits buffer", a.nc);
+  LP_CHECK(clsplan::cls_back_supports(a.out.nc) && a.out.nc_p == clsplan::class_pad(a.out.nc), LP_ERR_STATE,
+           "fused classifier: %d classes do not fit the logits buffer", a.out.nc);
   set_max_dynamic_lds(reinterpret_cast<const void*>(cls_back_kernel), 160 * 1024);
   int grid = (max_items + 3) / 4;
   if (grid > 256) grid = 256;
   if (grid < 1) grid = 1;
   LP_LAUNCH(cls_back_kernel, dim3(grid), dim3(CN_THREADS), CB_LDS + CB_DW + CB_BI + CB_S2, st, a);
   LP_HIP(hipGetLastError());
-}
-
-// conv1 (+BN) for the MFMA stem.  K index of lane group g, element j: g < 3: window row ky = g, byte j = kx*3 + c (j < 8);
-// g = 3: j < 3: the 9th byte (kx = 2, c = 2) of window row ky = j; rest zero.
-void pack_cls_stem(const std::vector<float>& w, const std::vector<float>& bias, std::vector<uint16_t>& frags, std::vector<float>& bias_cases) {
-  const double scale = 1.0 / 255.0 / 0.34, shift = 0.18 / 0.34;
-  frags.assign((size_t)2 * 64 * 8, 0);
-  for (int t = 0; t < 2; ++t)
-    for (int lane = 0; lane < 64; ++lane) {
-      const int gq = lane >> 4, m = lane & 15, co = t * 16 + m;
-      if (co >= 24) continue;
-      for (int j = 0; j < 8; ++j) {
-        int ky, kb;
-        if (gq < 3) { ky = gq; kb = j; }
-        else if (j < 3) { ky = j; kb = 8; }
-        else continue;
-        const int kx = kb / 3, c = kb % 3;
-        frags[((size_t)t * 64 + lane) * 8 + j] = f32_to_f16((float)((double)w[(((size_t)co * 3 + c) * 3 + ky) * 3 + kx] * scale));
-      }
-    }
-  bias_cases.assign((size_t)4 * 32, 0.f);
-  for (int ci = 0; ci < 4; ++ci)
-    for (int co = 0; co < 24; ++co) {
-      double s = 0.0;
-      for (int ky = 0; ky < 3; ++ky)
-        for (int kx = 0; kx < 3; ++kx) {
-          if ((ci & 1) && ky == 0) continue;  // top row of the window is above the image
-          if ((ci & 2) && kx == 0) continue;  // left column is left of the image
-          for (int c = 0; c < 3; ++c) s += (double)w[(((size_t)co * 3 + c) * 3 + ky) * 3 + kx];
-        }
-      bias_cases[(size_t)ci * 32 + co] = (float)((double)bias[co] - shift * s);
-    }
 }
 
 }  // namespace lp
