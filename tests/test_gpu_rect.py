@@ -51,7 +51,7 @@ def test_conv3x3_residual_on_a_map_narrower_than_a_strip(hw):
 # ---------------------------------------------------------------------------- 2. letterbox
 LB_CASES = [((384, 640), (1080, 1920)), ((384, 640), (720, 1280)), ((384, 640), (480, 640)), ((384, 640), (37, 100)),
             ((384, 640), (384, 640)), ((640, 384), (640, 360)), ((640, 384), (1920, 1080)), ((224, 416), (1080, 1920)),
-            ((224, 416), (100, 4480))]
+            ((224, 416), (100, 4480)), ((384, 640), (50, 2600))]
 
 
 @pytest.fixture(scope="module")
@@ -79,7 +79,8 @@ def test_letterbox_kernels_equal_rect_ref(lb_engines, shape, hw):
     """Both kernels (the launcher's choice = the tiled one where its LDS rows fit, and the per-pixel one) byte-equal to
     rect_ref.letterbox; ratio and pads bit-equal to lp_letterbox_geometry.  100 x 4480 into 224 x 416 is a 10.8 x down-scale:
     a tile row spans 4179 source bytes, 16 rows of 4192 are 67072 > 65536 bytes, so the launcher itself takes the per-pixel
-    kernel there."""
+    kernel there.  50 x 2600 into 384 x 640 is a 4.06 x down-scale over five column tiles: staged, with the span's first byte
+    far beyond the LDS shift from the second tile on."""
     from litepi.backend import letterbox_geometry
     SH, SW = shape
     rng = np.random.default_rng(hw[0] * 7 + hw[1] + SH)

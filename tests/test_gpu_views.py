@@ -7,6 +7,7 @@ import torch
 
 import tiling_ref as T
 import views_ref as V
+from test_gpu_rect import tiled_rows_fit
 
 pytestmark = pytest.mark.gpu
 
@@ -85,7 +86,10 @@ GATHER = {
                  (0, 0, 517, 333), "full"],
     (70, 720): [(0, 0, 720, 70),                        # 11.25x down at 64: the source span exceeds the LDS rows -> per-pixel kernel
                 (5, 3, 64, 64), (0, 0, 96, 64), (700, 50, 20, 20), (1, 1, 40, 40), "full"],
+    (60, 1400): [(0, 0, 1400, 60),                      # 4.4x down at 320 (only): staged, three column tiles, so the span's first byte
+                 (3, 1, 1290, 58), "full"],             # lies far beyond the LDS shift; the second window's origin is odd
 }
+GATHER_CASES = [(shape, s) for s in (64, 320) for shape in GATHER if not (shape == (60, 1400) and s == 64)]
 
 
 @pytest.fixture(scope="module")
@@ -97,8 +101,7 @@ def gather_engines():
         e.close()
 
 
-@pytest.mark.parametrize("s", [64, 320])
-@pytest.mark.parametrize("shape", list(GATHER))
+@pytest.mark.parametrize("shape,s", GATHER_CASES, ids=[f"shape{list(GATHER).index(shape)}-{s}" for shape, s in GATHER_CASES])
 def test_window_gather_bytes_equal_numpy(gather_engines, shape, s):
     eng = gather_engines[s]
     rng = np.random.default_rng(shape[0] * 7 + s)
@@ -108,6 +111,8 @@ def test_window_gather_bytes_equal_numpy(gather_engines, shape, s):
     scales = [V.window(v, *shape)[2] / V.view_geometry(s, *shape, v)["new_w"] for v in views]
     if s == 64:
         assert max(scales) > 10 or shape != (70, 720), "the per-pixel fallback is not reached"
+    if shape == (60, 1400):   # the launcher's row rule, computed on the CPU: every window is staged, none falls back
+        assert min(scales) > 4 and all(tiled_rows_fit(V.view_geometry(s, *shape, v)["new_w"], V.window(v, *shape)[2]) for v in views)
     lists = [views] if max(scales) <= 10 else [views, [v for v, sc in zip(views, scales) if sc <= 10]]   # with / without the fallback
     for lst in lists:
         want = exp[[views.index(v) for v in lst]]

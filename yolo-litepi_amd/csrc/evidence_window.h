@@ -6,6 +6,8 @@
 #pragma once
 #include <math.h>
 
+#include "letterbox_core.h"
+
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define LP_EW_HD __host__ __device__
 #else
@@ -50,12 +52,12 @@ LP_EW_HD inline bool evidence_window(float scale, int H, int W, float x1, float 
   return true;
 }
 
-// letterbox of a h x w window into E x E: make_geom(h, w, E, E)'s new size and integer borders (round half to even)
-struct EvGeom { int new_w, new_h, top, left; };
-LP_EW_HD inline EvGeom evidence_geom(int h, int w, int E) {
+// letterbox of a h x w window into E x E: make_geom(h, w, E, E)'s new size and integer borders (round half to even), as
+// the placement the letterbox core resamples into
+LP_EW_HD inline LbPlace evidence_geom(int h, int w, int E) {
   const double rh = (double)E / h, rw = (double)E / w;
   const double r = rh < rw ? rh : rw;
-  EvGeom g;
+  LbPlace g;
   g.new_w = (int)rint(w * r); g.new_h = (int)rint(h * r);
   const double dw = (E - g.new_w) / 2.0, dh = (E - g.new_h) / 2.0;
   g.top = (int)rint(dh - 0.1); g.left = (int)rint(dw - 0.1);

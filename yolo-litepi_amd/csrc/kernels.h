@@ -2,6 +2,7 @@
 // cls_kernels.hip).  All launches are asynchronous on the given stream.
 #pragma once
 #include "common.h"
+#include "letterbox_core.h"
 #include "surface_plan.h"
 
 namespace lp {
@@ -17,7 +18,8 @@ struct ImgGeom {
 };
 
 // ---- misc_kernels.hip ------------------------------------------------------------------
-// letterbox (e2e.py:66-86): B images -> uint8 BGR [B,SH,SW,3], cv2.INTER_LINEAR fixed point, border 114
+// letterbox (e2e.py:66-86): B images -> uint8 BGR [B,SH,SW,3], cv2.INTER_LINEAR fixed point, border 114.  host_geoms (the B
+// geometries) sizes the tiled kernel's LDS rows (lb_row_cap); without them, or when the rows do not fit, the per-pixel kernel runs
 void launch_letterbox(const uint8_t* src, const ImgGeom* geom, uint8_t* dst, int B, int SH, int SW, hipStream_t st,
                       const ImgGeom* host_geoms = nullptr);
 // Interp nearest x2 (model.ncnn.param:88,103)
@@ -116,8 +118,12 @@ struct ViewWin {
   int top, left;       // integer border offsets
   int pad;
 };
+// what the letterbox core (letterbox_core.h) resamples: a whole image of the source buffer, the window of a view
+LP_LB_HD LbSource lb_source(const uint8_t* src, const ImgGeom& g) { return LbSource{src + g.src_off, (long)g.h * g.w * 3, 3 * g.w, 0, 0, g.w, g.h}; }
+LP_LB_HD LbSource lb_source(const uint8_t* src, const ViewWin& v) { return LbSource{src + v.src_off, v.frame_bytes, v.pitch, v.x, v.y, v.w, v.h}; }
+template <class Table> LP_LB_HD LbPlace lb_place(const Table& t) { return LbPlace{t.new_w, t.new_h, t.top, t.left}; }
 // window views slot0 .. slot0+n-1 of the view batch [V,S,S,3] from wins[0 .. n); host_wins (the same n entries) sizes the
-// LDS rows: when a source row span does not fit (down-scales beyond ~10x) the per-pixel kernel runs
+// LDS rows (lb_row_cap): when they do not fit (lb_rows_fit: down-scales beyond ~10x) the per-pixel kernel runs
 void launch_window_views(const uint8_t* src, const ViewWin* wins, uint8_t* dst, int slot0, int n, int S, hipStream_t st,
                          const ViewWin* host_wins);
 

@@ -567,10 +567,7 @@ __device__ __forceinline__ void rr_strip_linear(const RrUnit& u, char* smem) {
       if (u.in_w == RR_S && u.in_h == RR_S) {
         v = r0[sx * 3 + c];   // cv2.resize returns a copy when the size already matches
       } else {
-        const int h0 = r0[sx * 3 + c] * ax0 + r0[sx1 * 3 + c] * ax1;
-        const int h1 = r1[sx * 3 + c] * ax0 + r1[sx1 * 3 + c] * ax1;
-        v = (((ay0 * (h0 >> 4)) >> 16) + ((ay1 * (h1 >> 4)) >> 16) + 2) >> 2;
-        v = v < 0 ? 0 : (v > 255 ? 255 : v);
+        v = lin_blend(r0[sx * 3 + c], r0[sx1 * 3 + c], r1[sx * 3 + c], r1[sx1 * 3 + c], ax0, ax1, ay0, ay1);
       }
       o[2 - c] = (uint8_t)v;   // BGR -> RGB
     }

@@ -2,7 +2,7 @@
 // the frames, and the frame NMS that merges the candidates of all views of one frame into ONE per-class greedy NMS with the
 // reference's arithmetic (e2e.py:89-119).  The letterboxed whole-frame views are made by the letterbox kernel itself
 // (misc_kernels.hip), so they are bit-identical to lp_test_letterbox.  Scaled views add the window gather:
-// the letterbox of any window of a frame.
+// the letterbox of any window of a frame, a front end of the same core (letterbox_core.h).
 #include "common.h"
 #include "kernels.h"
 #include "nms_dev.h"
@@ -69,104 +69,18 @@ void launch_crop_views(const uint8_t* src, const ImgGeom* geom, uint8_t* dst, in
 }
 
 // ------------------------------------------------------------------------------------
-// Window views (lp_run_views*): dst[slot] = letterbox(frame[y:y+h, x:x+w]) at any scale, 114 in the bars.  The tiled letterbox
-// (misc_kernels.hip) with the row pitch and the window width apart: a workgroup owns an 8 x 128 tile of the view, stages the
-// two source rows of each of its output rows into LDS with aligned 16-byte loads over the byte span its columns read -- a
-// window starts at byte 3x of a frame row, so the runs are unaligned in general: the span is widened down to the 16-byte
-// boundary below it, by the address itself, and a chunk that is not wholly inside the frame is read byte by byte -- and
-// resamples four adjacent pixels per thread from LDS with lin_coeff's fixed-point arithmetic over the WINDOW's size, bit
-// for bit what letterbox_kernel computes on the window copied out contiguously.  new == window size: plain copy.
+// Window views (lp_run_views*): dst[slot] = letterbox(frame[y:y+h, x:x+w]) at any scale, 114 in the bars.  Front ends of the
+// letterbox core (letterbox_core.h) over the windows of the view table: the row pitch and the window width apart, a window
+// starts at byte 3x of a frame row, so the staged runs are unaligned in general.  Bit for bit what letterbox_kernel computes
+// on the window copied out contiguously.
 // ------------------------------------------------------------------------------------
-#define VW_TH 8
-#define VW_TW 128
 __global__ __launch_bounds__(256) void window_views_kernel(const uint8_t* __restrict__ src, const ViewWin* __restrict__ wins,
                                                            uint8_t* __restrict__ dst, int slot0, int S, int row_cap) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t band[];   // [2 * VW_TH][row_cap]
-  __shared__ int s_shift[2 * VW_TH];                                // byte index of window byte b0 inside an LDS row
-  const int n = blockIdx.z, tid = threadIdx.x;
-  const int ox0 = blockIdx.x * VW_TW, oy0 = blockIdx.y * VW_TH;
+  extern __shared__ __attribute__((aligned(16))) uint8_t band[];   // [2 * LB_TH][row_cap]
+  __shared__ int s_shift[2 * LB_TH];                                // byte index of window byte b0 inside an LDS row
+  const int n = blockIdx.z;
   const ViewWin vw = wins[n];
-  const uint8_t* im = src + vw.src_off;
-  const bool resize = !(vw.new_w == vw.w && vw.new_h == vw.h);
-  // columns of the resized window this tile covers, and the byte span [b0, b1) of a WINDOW row they read
-  const int dxa = max(ox0 - vw.left, 0), dxb = min(min(ox0 + VW_TW, S) - vw.left, vw.new_w);   // [dxa, dxb)
-  int b0 = 0, b1 = 0;
-  if (dxa < dxb) {
-    int sa, sb, t0, t1;
-    if (resize) { lin_coeff(dxa, vw.new_w, vw.w, sa, t0, t1); lin_coeff(dxb - 1, vw.new_w, vw.w, sb, t0, t1); }
-    else { sa = dxa; sb = dxb - 1; }
-    const int sb1 = sb + 1 < vw.w ? sb + 1 : vw.w - 1;
-    b0 = 3 * sa; b1 = 3 * (sb1 + 1);
-  }
-  // ---- stage: LDS row 2j / 2j+1 = window rows sy / sy1 of output row oy0 + j
-  if (dxa < dxb) {
-    for (int r = tid >> 4; r < 2 * VW_TH; r += 16) {   // 16 threads per row
-      const int dy = oy0 + (r >> 1) - vw.top;
-      if (dy < 0 || dy >= vw.new_h) continue;
-      int sy, ay0, ay1;
-      if (resize) lin_coeff(dy, vw.new_h, vw.h, sy, ay0, ay1); else sy = dy;
-      const int syr = (r & 1) ? (sy + 1 < vw.h ? sy + 1 : vw.h - 1) : sy;
-      const long goff = (long)(vw.y + syr) * vw.pitch + 3L * vw.x + b0;   // byte offset of the span inside the frame
-      const int shift = (int)(reinterpret_cast<uintptr_t>(im + goff) & 15);
-      const long gal = goff - shift;                                       // 16-byte aligned start, relative to the frame
-      if ((tid & 15) == 0) s_shift[r] = shift;
-      int nchunk = (shift + (b1 - b0) + 15) >> 4;
-      nchunk = min(nchunk, row_cap >> 4);   // (the launcher sized row_cap for the span: never cuts)
-      for (int c = tid & 15; c < nchunk; c += 16) {
-        const long o = gal + 16L * c;
-        u32x4 v;
-        if (o >= 0 && o + 16 <= vw.frame_bytes) {
-          v = *reinterpret_cast<const u32x4*>(im + o);
-        } else {   // the chunk passes the frame's first or last byte: byte by byte, nothing outside the frame is touched
-          uint8_t t[16];
-#pragma unroll
-          for (int k = 0; k < 16; ++k) t[k] = (o + k >= 0 && o + k < vw.frame_bytes) ? im[o + k] : (uint8_t)0;
-          v = *reinterpret_cast<const u32x4*>(t);
-        }
-        *reinterpret_cast<u32x4*>(band + (size_t)r * row_cap + 16 * c) = v;
-      }
-    }
-  }
-  __syncthreads();
-  // ---- resample: thread = (row j, four adjacent columns)
-  const int j = tid >> 5, ox = ox0 + 4 * (tid & 31), oy = oy0 + j;
-  if (oy >= S || ox >= S) return;
-  const int dy = oy - vw.top;
-  const bool rowin = dy >= 0 && dy < vw.new_h;
-  int ay0 = 2048, ay1 = 0;
-  if (rowin && resize) { int sy; lin_coeff(dy, vw.new_h, vw.h, sy, ay0, ay1); }
-  const uint8_t* r0 = band + (size_t)(2 * j) * row_cap + (rowin ? s_shift[2 * j] : 0) - b0;
-  const uint8_t* r1 = band + (size_t)(2 * j + 1) * row_cap + (rowin ? s_shift[2 * j + 1] : 0) - b0;
-  uint32_t out[3] = {0u, 0u, 0u};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int dx = ox + q - vw.left;
-    uint32_t px[3] = {114u, 114u, 114u};
-    if (rowin && dx >= 0 && dx < vw.new_w) {
-      if (resize) {
-        int sx, ax0, ax1;
-        lin_coeff(dx, vw.new_w, vw.w, sx, ax0, ax1);
-        const int sx1 = sx + 1 < vw.w ? sx + 1 : vw.w - 1;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const int h0 = r0[sx * 3 + c] * ax0 + r0[sx1 * 3 + c] * ax1;
-          const int h1 = r1[sx * 3 + c] * ax0 + r1[sx1 * 3 + c] * ax1;
-          int v = (((ay0 * (h0 >> 4)) >> 16) + ((ay1 * (h1 >> 4)) >> 16) + 2) >> 2;
-          px[c] = (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-        }
-      } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) px[c] = r0[dx * 3 + c];
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int b = 3 * q + c;
-      out[b >> 2] |= px[c] << (8 * (b & 3));
-    }
-  }
-  uint32_t* o = reinterpret_cast<uint32_t*>(dst + ((long)(slot0 + n) * S * S + (long)oy * S + ox) * 3);   // 12-byte groups: 4-byte aligned (S % 4 == 0)
-  o[0] = out[0]; o[1] = out[1]; o[2] = out[2];
+  lb_tile(lb_source(src, vw), lb_place(vw), dst + (long)(slot0 + n) * S * S * 3, S, S, band, row_cap, s_shift);
 }
 
 // per-pixel form, straight from global memory: the windows whose source row span exceeds the LDS rows
@@ -175,35 +89,8 @@ __global__ __launch_bounds__(256) void window_views_pixel_kernel(const uint8_t* 
   const int n = blockIdx.y;
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= S * S) return;
-  const int oy = idx / S, ox = idx - oy * S;
   const ViewWin vw = wins[n];
-  uint8_t* o = dst + ((long)(slot0 + n) * S * S + idx) * 3;
-  const int dy = oy - vw.top, dx = ox - vw.left;
-  if (dy < 0 || dy >= vw.new_h || dx < 0 || dx >= vw.new_w) {
-    o[0] = 114; o[1] = 114; o[2] = 114;
-    return;
-  }
-  const uint8_t* im = src + vw.src_off + (long)vw.y * vw.pitch + 3L * vw.x;   // the window's first byte
-  if (vw.new_w == vw.w && vw.new_h == vw.h) {
-    const uint8_t* p = im + (long)dy * vw.pitch + dx * 3;
-    o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
-    return;
-  }
-  int sx, ax0, ax1, sy, ay0, ay1;
-  lin_coeff(dx, vw.new_w, vw.w, sx, ax0, ax1);
-  lin_coeff(dy, vw.new_h, vw.h, sy, ay0, ay1);
-  const int sx1 = sx + 1 < vw.w ? sx + 1 : vw.w - 1;
-  const int sy1 = sy + 1 < vw.h ? sy + 1 : vw.h - 1;
-  const uint8_t* r0 = im + (long)sy * vw.pitch;
-  const uint8_t* r1 = im + (long)sy1 * vw.pitch;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int h0 = r0[sx * 3 + c] * ax0 + r0[sx1 * 3 + c] * ax1;
-    const int h1 = r1[sx * 3 + c] * ax0 + r1[sx1 * 3 + c] * ax1;
-    int v = (((ay0 * (h0 >> 4)) >> 16) + ((ay1 * (h1 >> 4)) >> 16) + 2) >> 2;
-    v = v < 0 ? 0 : (v > 255 ? 255 : v);
-    o[c] = (uint8_t)v;
-  }
+  lb_pixel_thread(lb_source(src, vw), lb_place(vw), dst + (long)(slot0 + n) * S * S * 3, S, idx);
 }
 
 void launch_window_views(const uint8_t* src, const ViewWin* wins, uint8_t* dst, int slot0, int n, int S, hipStream_t st,
@@ -211,15 +98,10 @@ void launch_window_views(const uint8_t* src, const ViewWin* wins, uint8_t* dst, 
   if (n <= 0) return;
   LP_CHECK(S % 4 == 0 && host_wins, LP_ERR_ARG, "window views need det_input %% 4 == 0");
   int cap = 0;
-  for (int i = 0; i < n; ++i) {   // launch_letterbox's rule, over the windows
-    const ViewWin& w = host_wins[i];
-    const double scale = (double)w.w / (double)std::max(w.new_w, 1);
-    const int span = (int)(((double)VW_TW * scale + 4.0) * 3.0) + 32;   // source bytes of a tile row + alignment slack
-    cap = std::max(cap, (span + 15) & ~15);
-  }
-  if ((size_t)cap * 2 * VW_TH <= 64 * 1024) {
-    dim3 grid(ceil_div(S, VW_TW), ceil_div(S, VW_TH), n);
-    LP_LAUNCH(window_views_kernel, grid, dim3(256), (size_t)cap * 2 * VW_TH, st, src, wins, dst, slot0, S, cap);
+  for (int i = 0; i < n; ++i) cap = std::max(cap, lb_row_cap(host_wins[i].w, host_wins[i].new_w, LB_TW));
+  if (lb_rows_fit(cap)) {
+    dim3 grid(ceil_div(S, LB_TW), ceil_div(S, LB_TH), n);
+    LP_LAUNCH(window_views_kernel, grid, dim3(256), (size_t)cap * 2 * LB_TH, st, src, wins, dst, slot0, S, cap);
   } else {
     dim3 grid(ceil_div(S * S, 256), n);
     LP_LAUNCH(window_views_pixel_kernel, grid, dim3(256), 0, st, src, wins, dst, slot0, S);
