@@ -512,6 +512,7 @@ int lp_tracker_snapshot(lp_handle* h, int stream, lp_track_state* out, int cap, 
  *     update  quality.  Every sighted entry takes last_frame = t, hits, voted_class, voted_conf and vote_weight from the
  *             lp_track record, and missed = 0.  Quality q in fp32, each operation rounded on its own:
  *               LP_BEST_AREA (x2 - x1) * (y2 - y1); LP_BEST_DET_CONF det_conf; LP_BEST_CLS_CONF cls_class >= 0 ? cls_conf : -1.0f
+ *             (under LP_RANK_SHARPNESS, lp_inventory_set_rank below: q = the sharpness of the record's lp_quality instead)
  *             A later sighting replaces the best iff q > best_quality (ties keep the earlier sighting; a NaN never replaces).
  *             Replacing copies the box, det_class, best_frame = t, best_quality = q and, with crops = 1 and a crop for that
  *             record, the crop; LP_SIGN_HAS_CROP is set or cleared for that sighting
@@ -772,6 +773,73 @@ int lp_track_topk(lp_handle* h, const lp_det* dets, const int* counts, const lp_
  * (img[r], slot[r]) with total = classified = R, runs clear + select for B frames and downloads B * max_det records.
  * LP_ERR_ARG for R > max_rois or an img / slot out of range. */
 int lp_test_topk(lp_handle* h, const float* probs, int R, const int* img, const int* slot, int B, lp_topk* out);
+
+/* ---- crop quality: sharpness and exposure per detection, and an inventory rank (additive to ABI 310) ---- */
+/* The ROI resize leaves every ROI as an S x S x 3 uint8 RGB crop (S = cls_input): the bytes the classifier reads and the
+ * inventory's gallery copies.  With quality switched on, every pipeline call also measures those crops and leaves one
+ * lp_quality record per detection in a handle-owned device buffer of max_batch * max_det records, parallel to lp_det: record
+ * i of frame b describes dets[b*max_det+i] (for the tiled, views and focus families b indexes frames, not views, as the ROI
+ * list does).
+ * The rule, for one crop c[S][S][3] in R, G, B order, integers until the last step:
+ *   luma       Y(y,x) = (77*R + 150*G + 29*B + 128) >> 8, in 0..255
+ *   Laplacian  on the (S-2)^2 interior pixels: L(y,x) = Y(y-1,x) + Y(y+1,x) + Y(y,x-1) + Y(y,x+1) - 4*Y(y,x), in -1020..1020
+ *   sums       n = (S-2)^2, s1 = sum L, s2 = sum L^2 (int64);  N = S^2, t1 = sum Y, t2 = sum Y^2, lo = #{Y <= 4}, hi = #{Y >= 251}
+ *   record     in fp64, every operation rounded on its own, each result converted to fp32:
+ *                sharpness = (double)(n*s2 - s1*s1) / ((double)n*(double)n)      the variance of the Laplacian
+ *                luma_mean = (double)t1 / (double)N
+ *                luma_var  = (double)(N*t2 - t1*t1) / ((double)N*(double)N)
+ *                clip_lo   = (double)lo / (double)N,  clip_hi = (double)hi / (double)N
+ * The integer products are exact in int64 for every S <= 1024 (n*s2 and s1*s1 stay below 2^60, N*t2 and t1*t1 below 2^56).
+ * Every reduction is over integers, so the result does not depend on the order of summation: the device record equals
+ * lp_quality_measure of the same crop bit for bit.  The rule is one header for host and device (csrc/quality_measure.h).
+ * A pipeline call over B frames (lp_run_batch*, lp_run_tiled*, lp_run_views*, lp_run_focus*, lp_run_surfaces_device,
+ * lp_run_views_surfaces_device) writes all B * max_det records of its frames, in the same captured step, and leaves the
+ * records of frames >= B alone: every ROI among the first `classified` ROIs of the ROI list (lp_roi_overflow) gets its
+ * measure at (roi_img[r], roi_slot[r]) with LP_QUALITY_VALID; every other record is EMPTY (sharpness = -1, the other fields
+ * 0, flags = 0): records beyond the kept count, records a user-set max_rois left without a crop, the whole call when no
+ * classifier is loaded (no ROI list exists then).  The buffer holds the last pipeline call's records, like the ROI list.
+ * lp_detect, lp_detect_raw and lp_classify neither read nor write it.  In the host entry points the work is booked in
+ * t_classification.
+ * How it runs: a plain clear launch over the B * max_det records, then the measure launch: one workgroup per ROI, the crop
+ * read once with 16-byte loads, its luma plane held in LDS, integer reductions per wave and across waves, one thread writes
+ * the record.  The live ROI count is read on the device: no host synchronisation.  While off (the default) nothing changes:
+ * no launch, buffer or device branch is added; a handle switched on and off again runs the launches it ran before.
+ * DESIGN.md 6o. */
+typedef struct lp_quality {       /* 32 bytes, parallel to lp_det */
+  float sharpness;                /* variance of the Laplacian of the crop's luma; -1 for an empty record */
+  float luma_mean, luma_var;      /* 0..255, 0..16256.25 */
+  float clip_lo, clip_hi;         /* share of pixels with Y <= 4 / Y >= 251 */
+  int32_t flags;                  /* LP_QUALITY_VALID 1 */
+  int32_t reserved[2];            /* zero */
+} lp_quality;
+#define LP_QUALITY_VALID 1
+
+/* on = 1 switches quality on, 0 off (the default); anything else is LP_ERR_ARG.  The buffer is allocated at the first enable,
+ * cleared to the empty record, and stable until lp_destroy.  A change makes the run families capture their steps anew; a call
+ * that changes nothing does nothing.  LP_ERR_STATE when cls_input is no multiple of 4 (the crops are then not 16-byte aligned,
+ * keep_crops' condition), and for on = 0 while the inventory ranks by sharpness (below). */
+int lp_quality_enable(lp_handle* h, int on);
+/* the buffer's device address; LP_ERR_STATE while off */
+int lp_quality_buffer(lp_handle* h, const void** dev_quality);
+/* synchronises; the first B * max_det records.  LP_ERR_STATE while off, LP_ERR_ARG for B outside 1..max_batch. */
+int lp_quality_read(lp_handle* h, lp_quality* out, int B);
+/* pure host, no handle, no device: the rule above on one crop rgb[S][S][3].  LP_ERR_ARG for NULL or S outside 3..1024. */
+int lp_quality_measure(const uint8_t* rgb, int S, lp_quality* out);
+/* What step 4 of the inventory's rule ranks a track's sightings by.  LP_RANK_CONFIG (the default, and what
+ * lp_inventory_create restores): lp_inventory_config::best, the rule as stated there.  LP_RANK_SHARPNESS: q is the sharpness
+ * field of record (b, idx) of the handle's quality buffer, read as is when the inventory call runs; an empty record gives
+ * q = -1, so a sighting without a crop never replaces a measured one, and the first sighting is still the best whatever its
+ * q.  Everything else in the rule is unchanged; lp_sign::best_quality carries the sharpness, and the evidence store follows
+ * the same choice.  The largest sighting of a sign on a moving camera is usually the last before it leaves the frame and the
+ * most blurred; this rank keeps the sharpest crop instead.
+ * LP_ERR_STATE without an inventory, or for LP_RANK_SHARPNESS with quality off; LP_ERR_ARG for an unknown rank.  While the rank
+ * is LP_RANK_SHARPNESS, lp_inventory_device / lp_inventory with crops = 0 are LP_ERR_ARG before anything is enqueued (the buffer
+ * describes the last pipeline call, which is what crops = 1 asserts), and lp_quality_enable(h, 0) is LP_ERR_STATE. */
+enum lp_rank { LP_RANK_CONFIG = 0, LP_RANK_SHARPNESS = 1 };
+int lp_inventory_set_rank(lp_handle* h, int rank);
+/* test hook (needs quality on): on the ROI list and crops lp_test_set_rois installed, runs clear + measure for B frames and
+ * downloads B * max_det records.  LP_ERR_ARG for B outside 1..max_batch. */
+int lp_test_quality(lp_handle* h, int B, lp_quality* out);
 
 /* ---- classifier alone ------------------------------------------------------------ */
 /* replaces PyTorchClassifier.predict_batch (e2e.py:378-396) for R host BGR crops of

@@ -2,7 +2,7 @@
 // point replaces).  The handle (handle.h) owns the device, the stream, all activation/result buffers and the two
 // model plans; every pipeline stage runs on the GPU -- there is no CPU fallback anywhere.
 // This file: errors and small host helpers, the handle's lifecycle, and the RCCL binding.  The pipeline entry points are in
-// pipeline.cpp, pixfmt.cpp, views.cpp, tracking.cpp, inventory.cpp and topk.cpp, the test hooks in test_hooks.cpp.
+// pipeline.cpp, pixfmt.cpp, views.cpp, tracking.cpp, inventory.cpp, topk.cpp and quality.cpp, the test hooks in test_hooks.cpp.
 #include <cstdlib>
 #include <dlfcn.h>
 #include <mutex>

@@ -1,5 +1,5 @@
 // Internal to the C-ABI translation units (api.cpp, pipeline.cpp, pixfmt.cpp, views.cpp, tracking.cpp, inventory.cpp, focus.cpp,
-// topk.cpp, test_hooks.cpp): the handle behind include/litepi.h's lp_handle, the captured-step cache, and the pipeline pieces the entry points share.
+// topk.cpp, quality.cpp, test_hooks.cpp): the handle behind include/litepi.h's lp_handle, the captured-step cache, and the pipeline pieces the entry points share.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -99,6 +99,7 @@ struct Inventory {
   std::unique_ptr<Evidence> evid;   // null until lp_evidence_create: no other path looks at it
   lp_inventory_config cfg;
   int min_hits = 0, crop_bytes = 0;
+  int rank = LP_RANK_CONFIG;        // lp_inventory_set_rank: LP_RANK_SHARPNESS reads the handle's lp_quality records in step 4
   DevBuf entries, frame_no, head, log, log_crops, gallery, roi_of;
   DevBuf d_dets, d_counts, d_tracks;   // lp_inventory (host records): allocated on first use
   PlanRing ring;                       // a slot: the tracker's plan (plan_stream_jobs)
@@ -218,6 +219,10 @@ struct lp_handle {
   // allocated at the first enable and kept until lp_destroy.  While k == 0 no path looks at either.
   int topk_k = 0;
   lp::DevBuf d_topk;
+  // crop quality per detection (lp_quality_enable): on / off and the [max_batch * max_det] lp_quality records, allocated at the
+  // first enable and kept until lp_destroy.  While off no path looks at either.
+  bool quality_on = false;
+  lp::DevBuf d_quality;
   // where the last pipeline call's BGR frames and their geometry are (host bookkeeping; the evidence store reads them behind
   // lp_inventory*(crops = 1)).  Whatever rewrites or reallocates d_src or d_geom (ensure_src, upload_geom: every entry point
   // that does so, lp_detect* and lp_classify included) forgets them first; the pipeline entry points remember their own
@@ -338,6 +343,11 @@ void enqueue_classify(lp_handle* h, const uint8_t* src, int B, lp_det* dets, flo
 // top-k on: clear the B * max_det records of the call's frames, then (classify: a classifier ran and left its probabilities in
 // d_probs) the select over the classified ROIs; two plain launches.  Never called while top-k is off.
 void enqueue_topk(lp_handle* h, int B, bool classify, Profiler* prof);
+// quality on: clear the B * max_det records of the call's frames, then (classify: a classifier is loaded, so the ROI stage
+// left its crops in d_roi_rgb) the measure over the classified ROIs; two plain launches.  Never called while quality is off.
+void enqueue_quality(lp_handle* h, int B, bool classify, Profiler* prof);
+// the measure launch's arguments for B frames on the handle's ROI list and crops (pipeline.cpp; lp_test_quality shares them)
+QualityArgs quality_args(lp_handle* h, int B);
 // eager the first time a key is seen, captured into a hipGraph the second time, replayed from then on
 void run_or_capture(lp_handle* h, const GraphKey& key, bool allow, const std::function<void()>& enqueue);
 

@@ -32,6 +32,7 @@ static InvArgs base_args(const lp_handle* h) {
   a.log_crops = v.log_crops.as<uint8_t>(); a.gallery = v.gallery.as<uint8_t>(); a.roi_of = v.roi_of.as<int>();
   a.max_rois = h->max_rois; a.max_det = t.max_det; a.T = t.cfg.max_tracks; a.max_age = t.cfg.max_age; a.min_hits = v.min_hits;
   a.best = v.cfg.best; a.max_signs = v.cfg.max_signs; a.crop_bytes = v.crop_bytes;
+  a.quality = v.rank == LP_RANK_SHARPNESS ? h->d_quality.as<lp_quality>() : nullptr;   // lp_inventory_set_rank
   return a;
 }
 
@@ -78,6 +79,8 @@ static void check_inventory_call(lp_handle* h, int B, const int* stream_ids, int
   check_stream_ids(t, B, stream_ids);
   LP_CHECK(crops == 0 || crops == 1, LP_ERR_ARG, "crops %d is not 0 or 1", crops);
   LP_CHECK(!crops || v.cfg.keep_crops, LP_ERR_ARG, "crops = 1 on an inventory created with keep_crops = 0");
+  LP_CHECK(crops || v.rank != LP_RANK_SHARPNESS, LP_ERR_ARG,
+           "crops = 0 under LP_RANK_SHARPNESS: the quality records describe the last pipeline call, which is what crops = 1 asserts");
   LP_CHECK(!crops || !v.evid || (h->last_frames && h->last_fgeom && h->last_nframes >= B), LP_ERR_STATE,
            "crops = 1 with an evidence store: the handle remembers %d frames of its last pipeline call, this call has %d", h->last_nframes, B);
 }

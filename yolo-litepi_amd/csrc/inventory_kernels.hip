@@ -177,7 +177,8 @@ __device__ __forceinline__ void inventory_stream(const InvArgs& a, const EvArgs&
         s_w[W_LAST][s] = t; s_w[W_HITS][s] = t0v.z; s_w[W_VCLS][s] = t1v.x; s_w[W_VCONF][s] = t1v.y; s_w[W_VW][s] = t1v.z;
         s_missed[s] = 0;
         float q;
-        if (a.best == LP_BEST_AREA)
+        if (a.quality) q = a.quality[(size_t)b * max_det + idx].sharpness;   // LP_RANK_SHARPNESS: the record as it is, -1 when empty
+        else if (a.best == LP_BEST_AREA)
           q = __fmul_rn(__fsub_rn(__int_as_float(d0.z), __int_as_float(d0.x)), __fsub_rn(__int_as_float(d0.w), __int_as_float(d0.y)));
         else if (a.best == LP_BEST_DET_CONF) q = __int_as_float(d1.x);
         else q = d1.z >= 0 ? __int_as_float(d1.w) : -1.0f;

@@ -224,6 +224,21 @@ void launch_topk_clear(lp_topk* out, int n_records, hipStream_t st);
 // one wave per classified ROI: its top-k at (roi_img[r], roi_slot[r]); a ROI naming a record outside [B, max_det) is skipped
 void launch_topk_select(const TopkArgs& a, hipStream_t st);
 
+// ---- quality_kernels.hip (sharpness and exposure of every classified detection's crop, include/litepi.h lp_quality) ----
+struct QualityArgs {
+  const uint8_t* roi_rgb;   // [max_rois][S][S][3] RGB crops as roi_resize left them
+  const int* total;         // RoiTable::total: the classified ROI count, read on the device
+  const int* roi_img;       // [max_rois]
+  const int* roi_slot;      // [max_rois]
+  lp_quality* out;          // [B * max_det]
+  int S, B, max_det;
+  int cap;                  // min(max_rois, B * max_det): bounds the ROI count and sizes the grid
+};
+// the empty record (sharpness = -1, everything else 0) into n_records records
+void launch_quality_clear(lp_quality* out, int n_records, hipStream_t st);
+// one workgroup per classified ROI: its measure at (roi_img[r], roi_slot[r]); a ROI naming a record outside [B, max_det) is skipped
+void launch_quality_measure(const QualityArgs& a, hipStream_t st);
+
 // ---- inventory_kernels.hip (one record + best crop per finished track, include/litepi.h lp_inventory_*) ----
 struct InvEntry {      // one slot of a stream's inventory, 80 bytes, device resident between calls
   lp_sign sign;        // as it would be logged (flags: LP_SIGN_HAS_CROP only)
@@ -250,6 +265,7 @@ struct InvArgs {
   int* roi_of;              // [max_batch * max_det]
   int max_rois, B;
   int max_det, T, max_age, min_hits, best, max_signs, crop_bytes;
+  const lp_quality* quality;   // [max_batch * max_det] or null: LP_RANK_SHARPNESS ranks a sighting by its record's sharpness instead of `best`
 };
 // the record -> ROI scatter (crops only), then one wave per job
 void launch_inventory(const InvArgs& a, int n_jobs, hipStream_t st);

@@ -143,6 +143,26 @@ void enqueue_topk(lp_handle* h, int B, bool classify, Profiler* prof) {
   if (prof) prof->end(h->stream, "topk_select", "topk", 0.0, (double)a.nc * 4 + sizeof(lp_topk), true);
 }
 
+QualityArgs quality_args(lp_handle* h, int B) {
+  RoiTable tab = h->roi_table();
+  QualityArgs a;
+  a.roi_rgb = h->d_roi_rgb.as<uint8_t>(); a.total = tab.total; a.roi_img = tab.img; a.roi_slot = tab.slot; a.out = h->d_quality.as<lp_quality>();
+  a.S = h->cfg.cls_input; a.B = B; a.max_det = h->cfg.max_det;
+  a.cap = std::min(h->max_rois, B * h->cfg.max_det);
+  return a;
+}
+
+void enqueue_quality(lp_handle* h, int B, bool classify, Profiler* prof) {
+  if (prof) prof->begin(h->stream);
+  launch_quality_clear(h->d_quality.as<lp_quality>(), B * h->cfg.max_det, h->stream);
+  if (prof) prof->end(h->stream, "quality_clear", "quality", 0.0, (double)B * h->cfg.max_det * sizeof(lp_quality));
+  if (!classify) return;
+  const QualityArgs a = quality_args(h, B);
+  if (prof) prof->begin(h->stream);
+  launch_quality_measure(a, h->stream);
+  if (prof) prof->end(h->stream, "quality_measure", "quality", 0.0, 3.0 * a.S * a.S + sizeof(lp_quality), true);
+}
+
 // Run `enqueue` (kernel launches on h->stream only: no allocation, no synchronisation) eagerly the first time a key is
 // seen -- that call also performs every one-time set-up (LDS attributes, lazy packing) --, capture it into a hipGraph the
 // second time, replay the graph from then on.
@@ -281,6 +301,7 @@ void run_device_pass(lp_handle* h, GraphKind kind, int B, float conf, float iou,
   if (before) before(prof);
   const bool classify = h->cls && h->cls->loaded();
   const bool topk = h->topk_k > 0;   // lp_topk_enable: the step also fills the handle's lp_topk records
+  const bool quality = h->quality_on;   // lp_quality_enable: and its lp_quality records
   lp_det* dets = static_cast<lp_det*>(dev_dets);
   h->remember_frames(frames.src, front.roi_geom ? front.roi_geom : h->d_geom.as<ImgGeom>(), B);
   GraphKey key = frames.key;
@@ -291,6 +312,7 @@ void run_device_pass(lp_handle* h, GraphKind kind, int B, float conf, float iou,
     front.run(prof, dets, static_cast<int*>(dev_counts), classify ? min_area : -1, classify);
     if (classify) enqueue_classify(h, frames.src, B, dets, topk ? h->d_probs.as<float>() : nullptr, nullptr, nullptr, prof, 0, front.roi_geom);
     if (topk) enqueue_topk(h, B, classify, prof);
+    if (quality) enqueue_quality(h, B, classify, prof);
   });
   if (prof) prof->enabled = false;  // records are collected by lp_profile_read after the caller synchronises
 }
@@ -319,6 +341,7 @@ void run_host_pass(lp_handle* h, int B, float conf, float iou, int min_area, lp_
   run_or_capture(h, k3, prof == nullptr, [&]() {
     enqueue_classify(h, src, B, d_dets, topk ? h->d_probs.as<float>() : nullptr, nullptr, nullptr, prof, 2, roi_geom);
     if (topk) enqueue_topk(h, B, true, prof);
+    if (h->quality_on) enqueue_quality(h, B, true, prof);   // lp_quality_enable: part of the classification piece too
   });
   LP_HIP(hipEventRecord(h->ev[3], h->stream));
   LP_HIP(hipMemcpyAsync(dets, h->d_dets.p, (size_t)B * h->cfg.max_det * sizeof(lp_det), hipMemcpyDeviceToHost, h->stream));

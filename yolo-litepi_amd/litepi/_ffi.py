@@ -135,6 +135,21 @@ class LpTopk(C.Structure):
 # numpy view of lp_topk records
 TOPK_DTYPE = [("cls", "<i4", (LP_TOPK_MAX,)), ("prob", "<f4", (LP_TOPK_MAX,))]
 
+LP_QUALITY_VALID = 1
+LP_RANK_CONFIG, LP_RANK_SHARPNESS = 0, 1
+
+
+class LpQuality(C.Structure):
+    """lp_quality, 32 bytes, parallel to lp_det: sharpness (variance of the Laplacian of the crop's luma) and exposure of a
+    detection's classifier crop; the empty record is sharpness = -1, everything else 0"""
+    _fields_ = [("sharpness", C.c_float), ("luma_mean", C.c_float), ("luma_var", C.c_float), ("clip_lo", C.c_float), ("clip_hi", C.c_float),
+                ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+# numpy view of lp_quality records
+QUALITY_DTYPE = [("sharpness", "<f4"), ("luma_mean", "<f4"), ("luma_var", "<f4"), ("clip_lo", "<f4"), ("clip_hi", "<f4"), ("flags", "<i4"),
+                 ("reserved", "<i4", (2,))]
+
 SYMBOLS = [
     "lp_last_error", "lp_version", "lp_default_config", "lp_create", "lp_destroy", "lp_load_detector_ncnn",
     "lp_load_classifier_tensors", "lp_detect_raw", "lp_detect", "lp_run_batch", "lp_run_batch_device", "lp_classify",
@@ -157,6 +172,7 @@ SYMBOLS = [
     "lp_view_merge_default", "lp_view_merge_check", "lp_set_view_merge",
     "lp_surfaces_check", "lp_run_surfaces_device", "lp_run_views_surfaces_device", "lp_test_convert_surfaces", "lp_graph_stats",
     "lp_topk_enable", "lp_topk_buffer", "lp_topk_read", "lp_topk_select", "lp_track_topk_device", "lp_track_topk", "lp_test_topk",
+    "lp_quality_enable", "lp_quality_buffer", "lp_quality_read", "lp_quality_measure", "lp_inventory_set_rank", "lp_test_quality",
 ]
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
 
@@ -290,6 +306,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_track_topk_device.argtypes = [vp, vp, vp, vp, C.c_int, ip, vp]
     lib.lp_track_topk.argtypes = [vp, vp, ip, vp, C.c_int, ip, vp]
     lib.lp_test_topk.argtypes = [vp, fp, C.c_int, ip, ip, C.c_int, vp]
+    lib.lp_quality_enable.argtypes = [vp, C.c_int]
+    lib.lp_quality_buffer.argtypes = [vp, C.POINTER(vp)]
+    lib.lp_quality_read.argtypes = [vp, vp, C.c_int]
+    lib.lp_quality_measure.argtypes = [vp, C.c_int, C.POINTER(LpQuality)]
+    lib.lp_inventory_set_rank.argtypes = [vp, C.c_int]
+    lib.lp_test_quality.argtypes = [vp, C.c_int, vp]
     for s in SYMBOLS:
         if s not in ("lp_last_error", "lp_default_config", "lp_destroy", "lp_track_default_config", "lp_inventory_default_config",
                      "lp_evidence_default_config", "lp_focus_default_config", "lp_view_merge_default"):

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _ffi
-from ._ffi import (DET_DTYPE, SIGN_DTYPE, TOPK_DTYPE, TRACK_DTYPE, TRACK_STATE_DTYPE, LpConfig, LpFrameFormat, LpInventoryConfig, LpKernelTime, LpTiming,
+from ._ffi import (DET_DTYPE, QUALITY_DTYPE, SIGN_DTYPE, TOPK_DTYPE, TRACK_DTYPE, TRACK_STATE_DTYPE, LpConfig, LpFrameFormat, LpInventoryConfig, LpKernelTime, LpTiming,
                    LpTiling, LpTrackConfig, check)
 from .pixfmt import CSC_MATRICES, PIXEL_FORMATS, nv12_frame_hw
 from .surfaces import Surface, surface_array, surface_format, surface_from_tensors, surfaces_check  # noqa: F401  (re-exported)
@@ -172,6 +172,36 @@ def check_topk_options(topk, track_vote: str, track: bool) -> int:
     if track_vote == "distribution" and not (track and k >= 1):
         raise ValueError("track_vote='distribution' needs track=True and topk >= 1 (--track_vote distribution needs --track and --topk K)")
     return k
+
+
+def quality_measure(crop) -> np.ndarray:
+    """lp_quality_measure (host only, no GPU needed): the crop quality rule on one [S, S, 3] uint8 RGB crop -> one QUALITY_DTYPE
+    record; LitepiError(LP_ERR_ARG) for S outside 3..1024.  ValueError for a crop that is not square with 3 channels."""
+    lib = _ffi.load_library()
+    a = np.ascontiguousarray(crop, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[0] != a.shape[1] or a.shape[2] != 3:
+        raise ValueError(f"a crop is [S, S, 3] uint8 RGB, got shape {a.shape}")
+    out = np.zeros(1, dtype=QUALITY_DTYPE)
+    check(lib, lib.lp_quality_measure(a.ctypes.data, a.shape[0], C.cast(out.ctypes.data, C.POINTER(_ffi.LpQuality))))
+    return out[0]
+
+
+INVENTORY_RANKS = {"config": _ffi.LP_RANK_CONFIG, "sharpness": _ffi.LP_RANK_SHARPNESS}
+QUALITY_RESULT_KEYS = ("sharpness", "luma_mean", "clip_lo", "clip_hi")
+
+
+def check_quality_options(quality, inventory):
+    """the rules HybridPipeline shares with the CLI for quality / inventory best="sharpness": returns (quality on, rank name,
+    the inventory settings without the rank).  "sharpness" is no lp_best: the settings keep the default `best`, the rank is set
+    on the created inventory (Engine.inventory_set_rank) and quality is switched on."""
+    inv = dict(inventory) if isinstance(inventory, dict) else {}
+    rank = "config"
+    if inv.get("best") == "sharpness":
+        del inv["best"]
+        rank = "sharpness"
+        if not int(inv.get("keep_crops", 1)):
+            raise ValueError("inventory best='sharpness' needs keep_crops: the sharpness is measured on the crops the inventory keeps")
+    return bool(quality) or rank == "sharpness", rank, inv
 
 
 INVENTORY_CONFIG_FIELDS = ("max_signs", "keep_crops", "best", "min_hits")
@@ -657,6 +687,42 @@ class Engine:
         check(self.lib, self.lib.lp_test_topk(self._h, p.ctypes.data_as(fp), len(p), i.ctypes.data_as(ip), s.ctypes.data_as(ip), int(B),
                                               out.ctypes.data))
         return out
+
+    # ---- crop quality: sharpness and exposure per detection ------------------------------------
+    def quality_enable(self, on: bool = True) -> None:
+        """lp_quality_enable: on = every pipeline call also leaves an lp_quality record (sharpness, luma mean and variance, clipped
+        shares) of every classified detection's crop in the engine's buffer (quality_read, quality_buffer); off is the default."""
+        check(self.lib, self.lib.lp_quality_enable(self._h, int(on)))
+        self.quality_on = bool(on)
+
+    def quality_buffer(self) -> int:
+        """device address of the [max_batch * max_det] lp_quality records; stable for the engine's life."""
+        p = C.c_void_p()
+        check(self.lib, self.lib.lp_quality_buffer(self._h, C.byref(p)))
+        return int(p.value or 0)
+
+    def quality_read(self, B: int) -> np.ndarray:
+        """lp_quality_read (synchronises): the last pipeline call's records of its first B frames, (B, max_det) QUALITY_DTYPE,
+        parallel to the lp_det records; a detection without a crop has the empty record (sharpness -1, flags 0)."""
+        out = np.zeros((max(int(B), 0), self.cfg.max_det), dtype=QUALITY_DTYPE)
+        check(self.lib, self.lib.lp_quality_read(self._h, out.ctypes.data, int(B)))
+        return out
+
+    def test_quality(self, B: int) -> np.ndarray:
+        """lp_test_quality: the ROI list and crops test_set_rois installed through the clear + measure launches for B frames ->
+        (B, max_det) QUALITY_DTYPE records.  Needs quality on."""
+        out = np.zeros((max(int(B), 0), self.cfg.max_det), dtype=QUALITY_DTYPE)
+        check(self.lib, self.lib.lp_test_quality(self._h, int(B), out.ctypes.data))
+        return out
+
+    def inventory_set_rank(self, rank) -> None:
+        """lp_inventory_set_rank: "config" (lp_inventory_config's best, the default) or "sharpness" (a track's best sighting is
+        its sharpest crop; needs quality on), or the enum value.  inventory_create restores "config"."""
+        if isinstance(rank, str):
+            if rank not in INVENTORY_RANKS:
+                raise ValueError(f"rank must be one of {tuple(INVENTORY_RANKS)}, got {rank!r}")
+            rank = INVENTORY_RANKS[rank]
+        check(self.lib, self.lib.lp_inventory_set_rank(self._h, int(rank)))
 
     # ---- focus views: tracker-chosen windows and a sweep ---------------------------------------
     def focus_create(self, **cfg) -> None:
@@ -1326,7 +1392,7 @@ class HybridPipeline:
                  views=None, view_tile: Optional[int] = None, view_overlap: int = 0, view_full_frame: bool = True,
                  focus: Optional[int] = None, focus_config: Optional[Dict] = None, view_match: Optional[str] = None,
                  view_merge: Optional[str] = None, view_match_thr: Optional[float] = None, evidence=None,
-                 topk: Optional[int] = None, track_vote: str = "top1"):
+                 topk: Optional[int] = None, track_vote: str = "top1", quality: bool = False):
         """detector_param, detector_bin: an NCNN .param / .bin pair, or an .onnx file and None.
         inventory: True or a dict of lp_inventory_config's fields (max_signs, keep_crops, best, min_hits): every tracked call
         also feeds the engine's sign inventory, while the handle still holds that call's classifier crops; drain_signs() returns
@@ -1357,7 +1423,11 @@ class HybridPipeline:
         topk: K in 1..8 (Engine.topk_enable): every result dict gains "cls_topk", the [(class, prob), ...] of the detection's K
         most probable classes in descending order ([] for an unclassified detection); cls_topk[0] is (cls_class, cls_conf).
         track_vote: "top1" = a detection adds (cls_class, cls_conf) to its track's vote; "distribution" = it adds its K most
-        probable classes, each with its probability (lp_track_topk).  "distribution" needs track and topk >= 1."""
+        probable classes, each with its probability (lp_track_topk).  "distribution" needs track and topk >= 1.
+        quality: True (Engine.quality_enable) = every result dict gains "sharpness", "luma_mean", "clip_lo" and "clip_hi" of the
+        detection's classifier crop (floats; None for a detection without a crop).  inventory=dict(best="sharpness") ranks a
+        track's sightings by that sharpness instead of an lp_best (Engine.inventory_set_rank) and switches quality on."""
+        self.quality, self._inv_rank, inv_settings = check_quality_options(quality, inventory)
         self.topk = check_topk_options(topk, track_vote, bool(track) or track_config is not None)
         self.track_vote = track_vote
         merge_set = [n for n, v in (("view_match", view_match), ("view_merge", view_merge), ("view_match_thr", view_match_thr)) if v is not None]
@@ -1419,6 +1489,9 @@ class HybridPipeline:
         if self.topk:
             self.engine.topk_enable(self.topk)
         self._topk_parts: List[np.ndarray] = []   # the lp_topk records of a run_batch's engine calls, in frame order
+        if self.quality:
+            self.engine.quality_enable(True)
+        self._quality_parts: List[np.ndarray] = []   # the lp_quality records likewise
         if merge_set:
             self.engine.set_view_merge(view_match or "iou", view_merge or "nms", 0.0 if view_match_thr is None else view_match_thr)
         self.detector = NCNNDetector(detector_param, detector_bin, det_input_size, use_gpu_detector, detector_threads,
@@ -1434,7 +1507,9 @@ class HybridPipeline:
             self.engine.focus_create(slots=self.focus, **(focus_config or {}))
         self.signs_dropped = 0
         if self.inventory:
-            self.engine.inventory_create(**(inventory if isinstance(inventory, dict) else {}))
+            self.engine.inventory_create(**inv_settings)
+            if self._inv_rank != "config":
+                self.engine.inventory_set_rank(self._inv_rank)
         if self.evidence is not None:
             self.engine.evidence_create(**self.evidence)
         # ---- upload lanes (an experiment kept behind LITEPI_DROPIN_LANES=<n>, off by default: measured SLOWER, 3.2-3.6 ms per
@@ -1460,6 +1535,8 @@ class HybridPipeline:
                 e.load_classifier(self.classifier.state_dict)
                 if self.topk:
                     e.topk_enable(self.topk)
+                if self.quality:
+                    e.quality_enable(True)
                 self._lanes.append(e)
             self._lane_pool = ThreadPoolExecutor(max_workers=n_lanes, thread_name_prefix="litepi-lane")
             self._lane_cap = lane_cap
@@ -1485,7 +1562,7 @@ class HybridPipeline:
             k, lo, hi = arg
             e = self._lanes[k]
             d, c, nd, t = e.run_batch(images[lo:hi], conf, iou, min_area)
-            return d, c, nd, t, e.last_det_conf_avg, (e.topk_read(hi - lo) if self.topk else None)
+            return d, c, nd, t, e.last_det_conf_avg, (e.topk_read(hi - lo) if self.topk else None), (e.quality_read(hi - lo) if self.quality else None)
 
         parts = list(self._lane_pool.map(one, slices))
         dets = np.concatenate([p[0] for p in parts], 0)
@@ -1497,6 +1574,8 @@ class HybridPipeline:
         self.engine.last_det_conf_avg = np.concatenate([p[4] for p in parts])
         if self.topk:
             self._topk_parts = [p[5] for p in parts]
+        if self.quality:
+            self._quality_parts = [p[6] for p in parts]
         return dets, counts, num_det, timing
 
     def _run_grouped(self, images, feed, verb, frame_views, call):
@@ -1533,6 +1612,8 @@ class HybridPipeline:
             parts.append((d, c, nd, t, self.engine.last_det_conf_avg))
             if self.topk:   # the buffer holds the last engine call's records: read before the next call replaces them
                 self._topk_parts.append(self.engine.topk_read(len(g)))
+            if self.quality:
+                self._quality_parts.append(self.engine.quality_read(len(g)))
             if feed is not None:
                 feed(d[:len(g)], c[:len(g)], done)
             done += len(g)
@@ -1656,6 +1737,7 @@ class HybridPipeline:
                 e.from_feed = True
                 raise
         self._topk_parts = []
+        self._quality_parts = []
         t0 = time.perf_counter()
         try:
             if self.focus is not None:
@@ -1671,6 +1753,8 @@ class HybridPipeline:
                 dets, counts, num_det, timing = self.engine.run_batch(images, conf_threshold, iou_threshold, min_area)
                 if self.topk:
                     self._topk_parts.append(self.engine.topk_read(len(images)))
+                if self.quality:
+                    self._quality_parts.append(self.engine.quality_read(len(images)))
         except _ffi.LitepiError as e:
             if e.code != _ffi.LP_ERR_HIP or getattr(e, "from_feed", False):  # misuse / capacity errors are raised, only an engine failure yields "nothing found"
                 raise
@@ -1678,6 +1762,7 @@ class HybridPipeline:
             return [([], PipelineMetrics()) for _ in images]
         tracks = None
         topk = np.concatenate(self._topk_parts, 0) if self.topk else None
+        quality = np.concatenate(self._quality_parts, 0) if self.quality else None
         if do_track:
             B = len(images)
             if self.tile_overlap is not None or self.view_mode or self.focus is not None:
@@ -1715,6 +1800,11 @@ class HybridPipeline:
         if topk is not None:   # the valid entries of every used record, [(class, prob), ...]
             ku = topk[:B][np.arange(topk.shape[1])[None, :] < cnt_a[:, None]]
             topk_cols = [[(c, p) for c, p in zip(cs, ps) if c >= 0] for cs, ps in zip(ku["cls"].tolist(), ku["prob"].astype(np.float64).tolist())]
+        if quality is not None:   # every used record's four figures; None for a detection without a crop
+            qu = quality[:B][np.arange(quality.shape[1])[None, :] < cnt_a[:, None]]
+            ok = (qu["flags"] & _ffi.LP_QUALITY_VALID) != 0
+            qual_cols = [dict(zip(QUALITY_RESULT_KEYS, v)) if o else dict.fromkeys(QUALITY_RESULT_KEYS)
+                         for o, v in zip(ok.tolist(), zip(*(qu[k].astype(np.float64).tolist() for k in QUALITY_RESULT_KEYS)))]
         if tracks is not None:
             tu = tracks[:B][np.arange(tracks.shape[1])[None, :] < cnt_a[:, None]]
             trk_cols = list(zip(tu["track_id"].tolist(), tu["hits"].tolist(), tu["age"].tolist(), tu["voted_class"].tolist(),
@@ -1738,6 +1828,9 @@ class HybridPipeline:
                 if topk is not None:
                     for r, tk in zip(results, topk_cols[pos:e]):
                         r["cls_topk"] = tk
+                if quality is not None:
+                    for r, qd in zip(results, qual_cols[pos:e]):
+                        r.update(qd)
                 if tracks is not None:
                     for r, (tid, th, ta, tc_, tcc, tok) in zip(results, trk_cols[pos:e]):
                         r.update(track_id=tid, track_hits=th, track_age=ta, track_cls=tc_, track_cls_conf=tcc, track_confirmed=tok)

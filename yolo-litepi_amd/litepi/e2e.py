@@ -124,8 +124,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--inventory", action="store_true",
                    help="with --track: one row per finished track in signs.csv (final voted class, first / last frame, best sighting) "
                         "and the classifier's input crop of the best sighting as signs/sign_<stream>_<track>.png; collected on the device")
-    p.add_argument("--inventory_best", choices=["area", "det_conf", "cls_conf"], default="area",
-                   help="what makes a sighting the best of its track")
+    p.add_argument("--inventory_best", choices=["area", "det_conf", "cls_conf", "sharpness"], default="area",
+                   help="what makes a sighting the best of its track; sharpness: the variance of the Laplacian of its classifier crop "
+                        "(implies --quality)")
+    p.add_argument("--quality", action="store_true",
+                   help="with --track: measure sharpness and exposure of every detection's classifier crop on the device; tracks.csv "
+                        "gains the columns sharpness, luma_mean, clip_lo, clip_hi at the end (empty for a detection without a crop)")
     p.add_argument("--inventory_evidence", type=int, default=None, metavar="E",
                    help="with --track --inventory: also keep an E x E BGR picture of the surroundings of every sign's best sighting "
                         "(a multiple of 16 in 32..256), written as signs/sign_<stream>_<track>_evidence.png; signs.csv gains the "
@@ -393,7 +397,13 @@ TRACKS_CSV_COLUMNS = ("frame", "track_id", "x1", "y1", "x2", "y2", "det_conf", "
 
 SIGNS_CSV_COLUMNS = ("stream", "track_id", "first_frame", "last_frame", "hits", "voted_class", "voted_conf", "best_frame", "x1", "y1", "x2",
                      "y2", "det_class", "flushed", "crop")
+QUALITY_CSV_COLUMNS = ("sharpness", "luma_mean", "clip_lo", "clip_hi")   # --quality: appended to tracks.csv, at the end
 EVIDENCE_CSV_COLUMNS = ("evidence_x", "evidence_y", "evidence_w", "evidence_h")   # --inventory_evidence: the picture's window, at the end
+
+
+def quality_wanted(args) -> bool:
+    """--quality, or implied by --inventory_best sharpness"""
+    return bool(getattr(args, "quality", False)) or getattr(args, "inventory_best", "area") == "sharpness"
 
 
 def parse_views(text: str) -> List:
@@ -444,6 +454,10 @@ def check_frame_args(args) -> None:
                          "K most probable classes")
     if getattr(args, "inventory", False) and not getattr(args, "track", False):
         raise SystemExit("--inventory needs --track: the inventory lists the tracker's finished tracks")
+    if getattr(args, "inventory_best", "area") == "sharpness" and not (getattr(args, "track", False) and getattr(args, "inventory", False)):
+        raise SystemExit("--inventory_best sharpness needs --track --inventory: it ranks the sightings of the inventory's tracks")
+    if getattr(args, "quality", False) and not getattr(args, "track", False):
+        raise SystemExit("--quality needs --track: the figures are written to tracks.csv")
     if getattr(args, "inventory_evidence", None) is not None or getattr(args, "inventory_evidence_scale", None) is not None:
         if not (getattr(args, "track", False) and getattr(args, "inventory", False)):
             raise SystemExit("--inventory_evidence needs --track --inventory: the pictures belong to the inventory's signs")
@@ -548,6 +562,9 @@ def run_evaluation(args) -> Dict:
         track_kw["evidence"] = dict(size=args.inventory_evidence)
         if getattr(args, "inventory_evidence_scale", None) is not None:
             track_kw["evidence"]["scale"] = args.inventory_evidence_scale
+    quality_on = quality_wanted(args)
+    if quality_on:   # absent: the pipeline is constructed exactly as before
+        track_kw["quality"] = True
     if getattr(args, "topk", None) is not None:   # absent: the pipeline is constructed exactly as before
         track_kw["topk"] = args.topk
         if getattr(args, "track_vote", "top1") != "top1":
@@ -623,7 +640,8 @@ def run_evaluation(args) -> Dict:
             if args.track:
                 for f, (res, _) in zip(chunk, bench):
                     track_rows += [(f.index, r["track_id"], *r["bbox"], r["det_conf"], r["cls_class"], r["cls_conf"], r["track_cls"],
-                                    r["track_cls_conf"], r["track_hits"], int(r["track_confirmed"])) for r in res]
+                                    r["track_cls_conf"], r["track_hits"], int(r["track_confirmed"]),
+                                    *(("" if r[k] is None else r[k] for k in QUALITY_CSV_COLUMNS) if quality_on else ())) for r in res]
                 if args.inventory:
                     signs += pipeline.drain_signs()
             for f, im, (res, _) in zip(chunk, imgs, ev):
@@ -647,9 +665,9 @@ def run_evaluation(args) -> Dict:
         import csv
         with open(out_dir / "tracks.csv", "w", newline="") as fcsv:
             w = csv.writer(fcsv)
-            w.writerow(TRACKS_CSV_COLUMNS)
+            w.writerow(TRACKS_CSV_COLUMNS + (QUALITY_CSV_COLUMNS if quality_on else ()))
             w.writerows(track_rows)
-        confirmed = {r[1] for r in track_rows if r[-1] and r[1] > 0}
+        confirmed = {r[1] for r in track_rows if r[len(TRACKS_CSV_COLUMNS) - 1] and r[1] > 0}
         say(f"Tracking: {len(confirmed)} confirmed tracks over {len(files)} frames ({len(track_rows)} detections) -> {out_dir / 'tracks.csv'}")
     if getattr(args, "focus", None) is not None:
         import csv
