@@ -314,6 +314,65 @@ int lp_run_views_device(lp_handle* h, const void* dev_imgs, int B, int H, int W,
 int lp_test_view_windows(lp_handle* h, const uint8_t* img, int H, int W, const int* views, int n_views,
                          int byte_offset, uint8_t* out, int cap);
 
+/* ---- mapped views: rectify any lens into the detector batch via remap tables (additive to ABI 310) ---- */
+/* A window view is an axis-aligned rectangle scaled uniformly; a mapped view takes every one of its S x S pixels from wherever
+ * a per-pixel table says, and carries its boxes back to the frame through the same table.  The table is data: the caller
+ * computes it once for the lens and the virtual camera wanted (a rectified pinhole looking 40 degrees right out of a fisheye
+ * frame, a perspective cut of an equirectangular panorama, a rolled camera, a mirror; litepi/lens.py builds some).  Three rules,
+ * one definition for host and device (csrc/view_map.h):
+ * TABLE.  A map belongs to a square detector input S and a frame size H x W (1 .. 16384 a side).  xy[S][S][2] float32 holds,
+ *   for view pixel (row j, column i), the frame position (x, y) it shows, in pixel-index coordinates with pixel centres at
+ *   integers: cv2.remap's convention.  It is fixed once, on the host, in doubles:
+ *     fx = (int32)rint(min(max((double)x, -2.0), (double)W + 1.0) * 32.0);   fy likewise with H       (rint: round half to even)
+ *   i.e. fixed[S][S][2] int32 with 5 fractional bits.  A NaN anywhere is LP_ERR_ARG.
+ * PIXEL.  All in int32: ix = fx >> 5 (arithmetic), ax = fx & 31, iy, ay likewise; P(r, c) = the frame's BGR pixel where
+ *   0 <= r < H and 0 <= c < W, else (114, 114, 114); per channel
+ *     out = (P(iy,ix)*(32-ax)*(32-ay) + P(iy,ix+1)*ax*(32-ay) + P(iy+1,ix)*(32-ax)*ay + P(iy+1,ix+1)*ax*ay + 512) >> 10
+ *   This is the library's own rule, NOT cv2.remap's weight table: the same picture, not the same bytes.  No byte outside the
+ *   frame's H * W * 3 is read.
+ * BOX.  A candidate of a mapped view is decoded as for a crop of an S x S image (ratio 1, pads 0, clipped to [0, S]); its box
+ *   (x1, y1, x2, y2) is in view coordinates.  All in fp32, every operation rounded on its own, nothing contracted:
+ *     xm = (x1 + x2) * 0.5f, ym likewise; the eight sample points are the four corners and the four edge midpoints;
+ *     for a point (u, v):  tu = u - 0.5f;  i = min(max((int)floorf(tu), 0), S - 2);  fu = tu - (float)i;  tv, j, fv likewise
+ *       (linear extrapolation beyond the border pixels' centres);  X(r, c) = (float)fixed_x[r][c] * 0.03125f (exact);
+ *       top = X(j,i) + fu * (X(j,i+1) - X(j,i));  bot = X(j+1,i) + fu * (X(j+1,i+1) - X(j+1,i));
+ *       px = (top + fv * (bot - top)) + 0.5f;  py from fixed_y in the same way;
+ *   the frame box is (min px, min py, max px, max py) over the eight points, clipped with fminf / fmaxf to [0, W] x [0, H].
+ *   Score, class and anchor are untouched; a box that lands wholly outside becomes a zero-area box on the frame's edge and
+ *   stays a candidate, as a detection in a letterbox bar does.
+ * Everything behind the candidates is unchanged: the frame NMS in list order (ties: higher (view, anchor) first),
+ * lp_set_view_merge, NV12 through lp_set_input_format, top-k, quality, tracker, inventory and evidence; ROIs and evidence are
+ * cut from the native frame.  A handle that lists no map in a call runs exactly what it ran before.
+ * Out of scope: focus slots as maps, the surfaces entry points, rectangular handles (LP_ERR_STATE), an antialiased or
+ * higher-order resample (a map that shrinks the frame aliases), maps that differ per frame of one call.  DESIGN.md 6p. */
+#define LP_MAP_MAX 64   /* maps of one handle; each is a device table of S * S * 8 bytes (3.3 MB at 640) */
+/* The three rules, pure host (no handle, no device).  S in 2..16384; LP_ERR_ARG for NULL, a bad size or (lp_map_fixed) a NaN. */
+int lp_map_fixed(const float* xy, int S, int H, int W, int32_t* fixed);                               /* xy[S][S][2] -> fixed[S][S][2] */
+int lp_map_render(const int32_t* fixed, int S, const uint8_t* frame, int H, int W, uint8_t* out);  /* frame [H][W][3] -> out [S][S][3] */
+int lp_map_box(const int32_t* fixed, int S, int H, int W, const float* box, float* out);             /* view box [4] -> frame box [4] */
+/* A handle's maps.  lp_map_add fixes xy[S][S][2] (S = det_input) for H x W frames, keeps it as a device table and returns ids
+ * 0, 1, ... in order; more than LP_MAP_MAX is LP_ERR_STATE.  lp_map_clear drops all maps (ids start at 0 again; captured
+ * steps are captured anew); lp_destroy frees them.  Synchronous. */
+int lp_map_add(lp_handle* h, const float* xy, int H, int W, int* id);
+int lp_map_clear(lp_handle* h);
+/* lp_run_views with maps: every frame is seen through the n_views listed views in list order (lp_run_views' format; views may
+ * be NULL with n_views = 0) and then through the n_maps maps (ids of lp_map_add) in list order; n_views + n_maps >= 1.
+ * n_maps = 0 is lp_run_views, byte for byte.  Every frame of the call must have every listed map's H x W.  A frame-size
+ * mismatch, an unknown id, B * (n_views + n_maps) > max_batch or a list beyond the frame NMS capacity is LP_ERR_ARG before
+ * anything is enqueued, and the handle stays usable.  A changed map list is captured anew, an unchanged one replays. */
+int lp_run_mapped(lp_handle* h, const uint8_t* const* imgs, const int* heights, const int* widths, int B,
+                  const int* views, int n_views, const int* maps, int n_maps, float conf, float iou, int min_area,
+                  lp_det* dets, int* counts, int* num_det, float* det_conf_avg, lp_timing* timing);
+/* lp_run_views_device with maps; both lists are HOST arrays, read before the call returns.  Asynchronous. */
+int lp_run_mapped_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, const int* views, int n_views,
+                         const int* maps, int n_maps, float conf, float iou, int min_area, void* dev_dets, void* dev_counts);
+/* The mapped gather alone (tests): one host H x W frame, uploaded as in lp_test_view_windows (the buffer ends with the
+ * frame's last byte), through the n_maps maps in list order -> out [n_maps, S, S, 3] uint8 BGR (cap views of room). */
+int lp_test_map_views(lp_handle* h, const uint8_t* img, int H, int W, const int* maps, int n_maps,
+                      int byte_offset, uint8_t* out, int cap);
+/* The candidate kernel alone (tests): n <= 16384 host view boxes [n][4] through map `map` -> frame boxes out [n][4]. */
+int lp_test_map_boxes(lp_handle* h, int map, const float* boxes, int n, float* out);
+
 /* ---- pixel format of the frames (additive to ABI 310) ------------------------------- */
 /* Hardware video decoders and capture pipelines deliver NV12: a full-resolution Y plane followed by a half-resolution
  * interleaved UV plane (U first), 1.5 bytes per pixel.  With LP_PIX_NV12 set on the handle, every entry point that takes

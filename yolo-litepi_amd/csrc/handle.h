@@ -1,4 +1,4 @@
-// Internal to the C-ABI translation units (api.cpp, pipeline.cpp, pixfmt.cpp, views.cpp, tracking.cpp, inventory.cpp, focus.cpp,
+// Internal to the C-ABI translation units (api.cpp, pipeline.cpp, pixfmt.cpp, views.cpp, maps.cpp, tracking.cpp, inventory.cpp, focus.cpp,
 // topk.cpp, quality.cpp, test_hooks.cpp): the handle behind include/litepi.h's lp_handle, the captured-step cache, and the pipeline pieces the entry points share.
 #pragma once
 #include <algorithm>
@@ -211,6 +211,11 @@ struct lp_handle {
   // frame views (lp_run_tiled*, lp_run_views*): frame geometry, frame table + view slots, per-view counts; allocated on first use
   lp::DevBuf d_fgeom, d_ftab, d_vcnt;
   lp::DevBuf d_vwin;   // scaled views (lp_run_views*): the window table, [max_batch] ViewWin; allocated on first use
+  // mapped views (lp_map_add, lp_run_mapped*): the handle's maps as device tables fixed[S][S][2] (view_map.h) with the frame
+  // size they belong to, and the per-slot map table of a call, [max_batch] MapSlot; both allocated on first use
+  struct MapEntry { lp::DevBuf fixed; int H = 0, W = 0; double foot_bytes = 0.0; };   // foot_bytes: the frame bytes its positions span
+  std::vector<std::unique_ptr<MapEntry>> maps;
+  lp::DevBuf d_vmap;
   std::vector<char> tile_cache;
   lp_view_merge vmerge = {};   // lp_set_view_merge: how the frame NMS merges a frame's views (zeros: the reference's rule)
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // staged host pass: start, after the ROI resize, after the front, end
@@ -415,17 +420,21 @@ CropRois whole_crop_rois(const uint8_t* const* rois, const int* hs, const int* w
 // ---- frame views: tiled inference and scaled views (views.cpp) ------------------------------------------------------------------
 // One view of a frame: the letterboxed whole frame, a native S x S crop at (x, y) -- it may pass the frame's edge where the
 // frame is shorter than S --, or the window {x, y, w, h} letterboxed at its own scale.
-enum ViewKind { VIEW_FULL, VIEW_CROP, VIEW_WINDOW };
+// A mapped view (lp_run_mapped*) shows the frame through map x of the handle (lp_map_add); y, w and h are unused.
+enum ViewKind { VIEW_FULL, VIEW_CROP, VIEW_WINDOW, VIEW_MAPPED };
 struct FrameView { ViewKind kind; int x, y, w, h; };
 using FrameViews = std::vector<std::vector<FrameView>>;   // every frame's views, in the frame's view order
 // The call's view layout.  Batch slots: first the L letterboxed views (one launch of the letterbox kernel, so they are exactly
 // lp_run_batch's input), then the C crops, then the windows, whose table entries wins[i] fill slot L + C + i (no windows: an
-// empty table).  frames[f] / vslot list each frame's slots in the frame's view order.
+// empty table), then the mapped views, whose table entries maps[i] fill slot L + C + wins.size() + i (likewise).  frames[f] /
+// vslot list each frame's slots in the frame's view order.
 struct ViewLayout {
   std::vector<ImgGeom> vgeom;     // [V] by slot
   std::vector<TileFrame> frames;  // [F]
   std::vector<int> vslot;         // [V] frame-major
-  std::vector<ViewWin> wins;      // [V - L - C]
+  std::vector<ViewWin> wins;      // the windows
+  std::vector<MapSlot> maps;      // the mapped views: V = L + C + wins.size() + maps.size()
+  double map_src_bytes = 0.0;     // the frame bytes the mapped views' tables span (the profiler's booking)
   int L = 0, C = 0, V = 0, max_views = 0;
 };
 void check_tiling(const lp_tiling* t, int S);
@@ -434,15 +443,17 @@ void apply_view_merge(const lp_handle* h, float iou, FrameNmsArgs& a);
 // the frames' views under tiling (lp_tile_grid of every frame) / through one list of {x, y, w, h} views, validated against every frame
 FrameViews tiled_views(int S, const lp_tiling& t, const std::vector<ImgGeom>& fg);
 FrameViews listed_views(const lp_handle* h, const int* views, int n_views, const std::vector<ImgGeom>& fg);
+// the list (n_views may be 0), then the handle's maps of the given ids; every frame must have every listed map's size
+FrameViews mapped_views(const lp_handle* h, const int* views, int n_views, const int* maps, int n_maps, const std::vector<ImgGeom>& fg);
 // the one builder; LP_ERR_ARG for more views than max_batch or than the frame NMS holds per frame
 ViewLayout view_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const FrameViews& per);
-// upload the frame geometry, the frame table, the view slots, the view geometry and the window table when any of them changed;
-// a change invalidates captured graphs (geom_ver)
+// upload the frame geometry, the frame table, the view slots, the view geometry, the window table and the map table when any of
+// them changed; a change invalidates captured graphs (geom_ver)
 void upload_tiles(lp_handle* h, const std::vector<ImgGeom>& fg, const ViewLayout& lay);
-// letterboxed views through launch_letterbox, crops through launch_crop_views, windows through launch_window_views, into dst
-// [V,S,S,3]; what the layout does not contain is not launched
+// letterboxed views through launch_letterbox, crops through launch_crop_views, windows through launch_window_views, mapped views
+// through launch_map_views (d_maps: their device table), into dst [V,S,S,3]; what the layout does not contain is not launched
 void enqueue_view_gather(const uint8_t* src, const ImgGeom* d_geom, const ViewWin* d_wins, uint8_t* dst, const ViewLayout& lay, int S,
-                         hipStream_t st, Profiler* prof);
+                         hipStream_t st, Profiler* prof, const MapSlot* d_maps = nullptr);
 // view gather + detector on the views + frame NMS (+ the ROI list when with_rois); dead (focus views only): view slots whose
 // candidates are dropped between the detector and the view sort
 void enqueue_view_front(lp_handle* h, const uint8_t* src, const ViewLayout& lay, int F, float conf, float iou, int min_area, lp_det* dets,

@@ -127,6 +127,21 @@ template <class Table> LP_LB_HD LbPlace lb_place(const Table& t) { return LbPlac
 void launch_window_views(const uint8_t* src, const ViewWin* wins, uint8_t* dst, int slot0, int n, int S, hipStream_t st,
                          const ViewWin* host_wins);
 
+// ---- map_kernels.hip (mapped views, include/litepi.h lp_map_*) ------------------------------
+// One mapped view of the view batch, device resident, data of the step as ViewWin is: the view shows the H x W frame at
+// frame_off of the source buffer through the table fixed[S][S][2] (view_map.h).
+struct MapSlot {
+  const int32_t* fixed;
+  long frame_off;
+  int H, W;
+};
+// mapped views slot0 .. slot0+n-1 of the view batch [V,S,S,3] through maps[0 .. n) (view_map.h's pixel rule); no byte outside
+// a frame's H * W * 3 is read
+void launch_map_views(const uint8_t* src, const MapSlot* maps, uint8_t* dst, int slot0, int n, int S, hipStream_t st);
+// the boxes of the candidates of slots slot0 .. slot0+n-1 (cand [.][A], their counts read on the device) from view to frame
+// coordinates through maps[0 .. n) (view_map.h's box rule), in place
+void launch_map_candidates(const MapSlot* maps, Cand* cand, const int* cand_count, int slot0, int n, int A, int S, hipStream_t st);
+
 struct TileFrame { int view0, nviews; };   // frame f's views: vslot[view0 .. view0 + nviews), in the frame's view order
 struct FrameNmsArgs {
   Cand* cand;             // [V][A] per-view candidates; after the view sort, frame f's merged list at cand + view0 * A

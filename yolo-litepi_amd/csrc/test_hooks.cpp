@@ -46,8 +46,14 @@ void gather_one_frame(lp_handle* h, const uint8_t* img, const ImgGeom& frame, si
     d_wins.alloc(lay.wins.size() * sizeof(ViewWin));
     LP_HIP(hipMemcpy(d_wins.p, lay.wins.data(), lay.wins.size() * sizeof(ViewWin), hipMemcpyHostToDevice));
   }
+  DevBuf d_maps;
+  if (!lay.maps.empty()) {
+    d_maps.alloc(lay.maps.size() * sizeof(MapSlot));
+    LP_HIP(hipMemcpy(d_maps.p, lay.maps.data(), lay.maps.size() * sizeof(MapSlot), hipMemcpyHostToDevice));
+  }
   d_out.alloc((size_t)lay.V * vb);
-  enqueue_view_gather(d_src.as<uint8_t>(), d_geom.as<ImgGeom>(), d_wins.as<ViewWin>(), d_out.as<uint8_t>(), lay, S, h->stream, nullptr);
+  enqueue_view_gather(d_src.as<uint8_t>(), d_geom.as<ImgGeom>(), d_wins.as<ViewWin>(), d_out.as<uint8_t>(), lay, S, h->stream, nullptr,
+                      d_maps.as<MapSlot>());
   LP_HIP(hipStreamSynchronize(h->stream));
   for (int k = 0; k < lay.V; ++k)
     LP_HIP(hipMemcpy(out + (size_t)k * vb, d_out.as<uint8_t>() + (size_t)lay.vslot[k] * vb, vb, hipMemcpyDeviceToHost));
@@ -160,6 +166,50 @@ int lp_test_view_windows(lp_handle* h, const uint8_t* img, int H, int W, const i
   LP_CHECK(cap >= lay.V, LP_ERR_ARG, "%d views, room for %d", lay.V, cap);
   // the frame is the whole allocation but for the offset in front: nothing the gather may read lies beyond it
   gather_one_frame(h, img, fg[0], byte_offset, lay, out);
+  LP_API_END
+}
+
+int lp_test_map_views(lp_handle* h, const uint8_t* img, int H, int W, const int* maps, int n_maps, int byte_offset, uint8_t* out, int cap) {
+  LP_API_BEGIN
+  LP_CHECK(h && img && out && H > 0 && W > 0 && byte_offset >= 0 && byte_offset < 64, LP_ERR_ARG, "bad argument");
+  check_square(h, "lp_test_map_views");
+  LP_HIP(hipSetDevice(h->cfg.device));
+  const std::vector<ImgGeom> fg(1, make_geom(H, W, h->det_h(), h->det_w(), byte_offset));
+  const ViewLayout lay = view_layout(h, fg, mapped_views(h, nullptr, 0, maps, n_maps, fg));
+  LP_CHECK(cap >= lay.V, LP_ERR_ARG, "%d views, room for %d", lay.V, cap);
+  // the frame is the whole allocation but for the offset in front: nothing the gather may read lies beyond it
+  gather_one_frame(h, img, fg[0], byte_offset, lay, out);
+  LP_API_END
+}
+
+int lp_test_map_boxes(lp_handle* h, int map, const float* boxes, int n, float* out) {
+  LP_API_BEGIN
+  LP_CHECK(h && n >= 0 && n <= 16384 && (n == 0 || (boxes && out)), LP_ERR_ARG, "bad argument");
+  check_square(h, "lp_test_map_boxes");
+  LP_CHECK(map >= 0 && map < (int)h->maps.size(), LP_ERR_ARG, "id %d is not a map of the handle (it holds %zu)", map, h->maps.size());
+  if (n == 0) return LP_OK;
+  LP_HIP(hipSetDevice(h->cfg.device));
+  std::vector<Cand> cand(n);
+  for (int i = 0; i < n; ++i) {
+    Cand c;
+    c.x1 = boxes[4 * i]; c.y1 = boxes[4 * i + 1]; c.x2 = boxes[4 * i + 2]; c.y2 = boxes[4 * i + 3];
+    c.score = 1.f; c.cls = 0; c.anchor = i; c.pad = 0;
+    cand[i] = c;
+  }
+  MapSlot m;
+  memset(&m, 0, sizeof(m));
+  m.fixed = h->maps[map]->fixed.as<int32_t>(); m.H = h->maps[map]->H; m.W = h->maps[map]->W;
+  DevBuf d_map, d_cand, d_cnt;
+  d_map.alloc(sizeof(m)); LP_HIP(hipMemcpy(d_map.p, &m, sizeof(m), hipMemcpyHostToDevice));
+  d_cand.alloc((size_t)n * sizeof(Cand)); LP_HIP(hipMemcpy(d_cand.p, cand.data(), (size_t)n * sizeof(Cand), hipMemcpyHostToDevice));
+  d_cnt.alloc(16); LP_HIP(hipMemcpy(d_cnt.p, &n, 4, hipMemcpyHostToDevice));
+  launch_map_candidates(d_map.as<MapSlot>(), d_cand.as<Cand>(), d_cnt.as<int>(), 0, 1, n, h->cfg.det_input, h->stream);
+  LP_HIP(hipStreamSynchronize(h->stream));
+  LP_HIP(hipMemcpy(cand.data(), d_cand.p, (size_t)n * sizeof(Cand), hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; ++i) {
+    LP_CHECK(cand[i].score == 1.f && cand[i].cls == 0 && cand[i].anchor == i, LP_ERR_STATE, "candidate %d: score, class or anchor changed", i);
+    out[4 * i] = cand[i].x1; out[4 * i + 1] = cand[i].y1; out[4 * i + 2] = cand[i].x2; out[4 * i + 3] = cand[i].y2;
+  }
   LP_API_END
 }
 

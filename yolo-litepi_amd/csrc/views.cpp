@@ -1,8 +1,10 @@
-// Frame views: tiled inference (lp_tile_grid, lp_run_tiled*) and scaled views (lp_view_grid, lp_view_geometry, lp_run_views*;
-// include/litepi.h "tiled inference", "scaled views").  A frame is seen through a list of views -- the letterboxed whole frame,
-// native crops, windows letterboxed at their own scale --; every view's ImgGeom carries its place in the frame as ratio / pad,
-// so decode, frame NMS, ROI stage, tracker and inventory do not know which kind a view is.  One grid, one layout, one gather
-// and one host / one device front serve both families: they differ in how a call's frames become view lists.
+// Frame views: tiled inference (lp_tile_grid, lp_run_tiled*), scaled views (lp_view_grid, lp_view_geometry, lp_run_views*) and
+// mapped views (lp_run_mapped*; include/litepi.h "tiled inference", "scaled views", "mapped views").  A frame is seen through a
+// list of views -- the letterboxed whole frame, native crops, windows letterboxed at their own scale, views through a remap
+// table --; every view's ImgGeom carries its place in the frame as ratio / pad (a mapped view's candidates are carried to the
+// frame by map_candidates in front of the view sort), so decode, frame NMS, ROI stage, tracker and inventory do not know which
+// kind a view is.  One grid, one layout, one gather and one host / one device front serve the families: they differ in how a
+// call's frames become view lists.
 #include <cmath>
 
 #include "handle.h"
@@ -110,6 +112,24 @@ FrameViews listed_views(const lp_handle* h, const int* views, int n_views, const
   return per;
 }
 
+FrameViews mapped_views(const lp_handle* h, const int* views, int n_views, const int* maps, int n_maps, const std::vector<ImgGeom>& fg) {
+  LP_CHECK(n_views >= 0 && n_maps >= 0 && (views || n_views == 0) && (maps || n_maps == 0) && n_views + (long)n_maps >= 1, LP_ERR_ARG,
+           "a call needs at least one view or map (n_views = %d, n_maps = %d)", n_views, n_maps);
+  check_view_count(h, (int)fg.size(), (long)fg.size() * ((long)n_views + n_maps));
+  for (int k = 0; k < n_maps; ++k) {
+    LP_CHECK(maps[k] >= 0 && maps[k] < (int)h->maps.size(), LP_ERR_ARG, "map %d: id %d is not a map of the handle (it holds %zu)", k, maps[k],
+             h->maps.size());
+    const lp_handle::MapEntry& m = *h->maps[maps[k]];
+    for (size_t f = 0; f < fg.size(); ++f)
+      LP_CHECK(fg[f].h == m.H && fg[f].w == m.W, LP_ERR_ARG, "map %d (id %d) belongs to %dx%d frames, frame %zu is %dx%d", k, maps[k], m.W, m.H,
+               f, fg[f].w, fg[f].h);
+  }
+  FrameViews per = n_views ? listed_views(h, views, n_views, fg) : FrameViews(fg.size());
+  for (auto& list : per)
+    for (int k = 0; k < n_maps; ++k) list.push_back(FrameView{VIEW_MAPPED, maps[k], 0, 0, 0});
+  return per;
+}
+
 // ---- the layout ----------------------------------------------------------------------------------------------------------------
 // geometry of the window {x, y, w, h} of a frame: make_geom of a h x w image, the pads moved by the window's origin
 static ImgGeom window_geom(const ImgGeom& frame, const std::array<int, 4>& win, int S) {
@@ -125,13 +145,13 @@ static ImgGeom window_geom(const ImgGeom& frame, const std::array<int, 4>& win, 
 ViewLayout view_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const FrameViews& per) {
   const int S = h->cfg.det_input, F = (int)fg.size();
   ViewLayout lay;
-  int count[3] = {0, 0, 0};   // by ViewKind
+  int count[4] = {0, 0, 0, 0};   // by ViewKind
   for (const auto& views : per) {
     for (const FrameView& v : views) ++count[v.kind];
     lay.max_views = std::max(lay.max_views, (int)views.size());
   }
   lay.L = count[VIEW_FULL]; lay.C = count[VIEW_CROP];
-  lay.V = lay.L + lay.C + count[VIEW_WINDOW];
+  lay.V = lay.L + lay.C + count[VIEW_WINDOW] + count[VIEW_MAPPED];
   check_view_count(h, F, lay.V);
   if (h->det && h->det->loaded()) {   // the frame NMS's LDS flag masks: checked here, before anything is enqueued
     const int A = h->det->num_anchors();
@@ -141,7 +161,9 @@ ViewLayout view_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const
   }
   lay.vgeom.resize(lay.V);
   lay.wins.resize(count[VIEW_WINDOW]);
-  int next[3] = {0, lay.L, lay.L + lay.C};   // the first slot of every kind
+  lay.maps.resize(count[VIEW_MAPPED]);
+  const int first_map = lay.L + lay.C + count[VIEW_WINDOW];
+  int next[4] = {0, lay.L, lay.L + lay.C, first_map};   // the first slot of every kind
   for (int f = 0; f < F; ++f) {
     lay.frames.push_back(TileFrame{(int)lay.vslot.size(), (int)per[f].size()});
     for (const FrameView& v : per[f]) {
@@ -158,6 +180,14 @@ ViewLayout view_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const
         w.x = v.x; w.y = v.y; w.w = v.w; w.h = v.h;
         w.new_w = g.new_w; w.new_h = g.new_h; w.top = g.top; w.left = g.left;
         lay.wins[slot - lay.L - lay.C] = w;
+      } else if (v.kind == VIEW_MAPPED) {   // decoded as a crop of an S x S image; map_candidates carries the boxes to the frame
+        g.h = S; g.w = S; g.new_w = S; g.new_h = S; g.top = 0; g.left = 0;
+        g.ratio = 1.0f; g.pad_w = 0.f; g.pad_h = 0.f;
+        MapSlot m;
+        memset(&m, 0, sizeof(m));   // padding bytes too: the table is compared with memcmp
+        m.fixed = h->maps[v.x]->fixed.as<int32_t>(); m.frame_off = fg[f].src_off; m.H = fg[f].h; m.W = fg[f].w;
+        lay.maps[slot - first_map] = m;
+        lay.map_src_bytes += h->maps[v.x]->foot_bytes;
       }
       lay.vgeom[slot] = g;
       lay.vslot.push_back(slot);
@@ -166,8 +196,8 @@ ViewLayout view_layout(const lp_handle* h, const std::vector<ImgGeom>& fg, const
   return lay;
 }
 
-// upload the frame geometry, the frame table, the view slots, the view geometry and the window table when any of them changed;
-// a change invalidates captured graphs (geom_ver)
+// upload the frame geometry, the frame table, the view slots, the view geometry, the window table and the map table when any of
+// them changed; a change invalidates captured graphs (geom_ver)
 void upload_tiles(lp_handle* h, const std::vector<ImgGeom>& fg, const ViewLayout& lay) {
   const int B = h->cfg.max_batch;
   if (!h->d_fgeom.p) {
@@ -177,19 +207,24 @@ void upload_tiles(lp_handle* h, const std::vector<ImgGeom>& fg, const ViewLayout
   }
   const size_t nw = lay.wins.size();
   if (nw && !h->d_vwin.p) h->d_vwin.alloc((size_t)B * sizeof(ViewWin));
+  const size_t nm = lay.maps.size();
+  if (nm && !h->d_vmap.p) h->d_vmap.alloc((size_t)B * sizeof(MapSlot));
   h->upload_geom(lay.vgeom);
   const size_t nf = fg.size();
-  std::vector<char> blob(nf * sizeof(ImgGeom) + nf * sizeof(TileFrame) + lay.vslot.size() * sizeof(int) + nw * sizeof(ViewWin));
+  std::vector<char> blob(nf * sizeof(ImgGeom) + nf * sizeof(TileFrame) + lay.vslot.size() * sizeof(int) + nw * sizeof(ViewWin) +
+                         nm * sizeof(MapSlot));
   memcpy(blob.data(), fg.data(), nf * sizeof(ImgGeom));
   memcpy(blob.data() + nf * sizeof(ImgGeom), lay.frames.data(), nf * sizeof(TileFrame));
   memcpy(blob.data() + nf * (sizeof(ImgGeom) + sizeof(TileFrame)), lay.vslot.data(), lay.vslot.size() * sizeof(int));
-  if (nw) memcpy(blob.data() + blob.size() - nw * sizeof(ViewWin), lay.wins.data(), nw * sizeof(ViewWin));
+  if (nw) memcpy(blob.data() + blob.size() - nm * sizeof(MapSlot) - nw * sizeof(ViewWin), lay.wins.data(), nw * sizeof(ViewWin));
+  if (nm) memcpy(blob.data() + blob.size() - nm * sizeof(MapSlot), lay.maps.data(), nm * sizeof(MapSlot));
   if (blob == h->tile_cache) return;
   LP_HIP(hipMemcpyAsync(h->d_fgeom.p, fg.data(), nf * sizeof(ImgGeom), hipMemcpyHostToDevice, h->stream));
   LP_HIP(hipMemcpyAsync(h->d_ftab.p, lay.frames.data(), nf * sizeof(TileFrame), hipMemcpyHostToDevice, h->stream));
   LP_HIP(hipMemcpyAsync(h->d_ftab.as<char>() + (size_t)B * sizeof(TileFrame), lay.vslot.data(), lay.vslot.size() * sizeof(int),
                         hipMemcpyHostToDevice, h->stream));
   if (nw) LP_HIP(hipMemcpyAsync(h->d_vwin.p, lay.wins.data(), nw * sizeof(ViewWin), hipMemcpyHostToDevice, h->stream));
+  if (nm) LP_HIP(hipMemcpyAsync(h->d_vmap.p, lay.maps.data(), nm * sizeof(MapSlot), hipMemcpyHostToDevice, h->stream));
   LP_HIP(hipStreamSynchronize(h->stream));
   h->tile_cache.swap(blob);
   ++h->geom_ver;
@@ -197,8 +232,8 @@ void upload_tiles(lp_handle* h, const std::vector<ImgGeom>& fg, const ViewLayout
 
 // ---- gather and detect ---------------------------------------------------------------------------------------------------------
 void enqueue_view_gather(const uint8_t* src, const ImgGeom* d_geom, const ViewWin* d_wins, uint8_t* dst, const ViewLayout& lay, int S,
-                         hipStream_t st, Profiler* prof) {
-  const int nwin = (int)lay.wins.size();
+                         hipStream_t st, Profiler* prof, const MapSlot* d_maps) {
+  const int nwin = (int)lay.wins.size(), nmap = (int)lay.maps.size();
   if (lay.L > 0) enqueue_letterbox(src, d_geom, dst, lay.vgeom.data(), lay.L, S, S, st, prof);
   if (lay.C > 0) {
     if (prof) prof->begin(st);
@@ -214,6 +249,13 @@ void enqueue_view_gather(const uint8_t* src, const ImgGeom* d_geom, const ViewWi
       prof->end(st, "window_views_u8", "view_gather", 0.0, bytes);
     }
   }
+  if (nmap > 0) {
+    LP_CHECK(d_maps, LP_ERR_STATE, "mapped views without their table");
+    if (prof) prof->begin(st);
+    launch_map_views(src, d_maps, dst, lay.L + lay.C + nwin, nmap, S, st);
+    // booked as the table once (8 bytes per view pixel), every view byte once, and the frame bytes the tables' positions span
+    if (prof) prof->end(st, "map_views_u8", "view_gather", 0.0, (double)nmap * S * S * (8 + 3) + lay.map_src_bytes);
+  }
 }
 
 // the detector on the gathered views + view sort + frame NMS (+ the ROI list when with_rois)
@@ -225,6 +267,12 @@ static void enqueue_view_detect(lp_handle* h, const ViewLayout& lay, int F, floa
     if (prof) prof->begin(h->stream);
     launch_focus_mask(dead, h->d_cand_count.as<int>(), lay.V, h->stream);
     if (prof) prof->end(h->stream, "focus_mask", "nms", 0.0, 0.0);
+  }
+  if (!lay.maps.empty()) {   // mapped views: their candidates' boxes from view to frame coordinates, in front of the view sort
+    if (prof) prof->begin(h->stream);
+    launch_map_candidates(h->d_vmap.as<MapSlot>(), h->d_cand.as<Cand>(), h->d_cand_count.as<int>(), lay.V - (int)lay.maps.size(),
+                          (int)lay.maps.size(), h->det->num_anchors(), h->cfg.det_input, h->stream);
+    if (prof) prof->end(h->stream, "map_candidates", "nms", 0.0, 0.0);
   }
   FrameNmsArgs a;
   memset(&a, 0, sizeof(a));
@@ -245,7 +293,8 @@ static void enqueue_view_detect(lp_handle* h, const ViewLayout& lay, int F, floa
 // view gather + detector on the views + frame NMS (+ the ROI list when with_rois)
 void enqueue_view_front(lp_handle* h, const uint8_t* src, const ViewLayout& lay, int F, float conf, float iou, int min_area, lp_det* dets,
                         int* counts, bool with_rois, Profiler* prof, const int* dead) {
-  enqueue_view_gather(src, h->d_geom.as<ImgGeom>(), h->d_vwin.as<ViewWin>(), h->d_lb.as<uint8_t>(), lay, h->cfg.det_input, h->stream, prof);
+  enqueue_view_gather(src, h->d_geom.as<ImgGeom>(), h->d_vwin.as<ViewWin>(), h->d_lb.as<uint8_t>(), lay, h->cfg.det_input, h->stream, prof,
+                      h->d_vmap.as<MapSlot>());
   enqueue_view_detect(h, lay, F, conf, iou, min_area, dets, counts, with_rois, prof, dead);
 }
 
@@ -359,6 +408,25 @@ int lp_letterbox_geometry(int det_h, int det_w, int H, int W, float* ratio, floa
 
 void lp_view_merge_default(lp_view_merge* cfg) {
   if (cfg) memset(cfg, 0, sizeof(*cfg));   // LP_MATCH_IOU, LP_MERGE_SUPPRESS, the call's iou
+}
+
+int lp_run_mapped(lp_handle* h, const uint8_t* const* imgs, const int* hs, const int* ws, int B, const int* views, int n_views, const int* maps,
+                  int n_maps, float conf, float iou, int min_area, lp_det* dets, int* counts, int* num_det, float* det_conf_avg,
+                  lp_timing* timing) {
+  LP_API_BEGIN
+  check_square(h, "lp_run_mapped");
+  run_views_host(h, imgs, hs, ws, B, conf, iou, min_area, dets, counts, num_det, det_conf_avg, timing, GK_VIEWS_FRONT,
+                 [&](const std::vector<ImgGeom>& fg) { return view_layout(h, fg, mapped_views(h, views, n_views, maps, n_maps, fg)); });
+  LP_API_END
+}
+
+int lp_run_mapped_device(lp_handle* h, const void* dev_imgs, int B, int H, int W, const int* views, int n_views, const int* maps, int n_maps,
+                         float conf, float iou, int min_area, void* dev_dets, void* dev_counts) {
+  LP_API_BEGIN
+  check_square(h, "lp_run_mapped_device");
+  run_views_device(h, dev_imgs, B, H, W, conf, iou, min_area, dev_dets, dev_counts, GK_VIEWS_DEVICE,
+                   [&](const std::vector<ImgGeom>& fg) { return view_layout(h, fg, mapped_views(h, views, n_views, maps, n_maps, fg)); });
+  LP_API_END
 }
 
 int lp_view_merge_check(const lp_view_merge* cfg) {

@@ -173,7 +173,10 @@ SYMBOLS = [
     "lp_surfaces_check", "lp_run_surfaces_device", "lp_run_views_surfaces_device", "lp_test_convert_surfaces", "lp_graph_stats",
     "lp_topk_enable", "lp_topk_buffer", "lp_topk_read", "lp_topk_select", "lp_track_topk_device", "lp_track_topk", "lp_test_topk",
     "lp_quality_enable", "lp_quality_buffer", "lp_quality_read", "lp_quality_measure", "lp_inventory_set_rank", "lp_test_quality",
+    "lp_map_fixed", "lp_map_render", "lp_map_box", "lp_map_add", "lp_map_clear", "lp_run_mapped", "lp_run_mapped_device",
+    "lp_test_map_views", "lp_test_map_boxes",
 ]
+LP_MAP_MAX = 64
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
 
 _lib: Optional[C.CDLL] = None
@@ -312,6 +315,16 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_quality_measure.argtypes = [vp, C.c_int, C.POINTER(LpQuality)]
     lib.lp_inventory_set_rank.argtypes = [vp, C.c_int]
     lib.lp_test_quality.argtypes = [vp, C.c_int, vp]
+    lib.lp_map_fixed.argtypes = [fp, C.c_int, C.c_int, C.c_int, vp]
+    lib.lp_map_render.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp]
+    lib.lp_map_box.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, fp]
+    lib.lp_map_add.argtypes = [vp, fp, C.c_int, C.c_int, ip]
+    lib.lp_map_clear.argtypes = [vp]
+    lib.lp_run_mapped.argtypes = [vp, u8pp, ip, ip, C.c_int, ip, C.c_int, ip, C.c_int, C.c_float, C.c_float, C.c_int, vp, ip, ip, fp,
+                                  C.POINTER(LpTiming)]
+    lib.lp_run_mapped_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp]
+    lib.lp_test_map_views.argtypes = [vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, vp, C.c_int]
+    lib.lp_test_map_boxes.argtypes = [vp, C.c_int, fp, C.c_int, fp]
     for s in SYMBOLS:
         if s not in ("lp_last_error", "lp_default_config", "lp_destroy", "lp_track_default_config", "lp_inventory_default_config",
                      "lp_evidence_default_config", "lp_focus_default_config", "lp_view_merge_default"):

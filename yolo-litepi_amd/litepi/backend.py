@@ -92,6 +92,11 @@ def _ip(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_int))
 
 
+def _id_array(ids) -> np.ndarray:
+    """a list of map ids as the int32 array the library takes"""
+    return np.ascontiguousarray(np.asarray(list(ids) if ids is not None else [], dtype=np.int32).reshape(-1))
+
+
 def view_grid(tile: int, H: int, W: int, overlap: int = 0, full_frame: bool = True) -> List[Tuple[int, int, int, int]]:
     """The window grid of an H x W frame (lp_view_grid: host only, no GPU needed): (x, y, w, h) windows of side `tile` (or the
     frame's, where it is shorter) overlapping by `overlap`, row-major, behind (-1, -1, W, H) for the whole frame."""
@@ -126,6 +131,47 @@ def letterbox_geometry(det_h: int, det_w: int, H: int, W: int) -> Dict[str, obje
                                          C.byref(nh), C.byref(top), C.byref(left)))
     return dict(ratio=np.float32(r.value), pad_w=np.float32(pw.value), pad_h=np.float32(ph.value), new_w=nw.value, new_h=nh.value,
                 top=top.value, left=left.value)
+
+
+def _map_table(a, what: str = "xy") -> np.ndarray:
+    """a map table as the contiguous [S, S, 2] array the library takes"""
+    a = np.asarray(a)
+    if a.ndim != 3 or a.shape[0] != a.shape[1] or a.shape[2] != 2:
+        raise ValueError(f"{what} is [S, S, 2] (got {a.shape})")
+    return a
+
+
+def map_fixed(xy, H: int, W: int) -> np.ndarray:
+    """The fixed-point table of a map xy [S, S, 2] float32 (frame positions (x, y) of the view's pixels, pixel centres at
+    integers) for H x W frames (lp_map_fixed: host only): [S, S, 2] int32 with 5 fractional bits."""
+    lib = _ffi.load_library()
+    xy = np.ascontiguousarray(_map_table(xy), dtype=np.float32)
+    out = np.zeros(xy.shape, dtype=np.int32)
+    check(lib, lib.lp_map_fixed(xy.ctypes.data_as(C.POINTER(C.c_float)), xy.shape[0], int(H), int(W), out.ctypes.data))
+    return out
+
+
+def map_render(fixed, frame: np.ndarray) -> np.ndarray:
+    """The view [S, S, 3] of a BGR frame through a fixed table (lp_map_render: host only)."""
+    lib = _ffi.load_library()
+    fixed = np.ascontiguousarray(_map_table(fixed, "fixed"), dtype=np.int32)
+    frame = _as_bgr(frame)
+    S = fixed.shape[0]
+    out = np.zeros((S, S, 3), dtype=np.uint8)
+    check(lib, lib.lp_map_render(fixed.ctypes.data, S, frame.ctypes.data, frame.shape[0], frame.shape[1], out.ctypes.data))
+    return out
+
+
+def map_box(fixed, H: int, W: int, boxes) -> np.ndarray:
+    """View boxes [n, 4] (x1, y1, x2, y2) as frame boxes through a fixed table (lp_map_box: host only), float32."""
+    lib = _ffi.load_library()
+    fixed = np.ascontiguousarray(_map_table(fixed, "fixed"), dtype=np.int32)
+    b = np.ascontiguousarray(np.asarray(boxes, dtype=np.float32).reshape(-1, 4))
+    out = np.zeros_like(b)
+    fp = C.POINTER(C.c_float)
+    for k in range(len(b)):
+        check(lib, lib.lp_map_box(fixed.ctypes.data, fixed.shape[0], int(H), int(W), b[k].ctypes.data_as(fp), out[k].ctypes.data_as(fp)))
+    return out
 
 
 TRACK_CONFIG_FIELDS = ("n_streams", "max_tracks", "iou_match", "max_age", "min_hits", "new_conf", "vote_decay", "class_gate", "motion")
@@ -534,6 +580,35 @@ class Engine:
         v = _view_array(views)
         check(self.lib, self.lib.lp_run_views_device(self._h, C.c_void_p(dev_imgs), B, H, W, _ip(v), len(v), conf, iou, int(min_area),
                                                      C.c_void_p(dev_dets), C.c_void_p(dev_counts)))
+
+    # ---- mapped views: any lens through a remap table ---------------------------------------------
+    def map_add(self, xy, H: int, W: int) -> int:
+        """Register the map xy [S, S, 2] float32 (S = det_input; frame positions (x, y) of the view's pixels, cv2.remap's
+        convention) for H x W frames (lp_map_add); returns its id: 0, 1, ... in order."""
+        xy = np.ascontiguousarray(_map_table(xy), dtype=np.float32)
+        if xy.shape[0] != self.cfg.det_input:
+            raise ValueError(f"a map of this engine is [{self.cfg.det_input}, {self.cfg.det_input}, 2] (got {xy.shape})")
+        mid = C.c_int(-1)
+        check(self.lib, self.lib.lp_map_add(self._h, xy.ctypes.data_as(C.POINTER(C.c_float)), int(H), int(W), C.byref(mid)))
+        return mid.value
+
+    def map_clear(self) -> None:
+        """Drop every map of the engine (lp_map_clear); ids start at 0 again."""
+        check(self.lib, self.lib.lp_map_clear(self._h))
+
+    def run_mapped(self, images: Sequence[np.ndarray], views, maps, conf: float, iou: float, min_area: int):
+        """run_views with every frame also seen through the maps of the given ids, behind the listed views (lp_run_mapped;
+        views may be empty or None): same return values, per frame."""
+        v, m = _view_array(views or []), _id_array(maps)
+        return self._run_staged(self.lib.lp_run_mapped, images, (_ip(v) if len(v) else None, len(v), _ip(m) if len(m) else None, len(m)),
+                                conf, iou, min_area)
+
+    def run_mapped_device(self, dev_imgs: int, B: int, H: int, W: int, views, maps, conf: float, iou: float, min_area: int,
+                          dev_dets: int, dev_counts: int) -> None:
+        v, m = _view_array(views or []), _id_array(maps)
+        check(self.lib, self.lib.lp_run_mapped_device(self._h, C.c_void_p(dev_imgs), B, H, W, _ip(v) if len(v) else None, len(v),
+                                                      _ip(m) if len(m) else None, len(m), conf, iou, int(min_area),
+                                                      C.c_void_p(dev_dets), C.c_void_p(dev_counts)))
 
     # ---- decoder surfaces in place -------------------------------------------------------------
     def run_surfaces_device(self, surfaces: Sequence[Surface], conf: float, iou: float, min_area: int, dev_dets: int, dev_counts: int,
@@ -1033,6 +1108,25 @@ class Engine:
                                                       out.ctypes.data, len(v)))
         return out
 
+    def test_map_views(self, img: np.ndarray, maps, byte_offset: int = 0) -> np.ndarray:
+        """The mapped gather alone: one frame (uploaded byte_offset bytes past an aligned address, the buffer ending with its last
+        byte) through the maps of the given ids -> uint8 [n_maps, S, S, 3]."""
+        a = _as_bgr(img)
+        S = self.cfg.det_input
+        m = _id_array(maps)
+        out = np.empty((len(m), S, S, 3), np.uint8)
+        check(self.lib, self.lib.lp_test_map_views(self._h, a.ctypes.data, a.shape[0], a.shape[1], _ip(m), len(m), int(byte_offset),
+                                                   out.ctypes.data, len(m)))
+        return out
+
+    def test_map_boxes(self, map_id: int, boxes) -> np.ndarray:
+        """The candidate kernel alone: view boxes [n, 4] through map map_id -> frame boxes [n, 4] float32."""
+        b = np.ascontiguousarray(np.asarray(boxes, dtype=np.float32).reshape(-1, 4))
+        out = np.zeros_like(b)
+        fp = C.POINTER(C.c_float)
+        check(self.lib, self.lib.lp_test_map_boxes(self._h, int(map_id), b.ctypes.data_as(fp), len(b), out.ctypes.data_as(fp)))
+        return out
+
     def test_convert_frames(self, frames: np.ndarray, B: int, H: int, W: int, matrix: str = "bt601", pitch: int = 0, uv_offset: int = 0,
                             frame_stride: int = 0, byte_offset: int = 0) -> np.ndarray:
         """The NV12 converter alone: the bytes of B frames of one layout -> uint8 BGR [B, H, W, 3]."""
@@ -1392,7 +1486,8 @@ class HybridPipeline:
                  views=None, view_tile: Optional[int] = None, view_overlap: int = 0, view_full_frame: bool = True,
                  focus: Optional[int] = None, focus_config: Optional[Dict] = None, view_match: Optional[str] = None,
                  view_merge: Optional[str] = None, view_match_thr: Optional[float] = None, evidence=None,
-                 topk: Optional[int] = None, track_vote: str = "top1", quality: bool = False):
+                 topk: Optional[int] = None, track_vote: str = "top1", quality: bool = False, view_maps=None,
+                 view_maps_frame: Optional[Tuple[int, int]] = None):
         """detector_param, detector_bin: an NCNN .param / .bin pair, or an .onnx file and None.
         inventory: True or a dict of lp_inventory_config's fields (max_signs, keep_crops, best, min_hits): every tracked call
         also feeds the engine's sign inventory, while the handle still holds that call's classifier crops; drain_signs() returns
@@ -1415,6 +1510,10 @@ class HybridPipeline:
         chooses on the device, the free ones swept over a window grid (focus_config: lp_focus_config's other fields).  Needs
         track and a max_batch of at least 1 + K; mutually exclusive with tile_overlap, views and view_tile.  The windows of
         the last run_batch are in last_focus_views.
+        view_maps, view_maps_frame: mapped views (lp_run_mapped): a list of remap tables xy [S, S, 2] float32 (S = det_input_size;
+        litepi.lens builds some) for frames of view_maps_frame = (H, W); every frame is seen through `views` (if given) and then
+        through every map, and boxes come back in frame coordinates.  Needs a square det_input_size; mutually exclusive with
+        tile_overlap, view_tile and focus.
         view_match, view_merge, view_match_thr: how one frame's views are merged (Engine.set_view_merge): "ios" matches a box a
         view border cut with the whole box it lies in, "union" emits the box around a keeper and everything it absorbed.  Valid
         only together with tile_overlap, views, view_tile or focus.
@@ -1431,14 +1530,15 @@ class HybridPipeline:
         self.topk = check_topk_options(topk, track_vote, bool(track) or track_config is not None)
         self.track_vote = track_vote
         merge_set = [n for n, v in (("view_match", view_match), ("view_merge", view_merge), ("view_match_thr", view_match_thr)) if v is not None]
-        if merge_set and all(v is None for v in (tile_overlap, views, view_tile, focus)):
+        if merge_set and all(v is None for v in (tile_overlap, views, view_tile, focus, view_maps)):
             raise ValueError(f"{', '.join(merge_set)} need one of tile_overlap, views, view_tile or focus: a frame seen through one "
                              f"letterboxed view has nothing to merge")
         if merge_set:
             vm = view_merge_config(view_match or "iou", view_merge or "nms", 0.0 if view_match_thr is None else view_match_thr)
             if view_merge_check(vm) != 0:
                 raise ValueError(f"view_match_thr {view_match_thr!r} outside [0, 1)")
-        for name, value in (("tile_overlap", tile_overlap), ("views", views), ("view_tile", view_tile), ("focus", focus)):
+        for name, value in (("tile_overlap", tile_overlap), ("views", views), ("view_tile", view_tile), ("focus", focus),
+                            ("view_maps", view_maps)):
             if value is not None:
                 _square_only(det_input_size, name)
         self.tile_overlap, self.tile_full_frame = tile_overlap, bool(tile_full_frame)
@@ -1449,6 +1549,26 @@ class HybridPipeline:
             raise ValueError("views needs at least one view")
         self.view_tile, self.view_overlap, self.view_full_frame = view_tile, int(view_overlap), bool(view_full_frame)
         self.view_mode = self.views is not None or view_tile is not None
+        self.view_maps, self.view_maps_frame, self._map_ids = None, None, []
+        if view_maps is not None:
+            for name, value in (("tile_overlap", tile_overlap), ("view_tile", view_tile), ("focus", focus)):
+                if value is not None:
+                    raise ValueError(f"view_maps is mutually exclusive with {name}")
+            if view_maps_frame is None or len(tuple(view_maps_frame)) != 2 or min(int(v) for v in view_maps_frame) < 1:
+                raise ValueError("view_maps needs view_maps_frame = (H, W), the size of the frames the maps belong to")
+            side = det_input_hw(det_input_size)[1]
+            self.view_maps = [np.ascontiguousarray(_map_table(m, "a map of view_maps"), dtype=np.float32) for m in view_maps]
+            if not self.view_maps or len(self.view_maps) > _ffi.LP_MAP_MAX:
+                raise ValueError(f"view_maps holds 1..{_ffi.LP_MAP_MAX} maps (got {len(self.view_maps)})")
+            for m in self.view_maps:
+                if m.shape[0] != side:
+                    raise ValueError(f"a map of view_maps is [{side}, {side}, 2] for det_input_size {side} (got {m.shape})")
+                if np.isnan(m).any():
+                    raise ValueError("a map of view_maps holds a NaN")
+            self.view_maps_frame = (int(view_maps_frame[0]), int(view_maps_frame[1]))
+            self.view_mode = True
+        elif view_maps_frame is not None:
+            raise ValueError("view_maps_frame needs view_maps")
         self.focus = None if focus is None else int(focus)
         if self.focus is not None:
             if tile_overlap is not None or self.view_mode:
@@ -1502,6 +1622,8 @@ class HybridPipeline:
         self.track = bool(track)
         if self.track or track_config is not None:
             self.engine.tracker_create(**(track_config or {}))
+        if self.view_maps is not None:
+            self._map_ids = [self.engine.map_add(m, *self.view_maps_frame) for m in self.view_maps]
         self.last_focus_views: List = []
         if self.focus is not None:
             self.engine.focus_create(slots=self.focus, **(focus_config or {}))
@@ -1631,10 +1753,17 @@ class HybridPipeline:
                                  lambda g, _: self.engine.run_tiled(g, conf, iou, min_area, ov, full))
 
     def _run_views(self, images, conf, iou, min_area, feed=None):
-        """lp_run_views calls of consecutive frames that share a view list (view_tile: the grid of their size) and fit max_batch"""
+        """lp_run_views calls of consecutive frames that share a view list (view_tile: the grid of their size) and fit max_batch;
+        with view_maps, lp_run_mapped calls on the list and the maps"""
         def frame_views(fh, fw):
+            if self.view_maps is not None:
+                vs = self.views or []
+                return vs, len(vs) + len(self._map_ids)
             vs = self.views if self.views is not None else view_grid(self.view_tile, fh, fw, self.view_overlap, self.view_full_frame)
             return vs, len(vs)
+        if self.view_maps is not None:
+            return self._run_grouped(images, feed, "has", frame_views,
+                                     lambda g, vs: self.engine.run_mapped(g, vs, self._map_ids, conf, iou, min_area))
         return self._run_grouped(images, feed, "has", frame_views, lambda g, vs: self.engine.run_views(g, vs, conf, iou, min_area))
 
     def _run_focus(self, images, conf, iou, min_area, feed, ids):

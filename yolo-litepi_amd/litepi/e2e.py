@@ -96,6 +96,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--views", type=str, default=None,
                    help='scaled views given one by one, applied to every frame: "full;x,y,w,h;..." (full = the letterboxed whole '
                         'frame; x,y,w,h = a source window in frame pixels, letterboxed to det_input at its own scale)')
+    p.add_argument("--view_maps", type=str, default=None,
+                   help="mapped views (off when absent): an .npz with xy [M, S, S, 2] float32 remap tables (S = --det_input_size; "
+                        "frame positions of every view pixel, cv2.remap's convention; litepi.lens builds them) and frame [2] = "
+                        "(H, W) of the frames they belong to; every frame is seen through --views (if given) and through every "
+                        "map, merged by one NMS per frame; excludes --tile_overlap, --view_tile and --focus")
     p.add_argument("--focus", type=int, default=None,
                    help="focus views (off when absent; needs --track): every frame is seen through the whole frame and this many "
                         "windows the tracker chooses on the device -- native-resolution looks at the small tracked signs, the free "
@@ -424,10 +429,34 @@ def parse_views(text: str) -> List:
     return out
 
 
+def load_view_maps(path: str, det_input_size):
+    """--view_maps FILE.npz -> (xy [M, S, S, 2] float32, (H, W))"""
+    size = det_input_size if isinstance(det_input_size, tuple) else (det_input_size, det_input_size)
+    try:
+        with np.load(path) as z:
+            if "xy" not in z.files or "frame" not in z.files:
+                raise SystemExit(f"--view_maps {path}: the file holds {sorted(z.files)}, it needs xy [M, S, S, 2] and frame [2]")
+            xy, frame = np.asarray(z["xy"]), np.asarray(z["frame"]).reshape(-1)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"--view_maps {path}: {e}") from None
+    if xy.ndim != 4 or xy.shape[0] < 1 or xy.shape[1] != xy.shape[2] or xy.shape[3] != 2 or xy.shape[1] != size[1]:
+        raise SystemExit(f"--view_maps {path}: xy is {xy.shape}, it needs [M, {size[1]}, {size[1]}, 2] for --det_input_size {size[1]}")
+    if len(frame) != 2 or min(int(v) for v in frame) < 1:
+        raise SystemExit(f"--view_maps {path}: frame is {frame.tolist()}, it needs (H, W)")
+    if np.isnan(xy).any():
+        raise SystemExit(f"--view_maps {path}: xy holds a NaN")
+    return np.ascontiguousarray(xy, dtype=np.float32), (int(frame[0]), int(frame[1]))
+
+
 def check_frame_args(args) -> None:
     modes = [n for n in ("tile_overlap", "view_tile", "views", "focus") if getattr(args, n, None) is not None]
     if len(modes) > 1:
         raise SystemExit("--" + ", --".join(modes) + " exclude each other: one way of looking at a frame per run")
+    if getattr(args, "view_maps", None) is not None:
+        clash = [n for n in modes if n != "views"]
+        if clash:
+            raise SystemExit(f"--view_maps and --{clash[0]} exclude each other: maps combine with --views only")
+        modes = modes + ["view_maps"]
     merge_set = [n for n in ("view_match", "view_merge", "view_match_thr") if getattr(args, n, None) is not None]
     if merge_set and not modes:
         raise SystemExit("--" + ", --".join(merge_set) + " need one of --tile_overlap, --view_tile, --views or --focus: a frame seen "
@@ -441,6 +470,8 @@ def check_frame_args(args) -> None:
                          f"detector input are not supported")
     if getattr(args, "views", None) is not None:
         parse_views(args.views)
+    if getattr(args, "view_maps", None) is not None:
+        load_view_maps(args.view_maps, size)
     if getattr(args, "focus", None) is not None:
         if not getattr(args, "track", False):
             raise SystemExit("--focus needs --track: the windows are chosen from the tracker's state")
@@ -543,6 +574,12 @@ def run_evaluation(args) -> Dict:
         view_kw = dict(views=parse_views(args.views))
         max_batch = nb * len(view_kw["views"])
         max_rois = max_rois if max_rois > 0 else nb * max_det
+    map_frame = None
+    if getattr(args, "view_maps", None) is not None:   # the listed views, then every map, per frame
+        xy, map_frame = load_view_maps(args.view_maps, args.det_input_size)
+        view_kw.update(view_maps=list(xy), view_maps_frame=map_frame)
+        max_batch = nb * (len(view_kw.get("views", [])) + len(xy))
+        max_rois = max_rois if max_rois > 0 else nb * max_det
     if getattr(args, "focus", None) is not None:   # one whole-frame view and --focus windows per frame
         view_kw = dict(focus=args.focus, focus_config=dict(side_max=args.focus_side_max, margin=args.focus_margin,
                                                            sweep=0 if args.no_focus_sweep else 1))
@@ -611,6 +648,8 @@ def run_evaluation(args) -> Dict:
             for v in view_kw.get("views", []):   # --views windows are frame pixels: the warm-up frame must hold them
                 if v != "full":
                     wh, ww = max(wh, v[1] + v[3] + (v[1] + v[3]) % 2), max(ww, v[0] + v[2] + (v[0] + v[2]) % 2)
+            if map_frame is not None:   # --view_maps: the maps belong to one frame size
+                wh, ww = map_frame
             dummy = np.random.randint(0, 255, (wh * 3 // 2, ww) if args.pixel_format == "nv12" else (wh, ww, 3), dtype=np.uint8)
             for _ in range(n_warm):
                 if args.track:   # the warm-up frames are not part of the sequence: they never reach the tracker
