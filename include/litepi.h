@@ -900,6 +900,88 @@ int lp_inventory_set_rank(lp_handle* h, int rank);
  * downloads B * max_det records.  LP_ERR_ARG for B outside 1..max_batch. */
 int lp_test_quality(lp_handle* h, int B, lp_quality* out);
 
+/* ---- device-side evaluation: detections against ground truth (additive to ABI 310) -- */
+/* An evaluator belongs to a handle, like the tracker: a null pointer nobody else looks at until lp_eval_create.  It matches
+ * the lp_det records of a call against ground-truth boxes on the device and appends one compact row per record to a log in
+ * HBM; precision, recall, F1, mAP50 and mAP50-95 are then one host function over the drained rows
+ * (litepi.e2e.metrics_from_rows, the tail of evaluate_predictions).  Plain launches on the handle's stream, outside the
+ * captured step.  Without an evaluator nothing changes: no existing path gains a launch, a branch or a buffer.
+ *
+ * The rule, per frame with P records (the kept count clamped to 0..max_det) and G ground-truth boxes (0 <= G <= max_gt); the
+ * host (lp_eval_match) and the device run the same header, csrc/eval_match.h:
+ *   1 boxes    a record's box is its four fp32 coordinates truncated toward zero to int32 (the result dict's bbox; a NaN
+ *              gives 0).  Record and ground-truth coordinates are clamped to -2^29 .. 2^29, far beyond any frame, so that
+ *              nothing below leaves int64.
+ *   2 IoU      of the pair (p, g), in int64: iw = max(0, min(px2, gx2) - max(px1, gx1)), ih likewise, inter = iw * ih,
+ *              area = (x2 - x1) * (y2 - y1) of either box; then iou = (double)inter / ((double)(area_p + area_g - inter) + 1e-7):
+ *              one fp64 add and one correctly rounded fp64 division.
+ *   3 best     best(p) = the g with the largest iou(p, g), on an exact tie the HIGHER g; b(p) = that IoU.  With G == 0 or
+ *              b(p) == 0 the record has no best ground truth.
+ *   4 correct  per threshold thr[j] (n_thr doubles in any order): a record is a candidate if it has a best ground truth and
+ *              b(p) >= thr[j]; winner(g, j) = the LOWEST record index among the candidates with best(p) == g; bit j of
+ *              correct(p) is set iff p == winner(best(p), j) and the record's cls_class equals gt[best(p)].cls.  A winner of
+ *              the wrong class blocks its ground truth.
+ *   5 outputs  optionally one lp_match_rec per record (only the first P of a frame are written; gt = -1 and iou = 0 without a
+ *              best ground truth), and always one lp_eval_row per record in the evaluator's log.  frame is the evaluator's
+ *              own frame counter (it counts every frame of every call and is reset only by lp_eval_reset).  Rows are in
+ *              frame order, then record order, across calls: a row's position is the log head at the start of the call plus
+ *              the kept counts of the call's earlier frames plus the record index.  Rows at positions >= max_rows are not
+ *              written and are counted in `dropped`; the head keeps counting.  Also kept: the number of ground-truth boxes
+ *              per class (num_classes int32 counters) and the number of frames seen.
+ * Against evaluate_predictions (e2e.py:656-824 of the reference): its argsort()[::-1] is an unstable sort, so its choice
+ * among equal IoUs is undefined.  The `correct` matrix above equals the port's on every frame in which no record has two
+ * ground-truth boxes sharing its maximal IoU at or above the lowest threshold; on the other frames the rule above holds. */
+typedef struct lp_gt {   /* 32 bytes: parse_yolo_label's tuple */
+  int32_t cls, x1, y1, x2, y2;
+  int32_t reserved[3];
+} lp_gt;
+typedef struct lp_match_rec {   /* 16 bytes, one per lp_det record; the tag lp_match is the view-merge metric's enum */
+  uint32_t correct;   /* bit j: correct at thr[j] */
+  int32_t gt;         /* best(p), or -1 */
+  double iou;         /* b(p), or 0 */
+} lp_match_rec;
+typedef struct lp_eval_row {   /* 16 bytes */
+  float conf;         /* det_conf */
+  int32_t cls;        /* cls_class */
+  uint32_t correct;
+  int32_t frame;
+} lp_eval_row;
+#define LP_EVAL_MAX_GT 256
+#define LP_EVAL_MAX_THR 16
+typedef struct lp_eval_config {
+  int max_gt;         /* ground-truth boxes per frame, 1..256; default 64 */
+  int max_rows;       /* capacity of the row log, >= 1; default 1 << 20 */
+  int n_thr;          /* 1..16; default 10 */
+  int reserved0;
+  double thr[16];     /* default 0.5 + j * ((0.5 + 0.05) - 0.5) in double: np.arange(0.5, 1.0, 0.05)'s bit patterns */
+  int reserved[8];
+} lp_eval_config;
+void lp_eval_default_config(lp_eval_config* cfg);
+/* pure host, no handle, no device: LP_ERR_ARG for a value out of range, a NaN threshold, a non-zero reserved word or NULL */
+int lp_eval_config_check(const lp_eval_config* cfg);
+/* one evaluator per handle; calling it again replaces the evaluator (the log is lost, every counter restarts) */
+int lp_eval_create(lp_handle* h, const lp_eval_config* cfg);
+int lp_eval_destroy(lp_handle* h);   /* also done by lp_destroy */
+/* asynchronous on the handle's stream: head, dropped, the frame counter and the class counts become zero */
+int lp_eval_reset(lp_handle* h);
+/* dev_dets [B*max_det] lp_det and dev_counts [B] as lp_run_batch_device / lp_run_tiled_device / lp_run_views_device left them;
+ * gts HOST [B*max_gt] (frame b's boxes at gts[b*max_gt ..]), gt_counts HOST [B]; dev_matches [B*max_det] lp_match_rec or NULL.
+ * The host arrays are read before the call returns and travel through the evaluator's ring of pinned slots, so a pageable
+ * source never synchronises the stream and any number of calls may be enqueued without a synchronise in between.
+ * LP_ERR_STATE without an evaluator.  LP_ERR_ARG before anything is enqueued, the handle staying usable, for B outside
+ * 1..max_batch, a gt_counts[b] outside 0..max_gt, a ground-truth class outside 0..num_classes-1, NULL, or a record buffer
+ * that is not 16-byte aligned. */
+int lp_eval_device(lp_handle* h, const void* dev_dets, const void* dev_counts, int B, const lp_gt* gts, const int* gt_counts,
+                   void* dev_matches);
+/* the same on host records: upload, the same kernel, download of every frame's first P matches (matches may be NULL); synchronous */
+int lp_eval(lp_handle* h, const lp_det* dets, const int* counts, int B, const lp_gt* gts, const int* gt_counts, lp_match_rec* matches);
+/* synchronises.  *n = the rows in the log (at most max_rows); rows == NULL: the numbers only; cap < *n with rows != NULL is
+ * LP_ERR_ARG.  gt_per_class [num_classes], frames, dropped: any may be NULL.  Nothing is reset. */
+int lp_eval_drain(lp_handle* h, lp_eval_row* rows, int cap, int* n, int* gt_per_class, int* frames, int* dropped);
+/* pure host, no handle, no device: the rule on one frame.  LP_ERR_ARG for NULL where a count is positive, P < 0, G < 0 or
+ * n_thr outside 1..16. */
+int lp_eval_match(const lp_det* dets, int P, const lp_gt* gts, int G, const double* thr, int n_thr, lp_match_rec* out);
+
 /* ---- classifier alone ------------------------------------------------------------ */
 /* replaces PyTorchClassifier.predict_batch (e2e.py:378-396) for R host BGR crops of
  * individual sizes: ids [R], probs [R*num_classes] (softmax). */

@@ -14,9 +14,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "litepi", "liblitepi_hip.so")
-SOURCES = ["api.cpp", "pipeline.cpp", "pixfmt.cpp", "views.cpp", "maps.cpp", "tracking.cpp", "inventory.cpp", "focus.cpp", "surfaces.cpp", "topk.cpp", "quality.cpp", "test_hooks.cpp", "ncnn_graph.cpp", "onnx_graph.cpp", "detector.cpp", "detector_plan.cpp", "classifier.cpp", "resnet.cpp", "mbnet.cpp",
+SOURCES = ["api.cpp", "pipeline.cpp", "pixfmt.cpp", "views.cpp", "maps.cpp", "tracking.cpp", "inventory.cpp", "focus.cpp", "surfaces.cpp", "topk.cpp", "quality.cpp", "eval.cpp", "test_hooks.cpp", "ncnn_graph.cpp", "onnx_graph.cpp", "detector.cpp", "detector_plan.cpp", "classifier.cpp", "resnet.cpp", "mbnet.cpp",
            "conv_kernels.hip", "misc_kernels.hip", "post_kernels.hip", "cls_kernels.hip", "cls_fused.hip", "cls_net.hip", "head_kernels.hip", "c2f_kernels.hip",
-           "tile_kernels.hip", "map_kernels.hip", "csc_kernels.hip", "track_kernels.hip", "inventory_kernels.hip", "evidence_kernels.hip", "focus_kernels.hip", "topk_kernels.hip", "quality_kernels.hip"]
+           "tile_kernels.hip", "map_kernels.hip", "csc_kernels.hip", "track_kernels.hip", "inventory_kernels.hip", "evidence_kernels.hip", "focus_kernels.hip", "topk_kernels.hip", "quality_kernels.hip", "eval_kernels.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-x", "hip", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off", "-fgpu-flush-denormals-to-zero"]
 

@@ -152,6 +152,7 @@ void lp_destroy(lp_handle* h) {
   (void)hipDeviceSynchronize();
   h->drop_graphs();
   h->trk.reset();
+  h->evl.reset();
   for (auto& e : h->ev)
     if (e) (void)hipEventDestroy(e);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);

@@ -1,5 +1,5 @@
 // Internal to the C-ABI translation units (api.cpp, pipeline.cpp, pixfmt.cpp, views.cpp, maps.cpp, tracking.cpp, inventory.cpp, focus.cpp,
-// topk.cpp, quality.cpp, test_hooks.cpp): the handle behind include/litepi.h's lp_handle, the captured-step cache, and the pipeline pieces the entry points share.
+// topk.cpp, quality.cpp, eval.cpp, test_hooks.cpp): the handle behind include/litepi.h's lp_handle, the captured-step cache, and the pipeline pieces the entry points share.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -130,6 +130,18 @@ struct Tracker {
   PlanRing ring;                       // a slot: up to max_batch jobs, then the max_batch frame indices (plan_stream_jobs)
 };
 
+// Evaluator of a handle (lp_eval_*; include/litepi.h): the counters with the class counts behind them, the thresholds and the
+// row log stay in HBM between calls.  A call's ground truth goes through a plan ring of its own (a slot: max_batch EvalFrame,
+// then up to max_batch * max_gt lp_gt packed in frame order).
+struct Evaluator {
+  lp_eval_config cfg;
+  int nc = 1, max_det = 0, max_batch = 0;
+  size_t gts_off = 0;                  // of the packed boxes in a slot
+  DevBuf state, thr, log;              // EvalState + nc int32; n_thr doubles; max_rows lp_eval_row
+  DevBuf d_dets, d_counts, d_matches;  // lp_eval (host records): allocated on first use
+  PlanRing ring;
+};
+
 // a call's stream ids against the tracker's streams (tracker, inventory and focus calls)
 inline void check_stream_ids(const Tracker& t, int B, const int* stream_ids) {
   if (stream_ids)
@@ -192,6 +204,7 @@ struct lp_handle {
   int det_h() const { return cfg.det_input_h ? cfg.det_input_h : cfg.det_input; }
   int det_w() const { return cfg.det_input; }
   std::unique_ptr<lp::Tracker> trk;   // null until lp_tracker_create: no other path looks at it
+  std::unique_ptr<lp::Evaluator> evl; // null until lp_eval_create: no other path looks at it
   void* comm = nullptr;        // ncclComm_t of lp_comm_init
   int comm_rank = 0, comm_world = 1;
   // pinned staging of the host entry points + the copy workers (created on first use)

@@ -343,6 +343,26 @@ void launch_focus_plan(const FocusArgs& a, int n_jobs, hipStream_t st);
 // cand_count[v] = 0 for every view slot v < V with dead[v] (between the detector and the view sort)
 void launch_focus_mask(const int* dead, int* cand_count, int V, hipStream_t st);
 
+// ---- eval_kernels.hip (detections against ground truth, include/litepi.h lp_eval_*) ------------
+// the evaluator's counters, device resident between calls; the num_classes ground-truth counters follow it in the same buffer
+struct EvalState { long long head, dropped; int frames, pad[3]; };
+// A call's plan slot: EvalFrame[max_batch], then the frames' ground-truth boxes packed in frame order.
+struct EvalFrame { int first, count; };   // the frame's boxes are gts[first .. first + count)
+struct EvalArgs {
+  const lp_det* dets;       // [B * max_det]
+  const int* counts;        // [B]
+  lp_match_rec* matches;        // [B * max_det] or null
+  const EvalFrame* frames;  // [B] in the plan slot
+  const lp_gt* gts;         // packed, in the plan slot
+  const double* thr;        // [n_thr] device copy of the configuration's thresholds
+  EvalState* state;
+  int* gt_per_class;        // [nc]
+  lp_eval_row* log;         // [max_rows]
+  int B, max_det, n_thr, max_rows, nc;
+};
+// one workgroup per frame, then the one-thread launch that advances head, dropped and the frame counter
+void launch_eval(const EvalArgs& a, hipStream_t st);
+
 // ---- cls_kernels.hip ------------------------------------------------------------------
 // conv1 3x3/s2 (3->CO) + folded BN + ReLU on (x/255 - mean)/std of the uint8 RGB crops
 void launch_cls_stem(int prec, const uint8_t* rgb, const float* w /*[27][CO]*/, const float* bias, int CO,

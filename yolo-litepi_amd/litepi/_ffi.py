@@ -150,6 +150,34 @@ class LpQuality(C.Structure):
 QUALITY_DTYPE = [("sharpness", "<f4"), ("luma_mean", "<f4"), ("luma_var", "<f4"), ("clip_lo", "<f4"), ("clip_hi", "<f4"), ("flags", "<i4"),
                  ("reserved", "<i4", (2,))]
 
+LP_EVAL_MAX_GT, LP_EVAL_MAX_THR = 256, 16
+
+
+class LpGt(C.Structure):
+    """lp_gt, 32 bytes: one ground-truth box, parse_yolo_label's tuple"""
+    _fields_ = [("cls", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("x2", C.c_int32), ("y2", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class LpMatch(C.Structure):
+    """lp_match_rec, 16 bytes, parallel to lp_det: bit j of correct = correct at threshold j; gt = the best ground truth or -1"""
+    _fields_ = [("correct", C.c_uint32), ("gt", C.c_int32), ("iou", C.c_double)]
+
+
+class LpEvalRow(C.Structure):
+    """lp_eval_row, 16 bytes: one record in the evaluator's log"""
+    _fields_ = [("conf", C.c_float), ("cls", C.c_int32), ("correct", C.c_uint32), ("frame", C.c_int32)]
+
+
+class LpEvalConfig(C.Structure):
+    _fields_ = [("max_gt", C.c_int), ("max_rows", C.c_int), ("n_thr", C.c_int), ("reserved0", C.c_int), ("thr", C.c_double * LP_EVAL_MAX_THR),
+                ("reserved", C.c_int * 8)]
+
+
+# numpy views of lp_gt, lp_match_rec and lp_eval_row records
+GT_DTYPE = [("cls", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"), ("reserved", "<i4", (3,))]
+MATCH_DTYPE = [("correct", "<u4"), ("gt", "<i4"), ("iou", "<f8")]
+EVAL_ROW_DTYPE = [("conf", "<f4"), ("cls", "<i4"), ("correct", "<u4"), ("frame", "<i4")]
+
 SYMBOLS = [
     "lp_last_error", "lp_version", "lp_default_config", "lp_create", "lp_destroy", "lp_load_detector_ncnn",
     "lp_load_classifier_tensors", "lp_detect_raw", "lp_detect", "lp_run_batch", "lp_run_batch_device", "lp_classify",
@@ -175,6 +203,8 @@ SYMBOLS = [
     "lp_quality_enable", "lp_quality_buffer", "lp_quality_read", "lp_quality_measure", "lp_inventory_set_rank", "lp_test_quality",
     "lp_map_fixed", "lp_map_render", "lp_map_box", "lp_map_add", "lp_map_clear", "lp_run_mapped", "lp_run_mapped_device",
     "lp_test_map_views", "lp_test_map_boxes",
+    "lp_eval_default_config", "lp_eval_config_check", "lp_eval_create", "lp_eval_destroy", "lp_eval_reset", "lp_eval_device", "lp_eval",
+    "lp_eval_drain", "lp_eval_match",
 ]
 LP_MAP_MAX = 64
 ABI_VERSION = 310   # include/litepi.h LP_ABI_VERSION: a library built from another header is refused (load_library)
@@ -325,8 +355,19 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.lp_run_mapped_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp]
     lib.lp_test_map_views.argtypes = [vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, vp, C.c_int]
     lib.lp_test_map_boxes.argtypes = [vp, C.c_int, fp, C.c_int, fp]
+    evp = C.POINTER(LpEvalConfig)
+    lib.lp_eval_default_config.argtypes = [evp]
+    lib.lp_eval_default_config.restype = None
+    lib.lp_eval_config_check.argtypes = [evp]
+    lib.lp_eval_create.argtypes = [vp, evp]
+    lib.lp_eval_destroy.argtypes = [vp]
+    lib.lp_eval_reset.argtypes = [vp]
+    lib.lp_eval_device.argtypes = [vp, vp, vp, C.c_int, vp, ip, vp]
+    lib.lp_eval.argtypes = [vp, vp, ip, C.c_int, vp, ip, vp]
+    lib.lp_eval_drain.argtypes = [vp, vp, C.c_int, ip, ip, ip, ip]
+    lib.lp_eval_match.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_double), C.c_int, vp]
     for s in SYMBOLS:
-        if s not in ("lp_last_error", "lp_default_config", "lp_destroy", "lp_track_default_config", "lp_inventory_default_config",
+        if s not in ("lp_eval_default_config", "lp_last_error", "lp_default_config", "lp_destroy", "lp_track_default_config", "lp_inventory_default_config",
                      "lp_evidence_default_config", "lp_focus_default_config", "lp_view_merge_default"):
             getattr(lib, s).restype = C.c_int
     got = lib.lp_version()

@@ -232,6 +232,71 @@ def quality_measure(crop) -> np.ndarray:
     return out[0]
 
 
+EVAL_CONFIG_FIELDS = ("max_gt", "max_rows", "thr")
+
+
+def eval_config(**cfg) -> _ffi.LpEvalConfig:
+    """lp_eval_config with the library's defaults (lp_eval_default_config) and the given fields: max_gt, max_rows, and thr, a
+    sequence of 1..16 IoU thresholds (n_thr is its length).  Host only, no GPU needed."""
+    lib = _ffi.load_library()
+    c = _ffi.LpEvalConfig()
+    lib.lp_eval_default_config(C.byref(c))
+    for k, v in cfg.items():
+        if k not in EVAL_CONFIG_FIELDS:
+            raise TypeError(f"unknown evaluator setting {k!r} (one of {EVAL_CONFIG_FIELDS})")
+        if k == "thr":
+            t = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+            if not 1 <= len(t) <= _ffi.LP_EVAL_MAX_THR:
+                raise ValueError(f"thr holds 1..{_ffi.LP_EVAL_MAX_THR} thresholds (got {len(t)})")
+            c.n_thr = len(t)
+            for j in range(_ffi.LP_EVAL_MAX_THR):
+                c.thr[j] = float(t[j]) if j < len(t) else 0.0
+        else:
+            setattr(c, k, int(v))
+    return c
+
+
+def eval_config_check(cfg: Optional[_ffi.LpEvalConfig]) -> int:
+    """lp_eval_config_check's status for a configuration (host only, no GPU needed)."""
+    lib = _ffi.load_library()
+    return lib.lp_eval_config_check(C.byref(cfg) if cfg is not None else None)
+
+
+def gt_records(gts) -> np.ndarray:
+    """one frame's ground truth, [(cls, x1, y1, x2, y2), ...] (parse_yolo_label's tuples) or GT_DTYPE records -> GT_DTYPE records"""
+    if isinstance(gts, np.ndarray) and gts.dtype.names:
+        return np.ascontiguousarray(gts, dtype=_ffi.GT_DTYPE).reshape(-1)
+    a = np.asarray(gts, dtype=np.int64).reshape(-1, 5)
+    if len(a) and (np.abs(a) > 2 ** 31 - 1).any():
+        raise ValueError("a ground-truth value does not fit int32")
+    out = np.zeros(len(a), dtype=_ffi.GT_DTYPE)
+    for k, name in enumerate(("cls", "x1", "y1", "x2", "y2")):
+        out[name] = a[:, k]
+    return out
+
+
+def eval_match(dets, gts, thr=None) -> np.ndarray:
+    """lp_eval_match (host only, no GPU needed): the evaluator's matching rule on one frame.  dets: DET_DTYPE records, gts: as
+    gt_records takes them, thr: the IoU thresholds (None: np.arange(0.5, 1.0, 0.05)) -> one MATCH_DTYPE record per detection."""
+    lib = _ffi.load_library()
+    d = np.ascontiguousarray(dets, dtype=DET_DTYPE).reshape(-1)
+    g = gt_records(gts)
+    t = np.ascontiguousarray(np.arange(0.5, 1.0, 0.05) if thr is None else thr, dtype=np.float64).reshape(-1)
+    out = np.zeros(len(d), dtype=_ffi.MATCH_DTYPE)
+    check(lib, lib.lp_eval_match(d.ctypes.data, len(d), g.ctypes.data, len(g), t.ctypes.data_as(C.POINTER(C.c_double)), len(t), out.ctypes.data))
+    return out
+
+
+def check_eval_options(evaluate, gts, n_images: Optional[int] = None) -> None:
+    """the rule HybridPipeline.run_batch applies to evaluate / gts: one needs the other, and gts holds one list per image"""
+    if evaluate and gts is None:
+        raise ValueError("a pipeline constructed with evaluate needs run_batch(gts=...): one list of (cls, x1, y1, x2, y2) per image")
+    if gts is not None and not evaluate:
+        raise ValueError("run_batch(gts=...) needs a pipeline constructed with evaluate=True or an evaluator configuration")
+    if gts is not None and n_images is not None and len(gts) != n_images:
+        raise ValueError(f"gts must hold one list per image ({n_images}), got {len(gts)}")
+
+
 INVENTORY_RANKS = {"config": _ffi.LP_RANK_CONFIG, "sharpness": _ffi.LP_RANK_SHARPNESS}
 QUALITY_RESULT_KEYS = ("sharpness", "luma_mean", "clip_lo", "clip_hi")
 
@@ -695,6 +760,70 @@ class Engine:
         check(self.lib, self.lib.lp_tracker_snapshot(self._h, int(stream), st.ctypes.data, n.value, C.byref(n), acc.ctypes.data,
                                                      C.byref(nid), C.byref(ovf)))
         return {"tracks": st, "acc": acc, "next_id": nid.value, "overflow": ovf.value}
+
+    # ---- device-side evaluation: detections against ground truth ---------------------------------
+    def eval_create(self, **cfg) -> None:
+        """One evaluator per engine (lp_eval_create); calling it again replaces it.  Settings: max_gt, max_rows, thr
+        (eval_config)."""
+        c = eval_config(**cfg)
+        check(self.lib, self.lib.lp_eval_create(self._h, C.byref(c)))
+        self.eval_cfg = c
+
+    def eval_destroy(self) -> None:
+        check(self.lib, self.lib.lp_eval_destroy(self._h))
+        self.__dict__.pop("eval_cfg", None)
+
+    def eval_reset(self) -> None:
+        """Empties the log and zeroes every counter.  Asynchronous on the engine's stream."""
+        check(self.lib, self.lib.lp_eval_reset(self._h))
+
+    def _eval_gts(self, gts, B: int):
+        """per-frame ground truth -> ([B, max_gt] GT_DTYPE, [B] int32 counts); the engine refuses what does not fit"""
+        if len(gts) != max(B, 0):   # a bad B itself is the engine's to refuse
+            raise ValueError(f"gts must hold one list per frame ({B}), got {len(gts)}")
+        B = max(B, 0)
+        max_gt = self.eval_cfg.max_gt if hasattr(self, "eval_cfg") else _ffi.LP_EVAL_MAX_GT
+        recs = [gt_records(g) for g in gts]
+        cnt = np.array([len(r) for r in recs], dtype=np.int32)
+        table = np.zeros((B, max(max_gt, 1)), dtype=_ffi.GT_DTYPE)
+        for b, r in enumerate(recs):
+            table[b, :min(len(r), max_gt)] = r[:max_gt]   # a longer list keeps its count: lp_eval* answers LP_ERR_ARG
+        return table, cnt
+
+    def evaluate(self, dets: np.ndarray, counts, gts) -> np.ndarray:
+        """lp_eval on host records as run_batch / run_tiled return them: dets [B, max_det] lp_det records, counts [B], gts one
+        list of (cls, x1, y1, x2, y2) per frame -> [B, max_det] lp_match_rec records (MATCH_DTYPE), zero beyond a frame's count; the
+        rows go to the evaluator's log.  Synchronous."""
+        d = np.ascontiguousarray(dets, dtype=DET_DTYPE).reshape(-1, self.cfg.max_det)
+        B = d.shape[0]
+        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+        if cnt.shape != (B,):
+            raise ValueError(f"counts must hold one count per frame ({B}), got shape {cnt.shape}")
+        table, gcnt = self._eval_gts(gts, B)
+        out = np.zeros((B, self.cfg.max_det), dtype=_ffi.MATCH_DTYPE)
+        ip = C.POINTER(C.c_int)
+        check(self.lib, self.lib.lp_eval(self._h, d.ctypes.data, cnt.ctypes.data_as(ip), B, table.ctypes.data, gcnt.ctypes.data_as(ip),
+                                         out.ctypes.data))
+        return out
+
+    def eval_device(self, dev_dets: int, dev_counts: int, B: int, gts, dev_matches: int = 0) -> None:
+        """lp_eval_device: consumes the records run_batch_device / run_tiled_device / run_views_device left at dev_dets /
+        dev_counts; dev_matches: [B * max_det] lp_match_rec records, or 0 for none.  Asynchronous on the engine's stream: the ground
+        truth is read before the call returns."""
+        table, gcnt = self._eval_gts(gts, int(B))
+        check(self.lib, self.lib.lp_eval_device(self._h, C.c_void_p(dev_dets), C.c_void_p(dev_counts), int(B), table.ctypes.data,
+                                                gcnt.ctypes.data_as(C.POINTER(C.c_int)), C.c_void_p(dev_matches) if dev_matches else None))
+
+    def eval_drain(self) -> Dict[str, object]:
+        """The evaluator's log (synchronises, resets nothing): {"rows": EVAL_ROW_DTYPE records in frame order, then record order,
+        "gt_per_class": [num_classes] ground-truth boxes seen per class, "frames", "dropped": rows lost to a full log}."""
+        n, fr, dr = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib, self.lib.lp_eval_drain(self._h, None, 0, C.byref(n), None, C.byref(fr), C.byref(dr)))
+        rows = np.zeros(n.value, dtype=_ffi.EVAL_ROW_DTYPE)
+        per = np.zeros(max(self.cfg.num_classes, 1), dtype=np.int32)
+        check(self.lib, self.lib.lp_eval_drain(self._h, rows.ctypes.data, n.value, C.byref(n), per.ctypes.data_as(C.POINTER(C.c_int)),
+                                               C.byref(fr), C.byref(dr)))
+        return {"rows": rows, "gt_per_class": per, "frames": fr.value, "dropped": dr.value}
 
     # ---- class distributions: top-k per detection and the distribution vote --------------------
     def topk_enable(self, k: int) -> None:
@@ -1487,7 +1616,7 @@ class HybridPipeline:
                  focus: Optional[int] = None, focus_config: Optional[Dict] = None, view_match: Optional[str] = None,
                  view_merge: Optional[str] = None, view_match_thr: Optional[float] = None, evidence=None,
                  topk: Optional[int] = None, track_vote: str = "top1", quality: bool = False, view_maps=None,
-                 view_maps_frame: Optional[Tuple[int, int]] = None):
+                 view_maps_frame: Optional[Tuple[int, int]] = None, evaluate=False):
         """detector_param, detector_bin: an NCNN .param / .bin pair, or an .onnx file and None.
         inventory: True or a dict of lp_inventory_config's fields (max_signs, keep_crops, best, min_hits): every tracked call
         also feeds the engine's sign inventory, while the handle still holds that call's classifier crops; drain_signs() returns
@@ -1525,7 +1654,16 @@ class HybridPipeline:
         probable classes, each with its probability (lp_track_topk).  "distribution" needs track and topk >= 1.
         quality: True (Engine.quality_enable) = every result dict gains "sharpness", "luma_mean", "clip_lo" and "clip_hi" of the
         detection's classifier crop (floats; None for a detection without a crop).  inventory=dict(best="sharpness") ranks a
-        track's sightings by that sharpness instead of an lp_best (Engine.inventory_set_rank) and switches quality on."""
+        track's sightings by that sharpness instead of an lp_best (Engine.inventory_set_rank) and switches quality on.
+        evaluate: True or a dict of eval_config's settings (max_gt, max_rows, thr): the engine gets an evaluator
+        (Engine.eval_create), run_batch(gts=...) matches every engine call's records against the frames' ground truth on the
+        device, and evaluation() returns the metrics of everything fed so far.  Not available with the upload lanes."""
+        self.evaluate = bool(evaluate) or isinstance(evaluate, dict)
+        if self.evaluate:
+            if eval_config_check(eval_config(**(evaluate if isinstance(evaluate, dict) else {}))) != 0:
+                raise ValueError(f"evaluate {evaluate!r}: max_gt in 1..{_ffi.LP_EVAL_MAX_GT}, max_rows >= 1, thr without a NaN")
+            if int(os.environ.get("LITEPI_DROPIN_LANES", "1")) > 1:
+                raise ValueError("evaluate: the upload lanes run on other handles than the evaluator's; unset LITEPI_DROPIN_LANES")
         self.quality, self._inv_rank, inv_settings = check_quality_options(quality, inventory)
         self.topk = check_topk_options(topk, track_vote, bool(track) or track_config is not None)
         self.track_vote = track_vote
@@ -1634,6 +1772,8 @@ class HybridPipeline:
                 self.engine.inventory_set_rank(self._inv_rank)
         if self.evidence is not None:
             self.engine.evidence_create(**self.evidence)
+        if self.evaluate:   # absent: the engine is constructed exactly as before
+            self.engine.eval_create(**(evaluate if isinstance(evaluate, dict) else {}))
         # ---- upload lanes (an experiment kept behind LITEPI_DROPIN_LANES=<n>, off by default: measured SLOWER, 3.2-3.6 ms per
         # 64-frame call against 2.7-2.9 for one handle -- four 16-frame passes cost 1.4 ms of kernels instead of 0.9 and four
         # sets of copy workers fight over the cores; walking a large batch in chunks inside lp_run_batch gained nothing either
@@ -1846,11 +1986,19 @@ class HybridPipeline:
         return out
 
     def run_batch(self, images: Sequence[np.ndarray], conf_threshold: float = 0.5, iou_threshold: float = 0.45,
-                  min_area: int = 100, stream_ids=None, track: Optional[bool] = None) -> List[Tuple[List[Dict], PipelineMetrics]]:
+                  min_area: int = 100, stream_ids=None, track: Optional[bool] = None, gts=None,
+                  evaluate: Optional[bool] = None) -> List[Tuple[List[Dict], PipelineMetrics]]:
         """stream_ids: the tracker stream of every image (None: all stream 0); track: None = the constructor's setting.
+        gts: one list of (cls, x1, y1, x2, y2) per image: the engine's evaluator is fed behind every engine call of the batch
+        (evaluation() returns the metrics).  evaluate: None = the constructor's setting; False = this call is not scored (a
+        warm-up or a timing pass) and takes no gts.  evaluate without gts, or gts without evaluate, is a ValueError.
         With focus views, track=False still plans the windows from the tracker's state (and moves the sweep) but feeds it nothing.
         In tiled mode (and with scaled views) tracker and inventory are fed behind every engine call of the batch: if a later call of the batch
         fails, they have consumed the frames of the earlier ones although the caller gets no result for the batch."""
+        do_eval = self.evaluate if evaluate is None else bool(evaluate)
+        if do_eval and not self.evaluate:
+            raise ValueError("run_batch(evaluate=True) needs a pipeline constructed with evaluate=True or an evaluator configuration")
+        check_eval_options(do_eval, gts, len(images))
         do_track = self.track if track is None else bool(track)
         if do_track and not hasattr(self.engine, "track_cfg"):
             raise ValueError("run_batch(track=True) needs a pipeline constructed with track=True or a track_config")
@@ -1859,9 +2007,12 @@ class HybridPipeline:
         if do_track and stream_ids is not None:
             ids = self.engine._stream_ids(stream_ids, len(images))
 
-        def feed(d, c, first):   # a failure of the tracker or the inventory is never taken for an engine failure below
+        def feed(d, c, first):   # a failure of the tracker, the inventory or the evaluator is never taken for an engine failure below
             try:
-                fed.append(self._feed(d, c, ids, first, self._topk_parts[-1] if self.topk else None))
+                if do_track:
+                    fed.append(self._feed(d, c, ids, first, self._topk_parts[-1] if self.topk else None))
+                if do_eval:   # frame-level records of this engine call against its frames' ground truth
+                    self.engine.evaluate(d, np.asarray(c, dtype=np.int32), gts[first:first + len(c)])
             except _ffi.LitepiError as e:
                 e.from_feed = True
                 raise
@@ -1870,12 +2021,12 @@ class HybridPipeline:
         t0 = time.perf_counter()
         try:
             if self.focus is not None:
-                dets, counts, num_det, timing = self._run_focus(list(images), conf_threshold, iou_threshold, min_area, feed if do_track else None,
+                dets, counts, num_det, timing = self._run_focus(list(images), conf_threshold, iou_threshold, min_area, feed if (do_track or do_eval) else None,
                                                                 None if stream_ids is None else self.engine._stream_ids(stream_ids, len(images)))
             elif self.tile_overlap is not None:
-                dets, counts, num_det, timing = self._run_tiled(list(images), conf_threshold, iou_threshold, min_area, feed if do_track else None)
+                dets, counts, num_det, timing = self._run_tiled(list(images), conf_threshold, iou_threshold, min_area, feed if (do_track or do_eval) else None)
             elif self.view_mode:
-                dets, counts, num_det, timing = self._run_views(list(images), conf_threshold, iou_threshold, min_area, feed if do_track else None)
+                dets, counts, num_det, timing = self._run_views(list(images), conf_threshold, iou_threshold, min_area, feed if (do_track or do_eval) else None)
             elif self._lanes and len(images) >= 32 and len(images) <= self._lane_cap * len(self._lanes):
                 dets, counts, num_det, timing = self._run_lanes(list(images), conf_threshold, iou_threshold, min_area)
             else:
@@ -1884,6 +2035,12 @@ class HybridPipeline:
                     self._topk_parts.append(self.engine.topk_read(len(images)))
                 if self.quality:
                     self._quality_parts.append(self.engine.quality_read(len(images)))
+                if do_eval:
+                    try:
+                        self.engine.evaluate(dets[:len(images)], np.asarray(counts[:len(images)], dtype=np.int32), gts)
+                    except _ffi.LitepiError as e:
+                        e.from_feed = True
+                        raise
         except _ffi.LitepiError as e:
             if e.code != _ffi.LP_ERR_HIP or getattr(e, "from_feed", False):  # misuse / capacity errors are raised, only an engine failure yields "nothing found"
                 raise
@@ -1969,4 +2126,18 @@ class HybridPipeline:
 
     def run(self, image: np.ndarray, conf_threshold: float = 0.5, iou_threshold: float = 0.45,
             min_area: int = 100) -> Tuple[List[Dict], PipelineMetrics]:
-        return self.run_batch([image], conf_threshold, iou_threshold, min_area)[0]
+        return self.run_batch([image], conf_threshold, iou_threshold, min_area, **({"evaluate": False} if self.evaluate else {}))[0]
+
+    def evaluation(self, reset: bool = False) -> Dict:
+        """The metrics of everything run_batch(gts=...) fed the evaluator (synchronises): evaluate_predictions' dict, from the
+        drained rows (litepi.e2e.metrics_from_rows); eval_frames and eval_rows_dropped then hold the frames scored and the rows
+        lost to a full log.  reset: empty the evaluator afterwards."""
+        if not self.evaluate:
+            raise ValueError("evaluation needs a pipeline constructed with evaluate=True or an evaluator configuration")
+        from .e2e import metrics_from_rows
+        got = self.engine.eval_drain()
+        m = metrics_from_rows(got["rows"], got["gt_per_class"], self.engine.cfg.num_classes, self.engine.eval_cfg.n_thr)
+        self.eval_frames, self.eval_rows_dropped = got["frames"], got["dropped"]
+        if reset:
+            self.engine.eval_reset()
+        return m

@@ -150,6 +150,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--track_vote", type=str, choices=["top1", "distribution"], default="top1",
                    help="with --track: what a detection adds to its track's class vote -- top1: its arg-max class and confidence; "
                         "distribution: its K most probable classes, each with its probability (needs --topk K)")
+    p.add_argument("--device_eval", action="store_true",
+                   help="score the evaluation pass on the device: every chunk's parsed labels go to run_batch(gts=...) and the metrics "
+                        "come from the engine's evaluator (lp_eval_*) instead of evaluate_predictions; CSVs and overlays are as before.  "
+                        "This command reads image files and gains no time from it: the gain is for callers whose frames and "
+                        "detections stay on the device.  Not with --gpus N > 1")
+    p.add_argument("--device_eval_max_gt", type=int, default=64, help="with --device_eval: the most boxes a label file may hold (1..256)")
     p.add_argument("--no_jit", action="store_true", help="accepted and ignored: there is no TorchScript on this path (e2e_optimize.py:884)")
     return p
 
@@ -317,12 +323,10 @@ def _ap101(recall: np.ndarray, precision: np.ndarray) -> float:
     return float(trapz(np.interp(x, mrec, mpre), x))
 
 
-def evaluate_predictions(all_preds, all_gts, num_classes, iou_threshold=0.5, iou_thresholds=np.arange(0.5, 1.0, 0.05)) -> Dict:
-    """Ultralytics-style global evaluation with the semantics of the reference (e2e.py:656-824):
-    per IoU threshold, matches are ranked by IoU, de-duplicated per prediction then per ground
-    truth, and count only when the CLASSIFIER class equals the label; predictions are ranked
-    globally by detector confidence; AP is the 101-point interpolated area; the means run over the
-    classes present in the ground truth.  ``iou_threshold`` is unused, as in the reference."""
+def match_predictions(all_preds, all_gts, iou_thresholds=np.arange(0.5, 1.0, 0.05)) -> List:
+    """The per-frame matching of evaluate_predictions: one (correct [P, n_thr] bool, conf [P], cls [P], ground-truth classes)
+    per frame that holds a prediction or a ground truth.  Per IoU threshold, matches are ranked by IoU and de-duplicated per
+    prediction, then per ground truth; a match counts only when the CLASSIFIER class equals the label."""
     nt = len(iou_thresholds)
     stats = []
     for preds, gts in zip(all_preds, all_gts):
@@ -353,18 +357,50 @@ def evaluate_predictions(all_preds, all_gts, num_classes, iou_threshold=0.5, iou
         else:
             tcls = np.array([])
         stats.append((correct, pconf, pcls, tcls))
+    return stats
 
-    zeros = lambda: np.zeros(num_classes)  # noqa: E731
+
+def evaluate_predictions(all_preds, all_gts, num_classes, iou_threshold=0.5, iou_thresholds=np.arange(0.5, 1.0, 0.05)) -> Dict:
+    """Ultralytics-style global evaluation with the semantics of the reference (e2e.py:656-824):
+    per IoU threshold, matches are ranked by IoU, de-duplicated per prediction then per ground
+    truth, and count only when the CLASSIFIER class equals the label; predictions are ranked
+    globally by detector confidence; AP is the 101-point interpolated area; the means run over the
+    classes present in the ground truth.  ``iou_threshold`` is unused, as in the reference.  The matching is
+    match_predictions, the ranking and the AP integral evaluate_from_rows."""
+    stats = match_predictions(all_preds, all_gts, iou_thresholds)
     if not stats:
-        return {"precision": zeros(), "recall": zeros(), "f1": zeros(), "tp": zeros(), "fp": zeros(), "fn": zeros(),
-                "mAP50": 0.0, "mAP50_95": 0.0, "classes_present": np.zeros(num_classes, dtype=bool)}
+        return _empty_metrics(num_classes)
     tp = np.concatenate([s[0] for s in stats], 0)
     conf = np.concatenate([s[1] for s in stats], 0)
     pcls = np.concatenate([s[2] for s in stats], 0)
     tcls = np.concatenate([s[3] for s in stats], 0)
+    uniq, counts = np.unique(tcls, return_counts=True)
+    return _metrics_tail(tp, conf, pcls, uniq, counts, num_classes)
+
+
+def _empty_metrics(num_classes) -> Dict:
+    zeros = lambda: np.zeros(num_classes)  # noqa: E731
+    return {"precision": zeros(), "recall": zeros(), "f1": zeros(), "tp": zeros(), "fp": zeros(), "fn": zeros(),
+            "mAP50": 0.0, "mAP50_95": 0.0, "classes_present": np.zeros(num_classes, dtype=bool)}
+
+
+def evaluate_from_rows(tp, conf, pcls, gt_per_class, num_classes) -> Dict:
+    """The tail of evaluate_predictions: tp [N, n_thr] bool, conf [N] float64 and pcls [N], one row per prediction in frame
+    order, and gt_per_class [num_classes], the ground-truth boxes per class.  Ranks the rows globally by confidence and
+    integrates AP per class; the dict evaluate_predictions returns."""
+    gt_per_class = np.asarray(gt_per_class, dtype=np.int64)
+    if len(conf) == 0 and not gt_per_class.any():   # no frame held a prediction or a ground truth
+        return _empty_metrics(num_classes)
+    uniq = np.flatnonzero(gt_per_class)   # what np.unique(tcls, return_counts=True) gives for classes inside 0..num_classes-1
+    return _metrics_tail(tp, conf, pcls, uniq, gt_per_class[uniq], num_classes)
+
+
+def _metrics_tail(tp, conf, pcls, uniq, counts, num_classes) -> Dict:
+    """everything of evaluate_predictions from the global ranking on; uniq / counts: the ground-truth classes present and
+    their numbers of boxes, as np.unique(tcls, return_counts=True) returns them"""
+    zeros = lambda: np.zeros(num_classes)  # noqa: E731
     order = np.argsort(-conf)
     tp, pcls = tp[order], pcls[order]
-    uniq, counts = np.unique(tcls, return_counts=True)
     n_gt_of = dict(zip(uniq, counts))
     ap50, ap5095, pbest, rbest, fbest = zeros(), zeros(), zeros(), zeros(), zeros()
     tpc_, fpc_, fnc_ = zeros(), zeros(), zeros()
@@ -393,6 +429,16 @@ def evaluate_predictions(all_preds, all_gts, num_classes, iou_threshold=0.5, iou
             "mAP50": float(np.mean(ap50[present])) if len(present) else 0.0,
             "mAP50_95": float(np.mean(ap5095[present])) if len(present) else 0.0,
             "ap50_per_class": ap50, "classes_present": np.isin(np.arange(num_classes), uniq)}
+
+
+def metrics_from_rows(rows, gt_per_class, num_classes, n_thr) -> Dict:
+    """The metrics of an evaluator's drained log (Engine.eval_drain): rows are EVAL_ROW_DTYPE records in frame order, then
+    record order.  Bit j of `correct` becomes column j of the boolean matrix, conf the float64 of the float32 det_conf, as
+    the result dicts carry it, and the same tail as evaluate_predictions does the rest: the same arrays into the same numpy
+    calls, so also the same order among equal confidences."""
+    rows = np.asarray(rows)
+    tp = ((rows["correct"][:, None] >> np.arange(n_thr, dtype=np.uint32)[None, :]) & 1).astype(bool)
+    return evaluate_from_rows(tp, rows["conf"].astype(np.float64), rows["cls"].astype(np.int64), gt_per_class, num_classes)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -448,7 +494,42 @@ def load_view_maps(path: str, det_input_size):
     return np.ascontiguousarray(xy, dtype=np.float32), (int(frame[0]), int(frame[1]))
 
 
+def list_inputs(args):
+    """What a run processes: (files, raw, label_dir, (fw, fh)) -- the frames of --raw_frames (raw: the memory-mapped file), the
+    one image --input names, or the images of the --input directory, sampled by --num_samples."""
+    inp = Path(args.input)
+    raw, fw, fh = None, 0, 0
+    if args.raw_frames:
+        fw, fh = parse_frame_size(args.frame_size)
+        raw = read_raw_frames(args.raw_frames, fw, fh, args.pixel_format)
+        label_dir = Path(args.labels) if args.labels else None
+        files = [RawFrame(i, Path(args.raw_frames).parent) for i in range(len(raw))]
+        if args.num_samples:
+            files = sample_images(files, args.num_samples, args.seed)
+    elif inp.is_file():
+        files = [inp]
+        label_dir = Path(args.labels) if args.labels else None
+    else:
+        label_dir = Path(args.labels) if args.labels else inp / "labels"
+        files = sorted(list(inp.glob("*.jpg")) + list(inp.glob("*.png")) + list(inp.glob("*.jpeg")))
+        if args.num_samples:
+            files = sample_images(files, args.num_samples, args.seed)
+    return files, raw, label_dir, (fw, fh)
+
+
+def check_device_eval_labels(gts, max_gt: int, name) -> None:
+    """--device_eval: a label file with more boxes than the evaluator holds per frame is refused"""
+    if len(gts) > max_gt:
+        raise SystemExit(f"--device_eval: {name} holds {len(gts)} boxes, more than --device_eval_max_gt {max_gt}")
+
+
 def check_frame_args(args) -> None:
+    if getattr(args, "device_eval", False):
+        if args.gpus > 1:
+            raise SystemExit(f"--device_eval and --gpus {args.gpus} exclude each other: the sharded gather of the evaluator's rows is "
+                             f"not supported")
+        if not 1 <= getattr(args, "device_eval_max_gt", 64) <= 256:
+            raise SystemExit(f"--device_eval_max_gt {args.device_eval_max_gt} outside 1..256")
     modes = [n for n in ("tile_overlap", "view_tile", "views", "focus") if getattr(args, n, None) is not None]
     if len(modes) > 1:
         raise SystemExit("--" + ", --".join(modes) + " exclude each other: one way of looking at a frame per run")
@@ -590,6 +671,7 @@ def run_evaluation(args) -> Dict:
             view_kw[name] = getattr(args, name)
     import contextlib
     import io
+    files, raw, label_dir, (fw, fh) = list_inputs(args)
     # with --track off the pipeline is constructed and called exactly as before
     track_kw = dict(track=True, track_config=dict(iou_match=args.track_iou, max_age=args.track_max_age, min_hits=args.track_min_hits)) if args.track else {}
     if args.inventory:
@@ -607,6 +689,13 @@ def run_evaluation(args) -> Dict:
         if getattr(args, "track_vote", "top1") != "top1":
             track_kw["track_vote"] = args.track_vote
     bench_kw, eval_kw = (dict(track=True), dict(track=False)) if args.track else ({}, {})
+    device_eval = bool(getattr(args, "device_eval", False))
+    if device_eval:   # absent: the pipeline is constructed and called exactly as before
+        if world > 1:
+            raise SystemExit(f"--device_eval runs in one process (WORLD_SIZE is {world})")
+        # the log holds every record of the evaluation pass
+        track_kw["evaluate"] = dict(max_gt=args.device_eval_max_gt, max_rows=max(1, min(len(files) * max_det, 1 << 27)))
+        one_pass = args.yolo_conf == args.benchmark_conf   # then the benchmark pass is the evaluation pass, as without the flag
     with contextlib.redirect_stdout(io.StringIO()) if rank != 0 else contextlib.nullcontext():   # one banner, rank 0's
         pipeline = HybridPipeline(args.detector_param, args.detector_bin, args.classifier, args.clf_arch, num_classes,
                                   args.det_input_size, args.cls_input_size, False, args.detector_threads, args.device,
@@ -617,23 +706,6 @@ def run_evaluation(args) -> Dict:
     out_dir = Path(args.output) / combo
     out_dir.mkdir(parents=True, exist_ok=True)
 
-    inp = Path(args.input)
-    raw = None
-    if args.raw_frames:
-        fw, fh = parse_frame_size(args.frame_size)
-        raw = read_raw_frames(args.raw_frames, fw, fh, args.pixel_format)
-        label_dir = Path(args.labels) if args.labels else None
-        files = [RawFrame(i, Path(args.raw_frames).parent) for i in range(len(raw))]
-        if args.num_samples:
-            files = sample_images(files, args.num_samples, args.seed)
-    elif inp.is_file():
-        files = [inp]
-        label_dir = Path(args.labels) if args.labels else None
-    else:
-        label_dir = Path(args.labels) if args.labels else inp / "labels"
-        files = sorted(list(inp.glob("*.jpg")) + list(inp.glob("*.png")) + list(inp.glob("*.jpeg")))
-        if args.num_samples:
-            files = sample_images(files, args.num_samples, args.seed)
     say(f"\nFound {len(files)} images for processing" + (f" ({world} ranks, contiguous shards)" if world > 1 else ""))
     n_total = len(files)
     lo, hi = D.shard_range(n_total, rank, world)
@@ -653,7 +725,7 @@ def run_evaluation(args) -> Dict:
             dummy = np.random.randint(0, 255, (wh * 3 // 2, ww) if args.pixel_format == "nv12" else (wh, ww, 3), dtype=np.uint8)
             for _ in range(n_warm):
                 if args.track:   # the warm-up frames are not part of the sequence: they never reach the tracker
-                    pipeline.run_batch([dummy], 0.5, track=False)
+                    pipeline.run_batch([dummy], 0.5, track=False, **({"evaluate": False} if device_eval else {}))
                 else:
                     pipeline.run(dummy, conf_threshold=0.5)
             say(f"Warmup complete ({n_warm} passes)")
@@ -669,10 +741,23 @@ def run_evaluation(args) -> Dict:
             if not imgs:
                 continue
             # the tracker is fed exactly once per frame: by the benchmark pass; the evaluation pass is not tracked
-            bench = pipeline.run_batch(imgs, args.benchmark_conf, args.iou_threshold, args.min_area, **bench_kw)
+            chunk_gts = None
+            if device_eval:   # the labels are parsed once, in front of the pass that hands them to the evaluator
+                chunk_gts = []
+                for f, im in zip(chunk, imgs):
+                    lp = (label_dir / f"{f.stem}.txt") if label_dir else f.parent / "labels" / f"{f.stem}.txt"
+                    im_h, im_w = (fh, fw) if raw is not None else im.shape[:2]
+                    chunk_gts.append(parse_yolo_label(lp, im_w, im_h))
+                    check_device_eval_labels(chunk_gts[-1], args.device_eval_max_gt, lp)
+            scored_kw = dict(gts=chunk_gts) if device_eval else {}
+            bench = pipeline.run_batch(imgs, args.benchmark_conf, args.iou_threshold, args.min_area, **bench_kw,
+                                       **(scored_kw if device_eval and one_pass else {"evaluate": False} if device_eval else {}))
             bench_time += sum(m.t_total for _, m in bench) / 1000.0
             bench_views = list(getattr(pipeline, "last_focus_views", []))
-            ev = bench if args.yolo_conf == args.benchmark_conf else pipeline.run_batch(imgs, args.yolo_conf, args.iou_threshold, args.min_area, **eval_kw)
+            if device_eval:
+                ev = bench if one_pass else pipeline.run_batch(imgs, args.yolo_conf, args.iou_threshold, args.min_area, **eval_kw, **scored_kw)
+            else:
+                ev = bench if args.yolo_conf == args.benchmark_conf else pipeline.run_batch(imgs, args.yolo_conf, args.iou_threshold, args.min_area, **eval_kw)
             if getattr(args, "focus", None) is not None:   # the windows of the benchmark pass, the one the tracker follows
                 for f, wins in zip(chunk, bench_views):
                     focus_rows += [(f.index, k, *w) for k, w in enumerate(wins)]
@@ -683,10 +768,10 @@ def run_evaluation(args) -> Dict:
                                     *(("" if r[k] is None else r[k] for k in QUALITY_CSV_COLUMNS) if quality_on else ())) for r in res]
                 if args.inventory:
                     signs += pipeline.drain_signs()
-            for f, im, (res, _) in zip(chunk, imgs, ev):
+            for k, (f, im, (res, _)) in enumerate(zip(chunk, imgs, ev)):
                 lp = (label_dir / f"{f.stem}.txt") if label_dir else f.parent / "labels" / f"{f.stem}.txt"
                 im_h, im_w = (fh, fw) if raw is not None else im.shape[:2]
-                all_gts.append(parse_yolo_label(lp, im_w, im_h))
+                all_gts.append(chunk_gts[k] if chunk_gts is not None else parse_yolo_label(lp, im_w, im_h))
                 if args.save_viz:   # overlays of the evaluation pass, e2e.py:1003-1009
                     viz_dir = out_dir / "visualizations"
                     viz_dir.mkdir(parents=True, exist_ok=True)
@@ -698,6 +783,10 @@ def run_evaluation(args) -> Dict:
                 names.append(f.name)
         if args.inventory:   # the end of the sequence: the tracks still open are signs too
             signs += pipeline.drain_signs(flush=True)
+        device_metrics = pipeline.evaluation() if device_eval else None
+        if device_eval and pipeline.eval_rows_dropped:
+            raise SystemExit(f"--device_eval: {pipeline.eval_rows_dropped} records did not fit the evaluator's log; lower --max_det or "
+                             f"raise --yolo_conf")
     finally:
         pipeline.engine.close()
     if args.track:
@@ -747,7 +836,7 @@ def run_evaluation(args) -> Dict:
         if rank != 0:
             return {"rank": rank, "files": names}
         all_preds, all_gts, rank_times = got
-    m = evaluate_predictions(all_preds, all_gts, num_classes, args.iou_threshold)
+    m = device_metrics if device_eval else evaluate_predictions(all_preds, all_gts, num_classes, args.iou_threshold)
     # one rank: the reference's figure, mean per-image benchmark time; N ranks: the sharded job takes as long as its slowest rank
     avg = max(rank_times) / len(all_preds) if all_preds else 0.0
     return {"combo": combo, "detector": detector_name, "class_names": class_names, "metrics": m, "avg_time": avg,
