@@ -14,6 +14,7 @@
 #include "common.h"
 #include "conv.h"
 #include "conv_bounds.h"
+#include "stem_walk.h"
 #include <type_traits>
 #include <algorithm>
 #include <utility>
@@ -1651,39 +1652,52 @@ __global__ __launch_bounds__(256) void stem_mfma16_kernel(const uint8_t* __restr
 #define SB_ROWW 102                 /* dwords per staged input row: 3 + 131*3 bytes + the lanes' 3rd dword (<= 101); with SB_LW 65 the
                                        kernel's 31,968 B of LDS are 25 granules of 1280 B: FIVE workgroups per CU (32,512 B: four) */
 #define SB_PAIRS ((SB_SW + 1) / 2)  /* pixel pairs per stem row */
+static_assert(SB_SH == swalk::Geo<SB_TH>::SH && SB_SW == swalk::Geo<SB_TH>::SW && SB_LW == swalk::Geo<SB_TH>::LW && SB_IR == swalk::Geo<SB_TH>::IR &&
+              SB_ROWW == swalk::Geo<SB_TH>::ROWW && SB_PAIRS == swalk::PairWalk::PER_ROW && SB_TW == swalk::Geo<SB_TH>::TW, "stem_walk.h holds this geometry");
+
+// uint8 tile of a block kernel -> LDS: G::IR rows of G::ROWW dwords, row r = image row 4 oy0 - 3 + r, dword c = row dword w0 + c,
+// zeros outside the image (swalk::stage_src is the definition).  A wave owns half rows, so everything about a row -- its number,
+// clamp, validity and base address -- is computed once per row on the scalar unit (the wave index goes through readfirstlane:
+// tid >> 6 alone is not provably uniform); a lane computes its dword column, clamp and validity once.  A load is then a scalar base
+// + one vector byte offset, a store one select.  ALL of a thread's 18 loads are requested before the first store: unconditional,
+// from clamped addresses, masked when stored.  (As a loop of `if (inside) v = load; store v` this was one memory round trip per
+// row -- 18 in a row, ~15 of a workgroup's 18 us.)
+template <class G>
+__device__ __forceinline__ void stage_block_tile(const uint8_t* __restrict__ img, uint32_t* __restrict__ in_tile, int n, int oy0, int ox0, int Hin,
+                                                 int Win, int tid) {
+  const int row_words = Win * 3 / 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int c = swalk::stage_col(wave, lane), wi = swalk::tile_w0(ox0) + c;
+  const unsigned coff = 4u * (unsigned)swalk::clampi(wi, row_words);
+  const uint32_t cmask = swalk::inside(wi, row_words) ? 0xffffffffu : 0u;
+  const char* im = reinterpret_cast<const char*>(img) + (long)n * Hin * Win * 3;
+  const unsigned row_bytes = (unsigned)row_words * 4u;   // one image spans less than 2^31 bytes (launch_block checks): 32-bit row offsets
+  const int iy0 = swalk::tile_iy0(oy0);
+  constexpr int NR = swalk::stage_rows<G>();
+  uint32_t v[NR];
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    const char* row = im + (unsigned)swalk::clampi(iy0 + swalk::stage_row<G>(wave, k), Hin) * row_bytes;
+    v[k] = *reinterpret_cast<const uint32_t*>(row + coff);
+  }
+  if (c < G::ROWW) {
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      const int r = swalk::stage_row<G>(wave, k);
+      const uint32_t m = swalk::inside(iy0 + r, Hin) ? cmask : 0u;
+      in_tile[r * G::ROWW + c] = v[k] & m;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void stem_block_kernel(const StemBlockArgs a) {
   __shared__ uint32_t in_tile[SB_IR * SB_ROWW];
   __shared__ __attribute__((aligned(16))) char st_tile[SB_SH * SB_LW * 16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, col = lane & 15;
   const int n = blockIdx.x, ox0 = blockIdx.y * SB_TW, oy0 = blockIdx.z * SB_TH;
   // ---- 1. uint8 tile: input rows 4*oy0-3 .., bytes from (4*ox0-3)*3 (= 3 mod 4: tile byte 3 is that byte)
-  const int row_words = a.Win * 3 / 4;
-  const int w0 = (12 * ox0 - 9) >> 2;
-  const uint32_t* im = reinterpret_cast<const uint32_t*>(a.img + (long)n * a.Hin * a.Win * 3);
-  {  // a thread keeps its dword column and strides over rows.  ALL of its (up to 18) loads are requested before the first store:
-     // unconditional, from clamped addresses, masked when stored.  (As a loop of `if (inside) v = load; store v` this was one
-     // memory round trip per row -- 18 in a row, ~15 of a workgroup's 18 us.)
-    const int c = tid & 127, r0 = tid >> 7;
-    const int wi = w0 + c;
-    const bool colok = c < SB_ROWW && wi >= 0 && wi < row_words;
-    const int wic = wi < 0 ? 0 : (wi < row_words ? wi : row_words - 1);
-    constexpr int NR = (SB_IR + 1) / 2;
-    uint32_t v[NR];
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int iy = 4 * oy0 - 3 + r0 + 2 * k;
-      const int iyc = iy < 0 ? 0 : (iy < a.Hin ? iy : a.Hin - 1);
-      v[k] = im[(long)iyc * row_words + wic];
-    }
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int r = r0 + 2 * k;
-      const int iy = 4 * oy0 - 3 + r;
-      const uint32_t m = (colok && iy >= 0 && iy < a.Hin) ? 0xffffffffu : 0u;
-      if (c < SB_ROWW && r < SB_IR) in_tile[r * SB_ROWW + c] = v[k] & m;
-    }
-  }
+  stage_block_tile<swalk::Geo<SB_TH>>(a.img, in_tile, n, oy0, ox0, a.Hin, a.Win, tid);
   const half8 af0 = __builtin_bit_cast(half8, reinterpret_cast<const u32x4*>(a.afrag)[lane]);   // StemLayer::d_afrag_blk
   const half8 af1 = __builtin_bit_cast(half8, reinterpret_cast<const u32x4*>(a.afrag)[64 + lane]);
   const int c0 = (g & 1) * 4;
@@ -1699,24 +1713,28 @@ __global__ __launch_bounds__(256) void stem_block_kernel(const StemBlockArgs a) 
   // read rows two apart = 2 x 102 = 204 dwords = 12 banks apart (row pitch SB_ROWW = 102 dwords; 16 banks at round 3's first pitch of
   // 104, for which the simulation below was run): about half the bank conflicts of the (ky, h) = (q / 2, q % 2) order
   // (852 -> 522 LDS cycles per workgroup in a simulation of the access pattern).
-  const int ky0 = 2 * (g & 1), hh = g >> 1;
+  // (ky0 = 2 (g & 1), h = g >> 1: PairWalk::lane_rd, rd1)
   // pair index of this lane's column in tile t, as (row r, pair pp): t advances by 4 tiles = 64 pairs = 1 row + 31 pairs
-  // (an interior and a border form of the loop, chosen per workgroup: the per-pixel map test is 8 of an iteration's ~90 instructions
-  //  and four workgroups in five lie wholly inside the stem map)
+  // (an interior and a border form of the loop, chosen per workgroup: the per-pixel map test is 8 of an iteration's instructions
+  //  and four workgroups in five lie wholly inside the stem map).
+  // The walk (stem_walk.h, PairWalk): a lane keeps one read offset into in_tile and one write offset into st_tile; both advance by
+  // a constant per iteration, with one correction where the pair index leaves its row -- no multiply and no clamp in the loop.  A
+  // lane's pair index can pass NPAIR only in the last iteration (PW::FULL of PW::ITERS are all live): that one is peeled and keeps
+  // the clamp to the tile's last pair.
+  typedef swalk::PairWalk PW;
+  static_assert(PW::N == NPAIR && PW::NTILE == NTILE, "stem_walk.h holds this walk");
   auto stem_loop = [&](auto interior) {
-  int pi = wave * 16 + col;
-  int r = pi >= SB_PAIRS ? 1 : 0, pp = pi - r * SB_PAIRS;   // wave * 16 + col < 64 < 2 * SB_PAIRS
-  for (int t = wave; t < NTILE; t += 4) {
-    const bool live = pi < NPAIR;
-    const int rc = live ? r : SB_SH - 1, ppc = live ? pp : SB_PAIRS - 1;
+  // the lane's part of the read offset: step 0 reads row ky0, step 1 row 1 -- a per-lane constant further on
+  const int pos0 = PW::pos0(wave, col), lane_rd = PW::lane_rd(g), rd1 = PW::rd1(g), lane_wr = PW::lane_wr(g);
+  swalk::Walk w = swalk::start<PW>(pos0, lane_rd, lane_wr);
+  auto stem_iter = [&](const swalk::Walk& q, bool live) {
+    const int rc = q.r, ppc = q.p;
     half8 bf[2];
-    // window byte 3 + 12 pp + 8 h of tile row 2 r + ky: dword (2 r + ky) * ROWW + 3 pp + 2 h, byte 3 of it (32-bit index arithmetic:
-    // as pointer arithmetic on the __shared__ array the compiler built 64-bit products)
-    const int idx0 = 2 * rc * SB_ROWW + 3 * ppc + 2 * hh;
+    // window byte 3 + 12 pp + 8 h of tile row 2 r + ky: dword (2 r + ky) * ROWW + 3 pp + 2 h, byte 3 of it
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int idx = idx0 + (s == 0 ? ky0 : 1) * SB_ROWW;
-      const uint32_t d0 = in_tile[idx], d1 = in_tile[idx + 1], d2 = in_tile[idx + 2];
+      const uint32_t* src = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(in_tile) + (s == 0 ? q.rd : q.rd + rd1));
+      const uint32_t d0 = src[0], d1 = src[1], d2 = src[2];
       const uint32_t wa = __builtin_amdgcn_alignbyte(d1, d0, 3);   // bo & 3 == 3 always
       const uint32_t wb = __builtin_amdgcn_alignbyte(d2, d1, 3);
       // (the padded K groups of step 1 carry zero weights: whatever finite bytes they read contribute nothing)
@@ -1742,12 +1760,19 @@ __global__ __launch_bounds__(256) void stem_block_kernel(const StemBlockArgs a) 
         m = (sy >= 0 && sy < a.H1 && sx >= 0 && sx < a.W1) ? 0xffffffffu : 0u;
       }
       typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-      *reinterpret_cast<u32x2*>(st_tile + (rc * SB_LW + c) * 16 + c0 * 2) = u32x2{__builtin_bit_cast(uint32_t, q01) & m, __builtin_bit_cast(uint32_t, q23) & m};
+      *reinterpret_cast<u32x2*>(st_tile + q.wr) = u32x2{__builtin_bit_cast(uint32_t, q01) & m, __builtin_bit_cast(uint32_t, q23) & m};
     }
-    pi += 64;
-    pp += 31;
-    r += 1;
-    if (pp >= SB_PAIRS) { pp -= SB_PAIRS; r += 1; }
+  };
+  for (int i = 0; i < PW::FULL; ++i) {
+    stem_iter(w, true);
+    swalk::advance<PW>(w);
+  }
+#pragma unroll
+  for (int i = PW::FULL; i < PW::ITERS; ++i) {
+    const bool live = pos0 + PW::STEP * i < NPAIR;
+    const swalk::Walk dead = swalk::last<PW>(lane_rd, lane_wr);
+    stem_iter(swalk::Walk{live ? w.r : dead.r, live ? w.p : dead.p, live ? w.rd : dead.rd, live ? w.wr : dead.wr}, live);
+    swalk::advance<PW>(w);
   }
   };
   if (sb_interior) stem_loop(std::true_type{});   // (verified bit-identical to the border form on every workgroup)
@@ -1762,7 +1787,10 @@ __global__ __launch_bounds__(256) void stem_block_kernel(const StemBlockArgs a) 
   ConvArgs a2;
   a2.w2 = a.w2; a2.bias2 = a.b2;
   tail_load<half_t, 1, 1>(a2, lane, g, w2f, bias2);
-  a2.out = a.out; a2.out_pitch = a.out_pitch; a2.Cout = a.C2; a2.act = a.act2; a2.res = nullptr; a2.res_pitch = 0;
+  // the lane's output pointer at its pixel of the wave's first tile, once; a tile then adds a wave-uniform pixel count (the scalar
+  // unit's product with the pitch).  32-bit element offsets: launch_block checks the view's span
+  a2.out = reinterpret_cast<half_t*>(a.out) + eoff((n * a.H2 + oy0 + 2 * wave) * a.W2 + ox0 + col, a.out_pitch);
+  a2.out_pitch = a.out_pitch; a2.Cout = a.C2; a2.act = a.act2; a2.res = nullptr; a2.res_pitch = 0;
   int toff[3];
 #pragma unroll
   for (int s = 0; s < 3; ++s) {
@@ -1783,7 +1811,7 @@ __global__ __launch_bounds__(256) void stem_block_kernel(const StemBlockArgs a) 
       acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[s], __builtin_bit_cast(half8, *reinterpret_cast<const u32x4*>(base + toff[s])), acc, 0, 0, 0);
     const int gy = oy0 + oy, gx = ox0 + ox;
     if (gy < a.H2 && gx < a.W2) {
-      const long pix = (n * a.H2 + gy) * a.W2 + gx;
+      const long pix = (i >> 1) * a.W2 + (i & 1) * 16;   // relative to a2.out
       floatx4 v[1] = {acc};
       tail_store<half_t, 1, 1, ACT_SILU>(a2, pix, g, v, bias1, w2f, bias2);
     }
@@ -1808,35 +1836,12 @@ __global__ __launch_bounds__(256) void stem_block16_kernel(const StemBlockArgs a
   typedef SB16<TH_> K;
   __shared__ uint32_t in_tile[K::IR * K::ROWW];
   __shared__ __attribute__((aligned(16))) char st_tile[2 * K::PLANE];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, col = lane & 15;
   const int n = blockIdx.x, ox0 = blockIdx.y * K::TW, oy0 = blockIdx.z * K::TH;
   // ---- 1. uint8 tile (as stem_block_kernel)
-  const int row_words = a.Win * 3 / 4;
-  const int w0 = (12 * ox0 - 9) >> 2;
-  const uint32_t* im = reinterpret_cast<const uint32_t*>(a.img + (long)n * a.Hin * a.Win * 3);
-  {
-    const int c = tid & 127, r0 = tid >> 7;
-    const int wi = w0 + c;
-    const bool colok = c < K::ROWW && wi >= 0 && wi < row_words;
-    const int wic = wi < 0 ? 0 : (wi < row_words ? wi : row_words - 1);
-    constexpr int NR = (K::IR + 1) / 2;
-    uint32_t v[NR];
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int iy = 4 * oy0 - 3 + r0 + 2 * k;
-      const int iyc = iy < 0 ? 0 : (iy < a.Hin ? iy : a.Hin - 1);
-      v[k] = im[(long)iyc * row_words + wic];
-    }
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int r = r0 + 2 * k;
-      const int iy = 4 * oy0 - 3 + r;
-      const uint32_t m = (colok && iy >= 0 && iy < a.Hin) ? 0xffffffffu : 0u;
-      if (c < K::ROWW && r < K::IR) in_tile[r * K::ROWW + c] = v[k] & m;
-    }
-  }
-  const half8 af = __builtin_bit_cast(half8, reinterpret_cast<const u32x4*>(a.afrag)[lane]);   // StemLayer::d_afrag (16-channel form)
+  stage_block_tile<swalk::Geo<TH_>>(a.img, in_tile, n, oy0, ox0, a.Hin, a.Win, tid);
+  const half8 af =__builtin_bit_cast(half8, reinterpret_cast<const u32x4*>(a.afrag)[lane]);   // StemLayer::d_afrag (16-channel form)
   const floatx4 sb4 = *reinterpret_cast<const floatx4*>(a.sbias + 4 * g);
   // stride-2 conv: 5 K steps x 2 channel tiles, the 1x1 tail: 2 tiles x 1 step (ConvLayer's packing for the direct kernel)
   half8 a1[5][2];
@@ -1850,22 +1855,23 @@ __global__ __launch_bounds__(256) void stem_block16_kernel(const StemBlockArgs a
   const half2v k1024 = {(half_t)1024.f, (half_t)1024.f};
   const bool sb_interior = oy0 >= 1 && ox0 >= 1 && 2 * oy0 - 1 + K::SH <= a.H1 && 2 * ox0 - 1 + K::SW <= a.W1;
   // K group g < 3: bytes 0..7 of window row g (three consecutive dwords, byte-aligned); g == 3: byte 8 of the three rows (the
-  // dword two further on in each row, the same byte shift) -- one address form for all lanes: base + k * kstride
-  const int kstride = g < 3 ? 1 : K::ROWW;
-  const int gbase = g < 3 ? g * K::ROWW : 2;
-  auto stem_tile = [&](int pi, int (&d)[3], int& rc, int& cc, int& sh, bool& live) {
-    live = pi < K::NPIX;
-    const int pc = live ? pi : K::NPIX - 1;
-    rc = (pc * 1009) >> 16;              // pc / 65 for pc < 2 * 65 * 17 (1009 / 65536 = 1 / 64.95)
-    cc = pc - rc * K::SW;
-    if (cc >= K::SW) { cc -= K::SW; rc += 1; }
-    const int bo = 3 + 6 * cc;           // first window byte of this pixel inside a staged row
-    sh = bo & 3;
-    const int idx = 2 * rc * K::ROWW + (bo >> 2) + gbase;
+  // dword two further on in each row, the same byte shift) -- one address form for all lanes: base + k * kstride (PW::lane_rd,
+  // PW::kstride4, in bytes).
+  // The walk (stem_walk.h, PixelWalk): per tile a lane keeps the BYTE offset of its pixel's first window byte 3 + 6 cc of input row
+  // 2 rc (dword = offset >> 2, byte shift = offset & 3; the lane's K-group base is folded in) and the st_tile offset of its pixel;
+  // both advance by a constant per iteration with one correction at the row wrap -- no division, multiply or clamp in the loop.
+  // A lane's pixel index can pass NPIX only in the last iteration, which is peeled and keeps the clamp to the tile's last pixel.
+  typedef swalk::PixelWalk<TH_> PW;
+  static_assert(PW::N == K::NPIX && PW::NTILE == K::NTILE && PW::G::ROWW == K::ROWW && PW::G::LW == K::LW && PW::G::IR == K::IR, "stem_walk.h holds this walk");
+  static_assert(PW::G::ST_BYTES == K::PLANE, "stem_walk.h holds this plane");
+  const int lane_rd = PW::lane_rd(g), lane_wr = PW::lane_wr(g), kstride4 = PW::kstride4(g);
+  auto stem_tile = [&](const swalk::Walk& q, int (&d)[3]) {
+    const char* src = reinterpret_cast<const char*>(in_tile) + (q.rd & ~3);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) d[k] = (int)in_tile[idx + k * kstride];
+    for (int k = 0; k < 3; ++k) d[k] = *reinterpret_cast<const int*>(src + k * kstride4);
   };
-  auto stem_finish = [&](const int (&d)[3], int rc, int cc, int sh, bool live, auto interior) {   // interior: std::true_type for tiles wholly inside the stem map
+  auto stem_finish = [&](const int (&d)[3], const swalk::Walk& q, bool live, auto interior) {   // interior: std::true_type for tiles wholly inside the stem map
+    const int rc = q.r, cc = q.p, sh = q.rd & 3;
     uint32_t wa, wb;
     {
       const uint32_t wa0 = __builtin_amdgcn_alignbyte((uint32_t)d[1], (uint32_t)d[0], sh);
@@ -1895,19 +1901,34 @@ __global__ __launch_bounds__(256) void stem_block16_kernel(const StemBlockArgs a
         m = (sy >= 0 && sy < a.H1 && sx >= 0 && sx < a.W1) ? 0xffffffffu : 0u;
       }
       typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-      // channels 4g .. 4g+3: plane g >> 1, bytes 8 (g & 1) of the pixel
-      *reinterpret_cast<u32x2*>(st_tile + (g >> 1) * K::PLANE + (rc * K::LW + cc) * 16 + (g & 1) * 8) =
-          u32x2{__builtin_bit_cast(uint32_t, q01) & m, __builtin_bit_cast(uint32_t, q23) & m};
+      *reinterpret_cast<u32x2*>(st_tile + q.wr) = u32x2{__builtin_bit_cast(uint32_t, q01) & m, __builtin_bit_cast(uint32_t, q23) & m};
     }
   };
   auto stem_loop = [&](auto interior) {
-    for (int t = wave; t < K::NTILE; t += 8) {
-      int dA[3], dB[3], rA, cA, sA, rB, cB, sB;
-      bool lA, lB;
-      stem_tile(t * 16 + col, dA, rA, cA, sA, lA);
-      stem_tile((t + 4) * 16 + col, dB, rB, cB, sB, lB);
-      stem_finish(dA, rA, cA, sA, lA, interior);
-      stem_finish(dB, rB, cB, sB, lB, interior);
+    const int posA = PW::pos0(wave, col, 0), posB = PW::pos0(wave, col, 1);
+    swalk::Walk wA = swalk::start<PW>(posA, lane_rd, lane_wr), wB = swalk::start<PW>(posB, lane_rd, lane_wr);
+    for (int i = 0; i < PW::FULL; ++i) {
+      int dA[3], dB[3];
+      stem_tile(wA, dA);
+      stem_tile(wB, dB);
+      stem_finish(dA, wA, true, interior);
+      stem_finish(dB, wB, true, interior);
+      swalk::advance<PW>(wA);
+      swalk::advance<PW>(wB);
+    }
+#pragma unroll
+    for (int i = PW::FULL; i < PW::ITERS; ++i) {
+      const bool lA = posA + PW::STEP * i < K::NPIX, lB = posB + PW::STEP * i < K::NPIX;
+      const swalk::Walk dead = swalk::last<PW>(lane_rd, lane_wr);
+      const swalk::Walk qA = {lA ? wA.r : dead.r, lA ? wA.p : dead.p, lA ? wA.rd : dead.rd, lA ? wA.wr : dead.wr};
+      const swalk::Walk qB = {lB ? wB.r : dead.r, lB ? wB.p : dead.p, lB ? wB.rd : dead.rd, lB ? wB.wr : dead.wr};
+      int dA[3], dB[3];
+      stem_tile(qA, dA);
+      stem_tile(qB, dB);
+      stem_finish(dA, qA, lA, interior);
+      stem_finish(dB, qB, lB, interior);
+      swalk::advance<PW>(wA);
+      swalk::advance<PW>(wB);
     }
   };
   if (sb_interior) stem_loop(std::true_type{});   // (block-uniform: 80 % of the workgroups; the per-pixel test was 9 of a tile's ~80 instructions: 123 -> 120 us)
@@ -1920,7 +1941,9 @@ __global__ __launch_bounds__(256) void stem_block16_kernel(const StemBlockArgs a
   ConvArgs a2;
   a2.w2 = a.w2; a2.bias2 = a.b2;
   tail_load<half_t, 2, 2>(a2, lane, g, w2f, bias2);
-  a2.out = a.out; a2.out_pitch = a.out_pitch; a2.Cout = a.C2; a2.act = a.act2; a2.res = nullptr; a2.res_pitch = 0;
+  // (the lane's output pointer once, a wave-uniform pixel count per tile: as stem_block_kernel)
+  a2.out = reinterpret_cast<half_t*>(a.out) + eoff((n * a.H2 + oy0 + (K::TH / 4) * wave) * a.W2 + ox0 + col, a.out_pitch);
+  a2.out_pitch = a.out_pitch; a2.Cout = a.C2; a2.act = a.act2; a2.res = nullptr; a2.res_pitch = 0;
   int toff[5];
 #pragma unroll
   for (int s = 0; s < 5; ++s) {
@@ -1945,7 +1968,8 @@ __global__ __launch_bounds__(256) void stem_block16_kernel(const StemBlockArgs a
     }
     const int gy = oy0 + oy, gx = ox0 + ox;
     if (gy < a.H2 && gx < a.W2) {
-      const long pix = (n * a.H2 + gy) * a.W2 + gx;
+      static_assert(K::TH % 4 == 0, "a wave's tiles start on an even tile: whole output rows");
+      const long pix = (i >> 1) * a.W2 + (i & 1) * 16;   // relative to a2.out
       tail_store<half_t, 2, 2, ACT_SILU>(a2, pix, g, v, bias1, w2f, bias2);
     }
   }
@@ -2427,6 +2451,8 @@ void StemLayer::launch_block(const uint8_t* img, int N, int Hin, int Win, const 
   a.out = out.base; a.N = N; a.Hin = Hin; a.Win = Win; a.H1 = (Hin + 1) / 2; a.W1 = (Win + 1) / 2;
   a.H2 = out.H; a.W2 = out.W; a.out_pitch = out.pitch; a.C2 = c1.Cout2; a.act2 = c1.act2;
   LP_CHECK(a.H2 == (a.H1 + 1) / 2 && a.W2 == (a.W1 + 1) / 2 && out.C >= c1.Cout2, LP_ERR_STATE, "stem block: output view mismatch");
+  // the kernels' 32-bit offsets: a row inside one image (staging), lane pointer + tile offset (output)
+  LP_CHECK((double)Hin * Win * 3 < 2147483648.0 && span_ok(N, out), LP_ERR_STATE, "stem block: image or output view beyond 32-bit offsets");
   dim3 grid(N, ceil_div(a.W2, SB_TW), ceil_div(a.H2, SB_TH));
   if (CO == 16) {
     LP_LAUNCH(stem_block16_kernel<8>, grid, dim3(256), 0, st, a);
